@@ -10,6 +10,7 @@ GPUs (weak scaling) by the native sharded prover (zk_shard_*: RCCL all-to-all pe
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--log-n 21] [--log-blowup 3]
     python bench.py --gpus N --plan-only      # the sharded layout and a written-down estimate: no GPU, no timing
+    python bench.py --dump-outputs DIR        # also DIR/proof_data.npy, proof_state.npy, public_last.npy: the last timed proof
 
 `--gpus N` without a launcher starts the N ranks itself (one child process per GPU, before anything
 touches the GPU); under `torch.distributed.run` it reads RANK / LOCAL_RANK / WORLD_SIZE / MASTER_*.
@@ -67,7 +68,15 @@ def parse():
                     help="print zk_shard_plan for N = 2, 4, 8 (or --gpus N) at the weak and strong shapes with the estimated per-rank "
                          "critical path (one-GPU proxies under profiles/), as one JSON document; needs no GPU")
     ap.add_argument("--no-fieldhash-leg", action="store_true", help="N = 1: skip the fieldhash_2e24 leg (configs[4]; ~10 s incl. its oracle check)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (proof bytes, final channel state, public "
+                         "value) as DIR/<name>.npy in float32 / float64, for comparing the outputs of two builds")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (args.plan_only or args.staged_only):
+        ap.error("--dump-outputs needs the timed proofs: not with --plan-only or --staged-only")
+    return args
 
 
 def host_cores():
@@ -143,6 +152,25 @@ def kernel_clock_record(hash_name):
     k = max(rows, key=lambda r: r["grid_threads"])
     return {"clock_ghz": k["clock_ghz"], "valu_instr_per_wave": k["valu_instr_per_wave"], "launch_us_under_pmc": k["duration_us"],
             "stamp": {x: v.get(x) for x in ("commit", "build_hash", "collected")}}
+
+
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, proof):
+    """--dump-outputs: what a caller of the timed path receives from its last step (zk.Proof: the proof bytes, the final
+    channel state, the public value), exactly, as float32 / float64 arrays.  The trace is deterministic, so two builds run
+    with the same arguments can be compared file for file."""
+    import numpy as np
+    arrays = {"proof_data": np.frombuffer(proof.data, dtype=np.uint8).astype(np.float32),
+              "proof_state": np.frombuffer(proof.state, dtype=np.uint8).astype(np.float32),
+              "public_last": np.array([proof.public_last], dtype=np.float64)}       # < 2^32: exact in float64
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_CAP_BYTES, "the proof outgrew the --dump-outputs cap"
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    print(f"[bench] outputs of the last timed step written to {dirname}: " + ", ".join(f"{k}.npy {v.shape}" for k, v in arrays.items()),
+          file=sys.stderr, flush=True)
 
 
 def emit_line(R, result):
@@ -299,6 +327,8 @@ def emit_line(R, result):
                                     f"(the timed proof; oracle {dt_o:.1f} s on {host_cores()[0]} threads)", "equal": bool(ok)}
         out["cpu_baseline"] = {"value": N / dt_o, "unit": "field-elements/s", "cores": host_cores()[0], "kind": "port",
                                "sample": f"oracle full prover with the field hash, domain 2^{log_n + log_b}, {dt_o:.2f} s"}
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, proof)
     sys.stdout.flush()
     os.write(json_fd, (json.dumps(out) + "\n").encode())
     if out.get("parity_checked") is False and (out.get("parity") or {}).get("equal") is False:

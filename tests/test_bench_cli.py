@@ -282,3 +282,43 @@ def test_bench_supervisor_state_machine(script, want_rc, want_rungs, want_genera
     assert out.strip() == ""                                   # scripted workers print no line
     # the run's files are named after the supervisor's PARENT (the launcher, here this test process) and the rendezvous port
     assert [f for f in glob.glob("/tmp/zkbench_*") if f"_{os.getpid()}_0" in f] == []
+
+
+def test_bench_dump_outputs_writes_the_proof_exactly(tmp_path):
+    """--dump-outputs: the proof a caller receives (bytes, final channel state, public value) as float arrays that hold every value
+    exactly; a bad --steps or a run without timed proofs is refused before anything starts."""
+    import importlib.util
+    import types
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("zk_bench_module", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    proof = types.SimpleNamespace(data=bytes(range(256)) * 3 + b"\x07", state=bytes(range(255, 223, -1)), public_last=3221225472)
+    bench.dump_outputs(str(tmp_path / "out"), proof)
+    got = {n: np.load(str(tmp_path / "out" / (n + ".npy"))) for n in ("proof_data", "proof_state", "public_last")}
+    assert got["proof_data"].dtype == np.float32 and bytes(got["proof_data"].astype(np.uint8)) == proof.data
+    assert got["proof_state"].dtype == np.float32 and bytes(got["proof_state"].astype(np.uint8)) == proof.state
+    assert got["public_last"].dtype == np.float64 and int(got["public_last"][0]) == proof.public_last
+    for argv in (["--steps", "0"], ["--plan-only", "--dump-outputs", str(tmp_path / "x")]):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + argv, capture_output=True, text=True, timeout=60)
+        assert out.returncode == 2 and out.stdout == "", out.stderr[-2000:]
+    assert not (tmp_path / "x").exists()
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_are_the_last_timed_proof(tmp_path, orc):
+    """`bench.py --steps 3 --dump-outputs DIR`: the line holds the steps asked for and ms_per_step, and DIR holds the timed
+    proof of the deterministic trace, byte for byte the oracle's proof of the same trace."""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE")}
+    d = tmp_path / "dump"
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--log-n", "12", "--no-secondary",
+                          "--no-cpu-baseline", "--soak-seconds", "0", "--in-flight", "1", "--dump-outputs", str(d)],
+                         capture_output=True, text=True, timeout=280, env=env)
+    assert out.returncode == 0, out.stderr[-3000:]
+    rec = json.loads([l for l in out.stdout.splitlines() if l.strip()][-1])
+    assert rec["steps"] == 3 and rec["ms_per_step"] > 0
+    want = orc.prove(12, 3, want_vectors=False)
+    assert bytes(np.load(str(d / "proof_data.npy")).astype(np.uint8)) == want.proof
+    assert bytes(np.load(str(d / "proof_state.npy")).astype(np.uint8)) == want.state
+    assert int(np.load(str(d / "public_last.npy"))[0]) == want.public_last
