@@ -89,8 +89,12 @@ struct PowRaw { uint32_t hi, lo; };
 __device__ __forceinline__ PowRaw pow_fetch(const PowTable& t, uint32_t e) { return PowRaw{t.hi[e >> t.lo_bits], t.lo[e & ((1u << t.lo_bits) - 1u)]}; }
 __device__ __forceinline__ uint32_t pow_of(const PowRaw& r) { return mont_mul(r.hi, r.lo); }
 
-// Raw buffer over [base, base + 4 GiB): word at base + lane_off + row_off (bytes; lane_off in a VGPR, row_off uniform).
-// An arrays of this library has at most 2^30 words, so every offset fits 32 bits; out-of-range reads return 0.
+// Raw buffer over [base, base + 4 GiB - 1): word at base + lane_off + row_off (bytes; lane_off in a VGPR, row_off uniform).
+// The record count 2^32 - 1 is the largest there is, and a dword at byte offset 2^32 - 4 ends past it: the range check
+// treats it as out of range, so a load returns 0 and a store is dropped (on gfx950 the last coefficient of a 2^30-word array, read through a
+// resource based at the array's start, came back 0: tests/test_gpu_transforms.py, test_lde_30_0_end_of_buffer).  So every
+// resource is based near the words it reaches (the workgroup's base, its tile, its coefficient blocks), and offsets
+// from it stay well below 2^32 - 4.
 using Rsrc = __amdgpu_buffer_rsrc_t;
 __device__ __forceinline__ Rsrc make_rsrc(const void* base) {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)0xFFFFFFFFu, 0x00020000);
@@ -225,8 +229,9 @@ __global__ __launch_bounds__(kThreads) void ntt_pass_fast_kernel(NttPassArgs p) 
             for (int ta = 0; ta < RA; ++ta) x[ta] = cb[ta * RB];
         } else if (LDE) {
             const uint32_t a = (col0 + c) >> logS;                 // coefficient block; B columns share it
-            const Rsrc cb = make_rsrc(p.src);
-            const uint32_t off = (a << (LOGR + 2)) | (tb << 2);     // n <= 2^30 words: the byte offset fits 32 bits
+            const uint32_t a0 = col0 >> logS;                      // the tile's first block (col0 is a multiple of C > S)
+            const Rsrc cb = make_rsrc(p.src + ((size_t)a0 << LOGR));
+            const uint32_t off = ((a - a0) << (LOGR + 2)) | (tb << 2);
 #pragma unroll
             for (int ta = 0; ta < RA; ++ta) x[ta] = ld_b(cb, off, (uint32_t)(ta * RB * 4));
             if (PREP == 1) {
