@@ -272,7 +272,7 @@ int zk_batch_public_last(const zk_batch *b, uint32_t *out);
 int zk_batch_prove(zk_batch *b, uint8_t *proofs_out, size_t stride, uint8_t *states_out);
 
 /* ---- proof: proof.rs ------------------------------------------------------- */
-/* Proof::verify (proof.rs:15-149), CPU only, generalised from the literals
+/* Proof::verify (proof.rs:15-149) on the CPU (many proofs at once on the GPU: zk_verifier_run below), generalised from the literals
  * (1024, 8192, 10, 2338775057) to (log_n, log_blowup, public_last). */
 int zk_verify(const uint8_t *proof, size_t len, uint32_t log_n, uint32_t log_blowup,
               uint32_t public_last);
@@ -296,6 +296,27 @@ int zk_compute_root_from_path(uint32_t element, size_t index, const uint8_t *pat
 
 int zk_compute_root_from_path_ex(uint32_t element, size_t index, const uint8_t *path, size_t path_len,
                                  uint8_t out[32], int hash_kind);
+
+/* ---- batched verification on the GPU (csrc/verify.hip) ---------------------------------------------------------------
+ * The check number the CPU verifier stops at: 0 = accepted; otherwise the number zk_verify_queries names in its error
+ * (-(1000+k) / -1999 transcript replay when state != NULL, then verify_proof's -1 .. -8, -(100+k), -(200+k), -(300+k), -(400+k)).
+ * Returns ZK_OK if accepted, ZK_ERR_VERIFY if rejected (check_out set either way), ZK_ERR_INVALID on bad arguments. */
+int zk_verify_check(const uint8_t *proof, size_t len, const uint8_t *state, uint32_t log_n, uint32_t log_blowup,
+                    uint32_t public_last, int hash_kind, uint32_t n_queries, int32_t *check_out);
+
+/* A verifier for many proofs of one size (log_n, log_blowup: the sizes zk_verify_queries accepts).  It owns its streams and
+ * device buffers (grown on demand) and a pinned staging buffer.  One verifier is used from one host thread at a time. */
+typedef struct zk_verifier zk_verifier;
+int zk_verifier_create(int device, uint32_t log_n, uint32_t log_blowup, zk_verifier **out);
+int zk_verifier_destroy(zk_verifier *v);
+int zk_verifier_set_queries(zk_verifier *v, uint32_t n_queries);   /* 1..64, as zk_verify_queries */
+int zk_verifier_set_hash(zk_verifier *v, int hash_kind);
+/* count proofs at proofs + i*stride, each exactly zk_proof_data_len_queries(log_n, log_blowup, q) bytes (stride >= that, any
+ * alignment); states: count*32 bytes, or NULL = not strict; public_last[count].  checks_out[i] = what zk_verify_check returns
+ * in check_out for proof i, for EVERY input.  Returns ZK_OK if all were accepted, ZK_ERR_VERIFY if any was rejected
+ * (zk_last_error names the first rejected index and its check), other errors as usual.  count = 0 is a no-op. */
+int zk_verifier_run(zk_verifier *v, const uint8_t *proofs, size_t stride, size_t count, const uint8_t *states,
+                    const uint32_t *public_last, int32_t *checks_out);
 
 /* ---- Channel (channel.rs:6-37), host only ------------------------------------ */
 int zk_channel_new(zk_channel **out);                                        /* channel.rs:12 */

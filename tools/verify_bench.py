@@ -1,0 +1,156 @@
+"""Batched GPU verification against the CPU verifier: one JSON line.
+
+For each shape: the wall time of zk_verifier_run (Verifier.verify_raw: warm-up, then --steps timed calls, each ending in the
+call's own synchronisation), and the CPU's time for the same proofs with zk_verify_queries on 1 thread and on a 16-thread
+pool (ctypes releases the GIL).  --profile adds per-kernel times from a separate `rocprofv3 --kernel-trace --stats` run per
+shape (this script again with --inner).  Not part of bench.py: it measures this one feature.
+
+    python tools/verify_bench.py [--steps 20] [--warmup 3] [--profile] [--only NAME,...]
+"""
+import argparse
+import concurrent.futures
+import csv
+import glob
+import json
+import os
+import re
+import shutil
+import subprocess
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+
+import zkstark_amd as zk  # noqa: E402
+from zkstark_amd import _lib  # noqa: E402
+
+# name: (log_n, log_b, queries, hash, count, strict); proofs come from the batch prover, tiled when the count exceeds what one
+# batch of that size proves cheaply (the verifier does not care that two proofs are equal)
+SHAPES = {
+    "ref_strict_1024": (10, 3, 1, "sha256", 1024, True),
+    "ref_plain_1024": (10, 3, 1, "sha256", 1024, False),
+    "2e20_strict_1024": (17, 3, 1, "sha256", 1024, True),
+    "2e24_q1_strict_16": (21, 3, 1, "sha256", 16, True),
+    "2e24_q16_strict_16": (21, 3, 16, "sha256", 16, True),
+    "ref_field_strict_1024": (10, 3, 1, "field", 1024, True),
+    "2e24_q1_strict_1": (21, 3, 1, "sha256", 1, True),
+    "2e24_q1_strict_8": (21, 3, 1, "sha256", 8, True),
+    "2e24_q1_strict_64": (21, 3, 1, "sha256", 64, True),
+}
+PROFILED = ["ref_strict_1024", "ref_plain_1024", "2e20_strict_1024", "2e24_q1_strict_16", "2e24_q16_strict_16", "ref_field_strict_1024"]
+_cache = {}
+
+
+def proofs_for(log_n, log_b, q, hash, count):
+    """(data [count, len] uint8, states [count, 32], public_last [count]) of valid proofs."""
+    key = (log_n, log_b, q, hash)
+    if key not in _cache:
+        log_batch = 10 if log_n <= 10 else (6 if log_n <= 17 else 1)
+        with zk.BatchContext(log_n, log_b, log_batch, hash=hash, queries=q) as bc:
+            bc.gen_fibsq([1] * bc.batch, [3141592 + p for p in range(bc.batch)])
+            data, states = bc.prove_raw()
+            _cache[key] = (data, states, bc.public_last())
+    data, states, last = _cache[key]
+    idx = np.arange(count) % len(data)
+    return np.ascontiguousarray(data[idx]), np.ascontiguousarray(states[idx]), np.ascontiguousarray(last[idx])
+
+
+def gpu_times(shape, steps, warmup):
+    log_n, log_b, q, hash, count, strict = shape
+    data, states, last = proofs_for(log_n, log_b, q, hash, count)
+    with zk.Verifier(log_n, log_b, hash=hash, queries=q) as v:
+        for _ in range(warmup):
+            assert (v.verify_raw(data, last, states if strict else None) == 0).all()
+        ts = []
+        for _ in range(steps):
+            t0 = time.perf_counter()
+            v.verify_raw(data, last, states if strict else None)
+            ts.append((time.perf_counter() - t0) * 1e3)
+    return ts
+
+
+def cpu_ms(shape, threads):
+    log_n, log_b, q, hash, count, strict = shape
+    data, states, last = proofs_for(log_n, log_b, q, hash, count)
+    lib = _lib.load()
+    hk = zk.host.HASHES[hash]
+    plen = data.shape[1]
+    rows = [(data[i].ctypes.data, states[i].ctypes.data if strict else None, int(last[i])) for i in range(count)]
+
+    def one(r):
+        return lib.zk_verify_queries(r[0], plen, r[1], log_n, log_b, r[2], hk, q)
+
+    if threads == 1:
+        one(rows[0])
+        t0 = time.perf_counter()
+        rcs = [one(r) for r in rows]
+    else:
+        with concurrent.futures.ThreadPoolExecutor(threads) as ex:
+            list(ex.map(one, rows[:threads]))
+            t0 = time.perf_counter()
+            rcs = list(ex.map(one, rows, chunksize=max(1, count // (4 * threads))))
+    ms = (time.perf_counter() - t0) * 1e3
+    assert all(rc == 0 for rc in rcs)
+    return ms
+
+
+def profile(name, steps):
+    """Per-kernel totals (ms per zk_verifier_run call) from rocprofv3 --kernel-trace --stats over this script with --inner."""
+    rp = shutil.which("rocprofv3") or "/opt/rocm/bin/rocprofv3"
+    out = tempfile.mkdtemp(prefix="verify_bench_")
+    cmd = [rp, "--kernel-trace", "--stats", "--output-format", "csv", "-d", out, "-o", "vb", "--", sys.executable, os.path.abspath(__file__), "--inner", name,
+           "--steps", str(steps)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    if r.returncode != 0:
+        return {"error": f"rocprofv3 exit {r.returncode}: {r.stderr[-300:]}"}
+    stats = {}
+    for path in glob.glob(os.path.join(out, "**", "*kernel_stats.csv"), recursive=True):
+        with open(path) as f:
+            for row in csv.DictReader(f):
+                m = re.search(r"(verify_\w+_kernel(?:<\d+>)?)", row.get("Name", ""))
+                if m:                                 # --inner makes one warm-up call and `steps` timed ones
+                    stats[m.group(1)] = round(stats.get(m.group(1), 0.0) + float(row["TotalDurationNs"]) / 1e6 / (steps + 1), 4)
+    shutil.rmtree(out, ignore_errors=True)
+    return stats
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--profile", action="store_true")
+    ap.add_argument("--only", default="")
+    ap.add_argument("--inner", default="")
+    a = ap.parse_args()
+    if a.inner:                                       # under rocprofv3: the timed GPU calls of one shape only
+        gpu_times(SHAPES[a.inner], a.steps, 1)
+        return
+    names = [n for n in SHAPES if not a.only or n in a.only.split(",")]
+    res = {}
+    for name in names:
+        shape = SHAPES[name]
+        ts = sorted(gpu_times(shape, a.steps, a.warmup))
+        c1 = cpu_ms(shape, 1)
+        c16 = cpu_ms(shape, 16)
+        res[name] = {"log_n": shape[0], "log_blowup": shape[1], "queries": shape[2], "hash": shape[3], "count": shape[4],
+                     "strict": shape[5], "proof_bytes": int(_lib.load().zk_proof_data_len_queries(shape[0], shape[1], shape[2])),
+                     "gpu_ms_median": round(ts[len(ts) // 2], 4), "gpu_ms_min": round(ts[0], 4),
+                     "cpu_1t_ms": round(c1, 3), "cpu_16t_ms": round(c16, 3),
+                     "speedup_vs_16t": round(c16 / ts[len(ts) // 2], 2)}
+        print(f"# {name}: {res[name]}", file=sys.stderr, flush=True)
+    if a.profile:
+        for name in names:
+            if name in PROFILED:
+                res[name]["kernels_ms_per_call"] = profile(name, 5)
+    cross = {n: res[n] for n in ("2e24_q1_strict_1", "2e24_q1_strict_8", "2e24_q1_strict_16", "2e24_q1_strict_64") if n in res}
+    line = {"tool": "verify_bench", "build_hash": _lib.build_hash(), "steps": a.steps, "warmup": a.warmup, "shapes": res,
+            "crossover_2e24_strict": {n: {"count": r["count"], "gpu_ms": r["gpu_ms_median"], "cpu_16t_ms": r["cpu_16t_ms"]} for n, r in cross.items()}}
+    print(json.dumps(line), flush=True)
+
+
+if __name__ == "__main__":
+    main()

@@ -152,6 +152,12 @@ SYMBOLS = {
     "zk_verify": (_int, [_vp, _sz, _u32, _u32, _u32]),
     "zk_verify_ex": (_int, [_vp, _sz, _u32, _u32, _u32, _int]),
     "zk_compute_root_from_path_ex": (_int, [_u32, _sz, _vp, _sz, _vp, _int]),
+    "zk_verify_check": (_int, [_vp, _sz, _vp, _u32, _u32, _u32, _int, _u32, C.POINTER(C.c_int32)]),
+    "zk_verifier_create": (_int, [_int, _u32, _u32, C.POINTER(_vp)]),
+    "zk_verifier_destroy": (_int, [_vp]),
+    "zk_verifier_set_queries": (_int, [_vp, _u32]),
+    "zk_verifier_set_hash": (_int, [_vp, _int]),
+    "zk_verifier_run": (_int, [_vp, _vp, _sz, _sz, _vp, _vp, _vp]),
     "zk_merkle_build_host_ex": (_int, [_int, _vp, _sz, _vp, _int]),
     "zk_dev_merkle_build_ex": (_int, [_vp, _u32, _vp, _vp, _int]),
     "zk_dev_merkle_build_interleaved": (_int, [_vp, _u32, _u32, _vp, _vp, _int]),

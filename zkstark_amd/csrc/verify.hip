@@ -1,0 +1,483 @@
+// verify.hip -- batched proof verification on the device (zk_verifier_*) and the single-proof check number (zk_verify_check).
+//
+// The result of every proof is the number the CPU verifier stops at (transcript.hpp: verify_transcript, then verify_proof),
+// for every input.  The device gets there without a per-proof parser:
+//   * once the length is fixed, every field of a proof sits at a fixed offset if every u64 path count has its expected
+//     value (L for the four f / cp paths, L - k for the two paths of layer k).  verify_algebra_kernel checks the counts;
+//     a proof whose counts differ is "malformed" and the host runs verify_proof on it (only garbage takes that path).  On
+//     the fixed layout the checks -1, -3, -(200 + k) and -8 cannot fail;
+//   * every other check runs in parallel and posts an order key (query * (5 + 3R) + position, the order verify_proof
+//     visits them in); the smallest key per proof is the first failure (atomicMin);
+//   * strict mode: a transcript failure wins (verify_transcript runs first on the CPU), so it has its own result.
+// The raw-value rules of verify_proof are kept: values are reduced % P before arithmetic, but fv[3] is compared unreduced
+// with cp0, and the FRI expectation (lx[k + 1] or the free term) unreduced with a reduced calc.  Leaf hashes take the raw word.
+#include <cstdio>
+#include <cstring>
+#include <mutex>
+#include <new>
+#include <vector>
+
+#include "internal.hpp"
+#include "fieldhash_f64.hpp"
+#include "sha256.hpp"
+#include "transcript.hpp"
+
+using namespace zk;
+using namespace zk::impl;
+
+namespace zk {
+namespace {
+
+// The field hash's round constants for this translation unit (the build links without -fgpu-rdc, so kernels.hip's copy is
+// not visible here); filled once per device by ensure_verify_consts.
+__constant__ FieldHashConsts64 g_vfh_consts64;
+
+constexpr int32_t kNoFailure = 0x7f7f7f7f;   // the memset pattern of the per-proof key: above every order key
+constexpr uint32_t kVerifyThreads = 64;      // one wave per workgroup: the proofs of a batch spread over as many SIMDs as possible
+
+// Where the fields of a proof sit (in 32-bit words; every field of the wire format is 4-byte aligned and proof_data_len is a
+// multiple of 4), for the fixed layout.
+struct VerifyArgs {
+    const uint32_t* proofs;     // [count][words]
+    const uint32_t* pub;        // [count] public_last (raw)
+    const uint32_t* states;     // [count][8] Proof.state bytes as loaded words, or null
+    int32_t* best;              // [count] smallest order key of a failed check (kNoFailure: none)
+    uint32_t* malformed;        // [count] 1: a path count differs from the fixed layout
+    int32_t* tcode;             // [count] transcript result: 0, -(1000 + k), -1999
+    uint32_t count, words, q, R, L, B, N;
+    uint32_t log_n, h, gm1, gm2, gm3, inv2;
+    uint32_t qbase;             // first word of query 0's openings
+    uint32_t per_q;             // words of one query's openings
+};
+
+__device__ __forceinline__ uint32_t be_word(const uint32_t* p) { return __builtin_bswap32(*p); }
+
+// canonical residues in, canonical out (both operands < P)
+__device__ __forceinline__ uint32_t dmul(uint32_t a, uint32_t b) { return mont_mul(mont_mul(a, b), R2); }
+__device__ __forceinline__ uint32_t dpow(uint32_t a, uint32_t e) {
+    uint32_t r = 1, b = a;
+#pragma unroll 1
+    for (int i = 0; i < 32; ++i) {
+        const uint32_t t = dmul(r, b);
+        r = (e & 1u) ? t : r;
+        b = dmul(b, b);
+        e >>= 1;
+    }
+    return r;
+}
+__device__ __forceinline__ uint32_t dinv(uint32_t a) { return dpow(a, P - 2); }   // invmod: 0 -> 0, as on the host
+
+__device__ __forceinline__ uint32_t root_word(const VerifyArgs& a, uint32_t k) { return k == 0 ? 11u : 20u + 9u * (k - 1u); }
+__device__ __forceinline__ uint32_t layer_word(const VerifyArgs& a, uint32_t qk, uint32_t k) {
+    return a.qbase + qk * a.per_q + 4u * (3u + 8u * a.L) + 6u * k + 16u * (k * a.L - k * (k - 1u) / 2u);
+}
+__device__ __forceinline__ uint32_t query_tp(const VerifyArgs& a, const uint32_t* pr, uint32_t qk) {
+    return pr[20u + 9u * a.R + qk] % (a.N - 2u * a.B);                       // tp = test_raw % (N - 2B)
+}
+
+// (1) layout + algebra: one lane per (proof, query).  Path counts, the cp0 relation (-2) and the R FRI relations (-(100 + k)).
+__global__ void __launch_bounds__(kVerifyThreads) verify_algebra_kernel(VerifyArgs a) {
+    const uint64_t lane = (uint64_t)blockIdx.x * kVerifyThreads + threadIdx.x;
+    if (lane >= (uint64_t)a.count * a.q) return;
+    const uint32_t p = (uint32_t)(lane / a.q), qk = (uint32_t)(lane % a.q);
+    const uint32_t* pr = a.proofs + (size_t)p * a.words;
+    const uint32_t keys = 5u + 3u * a.R;
+    const uint32_t fq = a.qbase + qk * a.per_q;
+    bool ok = true;
+    for (uint32_t j = 0; j < 4; ++j) {
+        const uint32_t* c = pr + fq + j * (3u + 8u * a.L) + 1u;
+        ok = ok && c[0] == a.L && c[1] == 0u;
+    }
+    for (uint32_t k = 0; k < a.R; ++k) {
+        const uint32_t* c = pr + layer_word(a, qk, k) + 2u;
+        const uint32_t len = a.L - k;
+        ok = ok && c[0] == len && c[1] == 0u && c[2u + 8u * len] == len && c[3u + 8u * len] == 0u;
+    }
+    if (!ok) { a.malformed[p] = 1u; return; }
+
+    const uint32_t tp = query_tp(a, pr, qk);
+    const uint32_t x = dmul(GEN_W, dpow(a.h, tp));
+    int32_t key = kNoFailure;
+    {   // proof.rs:63-77
+        const uint32_t fb = 3u + 8u * a.L;
+        const uint32_t f_x = pr[fq] % P, f_gx = pr[fq + fb] % P, f_ggx = pr[fq + 2u * fb] % P, cp_raw = pr[fq + 3u * fb];
+        const uint32_t p0 = dmul(sub(f_x, 1u), dinv(sub(x, 1u)));
+        const uint32_t p1 = dmul(sub(f_x, a.pub[p] % P), dinv(sub(x, a.gm2)));
+        const uint32_t num = sub(sub(f_ggx, dmul(f_gx, f_gx)), dmul(f_x, f_x));
+        uint32_t xn = x;
+        for (uint32_t i = 0; i < a.log_n; ++i) xn = dmul(xn, xn);
+        const uint32_t den = dmul(sub(xn, 1u), dinv(dmul(dmul(sub(x, a.gm3), sub(x, a.gm2)), sub(x, a.gm1))));
+        const uint32_t p2 = dmul(num, dinv(den));
+        const uint32_t cp0 = add(add(dmul(pr[8] % P, p0), dmul(pr[9] % P, p1)), dmul(pr[10] % P, p2));
+        if (cp0 != cp_raw) key = (int32_t)(qk * keys);
+    }
+    // proof.rs:101-126, the relations in k order: the first failing one is the smallest key of this lane
+    uint32_t xk = x;
+    for (uint32_t k = 0; k < a.R && key == kNoFailure; ++k) {
+        const uint32_t lw = layer_word(a, qk, k);
+        const uint32_t lx = pr[lw] % P, lnx = pr[lw + 1u] % P;
+        const uint32_t gx = dmul(add(lx, lnx), a.inv2);
+        const uint32_t hx = dmul(sub(lx, lnx), dinv(dmul(xk, 2u)));
+        const uint32_t calc = add(gx, dmul(pr[19u + 9u * k] % P, hx));   // betas[k + 1]
+        const uint32_t expect = k + 1u < a.R ? pr[layer_word(a, qk, k + 1u)] : pr[19u + 9u * a.R];
+        if (calc != expect) key = (int32_t)(qk * keys + 5u + k);
+        xk = dmul(xk, xk);
+    }
+    if (key != kNoFailure) atomicMin(&a.best[p], key);
+}
+
+template <int HASH>
+__device__ __forceinline__ Digest vleaf(uint32_t v) {
+    if constexpr (HASH == 0) return sha256_leaf(v);
+    else return fieldhash_leaf64(v, g_vfh_consts64);
+}
+template <int HASH>
+__device__ __forceinline__ Digest vinner(const Digest& l, const Digest& r) {
+    if constexpr (HASH == 0) return sha256_inner(l, r);
+    else return fieldhash_inner64(l, r, g_vfh_consts64);
+}
+
+// (2) paths: one lane per (proof, query, path slot).  blockIdx.y = query * (4 + 2R) + slot and the proof on the lane, so every
+// lane of a wave walks a path of the same length; left / right is a select per level (merkle.rs:82-110).
+template <int HASH>
+__global__ void __launch_bounds__(kVerifyThreads) verify_paths_kernel(VerifyArgs a) {
+    const uint32_t p = blockIdx.x * kVerifyThreads + threadIdx.x;
+    if (p >= a.count) return;
+    const uint32_t slots = 4u + 2u * a.R;
+    const uint32_t qk = blockIdx.y / slots, slot = blockIdx.y % slots;
+    const uint32_t* pr = a.proofs + (size_t)p * a.words;
+    const uint32_t tp = query_tp(a, pr, qk);
+    uint32_t val_w, path_w, plen, idx, rootw, pos;
+    if (slot < 4u) {                                      // f(x), f(gx), f(g^2 x) against the f root, cp(x) against the cp root
+        val_w = a.qbase + qk * a.per_q + slot * (3u + 8u * a.L);
+        path_w = val_w + 3u;
+        plen = a.L;
+        idx = tp + (slot < 3u ? slot * a.B : 0u);
+        rootw = slot < 3u ? 0u : 11u;
+        pos = 1u + slot;
+    } else {                                              // layer k at x and at -x
+        const uint32_t k = (slot - 4u) / 2u, which = (slot - 4u) & 1u;
+        const uint32_t lw = layer_word(a, qk, k), size = a.N >> k;
+        plen = a.L - k;
+        val_w = lw + which;
+        path_w = lw + 4u + which * (2u + 8u * plen);
+        idx = which ? (tp + size / 2u) % size : tp % size;
+        rootw = root_word(a, k);
+        pos = 5u + a.R + 2u * k + which;
+    }
+    Digest cur = vleaf<HASH>(pr[val_w]);
+    uint32_t node = idx + (1u << plen) - 1u;              // heap index, < 2^31
+    for (uint32_t lvl = 0; lvl < plen; ++lvl) {
+        Digest sib;
+        const uint32_t* s = pr + path_w + 8u * lvl;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) sib.w[i] = be_word(s + i);
+        const bool right = (node & 1u) == 0u;             // an even heap index is a right child
+        Digest l, r;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) { l.w[i] = right ? sib.w[i] : cur.w[i]; r.w[i] = right ? cur.w[i] : sib.w[i]; }
+        cur = vinner<HASH>(l, r);
+        node = (node - (right ? 2u : 1u)) >> 1;
+    }
+    bool same = true;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) same = same && cur.w[i] == be_word(pr + rootw + i);
+    if (!same) atomicMin(&a.best[p], (int32_t)(qk * (5u + 3u * a.R) + pos));
+}
+
+// SHA-256(state || data[0 .. nw)) into state (channel.rs:19-26), streamed over sha256_compress.  nw is the same for every lane,
+// so the lanes of a wave stay in lockstep; data words are read little-endian and swapped to message order.
+__device__ __forceinline__ void commit_words(uint32_t (&st)[8], const uint32_t* data, uint32_t nw) {
+    const uint32_t M = 8u + nw;                           // message words
+    const uint32_t blocks = (4u * M + 9u + 63u) / 64u;
+    uint32_t hs[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) hs[i] = SHA_IV[i];
+    for (uint32_t b = 0; b < blocks; ++b) {
+        uint32_t w[16];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const uint32_t g = 16u * b + (uint32_t)i;
+            uint32_t v = 0u;
+            if (i < 8 && b == 0u) v = st[i & 7];
+            else if (g - 8u < nw) v = be_word(data + (g - 8u));
+            else if (g == M) v = 0x80000000u;
+            else if (i == 15 && b + 1u == blocks) v = 32u * M;   // bit length (the high word, i == 14, is 0)
+            w[i] = v;
+        }
+        sha256_compress(hs, w);
+    }
+#pragma unroll
+    for (int i = 0; i < 8; ++i) st[i] = hs[i];
+}
+
+// (3) transcript (strict only): one lane per proof, the commits of verify_transcript in its order.  The order is a schedule of
+// steps the same for every lane (a challenge, or a commit of nw words), walked by one loop with one commit site: the
+// compression is inlined once and the state stays in registers.
+__global__ void __launch_bounds__(kVerifyThreads) verify_transcript_kernel(VerifyArgs a) {
+    const uint32_t p = blockIdx.x * kVerifyThreads + threadIdx.x;
+    if (p >= a.count) return;
+    const uint32_t* pr = a.proofs + (size_t)p * a.words;
+    uint32_t st[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) st[i] = 0u;
+    const uint32_t R = a.R, L = a.L, q = a.q;
+    // steps: f root | 3 alphas | cp root | R x (beta, layer root) | free term | q query raws | q x (4 f paths, R layer pairs)
+    const uint32_t head = 6u + 2u * R + q;
+    const uint32_t steps = head + q * (4u + R);
+    uint32_t cur = 0, k = 0;
+    int32_t code = 0;
+    for (uint32_t s = 0; s < steps; ++s) {
+        bool chal;
+        uint32_t nw;
+        if (s < head) {
+            chal = (s >= 1u && s <= 3u) || (s >= 5u && s < 5u + 2u * R && ((s - 5u) & 1u) == 0u) || s >= 6u + 2u * R;
+            nw = chal ? 1u : (s == 5u + 2u * R ? 1u : 8u);
+        } else {
+            const uint32_t t = (s - head) % (4u + R);
+            chal = false;
+            nw = t < 4u ? 3u + 8u * L : 6u + 16u * (L - (t - 4u));
+        }
+        if (chal) {                                       // state word 0 (big-endian bytes 0..3) against the little-endian u32 here
+            ++k;
+            if (st[0] != pr[cur]) { code = -(int32_t)(1000u + k); break; }
+        }
+        commit_words(st, pr + cur, nw);
+        cur += nw;
+    }
+    if (code == 0) {
+        bool same = true;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) same = same && st[i] == be_word(a.states + (size_t)p * 8u + i);
+        if (!same) code = -1999;
+    }
+    a.tcode[p] = code;
+}
+
+std::mutex g_consts_mu;
+bool g_consts_done[64] = {false};
+
+hipError_t ensure_verify_consts() {
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    std::lock_guard<std::mutex> lk(g_consts_mu);
+    if (dev < 0 || dev >= 64 || g_consts_done[dev]) return hipSuccess;
+    FieldHashConsts c;
+    fieldhash_make_consts(c);
+    static FieldHashConsts64 c64;
+    fieldhash_make_consts64(c, c64);
+    e = hipMemcpyToSymbol(HIP_SYMBOL(g_vfh_consts64), &c64, sizeof c64);
+    if (e == hipSuccess) g_consts_done[dev] = true;
+    return e;
+}
+
+// An order key -> the check number verify_proof returns for it.
+int32_t key_to_check(int32_t key, uint32_t R) {
+    const uint32_t pos = (uint32_t)key % (5u + 3u * R);
+    if (pos == 0) return -2;
+    if (pos < 5) return -(int32_t)(3u + pos);             // -4 .. -7
+    if (pos < 5 + R) return -(int32_t)(100u + (pos - 5u));
+    const uint32_t j = pos - 5u - R;
+    return -(int32_t)((j & 1u ? 400u : 300u) + j / 2u);
+}
+
+}  // namespace
+}  // namespace zk
+
+struct zk_verifier {
+    int device = 0;
+    uint32_t log_n = 0, log_b = 0, queries = 1;
+    int hash = ZK_HASH_SHA256;
+    hipStream_t stream = nullptr, tstream = nullptr;   // paths + algebra; transcript (runs beside them)
+    hipEvent_t ev_in = nullptr, ev_t = nullptr;
+    uint8_t* d_buf = nullptr;                          // proofs, public_last, states, then the three per-proof results
+    uint8_t* h_in = nullptr;                           // pinned staging of the inputs
+    int32_t* h_out = nullptr;                          // pinned: best, malformed, tcode
+    size_t cap = 0, cap_in = 0, cap_out = 0;           // proofs the buffers hold
+};
+
+namespace {
+
+size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+int verifier_reserve(zk_verifier* v, size_t chunk, size_t len) {
+    const size_t in_bytes = chunk * (len + 4 + 32);
+    const size_t dev_bytes = align256(chunk * len) + align256(chunk * 4) + align256(chunk * 32) + 3 * align256(chunk * 4);
+    if (chunk <= v->cap && in_bytes <= v->cap_in && dev_bytes <= v->cap_out) return ZK_OK;
+    HIPCHK(hipStreamSynchronize(v->stream));
+    HIPCHK(hipStreamSynchronize(v->tstream));
+    if (v->d_buf) (void)hipFree(v->d_buf);
+    if (v->h_in) (void)hipHostFree(v->h_in);
+    if (v->h_out) (void)hipHostFree(v->h_out);
+    v->d_buf = nullptr; v->h_in = nullptr; v->h_out = nullptr; v->cap = v->cap_in = v->cap_out = 0;
+    if (hipMalloc((void**)&v->d_buf, dev_bytes) != hipSuccess) return fail(ZK_ERR_NOMEM, "zk_verifier_run: hipMalloc(%zu) failed", dev_bytes);
+    if (hipHostMalloc((void**)&v->h_in, in_bytes) != hipSuccess) return fail(ZK_ERR_NOMEM, "zk_verifier_run: hipHostMalloc(%zu) failed", in_bytes);
+    if (hipHostMalloc((void**)&v->h_out, chunk * 12) != hipSuccess) return fail(ZK_ERR_NOMEM, "zk_verifier_run: hipHostMalloc(%zu) failed", chunk * 12);
+    v->cap = chunk; v->cap_in = in_bytes; v->cap_out = dev_bytes;
+    return ZK_OK;
+}
+
+// One chunk of proofs: stage, copy in, three kernels, copy the per-proof results out, decide each proof.
+int verifier_chunk(zk_verifier* v, const uint8_t* proofs, size_t stride, size_t count, const uint8_t* states, const uint32_t* public_last,
+                   int32_t* checks_out, size_t len) {
+    const uint32_t log_n = v->log_n, log_b = v->log_b, q = v->queries, R = log_n, L = log_n + log_b;
+    // inputs: [count][len] proofs, [count] public_last, [count][32] states, packed into the pinned staging buffer
+    uint8_t* hp = v->h_in;
+    if (stride == len) memcpy(hp, proofs, count * len);
+    else for (size_t i = 0; i < count; ++i) memcpy(hp + i * len, proofs + i * stride, len);
+    memcpy(hp + count * len, public_last, count * 4);
+    if (states) memcpy(hp + count * len + count * 4, states, count * 32);
+    uint8_t* d = v->d_buf;
+    uint8_t* d_pub = d + align256(count * len);
+    uint8_t* d_states = d_pub + align256(count * 4);
+    uint8_t* d_res = d_states + align256(count * 32);
+    VerifyArgs a{};
+    a.proofs = reinterpret_cast<const uint32_t*>(d);
+    a.pub = reinterpret_cast<const uint32_t*>(d_pub);
+    a.states = reinterpret_cast<const uint32_t*>(d_states);
+    a.best = reinterpret_cast<int32_t*>(d_res);
+    a.malformed = reinterpret_cast<uint32_t*>(d_res + align256(count * 4));
+    a.tcode = reinterpret_cast<int32_t*>(d_res + 2 * align256(count * 4));
+    a.count = (uint32_t)count; a.words = (uint32_t)(len / 4); a.q = q; a.R = R; a.L = L;
+    a.B = 1u << log_b; a.N = 1u << L; a.log_n = log_n;
+    a.h = root_of_unity(L);
+    const uint32_t g = root_of_unity(log_n);
+    a.gm1 = invmod(g); a.gm2 = mulmod(a.gm1, a.gm1); a.gm3 = mulmod(a.gm2, a.gm1); a.inv2 = invmod(2);
+    a.qbase = 20u + 9u * R + q;
+    a.per_q = 4u * (3u + 8u * L);
+    for (uint32_t i = 0; i < R; ++i) a.per_q += 6u + 16u * (L - i);
+
+    HIPCHK(hipMemcpyAsync(d, hp, count * len, hipMemcpyHostToDevice, v->stream));
+    HIPCHK(hipMemcpyAsync(d_pub, hp + count * len, count * 4, hipMemcpyHostToDevice, v->stream));
+    if (states) HIPCHK(hipMemcpyAsync(d_states, hp + count * len + count * 4, count * 32, hipMemcpyHostToDevice, v->stream));
+    HIPCHK(hipMemsetAsync(a.best, 0x7f, count * 4, v->stream));
+    HIPCHK(hipMemsetAsync(a.malformed, 0, count * 4, v->stream));
+    HIPCHK(hipMemsetAsync(a.tcode, 0, count * 4, v->stream));
+    const uint32_t gx = (uint32_t)((count + kVerifyThreads - 1) / kVerifyThreads);
+    if (states) {                                      // the transcript chains run beside the paths: cost = max of the two
+        HIPCHK(hipEventRecord(v->ev_in, v->stream));
+        HIPCHK(hipStreamWaitEvent(v->tstream, v->ev_in, 0));
+        hipLaunchKernelGGL(verify_transcript_kernel, dim3(gx), dim3(kVerifyThreads), 0, v->tstream, a);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(v->ev_t, v->tstream));
+    }
+    const uint64_t lanes = (uint64_t)count * q;
+    hipLaunchKernelGGL(verify_algebra_kernel, dim3((uint32_t)((lanes + kVerifyThreads - 1) / kVerifyThreads)), dim3(kVerifyThreads), 0, v->stream, a);
+    HIPCHK(hipGetLastError());
+    const dim3 pgrid(gx, q * (4u + 2u * R));
+    if (v->hash == ZK_HASH_SHA256) hipLaunchKernelGGL(verify_paths_kernel<0>, pgrid, dim3(kVerifyThreads), 0, v->stream, a);
+    else hipLaunchKernelGGL(verify_paths_kernel<1>, pgrid, dim3(kVerifyThreads), 0, v->stream, a);
+    HIPCHK(hipGetLastError());
+    if (states) HIPCHK(hipStreamWaitEvent(v->stream, v->ev_t, 0));
+    HIPCHK(hipMemcpyAsync(v->h_out, a.best, count * 4, hipMemcpyDeviceToHost, v->stream));
+    HIPCHK(hipMemcpyAsync(v->h_out + count, a.malformed, count * 4, hipMemcpyDeviceToHost, v->stream));
+    HIPCHK(hipMemcpyAsync(v->h_out + 2 * count, a.tcode, count * 4, hipMemcpyDeviceToHost, v->stream));
+    HIPCHK(hipStreamSynchronize(v->stream));
+    const int32_t* best = v->h_out;
+    const int32_t* malformed = v->h_out + count;
+    const int32_t* tcode = v->h_out + 2 * count;
+    for (size_t i = 0; i < count; ++i) {
+        int32_t c;
+        if (states && tcode[i]) c = tcode[i];
+        else if (malformed[i]) c = verify_proof(proofs + i * stride, len, log_n, log_b, public_last[i], v->hash, q);   // garbage only
+        else c = best[i] == kNoFailure ? 0 : key_to_check(best[i], R);
+        checks_out[i] = c;
+    }
+    return ZK_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int zk_verify_check(const uint8_t* proof, size_t len, const uint8_t* state, uint32_t log_n, uint32_t log_b, uint32_t public_last,
+                    int hash_kind, uint32_t n_queries, int32_t* check_out) {
+    if (!proof || !check_out) return fail(ZK_ERR_INVALID, "zk_verify_check: null argument");
+    if (hash_kind != ZK_HASH_SHA256 && hash_kind != ZK_HASH_FIELD) return fail(ZK_ERR_INVALID, "zk_verify_check: unknown hash %d", hash_kind);
+    int rc = state ? verify_transcript(proof, len, state, log_n, log_b, n_queries) : 0;   // as zk_verify_queries: the replay first
+    if (!rc) rc = verify_proof(proof, len, log_n, log_b, public_last, hash_kind, n_queries);
+    *check_out = rc;
+    if (rc) return fail(ZK_ERR_VERIFY, "proof rejected at check %d", rc);
+    return ZK_OK;
+}
+
+int zk_verifier_destroy(zk_verifier* v) {
+    if (!v) return ZK_OK;
+    (void)hipSetDevice(v->device);
+    if (v->stream) (void)hipStreamSynchronize(v->stream);
+    if (v->tstream) (void)hipStreamSynchronize(v->tstream);
+    if (v->d_buf) (void)hipFree(v->d_buf);
+    if (v->h_in) (void)hipHostFree(v->h_in);
+    if (v->h_out) (void)hipHostFree(v->h_out);
+    if (v->ev_in) (void)hipEventDestroy(v->ev_in);
+    if (v->ev_t) (void)hipEventDestroy(v->ev_t);
+    if (v->stream) (void)hipStreamDestroy(v->stream);
+    if (v->tstream) (void)hipStreamDestroy(v->tstream);
+    delete v;
+    return ZK_OK;
+}
+
+int zk_verifier_create(int device, uint32_t log_n, uint32_t log_b, zk_verifier** out) {
+    if (!out) return fail(ZK_ERR_INVALID, "zk_verifier_create: out is null");
+    *out = nullptr;
+    // the sizes verify_proof accepts (it answers -1 to any other)
+    if (log_n < 2 || log_b < 1 || log_n + log_b > 30)
+        return fail(ZK_ERR_INVALID, "zk_verifier_create: need 2 <= log_n, 1 <= log_blowup, log_n + log_blowup <= 30 (got %u, %u)", log_n, log_b);
+    HIPCHK(hipSetDevice(device));
+    zk_verifier* v = new (std::nothrow) zk_verifier();
+    if (!v) return fail(ZK_ERR_NOMEM, "out of host memory");
+    v->device = device; v->log_n = log_n; v->log_b = log_b;
+    hipError_t e = hipStreamCreateWithFlags(&v->stream, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipStreamCreateWithFlags(&v->tstream, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&v->ev_in, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&v->ev_t, hipEventDisableTiming);
+    if (e == hipSuccess) e = ensure_verify_consts();
+    if (e != hipSuccess) {
+        zk_verifier_destroy(v);
+        return fail(ZK_ERR_HIP, "zk_verifier_create: %s", hipGetErrorString(e));
+    }
+    *out = v;
+    return ZK_OK;
+}
+
+int zk_verifier_set_queries(zk_verifier* v, uint32_t n_queries) {
+    if (!v) return fail(ZK_ERR_INVALID, "null verifier");
+    if (n_queries < 1 || n_queries > kMaxQueries) return fail(ZK_ERR_INVALID, "zk_verifier_set_queries: need 1 <= n_queries <= %u", kMaxQueries);
+    v->queries = n_queries;
+    return ZK_OK;
+}
+
+int zk_verifier_set_hash(zk_verifier* v, int hash_kind) {
+    if (!v) return fail(ZK_ERR_INVALID, "null verifier");
+    if (hash_kind != ZK_HASH_SHA256 && hash_kind != ZK_HASH_FIELD) return fail(ZK_ERR_INVALID, "zk_verifier_set_hash: unknown hash %d", hash_kind);
+    v->hash = hash_kind;
+    return ZK_OK;
+}
+
+int zk_verifier_run(zk_verifier* v, const uint8_t* proofs, size_t stride, size_t count, const uint8_t* states, const uint32_t* public_last,
+                    int32_t* checks_out) {
+    if (!v) return fail(ZK_ERR_INVALID, "null verifier");
+    if (count == 0) return ZK_OK;
+    if (!proofs || !public_last || !checks_out) return fail(ZK_ERR_INVALID, "zk_verifier_run: null argument");
+    const size_t len = proof_data_len(v->log_n, v->log_b, v->queries);
+    if (stride < len) return fail(ZK_ERR_INVALID, "zk_verifier_run: stride %zu < proof length %zu", stride, len);
+    if (count > SIZE_MAX / stride) return fail(ZK_ERR_INVALID, "zk_verifier_run: count * stride overflows");
+    HIPCHK(hipSetDevice(v->device));
+    // chunks of at most 2^16 proofs and ~256 MiB of proof bytes bound the staging and device buffers
+    size_t chunk = ((size_t)256 << 20) / len;
+    if (chunk > 65536) chunk = 65536;
+    if (chunk < 1) chunk = 1;
+    if (chunk > count) chunk = count;
+    if (int rc = verifier_reserve(v, chunk, len)) return rc;
+    for (size_t i = 0; i < count; i += chunk) {
+        const size_t c = count - i < chunk ? count - i : chunk;
+        if (int rc = verifier_chunk(v, proofs + i * stride, stride, c, states ? states + 32 * i : nullptr, public_last + i, checks_out + i, len))
+            return rc;
+    }
+    for (size_t i = 0; i < count; ++i)
+        if (checks_out[i]) return fail(ZK_ERR_VERIFY, "zk_verifier_run: proof %zu rejected at check %d", i, checks_out[i]);
+    return ZK_OK;
+}
+
+}  // extern "C"

@@ -155,6 +155,16 @@ class Proof:
         check(_lib.load().zk_verify_queries(self.data, len(self.data), self.state if strict else None, self.log_n,
                                             self.log_blowup, self.public_last, HASHES[self.hash], self.queries))
 
+    def check(self, strict=False):
+        """The number of the check the CPU verifier stops at (zk_verify_check): 0 = accepted; otherwise what verify()'s
+        error names.  Never raises for a rejected proof."""
+        out = C.c_int32()
+        rc = _lib.load().zk_verify_check(self.data, len(self.data), self.state if strict else None, self.log_n, self.log_blowup,
+                                         self.public_last, HASHES[self.hash], self.queries, C.byref(out))
+        if rc not in (_lib.ZK_OK, _ERR_VERIFY):
+            check(rc)
+        return out.value
+
     def size(self):                                  # proof.rs:151
         return _lib.load().zk_proof_size(len(self.data))
 
@@ -428,6 +438,71 @@ class BatchContext:
         last = self.public_last()
         return [Proof(states[p].tobytes(), data[p].tobytes(), self.log_n, self.log_blowup, int(last[p]), self.hash, self.queries)
                 for p in range(self.batch)]
+
+
+_ERR_VERIFY = -6
+
+
+class Verifier:
+    """Many proofs of one size checked at once on the GPU (zk_verifier_*).  Every result is the number Proof.check gives for
+    that proof: 0 = accepted, otherwise the CPU verifier's check number."""
+
+    def __init__(self, log_n, log_blowup, device=0, hash="sha256", queries=1):
+        self.log_n, self.log_blowup, self.hash, self.queries = log_n, log_blowup, hash, queries
+        self._h = C.c_void_p()
+        check(_lib.load().zk_verifier_create(device, log_n, log_blowup, C.byref(self._h)))
+        if hash != "sha256":
+            check(_lib.load().zk_verifier_set_hash(self._h, HASHES.get(hash, -1)))   # an unknown name: ZK_ERR_INVALID
+        if queries != 1:
+            check(_lib.load().zk_verifier_set_queries(self._h, queries))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            _lib.load().zk_verifier_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def __enter__(self): return self
+    def __exit__(self, *a): self.close()
+
+    @property
+    def proof_len(self):
+        return _lib.load().zk_proof_data_len_queries(self.log_n, self.log_blowup, self.queries)
+
+    def verify_raw(self, data, public_last, states=None):
+        """data: [count, stride] uint8 (stride >= proof_len; BatchContext.prove_raw()'s array as it is), public_last: [count],
+        states: [count, 32] uint8 or None (not strict).  Returns the check numbers as an int32 array of length count."""
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        if data.ndim != 2:
+            raise ZkError(-1, "verify_raw: data must be [count, stride]")
+        count, stride = data.shape
+        last = _u32arr(public_last)
+        if len(last) != count:
+            raise ZkError(-1, f"verify_raw: {len(last)} public_last values for {count} proofs")
+        st = None
+        if states is not None:
+            st = np.ascontiguousarray(states, dtype=np.uint8)
+            if st.shape != (count, 32):
+                raise ZkError(-1, f"verify_raw: states must be [{count}, 32]")
+        out = np.zeros(count, dtype=np.int32)
+        rc = _lib.load().zk_verifier_run(self._h, _ptr(data), stride, count, _ptr(st) if st is not None else None, _ptr(last), _ptr(out))
+        if rc not in (_lib.ZK_OK, _ERR_VERIFY):
+            check(rc)
+        return out
+
+    def verify(self, proofs, strict=True):
+        """proofs: a list of Proof of this verifier's size (their data, state and public_last are used)."""
+        proofs = list(proofs)
+        plen = self.proof_len
+        data = np.zeros((len(proofs), plen), dtype=np.uint8)
+        for i, p in enumerate(proofs):
+            if len(p.data) != plen:
+                raise ZkError(-1, f"verify: proof {i} has {len(p.data)} bytes, this verifier takes {plen}")
+            data[i] = np.frombuffer(p.data, dtype=np.uint8)
+        last = np.array([p.public_last & 0xFFFFFFFF for p in proofs], dtype=np.uint32)
+        states = np.array([np.frombuffer(p.state, dtype=np.uint8) for p in proofs], dtype=np.uint8).reshape(len(proofs), 32) if strict else None
+        return self.verify_raw(data, last, states)
 
 
 def shard_plan(world, log_n, log_blowup, min_layer_log=0, min_chunk_log=0, overlap_min_log=0, force_collectives=False, plain_collectives=False,
