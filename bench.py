@@ -9,17 +9,24 @@ Fibonacci-square traces.  With --gpus N > 1: ONE proof at domain 2^24 * N sharde
 GPUs (weak scaling) by the native sharded prover (zk_shard_*: RCCL all-to-all per commitment).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--log-n 21] [--log-blowup 3]
+    python bench.py --full                    # N = 1: also every secondary leg, the CPU baseline and the parity check
     python bench.py --gpus N --plan-only      # the sharded layout and a written-down estimate: no GPU, no timing
     python bench.py --dump-outputs DIR        # also DIR/proof_data.npy, proof_state.npy, public_last.npy: the last timed proof
 
 `--gpus N` without a launcher starts the N ranks itself (one child process per GPU, before anything
 touches the GPU); under `torch.distributed.run` it reads RANK / LOCAL_RANK / WORLD_SIZE / MASTER_*.
 
+A plain N = 1 run does only what the headline needs: context and trace, the warm-up proofs, the timed
+proofs, --dump-outputs, the line.  `--full` adds what used to run by default after the timed region:
+the verified proof, the per-kernel stages, the chain probe, the secondary legs (bench_legs.py), the CPU
+baseline and the parity check.  An N > 1 run is one shot and always carries its legs (--no-secondary
+drops them); --full changes nothing there.
+
 One JSON line on stdout (rank 0).  `roofline` is for the dominant kernel
 (merkle_subtree_kernel<leaf>), timed live with HIP events on the launch stream inside the
-timed region; `cpu_baseline` is the CPU oracle (oracle/, a port of the reference algorithm
-with O(N log N) transforms) on a bounded sample, rank 0 at N=1 only; `parity_checked` says the
-timed proof's bytes were compared with the oracle's proof of the same trace.
+timed region; with --full, `cpu_baseline` is the CPU oracle (oracle/, a port of the reference
+algorithm with O(N log N) transforms) on a bounded sample, rank 0 at N=1 only, and `parity_checked`
+says the timed proof's bytes were compared with the oracle's proof of the same trace.
 
 Three files since round 6: this one (arguments, the N = 1 headline, the one line), bench_legs.py (the secondary legs of
 the N = 1 line: configs[1], the full proof at 2^20, the field hash at 2^24, batches, ...), bench_multi.py (N > 1: launcher,
@@ -52,6 +59,9 @@ def parse():
     ap.add_argument("--log-blowup", type=int, default=3)
     ap.add_argument("--hash", choices=("sha256", "field"), default="sha256",
                     help="Merkle hash: the reference's SHA-256 (the benchmark), or the field-native hash of configs[4]")
+    ap.add_argument("--full", action="store_true",
+                    help="N = 1: after the timed proofs, also verify the last one, time every kernel class, run the chain probe, the "
+                         "secondary legs, the CPU baseline and the parity check against the oracle (the options below narrow this)")
     ap.add_argument("--no-secondary", action="store_true",
                     help="skip the secondary figures (configs[1], proofs in flight, batches, staged stages): profiling runs")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -237,7 +247,7 @@ def emit_line(R, result):
                              "durations overlap and achieved / frac are lower bounds (ZK_SHARD_ONE_BUILD_STREAM=1 gives unshared launches)")
     # the hashing of one proof against its floor: every Merkle launch of the per-stage proof, and the time the same
     # instruction count needs at the chain rate (a floor the kernels cannot beat by construction)
-    pk = result["per_kernel"]
+    pk = result.get("per_kernel") or {}
     hash_ms = sum(pk[k]["ms"] for k in ("merkle_leaf", "merkle_inner") if k in pk)
     hash_ops = sum(pk[k]["ops"] for k in ("merkle_leaf", "merkle_inner") if k in pk)
     if best_chain and hash_ops:
@@ -262,7 +272,7 @@ def emit_line(R, result):
             if note:
                 row["note"] = note
             stages.append(row)
-    for name, st in result["per_kernel"].items():
+    for name, st in pk.items():
         add_stage(name, st)
     for name, st in (result.get("staged") or {}).items():
         if name != "ntt":
@@ -298,7 +308,7 @@ def emit_line(R, result):
         out["transport"], out["transport_note"] = result["transport"], result["transport_note"]
         out["parity_checked"] = bool(result["parity"] and result["parity"].get("equal"))
         out["parity"] = result["parity"]
-    if world == 1 and not sharded_run and not args.no_cpu_baseline and args.hash == "sha256":
+    if args.full and world == 1 and not sharded_run and not args.no_cpu_baseline and args.hash == "sha256":
         sample = args.cpu_sample_log_n if args.cpu_sample_log_n is not None else log_n
         out["cpu_baseline"], oracle_proof = cpu_baseline(sample, log_b)
         if sample == log_n:
@@ -310,7 +320,7 @@ def emit_line(R, result):
                 print("[bench] PARITY FAILURE: the timed proof differs from the CPU oracle's", file=sys.stderr, flush=True)
         else:
             out["parity_checked"] = False
-    if world == 1 and not sharded_run and not args.no_cpu_baseline and args.hash == "field":
+    if args.full and world == 1 and not sharded_run and not args.no_cpu_baseline and args.hash == "field":
         # configs[4]: the hash is the build's own definition; the checker is the oracle's independent implementation (plain
         # residues; eight hashes at a time in exact double arithmetic, itself pinned on its scalar form by the CPU tests).
         # Round 4: fast enough for the benchmark's own size -- every byte of the TIMED proof and the final channel state.
@@ -336,7 +346,7 @@ def emit_line(R, result):
 
 def run_single(R):
     """N = 1: the headline (args.steps timed proofs at domain 2^(log_n + log_blowup), trace resident -> proof bytes on the host),
-    then the secondary legs (bench_legs.py), then the line."""
+    with --full then the per-kernel stages and the secondary legs (bench_legs.py), then the line."""
     import bench_legs as legs
     args, zk, barrier = R.args, R.zk, R.barrier
     log_n, log_b, local_rank = R.log_n, R.log_b, R.local_rank
@@ -356,16 +366,21 @@ def run_single(R):
     barrier()
     dt = time.perf_counter() - t0
     dom = ctx.kernel_stats(reset=True)["merkle_leaf"]
+    result = {"dt": dt, "dom": dom, "setup_ms": ctx.setup_ms,
+              "device_bytes": ctx.device_bytes, "proof_bytes": len(proof.data), "scaling": "weak",
+              "units": N * args.steps, "parallelism": "single-gpu", "host_levels": list(ctx.host_levels),
+              "host_hashing": zk.host_hash_mode(), "proof": proof}
+    if not args.full:                            # the headline is all a plain run measures
+        ctx.close()
+        emit_line(R, result)
+        return
     proof.verify()
     # one extra untimed step with every kernel class bracketed: per-stage table
     ctx.set_profiling("all")
     ctx.prove()
     per_kernel = ctx.kernel_stats(reset=True)
     ctx.set_profiling(())
-    result = {"dt": dt, "dom": dom, "per_kernel": per_kernel, "setup_ms": ctx.setup_ms,
-              "device_bytes": ctx.device_bytes, "proof_bytes": len(proof.data), "scaling": "weak",
-              "units": N * args.steps, "parallelism": "single-gpu", "host_levels": list(ctx.host_levels),
-              "host_hashing": zk.host_hash_mode(), "proof": proof, "legs_skipped": []}
+    result.update(per_kernel=per_kernel, legs_skipped=[])
     sha = args.hash == "sha256"
     secondary = not args.no_secondary
 

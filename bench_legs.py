@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""bench_legs.py -- the secondary legs of bench.py's N = 1 line: everything measured AFTER the headline (full prover at domain
-2^24) has been timed.  Each leg takes the run namespace R (bench.main), the headline's context where it needs it, and returns the
+"""bench_legs.py -- the secondary legs of bench.py's N = 1 line with --full: everything measured AFTER the headline (full prover at
+domain 2^24) has been timed.  Each leg takes the run namespace R (bench.main), the headline's context where it needs it, and returns the
 record that goes into the line under its own key.  Nothing here touches the oracle except `fieldhash_2e24`, which uses it as the
 CHECKER of the timed field-hash proof (the oracle is test infrastructure: oracle/__init__.py).
 

@@ -322,3 +322,54 @@ def test_bench_dump_outputs_are_the_last_timed_proof(tmp_path, orc):
     assert bytes(np.load(str(d / "proof_data.npy")).astype(np.uint8)) == want.proof
     assert bytes(np.load(str(d / "proof_state.npy")).astype(np.uint8)) == want.state
     assert int(np.load(str(d / "public_last.npy"))[0]) == want.public_last
+
+
+# what only `--full` adds to the N = 1 line: the CPU leg and its parity check, the per-kernel stages, the chain probe, the legs
+FULL_ONLY_KEYS = ("cpu_baseline", "parity_checked", "parity", "ms_per_step_device_only", "device_only", "soak", "lde_commit_2e20", "full_2e20",
+                  "reference_size_2e13", "batched_2e13", "pipelined", "legs_skipped")
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_the_headline_alone(tmp_path):
+    """A plain `bench.py --steps K --warmup W`: the headline line (metric, value, unit, ms_per_step of the K timed proofs) and the
+    last timed proof in --dump-outputs, and nothing measured or checked after the timed region."""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE")}
+    d = tmp_path / "dump"
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--log-n", "12", "--dump-outputs", str(d)],
+                         capture_output=True, text=True, timeout=280, env=env)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [l for l in out.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1
+    rec = json.loads(lines[0])
+    assert rec["metric"] == "field-elements/s through LDE+Merkle+FRI (full STARK-101 prover)" and rec["unit"] == "field-elements/s"
+    assert rec["higher_is_better"] is True and rec["dtype"] == "u32 (mod 3*2^30+1) + SHA-256"
+    assert rec["steps"] == 3 and rec["warmup"] == 1 and rec["n_gpus"] == 1 and rec["config"]["domain"] == 1 << 15
+    assert rec["value"] == pytest.approx((1 << 15) / (rec["ms_per_step"] * 1e-3), rel=1e-6)
+    assert rec["roofline"]["valu"]["chain"] == [] and rec["stages"] == []
+    for k in FULL_ONLY_KEYS:
+        assert rec.get(k) is None, k
+    assert not any(k.startswith(("batched_2e", "fieldhash_2e")) for k in rec)
+    assert sorted(os.listdir(d)) == ["proof_data.npy", "proof_state.npy", "public_last.npy"]
+    assert np.load(str(d / "proof_data.npy")).size == rec["proof_bytes"]
+
+
+@pytest.mark.gpu
+def test_bench_full_run_keeps_every_leg(tmp_path):
+    """`bench.py --full` at a small domain: the headline and, after it, everything a plain run leaves out -- the per-kernel stages, the
+    chain probe, every secondary leg, the CPU baseline and the timed proof byte-compared with the oracle -- in the one line."""
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE")}
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "3", "--warmup", "1", "--log-n", "14",
+                          "--soak-seconds", "0.5", "--batch-log", "1"], capture_output=True, text=True, timeout=280, env=env)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [l for l in out.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1
+    rec = json.loads(lines[0])
+    assert rec["steps"] == 3 and rec["value"] == pytest.approx((1 << 17) / (rec["ms_per_step"] * 1e-3), rel=1e-6)
+    assert rec["parity_checked"] is True and rec["parity"]["equal"] is True and rec["cpu_baseline"]["value"] > 0
+    kernels = {s["kernel"] for s in rec["stages"]}
+    assert "ntt" in kernels and any(k.startswith("merkle") for k in kernels) and len(rec["roofline"]["valu"]["chain"]) == 2
+    # the legs the line carries at any domain (the batched and field-hash legs at the benchmark's domain are reported at 2^24 only)
+    for k in ("soak", "lde_commit_2e20", "full_2e20", "reference_size_2e13", "batched_2e13", "pipelined"):
+        assert rec.get(k) is not None and "error" not in rec[k], k
+    assert "legs_skipped" not in rec

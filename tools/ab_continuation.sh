@@ -11,8 +11,8 @@ for v in "-DZK_MERKLE_CONTINUATION=0" "" "-DZK_MERKLE_CONTINUATION=0" ""; do
     tag=$(echo "d$v" | tr -d ' ' | tr -c 'A-Za-z0-9=_\n' '_')
     python -m zkstark_amd.build > $O/build_$tag.log 2>&1 || { echo "$v: build failed" | tee -a $O/summary.txt; continue; }
     timeout -k 10 300 python -m pytest tests/test_gpu_kernels.py tests/test_fieldhash.py -m gpu -x -q -k "merkle or fieldhash or prover" > $O/pytest_$tag.log 2>&1 || { echo "$v: PARITY FAILED" | tee -a $O/summary.txt; continue; }
-    timeout -k 10 300 python bench.py --hash field --steps 20 --warmup 3 --no-secondary --no-cpu-baseline --soak-seconds 0 > $O/field_$tag.json 2> $O/field_$tag.err
-    timeout -k 10 300 python bench.py --steps 60 --warmup 5 --no-secondary --no-cpu-baseline --soak-seconds 0 > $O/sha_$tag.json 2> $O/sha_$tag.err
+    timeout -k 10 300 python bench.py --full --hash field --steps 20 --warmup 3 --no-secondary --no-cpu-baseline --soak-seconds 0 > $O/field_$tag.json 2> $O/field_$tag.err
+    timeout -k 10 300 python bench.py --full --steps 60 --warmup 5 --no-secondary --no-cpu-baseline --soak-seconds 0 > $O/sha_$tag.json 2> $O/sha_$tag.err
     rm -rf $O/prof_$tag
     timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $O/prof_$tag -- python3 bench.py --hash field --steps 2 --warmup 1 --no-cpu-baseline --no-secondary --soak-seconds 0 --in-flight 1 > $O/prof_$tag.log 2>&1
     python3 - "$v" $O $tag >> $O/summary.txt <<'PY'

@@ -8,7 +8,7 @@ for v in "-DZK_FIELD_QUAD_MAX_NODES=0" "-DZK_FIELD_QUAD_MAX_NODES=64" "-DZK_FIEL
     tag=$(echo "d$v" | tr -d ' ' | tr -c 'A-Za-z0-9=_\n' '_')
     python -m zkstark_amd.build > $O/build_$tag.log 2>&1 || { echo "$v: build failed" | tee -a $O/summary.txt; continue; }
     timeout -k 10 300 python -m pytest tests/test_fieldhash.py -m gpu -x -q > $O/pytest_$tag.log 2>&1 || { echo "$v: PARITY FAILED" | tee -a $O/summary.txt; tail -5 $O/pytest_$tag.log; continue; }
-    timeout -k 10 300 python bench.py --hash field --steps 20 --warmup 3 --no-secondary --soak-seconds 0 > $O/field_$tag.json 2> $O/field_$tag.err
+    timeout -k 10 300 python bench.py --full --hash field --steps 20 --warmup 3 --no-secondary --soak-seconds 0 > $O/field_$tag.json 2> $O/field_$tag.err
     python3 - "$v" $O/field_$tag.json >> $O/summary.txt <<'PY'
 import json, sys
 v, f = sys.argv[1:3]

@@ -8,8 +8,8 @@ for v in "-DZK_MONT_VARIANT=2" "-DZK_MONT_VARIANT=4" "-DZK_MONT_VARIANT=4 -DZK_A
     export ZK_BUILD_DEFS="$v"
     tag=$(echo "$v" | tr -d ' ' | tr -c 'A-Za-z0-9=_\n' '_')
     python -m zkstark_amd.build > $O/build_$tag.log 2>&1 || { echo "$v: build failed" | tee -a $O/summary.txt; continue; }
-    timeout -k 10 300 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --soak-seconds 0 --in-flight 1 > $O/sha_$tag.json 2> $O/sha_$tag.err
-    timeout -k 10 300 python bench.py --hash field --steps 8 --warmup 2 --no-cpu-baseline --no-secondary --soak-seconds 0 --in-flight 1 > $O/field_$tag.json 2> $O/field_$tag.err
+    timeout -k 10 300 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --soak-seconds 0 --in-flight 1 > $O/sha_$tag.json 2> $O/sha_$tag.err
+    timeout -k 10 300 python bench.py --full --hash field --steps 8 --warmup 2 --no-cpu-baseline --no-secondary --soak-seconds 0 --in-flight 1 > $O/field_$tag.json 2> $O/field_$tag.err
     python3 - "$v" $O/sha_$tag.json $O/field_$tag.json >> $O/summary.txt <<'PY'
 import json, sys
 v, a, b = sys.argv[1:4]

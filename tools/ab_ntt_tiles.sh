@@ -8,7 +8,7 @@ for v in "" "-DZK_NTT_MID_MAX_LOG=30" "-DZK_NTT_SMALL_MAX_LOG=16 -DZK_NTT_MID_MA
     export ZK_BUILD_DEFS="$v"
     tag=$(echo "d$v" | tr -d ' ' | tr -c 'A-Za-z0-9=_\n' '_')
     python -m zkstark_amd.build > $O/build_$tag.log 2>&1 || { echo "$v: build failed" | tee -a $O/summary.txt; continue; }
-    timeout -k 10 300 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --soak-seconds 0 --in-flight 1 > $O/sha_$tag.json 2> $O/sha_$tag.err
+    timeout -k 10 300 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --soak-seconds 0 --in-flight 1 > $O/sha_$tag.json 2> $O/sha_$tag.err
     python3 - "$v" $O/sha_$tag.json >> $O/summary.txt <<'PY'
 import json, sys
 v, a = sys.argv[1:3]
