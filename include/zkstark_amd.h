@@ -68,7 +68,9 @@ const char *zk_version(void);
  *     its own compiler sees it (ZK_STRUCT_INIT zeroes the struct and sets it) BEFORE every call, for outputs as well as for
  *     inputs.  The library reads / writes at most struct_size bytes and refuses (ZK_ERR_INVALID, zk_last_error names the
  *     struct and both sizes) a size of 0 or one below the struct's size in ABI version 6 (the first with this rule): a
- *     caller compiled against an older, smaller layout gets an error instead of shifted fields or a stack overwrite;
+ *     caller compiled against an older, smaller layout gets an error instead of shifted fields or a stack overwrite; a size
+ *     between a published layout and the next (zk_transcript_info: 1244 bytes in version 6, 1256 with the grinding fields)
+ *     is refused too, as no header ever had it;
  *   - new fields are appended at the END only, so a caller compiled against a smaller (>= version 6) layout keeps working:
  *     input fields it does not know are taken as 0 (= default), output fields it does not know are not written. */
 #define ZK_ABI_VERSION 6u
@@ -118,6 +120,15 @@ int zk_ctx_sync(zk_ctx *ctx);
  * prover.rs:263).  With q > 1 the q raw indices are drawn in a row and each query's openings are
  * committed in turn; q = 1 is byte-identical to the reference format. */
 int zk_ctx_set_queries(zk_ctx *ctx, uint32_t n_queries);
+/* Proof-of-work grinding of later zk_prove* (zk_prove_resident, zk_prove_channel, zk_prove_many; DESIGN.md "Grinding"; the
+ * reference has none).  grind_bits = g in 0..32, default 0.  g = 0: no nonce, every byte as without this call.  g > 0: after the
+ * free term is committed (prover.rs:254) the prover finds the SMALLEST u64 w such that SHA-256(S || le64(w)) begins with g zero
+ * bits (S = the channel state; bits read MSB-first from byte 0, as zk_channel_get_u32 reads the state), commits le64(w) (bincode
+ * u64: 8 bytes between the free term and the first query raw) and draws the queries as before.  A cheating prover then redoes
+ * 2^g hashes per query set it tries: conjectured security bits ~ n_queries * log_blowup + g.  Small g is searched on the
+ * calling thread, larger g on the device (csrc/grind.hip); the nonce is the same either way.  The sharded prover (zk_shard_*)
+ * does not grind. */
+int zk_ctx_set_grinding(zk_ctx *ctx, uint32_t grind_bits);
 /* Opt-in reference self-checks.  The reference asserts its way through generate_proof; with on != 0 the same
  * checkpoints run inside every later zk_prove* on the data as it sits in HBM: the interpolant passes through every
  * trace point (prover.rs:64-66), every constraint division is exact and deg cp = n - 1 (prover.rs:148-159, :169), every
@@ -212,6 +223,8 @@ typedef struct zk_transcript_info {
     uint32_t query_raw;
     uint32_t public_last; /* a[n-2] */
     uint8_t roots[34][32]; /* trees 0 .. log_n + 1 */
+    uint32_t grind_bits;   /* zk_ctx_set_grinding of that proof (0: no nonce) */
+    uint64_t grind_nonce;  /* the nonce committed after the free term (grind_bits > 0) */
 } zk_transcript_info;
 int zk_last_transcript(const zk_ctx *ctx, zk_transcript_info *out);
 /* Optional per-kernel timing with HIP events on the context stream.  class_mask selects
@@ -253,6 +266,8 @@ size_t zk_batch_size(const zk_batch *b);                    /* 2^log_batch */
 /* As zk_ctx_set_queries (1..16 here) and zk_ctx_set_hash, for every proof of the batch. */
 int zk_batch_set_queries(zk_batch *b, uint32_t n_queries);
 int zk_batch_set_hash(zk_batch *b, int hash_kind);
+/* As zk_ctx_set_grinding, for every proof of the batch: one launch searches the nonces of all proofs of the batch at once. */
+int zk_batch_set_grinding(zk_batch *b, uint32_t grind_bits);
 /* on = 0: every tree level of the batch on the device (default: the host threads hash the top levels of each proof's
  * trees when the CPU has SHA extensions, as zk_ctx_set_host_levels).  Results are identical. */
 int zk_batch_set_host_levels(zk_batch *b, int on);
@@ -290,6 +305,14 @@ int zk_verify_strict(const uint8_t *proof, size_t len, const uint8_t state[32], 
 size_t zk_proof_size(size_t data_len);
 size_t zk_proof_data_len(uint32_t log_n, uint32_t log_blowup);
 size_t zk_proof_data_len_queries(uint32_t log_n, uint32_t log_blowup, uint32_t n_queries);
+/* With grind_bits > 0: 8 bytes more (the nonce). */
+size_t zk_proof_data_len_grind(uint32_t log_n, uint32_t log_blowup, uint32_t n_queries, uint32_t grind_bits);
+/* Proof-of-work search (zk_ctx_set_grinding): the smallest nonce >= start whose SHA-256(state || le64(nonce)) begins with
+ * grind_bits zero bits (0..32; 0 gives start), on the GPU (zk_grind) or on <= 16 host threads (zk_grind_host; threads is
+ * clamped to 1..16).  Gives up with an error naming grind_bits after 2^44 nonces.  A zk_channel user grinds on
+ * zk_channel_state and commits the 8 little-endian bytes with zk_channel_commit. */
+int zk_grind(int device, const uint8_t state[32], uint32_t grind_bits, uint64_t start, uint64_t *nonce_out);
+int zk_grind_host(const uint8_t state[32], uint32_t grind_bits, uint64_t start, uint32_t threads, uint64_t *nonce_out);
 /* compute_root_from_path (merkle.rs:82-110), CPU. */
 int zk_compute_root_from_path(uint32_t element, size_t index, const uint8_t *path, size_t path_len,
                               uint8_t out[32]);
@@ -303,6 +326,13 @@ int zk_compute_root_from_path_ex(uint32_t element, size_t index, const uint8_t *
  * Returns ZK_OK if accepted, ZK_ERR_VERIFY if rejected (check_out set either way), ZK_ERR_INVALID on bad arguments. */
 int zk_verify_check(const uint8_t *proof, size_t len, const uint8_t *state, uint32_t log_n, uint32_t log_blowup,
                     uint32_t public_last, int hash_kind, uint32_t n_queries, int32_t *check_out);
+/* zk_verify_check for proofs made with zk_ctx_set_grinding(grind_bits).  Strict (state != NULL): the nonce's hash must begin with
+ * grind_bits zero bits, else -1998 -- checked after the beta challenges and before the first query challenge, without advancing
+ * the k of -(1000+k); ANY nonce that meets the bits is accepted.  Not strict: the 8 nonce bytes are skipped unchecked -- the query
+ * raws are read from the proof, not derived (as the reference does), so the work would certify nothing there.  A proof whose
+ * length does not match grind_bits is rejected (-1). */
+int zk_verify_grind(const uint8_t *proof, size_t len, const uint8_t *state, uint32_t log_n, uint32_t log_blowup,
+                    uint32_t public_last, int hash_kind, uint32_t n_queries, uint32_t grind_bits, int32_t *check_out);
 
 /* A verifier for many proofs of one size (log_n, log_blowup: the sizes zk_verify_queries accepts).  It owns its streams and
  * device buffers (grown on demand) and a pinned staging buffer.  One verifier is used from one host thread at a time. */
@@ -311,6 +341,8 @@ int zk_verifier_create(int device, uint32_t log_n, uint32_t log_blowup, zk_verif
 int zk_verifier_destroy(zk_verifier *v);
 int zk_verifier_set_queries(zk_verifier *v, uint32_t n_queries);   /* 1..64, as zk_verify_queries */
 int zk_verifier_set_hash(zk_verifier *v, int hash_kind);
+/* Proofs made with zk_ctx_set_grinding(grind_bits): checks_out as zk_verify_grind gives them (-1998 in strict mode). */
+int zk_verifier_set_grinding(zk_verifier *v, uint32_t grind_bits);
 /* count proofs at proofs + i*stride, each exactly zk_proof_data_len_queries(log_n, log_blowup, q) bytes (stride >= that, any
  * alignment); states: count*32 bytes, or NULL = not strict; public_last[count].  checks_out[i] = what zk_verify_check returns
  * in check_out for proof i, for EVERY input.  Returns ZK_OK if all were accepted, ZK_ERR_VERIFY if any was rejected

@@ -38,7 +38,8 @@ class _Sized(C.Structure):
 
 class TranscriptInfo(_Sized):
     _fields_ = [("struct_size", C.c_uint32), ("alpha_raw", C.c_uint32 * 3), ("beta_raw", C.c_uint32 * 32), ("free_term", C.c_uint32),
-                ("query_raw", C.c_uint32), ("public_last", C.c_uint32), ("roots", (C.c_uint8 * 32) * 34)]
+                ("query_raw", C.c_uint32), ("public_last", C.c_uint32), ("roots", (C.c_uint8 * 32) * 34), ("grind_bits", C.c_uint32),
+                ("grind_nonce", C.c_uint64)]
 
 
 class KernelStat(_Sized):
@@ -127,6 +128,13 @@ SYMBOLS = {
     "zk_ctx_set_host_levels": (_int, [_vp, _u32, _u32]),
     "zk_ctx_get_host_levels": (_int, [_vp, C.POINTER(_u32), C.POINTER(_u32)]),
     "zk_ctx_set_queries": (_int, [_vp, _u32]),
+    "zk_ctx_set_grinding": (_int, [_vp, _u32]),
+    "zk_batch_set_grinding": (_int, [_vp, _u32]),
+    "zk_verifier_set_grinding": (_int, [_vp, _u32]),
+    "zk_proof_data_len_grind": (_sz, [_u32, _u32, _u32, _u32]),
+    "zk_verify_grind": (_int, [_vp, _sz, _vp, _u32, _u32, _u32, _int, _u32, _u32, C.POINTER(C.c_int32)]),
+    "zk_grind": (_int, [_int, _vp, _u32, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "zk_grind_host": (_int, [_vp, _u32, C.c_uint64, _u32, C.POINTER(C.c_uint64)]),
     "zk_ctx_set_early_launch": (_int, [_vp, _int]),
     "zk_ctx_get_early_launch": (_int, [_vp]),
     "zk_verify_queries": (_int, [_vp, _sz, _vp, _u32, _u32, _u32, _int, _u32]),

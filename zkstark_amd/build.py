@@ -20,7 +20,7 @@ CSRC = os.path.join(HERE, "csrc")
 OBJDIR = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libzkstark_amd.so")
 HASHFILE = LIB + ".hash"
-SOURCES = ["kernels.hip", "ntt_fast.hip", "domain.hip", "zkstark.hip", "batch.hip", "shard.hip", "verify.hip", "host_sha.cpp", "version.cpp"]
+SOURCES = ["kernels.hip", "ntt_fast.hip", "domain.hip", "zkstark.hip", "batch.hip", "shard.hip", "verify.hip", "grind.hip", "host_sha.cpp", "version.cpp"]
 HEADERS = ["field.hpp", "sha256.hpp", "sha256_quad.hpp", "fieldhash.hpp", "fieldhash_f64.hpp", "kernels.hpp", "transcript.hpp", "host_sha.hpp", "internal.hpp", "pool.hpp",
            "shard.hpp", "board.hpp", "peer.hpp", os.path.join("..", "..", "include", "zkstark_amd.h")]
 ARCH = "gfx950"

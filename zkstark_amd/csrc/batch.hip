@@ -50,7 +50,9 @@ struct zk_batch {
     uint32_t* h_last = nullptr;       // pinned: [batch][B] last layer / [batch] last trace values
     size_t per_proof_vals = 0, per_proof_digs = 0;   // per query
     uint32_t queries = 1;             // decommitment queries per proof (1 = the reference, prover.rs:263)
-    int hash = 0;                     // Merkle hash: 0 = SHA-256 (reference), 1 = field-native
+    uint32_t grind = 0;               // proof-of-work bits (zk_batch_set_grinding)
+    Grinder* grinder = nullptr;       // one launch grinds for every proof of the batch (created by the setter above kGrindHostMaxBits)
+    int hash = 0;                    // Merkle hash: 0 = SHA-256 (reference), 1 = field-native
     std::vector<uint32_t> first, last;
     bool have_traces = false;
     size_t device_bytes = 0;
@@ -90,6 +92,22 @@ MailArgs bmail(zk_batch* b, uint32_t log_m) {
     if (b->counters_dirty) { (void)hipMemsetAsync(b->d_counter, 0, 64, b->stream); b->counters_dirty = false; }
     m.mailbox = b->d_mail; m.seq = ++b->mail_seq; m.counter = b->d_counter; m.top = b->lb + bextra(b, log_m);
     return m;
+}
+// Proof-of-work nonce of every proof after its free term (DESIGN.md "Grinding"), committed to its channel: one thread per proof for
+// small g, else one launch per chunk for all proofs still searching.
+int bgrind(zk_batch* b, std::vector<Channel>& ch) {
+    const size_t nb = ch.size();
+    if (b->grind <= kGrindHostMaxBits || !b->grinder) {
+        std::atomic<int> bad{0};
+        b->pool->run(nb, 1, [&](size_t p) { uint64_t w; if (grind_channel(nullptr, ch[p], b->grind, &w)) bad.store(1); });
+        return bad.load() ? fail(ZK_ERR_HIP, "zk_batch_prove: grinding failed") : (int)ZK_OK;
+    }
+    std::vector<uint8_t> states(32 * nb);
+    std::vector<uint64_t> w(nb);
+    for (size_t p = 0; p < nb; ++p) memcpy(states.data() + 32 * p, ch[p].state, 32);
+    if (int rc = grind_device(b->grinder, states.data(), nb, b->grind, 0, w.data())) return rc;
+    b->pool->run(nb, 16, [&](size_t p) { grind_commit(ch[p], w[p]); });
+    return ZK_OK;
 }
 // the batch's roots of the last commit launch: [batch][8] state words in the mailbox
 int bwait_roots(zk_batch* b) {
@@ -162,6 +180,7 @@ int zk_batch_destroy(zk_batch* b) {
         if (p) (void)hipFree(p);
     for (void* p : {(void*)b->h_chal, (void*)b->h_mail, (void*)b->h_goff, (void*)b->h_gout, (void*)b->h_last, (void*)b->h_stage})
         if (p) (void)hipHostFree(p);
+    grinder_destroy(b->grinder);                         // on b->stream: before the stream goes
     if (b->stream) (void)hipStreamDestroy(b->stream);
     delete b->pool;
     delete b;
@@ -296,6 +315,18 @@ int zk_batch_set_hash(zk_batch* b, int hash_kind) {
     if (b->single) return zk_ctx_set_hash(b->single, hash_kind);
     return ZK_OK;
 }
+int zk_batch_set_grinding(zk_batch* b, uint32_t grind_bits) {
+    if (!b) return fail(ZK_ERR_INVALID, "null batch");
+    ZK_BATCH_EXCLUSIVE(b, "zk_batch_set_grinding");
+    if (grind_bits > kMaxGrindBits) return fail(ZK_ERR_INVALID, "zk_batch_set_grinding: need grind_bits <= %u (got %u)", kMaxGrindBits, grind_bits);
+    if (b->single) { b->grind = grind_bits; return zk_ctx_set_grinding(b->single, grind_bits); }
+    if (grind_bits > kGrindHostMaxBits && !b->grinder) {
+        HIPCHK(hipSetDevice(b->device));
+        if (int rc = grinder_create(b->device, b->stream, (uint32_t)b->batch, &b->grinder)) return rc;
+    }
+    b->grind = grind_bits;
+    return ZK_OK;
+}
 size_t zk_batch_device_bytes(const zk_batch* b) { return b ? b->device_bytes : 0; }
 
 // traces: [batch][n-1] canonical residues on the host (prover.rs:32-39 per proof)
@@ -361,7 +392,7 @@ int zk_batch_prove(zk_batch* b, uint8_t* proofs_out, size_t stride, uint8_t* sta
     if (!busy.mine) return fail(ZK_ERR_STATE, "zk_batch_prove: another zk_batch_prove is running on this batch");
     const uint32_t Q = b->queries;
     const int hash = b->hash;
-    const size_t plen = proof_data_len(b->log_n, b->log_b, Q);
+    const size_t plen = proof_data_len(b->log_n, b->log_b, Q, b->grind);
     if (stride < plen) return fail(ZK_ERR_BUFFER, "zk_batch_prove: stride %zu < proof length %zu", stride, plen);
     if (b->single) {
         size_t len = 0;
@@ -445,8 +476,13 @@ int zk_batch_prove(zk_batch* b, uint8_t* proofs_out, size_t stride, uint8_t* sta
     const size_t nv = Q * b->per_proof_vals, ndg = Q * b->per_proof_digs;     // per proof, all its queries
     uint64_t* voff = b->h_goff;
     uint64_t* doff = b->h_goff + nb * nv;
+    if (b->grind) {                                                       // free terms, then the nonces of all proofs at once
+        b->pool->run(nb, 16, [&](size_t p) { ch[p].commit_u32(b->h_last[p * B]); });   // prover.rs:254
+        if ((rc = bgrind(b, ch))) return rc;
+        lap("grind");
+    }
     b->pool->run(nb, 16, [&](size_t p) {
-        ch[p].commit_u32(b->h_last[p * B]);                               // prover.rs:254
+        if (!b->grind) ch[p].commit_u32(b->h_last[p * B]);               // prover.rs:254
         uint32_t qraw[kMaxQueries];
         for (uint32_t k = 0; k < Q; ++k) qraw[k] = ch[p].get_u32();       // prover.rs:263 (x Q)
         uint64_t* vo = voff + p * nv;

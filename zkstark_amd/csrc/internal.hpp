@@ -43,11 +43,13 @@ template <> struct AbiMin<zk_shard_stats>     { static constexpr uint32_t v = 11
 template <> struct AbiMin<zk_shard_plan_info> { static constexpr uint32_t v = 200;  static constexpr const char* name = "zk_shard_plan_info"; };
 template <> struct AbiMin<zk_chain_probe>     { static constexpr uint32_t v = 48;   static constexpr const char* name = "zk_chain_probe"; };
 // Bytes of *p the library may touch (min of the caller's and the library's size), or 0 after fail(): struct_size is 0, below
-// the version-6 size (a caller compiled against an older header, or one that never set it), or absurd.
+// the version-6 size (a caller compiled against an older header, or one that never set it), absurd, or between the version-6
+// size and this library's size -- no header has such a layout (zk_transcript_info grew from 1244 to 1256 bytes at once when the
+// grinding fields were appended), so the caller's idea of the struct is not one the library can honour field by field.
 template <class T> inline size_t abi_bytes(const T* p, const char* who) {
     static_assert(sizeof(T) >= AbiMin<T>::v && offsetof(T, struct_size) == 0, "a struct of the C ABI shrank or lost its size field");
     const uint32_t n = p->struct_size;
-    if (n < AbiMin<T>::v || n > (1u << 16)) {
+    if (n < AbiMin<T>::v || n > (1u << 16) || (n > AbiMin<T>::v && n < sizeof(T))) {
         fail(ZK_ERR_INVALID, "%s: %s.struct_size is %u; the caller sets it to sizeof(%s) before the call (ZK_STRUCT_INIT): at least %u bytes "
                              "(ABI version 6), %zu in this library (ABI version %u) -- was the caller compiled against another zkstark_amd.h?",
              who, AbiMin<T>::name, n, AbiMin<T>::name, AbiMin<T>::v, sizeof(T), (unsigned)ZK_ABI_VERSION);
@@ -115,6 +117,23 @@ int run_dif(const uint32_t* src, uint32_t* data, uint32_t log_m, const Plan& pl,
             hipStream_t s, Profiler* prof = nullptr, uint32_t batch = 1, size_t src_stride = 0, size_t data_stride = 0);
 // Forward transform, digit-reversed in, natural out.
 int run_dit(uint32_t* data, uint32_t log_m, const Plan& pl, PowTable tw, uint32_t L, hipStream_t s);
+
+// ---- grinding (grind.hip; DESIGN.md "Grinding") ----------------------------------------------------------------------------
+// Up to this many bits the provers search on the calling thread (one thread per proof in the batch prover): below it a launch
+// round trip costs more than the search: one host thread 15 us at g = 10 and 99 us at g = 12, a device search ~20 us for any
+// g <= 12 (profiles/grind_bench.json, small_g).  Results are identical either way.
+constexpr uint32_t kGrindHostMaxBits = 10;
+struct Grinder;   // device search state: a stream, a pinned mailbox, one best word per job
+// stream: the caller's stream (null: a stream of its own); max_jobs: states one grind_device call may search for
+int grinder_create(int device, void* stream, uint32_t max_jobs, Grinder** out);
+void grinder_destroy(Grinder* g);
+// the smallest nonce >= start for each of `count` 32-byte states, in one launch per chunk for all unfinished states
+int grind_device(Grinder* g, const uint8_t* states, size_t count, uint32_t bits, uint64_t start, uint64_t* nonces_out);
+// the same search on `threads` (<= 16) host threads; 1 = the calling thread alone
+int grind_host(const uint8_t state[32], uint32_t bits, uint64_t start, uint32_t threads, uint64_t* nonce_out);
+// the prover's step after the free term: the nonce for ch.state (host up to kGrindHostMaxBits or without a grinder, else the
+// device), committed to ch
+int grind_channel(Grinder* g, Channel& ch, uint32_t bits, uint64_t* nonce_out);
 
 }  // namespace impl
 }  // namespace zk

@@ -60,11 +60,39 @@ struct Channel {
 
 // q = number of decommitment queries (1 = the reference's format, prover.rs:263; q > 1: SURVEY.md 8f
 // item 1 -- the q raw indices are drawn in a row, then each query's openings are committed in turn).
-inline size_t proof_data_len(uint32_t log_n, uint32_t log_b, uint32_t q = 1) {
+// grind = proof-of-work bits (DESIGN.md "Grinding"): g > 0 puts the 8-byte nonce between the free term and the query raws.
+inline size_t proof_data_len(uint32_t log_n, uint32_t log_b, uint32_t q = 1, uint32_t grind = 0) {
     size_t L = log_n + log_b, R = log_n;
     size_t per_query = 4 + 4 * (4 + 8 + 32 * L);
     for (size_t i = 0; i < R; ++i) per_query += 8 + 2 * (8 + 32 * (L - i));
-    return 32 + 12 + 32 + R * 36 + 4 + (size_t)q * per_query;
+    return 32 + 12 + 32 + R * 36 + 4 + (grind ? 8 : 0) + (size_t)q * per_query;
+}
+
+// ---- grinding (DESIGN.md "Grinding"; the reference has none) -------------------------------------------------------------
+// After the free term, with channel state S, the prover commits le64(w) for the smallest w >= 0 such that SHA-256(S || le64(w))
+// starts with g zero bits (MSB-first from byte 0, as get_u32 reads the state).  The commit itself computes that hash, so the
+// bits are those of the channel state right after the nonce is committed.
+constexpr uint32_t kMaxGrindBits = 32;
+constexpr uint64_t kGrindLimit = (uint64_t)1 << 44;      // a search gives up after this many nonces
+// Digest word 0 of SHA-256(state || le64(w)): one compression of a single block.
+inline uint32_t grind_word0(const uint8_t state[32], uint64_t w) {
+    uint32_t blk[16] = {0};
+    for (int i = 0; i < 8; ++i)
+        blk[i] = ((uint32_t)state[4 * i] << 24) | ((uint32_t)state[4 * i + 1] << 16) | ((uint32_t)state[4 * i + 2] << 8) | state[4 * i + 3];
+    blk[8] = __builtin_bswap32((uint32_t)w);
+    blk[9] = __builtin_bswap32((uint32_t)(w >> 32));
+    blk[10] = 0x80000000u;
+    blk[15] = 320u;                                       // 40 bytes
+    uint32_t st[8];
+    for (int i = 0; i < 8; ++i) st[i] = SHA_IV[i];
+    host_sha_compress(st, blk);
+    return st[0];
+}
+inline bool grind_word_ok(uint32_t word0, uint32_t bits) { return bits == 0 || (word0 >> (32 - bits)) == 0; }
+inline void grind_commit(Channel& ch, uint64_t w) {
+    uint8_t b[8];
+    for (int i = 0; i < 8; ++i) b[i] = (uint8_t)(w >> (8 * i));   // bincode u64
+    ch.commit_bytes(b, 8);
 }
 
 // Merkle hash on the host (verifier): hash 0 = SHA-256 (merkle.rs:30-34, :42-45), 1 = field-native (fieldhash.hpp)
@@ -105,8 +133,11 @@ inline void compute_root_from_path(uint32_t element, size_t index, const uint8_t
 }
 
 // proof.rs:15-149 with the literals generalised.  Returns 0 or the negative index of the failed check.
-inline int verify_proof(const uint8_t* data, size_t len, uint32_t log_n, uint32_t log_b, uint32_t public_last, int hash = 0, uint32_t q = 1) {
-    if (log_n < 2 || log_b < 1 || log_n + log_b > 30 || q < 1 || q > 64) return -1;
+// grind > 0: the nonce after the free term is skipped.  Its work is a property of the Fiat-Shamir transcript, which only
+// verify_transcript replays; here the query raws are read from the proof (as the reference does), so checking it certifies nothing.
+inline int verify_proof(const uint8_t* data, size_t len, uint32_t log_n, uint32_t log_b, uint32_t public_last, int hash = 0, uint32_t q = 1,
+                        uint32_t grind = 0) {
+    if (log_n < 2 || log_b < 1 || log_n + log_b > 30 || q < 1 || q > 64 || grind > kMaxGrindBits) return -1;
     const size_t n = (size_t)1 << log_n, B = (size_t)1 << log_b, N = n << log_b, R = log_n, L = log_n + log_b;
     const uint8_t* p = data;
     size_t left = len;
@@ -135,6 +166,7 @@ inline int verify_proof(const uint8_t* data, size_t len, uint32_t log_n, uint32_
     roots[0] = take(32); betas[0] = 0;
     for (size_t i = 0; i < R; ++i) { betas[i + 1] = take32(); roots[i + 1] = take(32); }
     uint32_t free_term = take32();
+    if (grind) take(8);                                   // the nonce
     uint32_t test_raws[64];
     for (uint32_t k = 0; k < q; ++k) test_raws[k] = take32();
     const uint32_t g = root_of_unity(log_n), h = root_of_unity((uint32_t)L);
@@ -199,11 +231,13 @@ inline int verify_proof(const uint8_t* data, size_t len, uint32_t log_n, uint32_
 // (readme.md:1).  This replays the Fiat-Shamir channel over the proof bytes in the prover's commit
 // order (prover.rs:85, :163-165, :180, :200, :224, :254, :263, :274-277, :288), checks that every
 // challenge equals the one the transcript yields at that point and that the final state matches.
-// Returns 0, or -(1000 + k) for the k-th challenge / -1999 for the state.
-inline int verify_transcript(const uint8_t* data, size_t len, const uint8_t state[32], uint32_t log_n, uint32_t log_b, uint32_t q = 1) {
-    if (log_n < 2 || log_b < 1 || log_n + log_b > 30) return -1;
+// Returns 0, or -(1000 + k) for the k-th challenge / -1998 for a grinding nonce whose hash has fewer than `grind` leading zero
+// bits (checked after the betas and before the first query challenge; it does not advance k) / -1999 for the state.
+inline int verify_transcript(const uint8_t* data, size_t len, const uint8_t state[32], uint32_t log_n, uint32_t log_b, uint32_t q = 1,
+                             uint32_t grind = 0) {
+    if (log_n < 2 || log_b < 1 || log_n + log_b > 30 || grind > kMaxGrindBits) return -1;
     const size_t R = log_n, L = log_n + log_b;
-    if (q < 1 || q > 64 || len != proof_data_len(log_n, log_b, q)) return -1;
+    if (q < 1 || q > 64 || len != proof_data_len(log_n, log_b, q, grind)) return -1;
     Channel ch;
     const uint8_t* p = data;
     int k = 0;
@@ -224,6 +258,11 @@ inline int verify_transcript(const uint8_t* data, size_t len, const uint8_t stat
         commit(32);                                         // layer root
     }
     commit(4);                                              // free term
+    if (grind) {                                            // nonce: the commit is SHA-256(S || le64(w))
+        commit(8);
+        const uint32_t w0 = ((uint32_t)ch.state[0] << 24) | ((uint32_t)ch.state[1] << 16) | ((uint32_t)ch.state[2] << 8) | ch.state[3];
+        if (!grind_word_ok(w0, grind)) return -1998;
+    }
     for (uint32_t j = 0; j < q; ++j) if (!challenge()) return -(1000 + k);   // queries
     for (uint32_t j = 0; j < q; ++j) {
         for (int i = 0; i < 4; ++i) commit(4 + 8 + 32 * L);

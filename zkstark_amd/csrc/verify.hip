@@ -46,6 +46,8 @@ struct VerifyArgs {
     int32_t* tcode;             // [count] transcript result: 0, -(1000 + k), -1999
     uint32_t count, words, q, R, L, B, N;
     uint32_t log_n, h, gm1, gm2, gm3, inv2;
+    uint32_t gw;                // words of the grinding nonce after the free term: 0 or 2 (the query raws follow it)
+    uint32_t gmask;             // grinding: the state after the nonce commit must have (word 0 & gmask) == 0
     uint32_t qbase;             // first word of query 0's openings
     uint32_t per_q;             // words of one query's openings
 };
@@ -72,7 +74,7 @@ __device__ __forceinline__ uint32_t layer_word(const VerifyArgs& a, uint32_t qk,
     return a.qbase + qk * a.per_q + 4u * (3u + 8u * a.L) + 6u * k + 16u * (k * a.L - k * (k - 1u) / 2u);
 }
 __device__ __forceinline__ uint32_t query_tp(const VerifyArgs& a, const uint32_t* pr, uint32_t qk) {
-    return pr[20u + 9u * a.R + qk] % (a.N - 2u * a.B);                       // tp = test_raw % (N - 2B)
+    return pr[20u + 9u * a.R + a.gw + qk] % (a.N - 2u * a.B);                // tp = test_raw % (N - 2B)
 }
 
 // (1) layout + algebra: one lane per (proof, query).  Path counts, the cp0 relation (-2) and the R FRI relations (-(100 + k)).
@@ -222,8 +224,9 @@ __global__ void __launch_bounds__(kVerifyThreads) verify_transcript_kernel(Verif
 #pragma unroll
     for (int i = 0; i < 8; ++i) st[i] = 0u;
     const uint32_t R = a.R, L = a.L, q = a.q;
-    // steps: f root | 3 alphas | cp root | R x (beta, layer root) | free term | q query raws | q x (4 f paths, R layer pairs)
-    const uint32_t head = 6u + 2u * R + q;
+    // steps: f root | 3 alphas | cp root | R x (beta, layer root) | free term | [nonce] | q query raws | q x (4 f paths, R layer pairs)
+    const uint32_t gs = a.gw ? 1u : 0u;                   // the nonce step: a commit of 2 words, then the zero-bit test (-1998)
+    const uint32_t head = 6u + 2u * R + gs + q;
     const uint32_t steps = head + q * (4u + R);
     uint32_t cur = 0, k = 0;
     int32_t code = 0;
@@ -231,8 +234,8 @@ __global__ void __launch_bounds__(kVerifyThreads) verify_transcript_kernel(Verif
         bool chal;
         uint32_t nw;
         if (s < head) {
-            chal = (s >= 1u && s <= 3u) || (s >= 5u && s < 5u + 2u * R && ((s - 5u) & 1u) == 0u) || s >= 6u + 2u * R;
-            nw = chal ? 1u : (s == 5u + 2u * R ? 1u : 8u);
+            chal = (s >= 1u && s <= 3u) || (s >= 5u && s < 5u + 2u * R && ((s - 5u) & 1u) == 0u) || s >= 6u + 2u * R + gs;
+            nw = chal ? 1u : (s == 5u + 2u * R ? 1u : (gs && s == 6u + 2u * R) ? 2u : 8u);
         } else {
             const uint32_t t = (s - head) % (4u + R);
             chal = false;
@@ -244,6 +247,7 @@ __global__ void __launch_bounds__(kVerifyThreads) verify_transcript_kernel(Verif
         }
         commit_words(st, pr + cur, nw);
         cur += nw;
+        if (gs && s == 6u + 2u * R && (st[0] & a.gmask) != 0u) { code = -1998; break; }   // SHA-256(S || le64(w)) is the new state
     }
     if (code == 0) {
         bool same = true;
@@ -287,7 +291,7 @@ int32_t key_to_check(int32_t key, uint32_t R) {
 
 struct zk_verifier {
     int device = 0;
-    uint32_t log_n = 0, log_b = 0, queries = 1;
+    uint32_t log_n = 0, log_b = 0, queries = 1, grind = 0;
     int hash = ZK_HASH_SHA256;
     hipStream_t stream = nullptr, tstream = nullptr;   // paths + algebra; transcript (runs beside them)
     hipEvent_t ev_in = nullptr, ev_t = nullptr;
@@ -344,7 +348,9 @@ int verifier_chunk(zk_verifier* v, const uint8_t* proofs, size_t stride, size_t 
     a.h = root_of_unity(L);
     const uint32_t g = root_of_unity(log_n);
     a.gm1 = invmod(g); a.gm2 = mulmod(a.gm1, a.gm1); a.gm3 = mulmod(a.gm2, a.gm1); a.inv2 = invmod(2);
-    a.qbase = 20u + 9u * R + q;
+    a.gw = v->grind ? 2u : 0u;
+    a.gmask = v->grind ? ~0u << (32u - v->grind) : 0u;
+    a.qbase = 20u + 9u * R + a.gw + q;
     a.per_q = 4u * (3u + 8u * L);
     for (uint32_t i = 0; i < R; ++i) a.per_q += 6u + 16u * (L - i);
 
@@ -380,7 +386,7 @@ int verifier_chunk(zk_verifier* v, const uint8_t* proofs, size_t stride, size_t 
     for (size_t i = 0; i < count; ++i) {
         int32_t c;
         if (states && tcode[i]) c = tcode[i];
-        else if (malformed[i]) c = verify_proof(proofs + i * stride, len, log_n, log_b, public_last[i], v->hash, q);   // garbage only
+        else if (malformed[i]) c = verify_proof(proofs + i * stride, len, log_n, log_b, public_last[i], v->hash, q, v->grind);   // garbage only
         else c = best[i] == kNoFailure ? 0 : key_to_check(best[i], R);
         checks_out[i] = c;
     }
@@ -391,15 +397,19 @@ int verifier_chunk(zk_verifier* v, const uint8_t* proofs, size_t stride, size_t 
 
 extern "C" {
 
-int zk_verify_check(const uint8_t* proof, size_t len, const uint8_t* state, uint32_t log_n, uint32_t log_b, uint32_t public_last,
-                    int hash_kind, uint32_t n_queries, int32_t* check_out) {
+int zk_verify_grind(const uint8_t* proof, size_t len, const uint8_t* state, uint32_t log_n, uint32_t log_b, uint32_t public_last,
+                    int hash_kind, uint32_t n_queries, uint32_t grind_bits, int32_t* check_out) {
     if (!proof || !check_out) return fail(ZK_ERR_INVALID, "zk_verify_check: null argument");
     if (hash_kind != ZK_HASH_SHA256 && hash_kind != ZK_HASH_FIELD) return fail(ZK_ERR_INVALID, "zk_verify_check: unknown hash %d", hash_kind);
-    int rc = state ? verify_transcript(proof, len, state, log_n, log_b, n_queries) : 0;   // as zk_verify_queries: the replay first
-    if (!rc) rc = verify_proof(proof, len, log_n, log_b, public_last, hash_kind, n_queries);
+    int rc = state ? verify_transcript(proof, len, state, log_n, log_b, n_queries, grind_bits) : 0;   // as zk_verify_queries: the replay first
+    if (!rc) rc = verify_proof(proof, len, log_n, log_b, public_last, hash_kind, n_queries, grind_bits);
     *check_out = rc;
     if (rc) return fail(ZK_ERR_VERIFY, "proof rejected at check %d", rc);
     return ZK_OK;
+}
+int zk_verify_check(const uint8_t* proof, size_t len, const uint8_t* state, uint32_t log_n, uint32_t log_b, uint32_t public_last,
+                    int hash_kind, uint32_t n_queries, int32_t* check_out) {
+    return zk_verify_grind(proof, len, state, log_n, log_b, public_last, hash_kind, n_queries, 0, check_out);
 }
 
 int zk_verifier_destroy(zk_verifier* v) {
@@ -448,6 +458,13 @@ int zk_verifier_set_queries(zk_verifier* v, uint32_t n_queries) {
     return ZK_OK;
 }
 
+int zk_verifier_set_grinding(zk_verifier* v, uint32_t grind_bits) {
+    if (!v) return fail(ZK_ERR_INVALID, "null verifier");
+    if (grind_bits > kMaxGrindBits) return fail(ZK_ERR_INVALID, "zk_verifier_set_grinding: need grind_bits <= %u (got %u)", kMaxGrindBits, grind_bits);
+    v->grind = grind_bits;
+    return ZK_OK;
+}
+
 int zk_verifier_set_hash(zk_verifier* v, int hash_kind) {
     if (!v) return fail(ZK_ERR_INVALID, "null verifier");
     if (hash_kind != ZK_HASH_SHA256 && hash_kind != ZK_HASH_FIELD) return fail(ZK_ERR_INVALID, "zk_verifier_set_hash: unknown hash %d", hash_kind);
@@ -460,7 +477,7 @@ int zk_verifier_run(zk_verifier* v, const uint8_t* proofs, size_t stride, size_t
     if (!v) return fail(ZK_ERR_INVALID, "null verifier");
     if (count == 0) return ZK_OK;
     if (!proofs || !public_last || !checks_out) return fail(ZK_ERR_INVALID, "zk_verifier_run: null argument");
-    const size_t len = proof_data_len(v->log_n, v->log_b, v->queries);
+    const size_t len = proof_data_len(v->log_n, v->log_b, v->queries, v->grind);
     if (stride < len) return fail(ZK_ERR_INVALID, "zk_verifier_run: stride %zu < proof length %zu", stride, len);
     if (count > SIZE_MAX / stride) return fail(ZK_ERR_INVALID, "zk_verifier_run: count * stride overflows");
     HIPCHK(hipSetDevice(v->device));

@@ -110,7 +110,9 @@ struct zk_ctx {
     bool tail = false;                  // FRI-tail context (zk_tail_*): no trace / LDE / composition
     uint32_t hinv_host = 0;             // 1 / h (the host-side FRI rounds step through its powers)
     uint32_t queries = 1;               // decommitment queries (1 = the reference, prover.rs:263)
-    int hash = 0;                       // Merkle hash: 0 = SHA-256 (reference), 1 = field-native (configs[4])
+    uint32_t grind = 0;                 // proof-of-work bits before the query draw (zk_ctx_set_grinding; 0 = none, the reference)
+    Grinder* grinder = nullptr;         // device search on this context's stream (created by the setter when grind > kGrindHostMaxBits)
+    int hash = 0;                      // Merkle hash: 0 = SHA-256 (reference), 1 = field-native (configs[4])
     // opt-in reference self-checks (zk_ctx_set_checks; prover.rs:64-66, :148-159, :169, :228-251)
     bool checks = false;
     uint32_t* d_check = nullptr;        // N words of scratch + 2 result words
@@ -522,7 +524,7 @@ int prove_resident(zk_ctx* c, Channel& ch) {
     };
     const uint32_t R = c->R;
     const size_t B = c->B, N = c->N;
-    ch.data.reserve(ch.data.size() + proof_data_len(c->log_n, c->log_b, c->queries));
+    ch.data.reserve(ch.data.size() + proof_data_len(c->log_n, c->log_b, c->queries, c->grind));
     uint8_t root[32];
     int rc;
     memset(&c->info, 0, sizeof c->info);
@@ -569,6 +571,13 @@ int prove_resident(zk_ctx* c, Channel& ch) {
     if ((rc = last_layer_value(c, &free_term))) return rc;
     c->info.free_term = free_term;
     ch.commit_u32(free_term);                             // prover.rs:254
+    if (c->grind) {                                       // proof of work on the state after the free term (DESIGN.md "Grinding")
+        uint64_t w = 0;
+        if ((rc = grind_channel(c->grinder, ch, c->grind, &w))) return rc;
+        c->info.grind_bits = c->grind;
+        c->info.grind_nonce = w;
+        lap("grind");
+    }
     const uint32_t Q = c->queries;
     uint32_t qraws[64];
     for (uint32_t k = 0; k < Q; ++k) qraws[k] = ch.get_u32();   // prover.rs:263 (x Q)
@@ -863,6 +872,7 @@ int zk_ctx_destroy(zk_ctx* c) {
     if (c->h_gate) (void)hipHostFree(c->h_gate);
     if (c->h_dyn) (void)hipHostFree(c->h_dyn);
     if (c->h_stage) (void)hipHostFree(c->h_stage);
+    grinder_destroy(c->grinder);
     collect_kernel_stats(c);
     delete c->pool;
     for (hipEvent_t e : c->prof.pool) (void)hipEventDestroy(e);
@@ -897,6 +907,17 @@ int zk_ctx_set_queries(zk_ctx* c, uint32_t n_queries) {
     if (!c) return fail(ZK_ERR_INVALID, "null context");
     if (n_queries < 1 || n_queries > kMaxQueries) return fail(ZK_ERR_INVALID, "zk_ctx_set_queries: need 1 <= n_queries <= %u", kMaxQueries);
     c->queries = n_queries;
+    return ZK_OK;
+}
+int zk_ctx_set_grinding(zk_ctx* c, uint32_t grind_bits) {
+    if (!c) return fail(ZK_ERR_INVALID, "null context");
+    if (c->tail) return fail(ZK_ERR_STATE, "zk_ctx_set_grinding: FRI-tail context");
+    if (grind_bits > kMaxGrindBits) return fail(ZK_ERR_INVALID, "zk_ctx_set_grinding: need grind_bits <= %u (got %u)", kMaxGrindBits, grind_bits);
+    if (grind_bits > kGrindHostMaxBits && !c->grinder) {  // allocated here, not inside the first proof
+        HIPCHK(hipSetDevice(c->device));
+        if (int rc = grinder_create(c->device, c->stream, 1, &c->grinder)) return rc;
+    }
+    c->grind = grind_bits;
     return ZK_OK;
 }
 
@@ -1176,6 +1197,9 @@ int zk_verify_strict(const uint8_t* proof, size_t len, const uint8_t state[32], 
 size_t zk_proof_size(size_t data_len) { return 48 + data_len; }   // proof.rs:151-154: size_of::<Proof>() = 32 + 16
 size_t zk_proof_data_len(uint32_t log_n, uint32_t log_b) { return proof_data_len(log_n, log_b); }
 size_t zk_proof_data_len_queries(uint32_t log_n, uint32_t log_b, uint32_t n_queries) { return proof_data_len(log_n, log_b, n_queries); }
+size_t zk_proof_data_len_grind(uint32_t log_n, uint32_t log_b, uint32_t n_queries, uint32_t grind_bits) {
+    return proof_data_len(log_n, log_b, n_queries, grind_bits);
+}
 
 int zk_compute_root_from_path_ex(uint32_t element, size_t index, const uint8_t* path, size_t path_len, uint8_t out[32], int hash_kind) {
     if ((!path && path_len) || !out || path_len > 62 || (hash_kind != 0 && hash_kind != 1))

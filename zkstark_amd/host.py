@@ -144,23 +144,29 @@ class Channel:
 class Proof:
     """proof.rs:5-154.  verify() raises ZkError where the reference panics."""
 
-    def __init__(self, state, data, log_n=10, log_blowup=3, public_last=2338775057, hash="sha256", queries=1):   # proof.rs:11
+    def __init__(self, state, data, log_n=10, log_blowup=3, public_last=2338775057, hash="sha256", queries=1, grind_bits=0):   # proof.rs:11
         self.state, self.data = bytes(state), bytes(data)
         self.log_n, self.log_blowup, self.public_last = log_n, log_blowup, public_last
-        self.hash, self.queries = hash, queries
+        self.hash, self.queries, self.grind_bits = hash, queries, grind_bits
 
     def verify(self, strict=False):                  # proof.rs:15
         """strict=True also replays the channel: challenges must come from the transcript and `state`
-        must be its final state (the reference trusts the proof for both, proof.rs:22-37)."""
+        must be its final state (the reference trusts the proof for both, proof.rs:22-37); with grind_bits > 0 it also
+        checks the proof-of-work nonce."""
+        if self.grind_bits:
+            out = C.c_int32()
+            check(_lib.load().zk_verify_grind(self.data, len(self.data), self.state if strict else None, self.log_n, self.log_blowup,
+                                              self.public_last, HASHES[self.hash], self.queries, self.grind_bits, C.byref(out)))
+            return
         check(_lib.load().zk_verify_queries(self.data, len(self.data), self.state if strict else None, self.log_n,
                                             self.log_blowup, self.public_last, HASHES[self.hash], self.queries))
 
     def check(self, strict=False):
-        """The number of the check the CPU verifier stops at (zk_verify_check): 0 = accepted; otherwise what verify()'s
+        """The number of the check the CPU verifier stops at (zk_verify_grind): 0 = accepted; otherwise what verify()'s
         error names.  Never raises for a rejected proof."""
         out = C.c_int32()
-        rc = _lib.load().zk_verify_check(self.data, len(self.data), self.state if strict else None, self.log_n, self.log_blowup,
-                                         self.public_last, HASHES[self.hash], self.queries, C.byref(out))
+        rc = _lib.load().zk_verify_grind(self.data, len(self.data), self.state if strict else None, self.log_n, self.log_blowup,
+                                         self.public_last, HASHES[self.hash], self.queries, self.grind_bits, C.byref(out))
         if rc not in (_lib.ZK_OK, _ERR_VERIFY):
             check(rc)
         return out.value
@@ -229,9 +235,11 @@ def lde(trace, log_n, log_blowup, device=0):
 class Context:
     """Device-resident prover state for one (log_n, log_blowup): zk_ctx."""
 
-    def __init__(self, log_n=10, log_blowup=3, device=0, hash="sha256", queries=1, host_levels=None):
-        """host_levels: (top_log, tail_log) of zk_ctx_set_host_levels; None = the library default."""
+    def __init__(self, log_n=10, log_blowup=3, device=0, hash="sha256", queries=1, host_levels=None, grind_bits=0):
+        """host_levels: (top_log, tail_log) of zk_ctx_set_host_levels; None = the library default.  grind_bits: proof-of-work
+        bits before the query draw (zk_ctx_set_grinding; 0 = none)."""
         self.log_n, self.log_blowup, self.device, self.hash, self.queries = log_n, log_blowup, device, hash, queries
+        self.grind_bits = grind_bits
         self.n, self.B = 1 << log_n, 1 << log_blowup
         self.N, self.rounds = self.n * self.B, log_n
         self._h = C.c_void_p()
@@ -242,6 +250,8 @@ class Context:
             check(_lib.load().zk_ctx_set_queries(self._h, queries))
         if host_levels is not None:
             check(_lib.load().zk_ctx_set_host_levels(self._h, host_levels[0], host_levels[1]))
+        if grind_bits:
+            check(_lib.load().zk_ctx_set_grinding(self._h, grind_bits))
 
     def close(self):
         if getattr(self, "_h", None):
@@ -325,7 +335,7 @@ class Context:
 
     def prove(self, trace=None):
         """generate_proof as one C call (C++ host prover). trace=None: already uploaded."""
-        cap = _lib.load().zk_proof_data_len_queries(self.log_n, self.log_blowup, self.queries)
+        cap = _lib.load().zk_proof_data_len_grind(self.log_n, self.log_blowup, self.queries, self.grind_bits)
         buf = C.create_string_buffer(cap)
         st = C.create_string_buffer(32)
         n = C.c_size_t()
@@ -335,13 +345,15 @@ class Context:
             t = _u32arr(trace)
             check(_lib.load().zk_prove(self._h, _ptr(t), len(t), buf, cap, C.byref(n), st))
         info = self.last_transcript()
-        return Proof(st.raw, buf.raw[:n.value], self.log_n, self.log_blowup, info.public_last, self.hash, self.queries)
+        return Proof(st.raw, buf.raw[:n.value], self.log_n, self.log_blowup, info.public_last, self.hash, self.queries, self.grind_bits)
 
     def prove_channel(self, channel):
         """generate_proof(channel) (prover.rs:9) in one C call on the caller's Channel (zk_prove_channel): the
         resident trace is proved on top of whatever the channel already holds; returns channel.finalize(...)."""
         check(_lib.load().zk_prove_channel(self._h, channel._h))
-        return channel.finalize(self.log_n, self.log_blowup, self.last_transcript().public_last)
+        proof = channel.finalize(self.log_n, self.log_blowup, self.last_transcript().public_last)
+        proof.grind_bits = self.grind_bits
+        return proof
 
     def set_host_levels(self, top_log, tail_log):
         check(_lib.load().zk_ctx_set_host_levels(self._h, top_log, tail_log))
@@ -356,9 +368,24 @@ class Context:
         check(_lib.load().zk_ctx_set_checks(self._h, int(on)))
 
     def last_transcript(self):
+        """zk_transcript_info of the last proof: challenges, roots, and with grinding grind_bits and grind_nonce."""
         info = _lib.TranscriptInfo()
         check(_lib.load().zk_last_transcript(self._h, C.byref(info)))
         return info
+
+
+def grind(state, bits, start=0, device=0):
+    """zk_grind: the smallest nonce >= start whose SHA-256(state || le64(nonce)) begins with `bits` zero bits, searched on the GPU."""
+    out = C.c_uint64()
+    check(_lib.load().zk_grind(device, bytes(state), bits, start, C.byref(out)))
+    return out.value
+
+
+def grind_host(state, bits, start=0, threads=16):
+    """zk_grind_host: the same search on <= 16 host threads (the same nonce)."""
+    out = C.c_uint64()
+    check(_lib.load().zk_grind_host(bytes(state), bits, start, threads, C.byref(out)))
+    return out.value
 
 
 def prove_many(ctxs):
@@ -366,7 +393,7 @@ def prove_many(ctxs):
     library (zk_prove_many): returns the proofs in order."""
     ctxs = list(ctxs)
     c0 = ctxs[0]
-    stride = max(_lib.load().zk_proof_data_len_queries(c.log_n, c.log_blowup, c.queries) for c in ctxs)
+    stride = max(_lib.load().zk_proof_data_len_grind(c.log_n, c.log_blowup, c.queries, c.grind_bits) for c in ctxs)
     handles = (C.c_void_p * len(ctxs))(*[c._h for c in ctxs])
     data = np.zeros((len(ctxs), stride), dtype=np.uint8)
     lens = (C.c_size_t * len(ctxs))()
@@ -375,7 +402,7 @@ def prove_many(ctxs):
     out = []
     for i, c in enumerate(ctxs):
         out.append(Proof(states[i].tobytes(), data[i, :lens[i]].tobytes(), c.log_n, c.log_blowup, c.last_transcript().public_last,
-                         c.hash, c.queries))
+                         c.hash, c.queries, c.grind_bits))
     return out
 
 
@@ -383,8 +410,9 @@ class BatchContext:
     """2^log_batch proofs of one size in lockstep (zk_batch_*): every stage is one
     launch over the whole batch; each proof has its own channel and is byte-identical to Context.prove()."""
 
-    def __init__(self, log_n=10, log_blowup=3, log_batch=4, device=0, hash="sha256", queries=1):
+    def __init__(self, log_n=10, log_blowup=3, log_batch=4, device=0, hash="sha256", queries=1, grind_bits=0):
         self.log_n, self.log_blowup, self.log_batch, self.hash, self.queries = log_n, log_blowup, log_batch, hash, queries
+        self.grind_bits = grind_bits
         self.n, self.batch = 1 << log_n, 1 << log_batch
         self._h = C.c_void_p()
         check(_lib.load().zk_batch_create(device, log_n, log_blowup, log_batch, C.byref(self._h)))
@@ -392,6 +420,8 @@ class BatchContext:
             check(_lib.load().zk_batch_set_hash(self._h, HASHES[hash]))
         if queries != 1:
             check(_lib.load().zk_batch_set_queries(self._h, queries))
+        if grind_bits:
+            check(_lib.load().zk_batch_set_grinding(self._h, grind_bits))
 
     def close(self):
         if getattr(self, "_h", None):
@@ -427,7 +457,7 @@ class BatchContext:
 
     def prove_raw(self):
         """Returns (proof bytes [batch][len] as a uint8 array, states [batch][32])."""
-        plen = _lib.load().zk_proof_data_len_queries(self.log_n, self.log_blowup, self.queries)
+        plen = _lib.load().zk_proof_data_len_grind(self.log_n, self.log_blowup, self.queries, self.grind_bits)
         data = np.zeros((self.batch, plen), dtype=np.uint8)
         states = np.zeros((self.batch, 32), dtype=np.uint8)
         check(_lib.load().zk_batch_prove(self._h, data.ctypes.data_as(C.c_void_p), plen, states.ctypes.data_as(C.c_void_p)))
@@ -436,8 +466,8 @@ class BatchContext:
     def prove(self):
         data, states = self.prove_raw()
         last = self.public_last()
-        return [Proof(states[p].tobytes(), data[p].tobytes(), self.log_n, self.log_blowup, int(last[p]), self.hash, self.queries)
-                for p in range(self.batch)]
+        return [Proof(states[p].tobytes(), data[p].tobytes(), self.log_n, self.log_blowup, int(last[p]), self.hash, self.queries,
+                      self.grind_bits) for p in range(self.batch)]
 
 
 _ERR_VERIFY = -6
@@ -447,14 +477,16 @@ class Verifier:
     """Many proofs of one size checked at once on the GPU (zk_verifier_*).  Every result is the number Proof.check gives for
     that proof: 0 = accepted, otherwise the CPU verifier's check number."""
 
-    def __init__(self, log_n, log_blowup, device=0, hash="sha256", queries=1):
-        self.log_n, self.log_blowup, self.hash, self.queries = log_n, log_blowup, hash, queries
+    def __init__(self, log_n, log_blowup, device=0, hash="sha256", queries=1, grind_bits=0):
+        self.log_n, self.log_blowup, self.hash, self.queries, self.grind_bits = log_n, log_blowup, hash, queries, grind_bits
         self._h = C.c_void_p()
         check(_lib.load().zk_verifier_create(device, log_n, log_blowup, C.byref(self._h)))
         if hash != "sha256":
             check(_lib.load().zk_verifier_set_hash(self._h, HASHES.get(hash, -1)))   # an unknown name: ZK_ERR_INVALID
         if queries != 1:
             check(_lib.load().zk_verifier_set_queries(self._h, queries))
+        if grind_bits:
+            check(_lib.load().zk_verifier_set_grinding(self._h, grind_bits))
 
     def close(self):
         if getattr(self, "_h", None):
@@ -468,7 +500,7 @@ class Verifier:
 
     @property
     def proof_len(self):
-        return _lib.load().zk_proof_data_len_queries(self.log_n, self.log_blowup, self.queries)
+        return _lib.load().zk_proof_data_len_grind(self.log_n, self.log_blowup, self.queries, self.grind_bits)
 
     def verify_raw(self, data, public_last, states=None):
         """data: [count, stride] uint8 (stride >= proof_len; BatchContext.prove_raw()'s array as it is), public_last: [count],
