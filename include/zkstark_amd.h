@@ -189,6 +189,8 @@ int zk_layer_read(zk_ctx *ctx, uint32_t layer, size_t offset, size_t count, uint
 int zk_layer_write(zk_ctx *ctx, uint32_t layer, size_t offset, size_t count, const uint32_t *in);
 /* Index<usize> for Merkle (merkle.rs:74-79). */
 int zk_merkle_node(zk_ctx *ctx, uint32_t tree, size_t index, uint8_t out[32]);
+/* Nodes [first, first + count) of a tree in one copy, 32 bytes each as zk_merkle_node (out: 32 * count bytes). */
+int zk_merkle_nodes(zk_ctx *ctx, uint32_t tree, size_t first, size_t count, uint8_t *out);
 /* Merkle::trace (merkle.rs:54-71): sibling of the leaf first, child of the root last.
  * out holds 32 * log2(m) bytes; *path_len receives log2(m). */
 int zk_merkle_path(zk_ctx *ctx, uint32_t tree, size_t leaf, uint8_t *out, size_t *path_len);
@@ -285,6 +287,9 @@ int zk_batch_public_last(const zk_batch *b, uint32_t *out);
 /* proofs_out: [batch][stride] bytes, stride >= zk_proof_data_len(log_n, log_blowup); states_out:
  * [batch][32] (with q queries: zk_proof_data_len_queries).  Fails with ZK_ERR_CHECK, naming the proof, if a trace breaks the constraints. */
 int zk_batch_prove(zk_batch *b, uint8_t *proofs_out, size_t stride, uint8_t *states_out);
+/* Nodes [first, first + count) of batch tree `tree` (a heap over batch * m_l leaves; proof p's tree is the subtree under node
+ * 2^log_batch - 1 + p), 32 bytes each as zk_merkle_node.  Complete after zk_batch_prove. */
+int zk_batch_merkle_nodes(zk_batch *b, uint32_t tree, size_t first, size_t count, uint8_t *out);
 
 /* ---- proof: proof.rs ------------------------------------------------------- */
 /* Proof::verify (proof.rs:15-149) on the CPU (many proofs at once on the GPU: zk_verifier_run below), generalised from the literals

@@ -206,6 +206,18 @@ def test_context_argument_checks(zk):
         assert e.value.code == -1
 
 
+def test_bulk_node_reads_refuse_bad_arguments(zk):
+    """zk_merkle_nodes / zk_batch_merkle_nodes refuse a missing handle or output before touching the device (the range checks
+    need a context: tests/test_gpu_merkle_plans.py)."""
+    from zkstark_amd import _lib
+    lib = _lib.load()
+    buf = C.create_string_buffer(64)
+    for fn in (lib.zk_merkle_nodes, lib.zk_batch_merkle_nodes):
+        assert fn(None, 0, 0, 1, buf) == -1
+        assert fn(None, 0, 0, 0, None) == -1
+        assert buf.raw == bytes(64)
+
+
 def test_strict_verifier_replays_the_transcript(zk, orc):
     """challenges must be the transcript's, Proof.state must be the final state."""
     import struct as st

@@ -151,6 +151,7 @@ SYMBOLS = {
     "zk_layer_read": (_int, [_vp, _u32, _sz, _sz, _vp]),
     "zk_layer_write": (_int, [_vp, _u32, _sz, _sz, _vp]),
     "zk_merkle_node": (_int, [_vp, _u32, _sz, _vp]),
+    "zk_merkle_nodes": (_int, [_vp, _u32, _sz, _sz, _vp]),
     "zk_merkle_path": (_int, [_vp, _u32, _sz, _vp, C.POINTER(_sz)]),
     "zk_prove_resident": (_int, [_vp, _vp, _sz, C.POINTER(_sz), _vp]),
     "zk_prove_channel": (_int, [_vp, _vp]),
@@ -182,6 +183,7 @@ SYMBOLS = {
     "zk_batch_gen_fibsq": (_int, [_vp, _vp, _vp]),
     "zk_batch_public_last": (_int, [_vp, _vp]),
     "zk_batch_prove": (_int, [_vp, _vp, _sz, _vp]),
+    "zk_batch_merkle_nodes": (_int, [_vp, _u32, _sz, _sz, _vp]),
     "zk_committer_create": (_int, [_int, C.POINTER(_vp)]),
     "zk_committer_destroy": (_int, [_vp]),
     "zk_committer_set_top": (_int, [_vp, _u32]),

@@ -383,6 +383,18 @@ int zk_batch_public_last(const zk_batch* b, uint32_t* out) {
     return ZK_OK;
 }
 
+// Nodes [first, first + count) of batch tree `tree` (a heap over batch * m_l leaves; proof p's tree is the subtree under node
+// 2^log_batch - 1 + p).  Complete after zk_batch_prove: its last launches copy the host-built levels in (scatter_kernel).
+int zk_batch_merkle_nodes(zk_batch* b, uint32_t tree, size_t first, size_t count, uint8_t* out) {
+    if (!b || (!out && count)) return fail(ZK_ERR_INVALID, "zk_batch_merkle_nodes: null argument");
+    if (b->single) return zk_merkle_nodes(b->single, tree, first, count, out);
+    const size_t heap = tree <= b->R + 1 ? 2 * blayer_size(b, tree) * b->batch - 1 : 0;
+    if (tree > b->R + 1 || first > heap || count > heap - first) return fail(ZK_ERR_INVALID, "zk_batch_merkle_nodes: out of range");
+    BusyScope busy(b);
+    if (!busy.mine) return fail(ZK_ERR_STATE, "zk_batch_merkle_nodes: a zk_batch_prove is running on this batch");
+    return merkle_nodes_to_host(b->device, b->stream, b->d_trees + b->tree_off[tree], first, count, out);
+}
+
 // generate_proof (prover.rs:9-293) for every resident trace.  proofs_out: [batch][stride] bytes, stride >=
 // zk_proof_data_len(log_n, log_b); states_out: [batch][32] (Channel.state of each proof, proof.rs:6).
 int zk_batch_prove(zk_batch* b, uint8_t* proofs_out, size_t stride, uint8_t* states_out) {

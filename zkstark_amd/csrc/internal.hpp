@@ -188,6 +188,8 @@ int tail_open_begin(zk_ctx* tail, size_t x);
 int tail_open_end(zk_ctx* tail, uint32_t* vals_out, uint8_t* paths_out);
 // merkle.rs:54-71: node indices of the authentication path of `leaf` in a tree of m leaves
 void path_nodes(size_t m, size_t leaf, std::vector<size_t>& out);
+// zk_merkle_nodes / zk_batch_merkle_nodes: nodes [first, first + count) of the heap at d_heap, one copy on `s`, 32 bytes each
+int merkle_nodes_to_host(int device, hipStream_t s, const uint32_t* d_heap, size_t first, size_t count, uint8_t* out);
 
 }  // namespace impl
 }  // namespace zk

@@ -665,6 +665,19 @@ int tail_open_end(zk_ctx* c, uint32_t* vals_out, uint8_t* paths_out) {
     for (size_t i = 0; i < c->fetch_nodes.size(); ++i) digest_words_to_bytes(c->fetch_nodes[i], paths_out + 32 * i);
     return ZK_OK;
 }
+// Nodes [first, first + count) of a tree in one copy; the state words land in `out` and are turned into bytes in place.
+int merkle_nodes_to_host(int device, hipStream_t s, const uint32_t* d_heap, size_t first, size_t count, uint8_t* out) {
+    if (!count) return ZK_OK;
+    HIPCHK(hipSetDevice(device));
+    HIPCHK(hipMemcpyAsync(out, d_heap + first * 8, count * 32, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    for (size_t i = 0; i < count; ++i) {
+        uint32_t w[8];
+        memcpy(w, out + 32 * i, 32);
+        digest_words_to_bytes(w, out + 32 * i);
+    }
+    return ZK_OK;
+}
 }  // namespace impl
 }  // namespace zk
 
@@ -1085,6 +1098,15 @@ int zk_merkle_node(zk_ctx* c, uint32_t tree, size_t index, uint8_t out[32]) {
     HIPCHK(hipStreamSynchronize(c->stream));
     digest_words_to_bytes(c->h_small, out);
     return ZK_OK;
+}
+
+int zk_merkle_nodes(zk_ctx* c, uint32_t tree, size_t first, size_t count, uint8_t* out) {
+    if (!c || (!out && count)) return fail(ZK_ERR_INVALID, "zk_merkle_nodes: null argument");
+    if (tree > c->R + 1 || first > 2 * layer_size(c, tree) - 1 || count > 2 * layer_size(c, tree) - 1 - first)
+        return fail(ZK_ERR_INVALID, "zk_merkle_nodes: out of range");
+    HIPCHK(hipSetDevice(c->device));
+    if (int prc = settle_pending(c)) return prc;
+    return merkle_nodes_to_host(c->device, c->stream, c->d_trees + c->tree_off[tree], first, count, out);
 }
 
 int zk_merkle_path(zk_ctx* c, uint32_t tree, size_t leaf, uint8_t* out, size_t* path_len) {

@@ -232,6 +232,14 @@ def lde(trace, log_n, log_blowup, device=0):
     return out
 
 
+def _read_nodes(fn, handle, tree, heap, first, count):
+    if count is None:
+        count = max(heap - first, 0)
+    out = np.zeros((count, 32), dtype=np.uint8)
+    check(fn(handle, tree, first, count, out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
 class Context:
     """Device-resident prover state for one (log_n, log_blowup): zk_ctx."""
 
@@ -326,6 +334,10 @@ class Context:
         out = C.create_string_buffer(32)
         check(_lib.load().zk_merkle_node(self._h, tree, index, out))
         return out.raw
+
+    def merkle_nodes(self, tree, first=0, count=None):
+        """Nodes [first, first + count) of tree `tree` (default: the whole heap) as a [count, 32] uint8 array, in one copy."""
+        return _read_nodes(_lib.load().zk_merkle_nodes, self._h, tree, 2 * self.layer_size(tree) - 1, first, count)
 
     def merkle_path(self, tree, leaf):
         buf = C.create_string_buffer(32 * 64)
@@ -454,6 +466,11 @@ class BatchContext:
         out = np.zeros(self.batch, dtype=np.uint32)
         check(_lib.load().zk_batch_public_last(self._h, _ptr(out)))
         return out
+
+    def merkle_nodes(self, tree, first=0, count=None):
+        """Nodes of batch tree `tree`: a heap over batch * m_l leaves whose node 2^log_batch - 1 + p roots proof p's tree."""
+        m = (1 << (self.log_n + self.log_blowup)) >> max(tree - 1, 0)
+        return _read_nodes(_lib.load().zk_batch_merkle_nodes, self._h, tree, 2 * m * self.batch - 1, first, count)
 
     def prove_raw(self):
         """Returns (proof bytes [batch][len] as a uint8 array, states [batch][32])."""
