@@ -160,6 +160,28 @@ int zk_ctx_get_host_levels(const zk_ctx *ctx, uint32_t *top_log, uint32_t *tail_
  * holds the hardware queue another context's stream may be mapped to.  zk_ctx_get_early_launch: 1 when on AND supported. */
 int zk_ctx_set_early_launch(zk_ctx *ctx, int on);
 int zk_ctx_get_early_launch(const zk_ctx *ctx);
+/* FRI folding factor 2^fold_log between commitments, fold_log in 1..3 (default 1 = the reference, which folds by two and commits
+ * every layer: prover.rs:198-225; a proof made with the default is byte for byte what it was).  The log_n rounds are taken in groups
+ * of fold_log (the last may be shorter): a group draws ONE challenge beta (prover.rs:200), its output is that many successive
+ * folds (polynomial.rs:385 + prover.rs:204-211) with beta, beta^2, beta^4, computed in one pass, and only that output is committed
+ * (prover.rs:214, :224), under the reference's layer id (1 + round).  Per query a group opens the 2^steps coset values of its input
+ * layer and their paths -- the tuple of prover.rs:280-289 widened -- and the verifier (proof.rs:101-148 widened) folds them down
+ * to the next group's value.  A query still tests one coset per committed layer, so the conjectured security per query is
+ * unchanged; the price is proof size (leaves stay one value wide, so 2^steps paths per group): at domain 2^24 with one query
+ * 23 280 / 23 560 / 31 008 bytes for fold_log 1 / 2 / 3, with 32 queries 719 044 / 739 164 / 981 964 (zk_proof_data_len_fold).
+ * Trees per 2^24 proof: 23 / 13 / 9.  Honoured by zk_prove, zk_prove_resident, zk_prove_channel and zk_prove_many with every other
+ * option.  With fold_log > 1: every FRI layer is folded on the device (the host FRI tail of zk_ctx_set_host_levels is left out;
+ * the tree-top hand-over works as usual and results are identical for every setting); early launch is not used and
+ * zk_ctx_get_early_launch answers 0; zk_last_transcript has beta_raw[r0] = the challenge of the group that starts at round r0 and
+ * roots[id] for committed ids, the rest zero; zk_layer_read / zk_merkle_node(s) / zk_merkle_path of an id the proof did not
+ * materialise return ZK_ERR_STATE.  Measured, K = 1, 2, 3 interleaved in one process (profiles/fold_arity_bench.txt): 5.69 / 4.41 /
+ * 3.95 ms per proof at domain 2^24, 0.952 / 0.771 / 0.640 ms at 2^20.  NOT faster everywhere: at the reference's size (domain 2^13)
+ * 0.274 / 0.296 / 0.264 ms -- fold_log 2 is 8 % SLOWER than the default there and fold_log 3 only 4 % faster, because the default
+ * folds the small layers on the host thread and fuses every fold into its leaf hashing, while a folded proof pays one fold launch
+ * and one tree launch per group (docs/LOG.md "Folding factor").
+ * zk_batch_*, zk_shard_* / zk_tail_* and zk_verifier_* stay at factor 2. */
+int zk_ctx_set_fold(zk_ctx *ctx, uint32_t fold_log);
+uint32_t zk_ctx_get_fold(const zk_ctx *ctx);
 /* The HIP stream every stage is enqueued on (hipStream_t). */
 void *zk_ctx_stream(zk_ctx *ctx);
 
@@ -184,6 +206,9 @@ int zk_compose(zk_ctx *ctx, const uint32_t alpha_raw[3]);
 /* fri() + squared half domain + re-evaluation (polynomial.rs:385, prover.rs:198-211):
  * layer 2+round <- fold(layer 1+round, beta). */
 int zk_fri_fold(zk_ctx *ctx, uint32_t round, uint32_t beta_raw);
+/* `steps` (1..3) successive folds with the challenges beta, beta^2, beta^4 in one pass (zk_ctx_set_fold):
+ * layer 1+round+steps <- fold^steps(layer 1+round); round + steps <= log_n.  steps = 1 gives what zk_fri_fold gives. */
+int zk_fri_fold_multi(zk_ctx *ctx, uint32_t round, uint32_t steps, uint32_t beta_raw);
 /* Small device->host reads (decommit, tests). */
 int zk_layer_read(zk_ctx *ctx, uint32_t layer, size_t offset, size_t count, uint32_t *out);
 int zk_layer_write(zk_ctx *ctx, uint32_t layer, size_t offset, size_t count, const uint32_t *in);
@@ -312,6 +337,9 @@ size_t zk_proof_data_len(uint32_t log_n, uint32_t log_blowup);
 size_t zk_proof_data_len_queries(uint32_t log_n, uint32_t log_blowup, uint32_t n_queries);
 /* With grind_bits > 0: 8 bytes more (the nonce). */
 size_t zk_proof_data_len_grind(uint32_t log_n, uint32_t log_blowup, uint32_t n_queries, uint32_t grind_bits);
+/* Proofs made with zk_ctx_set_fold(fold_log): 32 + 12 + 32 + 36 G + 4 + (grind ? 8 : 0) + q (4 + 4 (12 + 32 L) + sum over the
+ * G = ceil(log_n / fold_log) groups of 2^steps (12 + 32 (L - r0))).  fold_log = 1: zk_proof_data_len_grind.  0 for a fold_log outside 1..3. */
+size_t zk_proof_data_len_fold(uint32_t log_n, uint32_t log_blowup, uint32_t n_queries, uint32_t grind_bits, uint32_t fold_log);
 /* Proof-of-work search (zk_ctx_set_grinding): the smallest nonce >= start whose SHA-256(state || le64(nonce)) begins with
  * grind_bits zero bits (0..32; 0 gives start), on the GPU (zk_grind) or on <= 16 host threads (zk_grind_host; threads is
  * clamped to 1..16).  Gives up with an error naming grind_bits after 2^44 nonces.  A zk_channel user grinds on
@@ -338,6 +366,14 @@ int zk_verify_check(const uint8_t *proof, size_t len, const uint8_t *state, uint
  * length does not match grind_bits is rejected (-1). */
 int zk_verify_grind(const uint8_t *proof, size_t len, const uint8_t *state, uint32_t log_n, uint32_t log_blowup,
                     uint32_t public_last, int hash_kind, uint32_t n_queries, uint32_t grind_bits, int32_t *check_out);
+
+/* zk_verify_grind for proofs made with zk_ctx_set_fold(fold_log) (proof.rs:101-148 widened): per group the 2^steps opened values
+ * are folded down with the formula of proof.rs:110-113 and compared with the next group's first value (the free term after the
+ * last).  Check numbers as zk_verify_grind with "k" read as the group index j: -(100+j) fold, -(200+j) path length, -(300+j) path
+ * of the first value, -(400+j) first failing path of the others; the replay counts 3 + G + q challenges.  fold_log = 1 gives every
+ * input the number zk_verify_grind gives it. */
+int zk_verify_fold(const uint8_t *proof, size_t len, const uint8_t *state, uint32_t log_n, uint32_t log_blowup,
+                   uint32_t public_last, int hash_kind, uint32_t n_queries, uint32_t grind_bits, uint32_t fold_log, int32_t *check_out);
 
 /* A verifier for many proofs of one size (log_n, log_blowup: the sizes zk_verify_queries accepts).  It owns its streams and
  * device buffers (grown on demand) and a pinned staging buffer.  One verifier is used from one host thread at a time. */
@@ -591,6 +627,10 @@ int zk_dev_compose(const zk_dom *dom, const uint32_t *d_f, uint32_t *d_cp, uint3
 /* polynomial.rs:385 + prover.rs:204-211: 2^log_m values of FRI layer `round` -> 2^(log_m-1). */
 int zk_dev_fri_fold(const zk_dom *dom, const uint32_t *d_in, uint32_t *d_out, uint32_t log_m, uint32_t round,
                     uint32_t beta_raw, void *stream);
+/* The same `steps` (1..3) times in one pass with the challenges beta, beta^2, beta^4: 2^log_m values of FRI layer `round` ->
+ * 2^(log_m-steps) values of layer round + steps (round + steps <= log_n).  steps = 1 is zk_dev_fri_fold. */
+int zk_dev_fri_fold_multi(const zk_dom *dom, const uint32_t *d_in, uint32_t *d_out, uint32_t log_m, uint32_t round,
+                          uint32_t steps, uint32_t beta_raw, void *stream);
 /* Batch trace generation: prover.rs:32-39 is serial per trace, so one
  * lane generates one trace; out[t*count + i] = a_i of trace t seeded by (a0[t], a1[t]). */
 int zk_dev_trace_fibsq_batch(const uint32_t *d_a0, const uint32_t *d_a1, uint32_t batch, uint32_t count,

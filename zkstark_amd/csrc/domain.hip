@@ -243,6 +243,39 @@ int dom_fold(const zk_dom* d, const uint32_t* d_in, uint32_t* d_out, uint32_t lo
     return ZK_OK;
 }
 
+// `steps` successive folds (rounds round .. round + steps - 1) with the challenges beta, beta^2, beta^4, ... in one pass: layer of
+// 2^log_m values -> 2^(log_m - steps).  Every constant that depends on the challenge or on a root of unity, not on the position,
+// is folded here into the launch arguments (FoldMultiArgs::c_mont).
+int fold_multi_args(const zk_dom* d, const uint32_t* d_in, uint32_t* d_out, uint32_t log_m, uint32_t round, uint32_t steps, uint32_t beta_raw,
+                    FoldMultiArgs& a) {
+    if (steps < 1 || steps > 3) return fail(ZK_ERR_INVALID, "fold: steps must be 1..3 (got %u)", steps);
+    if (log_m < steps || log_m + round != d->L)
+        return fail(ZK_ERR_INVALID, "fold: layer size 2^%u does not match round %u + %u steps of a 2^%u domain", log_m, round, steps, d->L);
+    a = FoldMultiArgs{};
+    a.in = d_in; a.out = d_out; a.log_m = log_m; a.round = round; a.steps = steps;
+    a.hinv = d->Hinv.view();
+    a.scale_mont = to_mont(invmod(1u << steps));
+    const uint32_t S = 1u << steps;
+    const uint32_t om_inv = invmod(powmod(d->h, (uint64_t)d->N >> steps));   // h^(N / S): index + m / S multiplies the point by it
+    uint32_t bk = beta_raw % P, ok = om_inv;                                  // beta^(2^k), w_S^(-2^k)
+    for (uint32_t k = 0; k < steps; ++k) {
+        const uint32_t base = mulmod(bk, mulmod(d->fold_k[round + k], 2));   // beta^(2^k) * w^(-2^(r+k))
+        uint32_t tw = 1;
+        for (uint32_t t = 0; t < (S >> (k + 1)); ++t) { a.c_mont[S - (S >> k) + t] = to_mont(mulmod(base, tw)); tw = mulmod(tw, ok); }
+        bk = mulmod(bk, bk); ok = mulmod(ok, ok);
+    }
+    return ZK_OK;
+}
+int dom_fold_multi(const zk_dom* d, const uint32_t* d_in, uint32_t* d_out, uint32_t log_m, uint32_t round, uint32_t steps, uint32_t beta_raw,
+                   hipStream_t s, Profiler* prof) {
+    if (steps == 1) return dom_fold(d, d_in, d_out, log_m, round, beta_raw, s, prof);
+    FoldMultiArgs a;
+    int rc = fold_multi_args(d, d_in, d_out, log_m, round, steps, beta_raw, a);
+    if (rc) return rc;
+    HIPCHK(launch_fri_fold_multi(a, s, prof));
+    return ZK_OK;
+}
+
 
 // Waits until the mailbox carries the sequence number of the last commit launch (polling host-coherent
 // memory: no blit kernel, no stream synchronisation on the commit -> challenge path).

@@ -176,6 +176,11 @@ int dom_compose(const zk_dom* d, const uint32_t* d_f, uint32_t* d_cp, uint32_t f
 int fold_args(const zk_dom* d, const uint32_t* d_in, uint32_t* d_out, uint32_t log_m, uint32_t round, uint32_t beta_raw, FoldArgs& a);
 int dom_fold(const zk_dom* d, const uint32_t* d_in, uint32_t* d_out, uint32_t log_m, uint32_t round, uint32_t beta_raw, hipStream_t s,
              Profiler* prof);
+// `steps` (1..3) folds in one pass with the challenges beta, beta^2, beta^4 (DESIGN.md "Folding factor"); steps = 1 is dom_fold
+int fold_multi_args(const zk_dom* d, const uint32_t* d_in, uint32_t* d_out, uint32_t log_m, uint32_t round, uint32_t steps, uint32_t beta_raw,
+                    FoldMultiArgs& a);
+int dom_fold_multi(const zk_dom* d, const uint32_t* d_in, uint32_t* d_out, uint32_t log_m, uint32_t round, uint32_t steps, uint32_t beta_raw,
+                   hipStream_t s, Profiler* prof = nullptr);
 
 // Waits until *flag (host-mapped memory written by a commit launch on `stream`) equals `want`.  poll (optional) is
 // called every few thousand spins; a non-zero return ends the wait with that code (the sharded prover looks for a

@@ -491,6 +491,77 @@ hipError_t launch_fri_fold(const FoldArgs& a, hipStream_t s, Profiler* prof) {
     return hipGetLastError();
 }
 
+// ---- fold by 2^STEPS in one pass (FoldMultiArgs) ---------------------------------------------------------------
+// v[t] = in[i + t m / S].  Step k: v[t] <- (v[t] + v[t + cnt]) + (v[t] - v[t + cnt]) * xinv^(2^k) * c[k][t], cnt = S >> (k+1);
+// xinv = h^(-2^r i) by one table look-up, squared between the steps; out[i] = v[0] * 2^-STEPS.
+template <int STEPS>
+__device__ __forceinline__ uint32_t fold_multi_one(const FoldMultiArgs& a, uint32_t (&v)[1 << STEPS], uint32_t xinv) {
+    constexpr int S = 1 << STEPS;
+#pragma unroll
+    for (int k = 0; k < STEPS; ++k) {
+        const int cnt = S >> (k + 1);
+#pragma unroll
+        for (int t = 0; t < cnt; ++t) {
+            const uint32_t u = v[t], w = v[t + cnt];
+            v[t] = add(add(u, w), mont_mul(sub(u, w), mont_mul(xinv, a.c_mont[S - (S >> k) + t])));
+        }
+        if (k + 1 < STEPS) xinv = mont_mul(xinv, xinv);
+    }
+    return mont_mul(v[0], a.scale_mont);
+}
+
+template <int STEPS>
+__global__ __launch_bounds__(256) void fri_fold_multi_kernel1(FoldMultiArgs a) {
+    constexpr int S = 1 << STEPS;
+    const size_t q = (size_t)1 << (a.log_m - STEPS);
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= q) return;
+    uint32_t v[S];
+#pragma unroll
+    for (int t = 0; t < S; ++t) v[t] = a.in[i + t * q];
+    a.out[i] = fold_multi_one<STEPS>(a, v, pow_lookup(a.hinv, (uint32_t)(i << a.round)));
+}
+
+// four consecutive outputs per thread: S coalesced 16-byte loads, one 16-byte store; x^-1 advances by h^(-2^r)
+template <int STEPS>
+__global__ __launch_bounds__(256) void fri_fold_multi_kernel(FoldMultiArgs a) {
+    constexpr int S = 1 << STEPS;
+    const size_t q = (size_t)1 << (a.log_m - STEPS);
+    const size_t i = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+    if (i >= q) return;
+    uint4 ld[S];
+#pragma unroll
+    for (int t = 0; t < S; ++t) ld[t] = reinterpret_cast<const uint4*>(a.in)[(i + t * q) >> 2];
+    uint32_t xinv = pow_lookup(a.hinv, (uint32_t)(i << a.round));
+    const uint32_t step = pow_lookup(a.hinv, 1u << a.round);
+    uint32_t r[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        uint32_t v[S];
+#pragma unroll
+        for (int t = 0; t < S; ++t) v[t] = e == 0 ? ld[t].x : e == 1 ? ld[t].y : e == 2 ? ld[t].z : ld[t].w;
+        r[e] = fold_multi_one<STEPS>(a, v, xinv);
+        if (e < 3) xinv = mont_mul(xinv, step);
+    }
+    reinterpret_cast<uint4*>(a.out)[i >> 2] = make_uint4(r[0], r[1], r[2], r[3]);
+}
+
+template <int STEPS>
+static void fold_multi_launch(const FoldMultiArgs& a, size_t q, bool wide, hipStream_t s) {
+    if (wide) hipLaunchKernelGGL(fri_fold_multi_kernel<STEPS>, dim3((uint32_t)((q / 4 + 255) / 256)), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(fri_fold_multi_kernel1<STEPS>, dim3((uint32_t)((q + 255) / 256)), dim3(256), 0, s, a);
+}
+hipError_t launch_fri_fold_multi(const FoldMultiArgs& a, hipStream_t s, Profiler* prof) {
+    if (a.steps < 1 || a.steps > 3 || a.log_m < a.steps) return hipErrorInvalidValue;
+    const size_t m = (size_t)1 << a.log_m, q = m >> a.steps;
+    ScopedKernelTimer tm(prof, K_FOLD, 4.0 * (double)(m + q), s);   // read m words, write m / S
+    const bool wide = q >= 4 && ((reinterpret_cast<uintptr_t>(a.in) | reinterpret_cast<uintptr_t>(a.out)) & 15u) == 0;
+    if (a.steps == 1) fold_multi_launch<1>(a, q, wide, s);
+    else if (a.steps == 2) fold_multi_launch<2>(a, q, wide, s);
+    else fold_multi_launch<3>(a, q, wide, s);
+    return hipGetLastError();
+}
+
 // ===========================================================================
 // Merkle tree
 // ===========================================================================

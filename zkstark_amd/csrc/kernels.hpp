@@ -210,6 +210,21 @@ struct FoldArgs {
 };
 hipError_t launch_fri_fold(const FoldArgs& a, hipStream_t s, Profiler* prof = nullptr);
 
+// `steps` (1..3) successive folds in one pass: layer r -> layer r + steps, S = 2^steps strided input streams, the radix-S
+// butterfly in registers, one store (DESIGN.md "Folding factor").  Output i < m / S folds in[i + t m / S], t < S; step k pairs
+// value t with value t + (S >> (k+1)) at the point (x_i w_S^t)^(2^k), w_S = h^(N / S).  The halvings are applied once (scale).
+struct FoldMultiArgs {
+    const uint32_t* in;   // m values
+    uint32_t* out;        // m / S values
+    uint32_t log_m, round, steps;
+    PowTable hinv;        // h^-1 table, order 2^L
+    uint32_t scale_mont;  // 2^-steps
+    // step k, pair t (< S >> (k+1)) at c_mont[S - (S >> k) + t] = beta^(2^k) * w^(-2^(r+k)) * w_S^(-t 2^k): everything that
+    // depends on the challenge or on a root of unity but not on i
+    uint32_t c_mont[7];
+};
+hipError_t launch_fri_fold_multi(const FoldMultiArgs& a, hipStream_t s, Profiler* prof = nullptr);
+
 // Merkle tree over m = 2^log_m u32 leaves.  nodes: (2m-1) * 8 words, heap order
 // (merkle.rs:14-51), each node the eight SHA-256 state words.
 // mail (optional): where the result of the build is posted for the host, see MailArgs.

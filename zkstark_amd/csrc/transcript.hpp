@@ -272,4 +272,170 @@ inline int verify_transcript(const uint8_t* data, size_t len, const uint8_t stat
     return 0;
 }
 
+// ---- FRI folding factor 2^K (DESIGN.md "Folding factor"; the reference folds by two: prover.rs:198-225) ---------------------
+// fold = K in 1..3.  The R = log_n reference rounds are taken in G = ceil(R / K) groups; group j starts at round r0 = j K and has
+// steps = min(K, R - r0) rounds.  A group draws ONE challenge beta; its output is `steps` successive reference folds with the
+// challenges beta, beta^2, beta^4, and only that output is committed.  Per query a group opens the s = 2^steps values of its
+// INPUT layer (len = N >> r0) at (x % len + t len / s) % len, t < s, then their s paths: the tuple of prover.rs:280-289 widened
+// (K = 1 is that tuple).  A query still tests one coset per layer, so the conjectured security per query is the reference's;
+// the price is s paths per group instead of 2 per round.
+constexpr uint32_t kMaxFoldLog = 3;
+inline uint32_t fold_groups(uint32_t R, uint32_t fold) { return (R + fold - 1) / fold; }
+inline uint32_t fold_steps(uint32_t R, uint32_t fold, uint32_t group) { const uint32_t r0 = group * fold; return R - r0 < fold ? R - r0 : fold; }
+inline size_t proof_data_len_fold(uint32_t log_n, uint32_t log_b, uint32_t q, uint32_t grind, uint32_t fold) {
+    const size_t L = log_n + log_b, R = log_n, G = fold_groups(log_n, fold);
+    size_t per_query = 4 + 4 * (4 + 8 + 32 * L);
+    for (uint32_t j = 0; j < G; ++j) per_query += ((size_t)1 << fold_steps(log_n, fold, j)) * (12 + 32 * (L - (size_t)j * fold));
+    (void)R;
+    return 32 + 12 + 32 + G * 36 + 4 + (grind ? 8 : 0) + (size_t)q * per_query;
+}
+
+// verify_proof (proof.rs:15-149) for a proof folded by 2^fold between commitments.  Check numbers as verify_proof with "k" read as
+// the group index j: -(100+j) fold, -(200+j) path length, -(300+j) path of t = 0, -(400+j) first failing path of t >= 1; per query
+// first every group's fold comparison, then per group its path lengths and paths.  fold = 1 gives verify_proof's number for every input.
+inline int verify_proof_fold(const uint8_t* data, size_t len, uint32_t log_n, uint32_t log_b, uint32_t public_last, int hash, uint32_t q,
+                             uint32_t grind, uint32_t fold) {
+    if (log_n < 2 || log_b < 1 || log_n + log_b > 30 || q < 1 || q > 64 || grind > kMaxGrindBits || fold < 1 || fold > kMaxFoldLog) return -1;
+    const size_t n = (size_t)1 << log_n, B = (size_t)1 << log_b, N = n << log_b, R = log_n, L = log_n + log_b;
+    const uint32_t G = fold_groups(log_n, fold);
+    const uint8_t* p = data;
+    size_t left = len;
+    bool bad = false;
+    auto take = [&](size_t k) -> const uint8_t* {
+        if (left < k) { bad = true; return nullptr; }
+        const uint8_t* r = p; p += k; left -= k; return r;
+    };
+    auto take32 = [&]() -> uint32_t {
+        const uint8_t* r = take(4);
+        return r ? ((uint32_t)r[0] | ((uint32_t)r[1] << 8) | ((uint32_t)r[2] << 16) | ((uint32_t)r[3] << 24)) : 0;
+    };
+    auto take_path = [&](size_t& plen) -> const uint8_t* {
+        const uint8_t* r = take(8);
+        if (!r) return nullptr;
+        uint64_t c = 0;
+        for (int i = 0; i < 8; ++i) c |= (uint64_t)r[i] << (8 * i);
+        if (c > 64) { bad = true; return nullptr; }
+        plen = (size_t)c;
+        return take(32 * plen);
+    };
+    const uint8_t* f_root = take(32);
+    uint32_t alpha[3] = {take32(), take32(), take32()};
+    const uint8_t* roots[40]; uint32_t betas[40];            // roots[j]: the tree over the INPUT layer of group j (roots[G]: the last layer)
+    roots[0] = take(32);
+    for (uint32_t j = 0; j < G; ++j) { betas[j] = take32(); roots[j + 1] = take(32); }
+    uint32_t free_term = take32();
+    if (grind) take(8);                                   // the nonce
+    uint32_t test_raws[64];
+    for (uint32_t k = 0; k < q; ++k) test_raws[k] = take32();
+    const uint32_t g = root_of_unity(log_n), h = root_of_unity((uint32_t)L);
+    for (uint32_t qk = 0; qk < q; ++qk) {
+        const uint32_t test_raw = test_raws[qk];
+        uint32_t fv[4]; const uint8_t* fp[4]; size_t fpl[4] = {0, 0, 0, 0};
+        for (int i = 0; i < 4; ++i) { fv[i] = take32(); fp[i] = take_path(fpl[i]); }
+        uint32_t lv[40][8]; const uint8_t* lp[40][8]; size_t lpl[40][8];
+        for (uint32_t j = 0; j < G; ++j) {
+            const uint32_t s = 1u << fold_steps(log_n, fold, j);
+            for (uint32_t t = 0; t < s; ++t) lv[j][t] = take32();
+            for (uint32_t t = 0; t < s; ++t) { lpl[j][t] = 0; lp[j][t] = take_path(lpl[j][t]); }
+        }
+        if (bad) return -1;
+        const size_t tp = (size_t)test_raw % (N - 2 * B);
+        const uint32_t x = mulmod(GEN_W, powmod(h, tp));
+        {   // proof.rs:63-77
+            uint32_t f_x = fv[0] % P, f_gx = fv[1] % P, f_ggx = fv[2] % P;
+            uint32_t gm1 = invmod(g), gm2 = mulmod(gm1, gm1), gm3 = mulmod(gm2, gm1);
+            uint32_t p0 = mulmod(sub(f_x, 1), invmod(sub(x, 1)));
+            uint32_t p1 = mulmod(sub(f_x, public_last % P), invmod(sub(x, gm2)));
+            uint32_t num = sub(sub(f_ggx, mulmod(f_gx, f_gx)), mulmod(f_x, f_x));
+            uint32_t den = mulmod(sub(powmod(x, n), 1), invmod(mulmod(mulmod(sub(x, gm3), sub(x, gm2)), sub(x, gm1))));
+            uint32_t p2 = mulmod(num, invmod(den));
+            uint32_t cp0 = add(add(mulmod(alpha[0] % P, p0), mulmod(alpha[1] % P, p1)), mulmod(alpha[2] % P, p2));
+            if (cp0 != fv[3]) return -2;
+        }
+        uint8_t root[32];
+        if (fpl[0] != L || fpl[1] != L || fpl[2] != L || fpl[3] != L) return -3;
+        compute_root_from_path(fv[0], tp, fp[0], fpl[0], root, hash);         if (memcmp(root, f_root, 32)) return -4;
+        compute_root_from_path(fv[1], tp + B, fp[1], fpl[1], root, hash);     if (memcmp(root, f_root, 32)) return -5;
+        compute_root_from_path(fv[2], tp + 2 * B, fp[2], fpl[2], root, hash); if (memcmp(root, f_root, 32)) return -6;
+        compute_root_from_path(fv[3], tp, fp[3], fpl[3], root, hash);         if (memcmp(root, roots[0], 32)) return -7;
+        // proof.rs:101-126 widened: the s opened values of a group folded pairwise (t with t + s/2, then again)
+        const uint32_t inv2 = invmod(2);
+        for (uint32_t j = 0; j < G; ++j) {
+            const uint32_t r0 = j * fold, steps = fold_steps(log_n, fold, j);
+            uint32_t cnt = 1u << steps, v[8];
+            for (uint32_t t = 0; t < cnt; ++t) v[t] = lv[j][t] % P;
+            uint32_t xk = powmod(x, (uint64_t)1 << r0);                        // the point of index tp % len in layer r0
+            uint32_t om = powmod(h, (uint64_t)N >> steps);                     // index + len / s: the point times a primitive s-th root of unity
+            uint32_t bk = betas[j] % P;
+            for (uint32_t k = 0; k < steps; ++k) {
+                cnt >>= 1;
+                uint32_t pt = xk;
+                for (uint32_t t = 0; t < cnt; ++t) {
+                    const uint32_t gx = mulmod(add(v[t], v[t + cnt]), inv2);
+                    const uint32_t hx = mulmod(sub(v[t], v[t + cnt]), invmod(mulmod(pt, 2)));
+                    v[t] = add(gx, mulmod(bk, hx));
+                    pt = mulmod(pt, om);
+                }
+                xk = mulmod(xk, xk); om = mulmod(om, om); bk = mulmod(bk, bk);
+            }
+            const uint32_t expect = (j + 1 < G) ? lv[j + 1][0] : free_term;
+            if (v[0] != expect) return -(int)(100 + j);
+        }
+        // proof.rs:129-148 widened
+        for (uint32_t j = 0; j < G; ++j) {
+            const uint32_t r0 = j * fold, s = 1u << fold_steps(log_n, fold, j);
+            const size_t size = N >> r0;
+            for (uint32_t t = 0; t < s; ++t) if (lpl[j][t] != L - r0) return -(int)(200 + j);
+            for (uint32_t t = 0; t < s; ++t) {
+                compute_root_from_path(lv[j][t], (tp % size + t * (size / s)) % size, lp[j][t], lpl[j][t], root, hash);
+                if (memcmp(root, roots[j], 32)) return t == 0 ? -(int)(300 + j) : -(int)(400 + j);
+            }
+        }
+    }
+    (void)R;
+    if (left != 0) return -8;
+    return 0;
+}
+
+// verify_transcript for the same format: 3 + G + q challenges (k counts them), one commit per group and query.
+inline int verify_transcript_fold(const uint8_t* data, size_t len, const uint8_t state[32], uint32_t log_n, uint32_t log_b, uint32_t q,
+                                  uint32_t grind, uint32_t fold) {
+    if (log_n < 2 || log_b < 1 || log_n + log_b > 30 || grind > kMaxGrindBits || fold < 1 || fold > kMaxFoldLog) return -1;
+    const size_t L = log_n + log_b;
+    const uint32_t G = fold_groups(log_n, fold);
+    if (q < 1 || q > 64 || len != proof_data_len_fold(log_n, log_b, q, grind, fold)) return -1;
+    Channel ch;
+    const uint8_t* p = data;
+    int k = 0;
+    auto commit = [&](size_t n) { ch.commit_bytes(p, n); p += n; };
+    auto challenge = [&]() -> bool {
+        uint32_t expect = ((uint32_t)ch.state[0] << 24) | ((uint32_t)ch.state[1] << 16) | ((uint32_t)ch.state[2] << 8) | ch.state[3];
+        uint32_t got = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
+        ++k;
+        if (got != expect) return false;
+        commit(4);
+        return true;
+    };
+    commit(32);                                             // f_eval root
+    for (int i = 0; i < 3; ++i) if (!challenge()) return -(1000 + k);
+    commit(32);                                             // cp root
+    for (uint32_t j = 0; j < G; ++j) {
+        if (!challenge()) return -(1000 + k);               // the group's beta
+        commit(32);                                         // root of the group's output
+    }
+    commit(4);                                              // free term
+    if (grind) {
+        commit(8);
+        const uint32_t w0 = ((uint32_t)ch.state[0] << 24) | ((uint32_t)ch.state[1] << 16) | ((uint32_t)ch.state[2] << 8) | ch.state[3];
+        if (!grind_word_ok(w0, grind)) return -1998;
+    }
+    for (uint32_t j = 0; j < q; ++j) if (!challenge()) return -(1000 + k);   // queries
+    for (uint32_t j = 0; j < q; ++j) {
+        for (int i = 0; i < 4; ++i) commit(4 + 8 + 32 * L);
+        for (uint32_t gi = 0; gi < G; ++gi) commit(((size_t)1 << fold_steps(log_n, fold, gi)) * (12 + 32 * (L - (size_t)gi * fold)));
+    }
+    if (memcmp(ch.state, state, 32)) return -1999;
+    return 0;
+}
+
 }  // namespace zk

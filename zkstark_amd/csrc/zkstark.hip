@@ -112,6 +112,10 @@ struct zk_ctx {
     uint32_t queries = 1;               // decommitment queries (1 = the reference, prover.rs:263)
     uint32_t grind = 0;                 // proof-of-work bits before the query draw (zk_ctx_set_grinding; 0 = none, the reference)
     Grinder* grinder = nullptr;         // device search on this context's stream (created by the setter when grind > kGrindHostMaxBits)
+    // FRI folding factor 2^fold between commitments (zk_ctx_set_fold; 1 = the reference, prover.rs:198-225).  skipped_*: bit id set =
+    // the last proof did not materialise layer / tree id (read-outs of it answer ZK_ERR_STATE until a stage call writes it)
+    uint32_t fold = 1;
+    uint64_t skipped_layers = 0, skipped_trees = 0;
     int hash = 0;                      // Merkle hash: 0 = SHA-256 (reference), 1 = field-native (configs[4])
     // opt-in reference self-checks (zk_ctx_set_checks; prover.rs:64-66, :148-159, :169, :228-251)
     bool checks = false;
@@ -192,7 +196,7 @@ MailArgs mail_of(zk_ctx* c, uint32_t tree, bool host, bool feed_tail = true) {
     c->tree_seq[tree] = m.seq;
     m.counter = c->d_counter;
     m.top = host ? top_of(c, tree) : 0;
-    if (feed_tail && m.top && c->host_tail && tree >= 1 && layer_log(c, tree) == c->host_tail + 1) {
+    if (feed_tail && c->fold == 1 && m.top && c->host_tail && tree >= 1 && layer_log(c, tree) == c->host_tail + 1) {
         m.dump_src = c->d_layers + c->layer_off[tree];
         m.dump_log = c->host_tail + 1;
         m.vals_off = (uint32_t)kMailValsOff;
@@ -330,7 +334,7 @@ int fri_round_commit(zk_ctx* c, uint32_t round, uint32_t beta_raw, uint8_t root[
 bool round_on_host(const zk_ctx* c, uint32_t round) {
     return c->hash == 0 && c->host_top && c->host_tail && c->L >= c->host_tail + 1 && c->L - round <= c->host_tail + 1;
 }
-bool can_gate(const zk_ctx* c, uint32_t round) { return c->early && c->early_ok && !c->checks && round < c->R && !round_on_host(c, round); }
+bool can_gate(const zk_ctx* c, uint32_t round) { return c->fold == 1 && c->early && c->early_ok && !c->checks && round < c->R && !round_on_host(c, round); }
 // The launches of do_fold_commit(round), enqueued behind a wait on the gate word; their one challenge-dependent constant is read
 // from a parameter slot the host fills in release_gated_fold.
 int enqueue_gated_fold(zk_ctx* c, uint32_t round) {
@@ -512,6 +516,90 @@ int open_wait(zk_ctx* c) {
 
 // generate_proof(channel) (prover.rs:9): everything is committed to, and every challenge drawn from, the
 // caller's channel `ch`, which may already hold a transcript prefix (main.rs:19 starts from a fresh one).
+// FRI rounds and decommitment of a proof folded by 2^fold between commitments (fold > 1; DESIGN.md "Folding factor"): per group of
+// `steps` rounds one challenge, one pass of the multi-fold kernel (prover.rs:201-211, steps times), one tree (prover.rs:214) over
+// its output, one root (prover.rs:224).  Every layer is folded on the device (no host FRI tail); tree tops go to the host as usual.
+int prove_fold_rounds(zk_ctx* c, Channel& ch) {
+    const uint32_t R = c->R, K = c->fold;
+    const size_t B = c->B, N = c->N, Lp = c->L;
+    uint8_t root[32];
+    int rc;
+    for (uint32_t r0 = 0; r0 < R; r0 += K) {
+        const uint32_t steps = R - r0 < K ? R - r0 : K, id = 1 + r0 + steps;
+        const uint32_t beta = c->info.beta_raw[r0] = ch.get_u32();            // prover.rs:200, once per group
+        if ((rc = dom_fold_multi(c->dom, c->d_layers + c->layer_off[1 + r0], c->d_layers + c->layer_off[id], c->L - r0, r0, steps, beta,
+                                 c->stream, prof_of(c)))) return rc;
+        if ((rc = do_merkle(c, id, true, false))) return rc;
+        if ((rc = read_commit(c, id, root))) return rc;
+        const size_t deg = c->n >> (r0 + steps);
+        if (c->checks && (rc = check_degree(c, id, (uint32_t)deg - (deg ? 1 : 0), "prover.rs:228-251 (FRI layer degree)"))) return rc;
+        ch.commit_hash(root);
+        memcpy(c->info.roots[id], root, 32);
+        for (uint32_t l = 2 + r0; l < id; ++l) { c->skipped_layers |= (uint64_t)1 << l; c->skipped_trees |= (uint64_t)1 << l; }
+    }
+    uint32_t free_term = 0;
+    if ((rc = last_layer_value(c, &free_term))) return rc;
+    c->info.free_term = free_term;
+    ch.commit_u32(free_term);                             // prover.rs:254
+    if (c->grind) {
+        uint64_t w = 0;
+        if ((rc = grind_channel(c->grinder, ch, c->grind, &w))) return rc;
+        c->info.grind_bits = c->grind;
+        c->info.grind_nonce = w;
+    }
+    const uint32_t Q = c->queries;
+    uint32_t qraws[64];
+    for (uint32_t k = 0; k < Q; ++k) qraws[k] = ch.get_u32();   // prover.rs:263
+    c->info.query_raw = qraws[0];
+    size_t per_query = 4;
+    for (uint32_t r0 = 0; r0 < R; r0 += K) per_query += (size_t)1 << (R - r0 < K ? R - r0 : K);
+    open_begin(c, (size_t)Q * per_query);
+    for (uint32_t k = 0; k < Q; ++k) {
+        const size_t x = (size_t)qraws[k] % (N - 2 * B);
+        open_val(c, 0, x);         open_path(c, 0, N, x);
+        open_val(c, 0, x + B);     open_path(c, 0, N, x + B);
+        open_val(c, 0, x + 2 * B); open_path(c, 0, N, x + 2 * B);
+        open_val(c, 1, x);         open_path(c, 1, N, x);
+        for (uint32_t r0 = 0; r0 < R; r0 += K) {          // prover.rs:280-289 widened: the s coset values of the group's input layer
+            const size_t s = (size_t)1 << (R - r0 < K ? R - r0 : K), len = N >> r0, xi = x % len;
+            for (size_t t = 0; t < s; ++t) {
+                const size_t idx = (xi + t * (len / s)) % len;
+                open_val(c, 1 + r0, idx); open_path(c, 1 + r0, len, idx);
+            }
+        }
+    }
+    if ((rc = open_launch(c))) return rc;
+    if ((rc = flush_host_parts(c))) return rc;
+    if ((rc = open_wait(c))) return rc;
+    std::vector<const uint32_t*>& vsrc = c->fetch_vals;
+    std::vector<const uint32_t*>& dsrc = c->fetch_nodes;
+    std::vector<uint8_t>& buf = c->commit_buf;
+    buf.resize(8 * (12 + 32 * Lp));
+    auto put32 = [](uint8_t* p, uint32_t v) { for (int i = 0; i < 4; ++i) p[i] = (uint8_t)(v >> (8 * i)); };
+    auto put_path = [&](uint8_t* p, size_t first, size_t plen) {
+        for (int i = 0; i < 8; ++i) p[i] = (uint8_t)((uint64_t)plen >> (8 * i));
+        for (size_t j = 0; j < plen; ++j) digest_words_to_bytes(dsrc[first + j], p + 8 + 32 * j);
+        return 8 + 32 * plen;
+    };
+    size_t vi = 0, dpos = 0;
+    for (uint32_t q = 0; q < Q; ++q) {
+        for (int k = 0; k < 4; ++k) {                         // (u32, AuthPath): prover.rs:274-277
+            put32(buf.data(), *vsrc[vi++]);
+            const size_t len = 4 + put_path(buf.data() + 4, dpos, Lp);
+            ch.commit_bytes(buf.data(), len);
+            dpos += Lp;
+        }
+        for (uint32_t r0 = 0; r0 < R; r0 += K) {              // s values, then their s paths: one commit per group
+            const size_t s = (size_t)1 << (R - r0 < K ? R - r0 : K), pl = Lp - r0;
+            size_t len = 0;
+            for (size_t t = 0; t < s; ++t) { put32(buf.data() + len, *vsrc[vi++]); len += 4; }
+            for (size_t t = 0; t < s; ++t) { len += put_path(buf.data() + len, dpos, pl); dpos += pl; }
+            ch.commit_bytes(buf.data(), len);
+        }
+    }
+    return ZK_OK;
+}
+
 int prove_resident(zk_ctx* c, Channel& ch) {
     if (!c->have_trace) return fail(ZK_ERR_STATE, "zk_prove_resident: no trace uploaded");
     static const bool timing = getenv("ZK_HOST_TIMING") != nullptr;
@@ -524,7 +612,8 @@ int prove_resident(zk_ctx* c, Channel& ch) {
     };
     const uint32_t R = c->R;
     const size_t B = c->B, N = c->N;
-    ch.data.reserve(ch.data.size() + proof_data_len(c->log_n, c->log_b, c->queries, c->grind));
+    ch.data.reserve(ch.data.size() + proof_data_len_fold(c->log_n, c->log_b, c->queries, c->grind, c->fold));
+    c->skipped_layers = c->skipped_trees = 0;
     uint8_t root[32];
     int rc;
     memset(&c->info, 0, sizeof c->info);
@@ -546,6 +635,7 @@ int prove_resident(zk_ctx* c, Channel& ch) {
     if (c->checks && (rc = check_degree(c, 1, (uint32_t)c->n - 1, "prover.rs:148-159/:169 (exact divisions, deg cp = n - 1)"))) return rc;
     ch.commit_hash(root);                                 // prover.rs:180
     memcpy(c->info.roots[1], root, 32);
+    if (c->fold > 1) return prove_fold_rounds(c, ch);
     for (uint32_t r = 0; r < R; ++r) {                    // prover.rs:198-225
         uint32_t beta = c->info.beta_raw[r] = ch.get_u32();   // prover.rs:200
         // prover.rs:201-214 (fold fused into the leaf hashing); on the host once the layers are small and present there
@@ -915,7 +1005,45 @@ int zk_ctx_set_early_launch(zk_ctx* c, int on) {
     c->early = on != 0;
     return ZK_OK;
 }
-int zk_ctx_get_early_launch(const zk_ctx* c) { return c && c->early && c->early_ok ? 1 : 0; }
+int zk_ctx_get_early_launch(const zk_ctx* c) { return c && c->early && c->early_ok && c->fold == 1 ? 1 : 0; }
+// FRI folding factor 2^fold_log between commitments (include/zkstark_amd.h).  A query of a folded proof opens 2^fold_log values and
+// paths per group: the decommitment buffers grow here, not inside the first proof.
+int zk_ctx_set_fold(zk_ctx* c, uint32_t fold_log) {
+    if (!c) return fail(ZK_ERR_INVALID, "null context");
+    if (c->tail) return fail(ZK_ERR_STATE, "zk_ctx_set_fold: FRI-tail context");
+    if (fold_log < 1 || fold_log > kMaxFoldLog) return fail(ZK_ERR_INVALID, "zk_ctx_set_fold: need 1 <= fold_log <= %u (got %u)", kMaxFoldLog, fold_log);
+    size_t opened = 4;
+    for (uint32_t r0 = 0; r0 < c->R; r0 += fold_log) opened += (size_t)1 << (c->R - r0 < fold_log ? c->R - r0 : fold_log);
+    const size_t cap = (size_t)kMaxQueries * opened * (c->L + 1) + 64;
+    if (cap > c->gather_cap) {
+        HIPCHK(hipSetDevice(c->device));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        uint64_t *d_off = nullptr, *h_off = nullptr, *dm_off = nullptr;
+        uint32_t *d_out = nullptr, *h_out = nullptr, *dm_out = nullptr;
+        hipError_t e = hipMalloc((void**)&d_off, cap * 8);
+        if (e == hipSuccess) e = hipMalloc((void**)&d_out, cap * 32);
+        if (e == hipSuccess) e = hipHostMalloc((void**)&h_off, cap * 8, hipHostMallocMapped | hipHostMallocCoherent);
+        if (e == hipSuccess) e = hipHostMalloc((void**)&h_out, cap * 32, hipHostMallocMapped | hipHostMallocCoherent);
+        if (e == hipSuccess) e = hipHostGetDevicePointer((void**)&dm_off, h_off, 0);
+        if (e == hipSuccess) e = hipHostGetDevicePointer((void**)&dm_out, h_out, 0);
+        if (e != hipSuccess) {
+            if (d_off) (void)hipFree(d_off);
+            if (d_out) (void)hipFree(d_out);
+            if (h_off) (void)hipHostFree(h_off);
+            if (h_out) (void)hipHostFree(h_out);
+            return fail(ZK_ERR_NOMEM, "zk_ctx_set_fold: decommitment buffers: %s", hipGetErrorString(e));
+        }
+        (void)hipFree(c->d_gather_off); (void)hipFree(c->d_gather_out);
+        (void)hipHostFree(c->h_gather_off); (void)hipHostFree(c->h_gather_out);
+        c->d_gather_off = d_off; c->d_gather_out = d_out; c->h_gather_off = h_off; c->h_gather_out = h_out;
+        c->dm_gather_off = dm_off; c->dm_gather_out = dm_out;
+        c->device_bytes += (cap - c->gather_cap) * 40;
+        c->gather_cap = cap;
+    }
+    c->fold = fold_log;
+    return ZK_OK;
+}
+uint32_t zk_ctx_get_fold(const zk_ctx* c) { return c ? c->fold : 0; }
 int zk_ctx_set_queries(zk_ctx* c, uint32_t n_queries) {
     if (!c) return fail(ZK_ERR_INVALID, "null context");
     if (n_queries < 1 || n_queries > kMaxQueries) return fail(ZK_ERR_INVALID, "zk_ctx_set_queries: need 1 <= n_queries <= %u", kMaxQueries);
@@ -1035,6 +1163,7 @@ int zk_merkle_commit(zk_ctx* c, uint32_t layer, uint8_t root_out[32]) {
     const double t0 = now_us();
     // the top of an earlier stand-alone commitment still waiting in the staging buffer: the same tree is rebuilt now (drop
     // it), another tree's top goes to the device before its staging space is reused
+    c->skipped_trees &= ~((uint64_t)1 << layer);
     if (c->pending_top && c->pending_tree == layer) c->pending_top = false;
     int rc = settle_pending(c);
     if (rc) return rc;
@@ -1064,12 +1193,24 @@ int zk_fri_fold(zk_ctx* c, uint32_t round, uint32_t beta_raw) {
     if (!c) return fail(ZK_ERR_INVALID, "null context");
     if (round >= c->R) return fail(ZK_ERR_INVALID, "zk_fri_fold: round %u out of range (%u rounds)", round, c->R);
     HIPCHK(hipSetDevice(c->device));
+    c->skipped_layers &= ~((uint64_t)1 << (2 + round));
     return do_fold(c, round, beta_raw);
+}
+// layer 1 + round -> layer 1 + round + steps in one pass (steps folds with beta, beta^2, beta^4); steps = 1 is zk_fri_fold
+int zk_fri_fold_multi(zk_ctx* c, uint32_t round, uint32_t steps, uint32_t beta_raw) {
+    if (!c) return fail(ZK_ERR_INVALID, "null context");
+    if (steps < 1 || steps > kMaxFoldLog) return fail(ZK_ERR_INVALID, "zk_fri_fold_multi: steps must be 1..%u (got %u)", kMaxFoldLog, steps);
+    if (round >= c->R || round + steps > c->R) return fail(ZK_ERR_INVALID, "zk_fri_fold_multi: rounds %u..%u out of range (%u rounds)", round, round + steps, c->R);
+    HIPCHK(hipSetDevice(c->device));
+    c->skipped_layers &= ~((uint64_t)1 << (1 + round + steps));
+    return dom_fold_multi(c->dom, c->d_layers + c->layer_off[1 + round], c->d_layers + c->layer_off[1 + round + steps], c->L - round, round, steps,
+                          beta_raw, c->stream, prof_of(c));
 }
 
 int zk_layer_read(zk_ctx* c, uint32_t layer, size_t offset, size_t count, uint32_t* out) {
     if (!c || (!out && count)) return fail(ZK_ERR_INVALID, "zk_layer_read: null argument");
     if (layer > c->R + 1 || offset + count > layer_size(c, layer)) return fail(ZK_ERR_INVALID, "zk_layer_read: out of range");
+    if ((c->skipped_layers >> layer) & 1) return fail(ZK_ERR_STATE, "zk_layer_read: layer %u was not materialised by the last proof (fold_log %u)", layer, c->fold);
     HIPCHK(hipSetDevice(c->device));
     if (int prc = settle_pending(c)) return prc;
     HIPCHK(hipMemcpyAsync(out, c->d_layers + c->layer_off[layer] + offset, count * 4, hipMemcpyDeviceToHost, c->stream));
@@ -1086,12 +1227,14 @@ int zk_layer_write(zk_ctx* c, uint32_t layer, size_t offset, size_t count, const
     HIPCHK(hipMemcpyAsync(c->d_layers + c->layer_off[layer] + offset, in, count * 4, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     if (layer == 0) c->have_lde = true;
+    c->skipped_layers &= ~((uint64_t)1 << layer);
     return ZK_OK;
 }
 
 int zk_merkle_node(zk_ctx* c, uint32_t tree, size_t index, uint8_t out[32]) {
     if (!c || !out) return fail(ZK_ERR_INVALID, "zk_merkle_node: null argument");
     if (tree > c->R + 1 || index >= 2 * layer_size(c, tree) - 1) return fail(ZK_ERR_INVALID, "zk_merkle_node: out of range");
+    if ((c->skipped_trees >> tree) & 1) return fail(ZK_ERR_STATE, "zk_merkle_node: tree %u was not built by the last proof (fold_log %u)", tree, c->fold);
     HIPCHK(hipSetDevice(c->device));
     if (int prc = settle_pending(c)) return prc;
     HIPCHK(hipMemcpyAsync(c->h_small, c->d_trees + c->tree_off[tree] + index * 8, 32, hipMemcpyDeviceToHost, c->stream));
@@ -1104,6 +1247,7 @@ int zk_merkle_nodes(zk_ctx* c, uint32_t tree, size_t first, size_t count, uint8_
     if (!c || (!out && count)) return fail(ZK_ERR_INVALID, "zk_merkle_nodes: null argument");
     if (tree > c->R + 1 || first > 2 * layer_size(c, tree) - 1 || count > 2 * layer_size(c, tree) - 1 - first)
         return fail(ZK_ERR_INVALID, "zk_merkle_nodes: out of range");
+    if ((c->skipped_trees >> tree) & 1) return fail(ZK_ERR_STATE, "zk_merkle_nodes: tree %u was not built by the last proof (fold_log %u)", tree, c->fold);
     HIPCHK(hipSetDevice(c->device));
     if (int prc = settle_pending(c)) return prc;
     return merkle_nodes_to_host(c->device, c->stream, c->d_trees + c->tree_off[tree], first, count, out);
@@ -1112,6 +1256,7 @@ int zk_merkle_nodes(zk_ctx* c, uint32_t tree, size_t first, size_t count, uint8_
 int zk_merkle_path(zk_ctx* c, uint32_t tree, size_t leaf, uint8_t* out, size_t* path_len) {
     if (!c || !out) return fail(ZK_ERR_INVALID, "zk_merkle_path: null argument");
     if (tree > c->R + 1 || leaf >= layer_size(c, tree)) return fail(ZK_ERR_INVALID, "zk_merkle_path: out of range");
+    if ((c->skipped_trees >> tree) & 1) return fail(ZK_ERR_STATE, "zk_merkle_path: tree %u was not built by the last proof (fold_log %u)", tree, c->fold);
     HIPCHK(hipSetDevice(c->device));
     if (int prc = settle_pending(c)) return prc;
     std::vector<size_t> nodes;
@@ -1221,6 +1366,21 @@ size_t zk_proof_data_len(uint32_t log_n, uint32_t log_b) { return proof_data_len
 size_t zk_proof_data_len_queries(uint32_t log_n, uint32_t log_b, uint32_t n_queries) { return proof_data_len(log_n, log_b, n_queries); }
 size_t zk_proof_data_len_grind(uint32_t log_n, uint32_t log_b, uint32_t n_queries, uint32_t grind_bits) {
     return proof_data_len(log_n, log_b, n_queries, grind_bits);
+}
+size_t zk_proof_data_len_fold(uint32_t log_n, uint32_t log_b, uint32_t n_queries, uint32_t grind_bits, uint32_t fold_log) {
+    if (fold_log < 1 || fold_log > kMaxFoldLog) return 0;
+    return proof_data_len_fold(log_n, log_b, n_queries, grind_bits, fold_log);
+}
+int zk_verify_fold(const uint8_t* proof, size_t len, const uint8_t* state, uint32_t log_n, uint32_t log_b, uint32_t public_last,
+                   int hash_kind, uint32_t n_queries, uint32_t grind_bits, uint32_t fold_log, int32_t* check_out) {
+    if (!proof || !check_out) return fail(ZK_ERR_INVALID, "zk_verify_fold: null argument");
+    if (hash_kind != ZK_HASH_SHA256 && hash_kind != ZK_HASH_FIELD) return fail(ZK_ERR_INVALID, "zk_verify_fold: unknown hash %d", hash_kind);
+    if (fold_log < 1 || fold_log > kMaxFoldLog) return fail(ZK_ERR_INVALID, "zk_verify_fold: need 1 <= fold_log <= %u (got %u)", kMaxFoldLog, fold_log);
+    int rc = state ? verify_transcript_fold(proof, len, state, log_n, log_b, n_queries, grind_bits, fold_log) : 0;   // as zk_verify_grind: the replay first
+    if (!rc) rc = verify_proof_fold(proof, len, log_n, log_b, public_last, hash_kind, n_queries, grind_bits, fold_log);
+    *check_out = rc;
+    if (rc) return fail(ZK_ERR_VERIFY, "proof rejected at check %d", rc);
+    return ZK_OK;
 }
 
 int zk_compute_root_from_path_ex(uint32_t element, size_t index, const uint8_t* path, size_t path_len, uint8_t out[32], int hash_kind) {
@@ -1371,6 +1531,15 @@ int zk_dev_fri_fold(const zk_dom* d, const uint32_t* d_in, uint32_t* d_out, uint
     if (!d || !d_in || !d_out) return fail(ZK_ERR_INVALID, "zk_dev_fri_fold: null argument");
     HIPCHK(hipSetDevice(d->device));
     return dom_fold(d, d_in, d_out, log_m, round, beta_raw, (hipStream_t)stream, dev_prof());
+}
+int zk_dev_fri_fold_multi(const zk_dom* d, const uint32_t* d_in, uint32_t* d_out, uint32_t log_m, uint32_t round, uint32_t steps,
+                          uint32_t beta_raw, void* stream) {
+    if (!d || !d_in || !d_out) return fail(ZK_ERR_INVALID, "zk_dev_fri_fold_multi: null argument");
+    if (steps < 1 || steps > kMaxFoldLog) return fail(ZK_ERR_INVALID, "zk_dev_fri_fold_multi: steps must be 1..%u (got %u)", kMaxFoldLog, steps);
+    if (round + steps > d->log_n || log_m + round != d->L)
+        return fail(ZK_ERR_INVALID, "zk_dev_fri_fold_multi: layer 2^%u, rounds %u..%u do not fit a domain of %u rounds", log_m, round, round + steps, d->log_n);
+    HIPCHK(hipSetDevice(d->device));
+    return dom_fold_multi(d, d_in, d_out, log_m, round, steps, beta_raw, (hipStream_t)stream, dev_prof());
 }
 int zk_dev_trace_fibsq_batch(const uint32_t* d_a0, const uint32_t* d_a1, uint32_t batch, uint32_t count, uint32_t* d_out, void* stream) {
     if ((batch && (!d_a0 || !d_a1 || !d_out))) return fail(ZK_ERR_INVALID, "zk_dev_trace_fibsq_batch: null argument");

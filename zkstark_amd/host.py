@@ -144,15 +144,21 @@ class Channel:
 class Proof:
     """proof.rs:5-154.  verify() raises ZkError where the reference panics."""
 
-    def __init__(self, state, data, log_n=10, log_blowup=3, public_last=2338775057, hash="sha256", queries=1, grind_bits=0):   # proof.rs:11
+    def __init__(self, state, data, log_n=10, log_blowup=3, public_last=2338775057, hash="sha256", queries=1, grind_bits=0,
+                 fold_log=1):   # proof.rs:11
         self.state, self.data = bytes(state), bytes(data)
         self.log_n, self.log_blowup, self.public_last = log_n, log_blowup, public_last
-        self.hash, self.queries, self.grind_bits = hash, queries, grind_bits
+        self.hash, self.queries, self.grind_bits, self.fold_log = hash, queries, grind_bits, fold_log
 
     def verify(self, strict=False):                  # proof.rs:15
         """strict=True also replays the channel: challenges must come from the transcript and `state`
         must be its final state (the reference trusts the proof for both, proof.rs:22-37); with grind_bits > 0 it also
         checks the proof-of-work nonce."""
+        if self.fold_log != 1:                       # folded by 2^fold_log between commitments (zk_ctx_set_fold)
+            out = C.c_int32()
+            check(_lib.load().zk_verify_fold(self.data, len(self.data), self.state if strict else None, self.log_n, self.log_blowup,
+                                             self.public_last, HASHES[self.hash], self.queries, self.grind_bits, self.fold_log, C.byref(out)))
+            return
         if self.grind_bits:
             out = C.c_int32()
             check(_lib.load().zk_verify_grind(self.data, len(self.data), self.state if strict else None, self.log_n, self.log_blowup,
@@ -165,8 +171,12 @@ class Proof:
         """The number of the check the CPU verifier stops at (zk_verify_grind): 0 = accepted; otherwise what verify()'s
         error names.  Never raises for a rejected proof."""
         out = C.c_int32()
-        rc = _lib.load().zk_verify_grind(self.data, len(self.data), self.state if strict else None, self.log_n, self.log_blowup,
-                                         self.public_last, HASHES[self.hash], self.queries, self.grind_bits, C.byref(out))
+        if self.fold_log != 1:
+            rc = _lib.load().zk_verify_fold(self.data, len(self.data), self.state if strict else None, self.log_n, self.log_blowup,
+                                            self.public_last, HASHES[self.hash], self.queries, self.grind_bits, self.fold_log, C.byref(out))
+        else:
+            rc = _lib.load().zk_verify_grind(self.data, len(self.data), self.state if strict else None, self.log_n, self.log_blowup,
+                                             self.public_last, HASHES[self.hash], self.queries, self.grind_bits, C.byref(out))
         if rc not in (_lib.ZK_OK, _ERR_VERIFY):
             check(rc)
         return out.value
@@ -243,9 +253,11 @@ def _read_nodes(fn, handle, tree, heap, first, count):
 class Context:
     """Device-resident prover state for one (log_n, log_blowup): zk_ctx."""
 
-    def __init__(self, log_n=10, log_blowup=3, device=0, hash="sha256", queries=1, host_levels=None, grind_bits=0):
+    def __init__(self, log_n=10, log_blowup=3, device=0, hash="sha256", queries=1, host_levels=None, grind_bits=0, fold_log=1):
         """host_levels: (top_log, tail_log) of zk_ctx_set_host_levels; None = the library default.  grind_bits: proof-of-work
-        bits before the query draw (zk_ctx_set_grinding; 0 = none)."""
+        bits before the query draw (zk_ctx_set_grinding; 0 = none).  fold_log: FRI folding factor 2^fold_log between commitments
+        (zk_ctx_set_fold; 1 = the reference)."""
+        self.fold_log = fold_log
         self.log_n, self.log_blowup, self.device, self.hash, self.queries = log_n, log_blowup, device, hash, queries
         self.grind_bits = grind_bits
         self.n, self.B = 1 << log_n, 1 << log_blowup
@@ -260,6 +272,13 @@ class Context:
             check(_lib.load().zk_ctx_set_host_levels(self._h, host_levels[0], host_levels[1]))
         if grind_bits:
             check(_lib.load().zk_ctx_set_grinding(self._h, grind_bits))
+        if fold_log != 1:
+            check(_lib.load().zk_ctx_set_fold(self._h, fold_log))
+
+    def set_fold(self, fold_log):
+        """zk_ctx_set_fold: fold by 2^fold_log (1..3) between commitments from the next proof on."""
+        check(_lib.load().zk_ctx_set_fold(self._h, fold_log))
+        self.fold_log = fold_log
 
     def close(self):
         if getattr(self, "_h", None):
@@ -319,6 +338,10 @@ class Context:
 
     def fri_fold(self, rnd, beta_raw): check(_lib.load().zk_fri_fold(self._h, rnd, beta_raw))
 
+    def fri_fold_multi(self, rnd, steps, beta_raw):
+        """zk_fri_fold_multi: layer 1 + rnd -> layer 1 + rnd + steps in one pass (challenges beta, beta^2, beta^4)."""
+        check(_lib.load().zk_fri_fold_multi(self._h, rnd, steps, beta_raw))
+
     def layer_read(self, layer, offset=0, count=None):
         if count is None:
             count = self.layer_size(layer) - offset
@@ -347,7 +370,7 @@ class Context:
 
     def prove(self, trace=None):
         """generate_proof as one C call (C++ host prover). trace=None: already uploaded."""
-        cap = _lib.load().zk_proof_data_len_grind(self.log_n, self.log_blowup, self.queries, self.grind_bits)
+        cap = _lib.load().zk_proof_data_len_fold(self.log_n, self.log_blowup, self.queries, self.grind_bits, self.fold_log)
         buf = C.create_string_buffer(cap)
         st = C.create_string_buffer(32)
         n = C.c_size_t()
@@ -357,14 +380,15 @@ class Context:
             t = _u32arr(trace)
             check(_lib.load().zk_prove(self._h, _ptr(t), len(t), buf, cap, C.byref(n), st))
         info = self.last_transcript()
-        return Proof(st.raw, buf.raw[:n.value], self.log_n, self.log_blowup, info.public_last, self.hash, self.queries, self.grind_bits)
+        return Proof(st.raw, buf.raw[:n.value], self.log_n, self.log_blowup, info.public_last, self.hash, self.queries, self.grind_bits,
+                     self.fold_log)
 
     def prove_channel(self, channel):
         """generate_proof(channel) (prover.rs:9) in one C call on the caller's Channel (zk_prove_channel): the
         resident trace is proved on top of whatever the channel already holds; returns channel.finalize(...)."""
         check(_lib.load().zk_prove_channel(self._h, channel._h))
         proof = channel.finalize(self.log_n, self.log_blowup, self.last_transcript().public_last)
-        proof.grind_bits = self.grind_bits
+        proof.grind_bits, proof.fold_log = self.grind_bits, self.fold_log
         return proof
 
     def set_host_levels(self, top_log, tail_log):
@@ -405,7 +429,7 @@ def prove_many(ctxs):
     library (zk_prove_many): returns the proofs in order."""
     ctxs = list(ctxs)
     c0 = ctxs[0]
-    stride = max(_lib.load().zk_proof_data_len_grind(c.log_n, c.log_blowup, c.queries, c.grind_bits) for c in ctxs)
+    stride = max(_lib.load().zk_proof_data_len_fold(c.log_n, c.log_blowup, c.queries, c.grind_bits, c.fold_log) for c in ctxs)
     handles = (C.c_void_p * len(ctxs))(*[c._h for c in ctxs])
     data = np.zeros((len(ctxs), stride), dtype=np.uint8)
     lens = (C.c_size_t * len(ctxs))()
@@ -414,7 +438,7 @@ def prove_many(ctxs):
     out = []
     for i, c in enumerate(ctxs):
         out.append(Proof(states[i].tobytes(), data[i, :lens[i]].tobytes(), c.log_n, c.log_blowup, c.last_transcript().public_last,
-                         c.hash, c.queries, c.grind_bits))
+                         c.hash, c.queries, c.grind_bits, c.fold_log))
     return out
 
 
