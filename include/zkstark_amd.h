@@ -179,7 +179,7 @@ int zk_ctx_get_early_launch(const zk_ctx *ctx);
  * 0.274 / 0.296 / 0.264 ms -- fold_log 2 is 8 % SLOWER than the default there and fold_log 3 only 4 % faster, because the default
  * folds the small layers on the host thread and fuses every fold into its leaf hashing, while a folded proof pays one fold launch
  * and one tree launch per group (docs/LOG.md "Folding factor").
- * zk_batch_*, zk_shard_* / zk_tail_* and zk_verifier_* stay at factor 2. */
+ * zk_shard_* / zk_tail_* and zk_verifier_* stay at factor 2. */
 int zk_ctx_set_fold(zk_ctx *ctx, uint32_t fold_log);
 uint32_t zk_ctx_get_fold(const zk_ctx *ctx);
 /* The HIP stream every stage is enqueued on (hipStream_t). */
@@ -295,6 +295,19 @@ int zk_batch_set_queries(zk_batch *b, uint32_t n_queries);
 int zk_batch_set_hash(zk_batch *b, int hash_kind);
 /* As zk_ctx_set_grinding, for every proof of the batch: one launch searches the nonces of all proofs of the batch at once. */
 int zk_batch_set_grinding(zk_batch *b, uint32_t grind_bits);
+/* As zk_ctx_set_fold, for every proof of the batch: fold_log 1..3, default 1 (with it every byte, launch and allocation of
+ * zk_batch_prove is what it was without this call).  With fold_log = K > 1 the rounds are taken in groups of K (the last may be
+ * shorter); per group every proof draws ONE challenge from its own channel, one batched multi-fold launch produces layer
+ * 1 + r0 + steps of the whole batch, one tree is built over it and the per-proof roots are committed under that id; the ids in
+ * between are neither computed nor committed.  Every proof is byte for byte what zk_prove returns from a context with the same
+ * (log_n, log_blowup, hash, n_queries, grind_bits, fold_log) and trace, its state too; its length is zk_proof_data_len_fold and it is
+ * checked with zk_verify_fold (zk_verifier_* stays at factor 2).  After a folded zk_batch_prove, zk_batch_merkle_nodes of a tree id
+ * the proof did not build returns ZK_ERR_STATE; a later proof with fold_log 1 materialises every id again.  The decommitment buffers
+ * are re-sized here (a folded proof opens up to 8 values per group).  Device memory: the layers and trees of the skipped ids stay
+ * allocated (the batch can go back to fold_log 1 at any time); fold_log > 1 adds 32 bytes per proof.
+ * zk_batch_get_fold: the current fold_log, 0 for a null batch. */
+int zk_batch_set_fold(zk_batch *b, uint32_t fold_log);
+uint32_t zk_batch_get_fold(const zk_batch *b);
 /* on = 0: every tree level of the batch on the device (default: the host threads hash the top levels of each proof's
  * trees when the CPU has SHA extensions, as zk_ctx_set_host_levels).  Results are identical. */
 int zk_batch_set_host_levels(zk_batch *b, int on);
@@ -310,10 +323,12 @@ int zk_batch_gen_fibsq(zk_batch *b, const uint32_t *a0, const uint32_t *a1);
 /* out[p] = a[n-2] of proof p: the public input its verifier needs (prover.rs:42, proof.rs:68). */
 int zk_batch_public_last(const zk_batch *b, uint32_t *out);
 /* proofs_out: [batch][stride] bytes, stride >= zk_proof_data_len(log_n, log_blowup); states_out:
- * [batch][32] (with q queries: zk_proof_data_len_queries).  Fails with ZK_ERR_CHECK, naming the proof, if a trace breaks the constraints. */
+ * [batch][32] (with q queries: zk_proof_data_len_queries; in general zk_proof_data_len_fold(log_n, log_blowup, n_queries, grind_bits,
+ * fold_log)).  Fails with ZK_ERR_CHECK, naming the proof, if a trace breaks the constraints. */
 int zk_batch_prove(zk_batch *b, uint8_t *proofs_out, size_t stride, uint8_t *states_out);
 /* Nodes [first, first + count) of batch tree `tree` (a heap over batch * m_l leaves; proof p's tree is the subtree under node
- * 2^log_batch - 1 + p), 32 bytes each as zk_merkle_node.  Complete after zk_batch_prove. */
+ * 2^log_batch - 1 + p), 32 bytes each as zk_merkle_node.  Complete after zk_batch_prove; ZK_ERR_STATE for a tree id that the last
+ * proof, folded by zk_batch_set_fold, did not build. */
 int zk_batch_merkle_nodes(zk_batch *b, uint32_t tree, size_t first, size_t count, uint8_t *out);
 
 /* ---- proof: proof.rs ------------------------------------------------------- */
@@ -631,6 +646,12 @@ int zk_dev_fri_fold(const zk_dom *dom, const uint32_t *d_in, uint32_t *d_out, ui
  * 2^(log_m-steps) values of layer round + steps (round + steps <= log_n).  steps = 1 is zk_dev_fri_fold. */
 int zk_dev_fri_fold_multi(const zk_dom *dom, const uint32_t *d_in, uint32_t *d_out, uint32_t log_m, uint32_t round,
                           uint32_t steps, uint32_t beta_raw, void *stream);
+/* zk_dev_fri_fold_multi over a proof-major batch: d_in = [batch][2^log_m], d_out = [batch][2^(log_m-steps)], proof b folded with
+ * its own challenge d_beta_raw[b] (raw u32 values on the device; values >= P are accepted and reduced).  d_work: 8 * batch words of
+ * caller scratch for the per-proof constants.  Stream-ordered: two launches, no allocation, no host synchronisation.  Any
+ * batch >= 1 with batch * 2^log_m <= 2^32; batch = 1 gives what zk_dev_fri_fold_multi gives. */
+int zk_dev_fri_fold_multi_batch(const zk_dom *dom, const uint32_t *d_in, uint32_t *d_out, uint32_t log_m, uint32_t round,
+                                uint32_t steps, const uint32_t *d_beta_raw, uint32_t *d_work, uint32_t batch, void *stream);
 /* Batch trace generation: prover.rs:32-39 is serial per trace, so one
  * lane generates one trace; out[t*count + i] = a_i of trace t seeded by (a0[t], a1[t]). */
 int zk_dev_trace_fibsq_batch(const uint32_t *d_a0, const uint32_t *d_a1, uint32_t batch, uint32_t count,

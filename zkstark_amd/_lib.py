@@ -139,6 +139,9 @@ SYMBOLS = {
     "zk_ctx_get_fold": (_u32, [_vp]),
     "zk_fri_fold_multi": (_int, [_vp, _u32, _u32, _u32]),
     "zk_dev_fri_fold_multi": (_int, [_vp, _vp, _vp, _u32, _u32, _u32, _u32, _vp]),
+    "zk_dev_fri_fold_multi_batch": (_int, [_vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _u32, _vp]),
+    "zk_batch_set_fold": (_int, [_vp, _u32]),
+    "zk_batch_get_fold": (_u32, [_vp]),
     "zk_proof_data_len_fold": (_sz, [_u32, _u32, _u32, _u32, _u32]),
     "zk_verify_fold": (_int, [_vp, _sz, _vp, _u32, _u32, _u32, _int, _u32, _u32, _u32, C.POINTER(C.c_int32)]),
     "zk_ctx_set_early_launch": (_int, [_vp, _int]),

@@ -51,6 +51,10 @@ struct zk_batch {
     size_t per_proof_vals = 0, per_proof_digs = 0;   // per query
     uint32_t queries = 1;             // decommitment queries per proof (1 = the reference, prover.rs:263)
     uint32_t grind = 0;               // proof-of-work bits (zk_batch_set_grinding)
+    uint32_t fold = 1;                // FRI folding factor 2^fold between commitments (zk_batch_set_fold; 1 = the reference)
+    uint32_t proved_fold = 1;         // ... of the last zk_batch_prove, whose skipped_trees these are:
+    uint64_t skipped_trees = 0;       // bit id: that proof built no tree (and no layer) `id`
+    uint32_t* d_work = nullptr;       // [batch][8] per-proof constants of the multi-fold (allocated by the first fold > 1)
     Grinder* grinder = nullptr;       // one launch grinds for every proof of the batch (created by the setter above kGrindHostMaxBits)
     int hash = 0;                    // Merkle hash: 0 = SHA-256 (reference), 1 = field-native
     std::vector<uint32_t> first, last;
@@ -145,7 +149,16 @@ const uint32_t* bfinish_roots(zk_batch* b, uint32_t tree, uint32_t log_m) {
     return lvl[0];
 }
 
-// gather buffers for q queries per proof (offsets in, values + digests out; device and pinned host copies)
+// openings of one query (prover.rs:266-289; folded: prove_fold_rounds): 4 values with paths of L digests, then per group of `fold`
+// rounds the 2^steps coset values of its input layer, each with a path of L - r0 digests
+void bopenings(const zk_batch* b, uint32_t fold, size_t* vals, size_t* digs) {
+    *vals = 4; *digs = 4 * (size_t)b->L;
+    for (uint32_t r0 = 0; r0 < b->R; r0 += fold) {
+        const size_t s = (size_t)1 << (b->R - r0 < fold ? b->R - r0 : fold);
+        *vals += s; *digs += s * (size_t)(b->L - r0);
+    }
+}
+// gather buffers for q queries per proof (offsets in, values + digests out; device and pinned host copies), for the current fold
 int balloc_gather(zk_batch* b, uint32_t q) {
     for (void* p : {(void*)b->d_goff, (void*)b->d_gout}) if (p) (void)hipFree(p);
     for (void* p : {(void*)b->h_goff, (void*)b->h_gout}) if (p) (void)hipHostFree(p);
@@ -176,7 +189,7 @@ int zk_batch_destroy(zk_batch* b) {
     if (b->stream) (void)hipStreamSynchronize(b->stream);
     dom_free(b->dom);
     for (void* p : {(void*)b->d_trace, (void*)b->d_coef, (void*)b->d_layers, (void*)b->d_trees, (void*)b->d_seed, (void*)b->d_chal,
-                    (void*)b->d_counter, (void*)b->d_goff, (void*)b->d_gout})
+                    (void*)b->d_counter, (void*)b->d_goff, (void*)b->d_gout, (void*)b->d_work})
         if (p) (void)hipFree(p);
     for (void* p : {(void*)b->h_chal, (void*)b->h_mail, (void*)b->h_goff, (void*)b->h_gout, (void*)b->h_last, (void*)b->h_stage})
         if (p) (void)hipHostFree(p);
@@ -238,9 +251,7 @@ int zk_batch_create(int device, uint32_t log_n, uint32_t log_b, uint32_t log_bat
     HIPCHK_B(hipMemsetAsync(b->d_counter, 0, 64, b->stream));
     HIPCHK_B(hipMemsetAsync(b->d_trace, 0, b->batch * b->n * 4, b->stream));
     // openings of one proof (prover.rs:266-289): 4 + 2R values, 4 L + sum 2 (L - i) digests
-    b->per_proof_vals = 4 + 2 * (size_t)b->R;
-    b->per_proof_digs = 4 * (size_t)b->L;
-    for (uint32_t i = 0; i < b->R; ++i) b->per_proof_digs += 2 * (size_t)(b->L - i);
+    bopenings(b, 1, &b->per_proof_vals, &b->per_proof_digs);
     if ((rc = balloc_gather(b, 1))) return bail(rc);
     HIPCHK_B(hipHostMalloc((void**)&b->h_chal, b->batch * sizeof(BatchChal)));
     HIPCHK_B(hipHostMalloc((void**)&b->h_last, b->batch * (b->B > 2 ? b->B : 2) * 4));
@@ -327,6 +338,36 @@ int zk_batch_set_grinding(zk_batch* b, uint32_t grind_bits) {
     b->grind = grind_bits;
     return ZK_OK;
 }
+// FRI folding factor 2^fold_log between commitments (include/zkstark_amd.h).  A query of a folded proof opens 2^steps values and paths
+// per group: the gather buffers are re-sized here, as zk_ctx_set_fold does, not inside the first proof.
+int zk_batch_set_fold(zk_batch* b, uint32_t fold_log) {
+    if (!b) return fail(ZK_ERR_INVALID, "null batch");
+    ZK_BATCH_EXCLUSIVE(b, "zk_batch_set_fold");
+    if (fold_log < 1 || fold_log > kMaxFoldLog) return fail(ZK_ERR_INVALID, "zk_batch_set_fold: need 1 <= fold_log <= %u (got %u)", kMaxFoldLog, fold_log);
+    if (b->single) {
+        if (int rc = zk_ctx_set_fold(b->single, fold_log)) return rc;
+        b->fold = fold_log;
+        return ZK_OK;
+    }
+    if (fold_log == b->fold) return ZK_OK;
+    HIPCHK(hipSetDevice(b->device));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    if (fold_log > 1 && !b->d_work) {
+        hipError_t e = hipMalloc((void**)&b->d_work, b->batch * 8 * 4);
+        if (e != hipSuccess) return fail(ZK_ERR_NOMEM, "zk_batch_set_fold: hipMalloc(%zu) failed: %s", b->batch * 32, hipGetErrorString(e));
+        b->device_bytes += b->batch * 32;
+    }
+    const size_t old_vals = b->per_proof_vals, old_digs = b->per_proof_digs;
+    bopenings(b, fold_log, &b->per_proof_vals, &b->per_proof_digs);
+    if (int rc = balloc_gather(b, b->queries)) {          // the old buffers are gone: put back what the old factor needs, or fail again later
+        b->per_proof_vals = old_vals; b->per_proof_digs = old_digs;
+        (void)balloc_gather(b, b->queries);
+        return rc;
+    }
+    b->fold = fold_log;
+    return ZK_OK;
+}
+uint32_t zk_batch_get_fold(const zk_batch* b) { return b ? b->fold : 0; }
 size_t zk_batch_device_bytes(const zk_batch* b) { return b ? b->device_bytes : 0; }
 
 // traces: [batch][n-1] canonical residues on the host (prover.rs:32-39 per proof)
@@ -392,11 +433,15 @@ int zk_batch_merkle_nodes(zk_batch* b, uint32_t tree, size_t first, size_t count
     if (tree > b->R + 1 || first > heap || count > heap - first) return fail(ZK_ERR_INVALID, "zk_batch_merkle_nodes: out of range");
     BusyScope busy(b);
     if (!busy.mine) return fail(ZK_ERR_STATE, "zk_batch_merkle_nodes: a zk_batch_prove is running on this batch");
+    if ((b->skipped_trees >> tree) & 1)
+        return fail(ZK_ERR_STATE, "zk_batch_merkle_nodes: tree %u was not built by the last proof (fold_log %u)", tree, b->proved_fold);
     return merkle_nodes_to_host(b->device, b->stream, b->d_trees + b->tree_off[tree], first, count, out);
 }
 
 // generate_proof (prover.rs:9-293) for every resident trace.  proofs_out: [batch][stride] bytes, stride >=
-// zk_proof_data_len(log_n, log_b); states_out: [batch][32] (Channel.state of each proof, proof.rs:6).
+// zk_proof_data_len_fold(log_n, log_b, queries, grind, fold); states_out: [batch][32] (Channel.state of each proof, proof.rs:6).
+// fold > 1 (DESIGN.md "Folding factor"): the rounds in groups of `fold`; per group one challenge per proof, one pass of the batched
+// multi-fold kernel and one tree over its output, as prove_fold_rounds (zkstark.hip) does for one proof.
 int zk_batch_prove(zk_batch* b, uint8_t* proofs_out, size_t stride, uint8_t* states_out) {
     if (!b || !proofs_out || !states_out) return fail(ZK_ERR_INVALID, "zk_batch_prove: null argument");
     if (!b->have_traces) return fail(ZK_ERR_STATE, "zk_batch_prove: no traces");
@@ -404,7 +449,8 @@ int zk_batch_prove(zk_batch* b, uint8_t* proofs_out, size_t stride, uint8_t* sta
     if (!busy.mine) return fail(ZK_ERR_STATE, "zk_batch_prove: another zk_batch_prove is running on this batch");
     const uint32_t Q = b->queries;
     const int hash = b->hash;
-    const size_t plen = proof_data_len(b->log_n, b->log_b, Q, b->grind);
+    const uint32_t K = b->fold;
+    const size_t plen = proof_data_len_fold(b->log_n, b->log_b, Q, b->grind, K);
     if (stride < plen) return fail(ZK_ERR_BUFFER, "zk_batch_prove: stride %zu < proof length %zu", stride, plen);
     if (b->single) {
         size_t len = 0;
@@ -431,6 +477,7 @@ int zk_batch_prove(zk_batch* b, uint8_t* proofs_out, size_t stride, uint8_t* sta
     // f = LDE of every trace, committed (prover.rs:60-85)
     if ((rc = dom_lde(d, b->d_trace, b->d_coef, b->d_layers + b->layer_off[0], b->stream, nullptr, (uint32_t)nb))) return rc;
     b->stage_used = 0; b->n_segs = 0; b->seg_words = 0;
+    b->skipped_trees = 0; b->proved_fold = K;
     HIPCHK(launch_merkle_build(b->d_layers + b->layer_off[0], L + lb, b->d_trees + b->tree_off[0], b->stream, nullptr, bmail(b, L), hash));
     // proof-independent part of the composition constants (compose_args with alpha = 1)
     ComposeBatchArgs ca;
@@ -453,7 +500,7 @@ int zk_batch_prove(zk_batch* b, uint8_t* proofs_out, size_t stride, uint8_t* sta
     });
     if ((rc = bchal_upload(b))) return rc;
     HIPCHK(launch_compose_merkle_batch(ca, lb, b->d_trees + b->tree_off[1], b->stream, nullptr, bmail(b, L), hash));   // prover.rs:166-176
-    for (uint32_t r = 0; r <= R; ++r) {
+    for (uint32_t r = 0; r <= R && K == 1; ++r) {
         if ((rc = wait_roots())) return rc;
         roots = bfinish_roots(b, 1 + r, L - r);                           // tree 1 + r: 2^(L - r) leaves per proof
         if (r == R) {
@@ -473,6 +520,28 @@ int zk_batch_prove(zk_batch* b, uint8_t* proofs_out, size_t stride, uint8_t* sta
         if ((rc = fold_args(d, b->d_layers + b->layer_off[1 + r], b->d_layers + b->layer_off[2 + r], L - r, r, 0, fa.a))) return rc;
         fa.chal = b->d_chal;
         HIPCHK(launch_fold_merkle_batch(fa, lb, b->d_trees + b->tree_off[2 + r], b->stream, nullptr, bmail(b, L - r - 1), hash));   // prover.rs:201-214
+    }
+    for (uint32_t r0 = 0; K > 1; ) {                                      // folded: tree 1 + r0 is the last one committed
+        if ((rc = wait_roots())) return rc;
+        roots = bfinish_roots(b, 1 + r0, L - r0);
+        if (r0 == R) {
+            b->pool->run(nb, 32, [&](size_t p) { uint8_t root[32]; digest_words_to_bytes(roots + 8 * p, root); ch[p].commit_hash(root); });
+            break;
+        }
+        const uint32_t steps = R - r0 < K ? R - r0 : K, id = 1 + r0 + steps;
+        b->pool->run(nb, 32, [&](size_t p) {
+            uint8_t root[32];
+            digest_words_to_bytes(roots + 8 * p, root);
+            ch[p].commit_hash(root);                                      // prover.rs:180 / :224
+            b->h_chal[p].c_mont = ch[p].get_u32();                        // prover.rs:200, once per group: RAW, reduced on the device
+        });
+        if ((rc = bchal_upload(b))) return rc;
+        if ((rc = dom_fold_multi_batch(d, b->d_layers + b->layer_off[1 + r0], b->d_layers + b->layer_off[id], L - r0, r0, steps, &b->d_chal->c_mont,
+                                       (uint32_t)(sizeof(BatchChal) / 4), b->d_work, (uint32_t)nb, b->stream, nullptr))) return rc;   // prover.rs:201-211, steps times
+        HIPCHK(launch_merkle_build(b->d_layers + b->layer_off[id], L - r0 - steps + lb, b->d_trees + b->tree_off[id], b->stream, nullptr,
+                                   bmail(b, L - r0 - steps), hash));      // prover.rs:214
+        for (uint32_t l = 2 + r0; l < id; ++l) b->skipped_trees |= (uint64_t)1 << l;
+        r0 += steps;
     }
     lap("lde .. last roots");
     if (timing) fprintf(stderr, "[zk batch timing]   of which waiting for the device %.1f us\n", t_wait);
@@ -516,10 +585,12 @@ int zk_batch_prove(zk_batch* b, uint8_t* proofs_out, size_t stride, uint8_t* sta
             *vo++ = b->layer_off[0] + p * N + x + B;     add_path(0, L, x + B);
             *vo++ = b->layer_off[0] + p * N + x + 2 * B; add_path(0, L, x + 2 * B);
             *vo++ = b->layer_off[1] + p * N + x;         add_path(1, L, x);
-            for (uint32_t i = 0; i < R; ++i) {
-                size_t len = N >> i, xi = x % len, nx = (xi + len / 2) % len;
-                *vo++ = b->layer_off[1 + i] + p * len + xi; add_path(1 + i, L - i, xi);
-                *vo++ = b->layer_off[1 + i] + p * len + nx; add_path(1 + i, L - i, nx);
+            for (uint32_t r0 = 0; r0 < R; r0 += K) {                      // per group the s coset values of its input layer (K = 1: the pair)
+                const size_t s = (size_t)1 << (R - r0 < K ? R - r0 : K), len = N >> r0, xi = x % len;
+                for (size_t t = 0; t < s; ++t) {
+                    const size_t idx = (xi + t * (len / s)) % len;
+                    *vo++ = b->layer_off[1 + r0] + p * len + idx; add_path(1 + r0, L - r0, idx);
+                }
             }
         }
     });
@@ -539,12 +610,24 @@ int zk_batch_prove(zk_batch* b, uint8_t* proofs_out, size_t stride, uint8_t* sta
         std::vector<uint8_t> dig(ndg * 32);
         for (size_t i = 0; i < ndg; ++i) digest_words_to_bytes(dw + 8 * i, dig.data() + 32 * i);
         size_t dpos = 0;
-        for (uint32_t q = 0; q < Q; ++q, vals += 4 + 2 * R) {
+        std::vector<uint8_t> grp;                                                                                   // one group's tuple
+        for (uint32_t q = 0; q < Q; ++q) {
             for (int k = 0; k < 4; ++k) { ch[p].commit_val_path(vals[k], dig.data() + 32 * dpos, L); dpos += L; }   // prover.rs:274-277
-            for (uint32_t i = 0; i < R; ++i) {                                                                       // prover.rs:280-289
-                size_t pl = L - i;
-                ch[p].commit_pair_paths(vals[4 + 2 * i], vals[5 + 2 * i], dig.data() + 32 * dpos, dig.data() + 32 * (dpos + pl), pl);
-                dpos += 2 * pl;
+            vals += 4;
+            for (uint32_t r0 = 0; r0 < R; r0 += K) {                                                                 // prover.rs:280-289
+                const size_t s = (size_t)1 << (R - r0 < K ? R - r0 : K), pl = L - r0;
+                if (s == 2) {
+                    ch[p].commit_pair_paths(vals[0], vals[1], dig.data() + 32 * dpos, dig.data() + 32 * (dpos + pl), pl);
+                } else {                                                  // widened: s values, then their s paths, one commit
+                    grp.clear();
+                    for (size_t t = 0; t < s; ++t) Channel::put32(grp, vals[t]);
+                    for (size_t t = 0; t < s; ++t) {
+                        Channel::put64(grp, pl);
+                        grp.insert(grp.end(), dig.data() + 32 * (dpos + t * pl), dig.data() + 32 * (dpos + (t + 1) * pl));
+                    }
+                    ch[p].commit_bytes(grp.data(), grp.size());
+                }
+                vals += s; dpos += s * pl;
             }
         }
         if (ch[p].data.size() != plen) { bad.store(1); return; }

@@ -266,6 +266,25 @@ int fold_multi_args(const zk_dom* d, const uint32_t* d_in, uint32_t* d_out, uint
     }
     return ZK_OK;
 }
+// The same for a proof-major batch (FoldMultiBatchArgs): the challenge-independent part of every constant (fold_multi_args with
+// beta = 1); the challenges stay on the device, d_work takes the per-proof constants.
+int fold_multi_batch_args(const zk_dom* d, const uint32_t* d_in, uint32_t* d_out, uint32_t log_m, uint32_t round, uint32_t steps,
+                          const uint32_t* d_beta_raw, uint32_t beta_stride, uint32_t* d_work, uint32_t batch, FoldMultiBatchArgs& a) {
+    a = FoldMultiBatchArgs{};
+    if (int rc = fold_multi_args(d, d_in, d_out, log_m, round, steps, 1u, a.a)) return rc;
+    if (batch < 1 || ((uint64_t)batch << log_m) > ((uint64_t)1 << 32))
+        return fail(ZK_ERR_INVALID, "fold: a batch of %u layers of 2^%u values does not fit 2^32 values", batch, log_m);
+    a.beta_raw = d_beta_raw; a.beta_stride = beta_stride; a.cb = d_work; a.batch = batch;
+    return ZK_OK;
+}
+int dom_fold_multi_batch(const zk_dom* d, const uint32_t* d_in, uint32_t* d_out, uint32_t log_m, uint32_t round, uint32_t steps,
+                         const uint32_t* d_beta_raw, uint32_t beta_stride, uint32_t* d_work, uint32_t batch, hipStream_t s, Profiler* prof) {
+    FoldMultiBatchArgs a;
+    int rc = fold_multi_batch_args(d, d_in, d_out, log_m, round, steps, d_beta_raw, beta_stride, d_work, batch, a);
+    if (rc) return rc;
+    HIPCHK(launch_fri_fold_multi_batch(a, s, prof));
+    return ZK_OK;
+}
 int dom_fold_multi(const zk_dom* d, const uint32_t* d_in, uint32_t* d_out, uint32_t log_m, uint32_t round, uint32_t steps, uint32_t beta_raw,
                    hipStream_t s, Profiler* prof) {
     if (steps == 1) return dom_fold(d, d_in, d_out, log_m, round, beta_raw, s, prof);

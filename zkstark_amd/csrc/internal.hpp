@@ -181,6 +181,13 @@ int fold_multi_args(const zk_dom* d, const uint32_t* d_in, uint32_t* d_out, uint
                     FoldMultiArgs& a);
 int dom_fold_multi(const zk_dom* d, const uint32_t* d_in, uint32_t* d_out, uint32_t log_m, uint32_t round, uint32_t steps, uint32_t beta_raw,
                    hipStream_t s, Profiler* prof = nullptr);
+// ... over a proof-major batch ([batch][2^log_m] -> [batch][2^(log_m - steps)]), proof b with the raw challenge
+// d_beta_raw[b * beta_stride] (device memory); d_work: 8 * batch words of device scratch.  Two launches, nothing else.
+int fold_multi_batch_args(const zk_dom* d, const uint32_t* d_in, uint32_t* d_out, uint32_t log_m, uint32_t round, uint32_t steps,
+                          const uint32_t* d_beta_raw, uint32_t beta_stride, uint32_t* d_work, uint32_t batch, FoldMultiBatchArgs& a);
+int dom_fold_multi_batch(const zk_dom* d, const uint32_t* d_in, uint32_t* d_out, uint32_t log_m, uint32_t round, uint32_t steps,
+                         const uint32_t* d_beta_raw, uint32_t beta_stride, uint32_t* d_work, uint32_t batch, hipStream_t s,
+                         Profiler* prof = nullptr);
 
 // Waits until *flag (host-mapped memory written by a commit launch on `stream`) equals `want`.  poll (optional) is
 // called every few thousand spins; a non-zero return ends the wait with that code (the sharded prover looks for a

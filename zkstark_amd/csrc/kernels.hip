@@ -495,7 +495,7 @@ hipError_t launch_fri_fold(const FoldArgs& a, hipStream_t s, Profiler* prof) {
 // v[t] = in[i + t m / S].  Step k: v[t] <- (v[t] + v[t + cnt]) + (v[t] - v[t + cnt]) * xinv^(2^k) * c[k][t], cnt = S >> (k+1);
 // xinv = h^(-2^r i) by one table look-up, squared between the steps; out[i] = v[0] * 2^-STEPS.
 template <int STEPS>
-__device__ __forceinline__ uint32_t fold_multi_one(const FoldMultiArgs& a, uint32_t (&v)[1 << STEPS], uint32_t xinv) {
+__device__ __forceinline__ uint32_t fold_multi_core(const uint32_t (&c)[7], uint32_t scale_mont, uint32_t (&v)[1 << STEPS], uint32_t xinv) {
     constexpr int S = 1 << STEPS;
 #pragma unroll
     for (int k = 0; k < STEPS; ++k) {
@@ -503,11 +503,15 @@ __device__ __forceinline__ uint32_t fold_multi_one(const FoldMultiArgs& a, uint3
 #pragma unroll
         for (int t = 0; t < cnt; ++t) {
             const uint32_t u = v[t], w = v[t + cnt];
-            v[t] = add(add(u, w), mont_mul(sub(u, w), mont_mul(xinv, a.c_mont[S - (S >> k) + t])));
+            v[t] = add(add(u, w), mont_mul(sub(u, w), mont_mul(xinv, c[S - (S >> k) + t])));
         }
         if (k + 1 < STEPS) xinv = mont_mul(xinv, xinv);
     }
-    return mont_mul(v[0], a.scale_mont);
+    return mont_mul(v[0], scale_mont);
+}
+template <int STEPS>
+__device__ __forceinline__ uint32_t fold_multi_one(const FoldMultiArgs& a, uint32_t (&v)[1 << STEPS], uint32_t xinv) {
+    return fold_multi_core<STEPS>(a.c_mont, a.scale_mont, v, xinv);
 }
 
 template <int STEPS>
@@ -559,6 +563,101 @@ hipError_t launch_fri_fold_multi(const FoldMultiArgs& a, hipStream_t s, Profiler
     if (a.steps == 1) fold_multi_launch<1>(a, q, wide, s);
     else if (a.steps == 2) fold_multi_launch<2>(a, q, wide, s);
     else fold_multi_launch<3>(a, q, wide, s);
+    return hipGetLastError();
+}
+
+// ---- the same over a proof-major batch (FoldMultiBatchArgs): in = [batch][m], out = [batch][m / S], proof b with its own challenge ----
+// One lane per proof turns the raw challenge into the proof's row of constants: cb[8 b + j] = beta_b^(2^k) * a.c_mont[j] for the
+// S - 1 slots j = S - (S >> k) + t the butterfly reads (a.c_mont holds the root-of-unity part only), the rest of the row 0.
+template <int STEPS>
+__global__ __launch_bounds__(256) void fri_fold_multi_batch_prep_kernel(FoldMultiBatchArgs p) {
+    constexpr int S = 1 << STEPS;
+    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= p.batch) return;
+    uint32_t bk = mont_mul(p.beta_raw[(size_t)b * p.beta_stride], R2_MONT);   // any u32 -> beta mod P, Montgomery form (field.rs:20-24)
+    uint32_t c[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+    for (int k = 0; k < STEPS; ++k) {
+#pragma unroll
+        for (int t = 0; t < (S >> (k + 1)); ++t) c[S - (S >> k) + t] = mont_mul(bk, p.a.c_mont[S - (S >> k) + t]);
+        if (k + 1 < STEPS) bk = mont_mul(bk, bk);
+    }
+    uint32_t* row = p.cb + (size_t)b * 8;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) row[j] = c[j];
+}
+template <int STEPS>
+__device__ __forceinline__ void fold_multi_batch_consts(const FoldMultiBatchArgs& p, size_t b, uint32_t (&c)[7]) {
+    constexpr int S = 1 << STEPS;
+    const uint32_t* row = p.cb + b * 8;
+#pragma unroll
+    for (int j = 0; j < 7; ++j) c[j] = j < S - 1 ? row[j] : 0u;
+}
+
+// one output per lane: per-proof outputs of fewer than 4 values, or buffers that are not 16-byte aligned
+template <int STEPS>
+__global__ __launch_bounds__(256) void fri_fold_multi_batch_kernel1(FoldMultiBatchArgs p) {
+    constexpr int S = 1 << STEPS;
+    const uint32_t log_q = p.a.log_m - STEPS;
+    const size_t q = (size_t)1 << log_q;
+    const size_t pos = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (pos >= ((size_t)p.batch << log_q)) return;
+    const size_t b = pos >> log_q, i = pos & (q - 1);
+    const uint32_t* in = p.a.in + (b << p.a.log_m);
+    uint32_t v[S];
+#pragma unroll
+    for (int t = 0; t < S; ++t) v[t] = in[i + t * q];
+    uint32_t c[7];
+    fold_multi_batch_consts<STEPS>(p, b, c);
+    p.a.out[pos] = fold_multi_core<STEPS>(c, p.a.scale_mont, v, pow_lookup(p.a.hinv, (uint32_t)(i << p.a.round)));
+}
+
+// four consecutive outputs of one proof per lane (m / S >= 4, so a group of four never straddles two proofs): S coalesced 16-byte
+// loads, one 16-byte store, one table look-up advanced by h^(-2^r)
+template <int STEPS>
+__global__ __launch_bounds__(256) void fri_fold_multi_batch_kernel(FoldMultiBatchArgs p) {
+    constexpr int S = 1 << STEPS;
+    const uint32_t log_q = p.a.log_m - STEPS;
+    const size_t q = (size_t)1 << log_q;
+    const size_t pos = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+    if (pos >= ((size_t)p.batch << log_q)) return;
+    const size_t b = pos >> log_q, i = pos & (q - 1);
+    const uint32_t* in = p.a.in + (b << p.a.log_m);
+    uint4 ld[S];
+#pragma unroll
+    for (int t = 0; t < S; ++t) ld[t] = reinterpret_cast<const uint4*>(in)[(i + t * q) >> 2];
+    uint32_t c[7];
+    fold_multi_batch_consts<STEPS>(p, b, c);
+    uint32_t xinv = pow_lookup(p.a.hinv, (uint32_t)(i << p.a.round));
+    const uint32_t step = pow_lookup(p.a.hinv, 1u << p.a.round);
+    uint32_t r[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        uint32_t v[S];
+#pragma unroll
+        for (int t = 0; t < S; ++t) v[t] = e == 0 ? ld[t].x : e == 1 ? ld[t].y : e == 2 ? ld[t].z : ld[t].w;
+        r[e] = fold_multi_core<STEPS>(c, p.a.scale_mont, v, xinv);
+        if (e < 3) xinv = mont_mul(xinv, step);
+    }
+    reinterpret_cast<uint4*>(p.a.out)[pos >> 2] = make_uint4(r[0], r[1], r[2], r[3]);
+}
+
+template <int STEPS>
+static void fold_multi_batch_launch(const FoldMultiBatchArgs& p, size_t total, bool wide, hipStream_t s) {
+    hipLaunchKernelGGL(fri_fold_multi_batch_prep_kernel<STEPS>, dim3((p.batch + 255) / 256), dim3(256), 0, s, p);
+    if (wide) hipLaunchKernelGGL(fri_fold_multi_batch_kernel<STEPS>, dim3((uint32_t)((total / 4 + 255) / 256)), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL(fri_fold_multi_batch_kernel1<STEPS>, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, s, p);
+}
+hipError_t launch_fri_fold_multi_batch(const FoldMultiBatchArgs& p, hipStream_t s, Profiler* prof) {
+    const FoldMultiArgs& a = p.a;
+    if (a.steps < 1 || a.steps > 3 || a.log_m < a.steps || a.log_m > 32 || p.batch < 1 || !p.beta_raw || !p.cb) return hipErrorInvalidValue;
+    const size_t m = (size_t)1 << a.log_m, q = m >> a.steps, total = (size_t)p.batch * q;
+    if ((size_t)p.batch * m > ((size_t)1 << 32)) return hipErrorInvalidValue;
+    ScopedKernelTimer tm(prof, K_FOLD, 4.0 * (double)p.batch * (double)(m + q), s);   // read batch * m words, write batch * m / S
+    const bool wide = q >= 4 && ((reinterpret_cast<uintptr_t>(a.in) | reinterpret_cast<uintptr_t>(a.out)) & 15u) == 0;
+    if (a.steps == 1) fold_multi_batch_launch<1>(p, total, wide, s);
+    else if (a.steps == 2) fold_multi_batch_launch<2>(p, total, wide, s);
+    else fold_multi_batch_launch<3>(p, total, wide, s);
     return hipGetLastError();
 }
 

@@ -224,6 +224,18 @@ struct FoldMultiArgs {
     uint32_t c_mont[7];
 };
 hipError_t launch_fri_fold_multi(const FoldMultiArgs& a, hipStream_t s, Profiler* prof = nullptr);
+// The same for a proof-major batch: a.in = [batch][m], a.out = [batch][m / S], proof b folds with its own challenge
+// beta_raw[b * beta_stride] (a raw u32, reduced mod P on the device).  a.c_mont holds only the root-of-unity part of each constant;
+// a one-lane-per-proof launch ahead of the fold writes cb[8 b + j] = beta_b^(2^k) * a.c_mont[j] (Montgomery form), which the fold
+// reads in place of the kernel argument.  cb: 8 * batch words of scratch.  batch * m <= 2^32; any batch >= 1.
+struct FoldMultiBatchArgs {
+    FoldMultiArgs a;
+    const uint32_t* beta_raw;
+    uint32_t beta_stride;     // in words
+    uint32_t* cb;
+    uint32_t batch;
+};
+hipError_t launch_fri_fold_multi_batch(const FoldMultiBatchArgs& a, hipStream_t s, Profiler* prof = nullptr);
 
 // Merkle tree over m = 2^log_m u32 leaves.  nodes: (2m-1) * 8 words, heap order
 // (merkle.rs:14-51), each node the eight SHA-256 state words.

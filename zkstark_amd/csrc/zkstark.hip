@@ -1541,6 +1541,17 @@ int zk_dev_fri_fold_multi(const zk_dom* d, const uint32_t* d_in, uint32_t* d_out
     HIPCHK(hipSetDevice(d->device));
     return dom_fold_multi(d, d_in, d_out, log_m, round, steps, beta_raw, (hipStream_t)stream, dev_prof());
 }
+int zk_dev_fri_fold_multi_batch(const zk_dom* d, const uint32_t* d_in, uint32_t* d_out, uint32_t log_m, uint32_t round, uint32_t steps,
+                                const uint32_t* d_beta_raw, uint32_t* d_work, uint32_t batch, void* stream) {
+    if (!d || !d_in || !d_out || !d_beta_raw || !d_work) return fail(ZK_ERR_INVALID, "zk_dev_fri_fold_multi_batch: null argument");
+    if (steps < 1 || steps > kMaxFoldLog) return fail(ZK_ERR_INVALID, "zk_dev_fri_fold_multi_batch: steps must be 1..%u (got %u)", kMaxFoldLog, steps);
+    if (round + steps > d->log_n || log_m + round != d->L)
+        return fail(ZK_ERR_INVALID, "zk_dev_fri_fold_multi_batch: layer 2^%u, rounds %u..%u do not fit a domain of %u rounds", log_m, round, round + steps, d->log_n);
+    if (batch < 1 || ((uint64_t)batch << log_m) > ((uint64_t)1 << 32))
+        return fail(ZK_ERR_INVALID, "zk_dev_fri_fold_multi_batch: need batch >= 1 and batch * 2^log_m <= 2^32 (got %u, log_m %u)", batch, log_m);
+    HIPCHK(hipSetDevice(d->device));
+    return dom_fold_multi_batch(d, d_in, d_out, log_m, round, steps, d_beta_raw, 1, d_work, batch, (hipStream_t)stream, dev_prof());
+}
 int zk_dev_trace_fibsq_batch(const uint32_t* d_a0, const uint32_t* d_a1, uint32_t batch, uint32_t count, uint32_t* d_out, void* stream) {
     if ((batch && (!d_a0 || !d_a1 || !d_out))) return fail(ZK_ERR_INVALID, "zk_dev_trace_fibsq_batch: null argument");
     HIPCHK(launch_trace_fibsq_batch(d_a0, d_a1, batch, count, d_out, (hipStream_t)stream));

@@ -446,9 +446,11 @@ class BatchContext:
     """2^log_batch proofs of one size in lockstep (zk_batch_*): every stage is one
     launch over the whole batch; each proof has its own channel and is byte-identical to Context.prove()."""
 
-    def __init__(self, log_n=10, log_blowup=3, log_batch=4, device=0, hash="sha256", queries=1, grind_bits=0):
+    def __init__(self, log_n=10, log_blowup=3, log_batch=4, device=0, hash="sha256", queries=1, grind_bits=0, fold_log=1):
+        """fold_log: FRI folding factor 2^fold_log between commitments for every proof of the batch (zk_batch_set_fold; 1 = the
+        reference)."""
         self.log_n, self.log_blowup, self.log_batch, self.hash, self.queries = log_n, log_blowup, log_batch, hash, queries
-        self.grind_bits = grind_bits
+        self.grind_bits, self.fold_log = grind_bits, 1
         self.n, self.batch = 1 << log_n, 1 << log_batch
         self._h = C.c_void_p()
         check(_lib.load().zk_batch_create(device, log_n, log_blowup, log_batch, C.byref(self._h)))
@@ -458,6 +460,13 @@ class BatchContext:
             check(_lib.load().zk_batch_set_queries(self._h, queries))
         if grind_bits:
             check(_lib.load().zk_batch_set_grinding(self._h, grind_bits))
+        if fold_log != 1:
+            self.set_fold(fold_log)
+
+    def set_fold(self, fold_log):
+        """zk_batch_set_fold: fold by 2^fold_log (1..3) between commitments from the next zk_batch_prove on."""
+        check(_lib.load().zk_batch_set_fold(self._h, fold_log))
+        self.fold_log = fold_log
 
     def close(self):
         if getattr(self, "_h", None):
@@ -498,7 +507,7 @@ class BatchContext:
 
     def prove_raw(self):
         """Returns (proof bytes [batch][len] as a uint8 array, states [batch][32])."""
-        plen = _lib.load().zk_proof_data_len_grind(self.log_n, self.log_blowup, self.queries, self.grind_bits)
+        plen = _lib.load().zk_proof_data_len_fold(self.log_n, self.log_blowup, self.queries, self.grind_bits, self.fold_log)
         data = np.zeros((self.batch, plen), dtype=np.uint8)
         states = np.zeros((self.batch, 32), dtype=np.uint8)
         check(_lib.load().zk_batch_prove(self._h, data.ctypes.data_as(C.c_void_p), plen, states.ctypes.data_as(C.c_void_p)))
@@ -508,7 +517,7 @@ class BatchContext:
         data, states = self.prove_raw()
         last = self.public_last()
         return [Proof(states[p].tobytes(), data[p].tobytes(), self.log_n, self.log_blowup, int(last[p]), self.hash, self.queries,
-                      self.grind_bits) for p in range(self.batch)]
+                      self.grind_bits, self.fold_log) for p in range(self.batch)]
 
 
 _ERR_VERIFY = -6
