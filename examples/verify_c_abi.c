@@ -4,7 +4,9 @@
  * verifies all 64 with one zk_verifier_run: strict (the transcript replay, as zk_verify_strict) and plain (the reference's
  * checks, proof.rs:15).  Prints the rejected index and the check it stopped at, which is the CPU verifier's number.
  *   gcc -O2 -Iinclude examples/verify_c_abi.c -Lzkstark_amd -lzkstark_amd -Wl,-rpath,$PWD/zkstark_amd -o verify_c_abi
- *   ./verify_c_abi [bad_index]
+ *   ./verify_c_abi [bad_index [fold_log]]
+ * fold_log 2 or 3: the batch is proved with that FRI folding factor (zk_batch_set_fold) and the verifier follows it
+ * (zk_verifier_set_fold); the CPU number then comes from zk_verify_fold.
  */
 #include <stdint.h>
 #include <stdio.h>
@@ -44,13 +46,15 @@ static size_t report(const char *mode, const int32_t *checks, size_t count) {
 int main(int argc, char **argv) {
     const uint32_t log_n = 10, log_b = 3, log_batch = 6;               /* prover.rs:48-57, 64 proofs */
     size_t bad_index = argc > 1 ? (size_t)atoi(argv[1]) : 17;
+    const uint32_t fold_log = argc > 2 ? (uint32_t)atoi(argv[2]) : 1;
     if (zk_abi_version() != ZK_ABI_VERSION) {                           /* the library on the path was built from another zkstark_amd.h */
         fprintf(stderr, "libzkstark_amd speaks ABI version %u, this program was compiled against %u\n", zk_abi_version(), ZK_ABI_VERSION);
         return 2;
     }
     zk_batch *b = NULL;
     CHECK(zk_batch_create(0, log_n, log_b, log_batch, &b));
-    size_t batch = zk_batch_size(b), plen = zk_proof_data_len(log_n, log_b);
+    if (fold_log != 1) CHECK(zk_batch_set_fold(b, fold_log));
+    size_t batch = zk_batch_size(b), plen = zk_proof_data_len_fold(log_n, log_b, 1, 0, fold_log);
     if (bad_index >= batch) bad_index = batch - 1;
     uint32_t *a0 = malloc(batch * 4), *a1 = malloc(batch * 4), *last = malloc(batch * 4);
     for (size_t p = 0; p < batch; ++p) { a0[p] = 1; a1[p] = 3141592 + (uint32_t)p; }
@@ -61,12 +65,14 @@ int main(int argc, char **argv) {
     CHECK(zk_batch_prove(b, proofs, plen, states));
     zk_batch_destroy(b);
 
-    /* one byte of the first sibling of the f(x) path: after the roots and challenges (76 + 36 log_n bytes), the free term (4),
-     * the query raw (4), f(x) (4) and the path's count (8) */
-    proofs[bad_index * plen + 76 + 36 * log_n + 4 + 4 + 4 + 8] ^= 0x01;
+    /* one byte of the first sibling of the f(x) path: after the roots and challenges (76 + 36 bytes per committed FRI layer: log_n
+     * of them, or one per group of fold_log rounds), the free term (4), the query raw (4), f(x) (4) and the path's count (8) */
+    const size_t layers = (log_n + fold_log - 1) / fold_log;
+    proofs[bad_index * plen + 76 + 36 * layers + 4 + 4 + 4 + 8] ^= 0x01;
 
     zk_verifier *v = NULL;
     CHECK(zk_verifier_create(0, log_n, log_b, &v));
+    if (fold_log != 1) CHECK(zk_verifier_set_fold(v, fold_log));
     int rc = zk_verifier_run(v, proofs, plen, batch, states, last, checks);      /* warm-up */
     double t0 = now_ms();
     rc = zk_verifier_run(v, proofs, plen, batch, states, last, checks);
@@ -80,7 +86,8 @@ int main(int argc, char **argv) {
     bad += report("plain", checks, batch);
     /* the CPU verifier's number for the same proof */
     int32_t cpu = 0;
-    zk_verify_check(proofs + bad_index * plen, plen, NULL, log_n, log_b, last[bad_index], ZK_HASH_SHA256, 1, &cpu);
+    if (fold_log != 1) zk_verify_fold(proofs + bad_index * plen, plen, NULL, log_n, log_b, last[bad_index], ZK_HASH_SHA256, 1, 0, fold_log, &cpu);
+    else zk_verify_check(proofs + bad_index * plen, plen, NULL, log_n, log_b, last[bad_index], ZK_HASH_SHA256, 1, &cpu);
     printf("cpu plain: proof %zu check %d\n", bad_index, cpu);
     zk_verifier_destroy(v);
     free(a0); free(a1); free(last); free(proofs); free(states); free(checks);

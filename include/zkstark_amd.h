@@ -179,7 +179,7 @@ int zk_ctx_get_early_launch(const zk_ctx *ctx);
  * 0.274 / 0.296 / 0.264 ms -- fold_log 2 is 8 % SLOWER than the default there and fold_log 3 only 4 % faster, because the default
  * folds the small layers on the host thread and fuses every fold into its leaf hashing, while a folded proof pays one fold launch
  * and one tree launch per group (docs/LOG.md "Folding factor").
- * zk_shard_* / zk_tail_* and zk_verifier_* stay at factor 2. */
+ * zk_verifier_* follows with zk_verifier_set_fold; zk_shard_* / zk_tail_* stay at factor 2. */
 int zk_ctx_set_fold(zk_ctx *ctx, uint32_t fold_log);
 uint32_t zk_ctx_get_fold(const zk_ctx *ctx);
 /* The HIP stream every stage is enqueued on (hipStream_t). */
@@ -301,7 +301,7 @@ int zk_batch_set_grinding(zk_batch *b, uint32_t grind_bits);
  * 1 + r0 + steps of the whole batch, one tree is built over it and the per-proof roots are committed under that id; the ids in
  * between are neither computed nor committed.  Every proof is byte for byte what zk_prove returns from a context with the same
  * (log_n, log_blowup, hash, n_queries, grind_bits, fold_log) and trace, its state too; its length is zk_proof_data_len_fold and it is
- * checked with zk_verify_fold (zk_verifier_* stays at factor 2).  After a folded zk_batch_prove, zk_batch_merkle_nodes of a tree id
+ * checked with zk_verify_fold, or in batches with zk_verifier_set_fold + zk_verifier_run.  After a folded zk_batch_prove, zk_batch_merkle_nodes of a tree id
  * the proof did not build returns ZK_ERR_STATE; a later proof with fold_log 1 materialises every id again.  The decommitment buffers
  * are re-sized here (a folded proof opens up to 8 values per group).  Device memory: the layers and trees of the skipped ids stay
  * allocated (the batch can go back to fold_log 1 at any time); fold_log > 1 adds 32 bytes per proof.
@@ -399,8 +399,16 @@ int zk_verifier_set_queries(zk_verifier *v, uint32_t n_queries);   /* 1..64, as 
 int zk_verifier_set_hash(zk_verifier *v, int hash_kind);
 /* Proofs made with zk_ctx_set_grinding(grind_bits): checks_out as zk_verify_grind gives them (-1998 in strict mode). */
 int zk_verifier_set_grinding(zk_verifier *v, uint32_t grind_bits);
-/* count proofs at proofs + i*stride, each exactly zk_proof_data_len_queries(log_n, log_blowup, q) bytes (stride >= that, any
- * alignment); states: count*32 bytes, or NULL = not strict; public_last[count].  checks_out[i] = what zk_verify_check returns
+/* Proofs made with zk_ctx_set_fold / zk_batch_set_fold(fold_log): fold_log 1..3, default 1, from the next zk_verifier_run on (a
+ * verifier may change factor between runs; its buffers grow for the longer proofs).  checks_out as zk_verify_fold gives them:
+ * the replay counts 3 + G + q challenges, and "k" in -(100+k) / -(300+k) / -(400+k) is the group index.  Out of range:
+ * ZK_ERR_INVALID and the setting is unchanged.  zk_verifier_get_fold: the current fold_log, 0 for a null verifier.
+ * Measured (profiles/verify_fold_bench.txt). */
+int zk_verifier_set_fold(zk_verifier *v, uint32_t fold_log);
+uint32_t zk_verifier_get_fold(const zk_verifier *v);
+/* count proofs at proofs + i*stride, each exactly zk_proof_data_len_fold(log_n, log_blowup, q, grind_bits, fold_log) bytes (with
+ * the defaults zk_proof_data_len_queries(log_n, log_blowup, q); stride >= that, any alignment); states: count*32 bytes, or NULL =
+ * not strict; public_last[count].  checks_out[i] = what zk_verify_fold (fold_log 1: zk_verify_grind, zk_verify_check) returns
  * in check_out for proof i, for EVERY input.  Returns ZK_OK if all were accepted, ZK_ERR_VERIFY if any was rejected
  * (zk_last_error names the first rejected index and its check), other errors as usual.  count = 0 is a no-op. */
 int zk_verifier_run(zk_verifier *v, const uint8_t *proofs, size_t stride, size_t count, const uint8_t *states,

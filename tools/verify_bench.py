@@ -5,11 +5,17 @@ call's own synchronisation), and the CPU's time for the same proofs with zk_veri
 pool (ctypes releases the GIL).  --profile adds per-kernel times from a separate `rocprofv3 --kernel-trace --stats` run per
 shape (this script again with --inner).  Not part of bench.py: it measures this one feature.
 
-    python tools/verify_bench.py [--steps 20] [--warmup 3] [--profile] [--only NAME,...]
+--fold K[,K...] measures proofs with the FRI folding factor 2^K (BatchContext(fold_log=K), Verifier(fold_log=K); the CPU side
+is zk_verify_fold).  With several K the timed calls are taken in --blocks rounds that visit every K in turn, in this one
+process, so that drift of the machine falls on every K alike; a result is then named NAME_kK and carries the median, minimum
+and maximum over all its calls.
+
+    python tools/verify_bench.py [--steps 20] [--warmup 3] [--profile] [--only NAME,...] [--fold 1,2,3 --blocks 5]
 """
 import argparse
 import concurrent.futures
 import csv
+import ctypes as C
 import glob
 import json
 import os
@@ -45,12 +51,12 @@ PROFILED = ["ref_strict_1024", "ref_plain_1024", "2e20_strict_1024", "2e24_q1_st
 _cache = {}
 
 
-def proofs_for(log_n, log_b, q, hash, count):
+def proofs_for(log_n, log_b, q, hash, count, fold=1):
     """(data [count, len] uint8, states [count, 32], public_last [count]) of valid proofs."""
-    key = (log_n, log_b, q, hash)
+    key = (log_n, log_b, q, hash, fold)
     if key not in _cache:
         log_batch = 10 if log_n <= 10 else (6 if log_n <= 17 else 1)
-        with zk.BatchContext(log_n, log_b, log_batch, hash=hash, queries=q) as bc:
+        with zk.BatchContext(log_n, log_b, log_batch, hash=hash, queries=q, fold_log=fold) as bc:
             bc.gen_fibsq([1] * bc.batch, [3141592 + p for p in range(bc.batch)])
             data, states = bc.prove_raw()
             _cache[key] = (data, states, bc.public_last())
@@ -59,29 +65,41 @@ def proofs_for(log_n, log_b, q, hash, count):
     return np.ascontiguousarray(data[idx]), np.ascontiguousarray(states[idx]), np.ascontiguousarray(last[idx])
 
 
-def gpu_times(shape, steps, warmup):
+def gpu_times(shape, steps, warmup, folds=(1,), blocks=1):
+    """{K: [ms of every timed call]}: `blocks` rounds over the K of `folds`, `steps` calls each, one verifier per K."""
     log_n, log_b, q, hash, count, strict = shape
-    data, states, last = proofs_for(log_n, log_b, q, hash, count)
-    with zk.Verifier(log_n, log_b, hash=hash, queries=q) as v:
-        for _ in range(warmup):
-            assert (v.verify_raw(data, last, states if strict else None) == 0).all()
-        ts = []
-        for _ in range(steps):
-            t0 = time.perf_counter()
-            v.verify_raw(data, last, states if strict else None)
-            ts.append((time.perf_counter() - t0) * 1e3)
+    vs, ts = {}, {K: [] for K in folds}
+    try:
+        for K in folds:
+            data, states, last = proofs_for(log_n, log_b, q, hash, count, K)
+            vs[K] = (zk.Verifier(log_n, log_b, hash=hash, queries=q, fold_log=K), data, states if strict else None, last)
+            for _ in range(warmup):
+                assert (vs[K][0].verify_raw(data, last, vs[K][2]) == 0).all()
+        for _ in range(blocks):
+            for K in folds:
+                v, data, states, last = vs[K]
+                for _ in range(steps):
+                    t0 = time.perf_counter()
+                    v.verify_raw(data, last, states)
+                    ts[K].append((time.perf_counter() - t0) * 1e3)
+    finally:
+        for v in vs.values():
+            v[0].close()
     return ts
 
 
-def cpu_ms(shape, threads):
+def cpu_ms(shape, threads, fold=1):
     log_n, log_b, q, hash, count, strict = shape
-    data, states, last = proofs_for(log_n, log_b, q, hash, count)
+    data, states, last = proofs_for(log_n, log_b, q, hash, count, fold)
     lib = _lib.load()
     hk = zk.host.HASHES[hash]
     plen = data.shape[1]
     rows = [(data[i].ctypes.data, states[i].ctypes.data if strict else None, int(last[i])) for i in range(count)]
+    check = C.c_int32 * 1
 
     def one(r):
+        if fold != 1:
+            return lib.zk_verify_fold(r[0], plen, r[1], log_n, log_b, r[2], hk, q, 0, fold, check())
         return lib.zk_verify_queries(r[0], plen, r[1], log_n, log_b, r[2], hk, q)
 
     if threads == 1:
@@ -125,29 +143,35 @@ def main():
     ap.add_argument("--profile", action="store_true")
     ap.add_argument("--only", default="")
     ap.add_argument("--inner", default="")
+    ap.add_argument("--fold", default="1", help="folding factors 2^K to measure, e.g. 1,2,3 (interleaved in one process)")
+    ap.add_argument("--blocks", type=int, default=1, help="rounds over the K of --fold, each of --steps calls per K")
     a = ap.parse_args()
+    folds = tuple(int(k) for k in a.fold.split(","))
     if a.inner:                                       # under rocprofv3: the timed GPU calls of one shape only
-        gpu_times(SHAPES[a.inner], a.steps, 1)
+        gpu_times(SHAPES[a.inner], a.steps, 1, folds[:1])
         return
     names = [n for n in SHAPES if not a.only or n in a.only.split(",")]
     res = {}
     for name in names:
         shape = SHAPES[name]
-        ts = sorted(gpu_times(shape, a.steps, a.warmup))
-        c1 = cpu_ms(shape, 1)
-        c16 = cpu_ms(shape, 16)
-        res[name] = {"log_n": shape[0], "log_blowup": shape[1], "queries": shape[2], "hash": shape[3], "count": shape[4],
-                     "strict": shape[5], "proof_bytes": int(_lib.load().zk_proof_data_len_queries(shape[0], shape[1], shape[2])),
-                     "gpu_ms_median": round(ts[len(ts) // 2], 4), "gpu_ms_min": round(ts[0], 4),
-                     "cpu_1t_ms": round(c1, 3), "cpu_16t_ms": round(c16, 3),
-                     "speedup_vs_16t": round(c16 / ts[len(ts) // 2], 2)}
-        print(f"# {name}: {res[name]}", file=sys.stderr, flush=True)
+        times = gpu_times(shape, a.steps, a.warmup, folds, a.blocks)
+        for K in folds:
+            ts = sorted(times[K])
+            c1 = cpu_ms(shape, 1, K)
+            c16 = cpu_ms(shape, 16, K)
+            key = name if folds == (1,) else f"{name}_k{K}"
+            res[key] = {"log_n": shape[0], "log_blowup": shape[1], "queries": shape[2], "hash": shape[3], "count": shape[4],
+                        "strict": shape[5], "fold_log": K, "proof_bytes": int(_lib.load().zk_proof_data_len_fold(shape[0], shape[1], shape[2], 0, K)),
+                        "gpu_ms_median": round(ts[len(ts) // 2], 4), "gpu_ms_min": round(ts[0], 4), "gpu_ms_max": round(ts[-1], 4),
+                        "cpu_1t_ms": round(c1, 3), "cpu_16t_ms": round(c16, 3),
+                        "speedup_vs_16t": round(c16 / ts[len(ts) // 2], 2)}
+            print(f"# {key}: {res[key]}", file=sys.stderr, flush=True)
     if a.profile:
         for name in names:
-            if name in PROFILED:
+            if name in PROFILED and name in res:
                 res[name]["kernels_ms_per_call"] = profile(name, 5)
     cross = {n: res[n] for n in ("2e24_q1_strict_1", "2e24_q1_strict_8", "2e24_q1_strict_16", "2e24_q1_strict_64") if n in res}
-    line = {"tool": "verify_bench", "build_hash": _lib.build_hash(), "steps": a.steps, "warmup": a.warmup, "shapes": res,
+    line = {"tool": "verify_bench", "build_hash": _lib.build_hash(), "steps": a.steps, "warmup": a.warmup, "fold": list(folds), "blocks": a.blocks, "shapes": res,
             "crossover_2e24_strict": {n: {"count": r["count"], "gpu_ms": r["gpu_ms_median"], "cpu_16t_ms": r["cpu_16t_ms"]} for n, r in cross.items()}}
     print(json.dumps(line), flush=True)
 

@@ -11,6 +11,15 @@
 //   * strict mode: a transcript failure wins (verify_transcript runs first on the CPU), so it has its own result.
 // The raw-value rules of verify_proof are kept: values are reduced % P before arithmetic, but fv[3] is compared unreduced
 // with cp0, and the FRI expectation (lx[k + 1] or the free term) unreduced with a reduced calc.  Leaf hashes take the raw word.
+//
+// Folding factor 2^K (zk_verifier_set_fold, K = 2 or 3; transcript.hpp: verify_transcript_fold, then verify_proof_fold): the R
+// rounds come in G = ceil(R / K) groups, group j opens the s_j = 2^steps_j values of its input layer (round r0 = j K) and then
+// their s_j paths of L - r0 digests, so the layout is fixed in the same way and only the last group can be short.  The order
+// keys are query * (5 + 9G) + position: 0 (-2), 1..4 (-4..-7), 5 + j (the fold comparison of group j), 5 + G + 8j + t (path t
+// of group j: -(300 + j) for t = 0, -(400 + j) for t >= 1).  The fold comparison inverts x once per (proof, query) and squares
+// the inverse from round to round; the inverse powers of the 8th root of unity that tell the s points of a group apart come
+// with the launch arguments (residues are canonical, so an algebraically equal evaluation is bit-exact).  K = 1 runs the
+// kernels it always ran: the paths and transcript kernels are templates whose unfolded instance is the code as it was.
 #include <cstdio>
 #include <cstring>
 #include <mutex>
@@ -50,6 +59,9 @@ struct VerifyArgs {
     uint32_t gmask;             // grinding: the state after the nonce commit must have (word 0 & gmask) == 0
     uint32_t qbase;             // first word of query 0's openings
     uint32_t per_q;             // words of one query's openings
+    // folding factor 2^K (K > 1 only): G groups of K rounds, the last one of ls <= K; constants in Montgomery form
+    uint32_t K, G, ls;
+    uint32_t inv2m, wm1, wm2, wm3;   // 1/2 and w, w^2, w^3 for w = the inverse of the primitive 8th root of unity h^(N/8)
 };
 
 __device__ __forceinline__ uint32_t be_word(const uint32_t* p) { return __builtin_bswap32(*p); }
@@ -74,7 +86,29 @@ __device__ __forceinline__ uint32_t layer_word(const VerifyArgs& a, uint32_t qk,
     return a.qbase + qk * a.per_q + 4u * (3u + 8u * a.L) + 6u * k + 16u * (k * a.L - k * (k - 1u) / 2u);
 }
 __device__ __forceinline__ uint32_t query_tp(const VerifyArgs& a, const uint32_t* pr, uint32_t qk) {
-    return pr[20u + 9u * a.R + a.gw + qk] % (a.N - 2u * a.B);                // tp = test_raw % (N - 2B)
+    return pr[a.qbase - a.q + qk] % (a.N - 2u * a.B);                        // tp = test_raw % (N - 2B); the raws end at qbase
+}
+
+// Folded layout: the first word of group j's openings (s values, then s paths of a u64 count and L - jK digests).  Every group
+// before j is full, so the offset has a closed form.
+__device__ __forceinline__ uint32_t group_word(const VerifyArgs& a, uint32_t qk, uint32_t j) {
+    return a.qbase + qk * a.per_q + 4u * (3u + 8u * a.L) + ((3u * j + 8u * (a.L * j - a.K * (j * (j - 1u) / 2u))) << a.K);
+}
+__device__ __forceinline__ uint32_t group_size(const VerifyArgs& a, uint32_t j) { return 1u << (j + 1u < a.G ? a.K : a.ls); }
+
+// proof.rs:63-77: the composition polynomial at x from f(x), f(gx), f(g^2 x), against the raw cp(x) of the proof
+__device__ __forceinline__ bool cp0_matches(const VerifyArgs& a, const uint32_t* pr, uint32_t p, uint32_t fq, uint32_t x) {
+    const uint32_t fb = 3u + 8u * a.L;
+    const uint32_t f_x = pr[fq] % P, f_gx = pr[fq + fb] % P, f_ggx = pr[fq + 2u * fb] % P, cp_raw = pr[fq + 3u * fb];
+    const uint32_t p0 = dmul(sub(f_x, 1u), dinv(sub(x, 1u)));
+    const uint32_t p1 = dmul(sub(f_x, a.pub[p] % P), dinv(sub(x, a.gm2)));
+    const uint32_t num = sub(sub(f_ggx, dmul(f_gx, f_gx)), dmul(f_x, f_x));
+    uint32_t xn = x;
+    for (uint32_t i = 0; i < a.log_n; ++i) xn = dmul(xn, xn);
+    const uint32_t den = dmul(sub(xn, 1u), dinv(dmul(dmul(sub(x, a.gm3), sub(x, a.gm2)), sub(x, a.gm1))));
+    const uint32_t p2 = dmul(num, dinv(den));
+    const uint32_t cp0 = add(add(dmul(pr[8] % P, p0), dmul(pr[9] % P, p1)), dmul(pr[10] % P, p2));
+    return cp0 == cp_raw;
 }
 
 // (1) layout + algebra: one lane per (proof, query).  Path counts, the cp0 relation (-2) and the R FRI relations (-(100 + k)).
@@ -100,19 +134,7 @@ __global__ void __launch_bounds__(kVerifyThreads) verify_algebra_kernel(VerifyAr
     const uint32_t tp = query_tp(a, pr, qk);
     const uint32_t x = dmul(GEN_W, dpow(a.h, tp));
     int32_t key = kNoFailure;
-    {   // proof.rs:63-77
-        const uint32_t fb = 3u + 8u * a.L;
-        const uint32_t f_x = pr[fq] % P, f_gx = pr[fq + fb] % P, f_ggx = pr[fq + 2u * fb] % P, cp_raw = pr[fq + 3u * fb];
-        const uint32_t p0 = dmul(sub(f_x, 1u), dinv(sub(x, 1u)));
-        const uint32_t p1 = dmul(sub(f_x, a.pub[p] % P), dinv(sub(x, a.gm2)));
-        const uint32_t num = sub(sub(f_ggx, dmul(f_gx, f_gx)), dmul(f_x, f_x));
-        uint32_t xn = x;
-        for (uint32_t i = 0; i < a.log_n; ++i) xn = dmul(xn, xn);
-        const uint32_t den = dmul(sub(xn, 1u), dinv(dmul(dmul(sub(x, a.gm3), sub(x, a.gm2)), sub(x, a.gm1))));
-        const uint32_t p2 = dmul(num, dinv(den));
-        const uint32_t cp0 = add(add(dmul(pr[8] % P, p0), dmul(pr[9] % P, p1)), dmul(pr[10] % P, p2));
-        if (cp0 != cp_raw) key = (int32_t)(qk * keys);
-    }
+    if (!cp0_matches(a, pr, p, fq, x)) key = (int32_t)(qk * keys);
     // proof.rs:101-126, the relations in k order: the first failing one is the smallest key of this lane
     uint32_t xk = x;
     for (uint32_t k = 0; k < a.R && key == kNoFailure; ++k) {
@@ -124,6 +146,75 @@ __global__ void __launch_bounds__(kVerifyThreads) verify_algebra_kernel(VerifyAr
         const uint32_t expect = k + 1u < a.R ? pr[layer_word(a, qk, k + 1u)] : pr[19u + 9u * a.R];
         if (calc != expect) key = (int32_t)(qk * keys + 5u + k);
         xk = dmul(xk, xk);
+    }
+    if (key != kNoFailure) atomicMin(&a.best[p], key);
+}
+
+// STEPS successive reference folds (proof.rs:110-113) of the 2^STEPS values of one group, in registers: round k pairs t with
+// t + cnt and divides by twice the point of t, x^(2^(r0 + k)) om^(2^k t) for the 2^STEPS-th root of unity om.  ixk comes in as
+// x^-(2^r0) and leaves squared STEPS times; om^-(2^k t) is w^e with e = (8 >> STEPS) (t << k) in 0..3, a constant once unrolled.
+template <int STEPS>
+__device__ __forceinline__ uint32_t fold_group(const VerifyArgs& a, const uint32_t* vals, uint32_t beta, uint32_t& ixk) {
+    constexpr int S = 1 << STEPS;
+    uint32_t v[S];
+#pragma unroll
+    for (int t = 0; t < S; ++t) v[t] = vals[t] % P;
+    uint32_t bk = beta;
+#pragma unroll
+    for (int k = 0; k < STEPS; ++k) {
+        const uint32_t m = dmul(bk, ixk);                 // beta^(2^k) / x^(2^(r0 + k))
+#pragma unroll
+        for (int t = 0; t < (S >> (k + 1)); ++t) {
+            const int e = (8 >> STEPS) * (t << k);
+            const uint32_t lo = v[t], hi = v[t + (S >> (k + 1))];
+            uint32_t h = dmul(sub(lo, hi), m);
+            if (e != 0) h = mont_mul(h, e == 1 ? a.wm1 : e == 2 ? a.wm2 : a.wm3);
+            v[t] = mont_mul(add(add(lo, hi), h), a.inv2m);     // ((lo + hi) + beta' (lo - hi) / point) / 2
+        }
+        ixk = dmul(ixk, ixk);
+        bk = dmul(bk, bk);
+    }
+    return v[0];
+}
+
+// (1) for a folded proof: one lane per (proof, query).  Path counts, the cp0 relation (-2) and the G fold comparisons
+// (-(100 + j)); K is the folding factor of the full groups, the short last group (a.ls < K) has its own instance.
+template <int K>
+__global__ void __launch_bounds__(kVerifyThreads) verify_fold_algebra_kernel(VerifyArgs a) {
+    const uint64_t lane = (uint64_t)blockIdx.x * kVerifyThreads + threadIdx.x;
+    if (lane >= (uint64_t)a.count * a.q) return;
+    const uint32_t p = (uint32_t)(lane / a.q), qk = (uint32_t)(lane % a.q);
+    const uint32_t* pr = a.proofs + (size_t)p * a.words;
+    const uint32_t keys = 5u + 9u * a.G;
+    const uint32_t fq = a.qbase + qk * a.per_q;
+    bool ok = true;
+    for (uint32_t j = 0; j < 4; ++j) {
+        const uint32_t* c = pr + fq + j * (3u + 8u * a.L) + 1u;
+        ok = ok && c[0] == a.L && c[1] == 0u;
+    }
+    for (uint32_t j = 0; j < a.G; ++j) {
+        const uint32_t s = group_size(a, j), len = a.L - j * (uint32_t)K;
+        const uint32_t* c = pr + group_word(a, qk, j) + s;
+        for (uint32_t t = 0; t < s; ++t) ok = ok && c[t * (2u + 8u * len)] == len && c[t * (2u + 8u * len) + 1u] == 0u;
+    }
+    if (!ok) { a.malformed[p] = 1u; return; }
+
+    const uint32_t tp = query_tp(a, pr, qk);
+    const uint32_t x = dmul(GEN_W, dpow(a.h, tp));
+    int32_t key = kNoFailure;
+    if (!cp0_matches(a, pr, p, fq, x)) key = (int32_t)(qk * keys);
+    // proof.rs:101-126 widened, the groups in j order: the first failing one is the smallest key of this lane
+    uint32_t ixk = dinv(x);                               // x = 5 h^tp is never zero: the one inversion of this lane's folds
+#pragma unroll 1
+    for (uint32_t j = 0; j < a.G && key == kNoFailure; ++j) {
+        const uint32_t* vals = pr + group_word(a, qk, j);
+        const uint32_t beta = pr[19u + 9u * j] % P;
+        uint32_t calc;
+        if (j + 1u < a.G || a.ls == (uint32_t)K) calc = fold_group<K>(a, vals, beta, ixk);
+        else if (K == 3 && a.ls == 2u) calc = fold_group<2>(a, vals, beta, ixk);
+        else calc = fold_group<1>(a, vals, beta, ixk);
+        const uint32_t expect = j + 1u < a.G ? pr[group_word(a, qk, j + 1u)] : pr[19u + 9u * a.G];
+        if (calc != expect) key = (int32_t)(qk * keys + 5u + j);
     }
     if (key != kNoFailure) atomicMin(&a.best[p], key);
 }
@@ -141,11 +232,12 @@ __device__ __forceinline__ Digest vinner(const Digest& l, const Digest& r) {
 
 // (2) paths: one lane per (proof, query, path slot).  blockIdx.y = query * (4 + 2R) + slot and the proof on the lane, so every
 // lane of a wave walks a path of the same length; left / right is a select per level (merkle.rs:82-110).
-template <int HASH>
+// FOLD: 4 + sum s_j slots; slot 4 + (j << K) + t is path t of group j, against the root of that group's input layer.
+template <int HASH, bool FOLD>
 __global__ void __launch_bounds__(kVerifyThreads) verify_paths_kernel(VerifyArgs a) {
     const uint32_t p = blockIdx.x * kVerifyThreads + threadIdx.x;
     if (p >= a.count) return;
-    const uint32_t slots = 4u + 2u * a.R;
+    const uint32_t slots = FOLD ? 4u + ((a.G - 1u) << a.K) + (1u << a.ls) : 4u + 2u * a.R;
     const uint32_t qk = blockIdx.y / slots, slot = blockIdx.y % slots;
     const uint32_t* pr = a.proofs + (size_t)p * a.words;
     const uint32_t tp = query_tp(a, pr, qk);
@@ -157,6 +249,15 @@ __global__ void __launch_bounds__(kVerifyThreads) verify_paths_kernel(VerifyArgs
         idx = tp + (slot < 3u ? slot * a.B : 0u);
         rootw = slot < 3u ? 0u : 11u;
         pos = 1u + slot;
+    } else if constexpr (FOLD) {                          // group j at (tp % size + t size / s) % size
+        const uint32_t j = (slot - 4u) >> a.K, t = (slot - 4u) & ((1u << a.K) - 1u);
+        const uint32_t s = group_size(a, j), gw = group_word(a, qk, j), size = a.N >> (j * a.K);
+        plen = a.L - j * a.K;
+        val_w = gw + t;
+        path_w = gw + s + t * (2u + 8u * plen) + 2u;
+        idx = (tp % size + t * (size / s)) % size;
+        rootw = root_word(a, j);
+        pos = 5u + a.G + 8u * j + t;
     } else {                                              // layer k at x and at -x
         const uint32_t k = (slot - 4u) / 2u, which = (slot - 4u) & 1u;
         const uint32_t lw = layer_word(a, qk, k), size = a.N >> k;
@@ -184,7 +285,7 @@ __global__ void __launch_bounds__(kVerifyThreads) verify_paths_kernel(VerifyArgs
     bool same = true;
 #pragma unroll
     for (int i = 0; i < 8; ++i) same = same && cur.w[i] == be_word(pr + rootw + i);
-    if (!same) atomicMin(&a.best[p], (int32_t)(qk * (5u + 3u * a.R) + pos));
+    if (!same) atomicMin(&a.best[p], (int32_t)(qk * (FOLD ? 5u + 9u * a.G : 5u + 3u * a.R) + pos));
 }
 
 // SHA-256(state || data[0 .. nw)) into state (channel.rs:19-26), streamed over sha256_compress.  nw is the same for every lane,
@@ -215,7 +316,9 @@ __device__ __forceinline__ void commit_words(uint32_t (&st)[8], const uint32_t* 
 
 // (3) transcript (strict only): one lane per proof, the commits of verify_transcript in its order.  The order is a schedule of
 // steps the same for every lane (a challenge, or a commit of nw words), walked by one loop with one commit site: the
-// compression is inlined once and the state stays in registers.
+// compression is inlined once and the state stays in registers.  FOLD (verify_transcript_fold): G (beta, root) pairs, and per
+// query one commit per group of its s_j values and paths.
+template <bool FOLD>
 __global__ void __launch_bounds__(kVerifyThreads) verify_transcript_kernel(VerifyArgs a) {
     const uint32_t p = blockIdx.x * kVerifyThreads + threadIdx.x;
     if (p >= a.count) return;
@@ -223,7 +326,7 @@ __global__ void __launch_bounds__(kVerifyThreads) verify_transcript_kernel(Verif
     uint32_t st[8];
 #pragma unroll
     for (int i = 0; i < 8; ++i) st[i] = 0u;
-    const uint32_t R = a.R, L = a.L, q = a.q;
+    const uint32_t R = FOLD ? a.G : a.R, L = a.L, q = a.q;   // R: the (beta, root) pairs = the layer commits of a query
     // steps: f root | 3 alphas | cp root | R x (beta, layer root) | free term | [nonce] | q query raws | q x (4 f paths, R layer pairs)
     const uint32_t gs = a.gw ? 1u : 0u;                   // the nonce step: a commit of 2 words, then the zero-bit test (-1998)
     const uint32_t head = 6u + 2u * R + gs + q;
@@ -239,7 +342,8 @@ __global__ void __launch_bounds__(kVerifyThreads) verify_transcript_kernel(Verif
         } else {
             const uint32_t t = (s - head) % (4u + R);
             chal = false;
-            nw = t < 4u ? 3u + 8u * L : 6u + 16u * (L - (t - 4u));
+            if constexpr (FOLD) nw = t < 4u ? 3u + 8u * L : (3u + 8u * (L - (t - 4u) * a.K)) << (t - 3u < R ? a.K : a.ls);
+            else nw = t < 4u ? 3u + 8u * L : 6u + 16u * (L - (t - 4u));
         }
         if (chal) {                                       // state word 0 (big-endian bytes 0..3) against the little-endian u32 here
             ++k;
@@ -285,13 +389,22 @@ int32_t key_to_check(int32_t key, uint32_t R) {
     const uint32_t j = pos - 5u - R;
     return -(int32_t)((j & 1u ? 400u : 300u) + j / 2u);
 }
+// The same for the keys of a folded proof (G groups): verify_proof_fold's number.
+int32_t fold_key_to_check(int32_t key, uint32_t G) {
+    const uint32_t pos = (uint32_t)key % (5u + 9u * G);
+    if (pos == 0) return -2;
+    if (pos < 5) return -(int32_t)(3u + pos);             // -4 .. -7
+    if (pos < 5 + G) return -(int32_t)(100u + (pos - 5u));
+    const uint32_t j = (pos - 5u - G) / 8u, t = (pos - 5u - G) % 8u;
+    return -(int32_t)((t ? 400u : 300u) + j);
+}
 
 }  // namespace
 }  // namespace zk
 
 struct zk_verifier {
     int device = 0;
-    uint32_t log_n = 0, log_b = 0, queries = 1, grind = 0;
+    uint32_t log_n = 0, log_b = 0, queries = 1, grind = 0, fold = 1;
     int hash = ZK_HASH_SHA256;
     hipStream_t stream = nullptr, tstream = nullptr;   // paths + algebra; transcript (runs beside them)
     hipEvent_t ev_in = nullptr, ev_t = nullptr;
@@ -326,6 +439,7 @@ int verifier_reserve(zk_verifier* v, size_t chunk, size_t len) {
 int verifier_chunk(zk_verifier* v, const uint8_t* proofs, size_t stride, size_t count, const uint8_t* states, const uint32_t* public_last,
                    int32_t* checks_out, size_t len) {
     const uint32_t log_n = v->log_n, log_b = v->log_b, q = v->queries, R = log_n, L = log_n + log_b;
+    const uint32_t K = v->fold, G = fold_groups(R, K);
     // inputs: [count][len] proofs, [count] public_last, [count][32] states, packed into the pinned staging buffer
     uint8_t* hp = v->h_in;
     if (stride == len) memcpy(hp, proofs, count * len);
@@ -350,9 +464,13 @@ int verifier_chunk(zk_verifier* v, const uint8_t* proofs, size_t stride, size_t 
     a.gm1 = invmod(g); a.gm2 = mulmod(a.gm1, a.gm1); a.gm3 = mulmod(a.gm2, a.gm1); a.inv2 = invmod(2);
     a.gw = v->grind ? 2u : 0u;
     a.gmask = v->grind ? ~0u << (32u - v->grind) : 0u;
-    a.qbase = 20u + 9u * R + a.gw + q;
+    a.qbase = 20u + 9u * G + a.gw + q;
     a.per_q = 4u * (3u + 8u * L);
-    for (uint32_t i = 0; i < R; ++i) a.per_q += 6u + 16u * (L - i);
+    for (uint32_t j = 0; j < G; ++j) a.per_q += (3u + 8u * (L - j * K)) << fold_steps(R, K, j);   // K = 1: 6 + 16 (L - j)
+    if (a.qbase + (size_t)q * a.per_q != len / 4) return fail(ZK_ERR_STATE, "zk_verifier_run: the layout does not add up to the proof length");
+    a.K = K; a.G = G; a.ls = fold_steps(R, K, G - 1u);
+    const uint32_t w = invmod(powmod(a.h, (uint64_t)a.N >> 3));
+    a.inv2m = to_mont(a.inv2); a.wm1 = to_mont(w); a.wm2 = to_mont(mulmod(w, w)); a.wm3 = to_mont(mulmod(mulmod(w, w), w));
 
     HIPCHK(hipMemcpyAsync(d, hp, count * len, hipMemcpyHostToDevice, v->stream));
     HIPCHK(hipMemcpyAsync(d_pub, hp + count * len, count * 4, hipMemcpyHostToDevice, v->stream));
@@ -364,16 +482,27 @@ int verifier_chunk(zk_verifier* v, const uint8_t* proofs, size_t stride, size_t 
     if (states) {                                      // the transcript chains run beside the paths: cost = max of the two
         HIPCHK(hipEventRecord(v->ev_in, v->stream));
         HIPCHK(hipStreamWaitEvent(v->tstream, v->ev_in, 0));
-        hipLaunchKernelGGL(verify_transcript_kernel, dim3(gx), dim3(kVerifyThreads), 0, v->tstream, a);
+        if (K == 1) hipLaunchKernelGGL(verify_transcript_kernel<false>, dim3(gx), dim3(kVerifyThreads), 0, v->tstream, a);
+        else hipLaunchKernelGGL(verify_transcript_kernel<true>, dim3(gx), dim3(kVerifyThreads), 0, v->tstream, a);
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(v->ev_t, v->tstream));
     }
     const uint64_t lanes = (uint64_t)count * q;
-    hipLaunchKernelGGL(verify_algebra_kernel, dim3((uint32_t)((lanes + kVerifyThreads - 1) / kVerifyThreads)), dim3(kVerifyThreads), 0, v->stream, a);
+    const dim3 agrid((uint32_t)((lanes + kVerifyThreads - 1) / kVerifyThreads));
+    if (K == 1) hipLaunchKernelGGL(verify_algebra_kernel, agrid, dim3(kVerifyThreads), 0, v->stream, a);
+    else if (K == 2) hipLaunchKernelGGL(verify_fold_algebra_kernel<2>, agrid, dim3(kVerifyThreads), 0, v->stream, a);
+    else hipLaunchKernelGGL(verify_fold_algebra_kernel<3>, agrid, dim3(kVerifyThreads), 0, v->stream, a);
     HIPCHK(hipGetLastError());
-    const dim3 pgrid(gx, q * (4u + 2u * R));
-    if (v->hash == ZK_HASH_SHA256) hipLaunchKernelGGL(verify_paths_kernel<0>, pgrid, dim3(kVerifyThreads), 0, v->stream, a);
-    else hipLaunchKernelGGL(verify_paths_kernel<1>, pgrid, dim3(kVerifyThreads), 0, v->stream, a);
+    const bool sha = v->hash == ZK_HASH_SHA256;
+    if (K == 1) {
+        const dim3 pgrid(gx, q * (4u + 2u * R));
+        if (sha) hipLaunchKernelGGL((verify_paths_kernel<0, false>), pgrid, dim3(kVerifyThreads), 0, v->stream, a);
+        else hipLaunchKernelGGL((verify_paths_kernel<1, false>), pgrid, dim3(kVerifyThreads), 0, v->stream, a);
+    } else {
+        const dim3 pgrid(gx, q * (4u + ((G - 1u) << K) + (1u << a.ls)));
+        if (sha) hipLaunchKernelGGL((verify_paths_kernel<0, true>), pgrid, dim3(kVerifyThreads), 0, v->stream, a);
+        else hipLaunchKernelGGL((verify_paths_kernel<1, true>), pgrid, dim3(kVerifyThreads), 0, v->stream, a);
+    }
     HIPCHK(hipGetLastError());
     if (states) HIPCHK(hipStreamWaitEvent(v->stream, v->ev_t, 0));
     HIPCHK(hipMemcpyAsync(v->h_out, a.best, count * 4, hipMemcpyDeviceToHost, v->stream));
@@ -386,8 +515,10 @@ int verifier_chunk(zk_verifier* v, const uint8_t* proofs, size_t stride, size_t 
     for (size_t i = 0; i < count; ++i) {
         int32_t c;
         if (states && tcode[i]) c = tcode[i];
-        else if (malformed[i]) c = verify_proof(proofs + i * stride, len, log_n, log_b, public_last[i], v->hash, q, v->grind);   // garbage only
-        else c = best[i] == kNoFailure ? 0 : key_to_check(best[i], R);
+        else if (malformed[i])                             // garbage only
+            c = K == 1 ? verify_proof(proofs + i * stride, len, log_n, log_b, public_last[i], v->hash, q, v->grind)
+                       : verify_proof_fold(proofs + i * stride, len, log_n, log_b, public_last[i], v->hash, q, v->grind, K);
+        else c = best[i] == kNoFailure ? 0 : (K == 1 ? key_to_check(best[i], R) : fold_key_to_check(best[i], G));
         checks_out[i] = c;
     }
     return ZK_OK;
@@ -472,12 +603,21 @@ int zk_verifier_set_hash(zk_verifier* v, int hash_kind) {
     return ZK_OK;
 }
 
+int zk_verifier_set_fold(zk_verifier* v, uint32_t fold_log) {
+    if (!v) return fail(ZK_ERR_INVALID, "null verifier");
+    if (fold_log < 1 || fold_log > kMaxFoldLog) return fail(ZK_ERR_INVALID, "zk_verifier_set_fold: need 1 <= fold_log <= %u (got %u)", kMaxFoldLog, fold_log);
+    v->fold = fold_log;
+    return ZK_OK;
+}
+
+uint32_t zk_verifier_get_fold(const zk_verifier* v) { return v ? v->fold : 0u; }
+
 int zk_verifier_run(zk_verifier* v, const uint8_t* proofs, size_t stride, size_t count, const uint8_t* states, const uint32_t* public_last,
                     int32_t* checks_out) {
     if (!v) return fail(ZK_ERR_INVALID, "null verifier");
     if (count == 0) return ZK_OK;
     if (!proofs || !public_last || !checks_out) return fail(ZK_ERR_INVALID, "zk_verifier_run: null argument");
-    const size_t len = proof_data_len(v->log_n, v->log_b, v->queries, v->grind);
+    const size_t len = proof_data_len_fold(v->log_n, v->log_b, v->queries, v->grind, v->fold);   // fold 1: proof_data_len
     if (stride < len) return fail(ZK_ERR_INVALID, "zk_verifier_run: stride %zu < proof length %zu", stride, len);
     if (count > SIZE_MAX / stride) return fail(ZK_ERR_INVALID, "zk_verifier_run: count * stride overflows");
     HIPCHK(hipSetDevice(v->device));
