@@ -462,7 +462,10 @@ def test_trace_fibsq_batch_on_device(zk, orc):
 
 def test_repeated_proofs_are_identical(zk):
     """Determinism under load (a latent LDS or hand-off race would show as a differing proof):
-    many proofs from one resident trace, two contexts proving concurrently from two host threads."""
+    many proofs from one resident trace, two contexts proving concurrently from two host threads.
+    What it cannot see: every proof writes the SAME data to the same addresses, so a consumer that reads what the previous proof
+    left there (a stale hand-over) still produces the right bytes.  tests/test_gpu_handover_soak.py alternates two traces on the
+    same buffers under load for that."""
     import threading
     a = zk.trace_fibsq((1 << 15) - 1)
     with zk.Context(15, 3) as c1, zk.Context(15, 3) as c2:
