@@ -145,7 +145,7 @@ def reach(launches):
 
 # ---- the proof's layout: where a differing byte falls ---------------------------------------------------------------------------
 def proof_fields(log_n, log_b, q=1, bits=0, K=1):
-    """[(name, first byte, end)] of a proof (transcript.hpp: proof_data_len_fold); K = 1 is the reference's layout."""
+    """[(name, first byte, end)] of a proof (transcript.hpp: proof_data_len); K = 1 is the reference's layout."""
     L = log_n + log_b
     groups = [(r0, min(K, log_n - r0)) for r0 in range(0, log_n, K)]
     out, pos = [], 0

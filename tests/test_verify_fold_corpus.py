@@ -45,6 +45,26 @@ def test_cpu_verifier_equals_the_reference_on_the_corpus(zk, orc, log_n, log_b, 
             assert (want != 0).sum() > len(items) // 2 and len(set(want.tolist())) >= 12
 
 
+@pytest.mark.parametrize("hash_kind", [0, 1], ids=["sha256", "field"])
+@pytest.mark.parametrize("log_n,log_b,q", [(4, 1, 1), (5, 2, 2), (10, 3, 1)])
+def test_k1_cpu_verifier_equals_the_reference_on_the_unfolded_corpus(zk, orc, log_n, log_b, q, hash_kind):
+    """K = 1 is the degenerate case of the one verifier in transcript.hpp, so comparing it with zk_verify_check compares the code
+    with itself.  This is its independent anchor: the plain-Python verifier of fold_ref.py at K = 1 over the corpus of the
+    unfolded wire format (tests/verify_corpus.py, proofs from the oracle), strict and plain."""
+    import verify_corpus
+    lib = zk.load()
+    items = verify_corpus.corpus(orc, log_n, log_b, q, hash_kind)
+    for strict in (True, False):
+        got = verify_fold_corpus.cpu_checks(lib, items, log_n, log_b, q, 0, 1, hash_kind, strict)
+        want = np.array([fold_ref.verify(orc, it.data, it.state if strict else None, log_n, log_b, it.public_last, hash_kind, q, 0, 1)
+                         for it in items], dtype=np.int32)
+        bad = [(items[i].label, int(got[i]), int(want[i])) for i in np.nonzero(got != want)[0][:20]]
+        assert not bad, (strict, bad)
+        assert want[0] == 0 and (want != 0).sum() > len(items) // 2
+        if not strict:
+            assert len(set(want.tolist())) >= 12
+
+
 def test_eight_point_trace_proofs_are_valid(zk, orc):
     """log_n = 3 (groups of 2 + 1 at K = 2), which oracle.prove refuses: the proofs verify_fold_corpus assembles from the oracle's
     primitives are accepted by both CPU verifiers, strict and plain, and a flipped value is rejected by both with one number."""

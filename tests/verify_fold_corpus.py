@@ -1,6 +1,6 @@
 """Tamper corpus for the verifier tests of folded proofs (tests/test_verify_fold_corpus.py, tests/test_gpu_verify_fold.py): the
-counterpart of tests/verify_corpus.py for the wire format with a FRI folding factor 2^K (transcript.hpp: proof_data_len_fold /
-verify_proof_fold).
+counterpart of tests/verify_corpus.py for the wire format with a FRI folding factor 2^K (transcript.hpp: proof_data_len /
+verify_proof with fold > 1).
 
 The valid proofs come from tests/fold_ref.py, built without the library.  For each there is one variant per field: the f
 root, each alpha, the cp root, each group's beta and output root, the free term, the nonce, each query raw, and per query the

@@ -5,6 +5,8 @@
 // bottom of one heap over batch*m_l leaves whose nodes of depth log_batch are the per-proof roots.
 // The device posts those (MailArgs.top = log_batch), each proof's own channel absorbs its root and
 // draws its own challenges (host threads), and the next launch reads them from a per-proof table.
+// One loop over the groups of `fold` rounds serves every folding factor (K = 1: one round per group, fold fused into the leaf
+// hashing); the openings and their encoding are transcript.hpp's for_each_opening and Channel::commit_group.
 #include <atomic>
 #include <condition_variable>
 #include <cstdio>
@@ -149,14 +151,10 @@ const uint32_t* bfinish_roots(zk_batch* b, uint32_t tree, uint32_t log_m) {
     return lvl[0];
 }
 
-// openings of one query (prover.rs:266-289; folded: prove_fold_rounds): 4 values with paths of L digests, then per group of `fold`
-// rounds the 2^steps coset values of its input layer, each with a path of L - r0 digests
+// values and path digests one query opens (transcript.hpp: for_each_opening)
 void bopenings(const zk_batch* b, uint32_t fold, size_t* vals, size_t* digs) {
-    *vals = 4; *digs = 4 * (size_t)b->L;
-    for (uint32_t r0 = 0; r0 < b->R; r0 += fold) {
-        const size_t s = (size_t)1 << (b->R - r0 < fold ? b->R - r0 : fold);
-        *vals += s; *digs += s * (size_t)(b->L - r0);
-    }
+    *vals = *digs = 0;
+    for_each_opening(b->log_n, b->log_b, fold, 0, [&](uint32_t, uint32_t log_len, size_t) { ++*vals; *digs += log_len; });
 }
 // gather buffers for q queries per proof (offsets in, values + digests out; device and pinned host copies), for the current fold
 int balloc_gather(zk_batch* b, uint32_t q) {
@@ -250,7 +248,6 @@ int zk_batch_create(int device, uint32_t log_n, uint32_t log_b, uint32_t log_bat
         return bail(rc);
     HIPCHK_B(hipMemsetAsync(b->d_counter, 0, 64, b->stream));
     HIPCHK_B(hipMemsetAsync(b->d_trace, 0, b->batch * b->n * 4, b->stream));
-    // openings of one proof (prover.rs:266-289): 4 + 2R values, 4 L + sum 2 (L - i) digests
     bopenings(b, 1, &b->per_proof_vals, &b->per_proof_digs);
     if ((rc = balloc_gather(b, 1))) return bail(rc);
     HIPCHK_B(hipHostMalloc((void**)&b->h_chal, b->batch * sizeof(BatchChal)));
@@ -441,7 +438,8 @@ int zk_batch_merkle_nodes(zk_batch* b, uint32_t tree, size_t first, size_t count
 // generate_proof (prover.rs:9-293) for every resident trace.  proofs_out: [batch][stride] bytes, stride >=
 // zk_proof_data_len_fold(log_n, log_b, queries, grind, fold); states_out: [batch][32] (Channel.state of each proof, proof.rs:6).
 // fold > 1 (DESIGN.md "Folding factor"): the rounds in groups of `fold`; per group one challenge per proof, one pass of the batched
-// multi-fold kernel and one tree over its output, as prove_fold_rounds (zkstark.hip) does for one proof.
+// multi-fold kernel and one tree over its output, as prove_fold_rounds (zkstark.hip) does for one proof.  The wire format (openings,
+// tuples, length) is transcript.hpp's for every fold.
 int zk_batch_prove(zk_batch* b, uint8_t* proofs_out, size_t stride, uint8_t* states_out) {
     if (!b || !proofs_out || !states_out) return fail(ZK_ERR_INVALID, "zk_batch_prove: null argument");
     if (!b->have_traces) return fail(ZK_ERR_STATE, "zk_batch_prove: no traces");
@@ -450,7 +448,7 @@ int zk_batch_prove(zk_batch* b, uint8_t* proofs_out, size_t stride, uint8_t* sta
     const uint32_t Q = b->queries;
     const int hash = b->hash;
     const uint32_t K = b->fold;
-    const size_t plen = proof_data_len_fold(b->log_n, b->log_b, Q, b->grind, K);
+    const size_t plen = proof_data_len(b->log_n, b->log_b, Q, b->grind, K);
     if (stride < plen) return fail(ZK_ERR_BUFFER, "zk_batch_prove: stride %zu < proof length %zu", stride, plen);
     if (b->single) {
         size_t len = 0;
@@ -500,47 +498,36 @@ int zk_batch_prove(zk_batch* b, uint8_t* proofs_out, size_t stride, uint8_t* sta
     });
     if ((rc = bchal_upload(b))) return rc;
     HIPCHK(launch_compose_merkle_batch(ca, lb, b->d_trees + b->tree_off[1], b->stream, nullptr, bmail(b, L), hash));   // prover.rs:166-176
-    for (uint32_t r = 0; r <= R && K == 1; ++r) {
+    for (uint32_t r0 = 0;;) {                                             // per group; tree 1 + r0 is the last one committed
         if ((rc = wait_roots())) return rc;
-        roots = bfinish_roots(b, 1 + r, L - r);                           // tree 1 + r: 2^(L - r) leaves per proof
-        if (r == R) {
-            b->pool->run(nb, 32, [&](size_t p) { uint8_t root[32]; digest_words_to_bytes(roots + 8 * p, root); ch[p].commit_hash(root); });
-            break;
-        }
-        const uint32_t winv_half = mulmod(invmod(powmod(d->shift, (uint64_t)1 << r)), invmod(2));
-        b->pool->run(nb, 32, [&](size_t p) {
-            uint8_t root[32];
-            digest_words_to_bytes(roots + 8 * p, root);
-            ch[p].commit_hash(root);                                      // prover.rs:180 / :224
-            uint32_t beta = ch[p].get_u32() % P;                          // prover.rs:200
-            b->h_chal[p].c_mont = to_mont(mulmod(beta, winv_half));
-        });
-        if ((rc = bchal_upload(b))) return rc;
-        FoldBatchArgs fa;
-        if ((rc = fold_args(d, b->d_layers + b->layer_off[1 + r], b->d_layers + b->layer_off[2 + r], L - r, r, 0, fa.a))) return rc;
-        fa.chal = b->d_chal;
-        HIPCHK(launch_fold_merkle_batch(fa, lb, b->d_trees + b->tree_off[2 + r], b->stream, nullptr, bmail(b, L - r - 1), hash));   // prover.rs:201-214
-    }
-    for (uint32_t r0 = 0; K > 1; ) {                                      // folded: tree 1 + r0 is the last one committed
-        if ((rc = wait_roots())) return rc;
-        roots = bfinish_roots(b, 1 + r0, L - r0);
+        roots = bfinish_roots(b, 1 + r0, L - r0);                         // tree 1 + r0: 2^(L - r0) leaves per proof
         if (r0 == R) {
             b->pool->run(nb, 32, [&](size_t p) { uint8_t root[32]; digest_words_to_bytes(roots + 8 * p, root); ch[p].commit_hash(root); });
             break;
         }
         const uint32_t steps = R - r0 < K ? R - r0 : K, id = 1 + r0 + steps;
+        // K = 1: the fold constant is reduced on the host; K > 1: the challenge goes up RAW and is reduced on the device
+        const uint32_t winv_half = K == 1 ? mulmod(invmod(powmod(d->shift, (uint64_t)1 << r0)), invmod(2)) : 0;
         b->pool->run(nb, 32, [&](size_t p) {
             uint8_t root[32];
             digest_words_to_bytes(roots + 8 * p, root);
             ch[p].commit_hash(root);                                      // prover.rs:180 / :224
-            b->h_chal[p].c_mont = ch[p].get_u32();                        // prover.rs:200, once per group: RAW, reduced on the device
+            const uint32_t beta = ch[p].get_u32();                        // prover.rs:200, once per group
+            b->h_chal[p].c_mont = K == 1 ? to_mont(mulmod(beta % P, winv_half)) : beta;
         });
         if ((rc = bchal_upload(b))) return rc;
-        if ((rc = dom_fold_multi_batch(d, b->d_layers + b->layer_off[1 + r0], b->d_layers + b->layer_off[id], L - r0, r0, steps, &b->d_chal->c_mont,
-                                       (uint32_t)(sizeof(BatchChal) / 4), b->d_work, (uint32_t)nb, b->stream, nullptr))) return rc;   // prover.rs:201-211, steps times
-        HIPCHK(launch_merkle_build(b->d_layers + b->layer_off[id], L - r0 - steps + lb, b->d_trees + b->tree_off[id], b->stream, nullptr,
-                                   bmail(b, L - r0 - steps), hash));      // prover.rs:214
-        for (uint32_t l = 2 + r0; l < id; ++l) b->skipped_trees |= (uint64_t)1 << l;
+        if (K == 1) {
+            FoldBatchArgs fa;
+            if ((rc = fold_args(d, b->d_layers + b->layer_off[1 + r0], b->d_layers + b->layer_off[id], L - r0, r0, 0, fa.a))) return rc;
+            fa.chal = b->d_chal;
+            HIPCHK(launch_fold_merkle_batch(fa, lb, b->d_trees + b->tree_off[id], b->stream, nullptr, bmail(b, L - r0 - 1), hash));   // prover.rs:201-214
+        } else {
+            if ((rc = dom_fold_multi_batch(d, b->d_layers + b->layer_off[1 + r0], b->d_layers + b->layer_off[id], L - r0, r0, steps, &b->d_chal->c_mont,
+                                           (uint32_t)(sizeof(BatchChal) / 4), b->d_work, (uint32_t)nb, b->stream, nullptr))) return rc;   // prover.rs:201-211, steps times
+            HIPCHK(launch_merkle_build(b->d_layers + b->layer_off[id], L - r0 - steps + lb, b->d_trees + b->tree_off[id], b->stream, nullptr,
+                                       bmail(b, L - r0 - steps), hash));      // prover.rs:214
+            for (uint32_t l = 2 + r0; l < id; ++l) b->skipped_trees |= (uint64_t)1 << l;
+        }
         r0 += steps;
     }
     lap("lde .. last roots");
@@ -579,20 +566,10 @@ int zk_batch_prove(zk_batch* b, uint8_t* proofs_out, size_t stride, uint8_t* sta
                 --dd;
             }
         };
-        for (uint32_t k = 0; k < Q; ++k) {
-            const size_t x = (size_t)qraw[k] % (N - 2 * B);
-            *vo++ = b->layer_off[0] + p * N + x;         add_path(0, L, x);
-            *vo++ = b->layer_off[0] + p * N + x + B;     add_path(0, L, x + B);
-            *vo++ = b->layer_off[0] + p * N + x + 2 * B; add_path(0, L, x + 2 * B);
-            *vo++ = b->layer_off[1] + p * N + x;         add_path(1, L, x);
-            for (uint32_t r0 = 0; r0 < R; r0 += K) {                      // per group the s coset values of its input layer (K = 1: the pair)
-                const size_t s = (size_t)1 << (R - r0 < K ? R - r0 : K), len = N >> r0, xi = x % len;
-                for (size_t t = 0; t < s; ++t) {
-                    const size_t idx = (xi + t * (len / s)) % len;
-                    *vo++ = b->layer_off[1 + r0] + p * len + idx; add_path(1 + r0, L - r0, idx);
-                }
-            }
-        }
+        for (uint32_t k = 0; k < Q; ++k)                                  // layer l is stored proof-major: proof p's values at p * len
+            for_each_opening(b->log_n, b->log_b, K, (size_t)qraw[k] % (N - 2 * B), [&](uint32_t layer, uint32_t log_len, size_t leaf) {
+                *vo++ = b->layer_off[layer] + (p << log_len) + leaf; add_path(layer, log_len, leaf);
+            });
     });
     lap("queries + opening offsets");
     const size_t tv = nb * nv, td = nb * ndg;
@@ -607,28 +584,14 @@ int zk_batch_prove(zk_batch* b, uint8_t* proofs_out, size_t stride, uint8_t* sta
     b->pool->run(nb, 4, [&](size_t p) {
         const uint32_t* vals = b->h_gout + p * nv;
         const uint32_t* dw = b->h_gout + tv + p * ndg * 8;
-        std::vector<uint8_t> dig(ndg * 32);
-        for (size_t i = 0; i < ndg; ++i) digest_words_to_bytes(dw + 8 * i, dig.data() + 32 * i);
-        size_t dpos = 0;
-        std::vector<uint8_t> grp;                                                                                   // one group's tuple
+        std::vector<uint8_t> buf(Channel::group_bytes((size_t)1 << fold_steps(R, K, 0), L));   // one buffer per proof: the first group's tuple is the largest
+        auto tuple = [&](size_t s, size_t pl) {
+            ch[p].commit_group(buf.data(), s, pl, [&](size_t t) { return vals[t]; }, [&](size_t i, uint8_t* out) { digest_words_to_bytes(dw + 8 * i, out); });
+            vals += s; dw += 8 * s * pl;
+        };
         for (uint32_t q = 0; q < Q; ++q) {
-            for (int k = 0; k < 4; ++k) { ch[p].commit_val_path(vals[k], dig.data() + 32 * dpos, L); dpos += L; }   // prover.rs:274-277
-            vals += 4;
-            for (uint32_t r0 = 0; r0 < R; r0 += K) {                                                                 // prover.rs:280-289
-                const size_t s = (size_t)1 << (R - r0 < K ? R - r0 : K), pl = L - r0;
-                if (s == 2) {
-                    ch[p].commit_pair_paths(vals[0], vals[1], dig.data() + 32 * dpos, dig.data() + 32 * (dpos + pl), pl);
-                } else {                                                  // widened: s values, then their s paths, one commit
-                    grp.clear();
-                    for (size_t t = 0; t < s; ++t) Channel::put32(grp, vals[t]);
-                    for (size_t t = 0; t < s; ++t) {
-                        Channel::put64(grp, pl);
-                        grp.insert(grp.end(), dig.data() + 32 * (dpos + t * pl), dig.data() + 32 * (dpos + (t + 1) * pl));
-                    }
-                    ch[p].commit_bytes(grp.data(), grp.size());
-                }
-                vals += s; dpos += s * pl;
-            }
+            for (int k = 0; k < 4; ++k) tuple(1, L);                                                                   // prover.rs:274-277
+            for (uint32_t j = 0, G = fold_groups(R, K); j < G; ++j) tuple((size_t)1 << fold_steps(R, K, j), L - j * K);   // prover.rs:280-289
         }
         if (ch[p].data.size() != plen) { bad.store(1); return; }
         memcpy(proofs_out + p * stride, ch[p].data.data(), plen);          // channel.rs:34-36

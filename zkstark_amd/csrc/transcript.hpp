@@ -1,4 +1,5 @@
-// transcript.hpp -- host-only Fiat-Shamir channel, proof wire format and verifier.
+// transcript.hpp -- host-only Fiat-Shamir channel, the proof wire format (one description for every folding factor: length, opening
+// order, decommitment tuple) and its verifier.
 //
 // Channel mirrors channel.rs:6-37; the byte encoding is bincode 1.x defaults
 // (little-endian fixed-width ints, [u8;32] raw, Box<[T]> = u64 count + items)
@@ -39,33 +40,72 @@ struct Channel {
         commit_u32(f);
         return f;
     }
-    static void put32(std::vector<uint8_t>& v, uint32_t x) { for (int i = 0; i < 4; ++i) v.push_back((uint8_t)(x >> (8 * i))); }
-    static void put64(std::vector<uint8_t>& v, uint64_t x) { for (int i = 0; i < 8; ++i) v.push_back((uint8_t)(x >> (8 * i))); }
-    // (u32, AuthPath): prover.rs:274-277
-    void commit_val_path(uint32_t val, const uint8_t* path, size_t plen) {
-        std::vector<uint8_t> b;
-        put32(b, val); put64(b, plen);
-        b.insert(b.end(), path, path + 32 * plen);
-        commit_bytes(b.data(), b.size());
+    // The one decommitment tuple of the wire format: s values, then their s authentication paths, each Box<[Hash]> = u64 count +
+    // plen digests, committed once.  s = 1 is (u32, AuthPath) of prover.rs:274-277, s = 2 the pair of prover.rs:280-289, s = 4 / 8
+    // a group of a folded proof.  buf: group_bytes(s, plen) bytes of the caller's, reused from tuple to tuple; val(t) gives value
+    // t, digest(i, out) writes digest i of the s * plen (path t starts at t * plen) as 32 bytes.
+    static size_t group_bytes(size_t s, size_t plen) { return s * (4 + 8 + 32 * plen); }
+    template <class Val, class Dig> void commit_group(uint8_t* buf, size_t s, size_t plen, Val val, Dig digest) {
+        uint8_t* p = buf;
+        for (size_t t = 0; t < s; ++t, p += 4) {
+            const uint32_t v = val(t);
+            for (int i = 0; i < 4; ++i) p[i] = (uint8_t)(v >> (8 * i));
+        }
+        for (size_t t = 0; t < s; ++t) {
+            for (int i = 0; i < 8; ++i) *p++ = (uint8_t)((uint64_t)plen >> (8 * i));
+            for (size_t j = 0; j < plen; ++j, p += 32) digest(t * plen + j, p);
+        }
+        commit_bytes(buf, (size_t)(p - buf));
     }
-    // (u32, u32, AuthPath, AuthPath): prover.rs:288
+    // ... from values and paths that already lie as bytes (the sharded prover's decommitment): s = 1 and s = 2
+    void commit_val_path(uint32_t val, const uint8_t* path, size_t plen) {
+        std::vector<uint8_t> b(group_bytes(1, plen));
+        commit_group(b.data(), 1, plen, [&](size_t) { return val; }, [&](size_t i, uint8_t* out) { memcpy(out, path + 32 * i, 32); });
+    }
     void commit_pair_paths(uint32_t v0, uint32_t v1, const uint8_t* p0, const uint8_t* p1, size_t plen) {
-        std::vector<uint8_t> b;
-        put32(b, v0); put32(b, v1);
-        put64(b, plen); b.insert(b.end(), p0, p0 + 32 * plen);
-        put64(b, plen); b.insert(b.end(), p1, p1 + 32 * plen);
-        commit_bytes(b.data(), b.size());
+        std::vector<uint8_t> b(group_bytes(2, plen));
+        commit_group(b.data(), 2, plen, [&](size_t t) { return t ? v1 : v0; },
+                     [&](size_t i, uint8_t* out) { memcpy(out, i < plen ? p0 + 32 * i : p1 + 32 * (i - plen), 32); });
     }
 };
 
-// q = number of decommitment queries (1 = the reference's format, prover.rs:263; q > 1: SURVEY.md 8f
-// item 1 -- the q raw indices are drawn in a row, then each query's openings are committed in turn).
+// ---- the proof format, in one place -----------------------------------------------------------------------------
+// fold = K in 1..3 is the FRI folding factor 2^K (DESIGN.md "Folding factor"; the reference folds by two, K = 1: prover.rs:198-225).
+// The R = log_n reference rounds are taken in G = ceil(R / K) groups; group j starts at round r0 = j K and has steps = min(K, R - r0)
+// rounds.  A group draws ONE challenge beta; its output is `steps` successive reference folds with the challenges beta, beta^2,
+// beta^4, and only that output is committed.  Per query a group opens the s = 2^steps values of its INPUT layer (len = N >> r0) at
+// (x % len + t len / s) % len, t < s, then their s paths: the tuple of prover.rs:280-289 widened.  K = 1 is that tuple: G = R groups
+// of one round, s = 2.  A query still tests one coset per layer, so the conjectured security per query is the reference's; the
+// price of K > 1 is s paths per group instead of 2 per round.
+// q = number of decommitment queries (1 = the reference's format, prover.rs:263; q > 1: SURVEY.md 8f item 1 -- the q raw indices
+// are drawn in a row, then each query's openings are committed in turn).
 // grind = proof-of-work bits (DESIGN.md "Grinding"): g > 0 puts the 8-byte nonce between the free term and the query raws.
-inline size_t proof_data_len(uint32_t log_n, uint32_t log_b, uint32_t q = 1, uint32_t grind = 0) {
-    size_t L = log_n + log_b, R = log_n;
-    size_t per_query = 4 + 4 * (4 + 8 + 32 * L);
-    for (size_t i = 0; i < R; ++i) per_query += 8 + 2 * (8 + 32 * (L - i));
-    return 32 + 12 + 32 + R * 36 + 4 + (grind ? 8 : 0) + (size_t)q * per_query;
+constexpr uint32_t kMaxFoldLog = 3;
+inline uint32_t fold_groups(uint32_t R, uint32_t fold) { return (R + fold - 1) / fold; }
+inline uint32_t fold_steps(uint32_t R, uint32_t fold, uint32_t group) { const uint32_t r0 = group * fold; return R - r0 < fold ? R - r0 : fold; }
+// Leaf t of the coset a group with `steps` rounds opens in its input layer of 2^log_len values, for the query index x.
+inline size_t coset_leaf(size_t x, uint32_t log_len, uint32_t steps, uint32_t t) {
+    const size_t len = (size_t)1 << log_len;
+    return (x % len + t * (len >> steps)) % len;
+}
+// The openings of one query in wire order, for x = query raw % (N - 2B): f at x, x + B, x + 2B (layer 0) and cp at x (layer 1),
+// one tuple each (prover.rs:266-277), then per group the s coset leaves of its input layer 1 + r0, one tuple per group.
+// open(layer id, log2 of the layer's length = digests of the path, leaf index).
+template <class Open> inline void for_each_opening(uint32_t log_n, uint32_t log_b, uint32_t fold, size_t x, Open open) {
+    const uint32_t L = log_n + log_b, G = fold_groups(log_n, fold);
+    const size_t B = (size_t)1 << log_b;
+    open(0u, L, x); open(0u, L, x + B); open(0u, L, x + 2 * B); open(1u, L, x);
+    for (uint32_t j = 0; j < G; ++j) {
+        const uint32_t r0 = j * fold, steps = fold_steps(log_n, fold, j);
+        for (uint32_t t = 0; t < (1u << steps); ++t) open(1u + r0, L - r0, coset_leaf(x, L - r0, steps, t));
+    }
+}
+// fold must be in 1..kMaxFoldLog (the callers check it).
+inline size_t proof_data_len(uint32_t log_n, uint32_t log_b, uint32_t q = 1, uint32_t grind = 0, uint32_t fold = 1) {
+    const size_t L = log_n + log_b, G = fold_groups(log_n, fold);
+    size_t per_query = 4 + 4 * Channel::group_bytes(1, L);
+    for (uint32_t j = 0; j < G; ++j) per_query += Channel::group_bytes((size_t)1 << fold_steps(log_n, fold, j), L - (size_t)j * fold);
+    return 32 + 12 + 32 + G * 36 + 4 + (grind ? 8 : 0) + (size_t)q * per_query;
 }
 
 // ---- grinding (DESIGN.md "Grinding"; the reference has none) -------------------------------------------------------------
@@ -132,171 +172,18 @@ inline void compute_root_from_path(uint32_t element, size_t index, const uint8_t
     memcpy(out, cur, 32);
 }
 
-// proof.rs:15-149 with the literals generalised.  Returns 0 or the negative index of the failed check.
+// proof.rs:15-149 with the literals generalised and the rounds taken in groups (the format above).  Returns 0 or the negative
+// index of the failed check: -1 sizes or layout, -2 cp0, -3 the four path lengths, -4..-7 the paths of f(x), f(gx), f(g^2 x), cp(x);
+// then per query first every group's fold comparison -(100+j), then per group j its path lengths -(200+j) and its paths,
+// -(300+j) for t = 0 and -(400+j) for the first failing t >= 1; -8 for bytes left over.  K = 1: j is the reference's round.
+// Values and challenges are reduced % P before arithmetic; what a fold is compared with (the next group's value 0, the free
+// term, fv[3]) is compared unreduced.
 // grind > 0: the nonce after the free term is skipped.  Its work is a property of the Fiat-Shamir transcript, which only
 // verify_transcript replays; here the query raws are read from the proof (as the reference does), so checking it certifies nothing.
 inline int verify_proof(const uint8_t* data, size_t len, uint32_t log_n, uint32_t log_b, uint32_t public_last, int hash = 0, uint32_t q = 1,
-                        uint32_t grind = 0) {
-    if (log_n < 2 || log_b < 1 || log_n + log_b > 30 || q < 1 || q > 64 || grind > kMaxGrindBits) return -1;
-    const size_t n = (size_t)1 << log_n, B = (size_t)1 << log_b, N = n << log_b, R = log_n, L = log_n + log_b;
-    const uint8_t* p = data;
-    size_t left = len;
-    bool bad = false;
-    auto take = [&](size_t k) -> const uint8_t* {
-        if (left < k) { bad = true; return nullptr; }
-        const uint8_t* q = p; p += k; left -= k; return q;
-    };
-    auto take32 = [&]() -> uint32_t {
-        const uint8_t* q = take(4);
-        return q ? ((uint32_t)q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)q[2] << 16) | ((uint32_t)q[3] << 24)) : 0;
-    };
-    auto take_path = [&](size_t& plen) -> const uint8_t* {
-        const uint8_t* q = take(8);
-        if (!q) return nullptr;
-        uint64_t c = 0;
-        for (int i = 0; i < 8; ++i) c |= (uint64_t)q[i] << (8 * i);
-        if (c > 64) { bad = true; return nullptr; }
-        plen = (size_t)c;
-        return take(32 * plen);
-    };
-    // proof.rs:20-46
-    const uint8_t* f_root = take(32);
-    uint32_t alpha[3] = {take32(), take32(), take32()};
-    const uint8_t* roots[40]; uint32_t betas[40];
-    roots[0] = take(32); betas[0] = 0;
-    for (size_t i = 0; i < R; ++i) { betas[i + 1] = take32(); roots[i + 1] = take(32); }
-    uint32_t free_term = take32();
-    if (grind) take(8);                                   // the nonce
-    uint32_t test_raws[64];
-    for (uint32_t k = 0; k < q; ++k) test_raws[k] = take32();
-    const uint32_t g = root_of_unity(log_n), h = root_of_unity((uint32_t)L);
-    auto fsub = [](uint32_t a, uint32_t b) { return sub(a, b); };
-    for (uint32_t qk = 0; qk < q; ++qk) {
-    const uint32_t test_raw = test_raws[qk];
-    uint32_t fv[4]; const uint8_t* fp[4]; size_t fpl[4] = {0, 0, 0, 0};
-    for (int i = 0; i < 4; ++i) { fv[i] = take32(); fp[i] = take_path(fpl[i]); }
-    uint32_t lx[40], lnx[40]; const uint8_t *lpx[40], *lpnx[40]; size_t plx[40], plnx[40];
-    for (size_t i = 0; i < R; ++i) {
-        lx[i] = take32(); lnx[i] = take32(); plx[i] = plnx[i] = 0;
-        lpx[i] = take_path(plx[i]); lpnx[i] = take_path(plnx[i]);
-    }
-    if (bad) return -1;
-    // proof.rs:49-60
-    const size_t tp = (size_t)test_raw % (N - 2 * B);
-    const uint32_t x = mulmod(GEN_W, powmod(h, tp));
-    {   // proof.rs:63-77
-        uint32_t f_x = fv[0] % P, f_gx = fv[1] % P, f_ggx = fv[2] % P;
-        uint32_t gm1 = invmod(g), gm2 = mulmod(gm1, gm1), gm3 = mulmod(gm2, gm1);
-        uint32_t p0 = mulmod(fsub(f_x, 1), invmod(fsub(x, 1)));
-        uint32_t p1 = mulmod(fsub(f_x, public_last % P), invmod(fsub(x, gm2)));
-        uint32_t num = fsub(fsub(f_ggx, mulmod(f_gx, f_gx)), mulmod(f_x, f_x));
-        uint32_t den = mulmod(fsub(powmod(x, n), 1), invmod(mulmod(mulmod(fsub(x, gm3), fsub(x, gm2)), fsub(x, gm1))));
-        uint32_t p2 = mulmod(num, invmod(den));
-        uint32_t cp0 = add(add(mulmod(alpha[0] % P, p0), mulmod(alpha[1] % P, p1)), mulmod(alpha[2] % P, p2));
-        if (cp0 != fv[3]) return -2;
-    }
-    uint8_t root[32];
-    if (fpl[0] != L || fpl[1] != L || fpl[2] != L || fpl[3] != L) return -3;
-    // proof.rs:80-95
-    compute_root_from_path(fv[0], tp, fp[0], fpl[0], root, hash);         if (memcmp(root, f_root, 32)) return -4;
-    compute_root_from_path(fv[1], tp + B, fp[1], fpl[1], root, hash);     if (memcmp(root, f_root, 32)) return -5;
-    compute_root_from_path(fv[2], tp + 2 * B, fp[2], fpl[2], root, hash); if (memcmp(root, f_root, 32)) return -6;
-    compute_root_from_path(fv[3], tp, fp[3], fpl[3], root, hash);         if (memcmp(root, roots[0], 32)) return -7;
-    // proof.rs:101-126
-    const uint32_t inv2 = invmod(2);
-    for (size_t k = 0; k < R; ++k) {
-        uint32_t xk = powmod(x, (uint64_t)1 << k);
-        uint32_t gx = mulmod(add(lx[k] % P, lnx[k] % P), inv2);
-        uint32_t hx = mulmod(fsub(lx[k] % P, lnx[k] % P), invmod(mulmod(xk, 2)));
-        uint32_t calc = add(gx, mulmod(betas[k + 1] % P, hx));
-        uint32_t expect = (k + 1 < R) ? lx[k + 1] : free_term;
-        if (calc != expect) return -(int)(100 + k);
-    }
-    // proof.rs:129-148
-    for (size_t k = 0; k < R; ++k) {
-        size_t size = N >> k;
-        if (plx[k] != L - k || plnx[k] != L - k) return -(int)(200 + k);
-        compute_root_from_path(lx[k], tp % size, lpx[k], plx[k], root, hash);
-        if (memcmp(root, roots[k], 32)) return -(int)(300 + k);
-        compute_root_from_path(lnx[k], (tp + size / 2) % size, lpnx[k], plnx[k], root, hash);
-        if (memcmp(root, roots[k], 32)) return -(int)(400 + k);
-    }
-    }
-    if (left != 0) return -8;
-    return 0;
-}
-
-// SURVEY.md section 8f item 1: the reference verifier reads the challenges out of the proof
-// (proof.rs:22-37) and never checks Proof.state (proof.rs:6); the author flags this as unfinished
-// (readme.md:1).  This replays the Fiat-Shamir channel over the proof bytes in the prover's commit
-// order (prover.rs:85, :163-165, :180, :200, :224, :254, :263, :274-277, :288), checks that every
-// challenge equals the one the transcript yields at that point and that the final state matches.
-// Returns 0, or -(1000 + k) for the k-th challenge / -1998 for a grinding nonce whose hash has fewer than `grind` leading zero
-// bits (checked after the betas and before the first query challenge; it does not advance k) / -1999 for the state.
-inline int verify_transcript(const uint8_t* data, size_t len, const uint8_t state[32], uint32_t log_n, uint32_t log_b, uint32_t q = 1,
-                             uint32_t grind = 0) {
-    if (log_n < 2 || log_b < 1 || log_n + log_b > 30 || grind > kMaxGrindBits) return -1;
-    const size_t R = log_n, L = log_n + log_b;
-    if (q < 1 || q > 64 || len != proof_data_len(log_n, log_b, q, grind)) return -1;
-    Channel ch;
-    const uint8_t* p = data;
-    int k = 0;
-    auto commit = [&](size_t n) { ch.commit_bytes(p, n); p += n; };
-    auto challenge = [&]() -> bool {
-        uint32_t expect = ((uint32_t)ch.state[0] << 24) | ((uint32_t)ch.state[1] << 16) | ((uint32_t)ch.state[2] << 8) | ch.state[3];
-        uint32_t got = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
-        ++k;
-        if (got != expect) return false;
-        commit(4);
-        return true;
-    };
-    commit(32);                                             // f_eval root
-    for (int i = 0; i < 3; ++i) if (!challenge()) return -(1000 + k);
-    commit(32);                                             // cp root
-    for (size_t r = 0; r < R; ++r) {
-        if (!challenge()) return -(1000 + k);               // beta
-        commit(32);                                         // layer root
-    }
-    commit(4);                                              // free term
-    if (grind) {                                            // nonce: the commit is SHA-256(S || le64(w))
-        commit(8);
-        const uint32_t w0 = ((uint32_t)ch.state[0] << 24) | ((uint32_t)ch.state[1] << 16) | ((uint32_t)ch.state[2] << 8) | ch.state[3];
-        if (!grind_word_ok(w0, grind)) return -1998;
-    }
-    for (uint32_t j = 0; j < q; ++j) if (!challenge()) return -(1000 + k);   // queries
-    for (uint32_t j = 0; j < q; ++j) {
-        for (int i = 0; i < 4; ++i) commit(4 + 8 + 32 * L);
-        for (size_t i = 0; i < R; ++i) commit(8 + 2 * (8 + 32 * (L - i)));
-    }
-    if (memcmp(ch.state, state, 32)) return -1999;
-    return 0;
-}
-
-// ---- FRI folding factor 2^K (DESIGN.md "Folding factor"; the reference folds by two: prover.rs:198-225) ---------------------
-// fold = K in 1..3.  The R = log_n reference rounds are taken in G = ceil(R / K) groups; group j starts at round r0 = j K and has
-// steps = min(K, R - r0) rounds.  A group draws ONE challenge beta; its output is `steps` successive reference folds with the
-// challenges beta, beta^2, beta^4, and only that output is committed.  Per query a group opens the s = 2^steps values of its
-// INPUT layer (len = N >> r0) at (x % len + t len / s) % len, t < s, then their s paths: the tuple of prover.rs:280-289 widened
-// (K = 1 is that tuple).  A query still tests one coset per layer, so the conjectured security per query is the reference's;
-// the price is s paths per group instead of 2 per round.
-constexpr uint32_t kMaxFoldLog = 3;
-inline uint32_t fold_groups(uint32_t R, uint32_t fold) { return (R + fold - 1) / fold; }
-inline uint32_t fold_steps(uint32_t R, uint32_t fold, uint32_t group) { const uint32_t r0 = group * fold; return R - r0 < fold ? R - r0 : fold; }
-inline size_t proof_data_len_fold(uint32_t log_n, uint32_t log_b, uint32_t q, uint32_t grind, uint32_t fold) {
-    const size_t L = log_n + log_b, R = log_n, G = fold_groups(log_n, fold);
-    size_t per_query = 4 + 4 * (4 + 8 + 32 * L);
-    for (uint32_t j = 0; j < G; ++j) per_query += ((size_t)1 << fold_steps(log_n, fold, j)) * (12 + 32 * (L - (size_t)j * fold));
-    (void)R;
-    return 32 + 12 + 32 + G * 36 + 4 + (grind ? 8 : 0) + (size_t)q * per_query;
-}
-
-// verify_proof (proof.rs:15-149) for a proof folded by 2^fold between commitments.  Check numbers as verify_proof with "k" read as
-// the group index j: -(100+j) fold, -(200+j) path length, -(300+j) path of t = 0, -(400+j) first failing path of t >= 1; per query
-// first every group's fold comparison, then per group its path lengths and paths.  fold = 1 gives verify_proof's number for every input.
-inline int verify_proof_fold(const uint8_t* data, size_t len, uint32_t log_n, uint32_t log_b, uint32_t public_last, int hash, uint32_t q,
-                             uint32_t grind, uint32_t fold) {
+                        uint32_t grind = 0, uint32_t fold = 1) {
     if (log_n < 2 || log_b < 1 || log_n + log_b > 30 || q < 1 || q > 64 || grind > kMaxGrindBits || fold < 1 || fold > kMaxFoldLog) return -1;
-    const size_t n = (size_t)1 << log_n, B = (size_t)1 << log_b, N = n << log_b, R = log_n, L = log_n + log_b;
+    const size_t n = (size_t)1 << log_n, B = (size_t)1 << log_b, N = n << log_b, L = log_n + log_b;
     const uint32_t G = fold_groups(log_n, fold);
     const uint8_t* p = data;
     size_t left = len;
@@ -318,6 +205,7 @@ inline int verify_proof_fold(const uint8_t* data, size_t len, uint32_t log_n, ui
         plen = (size_t)c;
         return take(32 * plen);
     };
+    // proof.rs:20-46
     const uint8_t* f_root = take(32);
     uint32_t alpha[3] = {take32(), take32(), take32()};
     const uint8_t* roots[40]; uint32_t betas[40];            // roots[j]: the tree over the INPUT layer of group j (roots[G]: the last layer)
@@ -339,6 +227,7 @@ inline int verify_proof_fold(const uint8_t* data, size_t len, uint32_t log_n, ui
             for (uint32_t t = 0; t < s; ++t) { lpl[j][t] = 0; lp[j][t] = take_path(lpl[j][t]); }
         }
         if (bad) return -1;
+        // proof.rs:49-60
         const size_t tp = (size_t)test_raw % (N - 2 * B);
         const uint32_t x = mulmod(GEN_W, powmod(h, tp));
         {   // proof.rs:63-77
@@ -354,11 +243,12 @@ inline int verify_proof_fold(const uint8_t* data, size_t len, uint32_t log_n, ui
         }
         uint8_t root[32];
         if (fpl[0] != L || fpl[1] != L || fpl[2] != L || fpl[3] != L) return -3;
+        // proof.rs:80-95
         compute_root_from_path(fv[0], tp, fp[0], fpl[0], root, hash);         if (memcmp(root, f_root, 32)) return -4;
         compute_root_from_path(fv[1], tp + B, fp[1], fpl[1], root, hash);     if (memcmp(root, f_root, 32)) return -5;
         compute_root_from_path(fv[2], tp + 2 * B, fp[2], fpl[2], root, hash); if (memcmp(root, f_root, 32)) return -6;
         compute_root_from_path(fv[3], tp, fp[3], fpl[3], root, hash);         if (memcmp(root, roots[0], 32)) return -7;
-        // proof.rs:101-126 widened: the s opened values of a group folded pairwise (t with t + s/2, then again)
+        // proof.rs:101-126: the s opened values of a group folded pairwise (t with t + s/2, then again)
         const uint32_t inv2 = invmod(2);
         for (uint32_t j = 0; j < G; ++j) {
             const uint32_t r0 = j * fold, steps = fold_steps(log_n, fold, j);
@@ -381,29 +271,33 @@ inline int verify_proof_fold(const uint8_t* data, size_t len, uint32_t log_n, ui
             const uint32_t expect = (j + 1 < G) ? lv[j + 1][0] : free_term;
             if (v[0] != expect) return -(int)(100 + j);
         }
-        // proof.rs:129-148 widened
+        // proof.rs:129-148
         for (uint32_t j = 0; j < G; ++j) {
-            const uint32_t r0 = j * fold, s = 1u << fold_steps(log_n, fold, j);
-            const size_t size = N >> r0;
+            const uint32_t r0 = j * fold, steps = fold_steps(log_n, fold, j), s = 1u << steps;
             for (uint32_t t = 0; t < s; ++t) if (lpl[j][t] != L - r0) return -(int)(200 + j);
             for (uint32_t t = 0; t < s; ++t) {
-                compute_root_from_path(lv[j][t], (tp % size + t * (size / s)) % size, lp[j][t], lpl[j][t], root, hash);
+                compute_root_from_path(lv[j][t], coset_leaf(tp, (uint32_t)L - r0, steps, t), lp[j][t], lpl[j][t], root, hash);
                 if (memcmp(root, roots[j], 32)) return t == 0 ? -(int)(300 + j) : -(int)(400 + j);
             }
         }
     }
-    (void)R;
     if (left != 0) return -8;
     return 0;
 }
 
-// verify_transcript for the same format: 3 + G + q challenges (k counts them), one commit per group and query.
-inline int verify_transcript_fold(const uint8_t* data, size_t len, const uint8_t state[32], uint32_t log_n, uint32_t log_b, uint32_t q,
-                                  uint32_t grind, uint32_t fold) {
+// SURVEY.md section 8f item 1: the reference verifier reads the challenges out of the proof
+// (proof.rs:22-37) and never checks Proof.state (proof.rs:6); the author flags this as unfinished
+// (readme.md:1).  This replays the Fiat-Shamir channel over the proof bytes in the prover's commit
+// order (prover.rs:85, :163-165, :180, :200, :224, :254, :263, :274-277, :288: one commit per tuple), checks that every
+// challenge equals the one the transcript yields at that point and that the final state matches.  There are 3 + G + q challenges.
+// Returns 0, or -(1000 + k) for the k-th challenge / -1998 for a grinding nonce whose hash has fewer than `grind` leading zero
+// bits (checked after the betas and before the first query challenge; it does not advance k) / -1999 for the state.
+inline int verify_transcript(const uint8_t* data, size_t len, const uint8_t state[32], uint32_t log_n, uint32_t log_b, uint32_t q = 1,
+                             uint32_t grind = 0, uint32_t fold = 1) {
     if (log_n < 2 || log_b < 1 || log_n + log_b > 30 || grind > kMaxGrindBits || fold < 1 || fold > kMaxFoldLog) return -1;
     const size_t L = log_n + log_b;
     const uint32_t G = fold_groups(log_n, fold);
-    if (q < 1 || q > 64 || len != proof_data_len_fold(log_n, log_b, q, grind, fold)) return -1;
+    if (q < 1 || q > 64 || len != proof_data_len(log_n, log_b, q, grind, fold)) return -1;
     Channel ch;
     const uint8_t* p = data;
     int k = 0;
@@ -424,15 +318,15 @@ inline int verify_transcript_fold(const uint8_t* data, size_t len, const uint8_t
         commit(32);                                         // root of the group's output
     }
     commit(4);                                              // free term
-    if (grind) {
+    if (grind) {                                            // nonce: the commit is SHA-256(S || le64(w))
         commit(8);
         const uint32_t w0 = ((uint32_t)ch.state[0] << 24) | ((uint32_t)ch.state[1] << 16) | ((uint32_t)ch.state[2] << 8) | ch.state[3];
         if (!grind_word_ok(w0, grind)) return -1998;
     }
     for (uint32_t j = 0; j < q; ++j) if (!challenge()) return -(1000 + k);   // queries
     for (uint32_t j = 0; j < q; ++j) {
-        for (int i = 0; i < 4; ++i) commit(4 + 8 + 32 * L);
-        for (uint32_t gi = 0; gi < G; ++gi) commit(((size_t)1 << fold_steps(log_n, fold, gi)) * (12 + 32 * (L - (size_t)gi * fold)));
+        for (int i = 0; i < 4; ++i) commit(Channel::group_bytes(1, L));
+        for (uint32_t gi = 0; gi < G; ++gi) commit(Channel::group_bytes((size_t)1 << fold_steps(log_n, fold, gi), L - (size_t)gi * fold));
     }
     if (memcmp(ch.state, state, 32)) return -1999;
     return 0;

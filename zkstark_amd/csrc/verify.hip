@@ -1,4 +1,5 @@
-// verify.hip -- batched proof verification on the device (zk_verifier_*) and the single-proof check number (zk_verify_check).
+// verify.hip -- batched proof verification on the device (zk_verifier_*).  The single-proof entry points (zk_verify*) are in
+// zkstark.hip; the CPU verifier itself, one for every folding factor, is transcript.hpp.
 //
 // The result of every proof is the number the CPU verifier stops at (transcript.hpp: verify_transcript, then verify_proof),
 // for every input.  The device gets there without a per-proof parser:
@@ -10,9 +11,9 @@
 //     visits them in); the smallest key per proof is the first failure (atomicMin);
 //   * strict mode: a transcript failure wins (verify_transcript runs first on the CPU), so it has its own result.
 // The raw-value rules of verify_proof are kept: values are reduced % P before arithmetic, but fv[3] is compared unreduced
-// with cp0, and the FRI expectation (lx[k + 1] or the free term) unreduced with a reduced calc.  Leaf hashes take the raw word.
+// with cp0, and the FRI expectation (value 0 of the next round's pair, or the free term) unreduced with a reduced calc.  Leaf hashes take the raw word.
 //
-// Folding factor 2^K (zk_verifier_set_fold, K = 2 or 3; transcript.hpp: verify_transcript_fold, then verify_proof_fold): the R
+// Folding factor 2^K (zk_verifier_set_fold, K = 2 or 3; transcript.hpp: verify_transcript, then verify_proof, with fold = K): the R
 // rounds come in G = ceil(R / K) groups, group j opens the s_j = 2^steps_j values of its input layer (round r0 = j K) and then
 // their s_j paths of L - r0 digests, so the layout is fixed in the same way and only the last group can be short.  The order
 // keys are query * (5 + 9G) + position: 0 (-2), 1..4 (-4..-7), 5 + j (the fold comparison of group j), 5 + G + 8j + t (path t
@@ -316,7 +317,7 @@ __device__ __forceinline__ void commit_words(uint32_t (&st)[8], const uint32_t* 
 
 // (3) transcript (strict only): one lane per proof, the commits of verify_transcript in its order.  The order is a schedule of
 // steps the same for every lane (a challenge, or a commit of nw words), walked by one loop with one commit site: the
-// compression is inlined once and the state stays in registers.  FOLD (verify_transcript_fold): G (beta, root) pairs, and per
+// compression is inlined once and the state stays in registers.  FOLD (verify_transcript with fold > 1): G (beta, root) pairs, and per
 // query one commit per group of its s_j values and paths.
 template <bool FOLD>
 __global__ void __launch_bounds__(kVerifyThreads) verify_transcript_kernel(VerifyArgs a) {
@@ -389,7 +390,7 @@ int32_t key_to_check(int32_t key, uint32_t R) {
     const uint32_t j = pos - 5u - R;
     return -(int32_t)((j & 1u ? 400u : 300u) + j / 2u);
 }
-// The same for the keys of a folded proof (G groups): verify_proof_fold's number.
+// The same for the keys of a folded proof (G groups): verify_proof's number with fold > 1.
 int32_t fold_key_to_check(int32_t key, uint32_t G) {
     const uint32_t pos = (uint32_t)key % (5u + 9u * G);
     if (pos == 0) return -2;
@@ -516,8 +517,7 @@ int verifier_chunk(zk_verifier* v, const uint8_t* proofs, size_t stride, size_t 
         int32_t c;
         if (states && tcode[i]) c = tcode[i];
         else if (malformed[i])                             // garbage only
-            c = K == 1 ? verify_proof(proofs + i * stride, len, log_n, log_b, public_last[i], v->hash, q, v->grind)
-                       : verify_proof_fold(proofs + i * stride, len, log_n, log_b, public_last[i], v->hash, q, v->grind, K);
+            c = verify_proof(proofs + i * stride, len, log_n, log_b, public_last[i], v->hash, q, v->grind, K);
         else c = best[i] == kNoFailure ? 0 : (K == 1 ? key_to_check(best[i], R) : fold_key_to_check(best[i], G));
         checks_out[i] = c;
     }
@@ -527,21 +527,6 @@ int verifier_chunk(zk_verifier* v, const uint8_t* proofs, size_t stride, size_t 
 }  // namespace
 
 extern "C" {
-
-int zk_verify_grind(const uint8_t* proof, size_t len, const uint8_t* state, uint32_t log_n, uint32_t log_b, uint32_t public_last,
-                    int hash_kind, uint32_t n_queries, uint32_t grind_bits, int32_t* check_out) {
-    if (!proof || !check_out) return fail(ZK_ERR_INVALID, "zk_verify_check: null argument");
-    if (hash_kind != ZK_HASH_SHA256 && hash_kind != ZK_HASH_FIELD) return fail(ZK_ERR_INVALID, "zk_verify_check: unknown hash %d", hash_kind);
-    int rc = state ? verify_transcript(proof, len, state, log_n, log_b, n_queries, grind_bits) : 0;   // as zk_verify_queries: the replay first
-    if (!rc) rc = verify_proof(proof, len, log_n, log_b, public_last, hash_kind, n_queries, grind_bits);
-    *check_out = rc;
-    if (rc) return fail(ZK_ERR_VERIFY, "proof rejected at check %d", rc);
-    return ZK_OK;
-}
-int zk_verify_check(const uint8_t* proof, size_t len, const uint8_t* state, uint32_t log_n, uint32_t log_b, uint32_t public_last,
-                    int hash_kind, uint32_t n_queries, int32_t* check_out) {
-    return zk_verify_grind(proof, len, state, log_n, log_b, public_last, hash_kind, n_queries, 0, check_out);
-}
 
 int zk_verifier_destroy(zk_verifier* v) {
     if (!v) return ZK_OK;
@@ -617,7 +602,7 @@ int zk_verifier_run(zk_verifier* v, const uint8_t* proofs, size_t stride, size_t
     if (!v) return fail(ZK_ERR_INVALID, "null verifier");
     if (count == 0) return ZK_OK;
     if (!proofs || !public_last || !checks_out) return fail(ZK_ERR_INVALID, "zk_verifier_run: null argument");
-    const size_t len = proof_data_len_fold(v->log_n, v->log_b, v->queries, v->grind, v->fold);   // fold 1: proof_data_len
+    const size_t len = proof_data_len(v->log_n, v->log_b, v->queries, v->grind, v->fold);
     if (stride < len) return fail(ZK_ERR_INVALID, "zk_verifier_run: stride %zu < proof length %zu", stride, len);
     if (count > SIZE_MAX / stride) return fail(ZK_ERR_INVALID, "zk_verifier_run: count * stride overflows");
     HIPCHK(hipSetDevice(v->device));

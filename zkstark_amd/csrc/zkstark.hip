@@ -514,14 +514,11 @@ int open_wait(zk_ctx* c) {
     return wait_mail(c, c->mail_seq);
 }
 
-// generate_proof(channel) (prover.rs:9): everything is committed to, and every challenge drawn from, the
-// caller's channel `ch`, which may already hold a transcript prefix (main.rs:19 starts from a fresh one).
-// FRI rounds and decommitment of a proof folded by 2^fold between commitments (fold > 1; DESIGN.md "Folding factor"): per group of
+// FRI rounds of a proof folded by 2^fold between commitments (fold > 1; DESIGN.md "Folding factor"): per group of
 // `steps` rounds one challenge, one pass of the multi-fold kernel (prover.rs:201-211, steps times), one tree (prover.rs:214) over
 // its output, one root (prover.rs:224).  Every layer is folded on the device (no host FRI tail); tree tops go to the host as usual.
 int prove_fold_rounds(zk_ctx* c, Channel& ch) {
     const uint32_t R = c->R, K = c->fold;
-    const size_t B = c->B, N = c->N, Lp = c->L;
     uint8_t root[32];
     int rc;
     for (uint32_t r0 = 0; r0 < R; r0 += K) {
@@ -537,82 +534,87 @@ int prove_fold_rounds(zk_ctx* c, Channel& ch) {
         memcpy(c->info.roots[id], root, 32);
         for (uint32_t l = 2 + r0; l < id; ++l) { c->skipped_layers |= (uint64_t)1 << l; c->skipped_trees |= (uint64_t)1 << l; }
     }
+    return ZK_OK;
+}
+
+// ZK_HOST_TIMING=1: the host time between named points of a proof, on stderr
+struct HostLaps {
+    const bool on;
+    std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+    void operator()(const char* what) {
+        if (!on) return;
+        auto t = std::chrono::steady_clock::now();
+        fprintf(stderr, "[zk timing] %-28s %8.1f us\n", what, std::chrono::duration<double, std::micro>(t - t0).count());
+        t0 = t;
+    }
+};
+
+// Everything after the last root, for every folding factor: the free term (prover.rs:254), grinding, the query draw (prover.rs:263)
+// and the decommitment (prover.rs:266-289) in the order of for_each_opening, one commit_group per tuple (transcript.hpp).
+int prove_finish(zk_ctx* c, Channel& ch, HostLaps& lap) {
+    const uint32_t R = c->R, K = c->fold, Q = c->queries, G = fold_groups(R, K);
+    const size_t B = c->B, N = c->N, Lp = c->L;
+    int rc;
+    // last layer: B evaluations of a degree-0 polynomial (prover.rs:238, :251)
     uint32_t free_term = 0;
     if ((rc = last_layer_value(c, &free_term))) return rc;
     c->info.free_term = free_term;
     ch.commit_u32(free_term);                             // prover.rs:254
-    if (c->grind) {
+    if (c->grind) {                                       // proof of work on the state after the free term (DESIGN.md "Grinding")
         uint64_t w = 0;
         if ((rc = grind_channel(c->grinder, ch, c->grind, &w))) return rc;
         c->info.grind_bits = c->grind;
         c->info.grind_nonce = w;
+        lap("grind");
     }
-    const uint32_t Q = c->queries;
     uint32_t qraws[64];
-    for (uint32_t k = 0; k < Q; ++k) qraws[k] = ch.get_u32();   // prover.rs:263
+    for (uint32_t k = 0; k < Q; ++k) qraws[k] = ch.get_u32();   // prover.rs:263 (x Q, SURVEY 8f item 1)
     c->info.query_raw = qraws[0];
-    size_t per_query = 4;
-    for (uint32_t r0 = 0; r0 < R; r0 += K) per_query += (size_t)1 << (R - r0 < K ? R - r0 : K);
+
+    // decommit (prover.rs:266-289).  Values and path nodes this thread built itself during the proof (tree tops, the small
+    // FRI layers and their trees) are still in the staging buffer and are read from there; everything else comes back
+    // through ONE launch that takes its work list from host-mapped memory, writes its results there and raises the
+    // mailbox flag behind them: no copy commands, no stream synchronisation.  The scatter that completes the device
+    // arrays with the host-built parts is enqueued behind it, off the proof's critical path.
+    size_t per_query = 0;
+    for_each_opening(c->log_n, c->log_b, K, 0, [&](uint32_t, uint32_t, size_t) { ++per_query; });
     open_begin(c, (size_t)Q * per_query);
-    for (uint32_t k = 0; k < Q; ++k) {
-        const size_t x = (size_t)qraws[k] % (N - 2 * B);
-        open_val(c, 0, x);         open_path(c, 0, N, x);
-        open_val(c, 0, x + B);     open_path(c, 0, N, x + B);
-        open_val(c, 0, x + 2 * B); open_path(c, 0, N, x + 2 * B);
-        open_val(c, 1, x);         open_path(c, 1, N, x);
-        for (uint32_t r0 = 0; r0 < R; r0 += K) {          // prover.rs:280-289 widened: the s coset values of the group's input layer
-            const size_t s = (size_t)1 << (R - r0 < K ? R - r0 : K), len = N >> r0, xi = x % len;
-            for (size_t t = 0; t < s; ++t) {
-                const size_t idx = (xi + t * (len / s)) % len;
-                open_val(c, 1 + r0, idx); open_path(c, 1 + r0, len, idx);
-            }
-        }
-    }
+    for (uint32_t k = 0; k < Q; ++k)
+        for_each_opening(c->log_n, c->log_b, K, (size_t)qraws[k] % (N - 2 * B), [&](uint32_t layer, uint32_t log_len, size_t leaf) {
+            open_val(c, layer, leaf); open_path(c, layer, (size_t)1 << log_len, leaf);
+        });
     if ((rc = open_launch(c))) return rc;
-    if ((rc = flush_host_parts(c))) return rc;
+    if ((rc = flush_host_parts(c))) return rc;            // completes the device arrays, behind the fetch: off the critical path
+    lap("free term + fetch enqueue");
     if ((rc = open_wait(c))) return rc;
-    std::vector<const uint32_t*>& vsrc = c->fetch_vals;
-    std::vector<const uint32_t*>& dsrc = c->fetch_nodes;
-    std::vector<uint8_t>& buf = c->commit_buf;
-    buf.resize(8 * (12 + 32 * Lp));
-    auto put32 = [](uint8_t* p, uint32_t v) { for (int i = 0; i < 4; ++i) p[i] = (uint8_t)(v >> (8 * i)); };
-    auto put_path = [&](uint8_t* p, size_t first, size_t plen) {
-        for (int i = 0; i < 8; ++i) p[i] = (uint8_t)((uint64_t)plen >> (8 * i));
-        for (size_t j = 0; j < plen; ++j) digest_words_to_bytes(dsrc[first + j], p + 8 + 32 * j);
-        return 8 + 32 * plen;
+    lap("fetch wait");
+    const uint32_t* const* vsrc = c->fetch_vals.data();
+    const uint32_t* const* dsrc = c->fetch_nodes.data();
+    std::vector<uint8_t>& buf = c->commit_buf;            // reused from proof to proof; the first group's tuple is the largest
+    buf.resize(Channel::group_bytes((size_t)1 << fold_steps(R, K, 0), Lp));
+    auto tuple = [&](size_t s, size_t plen) {
+        ch.commit_group(buf.data(), s, plen, [&](size_t t) { return *vsrc[t]; },
+                        [&](size_t i, uint8_t* out) { digest_words_to_bytes(dsrc[i], out); });
+        vsrc += s; dsrc += s * plen;
     };
-    size_t vi = 0, dpos = 0;
     for (uint32_t q = 0; q < Q; ++q) {
-        for (int k = 0; k < 4; ++k) {                         // (u32, AuthPath): prover.rs:274-277
-            put32(buf.data(), *vsrc[vi++]);
-            const size_t len = 4 + put_path(buf.data() + 4, dpos, Lp);
-            ch.commit_bytes(buf.data(), len);
-            dpos += Lp;
-        }
-        for (uint32_t r0 = 0; r0 < R; r0 += K) {              // s values, then their s paths: one commit per group
-            const size_t s = (size_t)1 << (R - r0 < K ? R - r0 : K), pl = Lp - r0;
-            size_t len = 0;
-            for (size_t t = 0; t < s; ++t) { put32(buf.data() + len, *vsrc[vi++]); len += 4; }
-            for (size_t t = 0; t < s; ++t) { len += put_path(buf.data() + len, dpos, pl); dpos += pl; }
-            ch.commit_bytes(buf.data(), len);
-        }
+        for (int k = 0; k < 4; ++k) tuple(1, Lp);                                             // (u32, AuthPath): prover.rs:274-277
+        for (uint32_t j = 0; j < G; ++j) tuple((size_t)1 << fold_steps(R, K, j), Lp - (size_t)j * K);   // prover.rs:280-289, per group
     }
-    return ZK_OK;
+    lap("decommit host hashing");
+    return ZK_OK;                                         // the proof is the channel: channel.rs:34-36
 }
 
+// generate_proof(channel) (prover.rs:9): everything is committed to, and every challenge drawn from, the
+// caller's channel `ch`, which may already hold a transcript prefix (main.rs:19 starts from a fresh one).
+// Only the round loops differ with the folding factor: K = 1 has the fused fold, the early launch and the host tail; K > 1 has
+// prove_fold_rounds.
 int prove_resident(zk_ctx* c, Channel& ch) {
     if (!c->have_trace) return fail(ZK_ERR_STATE, "zk_prove_resident: no trace uploaded");
     static const bool timing = getenv("ZK_HOST_TIMING") != nullptr;
-    auto T0 = std::chrono::steady_clock::now();
-    auto lap = [&](const char* what) {
-        if (!timing) return;
-        auto t = std::chrono::steady_clock::now();
-        fprintf(stderr, "[zk timing] %-28s %8.1f us\n", what, std::chrono::duration<double, std::micro>(t - T0).count());
-        T0 = t;
-    };
+    HostLaps lap{timing};
     const uint32_t R = c->R;
-    const size_t B = c->B, N = c->N;
-    ch.data.reserve(ch.data.size() + proof_data_len_fold(c->log_n, c->log_b, c->queries, c->grind, c->fold));
+    ch.data.reserve(ch.data.size() + proof_data_len(c->log_n, c->log_b, c->queries, c->grind, c->fold));
     c->skipped_layers = c->skipped_trees = 0;
     uint8_t root[32];
     int rc;
@@ -635,8 +637,9 @@ int prove_resident(zk_ctx* c, Channel& ch) {
     if (c->checks && (rc = check_degree(c, 1, (uint32_t)c->n - 1, "prover.rs:148-159/:169 (exact divisions, deg cp = n - 1)"))) return rc;
     ch.commit_hash(root);                                 // prover.rs:180
     memcpy(c->info.roots[1], root, 32);
-    if (c->fold > 1) return prove_fold_rounds(c, ch);
-    for (uint32_t r = 0; r < R; ++r) {                    // prover.rs:198-225
+    if (c->fold > 1) {
+        if ((rc = prove_fold_rounds(c, ch))) return rc;
+    } else for (uint32_t r = 0; r < R; ++r) {             // prover.rs:198-225
         uint32_t beta = c->info.beta_raw[r] = ch.get_u32();   // prover.rs:200
         // prover.rs:201-214 (fold fused into the leaf hashing); on the host once the layers are small and present there
         if (c->gate_pending) {
@@ -656,78 +659,7 @@ int prove_resident(zk_ctx* c, Channel& ch) {
     }
     lap("lde .. last root");
     if (timing) fprintf(stderr, "[zk timing]   of which: waiting for the device %.1f us, host hashing (tops + tail) %.1f us\n", c->t_wait, c->t_host_hash);
-    // last layer: B evaluations of a degree-0 polynomial (prover.rs:238, :251); free term prover.rs:254
-    uint32_t free_term = 0;
-    if ((rc = last_layer_value(c, &free_term))) return rc;
-    c->info.free_term = free_term;
-    ch.commit_u32(free_term);                             // prover.rs:254
-    if (c->grind) {                                       // proof of work on the state after the free term (DESIGN.md "Grinding")
-        uint64_t w = 0;
-        if ((rc = grind_channel(c->grinder, ch, c->grind, &w))) return rc;
-        c->info.grind_bits = c->grind;
-        c->info.grind_nonce = w;
-        lap("grind");
-    }
-    const uint32_t Q = c->queries;
-    uint32_t qraws[64];
-    for (uint32_t k = 0; k < Q; ++k) qraws[k] = ch.get_u32();   // prover.rs:263 (x Q, SURVEY 8f item 1)
-    c->info.query_raw = qraws[0];
-
-    // decommit (prover.rs:266-289).  Values and path nodes this thread built itself during the proof (tree tops, the small
-    // FRI layers and their trees) are still in the staging buffer and are read from there; everything else comes back
-    // through ONE launch that takes its work list from host-mapped memory, writes its results there and raises the
-    // mailbox flag behind them: no copy commands, no stream synchronisation.  The scatter that completes the device
-    // arrays with the host-built parts is enqueued behind it, off the proof's critical path.
-    open_begin(c, (size_t)Q * (4 + 2 * R));
-    for (uint32_t k = 0; k < Q; ++k) {
-        const size_t x = (size_t)qraws[k] % (N - 2 * B);
-        open_val(c, 0, x);         open_path(c, 0, N, x);
-        open_val(c, 0, x + B);     open_path(c, 0, N, x + B);
-        open_val(c, 0, x + 2 * B); open_path(c, 0, N, x + 2 * B);
-        open_val(c, 1, x);         open_path(c, 1, N, x);
-        for (uint32_t i = 0; i < R; ++i) {
-            size_t len = N >> i, xi = x % len, nx = (xi + len / 2) % len;
-            open_val(c, 1 + i, xi); open_path(c, 1 + i, len, xi);
-            open_val(c, 1 + i, nx); open_path(c, 1 + i, len, nx);
-        }
-    }
-    if ((rc = open_launch(c))) return rc;
-    if ((rc = flush_host_parts(c))) return rc;            // completes the device arrays, behind the fetch: off the critical path
-    lap("free term + fetch enqueue");
-    if ((rc = open_wait(c))) return rc;
-    lap("fetch wait");
-    std::vector<const uint32_t*>& vsrc = c->fetch_vals;
-    std::vector<const uint32_t*>& dsrc = c->fetch_nodes;
-    size_t vi = 0;
-    const size_t Lp = c->L;
-    std::vector<uint8_t>& buf = c->commit_buf;
-    buf.resize(8 + 2 * (8 + 32 * Lp));
-    auto put32 = [](uint8_t* p, uint32_t v) { for (int i = 0; i < 4; ++i) p[i] = (uint8_t)(v >> (8 * i)); };
-    auto put_path = [&](uint8_t* p, size_t first, size_t plen) {       // Box<[Hash]>: u64 count + items
-        for (int i = 0; i < 8; ++i) p[i] = (uint8_t)((uint64_t)plen >> (8 * i));
-        for (size_t j = 0; j < plen; ++j) digest_words_to_bytes(dsrc[first + j], p + 8 + 32 * j);
-        return 8 + 32 * plen;
-    };
-    size_t dpos = 0;
-    for (uint32_t q = 0; q < Q; ++q) {
-        for (int k = 0; k < 4; ++k) {                         // (u32, AuthPath): prover.rs:274-277
-            put32(buf.data(), *vsrc[vi++]);
-            const size_t len = 4 + put_path(buf.data() + 4, dpos, Lp);
-            ch.commit_bytes(buf.data(), len);
-            dpos += Lp;
-        }
-        for (uint32_t i = 0; i < R; ++i) {                    // (u32, u32, AuthPath, AuthPath): prover.rs:280-289
-            const size_t pl = Lp - i;
-            put32(buf.data(), *vsrc[vi]); put32(buf.data() + 4, *vsrc[vi + 1]);
-            vi += 2;
-            size_t len = 8 + put_path(buf.data() + 8, dpos, pl);
-            len += put_path(buf.data() + len, dpos + pl, pl);
-            ch.commit_bytes(buf.data(), len);
-            dpos += 2 * pl;
-        }
-    }
-    lap("decommit host hashing");
-    return ZK_OK;                                         // the proof is the channel: channel.rs:34-36
+    return prove_finish(c, ch, lap);
 }
 
 }  // namespace
@@ -1331,12 +1263,28 @@ int zk_last_transcript(const zk_ctx* c, zk_transcript_info* out) {
     return abi_put(out, c->info, "zk_last_transcript");
 }
 
+// Behind the seven zk_verify* entry points, after their own null checks: the hash and fold_log checks in the name of `who`, the
+// transcript replay first when a state is given, then the proof checks (transcript.hpp).  The check number goes to *check_out
+// (if any) and into the message: "proof rejected at check N" + reject_note, or, for the entry points that tell a failed replay
+// apart (replay_note not null), "transcript replay failed at check N" + replay_note.
+static int verify_entry(const char* who, const uint8_t* proof, size_t len, const uint8_t* state, uint32_t log_n, uint32_t log_b,
+                        uint32_t public_last, int hash_kind, uint32_t q, uint32_t grind, uint32_t fold, int32_t* check_out,
+                        const char* replay_note, const char* reject_note) {
+    if (hash_kind != ZK_HASH_SHA256 && hash_kind != ZK_HASH_FIELD) return fail(ZK_ERR_INVALID, "%s: unknown hash %d", who, hash_kind);
+    if (fold < 1 || fold > kMaxFoldLog) return fail(ZK_ERR_INVALID, "%s: need 1 <= fold_log <= %u (got %u)", who, kMaxFoldLog, fold);
+    int rc = state ? verify_transcript(proof, len, state, log_n, log_b, q, grind, fold) : 0;
+    const bool in_replay = rc != 0;
+    if (!rc) rc = verify_proof(proof, len, log_n, log_b, public_last, hash_kind, q, grind, fold);
+    if (check_out) *check_out = rc;
+    if (!rc) return ZK_OK;
+    if (in_replay && replay_note) return fail(ZK_ERR_VERIFY, "transcript replay failed at check %d%s", rc, replay_note);
+    return fail(ZK_ERR_VERIFY, "proof rejected at check %d%s", rc, reject_note);
+}
+static const char kProofRs[] = " (proof.rs:15-149)";
+
 int zk_verify_ex(const uint8_t* proof, size_t len, uint32_t log_n, uint32_t log_b, uint32_t public_last, int hash_kind) {
     if (!proof) return fail(ZK_ERR_INVALID, "zk_verify: null proof");
-    if (hash_kind != ZK_HASH_SHA256 && hash_kind != ZK_HASH_FIELD) return fail(ZK_ERR_INVALID, "zk_verify: unknown hash %d", hash_kind);
-    int rc = verify_proof(proof, len, log_n, log_b, public_last, hash_kind);
-    if (rc) return fail(ZK_ERR_VERIFY, "proof rejected at check %d (proof.rs:15-149)", rc);
-    return ZK_OK;
+    return verify_entry("zk_verify", proof, len, nullptr, log_n, log_b, public_last, hash_kind, 1, 0, 1, nullptr, nullptr, kProofRs);
 }
 int zk_verify(const uint8_t* proof, size_t len, uint32_t log_n, uint32_t log_b, uint32_t public_last) {
     return zk_verify_ex(proof, len, log_n, log_b, public_last, ZK_HASH_SHA256);
@@ -1344,44 +1292,39 @@ int zk_verify(const uint8_t* proof, size_t len, uint32_t log_n, uint32_t log_b, 
 int zk_verify_queries(const uint8_t* proof, size_t len, const uint8_t* state, uint32_t log_n, uint32_t log_b, uint32_t public_last,
                       int hash_kind, uint32_t n_queries) {
     if (!proof) return fail(ZK_ERR_INVALID, "zk_verify_queries: null proof");
-    if (hash_kind != ZK_HASH_SHA256 && hash_kind != ZK_HASH_FIELD) return fail(ZK_ERR_INVALID, "zk_verify_queries: unknown hash %d", hash_kind);
-    if (state) {
-        int rc = verify_transcript(proof, len, state, log_n, log_b, n_queries);
-        if (rc) return fail(ZK_ERR_VERIFY, "transcript replay failed at check %d", rc);
-    }
-    int rc = verify_proof(proof, len, log_n, log_b, public_last, hash_kind, n_queries);
-    if (rc) return fail(ZK_ERR_VERIFY, "proof rejected at check %d (proof.rs:15-149)", rc);
-    return ZK_OK;
+    return verify_entry("zk_verify_queries", proof, len, state, log_n, log_b, public_last, hash_kind, n_queries, 0, 1, nullptr, "", kProofRs);
 }
-
 int zk_verify_strict(const uint8_t* proof, size_t len, const uint8_t state[32], uint32_t log_n, uint32_t log_b, uint32_t public_last) {
     if (!proof || !state) return fail(ZK_ERR_INVALID, "zk_verify_strict: null argument");
-    int rc = verify_transcript(proof, len, state, log_n, log_b);
-    if (rc) return fail(ZK_ERR_VERIFY, "transcript replay failed at check %d (challenge not derived from the transcript, or final state mismatch)", rc);
-    return zk_verify(proof, len, log_n, log_b, public_last);
+    return verify_entry("zk_verify", proof, len, state, log_n, log_b, public_last, ZK_HASH_SHA256, 1, 0, 1, nullptr,
+                        " (challenge not derived from the transcript, or final state mismatch)", kProofRs);
 }
-
-size_t zk_proof_size(size_t data_len) { return 48 + data_len; }   // proof.rs:151-154: size_of::<Proof>() = 32 + 16
-size_t zk_proof_data_len(uint32_t log_n, uint32_t log_b) { return proof_data_len(log_n, log_b); }
-size_t zk_proof_data_len_queries(uint32_t log_n, uint32_t log_b, uint32_t n_queries) { return proof_data_len(log_n, log_b, n_queries); }
-size_t zk_proof_data_len_grind(uint32_t log_n, uint32_t log_b, uint32_t n_queries, uint32_t grind_bits) {
-    return proof_data_len(log_n, log_b, n_queries, grind_bits);
+// zk_verify_grind and zk_verify_check speak as "zk_verify_check" in their argument errors
+int zk_verify_grind(const uint8_t* proof, size_t len, const uint8_t* state, uint32_t log_n, uint32_t log_b, uint32_t public_last,
+                    int hash_kind, uint32_t n_queries, uint32_t grind_bits, int32_t* check_out) {
+    if (!proof || !check_out) return fail(ZK_ERR_INVALID, "zk_verify_check: null argument");
+    return verify_entry("zk_verify_check", proof, len, state, log_n, log_b, public_last, hash_kind, n_queries, grind_bits, 1, check_out, nullptr, "");
 }
-size_t zk_proof_data_len_fold(uint32_t log_n, uint32_t log_b, uint32_t n_queries, uint32_t grind_bits, uint32_t fold_log) {
-    if (fold_log < 1 || fold_log > kMaxFoldLog) return 0;
-    return proof_data_len_fold(log_n, log_b, n_queries, grind_bits, fold_log);
+int zk_verify_check(const uint8_t* proof, size_t len, const uint8_t* state, uint32_t log_n, uint32_t log_b, uint32_t public_last,
+                    int hash_kind, uint32_t n_queries, int32_t* check_out) {
+    return zk_verify_grind(proof, len, state, log_n, log_b, public_last, hash_kind, n_queries, 0, check_out);
 }
 int zk_verify_fold(const uint8_t* proof, size_t len, const uint8_t* state, uint32_t log_n, uint32_t log_b, uint32_t public_last,
                    int hash_kind, uint32_t n_queries, uint32_t grind_bits, uint32_t fold_log, int32_t* check_out) {
     if (!proof || !check_out) return fail(ZK_ERR_INVALID, "zk_verify_fold: null argument");
-    if (hash_kind != ZK_HASH_SHA256 && hash_kind != ZK_HASH_FIELD) return fail(ZK_ERR_INVALID, "zk_verify_fold: unknown hash %d", hash_kind);
-    if (fold_log < 1 || fold_log > kMaxFoldLog) return fail(ZK_ERR_INVALID, "zk_verify_fold: need 1 <= fold_log <= %u (got %u)", kMaxFoldLog, fold_log);
-    int rc = state ? verify_transcript_fold(proof, len, state, log_n, log_b, n_queries, grind_bits, fold_log) : 0;   // as zk_verify_grind: the replay first
-    if (!rc) rc = verify_proof_fold(proof, len, log_n, log_b, public_last, hash_kind, n_queries, grind_bits, fold_log);
-    *check_out = rc;
-    if (rc) return fail(ZK_ERR_VERIFY, "proof rejected at check %d", rc);
-    return ZK_OK;
+    return verify_entry("zk_verify_fold", proof, len, state, log_n, log_b, public_last, hash_kind, n_queries, grind_bits, fold_log, check_out, nullptr, "");
 }
+
+size_t zk_proof_size(size_t data_len) { return 48 + data_len; }   // proof.rs:151-154: size_of::<Proof>() = 32 + 16
+size_t zk_proof_data_len_fold(uint32_t log_n, uint32_t log_b, uint32_t n_queries, uint32_t grind_bits, uint32_t fold_log) {
+    if (fold_log < 1 || fold_log > kMaxFoldLog) return 0;
+    return proof_data_len(log_n, log_b, n_queries, grind_bits, fold_log);
+}
+size_t zk_proof_data_len_grind(uint32_t log_n, uint32_t log_b, uint32_t n_queries, uint32_t grind_bits) {
+    return zk_proof_data_len_fold(log_n, log_b, n_queries, grind_bits, 1);
+}
+size_t zk_proof_data_len_queries(uint32_t log_n, uint32_t log_b, uint32_t n_queries) { return zk_proof_data_len_fold(log_n, log_b, n_queries, 0, 1); }
+size_t zk_proof_data_len(uint32_t log_n, uint32_t log_b) { return zk_proof_data_len_fold(log_n, log_b, 1, 0, 1); }
 
 int zk_compute_root_from_path_ex(uint32_t element, size_t index, const uint8_t* path, size_t path_len, uint8_t out[32], int hash_kind) {
     if ((!path && path_len) || !out || path_len > 62 || (hash_kind != 0 && hash_kind != 1))
