@@ -182,6 +182,26 @@ int zk_ctx_get_early_launch(const zk_ctx *ctx);
  * zk_verifier_* follows with zk_verifier_set_fold; zk_shard_* / zk_tail_* stay at factor 2. */
 int zk_ctx_set_fold(zk_ctx *ctx, uint32_t fold_log);
 uint32_t zk_ctx_get_fold(const zk_ctx *ctx);
+/* Coset leaves: off by default (with it off every byte, launch and allocation is what it was); valid with every fold_log, hash,
+ * query count, grinding and zk_prove_channel.  With it on, the tree over the input layer of group j (id 1 + r0, len = N >> r0 values,
+ * s = 2^steps_j) has len / s leaves; leaf c holds the slots u = 0 .. s-1, slot u = layer[c + u len / s] -- the coset a query opens there --
+ * so a group opens ONE leaf of s values and ONE path of L - r0 - steps digests instead of s values and s paths.  Leaf hash: SHA-256 over
+ * the s slots, 4 bytes big-endian each (one block), or the field hash's compression of (slot_0 .. slot_{s-1}, 0, ..., 0, s); s = 1 is the
+ * one-value leaf; inner nodes are unchanged.  Tree 0 (f) and the tree over the last layer (never opened) keep one-value leaves; the
+ * layers stay in natural order.  Per query: the three f tuples as ever, NO separate cp(x) tuple (group 0's leaf contains it), then per
+ * group the s slot values in slot order, a u64 count and the path for leaf x % (len / s).  Length: zk_proof_data_len_coset; verifier:
+ * zk_verify_coset.  At domain 2^24 with one query 12 252 / 7 332 / 5 644 bytes for fold_log 1 / 2 / 3 (plain leaves 23 280 / 23 560 /
+ * 31 008), with 32 queries 366 148 / 219 868 / 170 316.  A tree over len / s leaves costs 2 len / s hashes instead of 2 len (a leaf of up
+ * to 8 words is still one compression), hashed by coset_leaf_hash_kernel and the inner build.  Every layer is a device layer, for
+ * fold_log 1 too: the host FRI tail, the fold and the composition fused into leaf hashing and early launch apply only with coset
+ * leaves off (zk_ctx_get_early_launch answers 0); the tree-top hand-over works as usual on the smaller trees (a tree of at most
+ * 2^top_log LEAVES hands over one level below its leaves) and results are identical for every setting.  zk_merkle_node(s) /
+ * zk_merkle_path address a coset tree by its own leaves: 2 len / s - 1 nodes, leaf index < len / s, L - r0 - steps digests.
+ * Measured: see DESIGN.md 7d.
+ * NOT covered: zk_batch_*, zk_verifier_* and zk_shard_* / zk_tail_* keep one-value leaves; a zk_verifier_run on coset proofs rejects
+ * them by length (-1). */
+int zk_ctx_set_coset_leaves(zk_ctx *ctx, int on);
+int zk_ctx_get_coset_leaves(const zk_ctx *ctx);
 /* The HIP stream every stage is enqueued on (hipStream_t). */
 void *zk_ctx_stream(zk_ctx *ctx);
 
@@ -200,6 +220,9 @@ int zk_lde(zk_ctx *ctx);
  * the stream by the next call that reads trees or layers from the device (zk_merkle_node, zk_merkle_path, zk_layer_read,
  * zk_ctx_sync, zk_ctx_stream), not by this one: a loop of commitments does not pay a copy launch per iteration. */
 int zk_merkle_commit(zk_ctx *ctx, uint32_t layer, uint8_t root_out[32]);
+/* The tree over a layer of len values with 2^steps-wide coset leaves (zk_ctx_set_coset_leaves): leaf c < len / 2^steps holds
+ * layer[c + u len / 2^steps], u < 2^steps.  steps 0..3 with at least two leaves; steps = 0 is zk_merkle_commit. */
+int zk_merkle_commit_coset(zk_ctx *ctx, uint32_t layer, uint32_t steps, uint8_t root_out[32]);
 /* Constraint quotients and their random combination (prover.rs:101-173):
  * layer 1 <- cp(w h^i).  alpha_raw are the raw u32 challenges (prover.rs:163-165). */
 int zk_compose(zk_ctx *ctx, const uint32_t alpha_raw[3]);
@@ -355,6 +378,9 @@ size_t zk_proof_data_len_grind(uint32_t log_n, uint32_t log_blowup, uint32_t n_q
 /* Proofs made with zk_ctx_set_fold(fold_log): 32 + 12 + 32 + 36 G + 4 + (grind ? 8 : 0) + q (4 + 4 (12 + 32 L) + sum over the
  * G = ceil(log_n / fold_log) groups of 2^steps (12 + 32 (L - r0))).  fold_log = 1: zk_proof_data_len_grind.  0 for a fold_log outside 1..3. */
 size_t zk_proof_data_len_fold(uint32_t log_n, uint32_t log_blowup, uint32_t n_queries, uint32_t grind_bits, uint32_t fold_log);
+/* Proofs made with zk_ctx_set_coset_leaves: 32 + 12 + 32 + 36 G + 4 + (grind ? 8 : 0) + q (4 + 3 (12 + 32 L) + sum over the groups of
+ * 4 s + 8 + 32 (L - r0 - steps)), s = 2^steps.  0 for a fold_log outside 1..3. */
+size_t zk_proof_data_len_coset(uint32_t log_n, uint32_t log_blowup, uint32_t n_queries, uint32_t grind_bits, uint32_t fold_log);
 /* Proof-of-work search (zk_ctx_set_grinding): the smallest nonce >= start whose SHA-256(state || le64(nonce)) begins with
  * grind_bits zero bits (0..32; 0 gives start), on the GPU (zk_grind) or on <= 16 host threads (zk_grind_host; threads is
  * clamped to 1..16).  Gives up with an error naming grind_bits after 2^44 nonces.  A zk_channel user grinds on
@@ -367,6 +393,9 @@ int zk_compute_root_from_path(uint32_t element, size_t index, const uint8_t *pat
 
 int zk_compute_root_from_path_ex(uint32_t element, size_t index, const uint8_t *path, size_t path_len,
                                  uint8_t out[32], int hash_kind);
+/* The same from the s = 1, 2, 4 or 8 slot values of coset leaf `leaf` (zk_ctx_set_coset_leaves); s = 1 is the call above. */
+int zk_compute_root_from_coset(const uint32_t *values, uint32_t s, size_t leaf, const uint8_t *path, size_t path_len,
+                               uint8_t out[32], int hash_kind);
 
 /* ---- batched verification on the GPU (csrc/verify.hip) ---------------------------------------------------------------
  * The check number the CPU verifier stops at: 0 = accepted; otherwise the number zk_verify_queries names in its error
@@ -389,6 +418,14 @@ int zk_verify_grind(const uint8_t *proof, size_t len, const uint8_t *state, uint
  * input the number zk_verify_grind gives it. */
 int zk_verify_fold(const uint8_t *proof, size_t len, const uint8_t *state, uint32_t log_n, uint32_t log_blowup,
                    uint32_t public_last, int hash_kind, uint32_t n_queries, uint32_t grind_bits, uint32_t fold_log, int32_t *check_out);
+
+/* zk_verify_fold for proofs made with zk_ctx_set_coset_leaves.  With rot = (x % len) / (len / s), value t of a group is slot
+ * (rot + t) % s of its leaf; from there on the fold arithmetic and its comparison are zk_verify_fold's.  Check numbers: -2 compares the
+ * recomputed cp0 with group 0's value 0, -3 covers the three f path lengths, -4..-6 the f paths, -(100+j) / -(200+j) / -(300+j) the fold,
+ * the path length and the path of group j; -7 and -(400+j) do not occur.  The replay counts 3 + G + q challenges and commits per
+ * query three f tuples and one tuple per group.  A plain proof is rejected by length (-1), as a coset proof is by zk_verify_fold. */
+int zk_verify_coset(const uint8_t *proof, size_t len, const uint8_t *state, uint32_t log_n, uint32_t log_blowup,
+                    uint32_t public_last, int hash_kind, uint32_t n_queries, uint32_t grind_bits, uint32_t fold_log, int32_t *check_out);
 
 /* A verifier for many proofs of one size (log_n, log_blowup: the sizes zk_verify_queries accepts).  It owns its streams and
  * device buffers (grown on demand) and a pinned staging buffer.  One verifier is used from one host thread at a time. */

@@ -137,6 +137,12 @@ SYMBOLS = {
     "zk_grind_host": (_int, [_vp, _u32, C.c_uint64, _u32, C.POINTER(C.c_uint64)]),
     "zk_ctx_set_fold": (_int, [_vp, _u32]),
     "zk_ctx_get_fold": (_u32, [_vp]),
+    "zk_ctx_set_coset_leaves": (_int, [_vp, _int]),
+    "zk_ctx_get_coset_leaves": (_int, [_vp]),
+    "zk_merkle_commit_coset": (_int, [_vp, _u32, _u32, _vp]),
+    "zk_proof_data_len_coset": (_sz, [_u32, _u32, _u32, _u32, _u32]),
+    "zk_verify_coset": (_int, [_vp, _sz, _vp, _u32, _u32, _u32, _int, _u32, _u32, _u32, C.POINTER(C.c_int32)]),
+    "zk_compute_root_from_coset": (_int, [_vp, _u32, _sz, _vp, _sz, _vp, _int]),
     "zk_fri_fold_multi": (_int, [_vp, _u32, _u32, _u32]),
     "zk_dev_fri_fold_multi": (_int, [_vp, _vp, _vp, _u32, _u32, _u32, _u32, _vp]),
     "zk_dev_fri_fold_multi_batch": (_int, [_vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _u32, _vp]),

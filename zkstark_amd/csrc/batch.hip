@@ -154,7 +154,7 @@ const uint32_t* bfinish_roots(zk_batch* b, uint32_t tree, uint32_t log_m) {
 // values and path digests one query opens (transcript.hpp: for_each_opening)
 void bopenings(const zk_batch* b, uint32_t fold, size_t* vals, size_t* digs) {
     *vals = *digs = 0;
-    for_each_opening(b->log_n, b->log_b, fold, 0, [&](uint32_t, uint32_t log_len, size_t) { ++*vals; *digs += log_len; });
+    for_each_opening(b->log_n, b->log_b, fold, 0, [&](uint32_t, uint32_t log_len, size_t, uint32_t) { ++*vals; *digs += log_len; });
 }
 // gather buffers for q queries per proof (offsets in, values + digests out; device and pinned host copies), for the current fold
 int balloc_gather(zk_batch* b, uint32_t q) {
@@ -567,7 +567,7 @@ int zk_batch_prove(zk_batch* b, uint8_t* proofs_out, size_t stride, uint8_t* sta
             }
         };
         for (uint32_t k = 0; k < Q; ++k)                                  // layer l is stored proof-major: proof p's values at p * len
-            for_each_opening(b->log_n, b->log_b, K, (size_t)qraw[k] % (N - 2 * B), [&](uint32_t layer, uint32_t log_len, size_t leaf) {
+            for_each_opening(b->log_n, b->log_b, K, (size_t)qraw[k] % (N - 2 * B), [&](uint32_t layer, uint32_t log_len, size_t leaf, uint32_t) {
                 *vo++ = b->layer_off[layer] + (p << log_len) + leaf; add_path(layer, log_len, leaf);
             });
     });

@@ -17,6 +17,7 @@
 //   Constants: c = (first 8 bytes, big-endian, of SHA-256("zkstark_amd.fieldhash.v1" || LE32(k))) mod P,
 //      k = 16 r + i for the full rounds, k = 128 + r for the partial rounds.
 //   leaf(v)      = trunc8(perm(s) + s),  s = (v, 0, ..., 0, 1)
+//   coset leaf(v_0 .. v_{k-1}), k in {1, 2, 4, 8} = trunc8(perm(s) + s),  s = (v_0, ..., v_{k-1}, 0, ..., 0, k)   (k = 1: leaf(v))
 //   node(l, r)   = trunc8(perm(s) + s),  s = l || r (8 elements each)
 //   A digest is 8 canonical residues; as bytes each is 4 bytes big-endian (32 bytes in all).
 #pragma once
@@ -138,6 +139,14 @@ ZK_HD void fh_compress(const uint32_t (&in)[kFhT], uint32_t (&out)[8], const Fie
 }
 ZK_HD Digest fieldhash_leaf(uint32_t v, const FieldHashConsts& c) {
     uint32_t in[kFhT] = {v, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1u};
+    Digest d;
+    fh_compress(in, d.w, c);
+    return d;
+}
+ZK_HD Digest fieldhash_coset_leaf(const uint32_t* v, uint32_t k, const FieldHashConsts& c) {
+    uint32_t in[kFhT] = {0};
+    for (uint32_t i = 0; i < k && i < 8; ++i) in[i] = v[i];
+    in[kFhT - 1] = k;
     Digest d;
     fh_compress(in, d.w, c);
     return d;

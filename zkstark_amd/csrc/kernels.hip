@@ -1320,6 +1320,61 @@ void dump_wg_trace() {
 }
 #endif
 
+// ---- coset leaves (transcript.hpp "coset") -------------------------------------------------------------------
+// Leaf c of the tree over a layer of 2^log_len values holds the s = 2^STEPS values layer[c + u len / s], u < s: what one query
+// opens in that layer.  A lane owns leaves c, c + stride, ...: its s loads are s coalesced runs across the wave (the layer stays
+// in natural order), the values of its NEXT leaf are in flight while it hashes the current one (the fetch / finish split of the
+// leaf sources), and a leaf is ONE compression whatever s: SHA-256 of 4 s <= 32 bytes is a single block whose padding words fold
+// away in the schedule, the field hash takes the state (slot_0 .. slot_{s-1}, 0, ..., 0, s).  s = 1 is Hasher::leaf.  The digest
+// goes to heap position len / s - 1 + c; the levels above are built from there by the inner kernels (launch_merkle_build_coset).
+template <int HASH, int S>
+__device__ __forceinline__ Digest coset_leaf_digest(const uint32_t (&v)[S]) {
+    Digest d;
+    if (HASH) {
+        uint32_t in[kFhT];
+#pragma unroll
+        for (int i = 0; i < kFhT; ++i) in[i] = i < S ? v[i] : 0u;
+        in[kFhT - 1] = (uint32_t)S;
+        fh64_compress(in, d.w, g_fh_consts64);
+    } else {
+        uint32_t w[16];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) w[i] = i < S ? v[i] : 0u;
+        w[S] = 0x80000000u;
+        w[15] = 32u * S;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) d.w[i] = SHA_IV[i];
+        sha256_compress(d.w, w);
+    }
+    return d;
+}
+constexpr int kCosetThreads = 256;
+template <int HASH, int STEPS>
+__global__ __launch_bounds__(kCosetThreads) void coset_leaf_hash_kernel(const uint32_t* __restrict__ layer, uint32_t log_len, uint32_t* __restrict__ nodes) {
+    constexpr int S = 1 << STEPS;
+    const size_t leaves = (size_t)1 << (log_len - STEPS);        // also the distance between two slots of a leaf
+    const size_t stride = (size_t)gridDim.x * kCosetThreads;     // a power of two <= leaves, or one workgroup: every lane of a wave makes the same trips
+    size_t c = (size_t)blockIdx.x * kCosetThreads + threadIdx.x;
+    if (c >= leaves) return;
+    uint32_t v[S], nx[S] = {};
+#pragma unroll
+    for (int u = 0; u < S; ++u) v[u] = layer[c + (size_t)u * leaves];
+    bool more;
+#pragma unroll 1
+    do {
+        const size_t cn = c + stride;
+        more = cn < leaves;
+        if (more) {
+#pragma unroll
+            for (int u = 0; u < S; ++u) nx[u] = layer[cn + (size_t)u * leaves];
+        }
+        store_digest(nodes, leaves - 1 + c, coset_leaf_digest<HASH, S>(v));
+#pragma unroll
+        for (int u = 0; u < S; ++u) v[u] = nx[u];
+        c = cn;
+    } while (more);
+}
+
 static double merkle_bytes(bool leaf, uint32_t depth, uint32_t k) {
     // inputs read once (4 B values or 32 B digests), every produced digest written once
     double in = (double)((size_t)1 << depth);
@@ -1501,6 +1556,38 @@ static hipError_t merkle_build_t(SRC src, double src_bytes, uint32_t log_m, uint
 hipError_t launch_merkle_build(const uint32_t* vals, uint32_t log_m, uint32_t* nodes, hipStream_t s, Profiler* prof,
                                const MailArgs& mail, int hash) {
     return merkle_build_t(PlainSrc{vals}, 4.0 * (double)((size_t)1 << log_m), log_m, nodes, s, prof, mail, hash);
+}
+// Tree with coset leaves over a layer of 2^log_len values (steps in 1..3, log_len > steps): one launch hashes the 2^(log_len - steps)
+// leaves into the heap, the build above them is the inner-mode build every chunked tree already ends with (mailbox and hand-over
+// as for every tree).  Each lane takes up to four leaves so that the loads of the next one overlap a hash.
+template <int HASH>
+static void coset_leaf_launch(const uint32_t* vals, uint32_t log_len, uint32_t steps, uint32_t* nodes, uint32_t blocks, hipStream_t s) {
+    const dim3 g(blocks), b(kCosetThreads);
+    if (steps == 1) hipLaunchKernelGGL((coset_leaf_hash_kernel<HASH, 1>), g, b, 0, s, vals, log_len, nodes);
+    else if (steps == 2) hipLaunchKernelGGL((coset_leaf_hash_kernel<HASH, 2>), g, b, 0, s, vals, log_len, nodes);
+    else hipLaunchKernelGGL((coset_leaf_hash_kernel<HASH, 3>), g, b, 0, s, vals, log_len, nodes);
+}
+hipError_t launch_merkle_build_coset(const uint32_t* vals, uint32_t log_len, uint32_t steps, uint32_t* nodes, hipStream_t s, Profiler* prof,
+                                     const MailArgs& mail, int hash) {
+    if (steps == 0) return launch_merkle_build(vals, log_len, nodes, s, prof, mail, hash);
+    if (steps > 3 || log_len <= steps) return hipErrorInvalidValue;
+    if (hash) {
+        hipError_t e = ensure_fieldhash_consts();
+        if (e != hipSuccess) return e;
+    }
+    const uint32_t log_m = log_len - steps;
+    const size_t leaves = (size_t)1 << log_m;
+    const size_t lanes = leaves > 4 * (size_t)kCosetThreads ? leaves / 4 : leaves;
+    const uint32_t blocks = (uint32_t)((lanes + kCosetThreads - 1) / kCosetThreads);
+    {
+        ScopedKernelTimer tm(prof, K_MERKLE_LEAF, 4.0 * (double)((size_t)1 << log_len) + 32.0 * (double)leaves, s,
+                             (double)leaves * (hash ? kFieldLeafOps : kShaLeafOps));
+        if (hash) coset_leaf_launch<1>(vals, log_len, steps, nodes, blocks, s);
+        else coset_leaf_launch<0>(vals, log_len, steps, nodes, blocks, s);
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    return merkle_build_t(PlainSrc{nullptr}, 0.0, log_m, nodes, s, prof, mail, hash, log_m, 0, false);
 }
 // commitment of a block whose leaves are still in all-to-all order (no interleave pass, no block buffer)
 hipError_t launch_merkle_build_interleaved(const uint32_t* recv, uint32_t log_parts, uint32_t log_cnt, uint32_t* nodes, hipStream_t s,

@@ -256,6 +256,11 @@ struct MailArgs {
 };
 hipError_t launch_merkle_build(const uint32_t* vals, uint32_t log_m, uint32_t* nodes, hipStream_t s, Profiler* prof = nullptr,
                                const MailArgs& mail = MailArgs{}, int hash = 0);
+// Coset leaves (transcript.hpp): leaf c of the 2^(log_len - steps) leaves holds vals[c + u 2^(log_len - steps)], u < 2^steps, hashed
+// by coset_leaf_hash_kernel (profiled as K_MERKLE_LEAF: 4 B per value read, 32 B per leaf written); the levels above come from the
+// inner-mode build.  steps = 0 is launch_merkle_build; steps <= 3 < log_len.
+hipError_t launch_merkle_build_coset(const uint32_t* vals, uint32_t log_len, uint32_t steps, uint32_t* nodes, hipStream_t s,
+                                     Profiler* prof = nullptr, const MailArgs& mail = MailArgs{}, int hash = 0);
 // level size (log2) at which a build switches from throughput launches to the workgroup-local latency phase;
 // 0 restores the build's default (zk_dev_set_merkle_latency_log); false: out of range (12 .. 24)
 bool set_merkle_latency_log(uint32_t v);

@@ -1,5 +1,5 @@
-// transcript.hpp -- host-only Fiat-Shamir channel, the proof wire format (one description for every folding factor: length, opening
-// order, decommitment tuple) and its verifier.
+// transcript.hpp -- host-only Fiat-Shamir channel, the proof wire format (one description for every folding factor, with one-value
+// or coset leaves: length, opening order, decommitment tuple) and its verifier.
 //
 // Channel mirrors channel.rs:6-37; the byte encoding is bincode 1.x defaults
 // (little-endian fixed-width ints, [u8;32] raw, Box<[T]> = u64 count + items)
@@ -44,14 +44,15 @@ struct Channel {
     // plen digests, committed once.  s = 1 is (u32, AuthPath) of prover.rs:274-277, s = 2 the pair of prover.rs:280-289, s = 4 / 8
     // a group of a folded proof.  buf: group_bytes(s, plen) bytes of the caller's, reused from tuple to tuple; val(t) gives value
     // t, digest(i, out) writes digest i of the s * plen (path t starts at t * plen) as 32 bytes.
-    static size_t group_bytes(size_t s, size_t plen) { return s * (4 + 8 + 32 * plen); }
-    template <class Val, class Dig> void commit_group(uint8_t* buf, size_t s, size_t plen, Val val, Dig digest) {
+    // coset (coset leaves, below): the s values are the slots of ONE leaf, in slot order, and ONE path of plen digests follows them.
+    static size_t group_bytes(size_t s, size_t plen, bool coset = false) { return 4 * s + (coset ? 1 : s) * (8 + 32 * plen); }
+    template <class Val, class Dig> void commit_group(uint8_t* buf, size_t s, size_t plen, Val val, Dig digest, bool coset = false) {
         uint8_t* p = buf;
         for (size_t t = 0; t < s; ++t, p += 4) {
             const uint32_t v = val(t);
             for (int i = 0; i < 4; ++i) p[i] = (uint8_t)(v >> (8 * i));
         }
-        for (size_t t = 0; t < s; ++t) {
+        for (size_t t = 0; t < (coset ? 1 : s); ++t) {
             for (int i = 0; i < 8; ++i) *p++ = (uint8_t)((uint64_t)plen >> (8 * i));
             for (size_t j = 0; j < plen; ++j, p += 32) digest(t * plen + j, p);
         }
@@ -80,6 +81,14 @@ struct Channel {
 // q = number of decommitment queries (1 = the reference's format, prover.rs:263; q > 1: SURVEY.md 8f item 1 -- the q raw indices
 // are drawn in a row, then each query's openings are committed in turn).
 // grind = proof-of-work bits (DESIGN.md "Grinding"): g > 0 puts the 8-byte nonce between the free term and the query raws.
+// coset = coset leaves (off = the format above).  The tree over the input layer of group j (id 1 + r0, len = N >> r0,
+// s = 2^steps_j) has len / s leaves; leaf c holds the slots u = 0 .. s-1, slot u = layer[c + u len / s] (the layer itself stays in
+// natural order): exactly what a query opens there, so a group is ONE leaf and ONE path of L - r0 - steps digests for leaf
+// x % (len / s).  Leaf hash: SHA-256 over the s slots, 4 bytes big-endian each (one block); field hash: the compression of
+// (slot_0 .. slot_{s-1}, 0, ..., 0, s) (fieldhash.hpp).  s = 1 is the one-value leaf.  Inner nodes are unchanged; tree 0 (f) and
+// the tree over the last layer (id 1 + log_n, never opened) keep one-value leaves.  Per query the three f tuples are sent as ever;
+// the separate cp(x) tuple is dropped (group 0's leaf contains it), then per group the s slot values in slot order, a u64 count and
+// the path.  With rot = (x % len) / (len / s), value t of the group (the one at (x % len + t len / s) % len) is slot (rot + t) % s.
 constexpr uint32_t kMaxFoldLog = 3;
 inline uint32_t fold_groups(uint32_t R, uint32_t fold) { return (R + fold - 1) / fold; }
 inline uint32_t fold_steps(uint32_t R, uint32_t fold, uint32_t group) { const uint32_t r0 = group * fold; return R - r0 < fold ? R - r0 : fold; }
@@ -90,21 +99,28 @@ inline size_t coset_leaf(size_t x, uint32_t log_len, uint32_t steps, uint32_t t)
 }
 // The openings of one query in wire order, for x = query raw % (N - 2B): f at x, x + B, x + 2B (layer 0) and cp at x (layer 1),
 // one tuple each (prover.rs:266-277), then per group the s coset leaves of its input layer 1 + r0, one tuple per group.
-// open(layer id, log2 of the layer's length = digests of the path, leaf index).
-template <class Open> inline void for_each_opening(uint32_t log_n, uint32_t log_b, uint32_t fold, size_t x, Open open) {
+// An opening is one LEAF and its path: open(layer id, log2 of the tree's leaf count = digests of the path, leaf index, slots_log);
+// the leaf holds the 2^slots_log values layer[leaf + u 2^(log2 leaf count)], u < 2^slots_log (0: a one-value leaf).
+// coset: no cp opening, and a group is one leaf of s slots.
+template <class Open> inline void for_each_opening(uint32_t log_n, uint32_t log_b, uint32_t fold, size_t x, Open open, bool coset = false) {
     const uint32_t L = log_n + log_b, G = fold_groups(log_n, fold);
     const size_t B = (size_t)1 << log_b;
-    open(0u, L, x); open(0u, L, x + B); open(0u, L, x + 2 * B); open(1u, L, x);
+    open(0u, L, x, 0u); open(0u, L, x + B, 0u); open(0u, L, x + 2 * B, 0u);
+    if (!coset) open(1u, L, x, 0u);
     for (uint32_t j = 0; j < G; ++j) {
         const uint32_t r0 = j * fold, steps = fold_steps(log_n, fold, j);
-        for (uint32_t t = 0; t < (1u << steps); ++t) open(1u + r0, L - r0, coset_leaf(x, L - r0, steps, t));
+        if (coset) open(1u + r0, L - r0 - steps, x % ((size_t)1 << (L - r0 - steps)), steps);
+        else for (uint32_t t = 0; t < (1u << steps); ++t) open(1u + r0, L - r0, coset_leaf(x, L - r0, steps, t), 0u);
     }
 }
 // fold must be in 1..kMaxFoldLog (the callers check it).
-inline size_t proof_data_len(uint32_t log_n, uint32_t log_b, uint32_t q = 1, uint32_t grind = 0, uint32_t fold = 1) {
+inline size_t proof_data_len(uint32_t log_n, uint32_t log_b, uint32_t q = 1, uint32_t grind = 0, uint32_t fold = 1, bool coset = false) {
     const size_t L = log_n + log_b, G = fold_groups(log_n, fold);
-    size_t per_query = 4 + 4 * Channel::group_bytes(1, L);
-    for (uint32_t j = 0; j < G; ++j) per_query += Channel::group_bytes((size_t)1 << fold_steps(log_n, fold, j), L - (size_t)j * fold);
+    size_t per_query = 4 + (coset ? 3 : 4) * Channel::group_bytes(1, L);
+    for (uint32_t j = 0; j < G; ++j) {
+        const size_t steps = fold_steps(log_n, fold, j);
+        per_query += Channel::group_bytes((size_t)1 << steps, L - (size_t)j * fold - (coset ? steps : 0), coset);
+    }
     return 32 + 12 + 32 + G * 36 + 4 + (grind ? 8 : 0) + (size_t)q * per_query;
 }
 
@@ -158,11 +174,19 @@ inline void host_node_hash(const uint8_t* l, const uint8_t* r, uint8_t out[32], 
     Sha256 h; h.update(l, 32); h.update(r, 32); h.finalize(out);
 }
 
-// merkle.rs:82-110
-inline void compute_root_from_path(uint32_t element, size_t index, const uint8_t* path, size_t plen, uint8_t out[32], int hash = 0) {
+// Leaf of s <= 8 slots (coset leaves, above); s = 1 is host_leaf_hash.
+inline void host_coset_leaf_hash(const uint32_t* slots, size_t s, uint8_t out[32], int hash) {
+    if (hash) { digest_words_to_bytes(fieldhash_coset_leaf(slots, (uint32_t)s, host_fieldhash_consts()).w, out); return; }
+    uint8_t be[32];
+    for (size_t u = 0; u < s; ++u) { be[4 * u] = (uint8_t)(slots[u] >> 24); be[4 * u + 1] = (uint8_t)(slots[u] >> 16); be[4 * u + 2] = (uint8_t)(slots[u] >> 8); be[4 * u + 3] = (uint8_t)slots[u]; }
+    Sha256 h; h.update(be, 4 * s); h.finalize(out);
+}
+
+// merkle.rs:82-110, from the s slots of leaf `index` (s = 1: the reference's one element)
+inline void compute_root_from_coset(const uint32_t* slots, size_t s, size_t index, const uint8_t* path, size_t plen, uint8_t out[32], int hash = 0) {
     index += ((size_t)1 << plen) - 1;
     uint8_t cur[32], nxt[32];
-    host_leaf_hash(element, cur, hash);
+    host_coset_leaf_hash(slots, s, cur, hash);
     for (size_t k = 0; k < plen; ++k) {
         if (index % 2 == 0) { host_node_hash(path + 32 * k, cur, nxt, hash); index -= 2; }
         else { host_node_hash(cur, path + 32 * k, nxt, hash); index -= 1; }
@@ -171,6 +195,9 @@ inline void compute_root_from_path(uint32_t element, size_t index, const uint8_t
     }
     memcpy(out, cur, 32);
 }
+inline void compute_root_from_path(uint32_t element, size_t index, const uint8_t* path, size_t plen, uint8_t out[32], int hash = 0) {
+    compute_root_from_coset(&element, 1, index, path, plen, out, hash);
+}
 
 // proof.rs:15-149 with the literals generalised and the rounds taken in groups (the format above).  Returns 0 or the negative
 // index of the failed check: -1 sizes or layout, -2 cp0, -3 the four path lengths, -4..-7 the paths of f(x), f(gx), f(g^2 x), cp(x);
@@ -178,11 +205,14 @@ inline void compute_root_from_path(uint32_t element, size_t index, const uint8_t
 // -(300+j) for t = 0 and -(400+j) for the first failing t >= 1; -8 for bytes left over.  K = 1: j is the reference's round.
 // Values and challenges are reduced % P before arithmetic; what a fold is compared with (the next group's value 0, the free
 // term, fv[3]) is compared unreduced.
+// coset: cp0 is compared with group 0's value 0 (-2), -3 covers the three f path lengths, -7 and -(400+j) do not occur: a group has
+// one path length -(200+j) and one path -(300+j).
 // grind > 0: the nonce after the free term is skipped.  Its work is a property of the Fiat-Shamir transcript, which only
 // verify_transcript replays; here the query raws are read from the proof (as the reference does), so checking it certifies nothing.
 inline int verify_proof(const uint8_t* data, size_t len, uint32_t log_n, uint32_t log_b, uint32_t public_last, int hash = 0, uint32_t q = 1,
-                        uint32_t grind = 0, uint32_t fold = 1) {
+                        uint32_t grind = 0, uint32_t fold = 1, bool coset = false) {
     if (log_n < 2 || log_b < 1 || log_n + log_b > 30 || q < 1 || q > 64 || grind > kMaxGrindBits || fold < 1 || fold > kMaxFoldLog) return -1;
+    const int nf = coset ? 3 : 4;                            // f(x), f(gx), f(g^2 x) and, with one-value leaves, cp(x)
     const size_t n = (size_t)1 << log_n, B = (size_t)1 << log_b, N = n << log_b, L = log_n + log_b;
     const uint32_t G = fold_groups(log_n, fold);
     const uint8_t* p = data;
@@ -219,16 +249,24 @@ inline int verify_proof(const uint8_t* data, size_t len, uint32_t log_n, uint32_
     for (uint32_t qk = 0; qk < q; ++qk) {
         const uint32_t test_raw = test_raws[qk];
         uint32_t fv[4]; const uint8_t* fp[4]; size_t fpl[4] = {0, 0, 0, 0};
-        for (int i = 0; i < 4; ++i) { fv[i] = take32(); fp[i] = take_path(fpl[i]); }
+        for (int i = 0; i < nf; ++i) { fv[i] = take32(); fp[i] = take_path(fpl[i]); }
         uint32_t lv[40][8]; const uint8_t* lp[40][8]; size_t lpl[40][8];
         for (uint32_t j = 0; j < G; ++j) {
             const uint32_t s = 1u << fold_steps(log_n, fold, j);
             for (uint32_t t = 0; t < s; ++t) lv[j][t] = take32();
-            for (uint32_t t = 0; t < s; ++t) { lpl[j][t] = 0; lp[j][t] = take_path(lpl[j][t]); }
+            for (uint32_t t = 0; t < (coset ? 1u : s); ++t) { lpl[j][t] = 0; lp[j][t] = take_path(lpl[j][t]); }
         }
         if (bad) return -1;
         // proof.rs:49-60
         const size_t tp = (size_t)test_raw % (N - 2 * B);
+        // value t of group j: as sent, or slot (rot + t) % s of the group's leaf
+        auto group_val = [&](uint32_t j, uint32_t t) -> uint32_t {
+            if (!coset) return lv[j][t];
+            const uint32_t steps = fold_steps(log_n, fold, j), lg = (uint32_t)L - j * fold;
+            const size_t rot = (tp & (((size_t)1 << lg) - 1)) >> (lg - steps);
+            return lv[j][(rot + t) & ((1u << steps) - 1u)];
+        };
+        if (coset) fv[3] = group_val(0, 0);
         const uint32_t x = mulmod(GEN_W, powmod(h, tp));
         {   // proof.rs:63-77
             uint32_t f_x = fv[0] % P, f_gx = fv[1] % P, f_ggx = fv[2] % P;
@@ -242,18 +280,18 @@ inline int verify_proof(const uint8_t* data, size_t len, uint32_t log_n, uint32_
             if (cp0 != fv[3]) return -2;
         }
         uint8_t root[32];
-        if (fpl[0] != L || fpl[1] != L || fpl[2] != L || fpl[3] != L) return -3;
+        for (int i = 0; i < nf; ++i) if (fpl[i] != L) return -3;
         // proof.rs:80-95
         compute_root_from_path(fv[0], tp, fp[0], fpl[0], root, hash);         if (memcmp(root, f_root, 32)) return -4;
         compute_root_from_path(fv[1], tp + B, fp[1], fpl[1], root, hash);     if (memcmp(root, f_root, 32)) return -5;
         compute_root_from_path(fv[2], tp + 2 * B, fp[2], fpl[2], root, hash); if (memcmp(root, f_root, 32)) return -6;
-        compute_root_from_path(fv[3], tp, fp[3], fpl[3], root, hash);         if (memcmp(root, roots[0], 32)) return -7;
+        if (!coset) { compute_root_from_path(fv[3], tp, fp[3], fpl[3], root, hash); if (memcmp(root, roots[0], 32)) return -7; }
         // proof.rs:101-126: the s opened values of a group folded pairwise (t with t + s/2, then again)
         const uint32_t inv2 = invmod(2);
         for (uint32_t j = 0; j < G; ++j) {
             const uint32_t r0 = j * fold, steps = fold_steps(log_n, fold, j);
             uint32_t cnt = 1u << steps, v[8];
-            for (uint32_t t = 0; t < cnt; ++t) v[t] = lv[j][t] % P;
+            for (uint32_t t = 0; t < cnt; ++t) v[t] = group_val(j, t) % P;
             uint32_t xk = powmod(x, (uint64_t)1 << r0);                        // the point of index tp % len in layer r0
             uint32_t om = powmod(h, (uint64_t)N >> steps);                     // index + len / s: the point times a primitive s-th root of unity
             uint32_t bk = betas[j] % P;
@@ -268,12 +306,18 @@ inline int verify_proof(const uint8_t* data, size_t len, uint32_t log_n, uint32_
                 }
                 xk = mulmod(xk, xk); om = mulmod(om, om); bk = mulmod(bk, bk);
             }
-            const uint32_t expect = (j + 1 < G) ? lv[j + 1][0] : free_term;
+            const uint32_t expect = (j + 1 < G) ? group_val(j + 1, 0) : free_term;
             if (v[0] != expect) return -(int)(100 + j);
         }
         // proof.rs:129-148
         for (uint32_t j = 0; j < G; ++j) {
             const uint32_t r0 = j * fold, steps = fold_steps(log_n, fold, j), s = 1u << steps;
+            if (coset) {
+                if (lpl[j][0] != L - r0 - steps) return -(int)(200 + j);
+                compute_root_from_coset(lv[j], s, tp & (((size_t)1 << (L - r0 - steps)) - 1), lp[j][0], lpl[j][0], root, hash);
+                if (memcmp(root, roots[j], 32)) return -(int)(300 + j);
+                continue;
+            }
             for (uint32_t t = 0; t < s; ++t) if (lpl[j][t] != L - r0) return -(int)(200 + j);
             for (uint32_t t = 0; t < s; ++t) {
                 compute_root_from_path(lv[j][t], coset_leaf(tp, (uint32_t)L - r0, steps, t), lp[j][t], lpl[j][t], root, hash);
@@ -288,16 +332,17 @@ inline int verify_proof(const uint8_t* data, size_t len, uint32_t log_n, uint32_
 // the reference verifier reads the challenges out of the proof
 // (proof.rs:22-37) and never checks Proof.state (proof.rs:6); the author flags this as unfinished
 // (readme.md:1).  This replays the Fiat-Shamir channel over the proof bytes in the prover's commit
-// order (prover.rs:85, :163-165, :180, :200, :224, :254, :263, :274-277, :288: one commit per tuple), checks that every
+// order (prover.rs:85, :163-165, :180, :200, :224, :254, :263, :274-277, :288: one commit per tuple; coset: three f tuples and one
+// tuple per group), checks that every
 // challenge equals the one the transcript yields at that point and that the final state matches.  There are 3 + G + q challenges.
 // Returns 0, or -(1000 + k) for the k-th challenge / -1998 for a grinding nonce whose hash has fewer than `grind` leading zero
 // bits (checked after the betas and before the first query challenge; it does not advance k) / -1999 for the state.
 inline int verify_transcript(const uint8_t* data, size_t len, const uint8_t state[32], uint32_t log_n, uint32_t log_b, uint32_t q = 1,
-                             uint32_t grind = 0, uint32_t fold = 1) {
+                             uint32_t grind = 0, uint32_t fold = 1, bool coset = false) {
     if (log_n < 2 || log_b < 1 || log_n + log_b > 30 || grind > kMaxGrindBits || fold < 1 || fold > kMaxFoldLog) return -1;
     const size_t L = log_n + log_b;
     const uint32_t G = fold_groups(log_n, fold);
-    if (q < 1 || q > 64 || len != proof_data_len(log_n, log_b, q, grind, fold)) return -1;
+    if (q < 1 || q > 64 || len != proof_data_len(log_n, log_b, q, grind, fold, coset)) return -1;
     Channel ch;
     const uint8_t* p = data;
     int k = 0;
@@ -325,8 +370,11 @@ inline int verify_transcript(const uint8_t* data, size_t len, const uint8_t stat
     }
     for (uint32_t j = 0; j < q; ++j) if (!challenge()) return -(1000 + k);   // queries
     for (uint32_t j = 0; j < q; ++j) {
-        for (int i = 0; i < 4; ++i) commit(Channel::group_bytes(1, L));
-        for (uint32_t gi = 0; gi < G; ++gi) commit(Channel::group_bytes((size_t)1 << fold_steps(log_n, fold, gi), L - (size_t)gi * fold));
+        for (int i = 0; i < (coset ? 3 : 4); ++i) commit(Channel::group_bytes(1, L));
+        for (uint32_t gi = 0; gi < G; ++gi) {
+            const size_t steps = fold_steps(log_n, fold, gi);
+            commit(Channel::group_bytes((size_t)1 << steps, L - (size_t)gi * fold - (coset ? steps : 0), coset));
+        }
     }
     if (memcmp(ch.state, state, 32)) return -1999;
     return 0;

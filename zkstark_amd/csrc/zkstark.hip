@@ -116,6 +116,10 @@ struct zk_ctx {
     // the last proof did not materialise layer / tree id (read-outs of it answer ZK_ERR_STATE until a stage call writes it)
     uint32_t fold = 1;
     uint64_t skipped_layers = 0, skipped_trees = 0;
+    // Coset leaves (zk_ctx_set_coset_leaves; transcript.hpp): the tree over a group's input layer has one leaf per opened coset.
+    // tree_steps[t]: tree t as it lies in d_trees has 2^tree_steps[t] values per leaf (0: one-value leaves), set by whatever built it
+    bool coset = false;
+    uint8_t tree_steps[40] = {};
     int hash = 0;                      // Merkle hash: 0 = SHA-256 (reference), 1 = field-native (configs[4])
     // opt-in reference self-checks (zk_ctx_set_checks; prover.rs:64-66, :148-159, :169, :228-251)
     bool checks = false;
@@ -144,6 +148,9 @@ int dmalloc(zk_ctx* c, T** p, size_t bytes) {
 
 size_t layer_size(const zk_ctx* c, uint32_t layer) { return layer == 0 ? c->N : (c->N >> (layer - 1)); }
 uint32_t layer_log(const zk_ctx* c, uint32_t layer) { return layer == 0 ? c->L : c->L - (layer - 1); }
+// log2 of the number of LEAVES of tree `tree` as it was last built (coset leaves hold 2^tree_steps values each)
+uint32_t tree_log(const zk_ctx* c, uint32_t tree) { return layer_log(c, tree) - c->tree_steps[tree]; }
+size_t tree_leaves(const zk_ctx* c, uint32_t tree) { return (size_t)1 << tree_log(c, tree); }
 
 Profiler* prof_of(zk_ctx* c) { return c->prof.mask ? &c->prof : nullptr; }
 
@@ -179,14 +186,16 @@ constexpr uint32_t host_sub_log() { return ZK_HOST_SUB_LOG; }
 // How much of tree `tree` the host finishes: the top `host_top` levels of SHA-256 trees larger than that.
 uint32_t top_of(const zk_ctx* c, uint32_t tree) {
     if (c->hash != 0 || !c->host_top) return 0;
-    const uint32_t lg = layer_log(c, tree);
+    const uint32_t lg = tree_log(c, tree);                            // coset trees are up to 8x smaller: the rule below is about leaves
     return lg > c->host_top ? c->host_top : lg - 1;                 // a smaller tree hands over one level below its leaves
 }
 // What the commit launch of `tree` posts to the host.  host = true (one-call flows): the digests of depth
 // host_top instead of the root, and for the layer with 2^(host_tail+1) values the values too -- the host
 // folds on from there.
-MailArgs mail_of(zk_ctx* c, uint32_t tree, bool host, bool feed_tail = true) {
+// steps: the tree about to be built has 2^steps values per leaf (every builder comes through here).
+MailArgs mail_of(zk_ctx* c, uint32_t tree, bool host, bool feed_tail = true, uint32_t steps = 0) {
     MailArgs m;
+    c->tree_steps[tree] = (uint8_t)steps;
     if (c->counters_dirty) {                              // stream-ordered behind whatever is left of the failed launch
         (void)hipMemsetAsync(c->d_counter, 0, 64, c->stream);
         c->counters_dirty = false;
@@ -196,7 +205,7 @@ MailArgs mail_of(zk_ctx* c, uint32_t tree, bool host, bool feed_tail = true) {
     c->tree_seq[tree] = m.seq;
     m.counter = c->d_counter;
     m.top = host ? top_of(c, tree) : 0;
-    if (feed_tail && c->fold == 1 && m.top && c->host_tail && tree >= 1 && layer_log(c, tree) == c->host_tail + 1) {
+    if (feed_tail && c->fold == 1 && !c->coset && m.top && c->host_tail && tree >= 1 && layer_log(c, tree) == c->host_tail + 1) {
         m.dump_src = c->d_layers + c->layer_off[tree];
         m.dump_log = c->host_tail + 1;
         m.vals_off = (uint32_t)kMailValsOff;
@@ -208,9 +217,10 @@ MailArgs mail_of(zk_ctx* c, uint32_t tree, bool host, bool feed_tail = true) {
 
 // Builds tree `layer`; the launch that reaches the hand-over depth posts its digests to the host mailbox.
 // host = false: the whole tree on the device; feed_tail = false: a stand-alone commitment (stage-by-stage API).
-int do_merkle(zk_ctx* c, uint32_t layer, bool host = false, bool feed_tail = true) {
-    HIPCHK(launch_merkle_build(c->d_layers + c->layer_off[layer], layer_log(c, layer), c->d_trees + c->tree_off[layer], c->stream,
-                               prof_of(c), mail_of(c, layer, host, feed_tail), c->hash));
+// steps > 0: coset leaves of 2^steps values (coset_leaf_hash_kernel, then the inner build).
+int do_merkle(zk_ctx* c, uint32_t layer, bool host = false, bool feed_tail = true, uint32_t steps = 0) {
+    HIPCHK(launch_merkle_build_coset(c->d_layers + c->layer_off[layer], layer_log(c, layer), steps, c->d_trees + c->tree_off[layer], c->stream,
+                                     prof_of(c), mail_of(c, layer, host, feed_tail, steps), c->hash));
     return ZK_OK;
 }
 
@@ -314,6 +324,7 @@ int host_fold_commit(zk_ctx* c, uint32_t round, uint32_t beta_raw, uint8_t root[
     c->tail_vals.assign(vals, vals + half);
     c->tail_log = log_out;
     c->t_host_hash += now_us() - t_begin;
+    c->tree_steps[2 + round] = 0;
     c->host_vals[2 + round] = vals;
     c->host_nodes[2 + round] = nodes;
     c->host_node_cnt[2 + round] = 2 * half - 1;
@@ -334,7 +345,7 @@ int fri_round_commit(zk_ctx* c, uint32_t round, uint32_t beta_raw, uint8_t root[
 bool round_on_host(const zk_ctx* c, uint32_t round) {
     return c->hash == 0 && c->host_top && c->host_tail && c->L >= c->host_tail + 1 && c->L - round <= c->host_tail + 1;
 }
-bool can_gate(const zk_ctx* c, uint32_t round) { return c->fold == 1 && c->early && c->early_ok && !c->checks && round < c->R && !round_on_host(c, round); }
+bool can_gate(const zk_ctx* c, uint32_t round) { return c->fold == 1 && !c->coset && c->early && c->early_ok && !c->checks && round < c->R && !round_on_host(c, round); }
 // The launches of do_fold_commit(round), enqueued behind a wait on the gate word; their one challenge-dependent constant is read
 // from a parameter slot the host fills in release_gated_fold.
 int enqueue_gated_fold(zk_ctx* c, uint32_t round) {
@@ -517,6 +528,8 @@ int open_wait(zk_ctx* c) {
 // FRI rounds of a proof folded by 2^fold between commitments (fold > 1; DESIGN.md "Folding factor"): per group of
 // `steps` rounds one challenge, one pass of the multi-fold kernel (prover.rs:201-211, steps times), one tree (prover.rs:214) over
 // its output, one root (prover.rs:224).  Every layer is folded on the device (no host FRI tail); tree tops go to the host as usual.
+// Coset leaves (any fold, 1 included, comes here): the tree over a group's output is the tree over the NEXT group's input, so its
+// leaves are that group's cosets; the last layer is never opened and keeps one-value leaves.
 int prove_fold_rounds(zk_ctx* c, Channel& ch) {
     const uint32_t R = c->R, K = c->fold;
     uint8_t root[32];
@@ -526,7 +539,8 @@ int prove_fold_rounds(zk_ctx* c, Channel& ch) {
         const uint32_t beta = c->info.beta_raw[r0] = ch.get_u32();            // prover.rs:200, once per group
         if ((rc = dom_fold_multi(c->dom, c->d_layers + c->layer_off[1 + r0], c->d_layers + c->layer_off[id], c->L - r0, r0, steps, beta,
                                  c->stream, prof_of(c)))) return rc;
-        if ((rc = do_merkle(c, id, true, false))) return rc;
+        const uint32_t leaf_steps = c->coset && r0 + steps < R ? (R - r0 - steps < K ? R - r0 - steps : K) : 0;
+        if ((rc = do_merkle(c, id, true, false, leaf_steps))) return rc;
         if ((rc = read_commit(c, id, root))) return rc;
         const size_t deg = c->n >> (r0 + steps);
         if (c->checks && (rc = check_degree(c, id, (uint32_t)deg - (deg ? 1 : 0), "prover.rs:228-251 (FRI layer degree)"))) return rc;
@@ -577,12 +591,14 @@ int prove_finish(zk_ctx* c, Channel& ch, HostLaps& lap) {
     // mailbox flag behind them: no copy commands, no stream synchronisation.  The scatter that completes the device
     // arrays with the host-built parts is enqueued behind it, off the proof's critical path.
     size_t per_query = 0;
-    for_each_opening(c->log_n, c->log_b, K, 0, [&](uint32_t, uint32_t, size_t) { ++per_query; });
+    const bool coset = c->coset;
+    for_each_opening(c->log_n, c->log_b, K, 0, [&](uint32_t, uint32_t, size_t, uint32_t slots_log) { per_query += (size_t)1 << slots_log; }, coset);
     open_begin(c, (size_t)Q * per_query);
     for (uint32_t k = 0; k < Q; ++k)
-        for_each_opening(c->log_n, c->log_b, K, (size_t)qraws[k] % (N - 2 * B), [&](uint32_t layer, uint32_t log_len, size_t leaf) {
-            open_val(c, layer, leaf); open_path(c, layer, (size_t)1 << log_len, leaf);
-        });
+        for_each_opening(c->log_n, c->log_b, K, (size_t)qraws[k] % (N - 2 * B), [&](uint32_t layer, uint32_t log_leaves, size_t leaf, uint32_t slots_log) {
+            for (size_t u = 0; u < ((size_t)1 << slots_log); ++u) open_val(c, layer, leaf + (u << log_leaves));
+            open_path(c, layer, (size_t)1 << log_leaves, leaf);
+        }, coset);
     if ((rc = open_launch(c))) return rc;
     if ((rc = flush_host_parts(c))) return rc;            // completes the device arrays, behind the fetch: off the critical path
     lap("free term + fetch enqueue");
@@ -592,14 +608,17 @@ int prove_finish(zk_ctx* c, Channel& ch, HostLaps& lap) {
     const uint32_t* const* dsrc = c->fetch_nodes.data();
     std::vector<uint8_t>& buf = c->commit_buf;            // reused from proof to proof; the first group's tuple is the largest
     buf.resize(Channel::group_bytes((size_t)1 << fold_steps(R, K, 0), Lp));
-    auto tuple = [&](size_t s, size_t plen) {
+    auto tuple = [&](size_t s, size_t plen, bool one_leaf) {
         ch.commit_group(buf.data(), s, plen, [&](size_t t) { return *vsrc[t]; },
-                        [&](size_t i, uint8_t* out) { digest_words_to_bytes(dsrc[i], out); });
-        vsrc += s; dsrc += s * plen;
+                        [&](size_t i, uint8_t* out) { digest_words_to_bytes(dsrc[i], out); }, one_leaf);
+        vsrc += s; dsrc += (one_leaf ? 1 : s) * plen;
     };
     for (uint32_t q = 0; q < Q; ++q) {
-        for (int k = 0; k < 4; ++k) tuple(1, Lp);                                             // (u32, AuthPath): prover.rs:274-277
-        for (uint32_t j = 0; j < G; ++j) tuple((size_t)1 << fold_steps(R, K, j), Lp - (size_t)j * K);   // prover.rs:280-289, per group
+        for (int k = 0; k < (coset ? 3 : 4); ++k) tuple(1, Lp, false);                        // (u32, AuthPath): prover.rs:274-277
+        for (uint32_t j = 0; j < G; ++j) {                                                    // prover.rs:280-289, per group
+            const size_t steps = fold_steps(R, K, j);
+            tuple((size_t)1 << steps, Lp - (size_t)j * K - (coset ? steps : 0), coset);
+        }
     }
     lap("decommit host hashing");
     return ZK_OK;                                         // the proof is the channel: channel.rs:34-36
@@ -608,13 +627,14 @@ int prove_finish(zk_ctx* c, Channel& ch, HostLaps& lap) {
 // generate_proof(channel) (prover.rs:9): everything is committed to, and every challenge drawn from, the
 // caller's channel `ch`, which may already hold a transcript prefix (main.rs:19 starts from a fresh one).
 // Only the round loops differ with the folding factor: K = 1 has the fused fold, the early launch and the host tail; K > 1 has
-// prove_fold_rounds.
+// prove_fold_rounds.  Coset leaves: cp is composed by its own launch (its tree has group 0's cosets as leaves, which the fused
+// one-value leaf source cannot hash) and every K takes prove_fold_rounds.
 int prove_resident(zk_ctx* c, Channel& ch) {
     if (!c->have_trace) return fail(ZK_ERR_STATE, "zk_prove_resident: no trace uploaded");
     static const bool timing = getenv("ZK_HOST_TIMING") != nullptr;
     HostLaps lap{timing};
     const uint32_t R = c->R;
-    ch.data.reserve(ch.data.size() + proof_data_len(c->log_n, c->log_b, c->queries, c->grind, c->fold));
+    ch.data.reserve(ch.data.size() + proof_data_len(c->log_n, c->log_b, c->queries, c->grind, c->fold, c->coset));
     c->skipped_layers = c->skipped_trees = 0;
     uint8_t root[32];
     int rc;
@@ -631,13 +651,15 @@ int prove_resident(zk_ctx* c, Channel& ch) {
     memcpy(c->info.roots[0], root, 32);
     uint32_t alpha[3];
     for (int i = 0; i < 3; ++i) alpha[i] = c->info.alpha_raw[i] = ch.get_u32();   // prover.rs:163-165
-    if ((rc = do_compose_commit(c, alpha))) return rc;    // prover.rs:166-176 (composition fused into the leaf hashing)
+    if (c->coset) {                                       // prover.rs:166-176, then the tree with group 0's cosets as leaves
+        if ((rc = do_compose(c, alpha)) || (rc = do_merkle(c, 1, true, false, fold_steps(R, c->fold, 0)))) return rc;
+    } else if ((rc = do_compose_commit(c, alpha))) return rc;    // prover.rs:166-176 (composition fused into the leaf hashing)
     if (can_gate(c, 0) && (rc = enqueue_gated_fold(c, 0))) return rc;   // early launch: round 0 queued before cp's digests are waited for
     if ((rc = read_commit(c, 1, root))) return rc;
     if (c->checks && (rc = check_degree(c, 1, (uint32_t)c->n - 1, "prover.rs:148-159/:169 (exact divisions, deg cp = n - 1)"))) return rc;
     ch.commit_hash(root);                                 // prover.rs:180
     memcpy(c->info.roots[1], root, 32);
-    if (c->fold > 1) {
+    if (c->fold > 1 || c->coset) {
         if ((rc = prove_fold_rounds(c, ch))) return rc;
     } else for (uint32_t r = 0; r < R; ++r) {             // prover.rs:198-225
         uint32_t beta = c->info.beta_raw[r] = ch.get_u32();   // prover.rs:200
@@ -937,7 +959,7 @@ int zk_ctx_set_early_launch(zk_ctx* c, int on) {
     c->early = on != 0;
     return ZK_OK;
 }
-int zk_ctx_get_early_launch(const zk_ctx* c) { return c && c->early && c->early_ok && c->fold == 1 ? 1 : 0; }
+int zk_ctx_get_early_launch(const zk_ctx* c) { return c && c->early && c->early_ok && c->fold == 1 && !c->coset ? 1 : 0; }
 // FRI folding factor 2^fold_log between commitments (include/zkstark_amd.h).  A query of a folded proof opens 2^fold_log values and
 // paths per group: the decommitment buffers grow here, not inside the first proof.
 int zk_ctx_set_fold(zk_ctx* c, uint32_t fold_log) {
@@ -976,6 +998,15 @@ int zk_ctx_set_fold(zk_ctx* c, uint32_t fold_log) {
     return ZK_OK;
 }
 uint32_t zk_ctx_get_fold(const zk_ctx* c) { return c ? c->fold : 0; }
+// Coset leaves (include/zkstark_amd.h): from the next proof on.  A coset proof opens fewer nodes than a plain one, so the
+// decommitment buffers of the current folding factor suffice.
+int zk_ctx_set_coset_leaves(zk_ctx* c, int on) {
+    if (!c) return fail(ZK_ERR_INVALID, "null context");
+    if (c->tail) return fail(ZK_ERR_STATE, "zk_ctx_set_coset_leaves: FRI-tail context");
+    c->coset = on != 0;
+    return ZK_OK;
+}
+int zk_ctx_get_coset_leaves(const zk_ctx* c) { return c && c->coset ? 1 : 0; }
 int zk_ctx_set_queries(zk_ctx* c, uint32_t n_queries) {
     if (!c) return fail(ZK_ERR_INVALID, "null context");
     if (n_queries < 1 || n_queries > kMaxQueries) return fail(ZK_ERR_INVALID, "zk_ctx_set_queries: need 1 <= n_queries <= %u", kMaxQueries);
@@ -1087,9 +1118,13 @@ int zk_lde(zk_ctx* c) {
     return rc;
 }
 
-int zk_merkle_commit(zk_ctx* c, uint32_t layer, uint8_t root_out[32]) {
+int zk_merkle_commit(zk_ctx* c, uint32_t layer, uint8_t root_out[32]) { return zk_merkle_commit_coset(c, layer, 0, root_out); }
+// the tree over `layer` with 2^steps values per leaf (leaf c: the values c + u len / 2^steps); steps = 0: one-value leaves
+int zk_merkle_commit_coset(zk_ctx* c, uint32_t layer, uint32_t steps, uint8_t root_out[32]) {
     if (!c || !root_out) return fail(ZK_ERR_INVALID, "zk_merkle_commit: null argument");
     if (layer > c->R + 1) return fail(ZK_ERR_INVALID, "zk_merkle_commit: layer %u out of range", layer);
+    if (steps > kMaxFoldLog || (steps && layer_log(c, layer) <= steps))
+        return fail(ZK_ERR_INVALID, "zk_merkle_commit_coset: need steps <= %u and at least two leaves (layer %u has 2^%u values, steps %u)", kMaxFoldLog, layer, layer_log(c, layer), steps);
     HIPCHK(hipSetDevice(c->device));
     static const bool timing = getenv("ZK_HOST_TIMING") != nullptr;
     const double t0 = now_us();
@@ -1100,7 +1135,7 @@ int zk_merkle_commit(zk_ctx* c, uint32_t layer, uint8_t root_out[32]) {
     int rc = settle_pending(c);
     if (rc) return rc;
     begin_proof(c);                                      // a stand-alone commitment: nothing staged, no host-side FRI tail
-    rc = do_merkle(c, layer, true, false);               // Merkle::new (merkle.rs:14); the last levels on this thread
+    rc = do_merkle(c, layer, true, false, steps);        // Merkle::new (merkle.rs:14); the last levels on this thread
     const double t1 = now_us();
     if (!rc) rc = read_commit(c, layer, root_out);
     const double t2 = now_us();
@@ -1165,7 +1200,7 @@ int zk_layer_write(zk_ctx* c, uint32_t layer, size_t offset, size_t count, const
 
 int zk_merkle_node(zk_ctx* c, uint32_t tree, size_t index, uint8_t out[32]) {
     if (!c || !out) return fail(ZK_ERR_INVALID, "zk_merkle_node: null argument");
-    if (tree > c->R + 1 || index >= 2 * layer_size(c, tree) - 1) return fail(ZK_ERR_INVALID, "zk_merkle_node: out of range");
+    if (tree > c->R + 1 || index >= 2 * tree_leaves(c, tree) - 1) return fail(ZK_ERR_INVALID, "zk_merkle_node: out of range");
     if ((c->skipped_trees >> tree) & 1) return fail(ZK_ERR_STATE, "zk_merkle_node: tree %u was not built by the last proof (fold_log %u)", tree, c->fold);
     HIPCHK(hipSetDevice(c->device));
     if (int prc = settle_pending(c)) return prc;
@@ -1177,7 +1212,7 @@ int zk_merkle_node(zk_ctx* c, uint32_t tree, size_t index, uint8_t out[32]) {
 
 int zk_merkle_nodes(zk_ctx* c, uint32_t tree, size_t first, size_t count, uint8_t* out) {
     if (!c || (!out && count)) return fail(ZK_ERR_INVALID, "zk_merkle_nodes: null argument");
-    if (tree > c->R + 1 || first > 2 * layer_size(c, tree) - 1 || count > 2 * layer_size(c, tree) - 1 - first)
+    if (tree > c->R + 1 || first > 2 * tree_leaves(c, tree) - 1 || count > 2 * tree_leaves(c, tree) - 1 - first)
         return fail(ZK_ERR_INVALID, "zk_merkle_nodes: out of range");
     if ((c->skipped_trees >> tree) & 1) return fail(ZK_ERR_STATE, "zk_merkle_nodes: tree %u was not built by the last proof (fold_log %u)", tree, c->fold);
     HIPCHK(hipSetDevice(c->device));
@@ -1187,12 +1222,12 @@ int zk_merkle_nodes(zk_ctx* c, uint32_t tree, size_t first, size_t count, uint8_
 
 int zk_merkle_path(zk_ctx* c, uint32_t tree, size_t leaf, uint8_t* out, size_t* path_len) {
     if (!c || !out) return fail(ZK_ERR_INVALID, "zk_merkle_path: null argument");
-    if (tree > c->R + 1 || leaf >= layer_size(c, tree)) return fail(ZK_ERR_INVALID, "zk_merkle_path: out of range");
+    if (tree > c->R + 1 || leaf >= tree_leaves(c, tree)) return fail(ZK_ERR_INVALID, "zk_merkle_path: out of range");
     if ((c->skipped_trees >> tree) & 1) return fail(ZK_ERR_STATE, "zk_merkle_path: tree %u was not built by the last proof (fold_log %u)", tree, c->fold);
     HIPCHK(hipSetDevice(c->device));
     if (int prc = settle_pending(c)) return prc;
     std::vector<size_t> nodes;
-    path_nodes(layer_size(c, tree), leaf, nodes);
+    path_nodes(tree_leaves(c, tree), leaf, nodes);
     for (size_t i = 0; i < nodes.size(); ++i) c->h_gather_off[i] = (uint64_t)c->tree_off[tree] + (uint64_t)nodes[i] * 8;
     HIPCHK(hipMemcpyAsync(c->d_gather_off, c->h_gather_off, nodes.size() * 8, hipMemcpyHostToDevice, c->stream));
     HIPCHK(launch_gather(c->d_trees, c->d_gather_off, (uint32_t)nodes.size(), 8, c->d_gather_out, c->stream));
@@ -1269,12 +1304,12 @@ int zk_last_transcript(const zk_ctx* c, zk_transcript_info* out) {
 // apart (replay_note not null), "transcript replay failed at check N" + replay_note.
 static int verify_entry(const char* who, const uint8_t* proof, size_t len, const uint8_t* state, uint32_t log_n, uint32_t log_b,
                         uint32_t public_last, int hash_kind, uint32_t q, uint32_t grind, uint32_t fold, int32_t* check_out,
-                        const char* replay_note, const char* reject_note) {
+                        const char* replay_note, const char* reject_note, bool coset = false) {
     if (hash_kind != ZK_HASH_SHA256 && hash_kind != ZK_HASH_FIELD) return fail(ZK_ERR_INVALID, "%s: unknown hash %d", who, hash_kind);
     if (fold < 1 || fold > kMaxFoldLog) return fail(ZK_ERR_INVALID, "%s: need 1 <= fold_log <= %u (got %u)", who, kMaxFoldLog, fold);
-    int rc = state ? verify_transcript(proof, len, state, log_n, log_b, q, grind, fold) : 0;
+    int rc = state ? verify_transcript(proof, len, state, log_n, log_b, q, grind, fold, coset) : 0;
     const bool in_replay = rc != 0;
-    if (!rc) rc = verify_proof(proof, len, log_n, log_b, public_last, hash_kind, q, grind, fold);
+    if (!rc) rc = verify_proof(proof, len, log_n, log_b, public_last, hash_kind, q, grind, fold, coset);
     if (check_out) *check_out = rc;
     if (!rc) return ZK_OK;
     if (in_replay && replay_note) return fail(ZK_ERR_VERIFY, "transcript replay failed at check %d%s", rc, replay_note);
@@ -1314,11 +1349,21 @@ int zk_verify_fold(const uint8_t* proof, size_t len, const uint8_t* state, uint3
     if (!proof || !check_out) return fail(ZK_ERR_INVALID, "zk_verify_fold: null argument");
     return verify_entry("zk_verify_fold", proof, len, state, log_n, log_b, public_last, hash_kind, n_queries, grind_bits, fold_log, check_out, nullptr, "");
 }
+// zk_verify_fold for proofs made with coset leaves (transcript.hpp)
+int zk_verify_coset(const uint8_t* proof, size_t len, const uint8_t* state, uint32_t log_n, uint32_t log_b, uint32_t public_last,
+                    int hash_kind, uint32_t n_queries, uint32_t grind_bits, uint32_t fold_log, int32_t* check_out) {
+    if (!proof || !check_out) return fail(ZK_ERR_INVALID, "zk_verify_coset: null argument");
+    return verify_entry("zk_verify_coset", proof, len, state, log_n, log_b, public_last, hash_kind, n_queries, grind_bits, fold_log, check_out, nullptr, "", true);
+}
 
 size_t zk_proof_size(size_t data_len) { return 48 + data_len; }   // proof.rs:151-154: size_of::<Proof>() = 32 + 16
 size_t zk_proof_data_len_fold(uint32_t log_n, uint32_t log_b, uint32_t n_queries, uint32_t grind_bits, uint32_t fold_log) {
     if (fold_log < 1 || fold_log > kMaxFoldLog) return 0;
     return proof_data_len(log_n, log_b, n_queries, grind_bits, fold_log);
+}
+size_t zk_proof_data_len_coset(uint32_t log_n, uint32_t log_b, uint32_t n_queries, uint32_t grind_bits, uint32_t fold_log) {
+    if (fold_log < 1 || fold_log > kMaxFoldLog) return 0;
+    return proof_data_len(log_n, log_b, n_queries, grind_bits, fold_log, true);
 }
 size_t zk_proof_data_len_grind(uint32_t log_n, uint32_t log_b, uint32_t n_queries, uint32_t grind_bits) {
     return zk_proof_data_len_fold(log_n, log_b, n_queries, grind_bits, 1);
@@ -1330,6 +1375,13 @@ int zk_compute_root_from_path_ex(uint32_t element, size_t index, const uint8_t* 
     if ((!path && path_len) || !out || path_len > 62 || (hash_kind != 0 && hash_kind != 1))
         return fail(ZK_ERR_INVALID, "zk_compute_root_from_path: bad argument");
     compute_root_from_path(element, index, path, path_len, out, hash_kind);
+    return ZK_OK;
+}
+// the root from the s = 1, 2, 4 or 8 values of coset leaf `leaf` and its path
+int zk_compute_root_from_coset(const uint32_t* values, uint32_t s, size_t leaf, const uint8_t* path, size_t path_len, uint8_t out[32], int hash_kind) {
+    if (!values || (!path && path_len) || !out || path_len > 62 || (hash_kind != 0 && hash_kind != 1) || (s != 1 && s != 2 && s != 4 && s != 8))
+        return fail(ZK_ERR_INVALID, "zk_compute_root_from_coset: bad argument");
+    compute_root_from_coset(values, s, leaf, path, path_len, out, hash_kind);
     return ZK_OK;
 }
 int zk_compute_root_from_path(uint32_t element, size_t index, const uint8_t* path, size_t path_len, uint8_t out[32]) {

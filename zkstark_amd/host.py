@@ -145,19 +145,28 @@ class Proof:
     """proof.rs:5-154.  verify() raises ZkError where the reference panics."""
 
     def __init__(self, state, data, log_n=10, log_blowup=3, public_last=2338775057, hash="sha256", queries=1, grind_bits=0,
-                 fold_log=1):   # proof.rs:11
+                 fold_log=1, coset_leaves=False):   # proof.rs:11
         self.state, self.data = bytes(state), bytes(data)
         self.log_n, self.log_blowup, self.public_last = log_n, log_blowup, public_last
         self.hash, self.queries, self.grind_bits, self.fold_log = hash, queries, grind_bits, fold_log
+        self.coset_leaves = bool(coset_leaves)       # made with zk_ctx_set_coset_leaves: zk_verify_coset, zk_proof_data_len_coset
+
+    def expected_len(self):
+        """The length the format gives a proof of this shape (zk_proof_data_len_fold / zk_proof_data_len_coset)."""
+        fn = _lib.load().zk_proof_data_len_coset if self.coset_leaves else _lib.load().zk_proof_data_len_fold
+        return fn(self.log_n, self.log_blowup, self.queries, self.grind_bits, self.fold_log)
+
+    def _verify_general(self, strict, out):
+        fn = _lib.load().zk_verify_coset if self.coset_leaves else _lib.load().zk_verify_fold
+        return fn(self.data, len(self.data), self.state if strict else None, self.log_n, self.log_blowup,
+                  self.public_last, HASHES[self.hash], self.queries, self.grind_bits, self.fold_log, C.byref(out))
 
     def verify(self, strict=False):                  # proof.rs:15
         """strict=True also replays the channel: challenges must come from the transcript and `state`
         must be its final state (the reference trusts the proof for both, proof.rs:22-37); with grind_bits > 0 it also
         checks the proof-of-work nonce."""
-        if self.fold_log != 1:                       # folded by 2^fold_log between commitments (zk_ctx_set_fold)
-            out = C.c_int32()
-            check(_lib.load().zk_verify_fold(self.data, len(self.data), self.state if strict else None, self.log_n, self.log_blowup,
-                                             self.public_last, HASHES[self.hash], self.queries, self.grind_bits, self.fold_log, C.byref(out)))
+        if self.fold_log != 1 or self.coset_leaves:  # folded by 2^fold_log between commitments (zk_ctx_set_fold), or coset leaves
+            check(self._verify_general(strict, C.c_int32()))
             return
         if self.grind_bits:
             out = C.c_int32()
@@ -171,9 +180,8 @@ class Proof:
         """The number of the check the CPU verifier stops at (zk_verify_grind): 0 = accepted; otherwise what verify()'s
         error names.  Never raises for a rejected proof."""
         out = C.c_int32()
-        if self.fold_log != 1:
-            rc = _lib.load().zk_verify_fold(self.data, len(self.data), self.state if strict else None, self.log_n, self.log_blowup,
-                                            self.public_last, HASHES[self.hash], self.queries, self.grind_bits, self.fold_log, C.byref(out))
+        if self.fold_log != 1 or self.coset_leaves:
+            rc = self._verify_general(strict, out)
         else:
             rc = _lib.load().zk_verify_grind(self.data, len(self.data), self.state if strict else None, self.log_n, self.log_blowup,
                                              self.public_last, HASHES[self.hash], self.queries, self.grind_bits, C.byref(out))
@@ -190,6 +198,15 @@ def compute_root_from_path(element, index, path, hash="sha256"):
     flat = b"".join(bytes(h) for h in path)
     out = C.create_string_buffer(32)
     check(_lib.load().zk_compute_root_from_path_ex(element, index, flat, len(path), out, HASHES[hash]))
+    return out.raw
+
+
+def compute_root_from_coset(values, leaf, path, hash="sha256"):
+    """zk_compute_root_from_coset: the root from the 1, 2, 4 or 8 slot values of coset leaf `leaf` and its path."""
+    v = _u32arr(values)
+    flat = b"".join(bytes(h) for h in path)
+    out = C.create_string_buffer(32)
+    check(_lib.load().zk_compute_root_from_coset(_ptr(v), len(v), leaf, flat, len(path), out, HASHES[hash]))
     return out.raw
 
 
@@ -253,11 +270,13 @@ def _read_nodes(fn, handle, tree, heap, first, count):
 class Context:
     """Device-resident prover state for one (log_n, log_blowup): zk_ctx."""
 
-    def __init__(self, log_n=10, log_blowup=3, device=0, hash="sha256", queries=1, host_levels=None, grind_bits=0, fold_log=1):
+    def __init__(self, log_n=10, log_blowup=3, device=0, hash="sha256", queries=1, host_levels=None, grind_bits=0, fold_log=1,
+                 coset_leaves=False):
         """host_levels: (top_log, tail_log) of zk_ctx_set_host_levels; None = the library default.  grind_bits: proof-of-work
         bits before the query draw (zk_ctx_set_grinding; 0 = none).  fold_log: FRI folding factor 2^fold_log between commitments
-        (zk_ctx_set_fold; 1 = the reference)."""
+        (zk_ctx_set_fold; 1 = the reference).  coset_leaves: one coset per Merkle leaf of the FRI trees (zk_ctx_set_coset_leaves)."""
         self.fold_log = fold_log
+        self.coset_leaves = False
         self.log_n, self.log_blowup, self.device, self.hash, self.queries = log_n, log_blowup, device, hash, queries
         self.grind_bits = grind_bits
         self.n, self.B = 1 << log_n, 1 << log_blowup
@@ -274,6 +293,17 @@ class Context:
             check(_lib.load().zk_ctx_set_grinding(self._h, grind_bits))
         if fold_log != 1:
             check(_lib.load().zk_ctx_set_fold(self._h, fold_log))
+        if coset_leaves:
+            self.set_coset_leaves(True)
+
+    def set_coset_leaves(self, on=True):
+        """zk_ctx_set_coset_leaves: from the next proof on, a group opens one leaf of 2^steps values and one path."""
+        check(_lib.load().zk_ctx_set_coset_leaves(self._h, int(bool(on))))
+        self.coset_leaves = bool(on)
+
+    def _proof_cap(self):
+        fn = _lib.load().zk_proof_data_len_coset if self.coset_leaves else _lib.load().zk_proof_data_len_fold
+        return fn(self.log_n, self.log_blowup, self.queries, self.grind_bits, self.fold_log)
 
     def set_fold(self, fold_log):
         """zk_ctx_set_fold: fold by 2^fold_log (1..3) between commitments from the next proof on."""
@@ -327,8 +357,12 @@ class Context:
 
     def lde(self): check(_lib.load().zk_lde(self._h))
 
-    def merkle_commit(self, layer):
+    def merkle_commit(self, layer, coset_steps=0):
+        """coset_steps > 0: leaves of 2^coset_steps values (zk_merkle_commit_coset); the tree then has layer_size >> coset_steps leaves."""
         out = C.create_string_buffer(32)
+        if coset_steps:
+            check(_lib.load().zk_merkle_commit_coset(self._h, layer, coset_steps, out))
+            return out.raw
         check(_lib.load().zk_merkle_commit(self._h, layer, out))
         return out.raw
 
@@ -358,9 +392,10 @@ class Context:
         check(_lib.load().zk_merkle_node(self._h, tree, index, out))
         return out.raw
 
-    def merkle_nodes(self, tree, first=0, count=None):
-        """Nodes [first, first + count) of tree `tree` (default: the whole heap) as a [count, 32] uint8 array, in one copy."""
-        return _read_nodes(_lib.load().zk_merkle_nodes, self._h, tree, 2 * self.layer_size(tree) - 1, first, count)
+    def merkle_nodes(self, tree, first=0, count=None, coset_steps=0):
+        """Nodes [first, first + count) of tree `tree` (default: the whole heap) as a [count, 32] uint8 array, in one copy.
+        coset_steps: what the tree was built with (its heap has 2 (layer_size >> coset_steps) - 1 nodes)."""
+        return _read_nodes(_lib.load().zk_merkle_nodes, self._h, tree, 2 * (self.layer_size(tree) >> coset_steps) - 1, first, count)
 
     def merkle_path(self, tree, leaf):
         buf = C.create_string_buffer(32 * 64)
@@ -370,7 +405,7 @@ class Context:
 
     def prove(self, trace=None):
         """generate_proof as one C call (C++ host prover). trace=None: already uploaded."""
-        cap = _lib.load().zk_proof_data_len_fold(self.log_n, self.log_blowup, self.queries, self.grind_bits, self.fold_log)
+        cap = self._proof_cap()
         buf = C.create_string_buffer(cap)
         st = C.create_string_buffer(32)
         n = C.c_size_t()
@@ -381,14 +416,14 @@ class Context:
             check(_lib.load().zk_prove(self._h, _ptr(t), len(t), buf, cap, C.byref(n), st))
         info = self.last_transcript()
         return Proof(st.raw, buf.raw[:n.value], self.log_n, self.log_blowup, info.public_last, self.hash, self.queries, self.grind_bits,
-                     self.fold_log)
+                     self.fold_log, self.coset_leaves)
 
     def prove_channel(self, channel):
         """generate_proof(channel) (prover.rs:9) in one C call on the caller's Channel (zk_prove_channel): the
         resident trace is proved on top of whatever the channel already holds; returns channel.finalize(...)."""
         check(_lib.load().zk_prove_channel(self._h, channel._h))
         proof = channel.finalize(self.log_n, self.log_blowup, self.last_transcript().public_last)
-        proof.grind_bits, proof.fold_log = self.grind_bits, self.fold_log
+        proof.grind_bits, proof.fold_log, proof.coset_leaves = self.grind_bits, self.fold_log, self.coset_leaves
         return proof
 
     def set_host_levels(self, top_log, tail_log):
@@ -429,7 +464,7 @@ def prove_many(ctxs):
     library (zk_prove_many): returns the proofs in order."""
     ctxs = list(ctxs)
     c0 = ctxs[0]
-    stride = max(_lib.load().zk_proof_data_len_fold(c.log_n, c.log_blowup, c.queries, c.grind_bits, c.fold_log) for c in ctxs)
+    stride = max(c._proof_cap() for c in ctxs)
     handles = (C.c_void_p * len(ctxs))(*[c._h for c in ctxs])
     data = np.zeros((len(ctxs), stride), dtype=np.uint8)
     lens = (C.c_size_t * len(ctxs))()
@@ -438,7 +473,7 @@ def prove_many(ctxs):
     out = []
     for i, c in enumerate(ctxs):
         out.append(Proof(states[i].tobytes(), data[i, :lens[i]].tobytes(), c.log_n, c.log_blowup, c.last_transcript().public_last,
-                         c.hash, c.queries, c.grind_bits, c.fold_log))
+                         c.hash, c.queries, c.grind_bits, c.fold_log, c.coset_leaves))
     return out
 
 
@@ -697,15 +732,51 @@ class ShardContext:
         return st.fields()
 
 
+def _generate_proof_coset(channel, ctx, a0, a1):
+    """generate_proof with coset leaves (zk_ctx_set_coset_leaves), stage by stage: the tree over a group's input layer has that
+    group's cosets as leaves; per query three f tuples, then per group the slots of one leaf and one path."""
+    n, B, N, R, K = ctx.n, ctx.B, ctx.N, ctx.rounds, ctx.fold_log
+    groups = [(r0, min(K, R - r0)) for r0 in range(0, R, K)]
+    a = trace_fibsq(n - 1, a0, a1)
+    ctx.trace_upload(a)
+    ctx.lde()
+    channel.commit(ctx.merkle_commit(0))
+    ctx.compose([channel.get_u32() for _ in range(3)])
+    channel.commit(ctx.merkle_commit(1, groups[0][1]))
+    for j, (r0, steps) in enumerate(groups):
+        ctx.fri_fold_multi(r0, steps, channel.get_u32())
+        channel.commit(ctx.merkle_commit(1 + r0 + steps, groups[j + 1][1] if j + 1 < len(groups) else 0))
+    last = ctx.layer_read(1 + R)
+    if not (last == last[0]).all():
+        raise ZkError(-7, "last FRI layer is not constant")
+    channel.commit(int(last[0]))
+    if ctx.grind_bits:
+        raise ZkError(-1, "generate_proof: grinding is part of Context.prove(), not of the stage-by-stage flow")
+    xs = [channel.get_u32() % (N - 2 * B) for _ in range(ctx.queries)]
+    for x in xs:
+        for idx in (x, x + B, x + 2 * B):
+            channel.commit((int(ctx.layer_read(0, idx, 1)[0]), ctx.merkle_path(0, idx)))
+        for r0, steps in groups:
+            leaves = (N >> r0) >> steps
+            c = x % leaves
+            channel.commit(tuple(int(ctx.layer_read(1 + r0, c + u * leaves, 1)[0]) for u in range(1 << steps)) + (ctx.merkle_path(1 + r0, c),))
+    proof = channel.finalize(ctx.log_n, ctx.log_blowup, int(a[n - 2]))
+    proof.hash, proof.queries, proof.fold_log, proof.coset_leaves = ctx.hash, ctx.queries, K, True
+    return proof
+
+
 def generate_proof(channel, log_n=10, log_blowup=3, a0=1, a1=3141592, ctx=None):
     """prover.rs:9-293, stage by stage over the C ABI, driven by `channel`.
 
     The reference literals are the defaults (trace 1023 values, domain 8192).
-    Context.prove() is the same flow inside one C call.
+    Context.prove() is the same flow inside one C call.  A context with coset leaves on (Context(coset_leaves=True)) gives the
+    coset-leaf proof of its folding factor, through the same stage calls.
     """
     own = ctx is None
     ctx = ctx or Context(log_n, log_blowup)
     try:
+        if ctx.coset_leaves:
+            return _generate_proof_coset(channel, ctx, a0, a1)
         n, B, N, R = ctx.n, ctx.B, ctx.N, ctx.rounds
         a = trace_fibsq(n - 1, a0, a1)                       # prover.rs:32-39
         ctx.trace_upload(a)
