@@ -198,8 +198,8 @@ uint32_t zk_ctx_get_fold(const zk_ctx *ctx);
  * 2^top_log LEAVES hands over one level below its leaves) and results are identical for every setting.  zk_merkle_node(s) /
  * zk_merkle_path address a coset tree by its own leaves: 2 len / s - 1 nodes, leaf index < len / s, L - r0 - steps digests.
  * Measured: see DESIGN.md 7d.
- * NOT covered: zk_batch_*, zk_verifier_* and zk_shard_* / zk_tail_* keep one-value leaves; a zk_verifier_run on coset proofs rejects
- * them by length (-1). */
+ * zk_verifier_* checks such proofs in batches with zk_verifier_set_coset_leaves.
+ * NOT covered: zk_batch_* and zk_shard_* / zk_tail_* keep one-value leaves. */
 int zk_ctx_set_coset_leaves(zk_ctx *ctx, int on);
 int zk_ctx_get_coset_leaves(const zk_ctx *ctx);
 /* The HIP stream every stage is enqueued on (hipStream_t). */
@@ -443,10 +443,20 @@ int zk_verifier_set_grinding(zk_verifier *v, uint32_t grind_bits);
  * Measured (profiles/verify_fold_bench.txt). */
 int zk_verifier_set_fold(zk_verifier *v, uint32_t fold_log);
 uint32_t zk_verifier_get_fold(const zk_verifier *v);
+/* Proofs made with zk_ctx_set_coset_leaves: off by default, any non-zero `on` means on, from the next zk_verifier_run on; it
+ * combines with every hash, query count, grinding and fold_log 1..3 (fold_log 1 with coset leaves is a format of its own: every
+ * group has two slots and one path).  A run then takes zk_proof_data_len_coset(log_n, log_blowup, q, grind_bits, fold_log) bytes
+ * per proof and checks_out[i] is what zk_verify_coset gives proof i, for EVERY input; a proof with one-value leaves is rejected
+ * with the number zk_verify_coset gives those bytes, and a coset proof by a verifier with the option off likewise with
+ * zk_verify_fold's.  A null verifier: ZK_ERR_INVALID.  zk_verifier_get_coset_leaves: 1 or 0, 0 for a null verifier.
+ * Not timed yet. */
+int zk_verifier_set_coset_leaves(zk_verifier *v, int on);
+int zk_verifier_get_coset_leaves(const zk_verifier *v);
 /* count proofs at proofs + i*stride, each exactly zk_proof_data_len_fold(log_n, log_blowup, q, grind_bits, fold_log) bytes (with
- * the defaults zk_proof_data_len_queries(log_n, log_blowup, q); stride >= that, any alignment); states: count*32 bytes, or NULL =
- * not strict; public_last[count].  checks_out[i] = what zk_verify_fold (fold_log 1: zk_verify_grind, zk_verify_check) returns
- * in check_out for proof i, for EVERY input.  Returns ZK_OK if all were accepted, ZK_ERR_VERIFY if any was rejected
+ * the defaults zk_proof_data_len_queries(log_n, log_blowup, q); with coset leaves zk_proof_data_len_coset of the same arguments;
+ * stride >= that, any alignment); states: count*32 bytes, or NULL = not strict; public_last[count].  checks_out[i] = what
+ * zk_verify_fold (fold_log 1: zk_verify_grind, zk_verify_check; coset leaves: zk_verify_coset) returns in check_out for proof i,
+ * for EVERY input.  Returns ZK_OK if all were accepted, ZK_ERR_VERIFY if any was rejected
  * (zk_last_error names the first rejected index and its check), other errors as usual.  count = 0 is a no-op. */
 int zk_verifier_run(zk_verifier *v, const uint8_t *proofs, size_t stride, size_t count, const uint8_t *states,
                     const uint32_t *public_last, int32_t *checks_out);

@@ -21,6 +21,14 @@
 // the inverse from round to round; the inverse powers of the 8th root of unity that tell the s points of a group apart come
 // with the launch arguments (residues are canonical, so an algebraically equal evaluation is bit-exact).  K = 1 runs the
 // kernels it always ran: the paths and transcript kernels are templates whose unfolded instance is the code as it was.
+//
+// Coset leaves (zk_verifier_set_coset_leaves; verify_transcript, then verify_proof, with coset = true; any K in 1..3, K = 1 being
+// G = R groups of s = 2): a query is three f tuples, then per group its s_j slot words in slot order, ONE u64 count and ONE path of
+// L - jK - steps_j digests, so the layout is fixed once the 3 + G counts have their values.  Value t of group j is slot
+// (rot + t) & (s - 1) with rot = (tp % len) >> (log len - steps): the kernels read it at that address.  The order keys are
+// query * (4 + 2G) + position: 0 (-2), 1..3 (-4..-6), 4 + j (the fold comparison of group j), 4 + G + j (the path of group j,
+// -(300 + j)); -3, -7, -(200 + j), -(400 + j) and -8 cannot occur on the fixed layout.  The coset kernels are instances of their
+// own (verify_coset_*_kernel, and the COSET instance of the transcript kernel); the other instances are the code they were.
 #include <cstdio>
 #include <cstring>
 #include <mutex>
@@ -96,11 +104,22 @@ __device__ __forceinline__ uint32_t group_word(const VerifyArgs& a, uint32_t qk,
     return a.qbase + qk * a.per_q + 4u * (3u + 8u * a.L) + ((3u * j + 8u * (a.L * j - a.K * (j * (j - 1u) / 2u))) << a.K);
 }
 __device__ __forceinline__ uint32_t group_size(const VerifyArgs& a, uint32_t j) { return 1u << (j + 1u < a.G ? a.K : a.ls); }
+// Coset leaves: the first word of group j's opening (s slots, a u64 count, L - jK - steps digests) after the three f tuples.  Every
+// group before j is full: 2^K + 2 + 8 (L - iK - K) words for i < j.
+__device__ __forceinline__ uint32_t coset_group_word(const VerifyArgs& a, uint32_t qk, uint32_t j) {
+    return a.qbase + qk * a.per_q + 3u * (3u + 8u * a.L) + j * ((1u << a.K) + 2u) + 8u * (j * (a.L - a.K) - a.K * (j * (j - 1u) / 2u));
+}
+// ... and the slot that holds value 0 of group j (the one at tp % len): rot = (tp % len) >> (log len - steps)
+__device__ __forceinline__ uint32_t coset_rot(const VerifyArgs& a, uint32_t tp, uint32_t j) {
+    const uint32_t lg = a.L - j * a.K, steps = j + 1u < a.G ? a.K : a.ls;
+    return (tp & ((1u << lg) - 1u)) >> (lg - steps);
+}
 
-// proof.rs:63-77: the composition polynomial at x from f(x), f(gx), f(g^2 x), against the raw cp(x) of the proof
-__device__ __forceinline__ bool cp0_matches(const VerifyArgs& a, const uint32_t* pr, uint32_t p, uint32_t fq, uint32_t x) {
+// proof.rs:63-77: the composition polynomial at x from f(x), f(gx), f(g^2 x), against the raw cp(x) of the proof: the value of
+// the fourth tuple, or, with coset leaves, slot rot0 of group 0's leaf, which starts where that tuple would
+__device__ __forceinline__ bool cp0_matches(const VerifyArgs& a, const uint32_t* pr, uint32_t p, uint32_t fq, uint32_t x, uint32_t rot0 = 0u) {
     const uint32_t fb = 3u + 8u * a.L;
-    const uint32_t f_x = pr[fq] % P, f_gx = pr[fq + fb] % P, f_ggx = pr[fq + 2u * fb] % P, cp_raw = pr[fq + 3u * fb];
+    const uint32_t f_x = pr[fq] % P, f_gx = pr[fq + fb] % P, f_ggx = pr[fq + 2u * fb] % P, cp_raw = pr[fq + 3u * fb + rot0];
     const uint32_t p0 = dmul(sub(f_x, 1u), dinv(sub(x, 1u)));
     const uint32_t p1 = dmul(sub(f_x, a.pub[p] % P), dinv(sub(x, a.gm2)));
     const uint32_t num = sub(sub(f_ggx, dmul(f_gx, f_gx)), dmul(f_x, f_x));
@@ -154,12 +173,13 @@ __global__ void __launch_bounds__(kVerifyThreads) verify_algebra_kernel(VerifyAr
 // STEPS successive reference folds (proof.rs:110-113) of the 2^STEPS values of one group, in registers: round k pairs t with
 // t + cnt and divides by twice the point of t, x^(2^(r0 + k)) om^(2^k t) for the 2^STEPS-th root of unity om.  ixk comes in as
 // x^-(2^r0) and leaves squared STEPS times; om^-(2^k t) is w^e with e = (8 >> STEPS) (t << k) in 0..3, a constant once unrolled.
+// rot (coset leaves): value t is read from slot (rot + t) & (S - 1) of the leaf at vals; the register index stays static.
 template <int STEPS>
-__device__ __forceinline__ uint32_t fold_group(const VerifyArgs& a, const uint32_t* vals, uint32_t beta, uint32_t& ixk) {
+__device__ __forceinline__ uint32_t fold_group(const VerifyArgs& a, const uint32_t* vals, uint32_t beta, uint32_t& ixk, uint32_t rot = 0u) {
     constexpr int S = 1 << STEPS;
     uint32_t v[S];
 #pragma unroll
-    for (int t = 0; t < S; ++t) v[t] = vals[t] % P;
+    for (int t = 0; t < S; ++t) v[t] = vals[(rot + (uint32_t)t) & (uint32_t)(S - 1)] % P;
     uint32_t bk = beta;
 #pragma unroll
     for (int k = 0; k < STEPS; ++k) {
@@ -216,6 +236,47 @@ __global__ void __launch_bounds__(kVerifyThreads) verify_fold_algebra_kernel(Ver
         else calc = fold_group<1>(a, vals, beta, ixk);
         const uint32_t expect = j + 1u < a.G ? pr[group_word(a, qk, j + 1u)] : pr[19u + 9u * a.G];
         if (calc != expect) key = (int32_t)(qk * keys + 5u + j);
+    }
+    if (key != kNoFailure) atomicMin(&a.best[p], key);
+}
+
+// (1) with coset leaves: one lane per (proof, query).  The 3 + G path counts, the cp0 relation (-2) against value 0 of group 0 and
+// the G fold comparisons (-(100 + j)) against value 0 of the next group, both raw; the values come from the rotated slots.
+template <int K>
+__global__ void __launch_bounds__(kVerifyThreads) verify_coset_algebra_kernel(VerifyArgs a) {
+    const uint64_t lane = (uint64_t)blockIdx.x * kVerifyThreads + threadIdx.x;
+    if (lane >= (uint64_t)a.count * a.q) return;
+    const uint32_t p = (uint32_t)(lane / a.q), qk = (uint32_t)(lane % a.q);
+    const uint32_t* pr = a.proofs + (size_t)p * a.words;
+    const uint32_t keys = 4u + 2u * a.G;
+    const uint32_t fq = a.qbase + qk * a.per_q;
+    bool ok = true;
+    for (uint32_t j = 0; j < 3; ++j) {
+        const uint32_t* c = pr + fq + j * (3u + 8u * a.L) + 1u;
+        ok = ok && c[0] == a.L && c[1] == 0u;
+    }
+    for (uint32_t j = 0; j < a.G; ++j) {
+        const uint32_t steps = j + 1u < a.G ? (uint32_t)K : a.ls;
+        const uint32_t* c = pr + coset_group_word(a, qk, j) + (1u << steps);
+        ok = ok && c[0] == a.L - j * (uint32_t)K - steps && c[1] == 0u;
+    }
+    if (!ok) { a.malformed[p] = 1u; return; }
+
+    const uint32_t tp = query_tp(a, pr, qk);
+    const uint32_t x = dmul(GEN_W, dpow(a.h, tp));
+    int32_t key = kNoFailure;
+    if (!cp0_matches(a, pr, p, fq, x, coset_rot(a, tp, 0u))) key = (int32_t)(qk * keys);
+    uint32_t ixk = dinv(x);                               // x = 5 h^tp is never zero: the one inversion of this lane's folds
+#pragma unroll 1
+    for (uint32_t j = 0; j < a.G && key == kNoFailure; ++j) {
+        const uint32_t* vals = pr + coset_group_word(a, qk, j);
+        const uint32_t beta = pr[19u + 9u * j] % P, rot = coset_rot(a, tp, j);
+        uint32_t calc;
+        if (j + 1u < a.G || a.ls == (uint32_t)K) calc = fold_group<K>(a, vals, beta, ixk, rot);
+        else if (K == 3 && a.ls == 2u) calc = fold_group<2>(a, vals, beta, ixk, rot);
+        else calc = fold_group<1>(a, vals, beta, ixk, rot);
+        const uint32_t expect = j + 1u < a.G ? pr[coset_group_word(a, qk, j + 1u) + coset_rot(a, tp, j + 1u)] : pr[19u + 9u * a.G];
+        if (calc != expect) key = (int32_t)(qk * keys + 4u + j);
     }
     if (key != kNoFailure) atomicMin(&a.best[p], key);
 }
@@ -289,6 +350,93 @@ __global__ void __launch_bounds__(kVerifyThreads) verify_paths_kernel(VerifyArgs
     if (!same) atomicMin(&a.best[p], (int32_t)(qk * (FOLD ? 5u + 9u * a.G : 5u + 3u * a.R) + pos));
 }
 
+// The digest of a leaf of s = 1, 2, 4 or 8 slot words, bit for bit host_coset_leaf_hash (transcript.hpp) and coset_leaf_digest
+// (kernels.hip), raw words >= P included: SHA-256 is one block over the s big-endian words with the padding in place, the field
+// hash the compression of (slot_0 .. slot_{s-1}, 0, ..., 0, s).  s = 1 is vleaf.  s is the same for every lane of a launch row
+// (a uniform branch skips the loads past s); the words are placed with selects on static register indices.
+template <int HASH>
+__device__ __forceinline__ Digest coset_vleaf(const uint32_t* slots, uint32_t s) {
+    uint32_t v[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) v[i] = 0u;
+    v[0] = slots[0];
+    if (s >= 2u) v[1] = slots[1];
+    if (s >= 4u) { v[2] = slots[2]; v[3] = slots[3]; }
+    if (s >= 8u) {
+#pragma unroll
+        for (int i = 4; i < 8; ++i) v[i] = slots[i];
+    }
+    Digest d;
+    if constexpr (HASH == 0) {
+        uint32_t w[16];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) w[i] = i < 8 ? ((uint32_t)i == s ? 0x80000000u : v[i]) : 0u;   // v[i] is 0 for i > s
+        w[8] = s == 8u ? 0x80000000u : 0u;
+        w[15] = 32u * s;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) d.w[i] = SHA_IV[i];
+        sha256_compress(d.w, w);
+    } else {
+        uint32_t in[kFhT];
+#pragma unroll
+        for (int i = 0; i < kFhT; ++i) in[i] = i < 8 ? v[i] : 0u;
+        in[kFhT - 1] = s;
+        fh64_compress(in, d.w, g_vfh_consts64);
+    }
+    return d;
+}
+
+// (2) with coset leaves: one lane per (proof, query, path slot).  blockIdx.y = query * (3 + G) + slot and the proof on the lane, so
+// every lane of a wave walks a path of the same length from a leaf of the same width.  Slots 0..2: f(x), f(gx), f(g^2 x), one-value
+// leaves against the f root; slot 3 + j: the leaf of group j from its s_j slot words in slot order (not rotated), leaf index
+// tp % (len / s), L - jK - steps digests, against the root of that group's input layer.
+template <int HASH>
+__global__ void __launch_bounds__(kVerifyThreads) verify_coset_paths_kernel(VerifyArgs a) {
+    const uint32_t p = blockIdx.x * kVerifyThreads + threadIdx.x;
+    if (p >= a.count) return;
+    const uint32_t slots = 3u + a.G;
+    const uint32_t qk = blockIdx.y / slots, slot = blockIdx.y % slots;
+    const uint32_t* pr = a.proofs + (size_t)p * a.words;
+    const uint32_t tp = query_tp(a, pr, qk);
+    uint32_t val_w, path_w, plen, idx, rootw, pos, s;
+    if (slot < 3u) {
+        val_w = a.qbase + qk * a.per_q + slot * (3u + 8u * a.L);
+        path_w = val_w + 3u;
+        plen = a.L;
+        idx = tp + slot * a.B;
+        rootw = 0u;
+        pos = 1u + slot;
+        s = 1u;
+    } else {
+        const uint32_t j = slot - 3u, steps = j + 1u < a.G ? a.K : a.ls;
+        s = 1u << steps;
+        val_w = coset_group_word(a, qk, j);
+        path_w = val_w + s + 2u;
+        plen = a.L - j * a.K - steps;                     // >= log_b >= 1
+        idx = tp & ((1u << plen) - 1u);
+        rootw = root_word(a, j);
+        pos = 4u + a.G + j;
+    }
+    Digest cur = coset_vleaf<HASH>(pr + val_w, s);
+    uint32_t node = idx + (1u << plen) - 1u;              // heap index, < 2^31
+    for (uint32_t lvl = 0; lvl < plen; ++lvl) {
+        Digest sib;
+        const uint32_t* sp = pr + path_w + 8u * lvl;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) sib.w[i] = be_word(sp + i);
+        const bool right = (node & 1u) == 0u;             // an even heap index is a right child
+        Digest l, r;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) { l.w[i] = right ? sib.w[i] : cur.w[i]; r.w[i] = right ? cur.w[i] : sib.w[i]; }
+        cur = vinner<HASH>(l, r);
+        node = (node - (right ? 2u : 1u)) >> 1;
+    }
+    bool same = true;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) same = same && cur.w[i] == be_word(pr + rootw + i);
+    if (!same) atomicMin(&a.best[p], (int32_t)(qk * (4u + 2u * a.G) + pos));
+}
+
 // SHA-256(state || data[0 .. nw)) into state (channel.rs:19-26), streamed over sha256_compress.  nw is the same for every lane,
 // so the lanes of a wave stay in lockstep; data words are read little-endian and swapped to message order.
 __device__ __forceinline__ void commit_words(uint32_t (&st)[8], const uint32_t* data, uint32_t nw) {
@@ -318,9 +466,12 @@ __device__ __forceinline__ void commit_words(uint32_t (&st)[8], const uint32_t* 
 // (3) transcript (strict only): one lane per proof, the commits of verify_transcript in its order.  The order is a schedule of
 // steps the same for every lane (a challenge, or a commit of nw words), walked by one loop with one commit site: the
 // compression is inlined once and the state stays in registers.  FOLD (verify_transcript with fold > 1): G (beta, root) pairs, and per
-// query one commit per group of its s_j values and paths.
-template <bool FOLD>
+// query one commit per group of its s_j values and paths.  COSET (with FOLD, any K): three f tuples per query, and a group's commit is
+// its s_j slots, one count and one path of L - jK - steps_j digests.
+template <bool FOLD, bool COSET = false>
 __global__ void __launch_bounds__(kVerifyThreads) verify_transcript_kernel(VerifyArgs a) {
+    static_assert(FOLD || !COSET, "the coset instance reads the group fields");
+    constexpr uint32_t NF = COSET ? 3u : 4u;              // f tuples per query
     const uint32_t p = blockIdx.x * kVerifyThreads + threadIdx.x;
     if (p >= a.count) return;
     const uint32_t* pr = a.proofs + (size_t)p * a.words;
@@ -328,10 +479,10 @@ __global__ void __launch_bounds__(kVerifyThreads) verify_transcript_kernel(Verif
 #pragma unroll
     for (int i = 0; i < 8; ++i) st[i] = 0u;
     const uint32_t R = FOLD ? a.G : a.R, L = a.L, q = a.q;   // R: the (beta, root) pairs = the layer commits of a query
-    // steps: f root | 3 alphas | cp root | R x (beta, layer root) | free term | [nonce] | q query raws | q x (4 f paths, R layer pairs)
+    // steps: f root | 3 alphas | cp root | R x (beta, layer root) | free term | [nonce] | q query raws | q x (NF f paths, R layer pairs)
     const uint32_t gs = a.gw ? 1u : 0u;                   // the nonce step: a commit of 2 words, then the zero-bit test (-1998)
     const uint32_t head = 6u + 2u * R + gs + q;
-    const uint32_t steps = head + q * (4u + R);
+    const uint32_t steps = head + q * (NF + R);
     uint32_t cur = 0, k = 0;
     int32_t code = 0;
     for (uint32_t s = 0; s < steps; ++s) {
@@ -341,9 +492,12 @@ __global__ void __launch_bounds__(kVerifyThreads) verify_transcript_kernel(Verif
             chal = (s >= 1u && s <= 3u) || (s >= 5u && s < 5u + 2u * R && ((s - 5u) & 1u) == 0u) || s >= 6u + 2u * R + gs;
             nw = chal ? 1u : (s == 5u + 2u * R ? 1u : (gs && s == 6u + 2u * R) ? 2u : 8u);
         } else {
-            const uint32_t t = (s - head) % (4u + R);
+            const uint32_t t = (s - head) % (NF + R);
             chal = false;
-            if constexpr (FOLD) nw = t < 4u ? 3u + 8u * L : (3u + 8u * (L - (t - 4u) * a.K)) << (t - 3u < R ? a.K : a.ls);
+            if constexpr (COSET) {
+                const uint32_t j = t - 3u, gsteps = t - 2u < R ? a.K : a.ls;   // t >= 3: group j, the last one short
+                nw = t < 3u ? 3u + 8u * L : (1u << gsteps) + 2u + 8u * (L - j * a.K - gsteps);
+            } else if constexpr (FOLD) nw = t < 4u ? 3u + 8u * L : (3u + 8u * (L - (t - 4u) * a.K)) << (t - 3u < R ? a.K : a.ls);
             else nw = t < 4u ? 3u + 8u * L : 6u + 16u * (L - (t - 4u));
         }
         if (chal) {                                       // state word 0 (big-endian bytes 0..3) against the little-endian u32 here
@@ -399,6 +553,14 @@ int32_t fold_key_to_check(int32_t key, uint32_t G) {
     const uint32_t j = (pos - 5u - G) / 8u, t = (pos - 5u - G) % 8u;
     return -(int32_t)((t ? 400u : 300u) + j);
 }
+// The same for the keys of a proof with coset leaves: one fold comparison and one path per group.
+int32_t coset_key_to_check(int32_t key, uint32_t G) {
+    const uint32_t pos = (uint32_t)key % (4u + 2u * G);
+    if (pos == 0) return -2;
+    if (pos < 4) return -(int32_t)(3u + pos);             // -4 .. -6
+    if (pos < 4 + G) return -(int32_t)(100u + (pos - 4u));
+    return -(int32_t)(300u + (pos - 4u - G));
+}
 
 }  // namespace
 }  // namespace zk
@@ -407,6 +569,7 @@ struct zk_verifier {
     int device = 0;
     uint32_t log_n = 0, log_b = 0, queries = 1, grind = 0, fold = 1;
     int hash = ZK_HASH_SHA256;
+    bool coset = false;                                // proofs with coset leaves (zk_verifier_set_coset_leaves)
     hipStream_t stream = nullptr, tstream = nullptr;   // paths + algebra; transcript (runs beside them)
     hipEvent_t ev_in = nullptr, ev_t = nullptr;
     uint8_t* d_buf = nullptr;                          // proofs, public_last, states, then the three per-proof results
@@ -441,6 +604,7 @@ int verifier_chunk(zk_verifier* v, const uint8_t* proofs, size_t stride, size_t 
                    int32_t* checks_out, size_t len) {
     const uint32_t log_n = v->log_n, log_b = v->log_b, q = v->queries, R = log_n, L = log_n + log_b;
     const uint32_t K = v->fold, G = fold_groups(R, K);
+    const bool coset = v->coset;
     // inputs: [count][len] proofs, [count] public_last, [count][32] states, packed into the pinned staging buffer
     uint8_t* hp = v->h_in;
     if (stride == len) memcpy(hp, proofs, count * len);
@@ -466,8 +630,12 @@ int verifier_chunk(zk_verifier* v, const uint8_t* proofs, size_t stride, size_t 
     a.gw = v->grind ? 2u : 0u;
     a.gmask = v->grind ? ~0u << (32u - v->grind) : 0u;
     a.qbase = 20u + 9u * G + a.gw + q;
-    a.per_q = 4u * (3u + 8u * L);
-    for (uint32_t j = 0; j < G; ++j) a.per_q += (3u + 8u * (L - j * K)) << fold_steps(R, K, j);   // K = 1: 6 + 16 (L - j)
+    a.per_q = (coset ? 3u : 4u) * (3u + 8u * L);
+    for (uint32_t j = 0; j < G; ++j) {
+        const uint32_t steps = fold_steps(R, K, j);
+        if (coset) a.per_q += (1u << steps) + 2u + 8u * (L - j * K - steps);
+        else a.per_q += (3u + 8u * (L - j * K)) << steps;   // K = 1: 6 + 16 (L - j)
+    }
     if (a.qbase + (size_t)q * a.per_q != len / 4) return fail(ZK_ERR_STATE, "zk_verifier_run: the layout does not add up to the proof length");
     a.K = K; a.G = G; a.ls = fold_steps(R, K, G - 1u);
     const uint32_t w = invmod(powmod(a.h, (uint64_t)a.N >> 3));
@@ -483,19 +651,28 @@ int verifier_chunk(zk_verifier* v, const uint8_t* proofs, size_t stride, size_t 
     if (states) {                                      // the transcript chains run beside the paths: cost = max of the two
         HIPCHK(hipEventRecord(v->ev_in, v->stream));
         HIPCHK(hipStreamWaitEvent(v->tstream, v->ev_in, 0));
-        if (K == 1) hipLaunchKernelGGL(verify_transcript_kernel<false>, dim3(gx), dim3(kVerifyThreads), 0, v->tstream, a);
+        if (coset) hipLaunchKernelGGL((verify_transcript_kernel<true, true>), dim3(gx), dim3(kVerifyThreads), 0, v->tstream, a);
+        else if (K == 1) hipLaunchKernelGGL(verify_transcript_kernel<false>, dim3(gx), dim3(kVerifyThreads), 0, v->tstream, a);
         else hipLaunchKernelGGL(verify_transcript_kernel<true>, dim3(gx), dim3(kVerifyThreads), 0, v->tstream, a);
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(v->ev_t, v->tstream));
     }
     const uint64_t lanes = (uint64_t)count * q;
     const dim3 agrid((uint32_t)((lanes + kVerifyThreads - 1) / kVerifyThreads));
-    if (K == 1) hipLaunchKernelGGL(verify_algebra_kernel, agrid, dim3(kVerifyThreads), 0, v->stream, a);
+    if (coset) {
+        if (K == 1) hipLaunchKernelGGL(verify_coset_algebra_kernel<1>, agrid, dim3(kVerifyThreads), 0, v->stream, a);
+        else if (K == 2) hipLaunchKernelGGL(verify_coset_algebra_kernel<2>, agrid, dim3(kVerifyThreads), 0, v->stream, a);
+        else hipLaunchKernelGGL(verify_coset_algebra_kernel<3>, agrid, dim3(kVerifyThreads), 0, v->stream, a);
+    } else if (K == 1) hipLaunchKernelGGL(verify_algebra_kernel, agrid, dim3(kVerifyThreads), 0, v->stream, a);
     else if (K == 2) hipLaunchKernelGGL(verify_fold_algebra_kernel<2>, agrid, dim3(kVerifyThreads), 0, v->stream, a);
     else hipLaunchKernelGGL(verify_fold_algebra_kernel<3>, agrid, dim3(kVerifyThreads), 0, v->stream, a);
     HIPCHK(hipGetLastError());
     const bool sha = v->hash == ZK_HASH_SHA256;
-    if (K == 1) {
+    if (coset) {
+        const dim3 pgrid(gx, q * (3u + G));
+        if (sha) hipLaunchKernelGGL(verify_coset_paths_kernel<0>, pgrid, dim3(kVerifyThreads), 0, v->stream, a);
+        else hipLaunchKernelGGL(verify_coset_paths_kernel<1>, pgrid, dim3(kVerifyThreads), 0, v->stream, a);
+    } else if (K == 1) {
         const dim3 pgrid(gx, q * (4u + 2u * R));
         if (sha) hipLaunchKernelGGL((verify_paths_kernel<0, false>), pgrid, dim3(kVerifyThreads), 0, v->stream, a);
         else hipLaunchKernelGGL((verify_paths_kernel<1, false>), pgrid, dim3(kVerifyThreads), 0, v->stream, a);
@@ -517,8 +694,9 @@ int verifier_chunk(zk_verifier* v, const uint8_t* proofs, size_t stride, size_t 
         int32_t c;
         if (states && tcode[i]) c = tcode[i];
         else if (malformed[i])                             // garbage only
-            c = verify_proof(proofs + i * stride, len, log_n, log_b, public_last[i], v->hash, q, v->grind, K);
-        else c = best[i] == kNoFailure ? 0 : (K == 1 ? key_to_check(best[i], R) : fold_key_to_check(best[i], G));
+            c = verify_proof(proofs + i * stride, len, log_n, log_b, public_last[i], v->hash, q, v->grind, K, coset);
+        else if (best[i] == kNoFailure) c = 0;
+        else c = coset ? coset_key_to_check(best[i], G) : K == 1 ? key_to_check(best[i], R) : fold_key_to_check(best[i], G);
         checks_out[i] = c;
     }
     return ZK_OK;
@@ -597,12 +775,20 @@ int zk_verifier_set_fold(zk_verifier* v, uint32_t fold_log) {
 
 uint32_t zk_verifier_get_fold(const zk_verifier* v) { return v ? v->fold : 0u; }
 
+int zk_verifier_set_coset_leaves(zk_verifier* v, int on) {
+    if (!v) return fail(ZK_ERR_INVALID, "null verifier");
+    v->coset = on != 0;
+    return ZK_OK;
+}
+
+int zk_verifier_get_coset_leaves(const zk_verifier* v) { return v && v->coset ? 1 : 0; }
+
 int zk_verifier_run(zk_verifier* v, const uint8_t* proofs, size_t stride, size_t count, const uint8_t* states, const uint32_t* public_last,
                     int32_t* checks_out) {
     if (!v) return fail(ZK_ERR_INVALID, "null verifier");
     if (count == 0) return ZK_OK;
     if (!proofs || !public_last || !checks_out) return fail(ZK_ERR_INVALID, "zk_verifier_run: null argument");
-    const size_t len = proof_data_len(v->log_n, v->log_b, v->queries, v->grind, v->fold);
+    const size_t len = proof_data_len(v->log_n, v->log_b, v->queries, v->grind, v->fold, v->coset);
     if (stride < len) return fail(ZK_ERR_INVALID, "zk_verifier_run: stride %zu < proof length %zu", stride, len);
     if (count > SIZE_MAX / stride) return fail(ZK_ERR_INVALID, "zk_verifier_run: count * stride overflows");
     HIPCHK(hipSetDevice(v->device));

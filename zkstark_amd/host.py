@@ -562,10 +562,12 @@ class Verifier:
     """Many proofs of one size checked at once on the GPU (zk_verifier_*).  Every result is the number Proof.check gives for
     that proof: 0 = accepted, otherwise the CPU verifier's check number."""
 
-    def __init__(self, log_n, log_blowup, device=0, hash="sha256", queries=1, grind_bits=0, fold_log=1):
-        """fold_log: the FRI folding factor 2^fold_log of the proofs to check (zk_verifier_set_fold; 1 = the reference)."""
+    def __init__(self, log_n, log_blowup, device=0, hash="sha256", queries=1, grind_bits=0, fold_log=1, coset_leaves=False):
+        """fold_log: the FRI folding factor 2^fold_log of the proofs to check (zk_verifier_set_fold; 1 = the reference).
+        coset_leaves: the proofs were made with coset leaves (zk_verifier_set_coset_leaves; Context(coset_leaves=True))."""
         self.log_n, self.log_blowup, self.hash, self.queries, self.grind_bits = log_n, log_blowup, hash, queries, grind_bits
         self.fold_log = 1
+        self.coset_leaves = False
         self._h = C.c_void_p()
         check(_lib.load().zk_verifier_create(device, log_n, log_blowup, C.byref(self._h)))
         if hash != "sha256":
@@ -576,11 +578,18 @@ class Verifier:
             check(_lib.load().zk_verifier_set_grinding(self._h, grind_bits))
         if fold_log != 1:
             self.set_fold(fold_log)
+        if coset_leaves:
+            self.set_coset_leaves(True)
 
     def set_fold(self, fold_log):
         """zk_verifier_set_fold: check proofs folded by 2^fold_log (1..3) between commitments from the next run on."""
         check(_lib.load().zk_verifier_set_fold(self._h, fold_log))
         self.fold_log = fold_log
+
+    def set_coset_leaves(self, on=True):
+        """zk_verifier_set_coset_leaves: from the next run on, check proofs with one coset per leaf and one path per group."""
+        check(_lib.load().zk_verifier_set_coset_leaves(self._h, int(bool(on))))
+        self.coset_leaves = bool(on)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -594,7 +603,8 @@ class Verifier:
 
     @property
     def proof_len(self):
-        return _lib.load().zk_proof_data_len_fold(self.log_n, self.log_blowup, self.queries, self.grind_bits, self.fold_log)
+        fn = _lib.load().zk_proof_data_len_coset if self.coset_leaves else _lib.load().zk_proof_data_len_fold
+        return fn(self.log_n, self.log_blowup, self.queries, self.grind_bits, self.fold_log)
 
     def verify_raw(self, data, public_last, states=None):
         """data: [count, stride] uint8 (stride >= proof_len; BatchContext.prove_raw()'s array as it is), public_last: [count],
@@ -618,13 +628,17 @@ class Verifier:
         return out
 
     def verify(self, proofs, strict=True):
-        """proofs: a list of Proof of this verifier's size and folding factor (their data, state and public_last are used)."""
+        """proofs: a list of Proof of this verifier's size, folding factor and leaf format (their data, state and public_last are used)."""
         proofs = list(proofs)
         plen = self.proof_len
         data = np.zeros((len(proofs), plen), dtype=np.uint8)
         for i, p in enumerate(proofs):
             if getattr(p, "fold_log", 1) != self.fold_log:
                 raise ZkError(-1, f"verify: proof {i} was folded with fold_log {getattr(p, 'fold_log', 1)}, this verifier is set to {self.fold_log}")
+            if bool(getattr(p, "coset_leaves", False)) != self.coset_leaves:
+                names = {True: "coset leaves", False: "one-value leaves"}
+                raise ZkError(-1, f"verify: proof {i} was made with {names[bool(getattr(p, 'coset_leaves', False))]}, "
+                                  f"this verifier is set to {names[self.coset_leaves]}")
             if len(p.data) != plen:
                 raise ZkError(-1, f"verify: proof {i} has {len(p.data)} bytes, this verifier takes {plen}")
             data[i] = np.frombuffer(p.data, dtype=np.uint8)
