@@ -198,8 +198,9 @@ uint32_t zk_ctx_get_fold(const zk_ctx *ctx);
  * 2^top_log LEAVES hands over one level below its leaves) and results are identical for every setting.  zk_merkle_node(s) /
  * zk_merkle_path address a coset tree by its own leaves: 2 len / s - 1 nodes, leaf index < len / s, L - r0 - steps digests.
  * Measured: see DESIGN.md 7d.
- * zk_verifier_* checks such proofs in batches with zk_verifier_set_coset_leaves.
- * NOT covered: zk_batch_* and zk_shard_* / zk_tail_* keep one-value leaves. */
+ * zk_verifier_* checks such proofs in batches with zk_verifier_set_coset_leaves; zk_batch_* makes them with
+ * zk_batch_set_coset_leaves.
+ * NOT covered: zk_shard_* / zk_tail_* keep one-value leaves. */
 int zk_ctx_set_coset_leaves(zk_ctx *ctx, int on);
 int zk_ctx_get_coset_leaves(const zk_ctx *ctx);
 /* The HIP stream every stage is enqueued on (hipStream_t). */
@@ -307,8 +308,11 @@ int zk_kernel_stats(zk_ctx *ctx, zk_kernel_stat *out, size_t count, int reset);
  * lockstep: the layers of the batch are stored proof-major, so every stage is ONE launch of the kernels
  * a single proof uses on a domain batch times larger, and the trees of the batch are the bottom of one
  * heap whose nodes of depth log_batch are the per-proof roots.  Every proof is byte-identical to what
- * zk_prove returns for the same trace.  log_batch <= 10; (log_n, log_blowup) as for zk_ctx_create (log_n >= 2, != 3), so
- * every proof a batch produces can be checked by zk_verify*. */
+ * zk_prove returns for the same trace from a context with the batch's settings: hash, queries, grinding, folding factor
+ * (zk_batch_set_fold) and leaf format (zk_batch_set_coset_leaves; off by default).  With coset leaves a tree over len values per
+ * proof has len / s leaves per proof and the batch heap batch * len / s.  log_batch <= 10; (log_n, log_blowup) as for
+ * zk_ctx_create (log_n >= 2, != 3), so every proof a batch produces can be checked by zk_verify*.  A batch of one (log_batch 0)
+ * is a zk_ctx: every setter forwards to it. */
 typedef struct zk_batch zk_batch;
 int zk_batch_create(int device, uint32_t log_n, uint32_t log_blowup, uint32_t log_batch, zk_batch **out);
 int zk_batch_destroy(zk_batch *b);
@@ -331,6 +335,21 @@ int zk_batch_set_grinding(zk_batch *b, uint32_t grind_bits);
  * zk_batch_get_fold: the current fold_log, 0 for a null batch. */
 int zk_batch_set_fold(zk_batch *b, uint32_t fold_log);
 uint32_t zk_batch_get_fold(const zk_batch *b);
+/* As zk_ctx_set_coset_leaves, for every proof of the batch: off by default (with it off every byte, launch and allocation of
+ * zk_batch_prove is what it was without this call); any non-zero `on` means on, from the next zk_batch_prove on.  It combines with every
+ * fold_log 1..3, hash, query count 1..16 and grinding.  With it on, proof p is byte for byte what zk_prove returns from a context with the
+ * same (log_n, log_blowup, hash, n_queries, grind_bits, fold_log), zk_ctx_set_coset_leaves(ctx, 1) and the same trace, its state too; its
+ * length is zk_proof_data_len_coset and it is checked with zk_verify_coset, or in batches with zk_verifier_set_coset_leaves.  The flow
+ * is the one-call prover's: trees 0 (f) and 1 + log_n (last layer) keep one-value leaves; cp is composed by a launch of its own and
+ * its tree has group 0's cosets as leaves; every group, for fold_log 1 too, is one batched multi-fold launch, and the tree over its
+ * output has the next group's cosets as leaves (coset_leaf_hash_batch_kernel, then the inner build).  The tree-top hand-over to the
+ * host threads goes by the per-proof leaf count; results are identical with zk_batch_set_host_levels 0 and 1.  The decommitment
+ * buffers are re-sized here, and the 32 bytes per proof of the multi-fold are allocated if they are not there yet; if an
+ * allocation fails the call fails as zk_batch_set_fold does and the batch keeps its format.  Refused with ZK_ERR_STATE while a
+ * zk_batch_prove runs.  A null batch: ZK_ERR_INVALID.  Measured: see DESIGN.md 7d.
+ * zk_batch_get_coset_leaves: 1 or 0, 0 for a null batch. */
+int zk_batch_set_coset_leaves(zk_batch *b, int on);
+int zk_batch_get_coset_leaves(const zk_batch *b);
 /* on = 0: every tree level of the batch on the device (default: the host threads hash the top levels of each proof's
  * trees when the CPU has SHA extensions, as zk_ctx_set_host_levels).  Results are identical. */
 int zk_batch_set_host_levels(zk_batch *b, int on);
@@ -347,11 +366,14 @@ int zk_batch_gen_fibsq(zk_batch *b, const uint32_t *a0, const uint32_t *a1);
 int zk_batch_public_last(const zk_batch *b, uint32_t *out);
 /* proofs_out: [batch][stride] bytes, stride >= zk_proof_data_len(log_n, log_blowup); states_out:
  * [batch][32] (with q queries: zk_proof_data_len_queries; in general zk_proof_data_len_fold(log_n, log_blowup, n_queries, grind_bits,
- * fold_log)).  Fails with ZK_ERR_CHECK, naming the proof, if a trace breaks the constraints. */
+ * fold_log); with coset leaves zk_proof_data_len_coset of the same arguments).  Fails with ZK_ERR_CHECK, naming the proof, if a trace
+ * breaks the constraints. */
 int zk_batch_prove(zk_batch *b, uint8_t *proofs_out, size_t stride, uint8_t *states_out);
 /* Nodes [first, first + count) of batch tree `tree` (a heap over batch * m_l leaves; proof p's tree is the subtree under node
  * 2^log_batch - 1 + p), 32 bytes each as zk_merkle_node.  Complete after zk_batch_prove; ZK_ERR_STATE for a tree id that the last
- * proof, folded by zk_batch_set_fold, did not build. */
+ * proof, folded by zk_batch_set_fold, did not build.  A tree the last proof built with coset leaves of 2^steps values is addressed by
+ * its own heap: 2 * batch * (len >> steps) - 1 nodes, anything beyond is ZK_ERR_INVALID; the batch remembers the steps of each tree per
+ * proof, so a later plain proof has full-size heaps again. */
 int zk_batch_merkle_nodes(zk_batch *b, uint32_t tree, size_t first, size_t count, uint8_t *out);
 
 /* ---- proof: proof.rs ------------------------------------------------------- */

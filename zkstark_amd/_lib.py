@@ -183,6 +183,8 @@ SYMBOLS = {
     "zk_verifier_set_hash": (_int, [_vp, _int]),
     "zk_verifier_set_fold": (_int, [_vp, _u32]),
     "zk_verifier_get_fold": (_u32, [_vp]),
+    "zk_batch_set_coset_leaves": (_int, [_vp, _int]),
+    "zk_batch_get_coset_leaves": (_int, [_vp]),
     "zk_verifier_set_coset_leaves": (_int, [_vp, _int]),
     "zk_verifier_get_coset_leaves": (_int, [_vp]),
     "zk_verifier_run": (_int, [_vp, _vp, _sz, _sz, _vp, _vp, _vp]),

@@ -7,6 +7,9 @@
 // draws its own challenges (host threads), and the next launch reads them from a per-proof table.
 // One loop over the groups of `fold` rounds serves every folding factor (K = 1: one round per group, fold fused into the leaf
 // hashing); the openings and their encoding are transcript.hpp's for_each_opening and Channel::commit_group.
+// Coset leaves (zk_batch_set_coset_leaves): the tree over a group's input layer has one leaf per opened coset, so proof p's tree over
+// len values has m = len / s leaves and the batch heap batch * m; cp is composed by its own launch, every K folds with the batched
+// multi-fold, and the trees come from launch_merkle_build_coset_batch -- prove_resident / prove_fold_rounds (zkstark.hip) per proof.
 #include <atomic>
 #include <condition_variable>
 #include <cstdio>
@@ -56,7 +59,9 @@ struct zk_batch {
     uint32_t fold = 1;                // FRI folding factor 2^fold between commitments (zk_batch_set_fold; 1 = the reference)
     uint32_t proved_fold = 1;         // ... of the last zk_batch_prove, whose skipped_trees these are:
     uint64_t skipped_trees = 0;       // bit id: that proof built no tree (and no layer) `id`
-    uint32_t* d_work = nullptr;       // [batch][8] per-proof constants of the multi-fold (allocated by the first fold > 1)
+    uint32_t* d_work = nullptr;       // [batch][8] per-proof constants of the multi-fold (allocated by the first fold > 1 or coset leaves)
+    bool coset = false;               // coset leaves (zk_batch_set_coset_leaves): from the next zk_batch_prove on
+    uint8_t tree_steps[34] = {0};     // tree id of the last zk_batch_prove: its leaves hold 2^tree_steps values (0: one-value leaves)
     Grinder* grinder = nullptr;       // one launch grinds for every proof of the batch (created by the setter above kGrindHostMaxBits)
     int hash = 0;                    // Merkle hash: 0 = SHA-256 (reference), 1 = field-native
     std::vector<uint32_t> first, last;
@@ -152,9 +157,11 @@ const uint32_t* bfinish_roots(zk_batch* b, uint32_t tree, uint32_t log_m) {
 }
 
 // values and path digests one query opens (transcript.hpp: for_each_opening)
-void bopenings(const zk_batch* b, uint32_t fold, size_t* vals, size_t* digs) {
+void bopenings(const zk_batch* b, uint32_t fold, bool coset, size_t* vals, size_t* digs) {
     *vals = *digs = 0;
-    for_each_opening(b->log_n, b->log_b, fold, 0, [&](uint32_t, uint32_t log_len, size_t, uint32_t) { ++*vals; *digs += log_len; });
+    for_each_opening(b->log_n, b->log_b, fold, 0, [&](uint32_t, uint32_t log_leaves, size_t, uint32_t slots_log) {
+        *vals += (size_t)1 << slots_log; *digs += log_leaves;
+    }, coset);
 }
 // gather buffers for q queries per proof (offsets in, values + digests out; device and pinned host copies), for the current fold
 int balloc_gather(zk_batch* b, uint32_t q) {
@@ -168,6 +175,27 @@ int balloc_gather(zk_batch* b, uint32_t q) {
     HIPCHK(hipHostMalloc((void**)&b->h_goff, slots * 8));
     HIPCHK(hipHostMalloc((void**)&b->h_gout, out_words * 4));
     b->queries = q;
+    return ZK_OK;
+}
+
+// The batch goes to (fold, coset): d_work for the multi-fold (every fold > 1, and every fold with coset leaves), the gather buffers for
+// what a query of that format opens.  On failure the batch keeps its settings and the buffers they need.
+int bset_format(zk_batch* b, uint32_t fold, bool coset, const char* who) {
+    HIPCHK(hipSetDevice(b->device));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    if ((fold > 1 || coset) && !b->d_work) {
+        hipError_t e = hipMalloc((void**)&b->d_work, b->batch * 8 * 4);
+        if (e != hipSuccess) return fail(ZK_ERR_NOMEM, "%s: hipMalloc(%zu) failed: %s", who, b->batch * 32, hipGetErrorString(e));
+        b->device_bytes += b->batch * 32;
+    }
+    const size_t old_vals = b->per_proof_vals, old_digs = b->per_proof_digs;
+    bopenings(b, fold, coset, &b->per_proof_vals, &b->per_proof_digs);
+    if (int rc = balloc_gather(b, b->queries)) {          // the old buffers are gone: put back what the old format needs, or fail again later
+        b->per_proof_vals = old_vals; b->per_proof_digs = old_digs;
+        (void)balloc_gather(b, b->queries);
+        return rc;
+    }
+    b->fold = fold; b->coset = coset;
     return ZK_OK;
 }
 
@@ -248,7 +276,7 @@ int zk_batch_create(int device, uint32_t log_n, uint32_t log_b, uint32_t log_bat
         return bail(rc);
     HIPCHK_B(hipMemsetAsync(b->d_counter, 0, 64, b->stream));
     HIPCHK_B(hipMemsetAsync(b->d_trace, 0, b->batch * b->n * 4, b->stream));
-    bopenings(b, 1, &b->per_proof_vals, &b->per_proof_digs);
+    bopenings(b, 1, false, &b->per_proof_vals, &b->per_proof_digs);
     if ((rc = balloc_gather(b, 1))) return bail(rc);
     HIPCHK_B(hipHostMalloc((void**)&b->h_chal, b->batch * sizeof(BatchChal)));
     HIPCHK_B(hipHostMalloc((void**)&b->h_last, b->batch * (b->B > 2 ? b->B : 2) * 4));
@@ -347,24 +375,23 @@ int zk_batch_set_fold(zk_batch* b, uint32_t fold_log) {
         return ZK_OK;
     }
     if (fold_log == b->fold) return ZK_OK;
-    HIPCHK(hipSetDevice(b->device));
-    HIPCHK(hipStreamSynchronize(b->stream));
-    if (fold_log > 1 && !b->d_work) {
-        hipError_t e = hipMalloc((void**)&b->d_work, b->batch * 8 * 4);
-        if (e != hipSuccess) return fail(ZK_ERR_NOMEM, "zk_batch_set_fold: hipMalloc(%zu) failed: %s", b->batch * 32, hipGetErrorString(e));
-        b->device_bytes += b->batch * 32;
-    }
-    const size_t old_vals = b->per_proof_vals, old_digs = b->per_proof_digs;
-    bopenings(b, fold_log, &b->per_proof_vals, &b->per_proof_digs);
-    if (int rc = balloc_gather(b, b->queries)) {          // the old buffers are gone: put back what the old factor needs, or fail again later
-        b->per_proof_vals = old_vals; b->per_proof_digs = old_digs;
-        (void)balloc_gather(b, b->queries);
-        return rc;
-    }
-    b->fold = fold_log;
-    return ZK_OK;
+    return bset_format(b, fold_log, b->coset, "zk_batch_set_fold");
 }
 uint32_t zk_batch_get_fold(const zk_batch* b) { return b ? b->fold : 0; }
+// Coset leaves (include/zkstark_amd.h): from the next zk_batch_prove on.  A coset proof opens fewer nodes and other values than a plain
+// one, so the gather buffers are re-sized here; every fold, 1 included, then runs on the multi-fold and needs d_work.
+int zk_batch_set_coset_leaves(zk_batch* b, int on) {
+    if (!b) return fail(ZK_ERR_INVALID, "null batch");
+    ZK_BATCH_EXCLUSIVE(b, "zk_batch_set_coset_leaves");
+    if (b->single) {
+        if (int rc = zk_ctx_set_coset_leaves(b->single, on)) return rc;
+        b->coset = on != 0;
+        return ZK_OK;
+    }
+    if ((on != 0) == b->coset) return ZK_OK;
+    return bset_format(b, b->fold, on != 0, "zk_batch_set_coset_leaves");
+}
+int zk_batch_get_coset_leaves(const zk_batch* b) { return b && b->coset ? 1 : 0; }
 size_t zk_batch_device_bytes(const zk_batch* b) { return b ? b->device_bytes : 0; }
 
 // traces: [batch][n-1] canonical residues on the host (prover.rs:32-39 per proof)
@@ -423,20 +450,22 @@ int zk_batch_public_last(const zk_batch* b, uint32_t* out) {
 
 // Nodes [first, first + count) of batch tree `tree` (a heap over batch * m_l leaves; proof p's tree is the subtree under node
 // 2^log_batch - 1 + p).  Complete after zk_batch_prove: its last launches copy the host-built levels in (scatter_kernel).
+// A tree the last proof built with coset leaves of 2^steps values has m_l = len >> steps leaves per proof: its own, smaller heap.
 int zk_batch_merkle_nodes(zk_batch* b, uint32_t tree, size_t first, size_t count, uint8_t* out) {
     if (!b || (!out && count)) return fail(ZK_ERR_INVALID, "zk_batch_merkle_nodes: null argument");
     if (b->single) return zk_merkle_nodes(b->single, tree, first, count, out);
-    const size_t heap = tree <= b->R + 1 ? 2 * blayer_size(b, tree) * b->batch - 1 : 0;
-    if (tree > b->R + 1 || first > heap || count > heap - first) return fail(ZK_ERR_INVALID, "zk_batch_merkle_nodes: out of range");
+    if (tree > b->R + 1) return fail(ZK_ERR_INVALID, "zk_batch_merkle_nodes: out of range");
     BusyScope busy(b);
     if (!busy.mine) return fail(ZK_ERR_STATE, "zk_batch_merkle_nodes: a zk_batch_prove is running on this batch");
+    const size_t heap = 2 * (blayer_size(b, tree) >> b->tree_steps[tree]) * b->batch - 1;   // read under the flag: a running proof rewrites tree_steps
+    if (first > heap || count > heap - first) return fail(ZK_ERR_INVALID, "zk_batch_merkle_nodes: out of range");
     if ((b->skipped_trees >> tree) & 1)
         return fail(ZK_ERR_STATE, "zk_batch_merkle_nodes: tree %u was not built by the last proof (fold_log %u)", tree, b->proved_fold);
     return merkle_nodes_to_host(b->device, b->stream, b->d_trees + b->tree_off[tree], first, count, out);
 }
 
 // generate_proof (prover.rs:9-293) for every resident trace.  proofs_out: [batch][stride] bytes, stride >=
-// zk_proof_data_len_fold(log_n, log_b, queries, grind, fold); states_out: [batch][32] (Channel.state of each proof, proof.rs:6).
+// zk_proof_data_len_fold(log_n, log_b, queries, grind, fold) (coset leaves: zk_proof_data_len_coset); states_out: [batch][32] (Channel.state of each proof, proof.rs:6).
 // fold > 1 (DESIGN.md "Folding factor"): the rounds in groups of `fold`; per group one challenge per proof, one pass of the batched
 // multi-fold kernel and one tree over its output, as prove_fold_rounds (zkstark.hip) does for one proof.  The wire format (openings,
 // tuples, length) is transcript.hpp's for every fold.
@@ -448,7 +477,8 @@ int zk_batch_prove(zk_batch* b, uint8_t* proofs_out, size_t stride, uint8_t* sta
     const uint32_t Q = b->queries;
     const int hash = b->hash;
     const uint32_t K = b->fold;
-    const size_t plen = proof_data_len(b->log_n, b->log_b, Q, b->grind, K);
+    const bool coset = b->coset;
+    const size_t plen = proof_data_len(b->log_n, b->log_b, Q, b->grind, K, coset);
     if (stride < plen) return fail(ZK_ERR_BUFFER, "zk_batch_prove: stride %zu < proof length %zu", stride, plen);
     if (b->single) {
         size_t len = 0;
@@ -476,6 +506,7 @@ int zk_batch_prove(zk_batch* b, uint8_t* proofs_out, size_t stride, uint8_t* sta
     if ((rc = dom_lde(d, b->d_trace, b->d_coef, b->d_layers + b->layer_off[0], b->stream, nullptr, (uint32_t)nb))) return rc;
     b->stage_used = 0; b->n_segs = 0; b->seg_words = 0;
     b->skipped_trees = 0; b->proved_fold = K;
+    memset(b->tree_steps, 0, sizeof b->tree_steps);
     HIPCHK(launch_merkle_build(b->d_layers + b->layer_off[0], L + lb, b->d_trees + b->tree_off[0], b->stream, nullptr, bmail(b, L), hash));
     // proof-independent part of the composition constants (compose_args with alpha = 1)
     ComposeBatchArgs ca;
@@ -497,26 +528,34 @@ int zk_batch_prove(zk_batch* b, uint8_t* proofs_out, size_t stride, uint8_t* sta
         c.alpha0_mont = to_mont(a0); c.alpha1g2_mont = to_mont(mulmod(a1, g2)); c.alpha2_mont = to_mont(a2);
     });
     if ((rc = bchal_upload(b))) return rc;
+    if (coset) {                                                          // prover.rs:166-176, then the tree with group 0's cosets as leaves
+        const uint32_t s0 = fold_steps(R, K, 0);
+        HIPCHK(launch_compose_batch(ca, lb, b->stream, nullptr));
+        b->tree_steps[1] = (uint8_t)s0;
+        HIPCHK(launch_merkle_build_coset_batch(b->d_layers + b->layer_off[1], L, s0, lb, b->d_trees + b->tree_off[1], b->stream, nullptr,
+                                               bmail(b, L - s0), hash));
+    } else
     HIPCHK(launch_compose_merkle_batch(ca, lb, b->d_trees + b->tree_off[1], b->stream, nullptr, bmail(b, L), hash));   // prover.rs:166-176
+    const bool fused = K == 1 && !coset;                                  // the fold inside the leaf hashing of its tree
     for (uint32_t r0 = 0;;) {                                             // per group; tree 1 + r0 is the last one committed
         if ((rc = wait_roots())) return rc;
-        roots = bfinish_roots(b, 1 + r0, L - r0);                         // tree 1 + r0: 2^(L - r0) leaves per proof
+        roots = bfinish_roots(b, 1 + r0, L - r0 - b->tree_steps[1 + r0]);   // tree 1 + r0: 2^(L - r0) values per proof, 2^tree_steps per leaf
         if (r0 == R) {
             b->pool->run(nb, 32, [&](size_t p) { uint8_t root[32]; digest_words_to_bytes(roots + 8 * p, root); ch[p].commit_hash(root); });
             break;
         }
         const uint32_t steps = R - r0 < K ? R - r0 : K, id = 1 + r0 + steps;
         // K = 1: the fold constant is reduced on the host; K > 1: the challenge goes up RAW and is reduced on the device
-        const uint32_t winv_half = K == 1 ? mulmod(invmod(powmod(d->shift, (uint64_t)1 << r0)), invmod(2)) : 0;
+        const uint32_t winv_half = fused ? mulmod(invmod(powmod(d->shift, (uint64_t)1 << r0)), invmod(2)) : 0;
         b->pool->run(nb, 32, [&](size_t p) {
             uint8_t root[32];
             digest_words_to_bytes(roots + 8 * p, root);
             ch[p].commit_hash(root);                                      // prover.rs:180 / :224
             const uint32_t beta = ch[p].get_u32();                        // prover.rs:200, once per group
-            b->h_chal[p].c_mont = K == 1 ? to_mont(mulmod(beta % P, winv_half)) : beta;
+            b->h_chal[p].c_mont = fused ? to_mont(mulmod(beta % P, winv_half)) : beta;
         });
         if ((rc = bchal_upload(b))) return rc;
-        if (K == 1) {
+        if (fused) {
             FoldBatchArgs fa;
             if ((rc = fold_args(d, b->d_layers + b->layer_off[1 + r0], b->d_layers + b->layer_off[id], L - r0, r0, 0, fa.a))) return rc;
             fa.chal = b->d_chal;
@@ -524,6 +563,13 @@ int zk_batch_prove(zk_batch* b, uint8_t* proofs_out, size_t stride, uint8_t* sta
         } else {
             if ((rc = dom_fold_multi_batch(d, b->d_layers + b->layer_off[1 + r0], b->d_layers + b->layer_off[id], L - r0, r0, steps, &b->d_chal->c_mont,
                                            (uint32_t)(sizeof(BatchChal) / 4), b->d_work, (uint32_t)nb, b->stream, nullptr))) return rc;   // prover.rs:201-211, steps times
+            // coset leaves: this tree is the one over the NEXT group's input, its leaves are that group's cosets (the last layer: one value)
+            const uint32_t leaf_steps = coset && r0 + steps < R ? (R - r0 - steps < K ? R - r0 - steps : K) : 0;
+            if (leaf_steps) {
+                b->tree_steps[id] = (uint8_t)leaf_steps;
+                HIPCHK(launch_merkle_build_coset_batch(b->d_layers + b->layer_off[id], L - r0 - steps, leaf_steps, lb, b->d_trees + b->tree_off[id],
+                                                       b->stream, nullptr, bmail(b, L - r0 - steps - leaf_steps), hash));
+            } else
             HIPCHK(launch_merkle_build(b->d_layers + b->layer_off[id], L - r0 - steps + lb, b->d_trees + b->tree_off[id], b->stream, nullptr,
                                        bmail(b, L - r0 - steps), hash));      // prover.rs:214
             for (uint32_t l = 2 + r0; l < id; ++l) b->skipped_trees |= (uint64_t)1 << l;
@@ -567,9 +613,11 @@ int zk_batch_prove(zk_batch* b, uint8_t* proofs_out, size_t stride, uint8_t* sta
             }
         };
         for (uint32_t k = 0; k < Q; ++k)                                  // layer l is stored proof-major: proof p's values at p * len
-            for_each_opening(b->log_n, b->log_b, K, (size_t)qraw[k] % (N - 2 * B), [&](uint32_t layer, uint32_t log_len, size_t leaf, uint32_t) {
-                *vo++ = b->layer_off[layer] + (p << log_len) + leaf; add_path(layer, log_len, leaf);
-            });
+            for_each_opening(b->log_n, b->log_b, K, (size_t)qraw[k] % (N - 2 * B), [&](uint32_t layer, uint32_t log_leaves, size_t leaf, uint32_t slots_log) {
+                for (size_t u = 0; u < ((size_t)1 << slots_log); ++u)     // the slots of one leaf (one value unless coset leaves)
+                    *vo++ = b->layer_off[layer] + (p << (log_leaves + slots_log)) + leaf + (u << log_leaves);
+                add_path(layer, log_leaves, leaf);
+            }, coset);
     });
     lap("queries + opening offsets");
     const size_t tv = nb * nv, td = nb * ndg;
@@ -585,13 +633,17 @@ int zk_batch_prove(zk_batch* b, uint8_t* proofs_out, size_t stride, uint8_t* sta
         const uint32_t* vals = b->h_gout + p * nv;
         const uint32_t* dw = b->h_gout + tv + p * ndg * 8;
         std::vector<uint8_t> buf(Channel::group_bytes((size_t)1 << fold_steps(R, K, 0), L));   // one buffer per proof: the first group's tuple is the largest
-        auto tuple = [&](size_t s, size_t pl) {
-            ch[p].commit_group(buf.data(), s, pl, [&](size_t t) { return vals[t]; }, [&](size_t i, uint8_t* out) { digest_words_to_bytes(dw + 8 * i, out); });
-            vals += s; dw += 8 * s * pl;
+        auto tuple = [&](size_t s, size_t pl, bool one_leaf) {
+            ch[p].commit_group(buf.data(), s, pl, [&](size_t t) { return vals[t]; }, [&](size_t i, uint8_t* out) { digest_words_to_bytes(dw + 8 * i, out); },
+                               one_leaf);
+            vals += s; dw += 8 * (one_leaf ? 1 : s) * pl;
         };
         for (uint32_t q = 0; q < Q; ++q) {
-            for (int k = 0; k < 4; ++k) tuple(1, L);                                                                   // prover.rs:274-277
-            for (uint32_t j = 0, G = fold_groups(R, K); j < G; ++j) tuple((size_t)1 << fold_steps(R, K, j), L - j * K);   // prover.rs:280-289
+            for (int k = 0; k < (coset ? 3 : 4); ++k) tuple(1, L, false);                                              // prover.rs:274-277
+            for (uint32_t j = 0, G = fold_groups(R, K); j < G; ++j) {                                                  // prover.rs:280-289
+                const uint32_t steps = fold_steps(R, K, j);
+                tuple((size_t)1 << steps, L - j * K - (coset ? steps : 0), coset);
+            }
         }
         if (ch[p].data.size() != plen) { bad.store(1); return; }
         memcpy(proofs_out + p * stride, ch[p].data.data(), plen);          // channel.rs:34-36

@@ -429,6 +429,24 @@ hipError_t launch_compose(const ComposeArgs& a, hipStream_t s, Profiler* prof) {
     return hipGetLastError();
 }
 
+// cp of a proof-major batch, stored only (the batched prover with coset leaves: the tree over cp then has group 0's cosets as
+// leaves, which the fused one-value leaf source cannot hash): value b * N + i = cp_b[i] with proof b's own trace constants and
+// challenges, the arithmetic of ComposeBatchSrc.
+__global__ __launch_bounds__(256) void compose_batch_kernel(ComposeArgs a, const BatchChal* __restrict__ chal, size_t total) {
+    const size_t pos = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (pos >= total) return;
+    const size_t b = pos >> a.logN, i = pos & (((size_t)1 << a.logN) - 1);
+    const BatchChal c = chal[b];
+    a.cp[pos] = compose_core<true>(a, a.f + (b << a.logN), c.first, c.last, c.alpha0_mont, c.alpha1g2_mont, c.alpha2_mont, i);
+}
+hipError_t launch_compose_batch(const ComposeBatchArgs& a, uint32_t log_batch, hipStream_t s, Profiler* prof) {
+    if (!a.chal || a.a.logN + log_batch > 32) return hipErrorInvalidValue;
+    const size_t total = (size_t)1 << (a.a.logN + log_batch);
+    ScopedKernelTimer tm(prof, K_COMPOSE, 8.0 * (double)total, s);   // read f once, write cp once
+    hipLaunchKernelGGL(compose_batch_kernel, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, s, a.a, a.chal, total);
+    return hipGetLastError();
+}
+
 // ===========================================================================
 // FRI fold
 // ===========================================================================
@@ -1588,6 +1606,74 @@ hipError_t launch_merkle_build_coset(const uint32_t* vals, uint32_t log_len, uin
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     return merkle_build_t(PlainSrc{nullptr}, 0.0, log_m, nodes, s, prof, mail, hash, log_m, 0, false);
+}
+// The same over a proof-major batch of 2^log_batch layers (vals: [batch][2^log_len]): the trees of the batch are the bottom of ONE
+// heap over batch * m leaves, m = 2^(log_len - steps) per proof.  Global leaf g belongs to proof p = g >> log_m and is that
+// proof's leaf c = g & (m - 1): it holds vals[(p << log_len) + c + u m], u < 2^steps (the single kernel over batch * len values
+// would mix the slots of different proofs), and its digest goes to heap position batch * m - 1 + g.  Everything else is
+// coset_leaf_hash_kernel's: one compression per leaf, the next leaf's loads in flight during a hash, the same number of trips for
+// every lane, and each of the s loads a coalesced run across the wave when m >= 64 (below that a wave spans several proofs and a
+// load is one run per proof).
+template <int HASH, int STEPS>
+__global__ __launch_bounds__(kCosetThreads) void coset_leaf_hash_batch_kernel(const uint32_t* __restrict__ vals, uint32_t log_len, uint32_t log_batch,
+                                                                              uint32_t* __restrict__ nodes) {
+    constexpr int S = 1 << STEPS;
+    const uint32_t log_m = log_len - STEPS;
+    const size_t m = (size_t)1 << log_m;                         // leaves per proof, also the distance between two slots of a leaf
+    const size_t total = m << log_batch;
+    const size_t stride = (size_t)gridDim.x * kCosetThreads;     // a power of two <= total, or every leaf has a lane of its own
+    size_t g = (size_t)blockIdx.x * kCosetThreads + threadIdx.x;
+    if (g >= total) return;
+    uint32_t v[S], nx[S] = {};
+    {
+        const uint32_t* src = vals + ((g >> log_m) << log_len) + (g & (m - 1));
+#pragma unroll
+        for (int u = 0; u < S; ++u) v[u] = src[(size_t)u * m];
+    }
+    bool more;
+#pragma unroll 1
+    do {
+        const size_t gn = g + stride;
+        more = gn < total;
+        if (more) {
+            const uint32_t* src = vals + ((gn >> log_m) << log_len) + (gn & (m - 1));
+#pragma unroll
+            for (int u = 0; u < S; ++u) nx[u] = src[(size_t)u * m];
+        }
+        store_digest(nodes, total - 1 + g, coset_leaf_digest<HASH, S>(v));
+#pragma unroll
+        for (int u = 0; u < S; ++u) v[u] = nx[u];
+        g = gn;
+    } while (more);
+}
+template <int HASH>
+static void coset_leaf_batch_launch(const uint32_t* vals, uint32_t log_len, uint32_t steps, uint32_t log_batch, uint32_t* nodes, uint32_t blocks,
+                                    hipStream_t s) {
+    const dim3 g(blocks), b(kCosetThreads);
+    if (steps == 1) hipLaunchKernelGGL((coset_leaf_hash_batch_kernel<HASH, 1>), g, b, 0, s, vals, log_len, log_batch, nodes);
+    else if (steps == 2) hipLaunchKernelGGL((coset_leaf_hash_batch_kernel<HASH, 2>), g, b, 0, s, vals, log_len, log_batch, nodes);
+    else hipLaunchKernelGGL((coset_leaf_hash_batch_kernel<HASH, 3>), g, b, 0, s, vals, log_len, log_batch, nodes);
+}
+hipError_t launch_merkle_build_coset_batch(const uint32_t* vals, uint32_t log_len, uint32_t steps, uint32_t log_batch, uint32_t* nodes, hipStream_t s,
+                                           Profiler* prof, const MailArgs& mail, int hash) {
+    if (steps < 1 || steps > 3 || log_len <= steps || log_len + log_batch > 32) return hipErrorInvalidValue;
+    if (hash) {
+        hipError_t e = ensure_fieldhash_consts();
+        if (e != hipSuccess) return e;
+    }
+    const uint32_t log_m = log_len - steps + log_batch;          // leaves of the batch heap
+    const size_t leaves = (size_t)1 << log_m;
+    const size_t lanes = leaves > 4 * (size_t)kCosetThreads ? leaves / 4 : leaves;   // up to four leaves per lane, as the single launch
+    const uint32_t blocks = (uint32_t)((lanes + kCosetThreads - 1) / kCosetThreads);
+    {
+        ScopedKernelTimer tm(prof, K_MERKLE_LEAF, 4.0 * (double)((size_t)1 << (log_len + log_batch)) + 32.0 * (double)leaves, s,
+                             (double)leaves * (hash ? kFieldLeafOps : kShaLeafOps));
+        if (hash) coset_leaf_batch_launch<1>(vals, log_len, steps, log_batch, nodes, blocks, s);
+        else coset_leaf_batch_launch<0>(vals, log_len, steps, log_batch, nodes, blocks, s);
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    return merkle_build_t(PlainSrc{nullptr}, 0.0, log_m, nodes, s, prof, mail, hash, log_m, 0, false);   // mail.top: the per-proof roots or below
 }
 // commitment of a block whose leaves are still in all-to-all order (no interleave pass, no block buffer)
 hipError_t launch_merkle_build_interleaved(const uint32_t* recv, uint32_t log_parts, uint32_t log_cnt, uint32_t* nodes, hipStream_t s,

@@ -301,6 +301,15 @@ hipError_t launch_compose_merkle_batch(const ComposeBatchArgs& a, uint32_t log_b
 hipError_t launch_fold_merkle_batch(const FoldBatchArgs& a, uint32_t log_batch, uint32_t* nodes, hipStream_t s, Profiler* prof,
                                     const MailArgs& mail, int hash);
 
+// cp of the whole batch without a tree (coset leaves: the tree over cp is launch_merkle_build_coset_batch's): a.a.cp[b N + i], the
+// arithmetic of launch_compose_merkle_batch's leaf source
+hipError_t launch_compose_batch(const ComposeBatchArgs& a, uint32_t log_batch, hipStream_t s, Profiler* prof = nullptr);
+// Coset leaves over a proof-major batch (vals: [batch][2^log_len], steps 1..3 < log_len): proof p's tree has m = 2^(log_len - steps)
+// leaves, leaf c holding vals[(p << log_len) + c + u m], u < 2^steps; the trees are the bottom of one heap over batch * m leaves
+// (nodes: (2 batch m - 1) * 8 words) whose nodes of depth log_batch are the per-proof roots (mail.top as for the other batch builds).
+hipError_t launch_merkle_build_coset_batch(const uint32_t* vals, uint32_t log_len, uint32_t steps, uint32_t log_batch, uint32_t* nodes, hipStream_t s,
+                                           Profiler* prof, const MailArgs& mail, int hash);
+
 // batch traces of prover.rs:32-39, one lane per trace: out[t*stride + i], i < count (stride 0 = count)
 hipError_t launch_trace_fibsq_batch(const uint32_t* a0, const uint32_t* a1, uint32_t batch, uint32_t count, uint32_t* out, hipStream_t s,
                                     uint32_t stride = 0);

@@ -481,11 +481,12 @@ class BatchContext:
     """2^log_batch proofs of one size in lockstep (zk_batch_*): every stage is one
     launch over the whole batch; each proof has its own channel and is byte-identical to Context.prove()."""
 
-    def __init__(self, log_n=10, log_blowup=3, log_batch=4, device=0, hash="sha256", queries=1, grind_bits=0, fold_log=1):
+    def __init__(self, log_n=10, log_blowup=3, log_batch=4, device=0, hash="sha256", queries=1, grind_bits=0, fold_log=1, coset_leaves=False):
         """fold_log: FRI folding factor 2^fold_log between commitments for every proof of the batch (zk_batch_set_fold; 1 = the
-        reference)."""
+        reference).  coset_leaves: one coset per Merkle leaf of the FRI trees (zk_batch_set_coset_leaves)."""
         self.log_n, self.log_blowup, self.log_batch, self.hash, self.queries = log_n, log_blowup, log_batch, hash, queries
         self.grind_bits, self.fold_log = grind_bits, 1
+        self.coset_leaves = False
         self.n, self.batch = 1 << log_n, 1 << log_batch
         self._h = C.c_void_p()
         check(_lib.load().zk_batch_create(device, log_n, log_blowup, log_batch, C.byref(self._h)))
@@ -497,11 +498,23 @@ class BatchContext:
             check(_lib.load().zk_batch_set_grinding(self._h, grind_bits))
         if fold_log != 1:
             self.set_fold(fold_log)
+        if coset_leaves:
+            self.set_coset_leaves(True)
 
     def set_fold(self, fold_log):
         """zk_batch_set_fold: fold by 2^fold_log (1..3) between commitments from the next zk_batch_prove on."""
         check(_lib.load().zk_batch_set_fold(self._h, fold_log))
         self.fold_log = fold_log
+
+    def set_coset_leaves(self, on=True):
+        """zk_batch_set_coset_leaves: from the next zk_batch_prove on, a group opens one leaf of 2^steps values and one path."""
+        check(_lib.load().zk_batch_set_coset_leaves(self._h, int(bool(on))))
+        self.coset_leaves = bool(on)
+
+    @property
+    def proof_len(self):
+        fn = _lib.load().zk_proof_data_len_coset if self.coset_leaves else _lib.load().zk_proof_data_len_fold
+        return fn(self.log_n, self.log_blowup, self.queries, self.grind_bits, self.fold_log)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -535,14 +548,15 @@ class BatchContext:
         check(_lib.load().zk_batch_public_last(self._h, _ptr(out)))
         return out
 
-    def merkle_nodes(self, tree, first=0, count=None):
-        """Nodes of batch tree `tree`: a heap over batch * m_l leaves whose node 2^log_batch - 1 + p roots proof p's tree."""
-        m = (1 << (self.log_n + self.log_blowup)) >> max(tree - 1, 0)
+    def merkle_nodes(self, tree, first=0, count=None, coset_steps=0):
+        """Nodes of batch tree `tree`: a heap over batch * m_l leaves whose node 2^log_batch - 1 + p roots proof p's tree.
+        coset_steps: what the last proof built the tree with (m_l = layer_size >> coset_steps leaves per proof)."""
+        m = ((1 << (self.log_n + self.log_blowup)) >> max(tree - 1, 0)) >> coset_steps
         return _read_nodes(_lib.load().zk_batch_merkle_nodes, self._h, tree, 2 * m * self.batch - 1, first, count)
 
     def prove_raw(self):
         """Returns (proof bytes [batch][len] as a uint8 array, states [batch][32])."""
-        plen = _lib.load().zk_proof_data_len_fold(self.log_n, self.log_blowup, self.queries, self.grind_bits, self.fold_log)
+        plen = self.proof_len
         data = np.zeros((self.batch, plen), dtype=np.uint8)
         states = np.zeros((self.batch, 32), dtype=np.uint8)
         check(_lib.load().zk_batch_prove(self._h, data.ctypes.data_as(C.c_void_p), plen, states.ctypes.data_as(C.c_void_p)))
@@ -552,7 +566,7 @@ class BatchContext:
         data, states = self.prove_raw()
         last = self.public_last()
         return [Proof(states[p].tobytes(), data[p].tobytes(), self.log_n, self.log_blowup, int(last[p]), self.hash, self.queries,
-                      self.grind_bits, self.fold_log) for p in range(self.batch)]
+                      self.grind_bits, self.fold_log, self.coset_leaves) for p in range(self.batch)]
 
 
 _ERR_VERIFY = -6
