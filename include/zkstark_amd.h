@@ -203,6 +203,37 @@ uint32_t zk_ctx_get_fold(const zk_ctx *ctx);
  * NOT covered: zk_shard_* / zk_tail_* keep one-value leaves. */
 int zk_ctx_set_coset_leaves(zk_ctx *ctx, int on);
 int zk_ctx_get_coset_leaves(const zk_ctx *ctx);
+/* Early stop: stop_log = D, default 0 (with 0 every byte, launch and allocation is what it was; the reference folds down to a
+ * constant, prover.rs:198-254); valid with every fold_log, leaf format, hash, query count, grinding, zk_prove_channel and zk_prove_many.
+ * With D > 0 only the first R' = log_n - D rounds are folded, in the groups of R' (G' = ceil(R' / fold_log), the last possibly shorter).
+ * The output of the last group, layer id 1 + R', holds M = 2^(D + log_blowup) evaluations of a polynomial p of degree < 2^D at
+ * X_i = (w h^i)^(2^R'), natural order.  It is NOT committed as a tree: the prover sends the 2^D monomial coefficients of p in X.  Header, in
+ * wire order: f_root, alpha0..2, root0, then beta_j, root_{j+1} for j = 0 .. G'-2, then beta_{G'-1}, then c_0 .. c_{2^D - 1} (canonical
+ * residues, 4 bytes little-endian each, committed to the channel in ONE piece of 4 * 2^D bytes -- they take the place of the last root
+ * and the free term), then the nonce (searched on the state after the coefficients) and the query raws.  Per query exactly the tuples of
+ * the G' groups, plain or coset; with coset leaves the tree over the last group's input has that group's cosets as leaves, and no tree has
+ * the stopped layer's values as leaves.  Length: zk_proof_data_len_stop; verifier: zk_verify_stop.
+ * Limits: D <= 8, D <= log_n - 1 (at least one round is folded), D + log_blowup <= 12 (the stopped layer fits one workgroup's LDS);
+ * anything else is ZK_ERR_INVALID and the setting is unchanged.
+ * Soundness: a query still tests one coset per committed layer, and the degree bound of the final polynomial holds by construction --
+ * 2^D coefficients are a polynomial of degree < 2^D, where the reference's constant is one of degree < 1.
+ * The prover: fri_final_poly_kernel (one workgroup: inverse NTT of the M values in LDS, scaling by M^-1 s^-k, s = w^(2^R')) and one copy of
+ * 2^D + 1 words replace the D last fold + tree launches and the free term.  If a coefficient of degree >= 2^D is non-zero the proof fails
+ * with ZK_ERR_CHECK "final FRI layer has degree >= 2^D" (the analogue of the prover.rs:238 check).  With zk_ctx_set_checks the degree
+ * checkpoints run for the layers that exist.  With D > 0 every layer is a device layer and every fold_log, 1 without coset leaves too,
+ * takes the grouped round loop: the fold fused into leaf hashing, early launch and the host FRI tail do not apply
+ * (zk_ctx_get_early_launch answers 0) -- that is the price at large domains for fold_log 1.  zk_last_transcript: free_term = c_0,
+ * roots[1 + R'] and everything past it zero.  After a stopped proof zk_layer_read of an id beyond 1 + R', and zk_merkle_node(s) /
+ * zk_merkle_path of a tree id >= 1 + R' (layer 1 + R' has no tree), return ZK_ERR_STATE; a later D = 0 proof materialises everything again.
+ * Not run or timed on a GPU yet (tools/fri_stop_bench.py is the tool; DESIGN.md 7d "Early stop"): fold_log 1 without coset leaves may
+ * well be slower with D > 0 at large domains.
+ * NOT covered: the batched prover (zk_batch_*), the batched GPU verifier (zk_verifier_*), zk_shard_* and zk_tail_* keep folding down to
+ * a constant.
+ * zk_ctx_get_fri_stop: the current D, 0 for a null context.  zk_ctx_final_poly: the coefficients of the last proof (count <- their
+ * number; ZK_ERR_BUFFER if cap is smaller, ZK_ERR_STATE before the first proof); with D = 0 count is 1 and out[0] the free term. */
+int zk_ctx_set_fri_stop(zk_ctx *ctx, uint32_t stop_log);
+uint32_t zk_ctx_get_fri_stop(const zk_ctx *ctx);
+int zk_ctx_final_poly(const zk_ctx *ctx, uint32_t *out, size_t cap, size_t *count);
 /* The HIP stream every stage is enqueued on (hipStream_t). */
 void *zk_ctx_stream(zk_ctx *ctx);
 
@@ -233,6 +264,11 @@ int zk_fri_fold(zk_ctx *ctx, uint32_t round, uint32_t beta_raw);
 /* `steps` (1..3) successive folds with the challenges beta, beta^2, beta^4 in one pass (zk_ctx_set_fold):
  * layer 1+round+steps <- fold^steps(layer 1+round); round + steps <= log_n.  steps = 1 gives what zk_fri_fold gives. */
 int zk_fri_fold_multi(zk_ctx *ctx, uint32_t round, uint32_t steps, uint32_t beta_raw);
+/* The stage behind zk_ctx_set_fri_stop (fri_final_poly_kernel): FRI layer id `layer` >= 1, M = layer size <= 4096 values at
+ * X_i = (w h^i)^(2^(layer-1)).  coef_out[k], k < M <- the monomial coefficients in X of the polynomial of degree < M through them
+ * (canonical residues); *high_nonzero <- how many coefficients with k >= bound are non-zero (bound >= M: 0).  A larger layer or
+ * layer 0: ZK_ERR_INVALID; a layer the last proof did not materialise: ZK_ERR_STATE. */
+int zk_fri_final_poly(zk_ctx *ctx, uint32_t layer, uint32_t bound, uint32_t *coef_out, uint32_t *high_nonzero);
 /* Small device->host reads (decommit, tests). */
 int zk_layer_read(zk_ctx *ctx, uint32_t layer, size_t offset, size_t count, uint32_t *out);
 int zk_layer_write(zk_ctx *ctx, uint32_t layer, size_t offset, size_t count, const uint32_t *in);
@@ -403,6 +439,11 @@ size_t zk_proof_data_len_fold(uint32_t log_n, uint32_t log_blowup, uint32_t n_qu
 /* Proofs made with zk_ctx_set_coset_leaves: 32 + 12 + 32 + 36 G + 4 + (grind ? 8 : 0) + q (4 + 3 (12 + 32 L) + sum over the groups of
  * 4 s + 8 + 32 (L - r0 - steps)), s = 2^steps.  0 for a fold_log outside 1..3. */
 size_t zk_proof_data_len_coset(uint32_t log_n, uint32_t log_blowup, uint32_t n_queries, uint32_t grind_bits, uint32_t fold_log);
+/* Proofs made with zk_ctx_set_fri_stop(stop_log = D): 32 + 12 + 32 + 36 (G' - 1) + 4 + 4 * 2^D + (grind ? 8 : 0) + q (per-query bytes of
+ * zk_proof_data_len_fold, or _coset when coset_leaves != 0, summed over the G' groups of log_n - D rounds only).  stop_log = 0: what
+ * zk_proof_data_len_fold / _coset return.  0 for a fold_log outside 1..3 or a stop_log outside the limits of zk_ctx_set_fri_stop. */
+size_t zk_proof_data_len_stop(uint32_t log_n, uint32_t log_blowup, uint32_t n_queries, uint32_t grind_bits, uint32_t fold_log,
+                              int coset_leaves, uint32_t stop_log);
 /* Proof-of-work search (zk_ctx_set_grinding): the smallest nonce >= start whose SHA-256(state || le64(nonce)) begins with
  * grind_bits zero bits (0..32; 0 gives start), on the GPU (zk_grind) or on <= 16 host threads (zk_grind_host; threads is
  * clamped to 1..16).  Gives up with an error naming grind_bits after 2^44 nonces.  A zk_channel user grinds on
@@ -448,6 +489,18 @@ int zk_verify_fold(const uint8_t *proof, size_t len, const uint8_t *state, uint3
  * query three f tuples and one tuple per group.  A plain proof is rejected by length (-1), as a coset proof is by zk_verify_fold. */
 int zk_verify_coset(const uint8_t *proof, size_t len, const uint8_t *state, uint32_t log_n, uint32_t log_blowup,
                     uint32_t public_last, int hash_kind, uint32_t n_queries, uint32_t grind_bits, uint32_t fold_log, int32_t *check_out);
+
+/* zk_verify_fold (coset_leaves = 0) / zk_verify_coset (coset_leaves != 0) for proofs made with zk_ctx_set_fri_stop(stop_log = D), over
+ * the G' groups of log_n - D rounds.  The last group's comparison "folded value == free term" becomes "== p(x^(2^R'))": p is evaluated by
+ * Horner from the 2^D coefficients, each reduced mod P on reading, as raw challenges are; it keeps the check number -(100 + (G' - 1)).
+ * The strict replay counts 3 + G' + q challenges, commits the coefficients in one piece and checks the nonce after them.  A proof whose
+ * length is not zk_proof_data_len_stop of the arguments is rejected with -1, strict or not, and so is a stop_log outside the limits.
+ * Soundness: one coset per committed layer is tested per query as before; the final polynomial's degree bound holds by construction.
+ * stop_log = 0 gives every input the number zk_verify_fold / zk_verify_coset gives it (the same code path).
+ * NOT covered: zk_verifier_* checks only proofs folded down to a constant. */
+int zk_verify_stop(const uint8_t *proof, size_t len, const uint8_t *state, uint32_t log_n, uint32_t log_blowup, uint32_t public_last,
+                   int hash_kind, uint32_t n_queries, uint32_t grind_bits, uint32_t fold_log, int coset_leaves, uint32_t stop_log,
+                   int32_t *check_out);
 
 /* A verifier for many proofs of one size (log_n, log_blowup: the sizes zk_verify_queries accepts).  It owns its streams and
  * device buffers (grown on demand) and a pinned staging buffer.  One verifier is used from one host thread at a time. */

@@ -144,6 +144,12 @@ SYMBOLS = {
     "zk_verify_coset": (_int, [_vp, _sz, _vp, _u32, _u32, _u32, _int, _u32, _u32, _u32, C.POINTER(C.c_int32)]),
     "zk_compute_root_from_coset": (_int, [_vp, _u32, _sz, _vp, _sz, _vp, _int]),
     "zk_fri_fold_multi": (_int, [_vp, _u32, _u32, _u32]),
+    "zk_ctx_set_fri_stop": (_int, [_vp, _u32]),
+    "zk_ctx_get_fri_stop": (_u32, [_vp]),
+    "zk_ctx_final_poly": (_int, [_vp, _vp, _sz, C.POINTER(_sz)]),
+    "zk_fri_final_poly": (_int, [_vp, _u32, _u32, _vp, C.POINTER(_u32)]),
+    "zk_proof_data_len_stop": (_sz, [_u32, _u32, _u32, _u32, _u32, _int, _u32]),
+    "zk_verify_stop": (_int, [_vp, _sz, _vp, _u32, _u32, _u32, _int, _u32, _u32, _u32, _int, _u32, C.POINTER(C.c_int32)]),
     "zk_dev_fri_fold_multi": (_int, [_vp, _vp, _vp, _u32, _u32, _u32, _u32, _vp]),
     "zk_dev_fri_fold_multi_batch": (_int, [_vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _u32, _vp]),
     "zk_batch_set_fold": (_int, [_vp, _u32]),

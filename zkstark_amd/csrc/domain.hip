@@ -295,6 +295,21 @@ int dom_fold_multi(const zk_dom* d, const uint32_t* d_in, uint32_t* d_out, uint3
     return ZK_OK;
 }
 
+// FRI layer `round` (2^log_m <= 4096 values at (shift h^i)^(2^round)) -> d_out[0] = non-zero coefficients of degree >= bound,
+// d_out[1 + k] = coefficient k of its interpolant in X, k < 2^log_m (FinalPolyArgs); `polys` layers / outputs in_stride / out_stride apart
+int dom_final_poly(const zk_dom* d, const uint32_t* d_in, uint32_t* d_out, uint32_t log_m, uint32_t round, uint32_t bound, hipStream_t s,
+                   Profiler* prof, uint32_t polys, size_t in_stride, size_t out_stride) {
+    if (log_m < 1 || log_m > kFinalPolyMaxLog || log_m + round != d->L)
+        return fail(ZK_ERR_INVALID, "final polynomial: layer size 2^%u does not match round %u of a 2^%u domain, or exceeds 2^%u values", log_m, round, d->L, kFinalPolyMaxLog);
+    FinalPolyArgs a{};
+    a.in = d_in; a.out = d_out; a.in_stride = in_stride; a.out_stride = out_stride; a.polys = polys;
+    a.log_m = log_m; a.bound = bound;
+    a.hinv = d->Hinv.view(); a.L = d->L;
+    a.minv_mont = to_mont(invmod(1u << log_m));
+    a.sinv_mont = to_mont(mulmod(d->fold_k[round], 2));      // w^(-2^r)
+    HIPCHK(launch_fri_final_poly(a, s, prof));
+    return ZK_OK;
+}
 
 // Waits until the mailbox carries the sequence number of the last commit launch (polling host-coherent
 // memory: no blit kernel, no stream synchronisation on the commit -> challenge path).

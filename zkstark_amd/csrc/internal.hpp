@@ -181,6 +181,10 @@ int fold_multi_args(const zk_dom* d, const uint32_t* d_in, uint32_t* d_out, uint
                     FoldMultiArgs& a);
 int dom_fold_multi(const zk_dom* d, const uint32_t* d_in, uint32_t* d_out, uint32_t log_m, uint32_t round, uint32_t steps, uint32_t beta_raw,
                    hipStream_t s, Profiler* prof = nullptr);
+// The interpolant of FRI layer 1 + round (2^log_m <= 4096 values) as monomial coefficients: d_out[1 + k] = c_k, d_out[0] = how many
+// c_k with k >= bound are non-zero (fri_final_poly_kernel); polys > 1: one workgroup per layer, strides in words
+int dom_final_poly(const zk_dom* d, const uint32_t* d_in, uint32_t* d_out, uint32_t log_m, uint32_t round, uint32_t bound, hipStream_t s,
+                   Profiler* prof = nullptr, uint32_t polys = 1, size_t in_stride = 0, size_t out_stride = 0);
 // ... over a proof-major batch ([batch][2^log_m] -> [batch][2^(log_m - steps)]), proof b with the raw challenge
 // d_beta_raw[b * beta_stride] (device memory); d_work: 8 * batch words of device scratch.  Two launches, nothing else.
 int fold_multi_batch_args(const zk_dom* d, const uint32_t* d_in, uint32_t* d_out, uint32_t log_m, uint32_t round, uint32_t steps,

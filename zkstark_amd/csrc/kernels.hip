@@ -4,6 +4,7 @@
 //                        and polynomial.rs:49-56 solve as used at prover.rs:60-70)
 //   compose_kernel       pointwise constraint composition (prover.rs:101-173)
 //   fri_fold_kernel      evaluation-form FRI fold (polynomial.rs:385-400 + prover.rs:204-211)
+//   fri_final_poly_kernel  coefficients of the layer an early-stopped FRI ends at (one workgroup, inverse NTT in LDS)
 //   merkle_*_kernel      SHA-256 Merkle heap (merkle.rs:14-51)
 //   gather_kernel        decommitment gather (merkle.rs:54-71, prover.rs:266-289)
 //
@@ -676,6 +677,59 @@ hipError_t launch_fri_fold_multi_batch(const FoldMultiBatchArgs& p, hipStream_t 
     if (a.steps == 1) fold_multi_batch_launch<1>(p, total, wide, s);
     else if (a.steps == 2) fold_multi_batch_launch<2>(p, total, wide, s);
     else fold_multi_batch_launch<3>(p, total, wide, s);
+    return hipGetLastError();
+}
+
+// ---- final polynomial of an early-stopped FRI (FinalPolyArgs) ------------------------------------------------------------------
+// One workgroup holds the M <= 4096 values and the M / 2 twiddles w_M^-j in LDS (24 KiB), runs the log2 M radix-2 stages of the
+// decimation-in-frequency inverse transform there (natural order in, bit-reversed out: position p ends as M q_bitrev(p), q(y) = p(s y))
+// and writes c_k = q_k s^-k in natural order.  It sits on the proof's critical path once, so it is built for latency: up to 1024 lanes
+// (two butterflies per lane and stage at M = 4096), the twiddles looked up once, nothing but LDS traffic between the barriers.  M may
+// be smaller than the workgroup (M = 4: two butterflies); every barrier is outside the divergent loops.
+constexpr uint32_t kFinalPolyThreads = 1024;
+__global__ __launch_bounds__(kFinalPolyThreads) void fri_final_poly_kernel(FinalPolyArgs a) {
+    __shared__ uint32_t x[1u << kFinalPolyMaxLog];
+    __shared__ uint32_t tw[1u << (kFinalPolyMaxLog - 1)];
+    __shared__ uint32_t high;
+    const uint32_t M = 1u << a.log_m, pairs = M >> 1, tid = threadIdx.x, nt = blockDim.x;
+    const uint32_t* in = a.in + (size_t)blockIdx.x * a.in_stride;
+    uint32_t* out = a.out + (size_t)blockIdx.x * a.out_stride;
+    if (tid == 0) high = 0;
+    for (uint32_t i = tid; i < M; i += nt) x[i] = in[i];
+    for (uint32_t j = tid; j < pairs; j += nt) tw[j] = pow_lookup(a.hinv, j << (a.L - a.log_m));
+    __syncthreads();
+    for (uint32_t lh = a.log_m; lh-- > 0; ) {                  // blocks of 2 * half values, twiddle w_(2 half)^-j = tw[j M / (2 half)]
+        const uint32_t half = 1u << lh, tsh = a.log_m - 1 - lh;
+        for (uint32_t b = tid; b < pairs; b += nt) {
+            const uint32_t j = b & (half - 1), i0 = ((b - j) << 1) + j;
+            const uint32_t u = x[i0], v = x[i0 + half];
+            x[i0] = add(u, v);
+            x[i0 + half] = mont_mul(sub(u, v), tw[j << tsh]);
+        }
+        __syncthreads();
+    }
+    uint32_t cnt = 0;
+    for (uint32_t k = tid; k < M; k += nt) {
+        uint32_t r = a.minv_mont, sp = a.sinv_mont;            // M^-1 s^-k by the bits of k (at most 12 steps)
+        for (uint32_t e = k; e; e >>= 1) {
+            if (e & 1) r = mont_mul(r, sp);
+            sp = mont_mul(sp, sp);
+        }
+        const uint32_t c = mont_mul(x[__brev(k) >> (32 - a.log_m)], r);
+        out[1 + k] = c;
+        cnt += (k >= a.bound && c != 0) ? 1u : 0u;
+    }
+    if (cnt) atomicAdd(&high, cnt);                            // the one add: into LDS
+    __syncthreads();
+    if (tid == 0) out[0] = high;
+}
+hipError_t launch_fri_final_poly(const FinalPolyArgs& a, hipStream_t s, Profiler* prof) {
+    if (a.log_m < 1 || a.log_m > kFinalPolyMaxLog || a.log_m > a.L || a.polys < 1 || !a.in || !a.out) return hipErrorInvalidValue;
+    const uint32_t M = 1u << a.log_m;
+    if (a.polys > 1 && (a.in_stride < M || a.out_stride < (size_t)M + 1)) return hipErrorInvalidValue;
+    ScopedKernelTimer tm(prof, K_FOLD, 4.0 * (double)a.polys * (double)(2 * M + 1), s);   // read M words, write M + 1
+    const uint32_t threads = M / 2 >= kFinalPolyThreads ? kFinalPolyThreads : (M / 2 <= 64 ? 64 : M / 2);
+    hipLaunchKernelGGL(fri_final_poly_kernel, dim3(a.polys), dim3(threads), 0, s, a);
     return hipGetLastError();
 }
 

@@ -237,6 +237,24 @@ struct FoldMultiBatchArgs {
 };
 hipError_t launch_fri_fold_multi_batch(const FoldMultiBatchArgs& a, hipStream_t s, Profiler* prof = nullptr);
 
+// The final polynomial of a proof that stops FRI early (transcript.hpp "stop"; DESIGN.md 7d "Early stop"): in = the M = 2^log_m <= 4096
+// evaluations of p at s w_M^i, i < M, natural order (w_M = the table root ^ (2^(L - log_m)), s the coset shift); out[1 + k] = the monomial
+// coefficient c_k of p, k < M (canonical), out[0] = the number of non-zero c_k with k >= bound.  One workgroup per polynomial:
+// polynomial b reads in + b * in_stride and writes out + b * out_stride (M + 1 words), so a batch is one launch.
+constexpr uint32_t kFinalPolyMaxLog = 12;
+struct FinalPolyArgs {
+    const uint32_t* in;
+    uint32_t* out;
+    size_t in_stride, out_stride;   // in words
+    uint32_t polys;
+    uint32_t log_m, bound;
+    PowTable hinv;                  // h^-1 table, order 2^L
+    uint32_t L;
+    uint32_t minv_mont;             // 1 / M
+    uint32_t sinv_mont;             // 1 / s
+};
+hipError_t launch_fri_final_poly(const FinalPolyArgs& a, hipStream_t s, Profiler* prof = nullptr);
+
 // Merkle tree over m = 2^log_m u32 leaves.  nodes: (2m-1) * 8 words, heap order
 // (merkle.rs:14-51), each node the eight SHA-256 state words.
 // mail (optional): where the result of the build is posted for the host, see MailArgs.

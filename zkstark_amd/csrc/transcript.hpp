@@ -89,7 +89,19 @@ struct Channel {
 // the tree over the last layer (id 1 + log_n, never opened) keep one-value leaves.  Per query the three f tuples are sent as ever;
 // the separate cp(x) tuple is dropped (group 0's leaf contains it), then per group the s slot values in slot order, a u64 count and
 // the path.  With rot = (x % len) / (len / s), value t of the group (the one at (x % len + t len / s) % len) is slot (rot + t) % s.
+// stop = D in 0..kMaxStopLog is the early stop (DESIGN.md 7d "Early stop"; 0 = fold down to a constant, the format above).  Only the
+// first R' = log_n - D rounds are folded, in the groups of R' (G' of them); the output of the last group, layer id 1 + R', holds
+// M = 2^(D + log_b) evaluations of a polynomial p of degree < 2^D at X_i = (w h^i)^(2^R').  It gets no tree: in place of the last root
+// and the free term the header carries the 2^D monomial coefficients of p in X (canonical residues, 4 bytes little-endian each,
+// ONE commit), then the nonce and the query raws as ever.  Per query the tuples of the G' groups are sent unchanged, and the last
+// group's fold is compared with p(x^(2^R')), evaluated by Horner.  A query still tests one coset per committed layer, and the
+// degree bound of the final polynomial holds by construction (2^D coefficients ARE a polynomial of degree < 2^D).
 constexpr uint32_t kMaxFoldLog = 3;
+constexpr uint32_t kMaxStopLog = 8, kMaxStopLayerLog = 12;   // the stopped layer (2^(D + log_b) values) fits one workgroup's LDS
+// D = 0, or 1 <= D <= 8 with at least one folded round and a stopped layer of at most 2^12 values
+inline bool stop_ok(uint32_t log_n, uint32_t log_b, uint32_t stop) {
+    return stop == 0 || (stop <= kMaxStopLog && stop + 1 <= log_n && stop + log_b <= kMaxStopLayerLog);
+}
 inline uint32_t fold_groups(uint32_t R, uint32_t fold) { return (R + fold - 1) / fold; }
 inline uint32_t fold_steps(uint32_t R, uint32_t fold, uint32_t group) { const uint32_t r0 = group * fold; return R - r0 < fold ? R - r0 : fold; }
 // Leaf t of the coset a group with `steps` rounds opens in its input layer of 2^log_len values, for the query index x.
@@ -102,26 +114,30 @@ inline size_t coset_leaf(size_t x, uint32_t log_len, uint32_t steps, uint32_t t)
 // An opening is one LEAF and its path: open(layer id, log2 of the tree's leaf count = digests of the path, leaf index, slots_log);
 // the leaf holds the 2^slots_log values layer[leaf + u 2^(log2 leaf count)], u < 2^slots_log (0: a one-value leaf).
 // coset: no cp opening, and a group is one leaf of s slots.
-template <class Open> inline void for_each_opening(uint32_t log_n, uint32_t log_b, uint32_t fold, size_t x, Open open, bool coset = false) {
-    const uint32_t L = log_n + log_b, G = fold_groups(log_n, fold);
+// stop: only the groups of the log_n - stop folded rounds are opened.
+template <class Open> inline void for_each_opening(uint32_t log_n, uint32_t log_b, uint32_t fold, size_t x, Open open, bool coset = false, uint32_t stop = 0) {
+    const uint32_t L = log_n + log_b, Rp = log_n - stop, G = fold_groups(Rp, fold);
     const size_t B = (size_t)1 << log_b;
     open(0u, L, x, 0u); open(0u, L, x + B, 0u); open(0u, L, x + 2 * B, 0u);
     if (!coset) open(1u, L, x, 0u);
     for (uint32_t j = 0; j < G; ++j) {
-        const uint32_t r0 = j * fold, steps = fold_steps(log_n, fold, j);
+        const uint32_t r0 = j * fold, steps = fold_steps(Rp, fold, j);
         if (coset) open(1u + r0, L - r0 - steps, x % ((size_t)1 << (L - r0 - steps)), steps);
         else for (uint32_t t = 0; t < (1u << steps); ++t) open(1u + r0, L - r0, coset_leaf(x, L - r0, steps, t), 0u);
     }
 }
-// fold must be in 1..kMaxFoldLog (the callers check it).
-inline size_t proof_data_len(uint32_t log_n, uint32_t log_b, uint32_t q = 1, uint32_t grind = 0, uint32_t fold = 1, bool coset = false) {
-    const size_t L = log_n + log_b, G = fold_groups(log_n, fold);
+// fold must be in 1..kMaxFoldLog and stop_ok(log_n, log_b, stop) must hold (the callers check both).
+inline size_t proof_data_len(uint32_t log_n, uint32_t log_b, uint32_t q = 1, uint32_t grind = 0, uint32_t fold = 1, bool coset = false, uint32_t stop = 0) {
+    const uint32_t Rp = log_n - stop;
+    const size_t L = log_n + log_b, G = fold_groups(Rp, fold);
     size_t per_query = 4 + (coset ? 3 : 4) * Channel::group_bytes(1, L);
     for (uint32_t j = 0; j < G; ++j) {
-        const size_t steps = fold_steps(log_n, fold, j);
+        const size_t steps = fold_steps(Rp, fold, j);
         per_query += Channel::group_bytes((size_t)1 << steps, L - (size_t)j * fold - (coset ? steps : 0), coset);
     }
-    return 32 + 12 + 32 + G * 36 + 4 + (grind ? 8 : 0) + (size_t)q * per_query;
+    // stop > 0: the last root and the free term give way to the 2^stop coefficients
+    const size_t head = stop ? 32 + 12 + 32 + (G - 1) * 36 + 4 + ((size_t)4 << stop) : 32 + 12 + 32 + G * 36 + 4;
+    return head + (grind ? 8 : 0) + (size_t)q * per_query;
 }
 
 // ---- grinding (DESIGN.md "Grinding"; the reference has none) -------------------------------------------------------------
@@ -209,12 +225,18 @@ inline void compute_root_from_path(uint32_t element, size_t index, const uint8_t
 // one path length -(200+j) and one path -(300+j).
 // grind > 0: the nonce after the free term is skipped.  Its work is a property of the Fiat-Shamir transcript, which only
 // verify_transcript replays; here the query raws are read from the proof (as the reference does), so checking it certifies nothing.
+// stop > 0 (early stop, above): the groups are those of log_n - stop rounds, the header ends with the 2^stop coefficients in place of
+// the last root and the free term, and the last group's fold -(100 + (G' - 1)) is compared with p(x^(2^R')) -- Horner over the
+// coefficients, each reduced % P on reading, as raw challenges are.
 inline int verify_proof(const uint8_t* data, size_t len, uint32_t log_n, uint32_t log_b, uint32_t public_last, int hash = 0, uint32_t q = 1,
-                        uint32_t grind = 0, uint32_t fold = 1, bool coset = false) {
+                        uint32_t grind = 0, uint32_t fold = 1, bool coset = false, uint32_t stop = 0) {
     if (log_n < 2 || log_b < 1 || log_n + log_b > 30 || q < 1 || q > 64 || grind > kMaxGrindBits || fold < 1 || fold > kMaxFoldLog) return -1;
+    if (!stop_ok(log_n, log_b, stop)) return -1;
+    if (stop && len != proof_data_len(log_n, log_b, q, grind, fold, coset, stop)) return -1;   // a stopped proof of another length: -1, strict or not
+    const uint32_t Rp = log_n - stop;
     const int nf = coset ? 3 : 4;                            // f(x), f(gx), f(g^2 x) and, with one-value leaves, cp(x)
     const size_t n = (size_t)1 << log_n, B = (size_t)1 << log_b, N = n << log_b, L = log_n + log_b;
-    const uint32_t G = fold_groups(log_n, fold);
+    const uint32_t G = fold_groups(Rp, fold);
     const uint8_t* p = data;
     size_t left = len;
     bool bad = false;
@@ -240,8 +262,9 @@ inline int verify_proof(const uint8_t* data, size_t len, uint32_t log_n, uint32_
     uint32_t alpha[3] = {take32(), take32(), take32()};
     const uint8_t* roots[40]; uint32_t betas[40];            // roots[j]: the tree over the INPUT layer of group j (roots[G]: the last layer)
     roots[0] = take(32);
-    for (uint32_t j = 0; j < G; ++j) { betas[j] = take32(); roots[j + 1] = take(32); }
-    uint32_t free_term = take32();
+    for (uint32_t j = 0; j < G; ++j) { betas[j] = take32(); roots[j + 1] = (stop && j + 1 == G) ? nullptr : take(32); }
+    const uint8_t* coefs = stop ? take((size_t)4 << stop) : nullptr;
+    uint32_t free_term = stop ? 0 : take32();
     if (grind) take(8);                                   // the nonce
     uint32_t test_raws[64];
     for (uint32_t k = 0; k < q; ++k) test_raws[k] = take32();
@@ -252,7 +275,7 @@ inline int verify_proof(const uint8_t* data, size_t len, uint32_t log_n, uint32_
         for (int i = 0; i < nf; ++i) { fv[i] = take32(); fp[i] = take_path(fpl[i]); }
         uint32_t lv[40][8]; const uint8_t* lp[40][8]; size_t lpl[40][8];
         for (uint32_t j = 0; j < G; ++j) {
-            const uint32_t s = 1u << fold_steps(log_n, fold, j);
+            const uint32_t s = 1u << fold_steps(Rp, fold, j);
             for (uint32_t t = 0; t < s; ++t) lv[j][t] = take32();
             for (uint32_t t = 0; t < (coset ? 1u : s); ++t) { lpl[j][t] = 0; lp[j][t] = take_path(lpl[j][t]); }
         }
@@ -262,7 +285,7 @@ inline int verify_proof(const uint8_t* data, size_t len, uint32_t log_n, uint32_
         // value t of group j: as sent, or slot (rot + t) % s of the group's leaf
         auto group_val = [&](uint32_t j, uint32_t t) -> uint32_t {
             if (!coset) return lv[j][t];
-            const uint32_t steps = fold_steps(log_n, fold, j), lg = (uint32_t)L - j * fold;
+            const uint32_t steps = fold_steps(Rp, fold, j), lg = (uint32_t)L - j * fold;
             const size_t rot = (tp & (((size_t)1 << lg) - 1)) >> (lg - steps);
             return lv[j][(rot + t) & ((1u << steps) - 1u)];
         };
@@ -289,7 +312,7 @@ inline int verify_proof(const uint8_t* data, size_t len, uint32_t log_n, uint32_
         // proof.rs:101-126: the s opened values of a group folded pairwise (t with t + s/2, then again)
         const uint32_t inv2 = invmod(2);
         for (uint32_t j = 0; j < G; ++j) {
-            const uint32_t r0 = j * fold, steps = fold_steps(log_n, fold, j);
+            const uint32_t r0 = j * fold, steps = fold_steps(Rp, fold, j);
             uint32_t cnt = 1u << steps, v[8];
             for (uint32_t t = 0; t < cnt; ++t) v[t] = group_val(j, t) % P;
             uint32_t xk = powmod(x, (uint64_t)1 << r0);                        // the point of index tp % len in layer r0
@@ -306,12 +329,21 @@ inline int verify_proof(const uint8_t* data, size_t len, uint32_t log_n, uint32_
                 }
                 xk = mulmod(xk, xk); om = mulmod(om, om); bk = mulmod(bk, bk);
             }
-            const uint32_t expect = (j + 1 < G) ? group_val(j + 1, 0) : free_term;
+            uint32_t expect = (j + 1 < G) ? group_val(j + 1, 0) : free_term;
+            if (stop && j + 1 == G) {                                          // p at the point of the stopped layer, x^(2^R')
+                const uint32_t xs = powmod(x, (uint64_t)1 << Rp);
+                expect = 0;
+                for (size_t k = (size_t)1 << stop; k-- > 0; ) {
+                    const uint8_t* cb = coefs + 4 * k;
+                    const uint32_t ck = ((uint32_t)cb[0] | ((uint32_t)cb[1] << 8) | ((uint32_t)cb[2] << 16) | ((uint32_t)cb[3] << 24)) % P;
+                    expect = add(mulmod(expect, xs), ck);
+                }
+            }
             if (v[0] != expect) return -(int)(100 + j);
         }
         // proof.rs:129-148
         for (uint32_t j = 0; j < G; ++j) {
-            const uint32_t r0 = j * fold, steps = fold_steps(log_n, fold, j), s = 1u << steps;
+            const uint32_t r0 = j * fold, steps = fold_steps(Rp, fold, j), s = 1u << steps;
             if (coset) {
                 if (lpl[j][0] != L - r0 - steps) return -(int)(200 + j);
                 compute_root_from_coset(lv[j], s, tp & (((size_t)1 << (L - r0 - steps)) - 1), lp[j][0], lpl[j][0], root, hash);
@@ -337,12 +369,14 @@ inline int verify_proof(const uint8_t* data, size_t len, uint32_t log_n, uint32_
 // challenge equals the one the transcript yields at that point and that the final state matches.  There are 3 + G + q challenges.
 // Returns 0, or -(1000 + k) for the k-th challenge / -1998 for a grinding nonce whose hash has fewer than `grind` leading zero
 // bits (checked after the betas and before the first query challenge; it does not advance k) / -1999 for the state.
+// stop > 0: 3 + G' + q challenges; the coefficients are one commit, in the place of the last root and the free term.
 inline int verify_transcript(const uint8_t* data, size_t len, const uint8_t state[32], uint32_t log_n, uint32_t log_b, uint32_t q = 1,
-                             uint32_t grind = 0, uint32_t fold = 1, bool coset = false) {
+                             uint32_t grind = 0, uint32_t fold = 1, bool coset = false, uint32_t stop = 0) {
     if (log_n < 2 || log_b < 1 || log_n + log_b > 30 || grind > kMaxGrindBits || fold < 1 || fold > kMaxFoldLog) return -1;
+    if (!stop_ok(log_n, log_b, stop)) return -1;
     const size_t L = log_n + log_b;
-    const uint32_t G = fold_groups(log_n, fold);
-    if (q < 1 || q > 64 || len != proof_data_len(log_n, log_b, q, grind, fold, coset)) return -1;
+    const uint32_t Rp = log_n - stop, G = fold_groups(Rp, fold);
+    if (q < 1 || q > 64 || len != proof_data_len(log_n, log_b, q, grind, fold, coset, stop)) return -1;
     Channel ch;
     const uint8_t* p = data;
     int k = 0;
@@ -360,9 +394,9 @@ inline int verify_transcript(const uint8_t* data, size_t len, const uint8_t stat
     commit(32);                                             // cp root
     for (uint32_t j = 0; j < G; ++j) {
         if (!challenge()) return -(1000 + k);               // the group's beta
-        commit(32);                                         // root of the group's output
+        if (!stop || j + 1 < G) commit(32);                 // root of the group's output
     }
-    commit(4);                                              // free term
+    commit(stop ? (size_t)4 << stop : 4);                   // free term, or the final polynomial's coefficients
     if (grind) {                                            // nonce: the commit is SHA-256(S || le64(w))
         commit(8);
         const uint32_t w0 = ((uint32_t)ch.state[0] << 24) | ((uint32_t)ch.state[1] << 16) | ((uint32_t)ch.state[2] << 8) | ch.state[3];
@@ -372,7 +406,7 @@ inline int verify_transcript(const uint8_t* data, size_t len, const uint8_t stat
     for (uint32_t j = 0; j < q; ++j) {
         for (int i = 0; i < (coset ? 3 : 4); ++i) commit(Channel::group_bytes(1, L));
         for (uint32_t gi = 0; gi < G; ++gi) {
-            const size_t steps = fold_steps(log_n, fold, gi);
+            const size_t steps = fold_steps(Rp, fold, gi);
             commit(Channel::group_bytes((size_t)1 << steps, L - (size_t)gi * fold - (coset ? steps : 0), coset));
         }
     }

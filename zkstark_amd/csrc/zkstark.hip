@@ -120,6 +120,11 @@ struct zk_ctx {
     // tree_steps[t]: tree t as it lies in d_trees has 2^tree_steps[t] values per leaf (0: one-value leaves), set by whatever built it
     bool coset = false;
     uint8_t tree_steps[40] = {};
+    // Early stop (zk_ctx_set_fri_stop; transcript.hpp): only the first R - stop rounds are folded; the last group's output gets no tree,
+    // its 2^stop coefficients (fri_final_poly_kernel -> d_final: one count word, then the coefficients) are committed instead
+    uint32_t stop = 0;
+    uint32_t* d_final = nullptr;        // 1 + 2^kFinalPolyMaxLog words, allocated by the first call that needs it
+    std::vector<uint32_t> final_poly;   // the last proof's coefficients (stop = 0: the free term)
     int hash = 0;                      // Merkle hash: 0 = SHA-256 (reference), 1 = field-native (configs[4])
     // opt-in reference self-checks (zk_ctx_set_checks; prover.rs:64-66, :148-159, :169, :228-251)
     bool checks = false;
@@ -205,7 +210,7 @@ MailArgs mail_of(zk_ctx* c, uint32_t tree, bool host, bool feed_tail = true, uin
     c->tree_seq[tree] = m.seq;
     m.counter = c->d_counter;
     m.top = host ? top_of(c, tree) : 0;
-    if (feed_tail && c->fold == 1 && !c->coset && m.top && c->host_tail && tree >= 1 && layer_log(c, tree) == c->host_tail + 1) {
+    if (feed_tail && c->fold == 1 && !c->coset && !c->stop && m.top && c->host_tail && tree >= 1 && layer_log(c, tree) == c->host_tail + 1) {
         m.dump_src = c->d_layers + c->layer_off[tree];
         m.dump_log = c->host_tail + 1;
         m.vals_off = (uint32_t)kMailValsOff;
@@ -345,7 +350,7 @@ int fri_round_commit(zk_ctx* c, uint32_t round, uint32_t beta_raw, uint8_t root[
 bool round_on_host(const zk_ctx* c, uint32_t round) {
     return c->hash == 0 && c->host_top && c->host_tail && c->L >= c->host_tail + 1 && c->L - round <= c->host_tail + 1;
 }
-bool can_gate(const zk_ctx* c, uint32_t round) { return c->fold == 1 && !c->coset && c->early && c->early_ok && !c->checks && round < c->R && !round_on_host(c, round); }
+bool can_gate(const zk_ctx* c, uint32_t round) { return c->fold == 1 && !c->coset && !c->stop && c->early && c->early_ok && !c->checks && round < c->R && !round_on_host(c, round); }
 // The launches of do_fold_commit(round), enqueued behind a wait on the gate word; their one challenge-dependent constant is read
 // from a parameter slot the host fills in release_gated_fold.
 int enqueue_gated_fold(zk_ctx* c, uint32_t round) {
@@ -403,6 +408,25 @@ int last_layer_value(zk_ctx* c, uint32_t* out) {
     for (size_t i = 1; i < c->B; ++i)
         if (v[i] != v[0]) return fail(ZK_ERR_CHECK, "last FRI layer is not constant (prover.rs:238): trace does not satisfy the constraints");
     *out = v[0];
+    return ZK_OK;
+}
+
+int final_alloc(zk_ctx* c) {
+    return c->d_final ? (int)ZK_OK : dmalloc(c, &c->d_final, (((size_t)1 << kFinalPolyMaxLog) + 1) * 4);
+}
+// Early stop: the 2^stop coefficients of the polynomial layer 1 + R - stop evaluates, through one launch and one small copy; the
+// analogue of the prover.rs:238 check is that every coefficient of degree >= 2^stop is zero.
+int final_poly_value(zk_ctx* c) {
+    const uint32_t Rp = c->R - c->stop;
+    const size_t cnt = (size_t)1 << c->stop;
+    int rc = final_alloc(c);
+    if (rc) return rc;
+    if ((rc = dom_final_poly(c->dom, c->d_layers + c->layer_off[1 + Rp], c->d_final, c->L - Rp, Rp, (uint32_t)cnt, c->stream, prof_of(c)))) return rc;
+    HIPCHK(hipMemcpyAsync(c->h_small, c->d_final, (cnt + 1) * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (c->h_small[0])
+        return fail(ZK_ERR_CHECK, "final FRI layer has degree >= 2^%u: trace does not satisfy the constraints (%u non-zero coefficients above; cf. prover.rs:238)", c->stop, c->h_small[0]);
+    c->final_poly.assign(c->h_small + 1, c->h_small + 1 + cnt);
     return ZK_OK;
 }
 
@@ -530,8 +554,10 @@ int open_wait(zk_ctx* c) {
 // its output, one root (prover.rs:224).  Every layer is folded on the device (no host FRI tail); tree tops go to the host as usual.
 // Coset leaves (any fold, 1 included, comes here): the tree over a group's output is the tree over the NEXT group's input, so its
 // leaves are that group's cosets; the last layer is never opened and keeps one-value leaves.
+// Early stop (any fold and leaf format comes here): the groups are those of the first R - stop rounds, and the last group's output
+// gets no tree and no root -- prove_finish commits its coefficients; ids past it are not materialised.
 int prove_fold_rounds(zk_ctx* c, Channel& ch) {
-    const uint32_t R = c->R, K = c->fold;
+    const uint32_t R = c->R - c->stop, K = c->fold;
     uint8_t root[32];
     int rc;
     for (uint32_t r0 = 0; r0 < R; r0 += K) {
@@ -540,13 +566,19 @@ int prove_fold_rounds(zk_ctx* c, Channel& ch) {
         if ((rc = dom_fold_multi(c->dom, c->d_layers + c->layer_off[1 + r0], c->d_layers + c->layer_off[id], c->L - r0, r0, steps, beta,
                                  c->stream, prof_of(c)))) return rc;
         const uint32_t leaf_steps = c->coset && r0 + steps < R ? (R - r0 - steps < K ? R - r0 - steps : K) : 0;
-        if ((rc = do_merkle(c, id, true, false, leaf_steps))) return rc;
-        if ((rc = read_commit(c, id, root))) return rc;
+        const bool stopped = c->stop && r0 + steps == R;                        // the layer the proof stops at: no tree
+        if (!stopped && ((rc = do_merkle(c, id, true, false, leaf_steps)) || (rc = read_commit(c, id, root)))) return rc;
         const size_t deg = c->n >> (r0 + steps);
         if (c->checks && (rc = check_degree(c, id, (uint32_t)deg - (deg ? 1 : 0), "prover.rs:228-251 (FRI layer degree)"))) return rc;
-        ch.commit_hash(root);
-        memcpy(c->info.roots[id], root, 32);
+        if (!stopped) {
+            ch.commit_hash(root);
+            memcpy(c->info.roots[id], root, 32);
+        }
         for (uint32_t l = 2 + r0; l < id; ++l) { c->skipped_layers |= (uint64_t)1 << l; c->skipped_trees |= (uint64_t)1 << l; }
+    }
+    if (c->stop) {
+        c->skipped_trees |= (uint64_t)1 << (1 + R);
+        for (uint32_t l = 2 + R; l <= c->R + 1; ++l) { c->skipped_layers |= (uint64_t)1 << l; c->skipped_trees |= (uint64_t)1 << l; }
     }
     return ZK_OK;
 }
@@ -566,14 +598,25 @@ struct HostLaps {
 // Everything after the last root, for every folding factor: the free term (prover.rs:254), grinding, the query draw (prover.rs:263)
 // and the decommitment (prover.rs:266-289) in the order of for_each_opening, one commit_group per tuple (transcript.hpp).
 int prove_finish(zk_ctx* c, Channel& ch, HostLaps& lap) {
-    const uint32_t R = c->R, K = c->fold, Q = c->queries, G = fold_groups(R, K);
+    const uint32_t R = c->R - c->stop, K = c->fold, Q = c->queries, G = fold_groups(R, K);   // early stop: the groups of the folded rounds
     const size_t B = c->B, N = c->N, Lp = c->L;
     int rc;
-    // last layer: B evaluations of a degree-0 polynomial (prover.rs:238, :251)
-    uint32_t free_term = 0;
-    if ((rc = last_layer_value(c, &free_term))) return rc;
-    c->info.free_term = free_term;
-    ch.commit_u32(free_term);                             // prover.rs:254
+    if (c->stop) {                                        // the final polynomial's coefficients, one commit (transcript.hpp "stop")
+        if ((rc = final_poly_value(c))) return rc;
+        c->info.free_term = c->final_poly[0];
+        std::vector<uint8_t>& cb = c->commit_buf;
+        cb.resize(4 * c->final_poly.size());
+        for (size_t k = 0; k < c->final_poly.size(); ++k)
+            for (int i = 0; i < 4; ++i) cb[4 * k + i] = (uint8_t)(c->final_poly[k] >> (8 * i));
+        ch.commit_bytes(cb.data(), cb.size());
+    } else {
+        // last layer: B evaluations of a degree-0 polynomial (prover.rs:238, :251)
+        uint32_t free_term = 0;
+        if ((rc = last_layer_value(c, &free_term))) return rc;
+        c->info.free_term = free_term;
+        ch.commit_u32(free_term);                         // prover.rs:254
+        c->final_poly.assign(1, free_term);
+    }
     if (c->grind) {                                       // proof of work on the state after the free term (DESIGN.md "Grinding")
         uint64_t w = 0;
         if ((rc = grind_channel(c->grinder, ch, c->grind, &w))) return rc;
@@ -592,13 +635,13 @@ int prove_finish(zk_ctx* c, Channel& ch, HostLaps& lap) {
     // arrays with the host-built parts is enqueued behind it, off the proof's critical path.
     size_t per_query = 0;
     const bool coset = c->coset;
-    for_each_opening(c->log_n, c->log_b, K, 0, [&](uint32_t, uint32_t, size_t, uint32_t slots_log) { per_query += (size_t)1 << slots_log; }, coset);
+    for_each_opening(c->log_n, c->log_b, K, 0, [&](uint32_t, uint32_t, size_t, uint32_t slots_log) { per_query += (size_t)1 << slots_log; }, coset, c->stop);
     open_begin(c, (size_t)Q * per_query);
     for (uint32_t k = 0; k < Q; ++k)
         for_each_opening(c->log_n, c->log_b, K, (size_t)qraws[k] % (N - 2 * B), [&](uint32_t layer, uint32_t log_leaves, size_t leaf, uint32_t slots_log) {
             for (size_t u = 0; u < ((size_t)1 << slots_log); ++u) open_val(c, layer, leaf + (u << log_leaves));
             open_path(c, layer, (size_t)1 << log_leaves, leaf);
-        }, coset);
+        }, coset, c->stop);
     if ((rc = open_launch(c))) return rc;
     if ((rc = flush_host_parts(c))) return rc;            // completes the device arrays, behind the fetch: off the critical path
     lap("free term + fetch enqueue");
@@ -628,13 +671,13 @@ int prove_finish(zk_ctx* c, Channel& ch, HostLaps& lap) {
 // caller's channel `ch`, which may already hold a transcript prefix (main.rs:19 starts from a fresh one).
 // Only the round loops differ with the folding factor: K = 1 has the fused fold, the early launch and the host tail; K > 1 has
 // prove_fold_rounds.  Coset leaves: cp is composed by its own launch (its tree has group 0's cosets as leaves, which the fused
-// one-value leaf source cannot hash) and every K takes prove_fold_rounds.
+// one-value leaf source cannot hash) and every K takes prove_fold_rounds.  Early stop: every K takes prove_fold_rounds too.
 int prove_resident(zk_ctx* c, Channel& ch) {
     if (!c->have_trace) return fail(ZK_ERR_STATE, "zk_prove_resident: no trace uploaded");
     static const bool timing = getenv("ZK_HOST_TIMING") != nullptr;
     HostLaps lap{timing};
     const uint32_t R = c->R;
-    ch.data.reserve(ch.data.size() + proof_data_len(c->log_n, c->log_b, c->queries, c->grind, c->fold, c->coset));
+    ch.data.reserve(ch.data.size() + proof_data_len(c->log_n, c->log_b, c->queries, c->grind, c->fold, c->coset, c->stop));
     c->skipped_layers = c->skipped_trees = 0;
     uint8_t root[32];
     int rc;
@@ -652,14 +695,14 @@ int prove_resident(zk_ctx* c, Channel& ch) {
     uint32_t alpha[3];
     for (int i = 0; i < 3; ++i) alpha[i] = c->info.alpha_raw[i] = ch.get_u32();   // prover.rs:163-165
     if (c->coset) {                                       // prover.rs:166-176, then the tree with group 0's cosets as leaves
-        if ((rc = do_compose(c, alpha)) || (rc = do_merkle(c, 1, true, false, fold_steps(R, c->fold, 0)))) return rc;
+        if ((rc = do_compose(c, alpha)) || (rc = do_merkle(c, 1, true, false, fold_steps(R - c->stop, c->fold, 0)))) return rc;
     } else if ((rc = do_compose_commit(c, alpha))) return rc;    // prover.rs:166-176 (composition fused into the leaf hashing)
     if (can_gate(c, 0) && (rc = enqueue_gated_fold(c, 0))) return rc;   // early launch: round 0 queued before cp's digests are waited for
     if ((rc = read_commit(c, 1, root))) return rc;
     if (c->checks && (rc = check_degree(c, 1, (uint32_t)c->n - 1, "prover.rs:148-159/:169 (exact divisions, deg cp = n - 1)"))) return rc;
     ch.commit_hash(root);                                 // prover.rs:180
     memcpy(c->info.roots[1], root, 32);
-    if (c->fold > 1 || c->coset) {
+    if (c->fold > 1 || c->coset || c->stop) {
         if ((rc = prove_fold_rounds(c, ch))) return rc;
     } else for (uint32_t r = 0; r < R; ++r) {             // prover.rs:198-225
         uint32_t beta = c->info.beta_raw[r] = ch.get_u32();   // prover.rs:200
@@ -919,6 +962,7 @@ int zk_ctx_destroy(zk_ctx* c) {
     if (c->d_trees) (void)hipFree(c->d_trees);
     if (c->d_counter) (void)hipFree(c->d_counter);
     if (c->d_check) (void)hipFree(c->d_check);
+    if (c->d_final) (void)hipFree(c->d_final);
     free_table(&c->ones);
     if (c->d_gather_off) (void)hipFree(c->d_gather_off);
     if (c->d_gather_out) (void)hipFree(c->d_gather_out);
@@ -959,7 +1003,7 @@ int zk_ctx_set_early_launch(zk_ctx* c, int on) {
     c->early = on != 0;
     return ZK_OK;
 }
-int zk_ctx_get_early_launch(const zk_ctx* c) { return c && c->early && c->early_ok && c->fold == 1 && !c->coset ? 1 : 0; }
+int zk_ctx_get_early_launch(const zk_ctx* c) { return c && c->early && c->early_ok && c->fold == 1 && !c->coset && !c->stop ? 1 : 0; }
 // FRI folding factor 2^fold_log between commitments (include/zkstark_amd.h).  A query of a folded proof opens 2^fold_log values and
 // paths per group: the decommitment buffers grow here, not inside the first proof.
 int zk_ctx_set_fold(zk_ctx* c, uint32_t fold_log) {
@@ -1007,6 +1051,30 @@ int zk_ctx_set_coset_leaves(zk_ctx* c, int on) {
     return ZK_OK;
 }
 int zk_ctx_get_coset_leaves(const zk_ctx* c) { return c && c->coset ? 1 : 0; }
+// Early stop (include/zkstark_amd.h): from the next proof on.  A stopped proof opens fewer nodes than a full one, so the decommitment
+// buffers suffice; the kernel's output buffer is allocated here, not inside the first proof.
+int zk_ctx_set_fri_stop(zk_ctx* c, uint32_t stop_log) {
+    if (!c) return fail(ZK_ERR_INVALID, "null context");
+    if (c->tail) return fail(ZK_ERR_STATE, "zk_ctx_set_fri_stop: FRI-tail context");
+    if (!stop_ok(c->log_n, c->log_b, stop_log))
+        return fail(ZK_ERR_INVALID, "zk_ctx_set_fri_stop: need stop_log <= %u, stop_log <= log_n - 1 = %u and stop_log + log_blowup <= %u (got %u)",
+                    kMaxStopLog, c->log_n - 1, kMaxStopLayerLog, stop_log);
+    if (stop_log) {
+        HIPCHK(hipSetDevice(c->device));
+        if (int rc = final_alloc(c)) return rc;
+    }
+    c->stop = stop_log;
+    return ZK_OK;
+}
+uint32_t zk_ctx_get_fri_stop(const zk_ctx* c) { return c ? c->stop : 0; }
+int zk_ctx_final_poly(const zk_ctx* c, uint32_t* out, size_t cap, size_t* count) {
+    if (!c || !count || (!out && cap)) return fail(ZK_ERR_INVALID, "zk_ctx_final_poly: null argument");
+    if (c->final_poly.empty()) return fail(ZK_ERR_STATE, "zk_ctx_final_poly: no proof made yet");
+    *count = c->final_poly.size();
+    if (c->final_poly.size() > cap) return fail(ZK_ERR_BUFFER, "zk_ctx_final_poly: %zu coefficients, room for %zu", c->final_poly.size(), cap);
+    memcpy(out, c->final_poly.data(), c->final_poly.size() * 4);
+    return ZK_OK;
+}
 int zk_ctx_set_queries(zk_ctx* c, uint32_t n_queries) {
     if (!c) return fail(ZK_ERR_INVALID, "null context");
     if (n_queries < 1 || n_queries > kMaxQueries) return fail(ZK_ERR_INVALID, "zk_ctx_set_queries: need 1 <= n_queries <= %u", kMaxQueries);
@@ -1174,10 +1242,28 @@ int zk_fri_fold_multi(zk_ctx* c, uint32_t round, uint32_t steps, uint32_t beta_r
                           beta_raw, c->stream, prof_of(c));
 }
 
+// coefficients of the interpolant of FRI layer id `layer` (at most 4096 values) and the number of non-zero ones at k >= bound
+int zk_fri_final_poly(zk_ctx* c, uint32_t layer, uint32_t bound, uint32_t* coef_out, uint32_t* high_nonzero) {
+    if (!c || !coef_out || !high_nonzero) return fail(ZK_ERR_INVALID, "zk_fri_final_poly: null argument");
+    if (layer < 1 || layer > c->R + 1) return fail(ZK_ERR_INVALID, "zk_fri_final_poly: layer %u out of range (FRI layers are 1..%u)", layer, c->R + 1);
+    const uint32_t lg = layer_log(c, layer);
+    if (lg > kFinalPolyMaxLog) return fail(ZK_ERR_INVALID, "zk_fri_final_poly: layer %u has 2^%u values, the limit is 2^%u", layer, lg, kFinalPolyMaxLog);
+    if ((c->skipped_layers >> layer) & 1) return fail(ZK_ERR_STATE, "zk_fri_final_poly: layer %u was not materialised by the last proof", layer);
+    HIPCHK(hipSetDevice(c->device));
+    int rc = settle_pending(c);
+    if (!rc) rc = final_alloc(c);
+    if (!rc) rc = dom_final_poly(c->dom, c->d_layers + c->layer_off[layer], c->d_final, lg, layer - 1, bound, c->stream, prof_of(c));
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(high_nonzero, c->d_final, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(coef_out, c->d_final + 1, ((size_t)4) << lg, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return ZK_OK;
+}
+
 int zk_layer_read(zk_ctx* c, uint32_t layer, size_t offset, size_t count, uint32_t* out) {
     if (!c || (!out && count)) return fail(ZK_ERR_INVALID, "zk_layer_read: null argument");
     if (layer > c->R + 1 || offset + count > layer_size(c, layer)) return fail(ZK_ERR_INVALID, "zk_layer_read: out of range");
-    if ((c->skipped_layers >> layer) & 1) return fail(ZK_ERR_STATE, "zk_layer_read: layer %u was not materialised by the last proof (fold_log %u)", layer, c->fold);
+    if ((c->skipped_layers >> layer) & 1) return fail(ZK_ERR_STATE, "zk_layer_read: layer %u was not materialised by the last proof (fold_log %u, fri_stop %u)", layer, c->fold, c->stop);
     HIPCHK(hipSetDevice(c->device));
     if (int prc = settle_pending(c)) return prc;
     HIPCHK(hipMemcpyAsync(out, c->d_layers + c->layer_off[layer] + offset, count * 4, hipMemcpyDeviceToHost, c->stream));
@@ -1201,7 +1287,7 @@ int zk_layer_write(zk_ctx* c, uint32_t layer, size_t offset, size_t count, const
 int zk_merkle_node(zk_ctx* c, uint32_t tree, size_t index, uint8_t out[32]) {
     if (!c || !out) return fail(ZK_ERR_INVALID, "zk_merkle_node: null argument");
     if (tree > c->R + 1 || index >= 2 * tree_leaves(c, tree) - 1) return fail(ZK_ERR_INVALID, "zk_merkle_node: out of range");
-    if ((c->skipped_trees >> tree) & 1) return fail(ZK_ERR_STATE, "zk_merkle_node: tree %u was not built by the last proof (fold_log %u)", tree, c->fold);
+    if ((c->skipped_trees >> tree) & 1) return fail(ZK_ERR_STATE, "zk_merkle_node: tree %u was not built by the last proof (fold_log %u, fri_stop %u)", tree, c->fold, c->stop);
     HIPCHK(hipSetDevice(c->device));
     if (int prc = settle_pending(c)) return prc;
     HIPCHK(hipMemcpyAsync(c->h_small, c->d_trees + c->tree_off[tree] + index * 8, 32, hipMemcpyDeviceToHost, c->stream));
@@ -1214,7 +1300,7 @@ int zk_merkle_nodes(zk_ctx* c, uint32_t tree, size_t first, size_t count, uint8_
     if (!c || (!out && count)) return fail(ZK_ERR_INVALID, "zk_merkle_nodes: null argument");
     if (tree > c->R + 1 || first > 2 * tree_leaves(c, tree) - 1 || count > 2 * tree_leaves(c, tree) - 1 - first)
         return fail(ZK_ERR_INVALID, "zk_merkle_nodes: out of range");
-    if ((c->skipped_trees >> tree) & 1) return fail(ZK_ERR_STATE, "zk_merkle_nodes: tree %u was not built by the last proof (fold_log %u)", tree, c->fold);
+    if ((c->skipped_trees >> tree) & 1) return fail(ZK_ERR_STATE, "zk_merkle_nodes: tree %u was not built by the last proof (fold_log %u, fri_stop %u)", tree, c->fold, c->stop);
     HIPCHK(hipSetDevice(c->device));
     if (int prc = settle_pending(c)) return prc;
     return merkle_nodes_to_host(c->device, c->stream, c->d_trees + c->tree_off[tree], first, count, out);
@@ -1223,7 +1309,7 @@ int zk_merkle_nodes(zk_ctx* c, uint32_t tree, size_t first, size_t count, uint8_
 int zk_merkle_path(zk_ctx* c, uint32_t tree, size_t leaf, uint8_t* out, size_t* path_len) {
     if (!c || !out) return fail(ZK_ERR_INVALID, "zk_merkle_path: null argument");
     if (tree > c->R + 1 || leaf >= tree_leaves(c, tree)) return fail(ZK_ERR_INVALID, "zk_merkle_path: out of range");
-    if ((c->skipped_trees >> tree) & 1) return fail(ZK_ERR_STATE, "zk_merkle_path: tree %u was not built by the last proof (fold_log %u)", tree, c->fold);
+    if ((c->skipped_trees >> tree) & 1) return fail(ZK_ERR_STATE, "zk_merkle_path: tree %u was not built by the last proof (fold_log %u, fri_stop %u)", tree, c->fold, c->stop);
     HIPCHK(hipSetDevice(c->device));
     if (int prc = settle_pending(c)) return prc;
     std::vector<size_t> nodes;
@@ -1304,12 +1390,12 @@ int zk_last_transcript(const zk_ctx* c, zk_transcript_info* out) {
 // apart (replay_note not null), "transcript replay failed at check N" + replay_note.
 static int verify_entry(const char* who, const uint8_t* proof, size_t len, const uint8_t* state, uint32_t log_n, uint32_t log_b,
                         uint32_t public_last, int hash_kind, uint32_t q, uint32_t grind, uint32_t fold, int32_t* check_out,
-                        const char* replay_note, const char* reject_note, bool coset = false) {
+                        const char* replay_note, const char* reject_note, bool coset = false, uint32_t stop = 0) {
     if (hash_kind != ZK_HASH_SHA256 && hash_kind != ZK_HASH_FIELD) return fail(ZK_ERR_INVALID, "%s: unknown hash %d", who, hash_kind);
     if (fold < 1 || fold > kMaxFoldLog) return fail(ZK_ERR_INVALID, "%s: need 1 <= fold_log <= %u (got %u)", who, kMaxFoldLog, fold);
-    int rc = state ? verify_transcript(proof, len, state, log_n, log_b, q, grind, fold, coset) : 0;
+    int rc = state ? verify_transcript(proof, len, state, log_n, log_b, q, grind, fold, coset, stop) : 0;
     const bool in_replay = rc != 0;
-    if (!rc) rc = verify_proof(proof, len, log_n, log_b, public_last, hash_kind, q, grind, fold, coset);
+    if (!rc) rc = verify_proof(proof, len, log_n, log_b, public_last, hash_kind, q, grind, fold, coset, stop);
     if (check_out) *check_out = rc;
     if (!rc) return ZK_OK;
     if (in_replay && replay_note) return fail(ZK_ERR_VERIFY, "transcript replay failed at check %d%s", rc, replay_note);
@@ -1355,6 +1441,13 @@ int zk_verify_coset(const uint8_t* proof, size_t len, const uint8_t* state, uint
     if (!proof || !check_out) return fail(ZK_ERR_INVALID, "zk_verify_coset: null argument");
     return verify_entry("zk_verify_coset", proof, len, state, log_n, log_b, public_last, hash_kind, n_queries, grind_bits, fold_log, check_out, nullptr, "", true);
 }
+// zk_verify_fold / zk_verify_coset for proofs that stop FRI early (transcript.hpp "stop"); stop_log = 0 is those two
+int zk_verify_stop(const uint8_t* proof, size_t len, const uint8_t* state, uint32_t log_n, uint32_t log_b, uint32_t public_last,
+                   int hash_kind, uint32_t n_queries, uint32_t grind_bits, uint32_t fold_log, int coset_leaves, uint32_t stop_log, int32_t* check_out) {
+    if (!proof || !check_out) return fail(ZK_ERR_INVALID, "zk_verify_stop: null argument");
+    return verify_entry("zk_verify_stop", proof, len, state, log_n, log_b, public_last, hash_kind, n_queries, grind_bits, fold_log, check_out, nullptr, "",
+                        coset_leaves != 0, stop_log);
+}
 
 size_t zk_proof_size(size_t data_len) { return 48 + data_len; }   // proof.rs:151-154: size_of::<Proof>() = 32 + 16
 size_t zk_proof_data_len_fold(uint32_t log_n, uint32_t log_b, uint32_t n_queries, uint32_t grind_bits, uint32_t fold_log) {
@@ -1364,6 +1457,10 @@ size_t zk_proof_data_len_fold(uint32_t log_n, uint32_t log_b, uint32_t n_queries
 size_t zk_proof_data_len_coset(uint32_t log_n, uint32_t log_b, uint32_t n_queries, uint32_t grind_bits, uint32_t fold_log) {
     if (fold_log < 1 || fold_log > kMaxFoldLog) return 0;
     return proof_data_len(log_n, log_b, n_queries, grind_bits, fold_log, true);
+}
+size_t zk_proof_data_len_stop(uint32_t log_n, uint32_t log_b, uint32_t n_queries, uint32_t grind_bits, uint32_t fold_log, int coset_leaves, uint32_t stop_log) {
+    if (fold_log < 1 || fold_log > kMaxFoldLog || !stop_ok(log_n, log_b, stop_log)) return 0;
+    return proof_data_len(log_n, log_b, n_queries, grind_bits, fold_log, coset_leaves != 0, stop_log);
 }
 size_t zk_proof_data_len_grind(uint32_t log_n, uint32_t log_b, uint32_t n_queries, uint32_t grind_bits) {
     return zk_proof_data_len_fold(log_n, log_b, n_queries, grind_bits, 1);

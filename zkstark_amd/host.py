@@ -145,18 +145,29 @@ class Proof:
     """proof.rs:5-154.  verify() raises ZkError where the reference panics."""
 
     def __init__(self, state, data, log_n=10, log_blowup=3, public_last=2338775057, hash="sha256", queries=1, grind_bits=0,
-                 fold_log=1, coset_leaves=False):   # proof.rs:11
+                 fold_log=1, coset_leaves=False, stop_log=0):   # proof.rs:11
         self.state, self.data = bytes(state), bytes(data)
+        self.stop_log = stop_log                     # made with zk_ctx_set_fri_stop: zk_verify_stop, zk_proof_data_len_stop
         self.log_n, self.log_blowup, self.public_last = log_n, log_blowup, public_last
         self.hash, self.queries, self.grind_bits, self.fold_log = hash, queries, grind_bits, fold_log
         self.coset_leaves = bool(coset_leaves)       # made with zk_ctx_set_coset_leaves: zk_verify_coset, zk_proof_data_len_coset
 
     def expected_len(self):
-        """The length the format gives a proof of this shape (zk_proof_data_len_fold / zk_proof_data_len_coset)."""
+        """The length the format gives a proof of this shape (zk_proof_data_len_fold / zk_proof_data_len_coset; stopped early:
+        zk_proof_data_len_stop)."""
+        if self.stop_log:
+            return _lib.load().zk_proof_data_len_stop(self.log_n, self.log_blowup, self.queries, self.grind_bits, self.fold_log,
+                                                      int(self.coset_leaves), self.stop_log)
         fn = _lib.load().zk_proof_data_len_coset if self.coset_leaves else _lib.load().zk_proof_data_len_fold
         return fn(self.log_n, self.log_blowup, self.queries, self.grind_bits, self.fold_log)
 
+    data_len = expected_len
+
     def _verify_general(self, strict, out):
+        if self.stop_log:
+            return _lib.load().zk_verify_stop(self.data, len(self.data), self.state if strict else None, self.log_n, self.log_blowup,
+                                              self.public_last, HASHES[self.hash], self.queries, self.grind_bits, self.fold_log,
+                                              int(self.coset_leaves), self.stop_log, C.byref(out))
         fn = _lib.load().zk_verify_coset if self.coset_leaves else _lib.load().zk_verify_fold
         return fn(self.data, len(self.data), self.state if strict else None, self.log_n, self.log_blowup,
                   self.public_last, HASHES[self.hash], self.queries, self.grind_bits, self.fold_log, C.byref(out))
@@ -165,7 +176,7 @@ class Proof:
         """strict=True also replays the channel: challenges must come from the transcript and `state`
         must be its final state (the reference trusts the proof for both, proof.rs:22-37); with grind_bits > 0 it also
         checks the proof-of-work nonce."""
-        if self.fold_log != 1 or self.coset_leaves:  # folded by 2^fold_log between commitments (zk_ctx_set_fold), or coset leaves
+        if self.fold_log != 1 or self.coset_leaves or self.stop_log:  # folded by 2^fold_log between commitments (zk_ctx_set_fold), coset leaves, early stop
             check(self._verify_general(strict, C.c_int32()))
             return
         if self.grind_bits:
@@ -180,7 +191,7 @@ class Proof:
         """The number of the check the CPU verifier stops at (zk_verify_grind): 0 = accepted; otherwise what verify()'s
         error names.  Never raises for a rejected proof."""
         out = C.c_int32()
-        if self.fold_log != 1 or self.coset_leaves:
+        if self.fold_log != 1 or self.coset_leaves or self.stop_log:
             rc = self._verify_general(strict, out)
         else:
             rc = _lib.load().zk_verify_grind(self.data, len(self.data), self.state if strict else None, self.log_n, self.log_blowup,
@@ -271,12 +282,14 @@ class Context:
     """Device-resident prover state for one (log_n, log_blowup): zk_ctx."""
 
     def __init__(self, log_n=10, log_blowup=3, device=0, hash="sha256", queries=1, host_levels=None, grind_bits=0, fold_log=1,
-                 coset_leaves=False):
+                 coset_leaves=False, stop_log=0):
         """host_levels: (top_log, tail_log) of zk_ctx_set_host_levels; None = the library default.  grind_bits: proof-of-work
         bits before the query draw (zk_ctx_set_grinding; 0 = none).  fold_log: FRI folding factor 2^fold_log between commitments
-        (zk_ctx_set_fold; 1 = the reference).  coset_leaves: one coset per Merkle leaf of the FRI trees (zk_ctx_set_coset_leaves)."""
+        (zk_ctx_set_fold; 1 = the reference).  coset_leaves: one coset per Merkle leaf of the FRI trees (zk_ctx_set_coset_leaves).
+        stop_log: stop FRI at a polynomial of degree < 2^stop_log and send its coefficients (zk_ctx_set_fri_stop; 0 = fold to a constant)."""
         self.fold_log = fold_log
         self.coset_leaves = False
+        self.stop_log = 0
         self.log_n, self.log_blowup, self.device, self.hash, self.queries = log_n, log_blowup, device, hash, queries
         self.grind_bits = grind_bits
         self.n, self.B = 1 << log_n, 1 << log_blowup
@@ -295,13 +308,36 @@ class Context:
             check(_lib.load().zk_ctx_set_fold(self._h, fold_log))
         if coset_leaves:
             self.set_coset_leaves(True)
+        if stop_log:
+            self.set_fri_stop(stop_log)
 
     def set_coset_leaves(self, on=True):
         """zk_ctx_set_coset_leaves: from the next proof on, a group opens one leaf of 2^steps values and one path."""
         check(_lib.load().zk_ctx_set_coset_leaves(self._h, int(bool(on))))
         self.coset_leaves = bool(on)
 
+    def set_fri_stop(self, stop_log):
+        """zk_ctx_set_fri_stop: from the next proof on, fold only log_n - stop_log rounds and commit the 2^stop_log coefficients of the
+        polynomial left (0: fold down to a constant, the reference)."""
+        check(_lib.load().zk_ctx_set_fri_stop(self._h, stop_log))
+        self.stop_log = stop_log
+
+    def final_poly(self):
+        """zk_ctx_final_poly: the coefficients the last proof ended with (stop_log 0: one value, the free term)."""
+        out, n = np.zeros(1 << 8, dtype=np.uint32), C.c_size_t()
+        check(_lib.load().zk_ctx_final_poly(self._h, _ptr(out), len(out), C.byref(n)))
+        return out[:n.value].copy()
+
+    def fri_final_poly(self, layer, bound):
+        """zk_fri_final_poly: (coefficients of the interpolant of FRI layer `layer`, number of non-zero ones of degree >= bound)."""
+        out, high = np.zeros(self.layer_size(layer), dtype=np.uint32), C.c_uint32()
+        check(_lib.load().zk_fri_final_poly(self._h, layer, bound, _ptr(out), C.byref(high)))
+        return out, high.value
+
     def _proof_cap(self):
+        if self.stop_log:
+            return _lib.load().zk_proof_data_len_stop(self.log_n, self.log_blowup, self.queries, self.grind_bits, self.fold_log,
+                                                      int(self.coset_leaves), self.stop_log)
         fn = _lib.load().zk_proof_data_len_coset if self.coset_leaves else _lib.load().zk_proof_data_len_fold
         return fn(self.log_n, self.log_blowup, self.queries, self.grind_bits, self.fold_log)
 
@@ -416,7 +452,7 @@ class Context:
             check(_lib.load().zk_prove(self._h, _ptr(t), len(t), buf, cap, C.byref(n), st))
         info = self.last_transcript()
         return Proof(st.raw, buf.raw[:n.value], self.log_n, self.log_blowup, info.public_last, self.hash, self.queries, self.grind_bits,
-                     self.fold_log, self.coset_leaves)
+                     self.fold_log, self.coset_leaves, self.stop_log)
 
     def prove_channel(self, channel):
         """generate_proof(channel) (prover.rs:9) in one C call on the caller's Channel (zk_prove_channel): the
@@ -424,6 +460,7 @@ class Context:
         check(_lib.load().zk_prove_channel(self._h, channel._h))
         proof = channel.finalize(self.log_n, self.log_blowup, self.last_transcript().public_last)
         proof.grind_bits, proof.fold_log, proof.coset_leaves = self.grind_bits, self.fold_log, self.coset_leaves
+        proof.stop_log = self.stop_log
         return proof
 
     def set_host_levels(self, top_log, tail_log):
@@ -473,7 +510,7 @@ def prove_many(ctxs):
     out = []
     for i, c in enumerate(ctxs):
         out.append(Proof(states[i].tobytes(), data[i, :lens[i]].tobytes(), c.log_n, c.log_blowup, c.last_transcript().public_last,
-                         c.hash, c.queries, c.grind_bits, c.fold_log, c.coset_leaves))
+                         c.hash, c.queries, c.grind_bits, c.fold_log, c.coset_leaves, c.stop_log))
     return out
 
 
