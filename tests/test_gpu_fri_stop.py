@@ -65,6 +65,52 @@ def test_kernel_returns_a_known_polynomial(zk, log_n, log_b, layer):
             assert lib.zk_fri_final_poly(ctx._h, 1 + (log_n + log_b - 13), 0, out.ctypes.data_as(C.c_void_p), C.byref(hi)) == ZK_ERR_INVALID
 
 
+# Every layer size the kernel accepts, M = 2 .. 4096: the workgroup is 64 lanes up to M = 128, then M / 2 lanes up to the cap of 1024 at
+# M = 2048 (reached exactly), then two butterflies per lane at M = 4096; every loop strides by the workgroup size.  M = 4 .. 32 occur in
+# both contexts, under two domain sizes and so two shifts s and two twiddle strides.
+ALL_SIZES = [(4, 1, layer) for layer in range(1, 6)] + [(10, 2, layer) for layer in range(1, 12)]
+
+
+@pytest.fixture(scope="module")
+def size_contexts(zk):
+    with zk.Context(4, 1) as small, zk.Context(10, 2) as big:
+        yield {(4, 1): small, (10, 2): big}
+
+
+def test_all_sizes_reach_every_layer_log():
+    logs = [ln + lb - (layer - 1) for ln, lb, layer in ALL_SIZES]
+    assert sorted(set(logs)) == list(range(1, 13)) and sorted(lg for lg in logs if logs.count(lg) == 2) == [2, 2, 3, 3, 4, 4, 5, 5]
+
+
+@pytest.mark.parametrize("log_n,log_b,layer", ALL_SIZES, ids=[f"{ln}-{lb}-M{1 << (ln + lb - layer + 1)}" for ln, lb, layer in ALL_SIZES])
+def test_kernel_at_every_size(size_contexts, log_n, log_b, layer):
+    """Random residues with 0 and P - 1 among them: the M coefficients evaluate back to the layer at its M points, high_nonzero is the
+    host's count for every bound in {0, 1, M / 2, M - 1, M}, the layer is left alone; then the evaluation of a known polynomial of degree
+    < M / 2^log_b comes back coefficient for coefficient.  Integers in the field: equality, no tolerance."""
+    ctx = size_contexts[(log_n, log_b)]
+    xs = stop_ref.points(log_n, log_b, layer - 1)
+    M = len(xs)
+    assert M == 1 << (log_n + log_b - (layer - 1)) == ctx.layer_size(layer)
+    vals = rand_field(np.random.default_rng(1000 * log_n + M), M)
+    vals[0], vals[-1] = 0, P - 1
+    ctx.layer_write(layer, vals)
+    for bound in sorted({0, 1, M // 2, M - 1, M}):
+        coef, high = ctx.fri_final_poly(layer, bound)
+        assert coef.shape == (M,) and (coef < P).all()
+        assert np.array_equal(stop_ref.evaluate(coef, xs), vals.astype(np.uint64)), bound
+        assert high == int(np.count_nonzero(coef[bound:])), bound
+    assert np.array_equal(ctx.layer_read(layer), vals)
+    deg = M >> log_b
+    want = rand_field(np.random.default_rng(7 * M + log_n), deg)
+    want[-1] = P - 1
+    known = stop_ref.evaluate(want, xs).astype(np.uint32)
+    ctx.layer_write(layer, known)
+    coef, high = ctx.fri_final_poly(layer, deg)
+    assert np.array_equal(coef[:deg], want) and not coef[deg:].any() and high == 0
+    assert ctx.fri_final_poly(layer, 0)[1] == int(np.count_nonzero(want)) and ctx.fri_final_poly(layer, deg - 1)[1] == 1
+    assert np.array_equal(ctx.layer_read(layer), known)
+
+
 SHAPES = ([(ln, lb, D) for ln, lb in ((4, 1), (5, 2), (6, 3)) for D in sorted({1, 2, ln - 1})]
           + [(10, 3, 4), (10, 3, 8), (9, 3, 8)])                  # (9, 3, 8): R' = 1, one group of one step for every K
 
