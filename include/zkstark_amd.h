@@ -227,8 +227,8 @@ int zk_ctx_get_coset_leaves(const zk_ctx *ctx);
  * zk_merkle_path of a tree id >= 1 + R' (layer 1 + R' has no tree), return ZK_ERR_STATE; a later D = 0 proof materialises everything again.
  * Not run or timed on a GPU yet (tools/fri_stop_bench.py is the tool; DESIGN.md 7d "Early stop"): fold_log 1 without coset leaves may
  * well be slower with D > 0 at large domains.
- * NOT covered: the batched prover (zk_batch_*), the batched GPU verifier (zk_verifier_*), zk_shard_* and zk_tail_* keep folding down to
- * a constant.
+ * zk_verifier_* checks such proofs in batches with zk_verifier_set_fri_stop.
+ * NOT covered: the batched prover (zk_batch_*), zk_shard_* and zk_tail_* keep folding down to a constant.
  * zk_ctx_get_fri_stop: the current D, 0 for a null context.  zk_ctx_final_poly: the coefficients of the last proof (count <- their
  * number; ZK_ERR_BUFFER if cap is smaller, ZK_ERR_STATE before the first proof); with D = 0 count is 1 and out[0] the free term. */
 int zk_ctx_set_fri_stop(zk_ctx *ctx, uint32_t stop_log);
@@ -497,7 +497,7 @@ int zk_verify_coset(const uint8_t *proof, size_t len, const uint8_t *state, uint
  * length is not zk_proof_data_len_stop of the arguments is rejected with -1, strict or not, and so is a stop_log outside the limits.
  * Soundness: one coset per committed layer is tested per query as before; the final polynomial's degree bound holds by construction.
  * stop_log = 0 gives every input the number zk_verify_fold / zk_verify_coset gives it (the same code path).
- * NOT covered: zk_verifier_* checks only proofs folded down to a constant. */
+ * Many proofs at once on the GPU: zk_verifier_set_fri_stop + zk_verifier_run. */
 int zk_verify_stop(const uint8_t *proof, size_t len, const uint8_t *state, uint32_t log_n, uint32_t log_blowup, uint32_t public_last,
                    int hash_kind, uint32_t n_queries, uint32_t grind_bits, uint32_t fold_log, int coset_leaves, uint32_t stop_log,
                    int32_t *check_out);
@@ -527,10 +527,22 @@ uint32_t zk_verifier_get_fold(const zk_verifier *v);
  * Not timed yet. */
 int zk_verifier_set_coset_leaves(zk_verifier *v, int on);
 int zk_verifier_get_coset_leaves(const zk_verifier *v);
+/* Proofs made with zk_ctx_set_fri_stop(stop_log = D): default 0, from the next zk_verifier_run on (a verifier may change D between
+ * runs; its buffers follow the proof length); it combines with every hash, query count, grinding, fold_log and leaf format, and no
+ * order between the setters is imposed.  Limits, against the verifier's own sizes: D = 0, or 1 <= D <= 8 with D <= log_n - 1 and
+ * D + log_blowup <= 12; anything else is ZK_ERR_INVALID and the setting is unchanged.  A run then takes
+ * zk_proof_data_len_stop(log_n, log_blowup, q, grind_bits, fold_log, coset_leaves, D) bytes per proof and checks_out[i] is what
+ * zk_verify_stop gives proof i with the same arguments, for EVERY input, strict or not: raw coefficients >= P are reduced on reading
+ * as on the CPU, and a proof of another D is rejected with the number zk_verify_stop gives those bytes.  With D = 0 lengths and
+ * launches are what they were.  A null verifier: ZK_ERR_INVALID.  zk_verifier_get_fri_stop: the current D, 0 for a null verifier.
+ * Not run or timed on a GPU yet (tools/verify_bench.py --stop is the tool; DESIGN.md 7d "Early stop"). */
+int zk_verifier_set_fri_stop(zk_verifier *v, uint32_t stop_log);
+uint32_t zk_verifier_get_fri_stop(const zk_verifier *v);
 /* count proofs at proofs + i*stride, each exactly zk_proof_data_len_fold(log_n, log_blowup, q, grind_bits, fold_log) bytes (with
  * the defaults zk_proof_data_len_queries(log_n, log_blowup, q); with coset leaves zk_proof_data_len_coset of the same arguments;
- * stride >= that, any alignment); states: count*32 bytes, or NULL = not strict; public_last[count].  checks_out[i] = what
- * zk_verify_fold (fold_log 1: zk_verify_grind, zk_verify_check; coset leaves: zk_verify_coset) returns in check_out for proof i,
+ * with an early stop zk_proof_data_len_stop; stride >= that, any alignment); states: count*32 bytes, or NULL = not strict;
+ * public_last[count].  checks_out[i] = what zk_verify_fold (fold_log 1: zk_verify_grind, zk_verify_check; coset leaves:
+ * zk_verify_coset; an early stop: zk_verify_stop) returns in check_out for proof i,
  * for EVERY input.  Returns ZK_OK if all were accepted, ZK_ERR_VERIFY if any was rejected
  * (zk_last_error names the first rejected index and its check), other errors as usual.  count = 0 is a no-op. */
 int zk_verifier_run(zk_verifier *v, const uint8_t *proofs, size_t stride, size_t count, const uint8_t *states,

@@ -193,6 +193,8 @@ SYMBOLS = {
     "zk_batch_get_coset_leaves": (_int, [_vp]),
     "zk_verifier_set_coset_leaves": (_int, [_vp, _int]),
     "zk_verifier_get_coset_leaves": (_int, [_vp]),
+    "zk_verifier_set_fri_stop": (_int, [_vp, _u32]),
+    "zk_verifier_get_fri_stop": (_u32, [_vp]),
     "zk_verifier_run": (_int, [_vp, _vp, _sz, _sz, _vp, _vp, _vp]),
     "zk_merkle_build_host_ex": (_int, [_int, _vp, _sz, _vp, _int]),
     "zk_dev_merkle_build_ex": (_int, [_vp, _u32, _vp, _vp, _int]),

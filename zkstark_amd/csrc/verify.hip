@@ -29,6 +29,14 @@
 // query * (4 + 2G) + position: 0 (-2), 1..3 (-4..-6), 4 + j (the fold comparison of group j), 4 + G + j (the path of group j,
 // -(300 + j)); -3, -7, -(200 + j), -(400 + j) and -8 cannot occur on the fixed layout.  The coset kernels are instances of their
 // own (verify_coset_*_kernel, and the COSET instance of the transcript kernel); the other instances are the code they were.
+//
+// Early stop (zk_verifier_set_fri_stop, D = 1..8; verify_transcript, then verify_proof, with stop = D; any K and leaf format): the
+// groups are the G' of the R' = log_n - D folded rounds, and the launch arguments carry R', G' and the last group's steps in the
+// places of R, G and ls, so every offset, path slot and order key above holds with them (the cp0 relation alone keeps log_n).  In the
+// header the last root and the free term give way to the 2^D coefficients at word 11 + 9G'.  Two things differ, each in a STOP
+// instance of its own (the instances without it are the code they were): the last group's fold is compared with p(x^(2^R')) by
+// Horner over the coefficients, each reduced % P on reading, canonical against canonical; and the transcript schedule has no last
+// root and commits the 2^D words in one piece where the free term was.
 #include <cstdio>
 #include <cstring>
 #include <mutex>
@@ -71,6 +79,7 @@ struct VerifyArgs {
     // folding factor 2^K (K > 1 only): G groups of K rounds, the last one of ls <= K; constants in Montgomery form
     uint32_t K, G, ls;
     uint32_t inv2m, wm1, wm2, wm3;   // 1/2 and w, w^2, w^3 for w = the inverse of the primitive 8th root of unity h^(N/8)
+    uint32_t D;                 // early stop: 2^D coefficients at word 11 + 9G (R, G, ls are then those of the log_n - D folded rounds)
 };
 
 __device__ __forceinline__ uint32_t be_word(const uint32_t* p) { return __builtin_bswap32(*p); }
@@ -131,8 +140,29 @@ __device__ __forceinline__ bool cp0_matches(const VerifyArgs& a, const uint32_t*
     return cp0 == cp_raw;
 }
 
+// Early stop: p(xs) for xs = x^(2^R'), the point of the stopped layer, by Horner from the highest of the 2^D coefficients; each is
+// reduced % P on reading (verify_proof does the same), the result is canonical.  xs goes to Montgomery form once, so a step is one
+// mont_mul (canonical * Montgomery = canonical) and one add.  Every lane of a proof reads the same <= 256 words.
+__device__ __forceinline__ uint32_t final_poly_at(const VerifyArgs& a, const uint32_t* pr, uint32_t xs) {
+    const uint32_t* c = pr + 11u + 9u * a.G;
+    const uint32_t xm = mont_mul(xs, R2);
+    uint32_t acc = 0u;
+#pragma unroll 1
+    for (uint32_t k = 1u << a.D; k-- > 0u;) acc = add(mont_mul(acc, xm), c[k] % P);
+    return acc;
+}
+// ... for the grouped kernels, which carry only the inverse power of x: R' <= 29 squarings of x give the forward one
+__device__ __forceinline__ uint32_t final_poly_at_power(const VerifyArgs& a, const uint32_t* pr, uint32_t x) {
+    uint32_t xs = x;
+#pragma unroll 1
+    for (uint32_t i = 0; i < a.R; ++i) xs = dmul(xs, xs);
+    return final_poly_at(a, pr, xs);
+}
+
 // (1) layout + algebra: one lane per (proof, query).  Path counts, the cp0 relation (-2) and the R FRI relations (-(100 + k)).
-__global__ void __launch_bounds__(kVerifyThreads) verify_algebra_kernel(VerifyArgs a) {
+// STOP: the last relation is against p(x^(2^R)) (xk squared once more is that power), a canonical value.
+template <bool STOP>
+__device__ __forceinline__ void verify_algebra(const VerifyArgs& a) {
     const uint64_t lane = (uint64_t)blockIdx.x * kVerifyThreads + threadIdx.x;
     if (lane >= (uint64_t)a.count * a.q) return;
     const uint32_t p = (uint32_t)(lane / a.q), qk = (uint32_t)(lane % a.q);
@@ -163,12 +193,16 @@ __global__ void __launch_bounds__(kVerifyThreads) verify_algebra_kernel(VerifyAr
         const uint32_t gx = dmul(add(lx, lnx), a.inv2);
         const uint32_t hx = dmul(sub(lx, lnx), dinv(dmul(xk, 2u)));
         const uint32_t calc = add(gx, dmul(pr[19u + 9u * k] % P, hx));   // betas[k + 1]
-        const uint32_t expect = k + 1u < a.R ? pr[layer_word(a, qk, k + 1u)] : pr[19u + 9u * a.R];
+        uint32_t expect;
+        if constexpr (STOP) expect = k + 1u < a.R ? pr[layer_word(a, qk, k + 1u)] : final_poly_at(a, pr, dmul(xk, xk));
+        else expect = k + 1u < a.R ? pr[layer_word(a, qk, k + 1u)] : pr[19u + 9u * a.R];
         if (calc != expect) key = (int32_t)(qk * keys + 5u + k);
         xk = dmul(xk, xk);
     }
     if (key != kNoFailure) atomicMin(&a.best[p], key);
 }
+__global__ void __launch_bounds__(kVerifyThreads) verify_algebra_kernel(VerifyArgs a) { verify_algebra<false>(a); }
+__global__ void __launch_bounds__(kVerifyThreads) verify_stop_algebra_kernel(VerifyArgs a) { verify_algebra<true>(a); }
 
 // STEPS successive reference folds (proof.rs:110-113) of the 2^STEPS values of one group, in registers: round k pairs t with
 // t + cnt and divides by twice the point of t, x^(2^(r0 + k)) om^(2^k t) for the 2^STEPS-th root of unity om.  ixk comes in as
@@ -200,7 +234,8 @@ __device__ __forceinline__ uint32_t fold_group(const VerifyArgs& a, const uint32
 
 // (1) for a folded proof: one lane per (proof, query).  Path counts, the cp0 relation (-2) and the G fold comparisons
 // (-(100 + j)); K is the folding factor of the full groups, the short last group (a.ls < K) has its own instance.
-template <int K>
+// STOP: the last group's comparison is against p(x^(2^R)), a canonical value.
+template <int K, bool STOP = false>
 __global__ void __launch_bounds__(kVerifyThreads) verify_fold_algebra_kernel(VerifyArgs a) {
     const uint64_t lane = (uint64_t)blockIdx.x * kVerifyThreads + threadIdx.x;
     if (lane >= (uint64_t)a.count * a.q) return;
@@ -234,7 +269,9 @@ __global__ void __launch_bounds__(kVerifyThreads) verify_fold_algebra_kernel(Ver
         if (j + 1u < a.G || a.ls == (uint32_t)K) calc = fold_group<K>(a, vals, beta, ixk);
         else if (K == 3 && a.ls == 2u) calc = fold_group<2>(a, vals, beta, ixk);
         else calc = fold_group<1>(a, vals, beta, ixk);
-        const uint32_t expect = j + 1u < a.G ? pr[group_word(a, qk, j + 1u)] : pr[19u + 9u * a.G];
+        uint32_t expect;
+        if constexpr (STOP) expect = j + 1u < a.G ? pr[group_word(a, qk, j + 1u)] : final_poly_at_power(a, pr, x);
+        else expect = j + 1u < a.G ? pr[group_word(a, qk, j + 1u)] : pr[19u + 9u * a.G];
         if (calc != expect) key = (int32_t)(qk * keys + 5u + j);
     }
     if (key != kNoFailure) atomicMin(&a.best[p], key);
@@ -242,7 +279,8 @@ __global__ void __launch_bounds__(kVerifyThreads) verify_fold_algebra_kernel(Ver
 
 // (1) with coset leaves: one lane per (proof, query).  The 3 + G path counts, the cp0 relation (-2) against value 0 of group 0 and
 // the G fold comparisons (-(100 + j)) against value 0 of the next group, both raw; the values come from the rotated slots.
-template <int K>
+// STOP: the last group's comparison is against p(x^(2^R)), a canonical value.
+template <int K, bool STOP = false>
 __global__ void __launch_bounds__(kVerifyThreads) verify_coset_algebra_kernel(VerifyArgs a) {
     const uint64_t lane = (uint64_t)blockIdx.x * kVerifyThreads + threadIdx.x;
     if (lane >= (uint64_t)a.count * a.q) return;
@@ -275,7 +313,9 @@ __global__ void __launch_bounds__(kVerifyThreads) verify_coset_algebra_kernel(Ve
         if (j + 1u < a.G || a.ls == (uint32_t)K) calc = fold_group<K>(a, vals, beta, ixk, rot);
         else if (K == 3 && a.ls == 2u) calc = fold_group<2>(a, vals, beta, ixk, rot);
         else calc = fold_group<1>(a, vals, beta, ixk, rot);
-        const uint32_t expect = j + 1u < a.G ? pr[coset_group_word(a, qk, j + 1u) + coset_rot(a, tp, j + 1u)] : pr[19u + 9u * a.G];
+        uint32_t expect;
+        if constexpr (STOP) expect = j + 1u < a.G ? pr[coset_group_word(a, qk, j + 1u) + coset_rot(a, tp, j + 1u)] : final_poly_at_power(a, pr, x);
+        else expect = j + 1u < a.G ? pr[coset_group_word(a, qk, j + 1u) + coset_rot(a, tp, j + 1u)] : pr[19u + 9u * a.G];
         if (calc != expect) key = (int32_t)(qk * keys + 4u + j);
     }
     if (key != kNoFailure) atomicMin(&a.best[p], key);
@@ -467,8 +507,9 @@ __device__ __forceinline__ void commit_words(uint32_t (&st)[8], const uint32_t* 
 // steps the same for every lane (a challenge, or a commit of nw words), walked by one loop with one commit site: the
 // compression is inlined once and the state stays in registers.  FOLD (verify_transcript with fold > 1): G (beta, root) pairs, and per
 // query one commit per group of its s_j values and paths.  COSET (with FOLD, any K): three f tuples per query, and a group's commit is
-// its s_j slots, one count and one path of L - jK - steps_j digests.
-template <bool FOLD, bool COSET = false>
+// its s_j slots, one count and one path of L - jK - steps_j digests.  STOP: the last of the R betas has no root after it, and the step
+// of the free term commits the 2^D coefficients, so that step (ft) and everything after it come one step earlier.
+template <bool FOLD, bool COSET = false, bool STOP = false>
 __global__ void __launch_bounds__(kVerifyThreads) verify_transcript_kernel(VerifyArgs a) {
     static_assert(FOLD || !COSET, "the coset instance reads the group fields");
     constexpr uint32_t NF = COSET ? 3u : 4u;              // f tuples per query
@@ -480,8 +521,10 @@ __global__ void __launch_bounds__(kVerifyThreads) verify_transcript_kernel(Verif
     for (int i = 0; i < 8; ++i) st[i] = 0u;
     const uint32_t R = FOLD ? a.G : a.R, L = a.L, q = a.q;   // R: the (beta, root) pairs = the layer commits of a query
     // steps: f root | 3 alphas | cp root | R x (beta, layer root) | free term | [nonce] | q query raws | q x (NF f paths, R layer pairs)
+    // STOP:  f root | 3 alphas | cp root | (R - 1) x (beta, layer root) | beta | 2^D coefficients | [nonce] | q query raws | the same
     const uint32_t gs = a.gw ? 1u : 0u;                   // the nonce step: a commit of 2 words, then the zero-bit test (-1998)
-    const uint32_t head = 6u + 2u * R + gs + q;
+    const uint32_t ft = (STOP ? 4u : 5u) + 2u * R;        // the step of the free term, or of the coefficients
+    const uint32_t head = ft + 1u + gs + q;
     const uint32_t steps = head + q * (NF + R);
     uint32_t cur = 0, k = 0;
     int32_t code = 0;
@@ -489,8 +532,8 @@ __global__ void __launch_bounds__(kVerifyThreads) verify_transcript_kernel(Verif
         bool chal;
         uint32_t nw;
         if (s < head) {
-            chal = (s >= 1u && s <= 3u) || (s >= 5u && s < 5u + 2u * R && ((s - 5u) & 1u) == 0u) || s >= 6u + 2u * R + gs;
-            nw = chal ? 1u : (s == 5u + 2u * R ? 1u : (gs && s == 6u + 2u * R) ? 2u : 8u);
+            chal = (s >= 1u && s <= 3u) || (s >= 5u && s < ft && ((s - 5u) & 1u) == 0u) || s >= ft + 1u + gs;
+            nw = chal ? 1u : (s == ft ? (STOP ? 1u << a.D : 1u) : (gs && s == ft + 1u) ? 2u : 8u);
         } else {
             const uint32_t t = (s - head) % (NF + R);
             chal = false;
@@ -506,7 +549,7 @@ __global__ void __launch_bounds__(kVerifyThreads) verify_transcript_kernel(Verif
         }
         commit_words(st, pr + cur, nw);
         cur += nw;
-        if (gs && s == 6u + 2u * R && (st[0] & a.gmask) != 0u) { code = -1998; break; }   // SHA-256(S || le64(w)) is the new state
+        if (gs && s == ft + 1u && (st[0] & a.gmask) != 0u) { code = -1998; break; }   // SHA-256(S || le64(w)) is the new state
     }
     if (code == 0) {
         bool same = true;
@@ -570,6 +613,7 @@ struct zk_verifier {
     uint32_t log_n = 0, log_b = 0, queries = 1, grind = 0, fold = 1;
     int hash = ZK_HASH_SHA256;
     bool coset = false;                                // proofs with coset leaves (zk_verifier_set_coset_leaves)
+    uint32_t stop = 0;                                 // early stop D (zk_verifier_set_fri_stop): the proofs carry 2^D coefficients
     hipStream_t stream = nullptr, tstream = nullptr;   // paths + algebra; transcript (runs beside them)
     hipEvent_t ev_in = nullptr, ev_t = nullptr;
     uint8_t* d_buf = nullptr;                          // proofs, public_last, states, then the three per-proof results
@@ -602,7 +646,8 @@ int verifier_reserve(zk_verifier* v, size_t chunk, size_t len) {
 // One chunk of proofs: stage, copy in, three kernels, copy the per-proof results out, decide each proof.
 int verifier_chunk(zk_verifier* v, const uint8_t* proofs, size_t stride, size_t count, const uint8_t* states, const uint32_t* public_last,
                    int32_t* checks_out, size_t len) {
-    const uint32_t log_n = v->log_n, log_b = v->log_b, q = v->queries, R = log_n, L = log_n + log_b;
+    const uint32_t log_n = v->log_n, log_b = v->log_b, q = v->queries, D = v->stop, L = log_n + log_b;
+    const uint32_t R = log_n - D;                      // the folded rounds (early stop: R', and G' groups below)
     const uint32_t K = v->fold, G = fold_groups(R, K);
     const bool coset = v->coset;
     // inputs: [count][len] proofs, [count] public_last, [count][32] states, packed into the pinned staging buffer
@@ -629,7 +674,8 @@ int verifier_chunk(zk_verifier* v, const uint8_t* proofs, size_t stride, size_t 
     a.gm1 = invmod(g); a.gm2 = mulmod(a.gm1, a.gm1); a.gm3 = mulmod(a.gm2, a.gm1); a.inv2 = invmod(2);
     a.gw = v->grind ? 2u : 0u;
     a.gmask = v->grind ? ~0u << (32u - v->grind) : 0u;
-    a.qbase = 20u + 9u * G + a.gw + q;
+    a.D = D;
+    a.qbase = (D ? 11u + 9u * G + (1u << D) : 20u + 9u * G) + a.gw + q;   // D > 0: no last root, the coefficients for the free term
     a.per_q = (coset ? 3u : 4u) * (3u + 8u * L);
     for (uint32_t j = 0; j < G; ++j) {
         const uint32_t steps = fold_steps(R, K, j);
@@ -651,7 +697,11 @@ int verifier_chunk(zk_verifier* v, const uint8_t* proofs, size_t stride, size_t 
     if (states) {                                      // the transcript chains run beside the paths: cost = max of the two
         HIPCHK(hipEventRecord(v->ev_in, v->stream));
         HIPCHK(hipStreamWaitEvent(v->tstream, v->ev_in, 0));
-        if (coset) hipLaunchKernelGGL((verify_transcript_kernel<true, true>), dim3(gx), dim3(kVerifyThreads), 0, v->tstream, a);
+        if (D) {
+            if (coset) hipLaunchKernelGGL((verify_transcript_kernel<true, true, true>), dim3(gx), dim3(kVerifyThreads), 0, v->tstream, a);
+            else if (K == 1) hipLaunchKernelGGL((verify_transcript_kernel<false, false, true>), dim3(gx), dim3(kVerifyThreads), 0, v->tstream, a);
+            else hipLaunchKernelGGL((verify_transcript_kernel<true, false, true>), dim3(gx), dim3(kVerifyThreads), 0, v->tstream, a);
+        } else if (coset) hipLaunchKernelGGL((verify_transcript_kernel<true, true>), dim3(gx), dim3(kVerifyThreads), 0, v->tstream, a);
         else if (K == 1) hipLaunchKernelGGL(verify_transcript_kernel<false>, dim3(gx), dim3(kVerifyThreads), 0, v->tstream, a);
         else hipLaunchKernelGGL(verify_transcript_kernel<true>, dim3(gx), dim3(kVerifyThreads), 0, v->tstream, a);
         HIPCHK(hipGetLastError());
@@ -659,7 +709,15 @@ int verifier_chunk(zk_verifier* v, const uint8_t* proofs, size_t stride, size_t 
     }
     const uint64_t lanes = (uint64_t)count * q;
     const dim3 agrid((uint32_t)((lanes + kVerifyThreads - 1) / kVerifyThreads));
-    if (coset) {
+    if (D) {                                           // the STOP instances: the last group against the final polynomial
+        if (coset) {
+            if (K == 1) hipLaunchKernelGGL((verify_coset_algebra_kernel<1, true>), agrid, dim3(kVerifyThreads), 0, v->stream, a);
+            else if (K == 2) hipLaunchKernelGGL((verify_coset_algebra_kernel<2, true>), agrid, dim3(kVerifyThreads), 0, v->stream, a);
+            else hipLaunchKernelGGL((verify_coset_algebra_kernel<3, true>), agrid, dim3(kVerifyThreads), 0, v->stream, a);
+        } else if (K == 1) hipLaunchKernelGGL(verify_stop_algebra_kernel, agrid, dim3(kVerifyThreads), 0, v->stream, a);
+        else if (K == 2) hipLaunchKernelGGL((verify_fold_algebra_kernel<2, true>), agrid, dim3(kVerifyThreads), 0, v->stream, a);
+        else hipLaunchKernelGGL((verify_fold_algebra_kernel<3, true>), agrid, dim3(kVerifyThreads), 0, v->stream, a);
+    } else if (coset) {
         if (K == 1) hipLaunchKernelGGL(verify_coset_algebra_kernel<1>, agrid, dim3(kVerifyThreads), 0, v->stream, a);
         else if (K == 2) hipLaunchKernelGGL(verify_coset_algebra_kernel<2>, agrid, dim3(kVerifyThreads), 0, v->stream, a);
         else hipLaunchKernelGGL(verify_coset_algebra_kernel<3>, agrid, dim3(kVerifyThreads), 0, v->stream, a);
@@ -694,7 +752,7 @@ int verifier_chunk(zk_verifier* v, const uint8_t* proofs, size_t stride, size_t 
         int32_t c;
         if (states && tcode[i]) c = tcode[i];
         else if (malformed[i])                             // garbage only
-            c = verify_proof(proofs + i * stride, len, log_n, log_b, public_last[i], v->hash, q, v->grind, K, coset);
+            c = verify_proof(proofs + i * stride, len, log_n, log_b, public_last[i], v->hash, q, v->grind, K, coset, D);
         else if (best[i] == kNoFailure) c = 0;
         else c = coset ? coset_key_to_check(best[i], G) : K == 1 ? key_to_check(best[i], R) : fold_key_to_check(best[i], G);
         checks_out[i] = c;
@@ -775,6 +833,17 @@ int zk_verifier_set_fold(zk_verifier* v, uint32_t fold_log) {
 
 uint32_t zk_verifier_get_fold(const zk_verifier* v) { return v ? v->fold : 0u; }
 
+int zk_verifier_set_fri_stop(zk_verifier* v, uint32_t stop_log) {
+    if (!v) return fail(ZK_ERR_INVALID, "null verifier");
+    if (!stop_ok(v->log_n, v->log_b, stop_log))
+        return fail(ZK_ERR_INVALID, "zk_verifier_set_fri_stop: need stop_log 0, or 1 <= stop_log <= %u with stop_log <= log_n - 1 and stop_log + log_blowup <= %u (got %u for %u, %u)",
+                    kMaxStopLog, kMaxStopLayerLog, stop_log, v->log_n, v->log_b);
+    v->stop = stop_log;
+    return ZK_OK;
+}
+
+uint32_t zk_verifier_get_fri_stop(const zk_verifier* v) { return v ? v->stop : 0u; }
+
 int zk_verifier_set_coset_leaves(zk_verifier* v, int on) {
     if (!v) return fail(ZK_ERR_INVALID, "null verifier");
     v->coset = on != 0;
@@ -788,7 +857,7 @@ int zk_verifier_run(zk_verifier* v, const uint8_t* proofs, size_t stride, size_t
     if (!v) return fail(ZK_ERR_INVALID, "null verifier");
     if (count == 0) return ZK_OK;
     if (!proofs || !public_last || !checks_out) return fail(ZK_ERR_INVALID, "zk_verifier_run: null argument");
-    const size_t len = proof_data_len(v->log_n, v->log_b, v->queries, v->grind, v->fold, v->coset);
+    const size_t len = proof_data_len(v->log_n, v->log_b, v->queries, v->grind, v->fold, v->coset, v->stop);
     if (stride < len) return fail(ZK_ERR_INVALID, "zk_verifier_run: stride %zu < proof length %zu", stride, len);
     if (count > SIZE_MAX / stride) return fail(ZK_ERR_INVALID, "zk_verifier_run: count * stride overflows");
     HIPCHK(hipSetDevice(v->device));

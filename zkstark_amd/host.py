@@ -613,12 +613,14 @@ class Verifier:
     """Many proofs of one size checked at once on the GPU (zk_verifier_*).  Every result is the number Proof.check gives for
     that proof: 0 = accepted, otherwise the CPU verifier's check number."""
 
-    def __init__(self, log_n, log_blowup, device=0, hash="sha256", queries=1, grind_bits=0, fold_log=1, coset_leaves=False):
+    def __init__(self, log_n, log_blowup, device=0, hash="sha256", queries=1, grind_bits=0, fold_log=1, coset_leaves=False, stop_log=0):
         """fold_log: the FRI folding factor 2^fold_log of the proofs to check (zk_verifier_set_fold; 1 = the reference).
-        coset_leaves: the proofs were made with coset leaves (zk_verifier_set_coset_leaves; Context(coset_leaves=True))."""
+        coset_leaves: the proofs were made with coset leaves (zk_verifier_set_coset_leaves; Context(coset_leaves=True)).
+        stop_log: the proofs stop FRI early at a polynomial of 2^stop_log coefficients (zk_verifier_set_fri_stop; Context(stop_log=))."""
         self.log_n, self.log_blowup, self.hash, self.queries, self.grind_bits = log_n, log_blowup, hash, queries, grind_bits
         self.fold_log = 1
         self.coset_leaves = False
+        self.stop_log = 0
         self._h = C.c_void_p()
         check(_lib.load().zk_verifier_create(device, log_n, log_blowup, C.byref(self._h)))
         if hash != "sha256":
@@ -631,6 +633,14 @@ class Verifier:
             self.set_fold(fold_log)
         if coset_leaves:
             self.set_coset_leaves(True)
+        if stop_log:
+            self.set_fri_stop(stop_log)
+
+    def set_fri_stop(self, stop_log):
+        """zk_verifier_set_fri_stop: from the next run on, check proofs that send the final polynomial's 2^stop_log coefficients
+        (0: proofs folded down to a constant)."""
+        check(_lib.load().zk_verifier_set_fri_stop(self._h, stop_log))
+        self.stop_log = stop_log
 
     def set_fold(self, fold_log):
         """zk_verifier_set_fold: check proofs folded by 2^fold_log (1..3) between commitments from the next run on."""
@@ -654,6 +664,9 @@ class Verifier:
 
     @property
     def proof_len(self):
+        if self.stop_log:
+            return _lib.load().zk_proof_data_len_stop(self.log_n, self.log_blowup, self.queries, self.grind_bits, self.fold_log,
+                                                      int(self.coset_leaves), self.stop_log)
         fn = _lib.load().zk_proof_data_len_coset if self.coset_leaves else _lib.load().zk_proof_data_len_fold
         return fn(self.log_n, self.log_blowup, self.queries, self.grind_bits, self.fold_log)
 
@@ -679,7 +692,8 @@ class Verifier:
         return out
 
     def verify(self, proofs, strict=True):
-        """proofs: a list of Proof of this verifier's size, folding factor and leaf format (their data, state and public_last are used)."""
+        """proofs: a list of Proof of this verifier's size, folding factor, leaf format and early stop (their data, state and public_last
+        are used)."""
         proofs = list(proofs)
         plen = self.proof_len
         data = np.zeros((len(proofs), plen), dtype=np.uint8)
@@ -690,6 +704,8 @@ class Verifier:
                 names = {True: "coset leaves", False: "one-value leaves"}
                 raise ZkError(-1, f"verify: proof {i} was made with {names[bool(getattr(p, 'coset_leaves', False))]}, "
                                   f"this verifier is set to {names[self.coset_leaves]}")
+            if getattr(p, "stop_log", 0) != self.stop_log:
+                raise ZkError(-1, f"verify: proof {i} was made with stop_log {getattr(p, 'stop_log', 0)}, this verifier is set to stop_log {self.stop_log}")
             if len(p.data) != plen:
                 raise ZkError(-1, f"verify: proof {i} has {len(p.data)} bytes, this verifier takes {plen}")
             data[i] = np.frombuffer(p.data, dtype=np.uint8)
