@@ -227,8 +227,8 @@ int zk_ctx_get_coset_leaves(const zk_ctx *ctx);
  * zk_merkle_path of a tree id >= 1 + R' (layer 1 + R' has no tree), return ZK_ERR_STATE; a later D = 0 proof materialises everything again.
  * Not run or timed on a GPU yet (tools/fri_stop_bench.py is the tool; DESIGN.md 7d "Early stop"): fold_log 1 without coset leaves may
  * well be slower with D > 0 at large domains.
- * zk_verifier_* checks such proofs in batches with zk_verifier_set_fri_stop.
- * NOT covered: the batched prover (zk_batch_*), zk_shard_* and zk_tail_* keep folding down to a constant.
+ * zk_verifier_* checks such proofs in batches with zk_verifier_set_fri_stop; zk_batch_* makes them with zk_batch_set_fri_stop.
+ * NOT covered: zk_shard_* and zk_tail_* keep folding down to a constant.
  * zk_ctx_get_fri_stop: the current D, 0 for a null context.  zk_ctx_final_poly: the coefficients of the last proof (count <- their
  * number; ZK_ERR_BUFFER if cap is smaller, ZK_ERR_STATE before the first proof); with D = 0 count is 1 and out[0] the free term. */
 int zk_ctx_set_fri_stop(zk_ctx *ctx, uint32_t stop_log);
@@ -345,7 +345,7 @@ int zk_kernel_stats(zk_ctx *ctx, zk_kernel_stat *out, size_t count, int reset);
  * a single proof uses on a domain batch times larger, and the trees of the batch are the bottom of one
  * heap whose nodes of depth log_batch are the per-proof roots.  Every proof is byte-identical to what
  * zk_prove returns for the same trace from a context with the batch's settings: hash, queries, grinding, folding factor
- * (zk_batch_set_fold) and leaf format (zk_batch_set_coset_leaves; off by default).  With coset leaves a tree over len values per
+ * (zk_batch_set_fold), leaf format (zk_batch_set_coset_leaves; off by default) and early stop (zk_batch_set_fri_stop; 0 by default).  With coset leaves a tree over len values per
  * proof has len / s leaves per proof and the batch heap batch * len / s.  log_batch <= 10; (log_n, log_blowup) as for
  * zk_ctx_create (log_n >= 2, != 3), so every proof a batch produces can be checked by zk_verify*.  A batch of one (log_batch 0)
  * is a zk_ctx: every setter forwards to it. */
@@ -386,6 +386,28 @@ uint32_t zk_batch_get_fold(const zk_batch *b);
  * zk_batch_get_coset_leaves: 1 or 0, 0 for a null batch. */
 int zk_batch_set_coset_leaves(zk_batch *b, int on);
 int zk_batch_get_coset_leaves(const zk_batch *b);
+/* As zk_ctx_set_fri_stop, for every proof of the batch: stop_log = D, default 0 (with 0 every byte, launch and allocation of
+ * zk_batch_prove is what it was without this call), from the next zk_batch_prove on.  It combines with every fold_log 1..3, leaf format,
+ * hash, query count 1..16 and grinding; the limits are zk_ctx_set_fri_stop's (D <= 8, D <= log_n - 1, D + log_blowup <= 12; anything else
+ * is ZK_ERR_INVALID and the setting is unchanged).  With D > 0, proof p is byte for byte what zk_prove returns from a context with the same
+ * (log_n, log_blowup, hash, n_queries, grind_bits, fold_log, coset leaves), zk_ctx_set_fri_stop(ctx, D) and the same trace, its state too;
+ * its length is zk_proof_data_len_stop and it is checked with zk_verify_stop, or in batches with zk_verifier_set_fri_stop.  The flow is
+ * the one-call prover's: only the first R' = log_n - D rounds are folded, in the groups of R'; every group, for fold_log 1 without coset
+ * leaves too, is one batched multi-fold launch (the fold fused into leaf hashing does not apply); the last group's output, layer
+ * 1 + R' of the batch, gets no tree, no hand-over and no root.  One launch of fri_final_poly_batch_kernel (4096 / M layers of
+ * M = 2^(D + log_blowup) values per workgroup, one shared twiddle table) writes a compact [batch][1 + 2^D] table -- per proof its own
+ * count of non-zero coefficients of degree >= 2^D, then c_0 .. c_(2^D - 1) -- and one copy brings it to the host; each proof's channel
+ * commits its 4 * 2^D coefficient bytes in one piece.  A non-zero count fails the call with ZK_ERR_CHECK "proof p of the batch: final FRI
+ * layer has degree >= 2^D" for the lowest such p.  After a stopped zk_batch_prove, zk_batch_merkle_nodes of a tree id >= 1 + R' returns
+ * ZK_ERR_STATE; a later D = 0 proof materialises every id again.  The decommitment buffers are re-sized here, the 32 bytes per proof of
+ * the multi-fold are allocated if they are not there yet, and (1 + 2^D) words per proof are allocated on the device and in pinned host
+ * memory; if an allocation fails the call fails as zk_batch_set_fold does and the batch keeps its format and buffers.  Setting the D the
+ * batch already has changes nothing.  Refused with ZK_ERR_STATE while a zk_batch_prove runs.  A null batch: ZK_ERR_INVALID.
+ * What has been run and timed on a GPU is recorded in DESIGN.md 7d "Early stop in the batched prover" (tools/batch_stop_bench.py is the tool): fold_log 1
+ * without coset leaves gives up the fused fold + leaf-hash launch with D > 0 and may well be slower than D = 0 at large domains.
+ * zk_batch_get_fri_stop: the current D, 0 for a null batch. */
+int zk_batch_set_fri_stop(zk_batch *b, uint32_t stop_log);
+uint32_t zk_batch_get_fri_stop(const zk_batch *b);
 /* on = 0: every tree level of the batch on the device (default: the host threads hash the top levels of each proof's
  * trees when the CPU has SHA extensions, as zk_ctx_set_host_levels).  Results are identical. */
 int zk_batch_set_host_levels(zk_batch *b, int on);
@@ -402,7 +424,7 @@ int zk_batch_gen_fibsq(zk_batch *b, const uint32_t *a0, const uint32_t *a1);
 int zk_batch_public_last(const zk_batch *b, uint32_t *out);
 /* proofs_out: [batch][stride] bytes, stride >= zk_proof_data_len(log_n, log_blowup); states_out:
  * [batch][32] (with q queries: zk_proof_data_len_queries; in general zk_proof_data_len_fold(log_n, log_blowup, n_queries, grind_bits,
- * fold_log); with coset leaves zk_proof_data_len_coset of the same arguments).  Fails with ZK_ERR_CHECK, naming the proof, if a trace
+ * fold_log); with coset leaves zk_proof_data_len_coset of the same arguments; with an early stop zk_proof_data_len_stop).  Fails with ZK_ERR_CHECK, naming the proof, if a trace
  * breaks the constraints. */
 int zk_batch_prove(zk_batch *b, uint8_t *proofs_out, size_t stride, uint8_t *states_out);
 /* Nodes [first, first + count) of batch tree `tree` (a heap over batch * m_l leaves; proof p's tree is the subtree under node

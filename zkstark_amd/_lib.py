@@ -191,6 +191,8 @@ SYMBOLS = {
     "zk_verifier_get_fold": (_u32, [_vp]),
     "zk_batch_set_coset_leaves": (_int, [_vp, _int]),
     "zk_batch_get_coset_leaves": (_int, [_vp]),
+    "zk_batch_set_fri_stop": (_int, [_vp, _u32]),
+    "zk_batch_get_fri_stop": (_u32, [_vp]),
     "zk_verifier_set_coset_leaves": (_int, [_vp, _int]),
     "zk_verifier_get_coset_leaves": (_int, [_vp]),
     "zk_verifier_set_fri_stop": (_int, [_vp, _u32]),

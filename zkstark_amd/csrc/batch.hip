@@ -10,6 +10,9 @@
 // Coset leaves (zk_batch_set_coset_leaves): the tree over a group's input layer has one leaf per opened coset, so proof p's tree over
 // len values has m = len / s leaves and the batch heap batch * m; cp is composed by its own launch, every K folds with the batched
 // multi-fold, and the trees come from launch_merkle_build_coset_batch -- prove_resident / prove_fold_rounds (zkstark.hip) per proof.
+// Early stop (zk_batch_set_fri_stop, D > 0): the groups are those of the first R' = log_n - D rounds, every K folds with the batched
+// multi-fold, the last group's output (layer 1 + R' of the batch) gets no tree; one launch of fri_final_poly_batch_kernel turns it into
+// the compact [batch][1 + 2^D] table (count, coefficients) and each proof's channel commits its own 4 * 2^D bytes -- prove_finish per proof.
 #include <atomic>
 #include <condition_variable>
 #include <cstdio>
@@ -57,9 +60,11 @@ struct zk_batch {
     uint32_t queries = 1;             // decommitment queries per proof (1 = the reference, prover.rs:263)
     uint32_t grind = 0;               // proof-of-work bits (zk_batch_set_grinding)
     uint32_t fold = 1;                // FRI folding factor 2^fold between commitments (zk_batch_set_fold; 1 = the reference)
-    uint32_t proved_fold = 1;         // ... of the last zk_batch_prove, whose skipped_trees these are:
+    uint32_t stop = 0;                // early stop D (zk_batch_set_fri_stop; 0 = fold down to a constant, the reference)
+    uint32_t proved_fold = 1, proved_stop = 0;   // ... of the last zk_batch_prove, whose skipped_trees these are:
     uint64_t skipped_trees = 0;       // bit id: that proof built no tree (and no layer) `id`
-    uint32_t* d_work = nullptr;       // [batch][8] per-proof constants of the multi-fold (allocated by the first fold > 1 or coset leaves)
+    uint32_t* d_work = nullptr;       // [batch][8] per-proof constants of the multi-fold (allocated by the first fold > 1, coset leaves or early stop)
+    uint32_t *d_final = nullptr, *h_final = nullptr;   // [batch][1 + 2^stop]: count of high coefficients, final polynomial (stop > 0; h_: pinned)
     bool coset = false;               // coset leaves (zk_batch_set_coset_leaves): from the next zk_batch_prove on
     uint8_t tree_steps[34] = {0};     // tree id of the last zk_batch_prove: its leaves hold 2^tree_steps values (0: one-value leaves)
     Grinder* grinder = nullptr;       // one launch grinds for every proof of the batch (created by the setter above kGrindHostMaxBits)
@@ -157,11 +162,11 @@ const uint32_t* bfinish_roots(zk_batch* b, uint32_t tree, uint32_t log_m) {
 }
 
 // values and path digests one query opens (transcript.hpp: for_each_opening)
-void bopenings(const zk_batch* b, uint32_t fold, bool coset, size_t* vals, size_t* digs) {
+void bopenings(const zk_batch* b, uint32_t fold, bool coset, uint32_t stop, size_t* vals, size_t* digs) {
     *vals = *digs = 0;
     for_each_opening(b->log_n, b->log_b, fold, 0, [&](uint32_t, uint32_t log_leaves, size_t, uint32_t slots_log) {
         *vals += (size_t)1 << slots_log; *digs += log_leaves;
-    }, coset);
+    }, coset, stop);
 }
 // gather buffers for q queries per proof (offsets in, values + digests out; device and pinned host copies), for the current fold
 int balloc_gather(zk_batch* b, uint32_t q) {
@@ -178,24 +183,41 @@ int balloc_gather(zk_batch* b, uint32_t q) {
     return ZK_OK;
 }
 
-// The batch goes to (fold, coset): d_work for the multi-fold (every fold > 1, and every fold with coset leaves), the gather buffers for
-// what a query of that format opens.  On failure the batch keeps its settings and the buffers they need.
-int bset_format(zk_batch* b, uint32_t fold, bool coset, const char* who) {
+// The batch goes to (fold, coset, stop): d_work for the multi-fold (every fold > 1, and every fold with coset leaves or an early stop),
+// the [batch][1 + 2^stop] tables of the final polynomials, the gather buffers for what a query of that format opens.  On failure the
+// batch keeps its settings and the buffers they need.
+int bset_format(zk_batch* b, uint32_t fold, bool coset, uint32_t stop, const char* who) {
     HIPCHK(hipSetDevice(b->device));
     HIPCHK(hipStreamSynchronize(b->stream));
-    if ((fold > 1 || coset) && !b->d_work) {
+    if ((fold > 1 || coset || stop) && !b->d_work) {
         hipError_t e = hipMalloc((void**)&b->d_work, b->batch * 8 * 4);
         if (e != hipSuccess) return fail(ZK_ERR_NOMEM, "%s: hipMalloc(%zu) failed: %s", who, b->batch * 32, hipGetErrorString(e));
         b->device_bytes += b->batch * 32;
     }
+    auto final_bytes = [&](uint32_t D) { return D ? b->batch * (((size_t)1 << D) + 1) * 4 : (size_t)0; };
+    uint32_t *nd_final = nullptr, *nh_final = nullptr;    // the new tables first: the old ones stay until nothing can fail any more
+    if (stop && stop != b->stop) {
+        hipError_t e = hipMalloc((void**)&nd_final, final_bytes(stop));
+        if (e == hipSuccess && (e = hipHostMalloc((void**)&nh_final, final_bytes(stop))) != hipSuccess) { (void)hipFree(nd_final); nd_final = nullptr; }
+        if (e != hipSuccess) return fail(ZK_ERR_NOMEM, "%s: allocating %zu bytes for the final polynomials failed: %s", who, final_bytes(stop), hipGetErrorString(e));
+    }
     const size_t old_vals = b->per_proof_vals, old_digs = b->per_proof_digs;
-    bopenings(b, fold, coset, &b->per_proof_vals, &b->per_proof_digs);
+    bopenings(b, fold, coset, stop, &b->per_proof_vals, &b->per_proof_digs);
     if (int rc = balloc_gather(b, b->queries)) {          // the old buffers are gone: put back what the old format needs, or fail again later
         b->per_proof_vals = old_vals; b->per_proof_digs = old_digs;
         (void)balloc_gather(b, b->queries);
+        if (nd_final) (void)hipFree(nd_final);
+        if (nh_final) (void)hipHostFree(nh_final);
         return rc;
     }
-    b->fold = fold; b->coset = coset;
+    if (stop != b->stop) {                                // stop = 0 gives the tables back
+        if (b->d_final) (void)hipFree(b->d_final);
+        if (b->h_final) (void)hipHostFree(b->h_final);
+        b->device_bytes += final_bytes(stop);
+        b->device_bytes -= final_bytes(b->stop);
+        b->d_final = nd_final; b->h_final = nh_final;
+    }
+    b->fold = fold; b->coset = coset; b->stop = stop;
     return ZK_OK;
 }
 
@@ -215,9 +237,9 @@ int zk_batch_destroy(zk_batch* b) {
     if (b->stream) (void)hipStreamSynchronize(b->stream);
     dom_free(b->dom);
     for (void* p : {(void*)b->d_trace, (void*)b->d_coef, (void*)b->d_layers, (void*)b->d_trees, (void*)b->d_seed, (void*)b->d_chal,
-                    (void*)b->d_counter, (void*)b->d_goff, (void*)b->d_gout, (void*)b->d_work})
+                    (void*)b->d_counter, (void*)b->d_goff, (void*)b->d_gout, (void*)b->d_work, (void*)b->d_final})
         if (p) (void)hipFree(p);
-    for (void* p : {(void*)b->h_chal, (void*)b->h_mail, (void*)b->h_goff, (void*)b->h_gout, (void*)b->h_last, (void*)b->h_stage})
+    for (void* p : {(void*)b->h_chal, (void*)b->h_mail, (void*)b->h_goff, (void*)b->h_gout, (void*)b->h_last, (void*)b->h_stage, (void*)b->h_final})
         if (p) (void)hipHostFree(p);
     grinder_destroy(b->grinder);                         // on b->stream: before the stream goes
     if (b->stream) (void)hipStreamDestroy(b->stream);
@@ -276,7 +298,7 @@ int zk_batch_create(int device, uint32_t log_n, uint32_t log_b, uint32_t log_bat
         return bail(rc);
     HIPCHK_B(hipMemsetAsync(b->d_counter, 0, 64, b->stream));
     HIPCHK_B(hipMemsetAsync(b->d_trace, 0, b->batch * b->n * 4, b->stream));
-    bopenings(b, 1, false, &b->per_proof_vals, &b->per_proof_digs);
+    bopenings(b, 1, false, 0, &b->per_proof_vals, &b->per_proof_digs);
     if ((rc = balloc_gather(b, 1))) return bail(rc);
     HIPCHK_B(hipHostMalloc((void**)&b->h_chal, b->batch * sizeof(BatchChal)));
     HIPCHK_B(hipHostMalloc((void**)&b->h_last, b->batch * (b->B > 2 ? b->B : 2) * 4));
@@ -375,7 +397,7 @@ int zk_batch_set_fold(zk_batch* b, uint32_t fold_log) {
         return ZK_OK;
     }
     if (fold_log == b->fold) return ZK_OK;
-    return bset_format(b, fold_log, b->coset, "zk_batch_set_fold");
+    return bset_format(b, fold_log, b->coset, b->stop, "zk_batch_set_fold");
 }
 uint32_t zk_batch_get_fold(const zk_batch* b) { return b ? b->fold : 0; }
 // Coset leaves (include/zkstark_amd.h): from the next zk_batch_prove on.  A coset proof opens fewer nodes and other values than a plain
@@ -389,9 +411,27 @@ int zk_batch_set_coset_leaves(zk_batch* b, int on) {
         return ZK_OK;
     }
     if ((on != 0) == b->coset) return ZK_OK;
-    return bset_format(b, b->fold, on != 0, "zk_batch_set_coset_leaves");
+    return bset_format(b, b->fold, on != 0, b->stop, "zk_batch_set_coset_leaves");
 }
 int zk_batch_get_coset_leaves(const zk_batch* b) { return b && b->coset ? 1 : 0; }
+// Early stop (include/zkstark_amd.h): from the next zk_batch_prove on.  A stopped proof opens only the groups of log_n - stop_log rounds,
+// so the gather buffers are re-sized here; every fold, 1 included, then runs on the multi-fold and needs d_work, and the tables of the
+// final polynomials are allocated for this stop_log.
+int zk_batch_set_fri_stop(zk_batch* b, uint32_t stop_log) {
+    if (!b) return fail(ZK_ERR_INVALID, "null batch");
+    ZK_BATCH_EXCLUSIVE(b, "zk_batch_set_fri_stop");
+    if (!stop_ok(b->log_n, b->log_b, stop_log))
+        return fail(ZK_ERR_INVALID, "zk_batch_set_fri_stop: need stop_log <= %u, stop_log <= log_n - 1 = %u and stop_log + log_blowup <= %u (got %u)",
+                    kMaxStopLog, b->log_n - 1, kMaxStopLayerLog, stop_log);
+    if (b->single) {
+        if (int rc = zk_ctx_set_fri_stop(b->single, stop_log)) return rc;
+        b->stop = stop_log;
+        return ZK_OK;
+    }
+    if (stop_log == b->stop) return ZK_OK;
+    return bset_format(b, b->fold, b->coset, stop_log, "zk_batch_set_fri_stop");
+}
+uint32_t zk_batch_get_fri_stop(const zk_batch* b) { return b ? b->stop : 0; }
 size_t zk_batch_device_bytes(const zk_batch* b) { return b ? b->device_bytes : 0; }
 
 // traces: [batch][n-1] canonical residues on the host (prover.rs:32-39 per proof)
@@ -460,15 +500,17 @@ int zk_batch_merkle_nodes(zk_batch* b, uint32_t tree, size_t first, size_t count
     const size_t heap = 2 * (blayer_size(b, tree) >> b->tree_steps[tree]) * b->batch - 1;   // read under the flag: a running proof rewrites tree_steps
     if (first > heap || count > heap - first) return fail(ZK_ERR_INVALID, "zk_batch_merkle_nodes: out of range");
     if ((b->skipped_trees >> tree) & 1)
-        return fail(ZK_ERR_STATE, "zk_batch_merkle_nodes: tree %u was not built by the last proof (fold_log %u)", tree, b->proved_fold);
+        return fail(ZK_ERR_STATE, "zk_batch_merkle_nodes: tree %u was not built by the last proof (fold_log %u, fri_stop %u)", tree, b->proved_fold, b->proved_stop);
     return merkle_nodes_to_host(b->device, b->stream, b->d_trees + b->tree_off[tree], first, count, out);
 }
 
 // generate_proof (prover.rs:9-293) for every resident trace.  proofs_out: [batch][stride] bytes, stride >=
-// zk_proof_data_len_fold(log_n, log_b, queries, grind, fold) (coset leaves: zk_proof_data_len_coset); states_out: [batch][32] (Channel.state of each proof, proof.rs:6).
+// zk_proof_data_len_fold(log_n, log_b, queries, grind, fold) (coset leaves: zk_proof_data_len_coset; early stop: zk_proof_data_len_stop); states_out: [batch][32] (Channel.state of each proof, proof.rs:6).
 // fold > 1 (DESIGN.md "Folding factor"): the rounds in groups of `fold`; per group one challenge per proof, one pass of the batched
 // multi-fold kernel and one tree over its output, as prove_fold_rounds (zkstark.hip) does for one proof.  The wire format (openings,
 // tuples, length) is transcript.hpp's for every fold.
+// stop > 0: the loop ends after the fold of the last group of R - stop rounds, whose output gets no tree, no mailbox wait and no root; the
+// final polynomials of the whole batch come from one launch and one copy, and the ids from 1 + R - stop on are not materialised.
 int zk_batch_prove(zk_batch* b, uint8_t* proofs_out, size_t stride, uint8_t* states_out) {
     if (!b || !proofs_out || !states_out) return fail(ZK_ERR_INVALID, "zk_batch_prove: null argument");
     if (!b->have_traces) return fail(ZK_ERR_STATE, "zk_batch_prove: no traces");
@@ -478,7 +520,8 @@ int zk_batch_prove(zk_batch* b, uint8_t* proofs_out, size_t stride, uint8_t* sta
     const int hash = b->hash;
     const uint32_t K = b->fold;
     const bool coset = b->coset;
-    const size_t plen = proof_data_len(b->log_n, b->log_b, Q, b->grind, K, coset);
+    const uint32_t stop = b->stop;
+    const size_t plen = proof_data_len(b->log_n, b->log_b, Q, b->grind, K, coset, stop);
     if (stride < plen) return fail(ZK_ERR_BUFFER, "zk_batch_prove: stride %zu < proof length %zu", stride, plen);
     if (b->single) {
         size_t len = 0;
@@ -489,6 +532,7 @@ int zk_batch_prove(zk_batch* b, uint8_t* proofs_out, size_t stride, uint8_t* sta
     HIPCHK(hipSetDevice(b->device));
     const size_t nb = b->batch, N = b->N, B = b->B;
     const uint32_t R = b->R, L = b->L, lb = b->lb;
+    const uint32_t Rp = R - stop;                                         // folded rounds (early stop: the groups are those of Rp)
     const zk_dom* d = b->dom;
     std::vector<Channel> ch(nb);
     for (auto& c : ch) c.data.reserve(plen);
@@ -505,7 +549,7 @@ int zk_batch_prove(zk_batch* b, uint8_t* proofs_out, size_t stride, uint8_t* sta
     // f = LDE of every trace, committed (prover.rs:60-85)
     if ((rc = dom_lde(d, b->d_trace, b->d_coef, b->d_layers + b->layer_off[0], b->stream, nullptr, (uint32_t)nb))) return rc;
     b->stage_used = 0; b->n_segs = 0; b->seg_words = 0;
-    b->skipped_trees = 0; b->proved_fold = K;
+    b->skipped_trees = 0; b->proved_fold = K; b->proved_stop = stop;
     memset(b->tree_steps, 0, sizeof b->tree_steps);
     HIPCHK(launch_merkle_build(b->d_layers + b->layer_off[0], L + lb, b->d_trees + b->tree_off[0], b->stream, nullptr, bmail(b, L), hash));
     // proof-independent part of the composition constants (compose_args with alpha = 1)
@@ -529,14 +573,14 @@ int zk_batch_prove(zk_batch* b, uint8_t* proofs_out, size_t stride, uint8_t* sta
     });
     if ((rc = bchal_upload(b))) return rc;
     if (coset) {                                                          // prover.rs:166-176, then the tree with group 0's cosets as leaves
-        const uint32_t s0 = fold_steps(R, K, 0);
+        const uint32_t s0 = fold_steps(Rp, K, 0);
         HIPCHK(launch_compose_batch(ca, lb, b->stream, nullptr));
         b->tree_steps[1] = (uint8_t)s0;
         HIPCHK(launch_merkle_build_coset_batch(b->d_layers + b->layer_off[1], L, s0, lb, b->d_trees + b->tree_off[1], b->stream, nullptr,
                                                bmail(b, L - s0), hash));
     } else
     HIPCHK(launch_compose_merkle_batch(ca, lb, b->d_trees + b->tree_off[1], b->stream, nullptr, bmail(b, L), hash));   // prover.rs:166-176
-    const bool fused = K == 1 && !coset;                                  // the fold inside the leaf hashing of its tree
+    const bool fused = K == 1 && !coset && !stop;                         // the fold inside the leaf hashing of its tree
     for (uint32_t r0 = 0;;) {                                             // per group; tree 1 + r0 is the last one committed
         if ((rc = wait_roots())) return rc;
         roots = bfinish_roots(b, 1 + r0, L - r0 - b->tree_steps[1 + r0]);   // tree 1 + r0: 2^(L - r0) values per proof, 2^tree_steps per leaf
@@ -544,7 +588,8 @@ int zk_batch_prove(zk_batch* b, uint8_t* proofs_out, size_t stride, uint8_t* sta
             b->pool->run(nb, 32, [&](size_t p) { uint8_t root[32]; digest_words_to_bytes(roots + 8 * p, root); ch[p].commit_hash(root); });
             break;
         }
-        const uint32_t steps = R - r0 < K ? R - r0 : K, id = 1 + r0 + steps;
+        const uint32_t steps = Rp - r0 < K ? Rp - r0 : K, id = 1 + r0 + steps;
+        const bool stopped = stop && r0 + steps == Rp;                    // the layer the proofs stop at: no tree
         // K = 1: the fold constant is reduced on the host; K > 1: the challenge goes up RAW and is reduced on the device
         const uint32_t winv_half = fused ? mulmod(invmod(powmod(d->shift, (uint64_t)1 << r0)), invmod(2)) : 0;
         b->pool->run(nb, 32, [&](size_t p) {
@@ -564,7 +609,12 @@ int zk_batch_prove(zk_batch* b, uint8_t* proofs_out, size_t stride, uint8_t* sta
             if ((rc = dom_fold_multi_batch(d, b->d_layers + b->layer_off[1 + r0], b->d_layers + b->layer_off[id], L - r0, r0, steps, &b->d_chal->c_mont,
                                            (uint32_t)(sizeof(BatchChal) / 4), b->d_work, (uint32_t)nb, b->stream, nullptr))) return rc;   // prover.rs:201-211, steps times
             // coset leaves: this tree is the one over the NEXT group's input, its leaves are that group's cosets (the last layer: one value)
-            const uint32_t leaf_steps = coset && r0 + steps < R ? (R - r0 - steps < K ? R - r0 - steps : K) : 0;
+            const uint32_t leaf_steps = coset && r0 + steps < Rp ? (Rp - r0 - steps < K ? Rp - r0 - steps : K) : 0;
+            for (uint32_t l = 2 + r0; l < id; ++l) b->skipped_trees |= (uint64_t)1 << l;
+            if (stopped) {
+                for (uint32_t l = id; l <= R + 1; ++l) b->skipped_trees |= (uint64_t)1 << l;
+                break;
+            }
             if (leaf_steps) {
                 b->tree_steps[id] = (uint8_t)leaf_steps;
                 HIPCHK(launch_merkle_build_coset_batch(b->d_layers + b->layer_off[id], L - r0 - steps, leaf_steps, lb, b->d_trees + b->tree_off[id],
@@ -572,12 +622,22 @@ int zk_batch_prove(zk_batch* b, uint8_t* proofs_out, size_t stride, uint8_t* sta
             } else
             HIPCHK(launch_merkle_build(b->d_layers + b->layer_off[id], L - r0 - steps + lb, b->d_trees + b->tree_off[id], b->stream, nullptr,
                                        bmail(b, L - r0 - steps), hash));      // prover.rs:214
-            for (uint32_t l = 2 + r0; l < id; ++l) b->skipped_trees |= (uint64_t)1 << l;
         }
         r0 += steps;
     }
     lap("lde .. last roots");
     if (timing) fprintf(stderr, "[zk batch timing]   of which waiting for the device %.1f us\n", t_wait);
+    const size_t ncoef = (size_t)1 << stop, frow = ncoef + 1;             // early stop: a row of h_final is (count, c_0 .. c_(2^stop - 1))
+    if (stop) {
+        // final polynomials: layer 1 + Rp holds 2^(stop + log_b) values per proof; every coefficient of degree >= 2^stop must be zero
+        if ((rc = dom_final_poly_batch(d, b->d_layers + b->layer_off[1 + Rp], b->d_final, L - Rp, Rp, (uint32_t)ncoef, (uint32_t)nb, b->stream, nullptr))) return rc;
+        HIPCHK(hipMemcpyAsync(b->h_final, b->d_final, nb * frow * 4, hipMemcpyDeviceToHost, b->stream));
+        HIPCHK(hipStreamSynchronize(b->stream));
+        for (size_t p = 0; p < nb; ++p)
+            if (b->h_final[p * frow])
+                return fail(ZK_ERR_CHECK, "proof %zu of the batch: final FRI layer has degree >= 2^%u: its trace does not satisfy the constraints (%u non-zero coefficients above; cf. prover.rs:238)",
+                            p, stop, b->h_final[p * frow]);
+    } else {
     // last layers: B equal values per proof (prover.rs:238, :251), free term (prover.rs:254)
     HIPCHK(hipMemcpyAsync(b->h_last, b->d_layers + b->layer_off[1 + R], nb * B * 4, hipMemcpyDeviceToHost, b->stream));
     HIPCHK(hipStreamSynchronize(b->stream));
@@ -585,18 +645,28 @@ int zk_batch_prove(zk_batch* b, uint8_t* proofs_out, size_t stride, uint8_t* sta
         for (size_t i = 1; i < B; ++i)
             if (b->h_last[p * B + i] != b->h_last[p * B])
                 return fail(ZK_ERR_CHECK, "proof %zu of the batch: last FRI layer is not constant (prover.rs:238): its trace does not satisfy the constraints", p);
+    }
+    // the free term (prover.rs:254), or the 4 * 2^stop coefficient bytes in one commit (transcript.hpp "stop")
+    auto commit_final = [&](size_t p) {
+        if (!stop) { ch[p].commit_u32(b->h_last[p * B]); return; }
+        uint8_t cb[4 << kMaxStopLog];
+        const uint32_t* c = b->h_final + p * frow + 1;
+        for (size_t k = 0; k < ncoef; ++k)
+            for (int i = 0; i < 4; ++i) cb[4 * k + i] = (uint8_t)(c[k] >> (8 * i));
+        ch[p].commit_bytes(cb, 4 * ncoef);
+    };
     // queries and the offsets of every opening (prover.rs:263-289); node j of proof p's tree over m leaves
     // (depth dd, index i) is node 2^(lb+dd) - 1 + p 2^dd + i of the batch heap
     const size_t nv = Q * b->per_proof_vals, ndg = Q * b->per_proof_digs;     // per proof, all its queries
     uint64_t* voff = b->h_goff;
     uint64_t* doff = b->h_goff + nb * nv;
     if (b->grind) {                                                       // free terms, then the nonces of all proofs at once
-        b->pool->run(nb, 16, [&](size_t p) { ch[p].commit_u32(b->h_last[p * B]); });   // prover.rs:254
+        b->pool->run(nb, 16, [&](size_t p) { commit_final(p); });
         if ((rc = bgrind(b, ch))) return rc;
         lap("grind");
     }
     b->pool->run(nb, 16, [&](size_t p) {
-        if (!b->grind) ch[p].commit_u32(b->h_last[p * B]);               // prover.rs:254
+        if (!b->grind) commit_final(p);
         uint32_t qraw[kMaxQueries];
         for (uint32_t k = 0; k < Q; ++k) qraw[k] = ch[p].get_u32();       // prover.rs:263 (x Q)
         uint64_t* vo = voff + p * nv;
@@ -617,7 +687,7 @@ int zk_batch_prove(zk_batch* b, uint8_t* proofs_out, size_t stride, uint8_t* sta
                 for (size_t u = 0; u < ((size_t)1 << slots_log); ++u)     // the slots of one leaf (one value unless coset leaves)
                     *vo++ = b->layer_off[layer] + (p << (log_leaves + slots_log)) + leaf + (u << log_leaves);
                 add_path(layer, log_leaves, leaf);
-            }, coset);
+            }, coset, stop);
     });
     lap("queries + opening offsets");
     const size_t tv = nb * nv, td = nb * ndg;
@@ -632,7 +702,7 @@ int zk_batch_prove(zk_batch* b, uint8_t* proofs_out, size_t stride, uint8_t* sta
     b->pool->run(nb, 4, [&](size_t p) {
         const uint32_t* vals = b->h_gout + p * nv;
         const uint32_t* dw = b->h_gout + tv + p * ndg * 8;
-        std::vector<uint8_t> buf(Channel::group_bytes((size_t)1 << fold_steps(R, K, 0), L));   // one buffer per proof: the first group's tuple is the largest
+        std::vector<uint8_t> buf(Channel::group_bytes((size_t)1 << fold_steps(Rp, K, 0), L));   // one buffer per proof: the first group's tuple is the largest
         auto tuple = [&](size_t s, size_t pl, bool one_leaf) {
             ch[p].commit_group(buf.data(), s, pl, [&](size_t t) { return vals[t]; }, [&](size_t i, uint8_t* out) { digest_words_to_bytes(dw + 8 * i, out); },
                                one_leaf);
@@ -640,8 +710,8 @@ int zk_batch_prove(zk_batch* b, uint8_t* proofs_out, size_t stride, uint8_t* sta
         };
         for (uint32_t q = 0; q < Q; ++q) {
             for (int k = 0; k < (coset ? 3 : 4); ++k) tuple(1, L, false);                                              // prover.rs:274-277
-            for (uint32_t j = 0, G = fold_groups(R, K); j < G; ++j) {                                                  // prover.rs:280-289
-                const uint32_t steps = fold_steps(R, K, j);
+            for (uint32_t j = 0, G = fold_groups(Rp, K); j < G; ++j) {                                                 // prover.rs:280-289
+                const uint32_t steps = fold_steps(Rp, K, j);
                 tuple((size_t)1 << steps, L - j * K - (coset ? steps : 0), coset);
             }
         }

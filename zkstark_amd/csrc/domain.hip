@@ -311,6 +311,23 @@ int dom_final_poly(const zk_dom* d, const uint32_t* d_in, uint32_t* d_out, uint3
     return ZK_OK;
 }
 
+// `batch` layers `round`, proof-major ([batch][2^log_m]) -> d_out = [batch][1 + bound]: per layer its count of non-zero coefficients of
+// degree >= bound, then coefficients 0 .. bound - 1 (launch_fri_final_poly_batch)
+int dom_final_poly_batch(const zk_dom* d, const uint32_t* d_in, uint32_t* d_out, uint32_t log_m, uint32_t round, uint32_t bound, uint32_t batch,
+                         hipStream_t s, Profiler* prof) {
+    if (log_m < 1 || log_m > kFinalPolyMaxLog || log_m + round != d->L || bound < 1 || bound > (1u << log_m) || batch < 1)
+        return fail(ZK_ERR_INVALID, "final polynomials: %u layers of 2^%u values, bound %u, do not match round %u of a 2^%u domain (at most 2^%u values)",
+                    batch, log_m, bound, round, d->L, kFinalPolyMaxLog);
+    FinalPolyArgs a{};
+    a.in = d_in; a.out = d_out; a.in_stride = (size_t)1 << log_m; a.out_stride = (size_t)bound + 1; a.polys = batch;
+    a.log_m = log_m; a.bound = bound;
+    a.hinv = d->Hinv.view(); a.L = d->L;
+    a.minv_mont = to_mont(invmod(1u << log_m));
+    a.sinv_mont = to_mont(mulmod(d->fold_k[round], 2));      // w^(-2^r)
+    HIPCHK(launch_fri_final_poly_batch(a, s, prof));
+    return ZK_OK;
+}
+
 // Waits until the mailbox carries the sequence number of the last commit launch (polling host-coherent
 // memory: no blit kernel, no stream synchronisation on the commit -> challenge path).
 int wait_flag(const uint32_t* flag, uint32_t want, hipStream_t stream, int (*poll)(void*), void* poll_user, double timeout_s) {

@@ -185,6 +185,10 @@ int dom_fold_multi(const zk_dom* d, const uint32_t* d_in, uint32_t* d_out, uint3
 // c_k with k >= bound are non-zero (fri_final_poly_kernel); polys > 1: one workgroup per layer, strides in words
 int dom_final_poly(const zk_dom* d, const uint32_t* d_in, uint32_t* d_out, uint32_t log_m, uint32_t round, uint32_t bound, hipStream_t s,
                    Profiler* prof = nullptr, uint32_t polys = 1, size_t in_stride = 0, size_t out_stride = 0);
+// ... of a proof-major batch of such layers ([batch][2^log_m]) into the compact table d_out = [batch][1 + bound]: the layer's own count,
+// then c_0 .. c_(bound-1) (fri_final_poly_batch_kernel: 4096 >> log_m layers per workgroup)
+int dom_final_poly_batch(const zk_dom* d, const uint32_t* d_in, uint32_t* d_out, uint32_t log_m, uint32_t round, uint32_t bound, uint32_t batch,
+                         hipStream_t s, Profiler* prof = nullptr);
 // ... over a proof-major batch ([batch][2^log_m] -> [batch][2^(log_m - steps)]), proof b with the raw challenge
 // d_beta_raw[b * beta_stride] (device memory); d_work: 8 * batch words of device scratch.  Two launches, nothing else.
 int fold_multi_batch_args(const zk_dom* d, const uint32_t* d_in, uint32_t* d_out, uint32_t log_m, uint32_t round, uint32_t steps,

@@ -5,6 +5,7 @@
 //   compose_kernel       pointwise constraint composition (prover.rs:101-173)
 //   fri_fold_kernel      evaluation-form FRI fold (polynomial.rs:385-400 + prover.rs:204-211)
 //   fri_final_poly_kernel  coefficients of the layer an early-stopped FRI ends at (one workgroup, inverse NTT in LDS)
+//   fri_final_poly_batch_kernel  the same for a proof-major batch: 4096 / M layers per workgroup, compact [1 + 2^D] output
 //   merkle_*_kernel      SHA-256 Merkle heap (merkle.rs:14-51)
 //   gather_kernel        decommitment gather (merkle.rs:54-71, prover.rs:266-289)
 //
@@ -730,6 +731,64 @@ hipError_t launch_fri_final_poly(const FinalPolyArgs& a, hipStream_t s, Profiler
     ScopedKernelTimer tm(prof, K_FOLD, 4.0 * (double)a.polys * (double)(2 * M + 1), s);   // read M words, write M + 1
     const uint32_t threads = M / 2 >= kFinalPolyThreads ? kFinalPolyThreads : (M / 2 <= 64 ? 64 : M / 2);
     hipLaunchKernelGGL(fri_final_poly_kernel, dim3(a.polys), dim3(threads), 0, s, a);
+    return hipGetLastError();
+}
+
+// The same for a proof-major batch (launch_fri_final_poly_batch): one workgroup takes per = min(4096 / M, kFinalPolyBatchMaxPer)
+// consecutive layers -- one contiguous run of per * M words -- into the same 16 KiB of LDS, builds the twiddle table once for all of
+// them and runs every stage over the (layer, butterfly) pairs, so all lanes work at small M.  Only the count and the `bound` low
+// coefficients of a layer are written ([polys][1 + bound]); the high ones are computed and counted per layer (LDS counters) and dropped.
+// The last workgroup may hold fewer layers: `tot` bounds every loop.  The arithmetic per value is fri_final_poly_kernel's, in its order.
+__global__ __launch_bounds__(kFinalPolyThreads) void fri_final_poly_batch_kernel(FinalPolyArgs a, uint32_t per) {
+    __shared__ uint32_t x[1u << kFinalPolyMaxLog];
+    __shared__ uint32_t tw[1u << (kFinalPolyMaxLog - 1)];
+    __shared__ uint32_t high[kFinalPolyBatchMaxPer];
+    const uint32_t M = 1u << a.log_m, pairs = M >> 1, tid = threadIdx.x, nt = blockDim.x;
+    const uint32_t first = blockIdx.x * per;                   // < polys: the grid is ceil(polys / per)
+    const uint32_t np = a.polys - first < per ? a.polys - first : per;
+    const uint32_t tot = np << a.log_m;                        // <= 4096 values of this workgroup
+    const uint32_t* in = a.in + ((size_t)first << a.log_m);
+    uint32_t* out = a.out + (size_t)first * a.out_stride;
+    for (uint32_t q = tid; q < np; q += nt) high[q] = 0;
+    for (uint32_t i = tid; i < tot; i += nt) x[i] = in[i];
+    for (uint32_t j = tid; j < pairs; j += nt) tw[j] = pow_lookup(a.hinv, j << (a.L - a.log_m));
+    __syncthreads();
+    for (uint32_t lh = a.log_m; lh-- > 0; ) {
+        const uint32_t half = 1u << lh, tsh = a.log_m - 1 - lh;
+        for (uint32_t t = tid; t < (tot >> 1); t += nt) {       // layer t / pairs, butterfly t % pairs
+            const uint32_t b = t & (pairs - 1), j = b & (half - 1), i0 = ((t - b) << 1) + ((b - j) << 1) + j;
+            const uint32_t u = x[i0], v = x[i0 + half];
+            x[i0] = add(u, v);
+            x[i0 + half] = mont_mul(sub(u, v), tw[j << tsh]);
+        }
+        __syncthreads();
+    }
+    for (uint32_t t = tid; t < tot; t += nt) {
+        const uint32_t q = t >> a.log_m, k = t & (M - 1);
+        uint32_t r = a.minv_mont, sp = a.sinv_mont;
+        for (uint32_t e = k; e; e >>= 1) {
+            if (e & 1) r = mont_mul(r, sp);
+            sp = mont_mul(sp, sp);
+        }
+        const uint32_t c = mont_mul(x[(t - k) + (__brev(k) >> (32 - a.log_m))], r);
+        if (k < a.bound) out[(size_t)q * a.out_stride + 1 + k] = c;
+        else if (c != 0) atomicAdd(&high[q], 1u);              // into LDS; none for a trace that satisfies the constraints
+    }
+    __syncthreads();
+    for (uint32_t q = tid; q < np; q += nt) out[(size_t)q * a.out_stride] = high[q];
+}
+hipError_t launch_fri_final_poly_batch(const FinalPolyArgs& a, hipStream_t s, Profiler* prof) {
+    if (a.log_m < 1 || a.log_m > kFinalPolyMaxLog || a.log_m > a.L || a.polys < 1 || !a.in || !a.out) return hipErrorInvalidValue;
+    const uint32_t M = 1u << a.log_m;
+    if (a.bound < 1 || a.bound > M || a.in_stride != M || a.out_stride != (size_t)a.bound + 1) return hipErrorInvalidValue;
+    uint32_t per = (1u << kFinalPolyMaxLog) >> a.log_m;
+    if (per > kFinalPolyBatchMaxPer) per = kFinalPolyBatchMaxPer;
+    ScopedKernelTimer tm(prof, K_FOLD, 4.0 * (double)a.polys * (double)(M + a.bound + 1), s);   // read M words, write bound + 1
+    // one lane per butterfly of the fullest workgroup (the read-in and read-out loops then take two values per lane), in whole waves:
+    // polys need not be a power of two (3 layers of M = 64 are 96 butterflies -> 128 lanes)
+    const uint32_t most = (a.polys < per ? a.polys : per) << (a.log_m - 1);
+    const uint32_t threads = most >= kFinalPolyThreads ? kFinalPolyThreads : ((most + 63u) & ~63u);
+    hipLaunchKernelGGL(fri_final_poly_batch_kernel, dim3((a.polys + per - 1) / per), dim3(threads), 0, s, a, per);
     return hipGetLastError();
 }
 

@@ -254,6 +254,12 @@ struct FinalPolyArgs {
     uint32_t sinv_mont;             // 1 / s
 };
 hipError_t launch_fri_final_poly(const FinalPolyArgs& a, hipStream_t s, Profiler* prof = nullptr);
+// The batch form (zk_batch_prove with an early stop): in = [polys][M] (in_stride == M), out = [polys][1 + bound] (out_stride == 1 + bound,
+// 1 <= bound <= M): word 0 of a row is that layer's own count of non-zero c_k with k >= bound, then c_0 .. c_(bound-1); the coefficients
+// above bound are computed and counted, not stored.  One workgroup takes min(4096 / M, kFinalPolyBatchMaxPer) layers and shares one
+// twiddle table among them; every coefficient is launch_fri_final_poly's, word for word.
+constexpr uint32_t kFinalPolyBatchMaxPer = 1024;   // per-layer counters in LDS (M >= 4 never needs more)
+hipError_t launch_fri_final_poly_batch(const FinalPolyArgs& a, hipStream_t s, Profiler* prof = nullptr);
 
 // Merkle tree over m = 2^log_m u32 leaves.  nodes: (2m-1) * 8 words, heap order
 // (merkle.rs:14-51), each node the eight SHA-256 state words.

@@ -518,12 +518,15 @@ class BatchContext:
     """2^log_batch proofs of one size in lockstep (zk_batch_*): every stage is one
     launch over the whole batch; each proof has its own channel and is byte-identical to Context.prove()."""
 
-    def __init__(self, log_n=10, log_blowup=3, log_batch=4, device=0, hash="sha256", queries=1, grind_bits=0, fold_log=1, coset_leaves=False):
+    def __init__(self, log_n=10, log_blowup=3, log_batch=4, device=0, hash="sha256", queries=1, grind_bits=0, fold_log=1, coset_leaves=False,
+                 stop_log=0):
         """fold_log: FRI folding factor 2^fold_log between commitments for every proof of the batch (zk_batch_set_fold; 1 = the
-        reference).  coset_leaves: one coset per Merkle leaf of the FRI trees (zk_batch_set_coset_leaves)."""
+        reference).  coset_leaves: one coset per Merkle leaf of the FRI trees (zk_batch_set_coset_leaves).  stop_log: every proof stops
+        FRI at a polynomial of degree < 2^stop_log and sends its coefficients (zk_batch_set_fri_stop; 0 = fold to a constant)."""
         self.log_n, self.log_blowup, self.log_batch, self.hash, self.queries = log_n, log_blowup, log_batch, hash, queries
         self.grind_bits, self.fold_log = grind_bits, 1
         self.coset_leaves = False
+        self.stop_log = 0
         self.n, self.batch = 1 << log_n, 1 << log_batch
         self._h = C.c_void_p()
         check(_lib.load().zk_batch_create(device, log_n, log_blowup, log_batch, C.byref(self._h)))
@@ -537,6 +540,14 @@ class BatchContext:
             self.set_fold(fold_log)
         if coset_leaves:
             self.set_coset_leaves(True)
+        if stop_log:
+            self.set_fri_stop(stop_log)
+
+    def set_fri_stop(self, stop_log):
+        """zk_batch_set_fri_stop: from the next zk_batch_prove on, every proof folds only log_n - stop_log rounds and commits the
+        2^stop_log coefficients of its final polynomial (0 = fold down to a constant)."""
+        check(_lib.load().zk_batch_set_fri_stop(self._h, stop_log))
+        self.stop_log = stop_log
 
     def set_fold(self, fold_log):
         """zk_batch_set_fold: fold by 2^fold_log (1..3) between commitments from the next zk_batch_prove on."""
@@ -550,6 +561,9 @@ class BatchContext:
 
     @property
     def proof_len(self):
+        if self.stop_log:
+            return _lib.load().zk_proof_data_len_stop(self.log_n, self.log_blowup, self.queries, self.grind_bits, self.fold_log,
+                                                      int(self.coset_leaves), self.stop_log)
         fn = _lib.load().zk_proof_data_len_coset if self.coset_leaves else _lib.load().zk_proof_data_len_fold
         return fn(self.log_n, self.log_blowup, self.queries, self.grind_bits, self.fold_log)
 
@@ -603,7 +617,7 @@ class BatchContext:
         data, states = self.prove_raw()
         last = self.public_last()
         return [Proof(states[p].tobytes(), data[p].tobytes(), self.log_n, self.log_blowup, int(last[p]), self.hash, self.queries,
-                      self.grind_bits, self.fold_log, self.coset_leaves) for p in range(self.batch)]
+                      self.grind_bits, self.fold_log, self.coset_leaves, self.stop_log) for p in range(self.batch)]
 
 
 _ERR_VERIFY = -6
