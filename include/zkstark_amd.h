@@ -53,8 +53,18 @@ typedef struct zk_channel zk_channel;   /* Channel (channel.rs:6-37), see below 
 /* Merkle hash.  SHA-256 is the reference's (merkle.rs:1-2) and the default everywhere.  The
  * field-native hash (a Poseidon2-style permutation over GF(P), csrc/fieldhash.hpp) is the build's
  * own definition for BASELINE.json configs[4]; it has no reference counterpart.  The transcript
- * (channel.rs) always uses SHA-256.  Functions with an _ex suffix take the selector. */
-enum zk_hash_kind { ZK_HASH_SHA256 = 0, ZK_HASH_FIELD = 1 };
+ * (channel.rs) always uses SHA-256.  Functions with an _ex suffix take the selector.
+ * ZK_HASH_BLAKE2S is unkeyed BLAKE2s-256 (RFC 7693; csrc/blake2s.hpp): a leaf is the hash of its slots, 4 bytes
+ * big-endian each (the message the SHA-256 leaf hashes), a node the hash of left || right -- one compression either way, and the 32
+ * bytes in roots, paths and proofs are hashlib.blake2s(msg).digest().  Proof layouts and lengths do not depend on the hash.  Accepted by
+ * zk_ctx_set_hash (with every setting of queries, grinding, folding factor, coset leaves and early stop; hence by zk_prove,
+ * zk_prove_resident, zk_prove_channel and zk_prove_many), the CPU verifiers zk_verify_ex, zk_verify_queries, zk_verify_grind,
+ * zk_verify_coset and zk_verify_stop (the general one: every setting, fold_log 1 and stop_log 0 included), zk_compute_root_from_path_ex,
+ * zk_compute_root_from_coset, zk_dev_merkle_build_ex, zk_merkle_build_host_ex and zk_probe_hash_chain.  Not built yet, refused with
+ * ZK_ERR_INVALID: zk_verify_check and zk_verify_fold (they keep the two hashes they were defined with; use zk_verify_stop), zk_batch_set_hash, zk_verifier_set_hash, zk_shard_set_hash, zk_tail_run, zk_dev_merkle_build_interleaved,
+ * zk_dev_merkle_commit*, zk_dev_merkle_build_chunk and zk_dev_merkle_finish.  Speed against SHA-256: not timed yet
+ * (tools/hash_kinds_bench.py). */
+enum zk_hash_kind { ZK_HASH_SHA256 = 0, ZK_HASH_FIELD = 1, ZK_HASH_BLAKE2S = 2 };
 
 const char *zk_last_error(void);
 const char *zk_version(void);
@@ -186,7 +196,8 @@ uint32_t zk_ctx_get_fold(const zk_ctx *ctx);
  * query count, grinding and zk_prove_channel.  With it on, the tree over the input layer of group j (id 1 + r0, len = N >> r0 values,
  * s = 2^steps_j) has len / s leaves; leaf c holds the slots u = 0 .. s-1, slot u = layer[c + u len / s] -- the coset a query opens there --
  * so a group opens ONE leaf of s values and ONE path of L - r0 - steps digests instead of s values and s paths.  Leaf hash: SHA-256 over
- * the s slots, 4 bytes big-endian each (one block), or the field hash's compression of (slot_0 .. slot_{s-1}, 0, ..., 0, s); s = 1 is the
+ * the s slots, 4 bytes big-endian each (one block), BLAKE2s-256 over the same message, or the field hash's compression of
+ * (slot_0 .. slot_{s-1}, 0, ..., 0, s); s = 1 is the
  * one-value leaf; inner nodes are unchanged.  Tree 0 (f) and the tree over the last layer (never opened) keep one-value leaves; the
  * layers stay in natural order.  Per query: the three f tuples as ever, NO separate cp(x) tuple (group 0's leaf contains it), then per
  * group the s slot values in slot order, a u64 count and the path for leaf x % (len / s).  Length: zk_proof_data_len_coset; verifier:

@@ -366,6 +366,8 @@ int zk_batch_set_queries(zk_batch* b, uint32_t n_queries) {
     return n_queries == b->queries ? (int)ZK_OK : balloc_gather(b, n_queries);
 }
 int zk_batch_set_hash(zk_batch* b, int hash_kind) {
+    // refused before the handle is looked at: no setting of this class takes it
+    if (hash_kind == ZK_HASH_BLAKE2S) return fail(ZK_ERR_INVALID, "zk_batch_set_hash: BLAKE2s (hash 2) is not built for this entry point yet");
     if (!b) return fail(ZK_ERR_INVALID, "null batch");
     ZK_BATCH_EXCLUSIVE(b, "zk_batch_set_hash");
     if (hash_kind != ZK_HASH_SHA256 && hash_kind != ZK_HASH_FIELD) return fail(ZK_ERR_INVALID, "zk_batch_set_hash: unknown hash %d", hash_kind);

@@ -7,6 +7,7 @@
 //   fri_final_poly_kernel  coefficients of the layer an early-stopped FRI ends at (one workgroup, inverse NTT in LDS)
 //   fri_final_poly_batch_kernel  the same for a proof-major batch: 4096 / M layers per workgroup, compact [1 + 2^D] output
 //   merkle_*_kernel      SHA-256 Merkle heap (merkle.rs:14-51)
+//   b2s_subtree_kernel   the throughput launches of a BLAKE2s-256 heap (blake2s.hpp)
 //   gather_kernel        decommitment gather (merkle.rs:54-71, prover.rs:266-289)
 //
 // All bulk data is canonical u32 residues; all constants are in Montgomery form (field.hpp).
@@ -15,6 +16,7 @@
 
 #include <cstdlib>
 
+#include "blake2s.hpp"
 #include "field.hpp"
 #include "fieldhash_f64.hpp"
 #include "sha256_quad.hpp"
@@ -807,7 +809,7 @@ hipError_t launch_fri_final_poly_batch(const FinalPolyArgs& a, hipStream_t s, Pr
 // digest is written once in a contiguous 2 KiB run.  All control flow is wave-uniform.  One launch lowers the tree by k levels; the last
 // <= 2^11 nodes are finished by a single workgroup that keeps the level in LDS.
 
-// Merkle hash selector: 0 = SHA-256 (merkle.rs:1-2), 1 = field-native hash (fieldhash.hpp).
+// Merkle hash selector (zk_hash_kind): 0 = SHA-256 (merkle.rs:1-2), 1 = field-native hash (fieldhash.hpp), 2 = BLAKE2s-256 (blake2s.hpp).
 __constant__ FieldHashConsts g_fh_consts;       // Montgomery form: the 16-lane row form of the narrow levels (fieldhash_inner_row16)
 __constant__ FieldHashConsts64 g_fh_consts64;   // canonical residues as doubles: every other field hash on the device (fieldhash_f64.hpp)
 
@@ -822,6 +824,11 @@ template <> struct Hasher<0> {
 template <> struct Hasher<1> {
     static __device__ __forceinline__ Digest leaf(uint32_t v) { return fieldhash_leaf64(v, g_fh_consts64); }
     static __device__ __forceinline__ Digest inner(const Digest& l, const Digest& r) { return fieldhash_inner64(l, r, g_fh_consts64); }
+};
+// BLAKE2s-256: one compression per leaf and per node, no schedule (blake2s.hpp; the byte order of a Digest is settled there).
+template <> struct Hasher<2> {
+    static __device__ __forceinline__ Digest leaf(uint32_t v) { return blake2s_leaf(v); }
+    static __device__ __forceinline__ Digest inner(const Digest& l, const Digest& r) { return blake2s_inner(l, r); }
 };
 
 // Where the leaf values of a tree come from.  The prover fuses the elementwise producer of a layer
@@ -1010,6 +1017,71 @@ __global__ __launch_bounds__(kMerkleThreads) void merkle_subtree_kernel(SRC src,
             Digest l = lds_digest(x), r = lds_digest(x + 2);
             __builtin_amdgcn_wave_barrier();
             d = Hasher<HASH>::inner(l, r);
+            idx >>= 1;
+            ++lvl;
+            store_digest(nodes, (((size_t)1 << (depth_in - lvl)) - 1) + (base >> lvl) + (size_t)idx * 64 + lane, d);
+        }
+        if (LEAF && more) val = src.finish(raw, pos + 64 - off);
+    }
+}
+
+// The throughput launch of a BLAKE2s tree.  The walk is merkle_subtree_kernel's, argument for argument: 64 * 2^k
+// inputs per wave in groups of 64, sibling groups paired through the wave's (k + 1) x 2 KiB of LDS, every level on all 64 lanes, every
+// digest stored once in a contiguous 2 KiB run -- so merkle_build_t plans one geometry for every hash.  It is a kernel of its own, not
+// a third instantiation of that template, because the machine code of the SHA-256 and field-hash instances is pinned instruction for
+// instruction (tests/test_kernel_descriptors.py) and must not move when this one is tuned.  One compression per node and no message
+// schedule leave 16 + 16 live words in the hash; the next group's inputs (a leaf source's Raw, or the eight words of a digest) stay
+// in flight across it exactly as there: fetch() ahead of the hash, finish() behind the group's digest stores.
+// Only the sources the one-call prover reaches are instantiated (B2sSrc); the builds of the batched, sharded and chunked provers
+// refuse the hash one level up.
+template <class SRC> struct B2sSrc { static constexpr bool ok = false; };
+template <> struct B2sSrc<PlainSrc> { static constexpr bool ok = true; };
+template <> struct B2sSrc<ComposeSrc> { static constexpr bool ok = true; };
+template <> struct B2sSrc<FoldSrc> { static constexpr bool ok = true; };
+
+template <class SRC, bool LEAF>
+__global__ __launch_bounds__(kMerkleThreads) void b2s_subtree_kernel(SRC src, uint32_t* nodes, uint32_t depth_in, uint32_t k, size_t off) {
+    extern __shared__ __attribute__((aligned(16))) uint4 stage[];   // per wave: k pending left groups + the scratch group, 128 uint4 each
+    src_prepare(src, 0);
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const size_t gwave = (size_t)blockIdx.x * (kMerkleThreads / 64) + wave;
+    const size_t base = (gwave << (6 + k)) + off;                // first input of this wave (off: the chunk's first node at this depth)
+    const size_t in_base = ((size_t)1 << depth_in) - 1;
+    uint4* my = stage + (size_t)wave * (k + 1) * 128;
+    uint4* scratch = my + (size_t)k * 128;
+    typename SRC::Raw raw;
+    Digest dnext;
+    uint32_t val = 0;
+    if (LEAF) val = src.load(base + lane - off);                 // the source is chunk-local
+    else dnext = load_digest(nodes, in_base + base + lane);
+#pragma unroll 1
+    for (uint32_t i = 0; i < (1u << k); ++i) {
+        Digest d;
+        const size_t pos = base + (size_t)i * 64 + lane;         // 64 consecutive inputs: coalesced
+        const bool more = i + 1 < (1u << k);                     // wave-uniform
+        if (LEAF) {
+            if (more) raw = src.fetch(pos + 64 - off);
+            d = blake2s_leaf(val);
+            store_digest(nodes, in_base + pos, d);
+        } else {
+            d = dnext;
+            if (more) dnext = load_digest(nodes, in_base + pos + 64);
+        }
+        uint32_t idx = i, lvl = 0;
+#pragma unroll 1
+        while (lvl < k) {                                        // wave-uniform
+            uint4* left = my + lvl * 128;
+            uint4* grp = (idx & 1u) ? scratch : left;
+            grp[2 * lane] = make_uint4(d.w[0], d.w[1], d.w[2], d.w[3]);
+            grp[2 * lane + 1] = make_uint4(d.w[4], d.w[5], d.w[6], d.w[7]);
+            if (!(idx & 1u)) break;
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            // children 2*lane, 2*lane+1 of the 128 buffered nodes: lanes 0-31 pair the left group, lanes 32-63 the right
+            const uint4* x = (lane < 32u ? left : scratch - 128) + 4 * lane;
+            const Digest l = lds_digest(x), r = lds_digest(x + 2);
+            __builtin_amdgcn_wave_barrier();
+            d = blake2s_inner(l, r);
             idx >>= 1;
             ++lvl;
             store_digest(nodes, (((size_t)1 << (depth_in - lvl)) - 1) + (base >> lvl) + (size_t)idx * 64 + lane, d);
@@ -1456,12 +1528,15 @@ void dump_wg_trace() {
 // opens in that layer.  A lane owns leaves c, c + stride, ...: its s loads are s coalesced runs across the wave (the layer stays
 // in natural order), the values of its NEXT leaf are in flight while it hashes the current one (the fetch / finish split of the
 // leaf sources), and a leaf is ONE compression whatever s: SHA-256 of 4 s <= 32 bytes is a single block whose padding words fold
-// away in the schedule, the field hash takes the state (slot_0 .. slot_{s-1}, 0, ..., 0, s).  s = 1 is Hasher::leaf.  The digest
+// away in the schedule, BLAKE2s-256 of the same message is one compression whose zero words fold away, the field hash takes the
+// state (slot_0 .. slot_{s-1}, 0, ..., 0, s).  s = 1 is Hasher::leaf.  The digest
 // goes to heap position len / s - 1 + c; the levels above are built from there by the inner kernels (launch_merkle_build_coset).
 template <int HASH, int S>
 __device__ __forceinline__ Digest coset_leaf_digest(const uint32_t (&v)[S]) {
     Digest d;
-    if (HASH) {
+    if (HASH == ZK_HASH_BLAKE2S) {
+        d = blake2s_slots<S>(v);
+    } else if (HASH == ZK_HASH_FIELD) {
         uint32_t in[kFhT];
 #pragma unroll
         for (int i = 0; i < kFhT; ++i) in[i] = i < S ? v[i] : 0u;
@@ -1512,9 +1587,10 @@ static double merkle_bytes(bool leaf, uint32_t depth, uint32_t k) {
     double produced = (leaf ? in : 0.0) + in * (1.0 - 1.0 / (double)((size_t)1 << k));
     return (leaf ? 4.0 : 32.0) * in + 32.0 * produced;
 }
+static double hash_leaf_ops(int hash) { return hash == ZK_HASH_FIELD ? kFieldLeafOps : hash == ZK_HASH_BLAKE2S ? kB2sLeafOps : kShaLeafOps; }
 static double merkle_ops(bool leaf, uint32_t depth, uint32_t k, int hash) {
     double in = (double)((size_t)1 << depth);
-    double lo = hash ? kFieldLeafOps : kShaLeafOps, io = hash ? kFieldInnerOps : kShaInnerOps;
+    double lo = hash_leaf_ops(hash), io = hash == ZK_HASH_FIELD ? kFieldInnerOps : hash == ZK_HASH_BLAKE2S ? kB2sInnerOps : kShaInnerOps;
     return (leaf ? in * lo : 0.0) + in * (1.0 - 1.0 / (double)((size_t)1 << k)) * io;
 }
 
@@ -1568,16 +1644,20 @@ bool set_merkle_latency_log(uint32_t v) {
 // pass: measured per form): SHA-256 one lane per hash 4.6 (256 per pass), main / helper lanes 4.9 (128),
 // four lanes per hash 3.1 (64); field hash one lane per hash in double precision ~11 (256 per pass; tools/fh64_probe.hip: 10.7 us
 // on a lone wave), a row of 16 lanes in double precision 3.9 (16 per pass; the 32-bit row form of rounds 3-4: 5.4).
+// BLAKE2s one lane per hash: DERIVED, not traced -- its instruction count times the time per instruction of the SHA-256 one-lane entry
+// (4.6 us / kShaInnerOps for a node, 2.6 us / kShaLeafOps for a leaf), 256 per pass; to be replaced by a trace (tools/wg_trace.py).
+constexpr double kB2sLevelUs = kB2sInnerOps * 4.6 / kShaInnerOps, kB2sLeafUs = kB2sLeafOps * 2.6 / kShaLeafOps;
 static double wg_level_us(uint32_t w, int hash) {
     if (w == 0) return 0.0;
-    if (hash) return w <= kFieldRowMaxNodes ? (double)((w + 15) / 16) * 3.7 : w <= kFieldQuadMaxNodes ? (double)((w + 63) / 64) * 5.3 : (double)((w + 255) / 256) * 10.8;   // round 6: as traced (tools/wg_trace.py)
+    if (hash == ZK_HASH_BLAKE2S) return (double)((w + 255) / 256) * kB2sLevelUs;
+    if (hash == ZK_HASH_FIELD) return w <= kFieldRowMaxNodes ? (double)((w + 15) / 16) * 3.7 : w <= kFieldQuadMaxNodes ? (double)((w + 63) / 64) * 5.3 : (double)((w + 255) / 256) * 10.8;   // round 6: as traced (tools/wg_trace.py)
     return w <= 64 ? 3.1 : w <= 128 ? 4.9 : (double)((w + 255) / 256) * 4.6;
 }
 static double wg_phase_us(bool leaf, uint32_t cnt_log, uint32_t levels, int hash, uint32_t blocks) {
     const uint32_t cnt = 1u << cnt_log;
     double us = !leaf ? 1.0                                                        // the first load, or the leaf hashes:
-                : hash ? (cnt <= kFieldRowLeafMax ? (double)((cnt + 15) / 16) * 3.7 : (double)((cnt + 255) / 256) * 10.8)
-                       : (double)((cnt + 255) / 256) * 2.6;
+                : hash == ZK_HASH_FIELD ? (cnt <= kFieldRowLeafMax ? (double)((cnt + 15) / 16) * 3.7 : (double)((cnt + 255) / 256) * 10.8)
+                : (double)((cnt + 255) / 256) * (hash == ZK_HASH_BLAKE2S ? kB2sLeafUs : 2.6);
     for (uint32_t t = 1; t <= levels; ++t) us += wg_level_us(cnt >> t, hash);
     return blocks > 256 ? us * (double)blocks / 256.0 : us;                        // more workgroups than compute units take turns
 }
@@ -1597,7 +1677,8 @@ template <class SRC>
 static hipError_t merkle_build_t(SRC src, double src_bytes, uint32_t log_m, uint32_t* nodes, hipStream_t s, Profiler* prof,
                                  const MailArgs& mail_in, int hash, uint32_t log_sub = 0xffffffffu, size_t chunk = 0,
                                  bool leaf_mode = true, uint32_t tp_floor = 0) {
-    if (hash) {
+    if (hash == ZK_HASH_BLAKE2S && !B2sSrc<SRC>::ok) return hipErrorInvalidValue;   // only the one-call prover's sources (b2s_subtree_kernel)
+    if (hash == ZK_HASH_FIELD) {
         hipError_t e = ensure_fieldhash_consts();
         if (e != hipSuccess) return e;
     }
@@ -1621,7 +1702,12 @@ static hipError_t merkle_build_t(SRC src, double src_bytes, uint32_t log_m, uint
         uint32_t blocks = (uint32_t)(lanes / kMerkleThreads);
         size_t sh = (size_t)(kMerkleThreads / 64) * (k + 1) * 128 * sizeof(uint4);
         ScopedKernelTimer tm(prof, leaf ? K_MERKLE_LEAF : K_MERKLE_INNER, first_bytes(merkle_bytes(leaf, depth - stop, k)), s, merkle_ops(leaf, depth - stop, k, hash));
-        if (hash) {
+        if (hash == ZK_HASH_BLAKE2S) {
+            if constexpr (B2sSrc<SRC>::ok) {
+                if (leaf) hipLaunchKernelGGL((b2s_subtree_kernel<SRC, true>), dim3(blocks), dim3(kMerkleThreads), sh, s, src, nodes, depth, k, off_at(depth));
+                else hipLaunchKernelGGL((b2s_subtree_kernel<PlainSrc, false>), dim3(blocks), dim3(kMerkleThreads), sh, s, none, nodes, depth, k, off_at(depth));
+            }
+        } else if (hash == ZK_HASH_FIELD) {
             if (leaf) hipLaunchKernelGGL((merkle_subtree_kernel<SRC, true, 1>), dim3(blocks), dim3(kMerkleThreads), sh, s, src, nodes, depth, k, off_at(depth));
             else hipLaunchKernelGGL((merkle_subtree_kernel<PlainSrc, false, 1>), dim3(blocks), dim3(kMerkleThreads), sh, s, none, nodes, depth, k, off_at(depth));
         } else {
@@ -1644,7 +1730,12 @@ static hipError_t merkle_build_t(SRC src, double src_bytes, uint32_t log_m, uint
         const size_t sh = ((size_t)2 << lds_log) * sizeof(uint4) + 2 * 16 * 128 * sizeof(uint32_t);
         ScopedKernelTimer tm(prof, K_MERKLE_TOP, first_bytes(merkle_bytes(leaf, span, j)) + (j2 ? merkle_bytes(false, span - j, j2) : 0.0), s,
                              merkle_ops(leaf, span, j, hash) + (j2 ? merkle_ops(false, span - j, j2, hash) : 0.0));
-        if (hash) {
+        if (hash == ZK_HASH_BLAKE2S) {
+            if constexpr (B2sSrc<SRC>::ok) {
+                if (leaf) hipLaunchKernelGGL((merkle_wg_kernel<SRC, true, 2>), dim3(blocks), dim3(kWgThreads), sh, s, src, nodes, depth, j, mail, off_at(depth), j2, lds_log);
+                else hipLaunchKernelGGL((merkle_wg_kernel<PlainSrc, false, 2>), dim3(blocks), dim3(kWgThreads), sh, s, none, nodes, depth, j, mail, off_at(depth), j2, lds_log);
+            }
+        } else if (hash == ZK_HASH_FIELD) {
             if (leaf) hipLaunchKernelGGL((merkle_wg_kernel<SRC, true, 1>), dim3(blocks), dim3(kWgThreads), sh, s, src, nodes, depth, j, mail, off_at(depth), j2, lds_log);
             else hipLaunchKernelGGL((merkle_wg_kernel<PlainSrc, false, 1>), dim3(blocks), dim3(kWgThreads), sh, s, none, nodes, depth, j, mail, off_at(depth), j2, lds_log);
         } else {
@@ -1702,7 +1793,7 @@ hipError_t launch_merkle_build_coset(const uint32_t* vals, uint32_t log_len, uin
                                      const MailArgs& mail, int hash) {
     if (steps == 0) return launch_merkle_build(vals, log_len, nodes, s, prof, mail, hash);
     if (steps > 3 || log_len <= steps) return hipErrorInvalidValue;
-    if (hash) {
+    if (hash == ZK_HASH_FIELD) {
         hipError_t e = ensure_fieldhash_consts();
         if (e != hipSuccess) return e;
     }
@@ -1712,8 +1803,9 @@ hipError_t launch_merkle_build_coset(const uint32_t* vals, uint32_t log_len, uin
     const uint32_t blocks = (uint32_t)((lanes + kCosetThreads - 1) / kCosetThreads);
     {
         ScopedKernelTimer tm(prof, K_MERKLE_LEAF, 4.0 * (double)((size_t)1 << log_len) + 32.0 * (double)leaves, s,
-                             (double)leaves * (hash ? kFieldLeafOps : kShaLeafOps));
-        if (hash) coset_leaf_launch<1>(vals, log_len, steps, nodes, blocks, s);
+                             (double)leaves * hash_leaf_ops(hash));
+        if (hash == ZK_HASH_BLAKE2S) coset_leaf_launch<2>(vals, log_len, steps, nodes, blocks, s);
+        else if (hash == ZK_HASH_FIELD) coset_leaf_launch<1>(vals, log_len, steps, nodes, blocks, s);
         else coset_leaf_launch<0>(vals, log_len, steps, nodes, blocks, s);
     }
     hipError_t e = hipGetLastError();
@@ -1770,7 +1862,8 @@ static void coset_leaf_batch_launch(const uint32_t* vals, uint32_t log_len, uint
 hipError_t launch_merkle_build_coset_batch(const uint32_t* vals, uint32_t log_len, uint32_t steps, uint32_t log_batch, uint32_t* nodes, hipStream_t s,
                                            Profiler* prof, const MailArgs& mail, int hash) {
     if (steps < 1 || steps > 3 || log_len <= steps || log_len + log_batch > 32) return hipErrorInvalidValue;
-    if (hash) {
+    if (hash == ZK_HASH_BLAKE2S) return hipErrorInvalidValue;   // the batched prover has no BLAKE2s yet (zk_batch_set_hash refuses it)
+    if (hash == ZK_HASH_FIELD) {
         hipError_t e = ensure_fieldhash_consts();
         if (e != hipSuccess) return e;
     }
@@ -1780,8 +1873,8 @@ hipError_t launch_merkle_build_coset_batch(const uint32_t* vals, uint32_t log_le
     const uint32_t blocks = (uint32_t)((lanes + kCosetThreads - 1) / kCosetThreads);
     {
         ScopedKernelTimer tm(prof, K_MERKLE_LEAF, 4.0 * (double)((size_t)1 << (log_len + log_batch)) + 32.0 * (double)leaves, s,
-                             (double)leaves * (hash ? kFieldLeafOps : kShaLeafOps));
-        if (hash) coset_leaf_batch_launch<1>(vals, log_len, steps, log_batch, nodes, blocks, s);
+                             (double)leaves * hash_leaf_ops(hash));
+        if (hash == ZK_HASH_FIELD) coset_leaf_batch_launch<1>(vals, log_len, steps, log_batch, nodes, blocks, s);
         else coset_leaf_batch_launch<0>(vals, log_len, steps, log_batch, nodes, blocks, s);
     }
     hipError_t e = hipGetLastError();
@@ -1895,7 +1988,7 @@ __global__ __launch_bounds__(256) void hash_chain_probe_kernel(uint32_t* out, ui
     for (uint32_t it = 0; it < hashes; ++it) {
         Digest r = d;
         r.w[0] ^= seed;
-        if (HASH) r.w[0] &= 0x7fffffffu;          // stays a canonical residue
+        if (HASH == ZK_HASH_FIELD) r.w[0] &= 0x7fffffffu;   // stays a canonical residue
         d = Hasher<HASH>::inner(d, r);
     }
     const unsigned long long c1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
@@ -1909,7 +2002,9 @@ __global__ __launch_bounds__(256) void hash_chain_probe_kernel(uint32_t* out, ui
     }
 }
 hipError_t launch_hash_chain_probe(int hash, uint32_t blocks, uint32_t* out, uint32_t seed, uint32_t hashes, unsigned long long* rec, hipStream_t s) {
-    if (hash) {
+    if (hash == ZK_HASH_BLAKE2S) {
+        hipLaunchKernelGGL(hash_chain_probe_kernel<2>, dim3(blocks), dim3(256), 0, s, out, seed, hashes, rec);
+    } else if (hash == ZK_HASH_FIELD) {
         hipError_t e = ensure_fieldhash_consts();
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL(hash_chain_probe_kernel<1>, dim3(blocks), dim3(256), 0, s, out, seed, hashes, rec);

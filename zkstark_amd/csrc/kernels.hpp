@@ -7,6 +7,8 @@
 
 #include <vector>
 
+#include "../../include/zkstark_amd.h"   // zk_hash_kind: what every `int hash` below holds
+
 namespace zk {
 
 // ---- optional per-kernel timing (HIP events on the launch stream) ---------------
@@ -32,6 +34,12 @@ constexpr double kNttOpsPerElement = 57.0;  // VALU instructions per element of 
 // (32-bit Montgomery form, rounds 1-4: 8 895 / 9 235 / 9 092.)
 constexpr double kFieldLeafOps = 5015.0;
 constexpr double kFieldInnerOps = 5072.0;
+// BLAKE2s-256 (blake2s.hpp): one compression per hash, by ISA loop count (tools/kernel_descriptors.py --loops).  Leaf: the leaf loop of
+// b2s_subtree_kernel<PlainSrc, true> (its address arithmetic included, as for the field hash).  Inner: the chain probe's loop body, 980,
+// plus the 7 byte swaps the probe saves because its two inputs differ in one word only; the pairing loop of the subtree kernel has
+// 1 012 with its LDS and heap addressing.  tests/test_kernel_descriptors_blake2s.py holds both to the binary.
+constexpr double kB2sLeafOps = 954.0;
+constexpr double kB2sInnerOps = 987.0;
 
 struct Profiler {
     uint32_t mask = 0;
@@ -264,7 +272,9 @@ hipError_t launch_fri_final_poly_batch(const FinalPolyArgs& a, hipStream_t s, Pr
 // Merkle tree over m = 2^log_m u32 leaves.  nodes: (2m-1) * 8 words, heap order
 // (merkle.rs:14-51), each node the eight SHA-256 state words.
 // mail (optional): where the result of the build is posted for the host, see MailArgs.
-// hash: 0 = SHA-256 (the reference, merkle.rs:1-2), 1 = field-native hash (fieldhash.hpp, configs[4]).
+// hash (zk_hash_kind): 0 = SHA-256 (the reference, merkle.rs:1-2), 1 = field-native hash (fieldhash.hpp, configs[4]), 2 = BLAKE2s-256
+// (blake2s.hpp; launch_merkle_build, _build_coset, launch_compose_merkle and launch_fold_merkle only -- the others return
+// hipErrorInvalidValue for it).
 // The commit -> challenge hand-off.  mailbox is host-mapped memory: word 0 <- seq (last), words
 // kMailDigests.. <- the 2^top digests of depth `top` (top = 0: the root; the build stops at that depth and
 // the host finishes the tree, host_sha.hpp), then, if dump_src is set, 2^dump_log leaf values.  The

@@ -1297,6 +1297,8 @@ int zk_shard_lde_commit(zk_shard* s, uint8_t root_out[32]) {
 
 // Merkle hash and number of queries: like zk_ctx_set_hash / zk_ctx_set_queries, the same on every rank.
 int zk_shard_set_hash(zk_shard* s, int hash_kind) {
+    // refused before the handle is looked at: no setting of this class takes it
+    if (hash_kind == ZK_HASH_BLAKE2S) return fail(ZK_ERR_INVALID, "zk_shard_set_hash: BLAKE2s (hash 2) is not built for this entry point yet");
     if (!s) return fail(ZK_ERR_INVALID, "null prover");
     if (hash_kind != ZK_HASH_SHA256 && hash_kind != ZK_HASH_FIELD) return fail(ZK_ERR_INVALID, "zk_shard_set_hash: unknown hash %d", hash_kind);
     s->hash = hash_kind;

@@ -11,6 +11,8 @@
 
 #include <vector>
 
+#include "../../include/zkstark_amd.h"
+#include "blake2s.hpp"
 #include "field.hpp"
 #include "fieldhash.hpp"
 #include "sha256.hpp"
@@ -84,8 +86,8 @@ struct Channel {
 // coset = coset leaves (off = the format above).  The tree over the input layer of group j (id 1 + r0, len = N >> r0,
 // s = 2^steps_j) has len / s leaves; leaf c holds the slots u = 0 .. s-1, slot u = layer[c + u len / s] (the layer itself stays in
 // natural order): exactly what a query opens there, so a group is ONE leaf and ONE path of L - r0 - steps digests for leaf
-// x % (len / s).  Leaf hash: SHA-256 over the s slots, 4 bytes big-endian each (one block); field hash: the compression of
-// (slot_0 .. slot_{s-1}, 0, ..., 0, s) (fieldhash.hpp).  s = 1 is the one-value leaf.  Inner nodes are unchanged; tree 0 (f) and
+// x % (len / s).  Leaf hash: SHA-256 over the s slots, 4 bytes big-endian each (one block); BLAKE2s-256 over the same message
+// (blake2s.hpp); field hash: the compression of (slot_0 .. slot_{s-1}, 0, ..., 0, s) (fieldhash.hpp).  s = 1 is the one-value leaf.  Inner nodes are unchanged; tree 0 (f) and
 // the tree over the last layer (id 1 + log_n, never opened) keep one-value leaves.  Per query the three f tuples are sent as ever;
 // the separate cp(x) tuple is dropped (group 0's leaf contains it), then per group the s slot values in slot order, a u64 count and
 // the path.  With rot = (x % len) / (len / s), value t of the group (the one at (x % len + t len / s) % len) is slot (rot + t) % s.
@@ -167,7 +169,8 @@ inline void grind_commit(Channel& ch, uint64_t w) {
     ch.commit_bytes(b, 8);
 }
 
-// Merkle hash on the host (verifier): hash 0 = SHA-256 (merkle.rs:30-34, :42-45), 1 = field-native (fieldhash.hpp)
+// Merkle hash on the host (verifier), a zk_hash_kind: SHA-256 (merkle.rs:30-34, :42-45), field-native (fieldhash.hpp) or
+// BLAKE2s-256 (blake2s.hpp).  The channel and the grinding hash above are SHA-256 whatever the Merkle hash.
 inline const FieldHashConsts& host_fieldhash_consts() {
     static const FieldHashConsts c = [] { FieldHashConsts t; fieldhash_make_consts(t); return t; }();
     return c;
@@ -176,15 +179,16 @@ inline void bytes_to_digest(const uint8_t* b, Digest& d) {
     for (int i = 0; i < 8; ++i) d.w[i] = ((uint32_t)b[4 * i] << 24) | ((uint32_t)b[4 * i + 1] << 16) | ((uint32_t)b[4 * i + 2] << 8) | b[4 * i + 3];
 }
 inline void host_leaf_hash(uint32_t element, uint8_t out[32], int hash) {
-    if (hash) { digest_words_to_bytes(fieldhash_leaf(element, host_fieldhash_consts()).w, out); return; }
+    if (hash == ZK_HASH_BLAKE2S) { digest_words_to_bytes(blake2s_leaf(element).w, out); return; }
+    if (hash == ZK_HASH_FIELD) { digest_words_to_bytes(fieldhash_leaf(element, host_fieldhash_consts()).w, out); return; }
     uint8_t be[4] = {(uint8_t)(element >> 24), (uint8_t)(element >> 16), (uint8_t)(element >> 8), (uint8_t)element};
     Sha256 h; h.update(be, 4); h.finalize(out);
 }
 inline void host_node_hash(const uint8_t* l, const uint8_t* r, uint8_t out[32], int hash) {
-    if (hash) {
+    if (hash != ZK_HASH_SHA256) {
         Digest dl, dr;
         bytes_to_digest(l, dl); bytes_to_digest(r, dr);
-        digest_words_to_bytes(fieldhash_inner(dl, dr, host_fieldhash_consts()).w, out);
+        digest_words_to_bytes((hash == ZK_HASH_BLAKE2S ? blake2s_inner(dl, dr) : fieldhash_inner(dl, dr, host_fieldhash_consts())).w, out);
         return;
     }
     Sha256 h; h.update(l, 32); h.update(r, 32); h.finalize(out);
@@ -192,7 +196,8 @@ inline void host_node_hash(const uint8_t* l, const uint8_t* r, uint8_t out[32], 
 
 // Leaf of s <= 8 slots (coset leaves, above); s = 1 is host_leaf_hash.
 inline void host_coset_leaf_hash(const uint32_t* slots, size_t s, uint8_t out[32], int hash) {
-    if (hash) { digest_words_to_bytes(fieldhash_coset_leaf(slots, (uint32_t)s, host_fieldhash_consts()).w, out); return; }
+    if (hash == ZK_HASH_BLAKE2S) { digest_words_to_bytes(blake2s_coset_leaf(slots, s).w, out); return; }
+    if (hash == ZK_HASH_FIELD) { digest_words_to_bytes(fieldhash_coset_leaf(slots, (uint32_t)s, host_fieldhash_consts()).w, out); return; }
     uint8_t be[32];
     for (size_t u = 0; u < s; ++u) { be[4 * u] = (uint8_t)(slots[u] >> 24); be[4 * u + 1] = (uint8_t)(slots[u] >> 16); be[4 * u + 2] = (uint8_t)(slots[u] >> 8); be[4 * u + 3] = (uint8_t)slots[u]; }
     Sha256 h; h.update(be, 4 * s); h.finalize(out);

@@ -818,6 +818,8 @@ int zk_verifier_set_grinding(zk_verifier* v, uint32_t grind_bits) {
 }
 
 int zk_verifier_set_hash(zk_verifier* v, int hash_kind) {
+    // refused before the handle is looked at: no setting of this class takes it
+    if (hash_kind == ZK_HASH_BLAKE2S) return fail(ZK_ERR_INVALID, "zk_verifier_set_hash: BLAKE2s (hash 2) is not built for this entry point yet");
     if (!v) return fail(ZK_ERR_INVALID, "null verifier");
     if (hash_kind != ZK_HASH_SHA256 && hash_kind != ZK_HASH_FIELD) return fail(ZK_ERR_INVALID, "zk_verifier_set_hash: unknown hash %d", hash_kind);
     v->hash = hash_kind;

@@ -125,7 +125,7 @@ struct zk_ctx {
     uint32_t stop = 0;
     uint32_t* d_final = nullptr;        // 1 + 2^kFinalPolyMaxLog words, allocated by the first call that needs it
     std::vector<uint32_t> final_poly;   // the last proof's coefficients (stop = 0: the free term)
-    int hash = 0;                      // Merkle hash: 0 = SHA-256 (reference), 1 = field-native (configs[4])
+    int hash = 0;                      // Merkle hash (zk_hash_kind): 0 = SHA-256 (reference), 1 = field-native (configs[4]), 2 = BLAKE2s-256
     // opt-in reference self-checks (zk_ctx_set_checks; prover.rs:64-66, :148-159, :169, :228-251)
     bool checks = false;
     uint32_t* d_check = nullptr;        // N words of scratch + 2 result words
@@ -1116,9 +1116,13 @@ int zk_ctx_set_checks(zk_ctx* c, int on) {
     c->checks = on != 0;
     return ZK_OK;
 }
+// What the entry points that have no BLAKE2s yet (batched, sharded and chunked builds: DESIGN.md 7e) answer to ZK_HASH_BLAKE2S.
+static const char kNoBlake2s[] = "BLAKE2s (hash 2) is not built for this entry point yet";
 int zk_ctx_set_hash(zk_ctx* c, int hash_kind) {
     if (!c) return fail(ZK_ERR_INVALID, "null context");
-    if (hash_kind != ZK_HASH_SHA256 && hash_kind != ZK_HASH_FIELD) return fail(ZK_ERR_INVALID, "zk_ctx_set_hash: unknown hash %d", hash_kind);
+    if (hash_kind != ZK_HASH_SHA256 && hash_kind != ZK_HASH_FIELD && hash_kind != ZK_HASH_BLAKE2S)
+        return fail(ZK_ERR_INVALID, "zk_ctx_set_hash: unknown hash %d", hash_kind);
+    if (hash_kind == ZK_HASH_BLAKE2S && c->tail) return fail(ZK_ERR_INVALID, "zk_ctx_set_hash: %s", kNoBlake2s);
     c->hash = hash_kind;
     return ZK_OK;
 }
@@ -1391,7 +1395,7 @@ int zk_last_transcript(const zk_ctx* c, zk_transcript_info* out) {
 static int verify_entry(const char* who, const uint8_t* proof, size_t len, const uint8_t* state, uint32_t log_n, uint32_t log_b,
                         uint32_t public_last, int hash_kind, uint32_t q, uint32_t grind, uint32_t fold, int32_t* check_out,
                         const char* replay_note, const char* reject_note, bool coset = false, uint32_t stop = 0) {
-    if (hash_kind != ZK_HASH_SHA256 && hash_kind != ZK_HASH_FIELD) return fail(ZK_ERR_INVALID, "%s: unknown hash %d", who, hash_kind);
+    if (hash_kind != ZK_HASH_SHA256 && hash_kind != ZK_HASH_FIELD && hash_kind != ZK_HASH_BLAKE2S) return fail(ZK_ERR_INVALID, "%s: unknown hash %d", who, hash_kind);
     if (fold < 1 || fold > kMaxFoldLog) return fail(ZK_ERR_INVALID, "%s: need 1 <= fold_log <= %u (got %u)", who, kMaxFoldLog, fold);
     int rc = state ? verify_transcript(proof, len, state, log_n, log_b, q, grind, fold, coset, stop) : 0;
     const bool in_replay = rc != 0;
@@ -1428,11 +1432,14 @@ int zk_verify_grind(const uint8_t* proof, size_t len, const uint8_t* state, uint
 }
 int zk_verify_check(const uint8_t* proof, size_t len, const uint8_t* state, uint32_t log_n, uint32_t log_b, uint32_t public_last,
                     int hash_kind, uint32_t n_queries, int32_t* check_out) {
+    // this entry point and zk_verify_fold keep the two hashes they were defined with; BLAKE2s proofs of every setting go to zk_verify_stop
+    if (hash_kind == ZK_HASH_BLAKE2S) return fail(ZK_ERR_INVALID, "zk_verify_check: BLAKE2s (hash 2) proofs are verified by zk_verify_stop");
     return zk_verify_grind(proof, len, state, log_n, log_b, public_last, hash_kind, n_queries, 0, check_out);
 }
 int zk_verify_fold(const uint8_t* proof, size_t len, const uint8_t* state, uint32_t log_n, uint32_t log_b, uint32_t public_last,
                    int hash_kind, uint32_t n_queries, uint32_t grind_bits, uint32_t fold_log, int32_t* check_out) {
     if (!proof || !check_out) return fail(ZK_ERR_INVALID, "zk_verify_fold: null argument");
+    if (hash_kind == ZK_HASH_BLAKE2S) return fail(ZK_ERR_INVALID, "zk_verify_fold: BLAKE2s (hash 2) proofs are verified by zk_verify_stop");
     return verify_entry("zk_verify_fold", proof, len, state, log_n, log_b, public_last, hash_kind, n_queries, grind_bits, fold_log, check_out, nullptr, "");
 }
 // zk_verify_fold for proofs made with coset leaves (transcript.hpp)
@@ -1469,14 +1476,14 @@ size_t zk_proof_data_len_queries(uint32_t log_n, uint32_t log_b, uint32_t n_quer
 size_t zk_proof_data_len(uint32_t log_n, uint32_t log_b) { return zk_proof_data_len_fold(log_n, log_b, 1, 0, 1); }
 
 int zk_compute_root_from_path_ex(uint32_t element, size_t index, const uint8_t* path, size_t path_len, uint8_t out[32], int hash_kind) {
-    if ((!path && path_len) || !out || path_len > 62 || (hash_kind != 0 && hash_kind != 1))
+    if ((!path && path_len) || !out || path_len > 62 || hash_kind < ZK_HASH_SHA256 || hash_kind > ZK_HASH_BLAKE2S)
         return fail(ZK_ERR_INVALID, "zk_compute_root_from_path: bad argument");
     compute_root_from_path(element, index, path, path_len, out, hash_kind);
     return ZK_OK;
 }
 // the root from the s = 1, 2, 4 or 8 values of coset leaf `leaf` and its path
 int zk_compute_root_from_coset(const uint32_t* values, uint32_t s, size_t leaf, const uint8_t* path, size_t path_len, uint8_t out[32], int hash_kind) {
-    if (!values || (!path && path_len) || !out || path_len > 62 || (hash_kind != 0 && hash_kind != 1) || (s != 1 && s != 2 && s != 4 && s != 8))
+    if (!values || (!path && path_len) || !out || path_len > 62 || hash_kind < ZK_HASH_SHA256 || hash_kind > ZK_HASH_BLAKE2S || (s != 1 && s != 2 && s != 4 && s != 8))
         return fail(ZK_ERR_INVALID, "zk_compute_root_from_coset: bad argument");
     compute_root_from_coset(values, s, leaf, path, path_len, out, hash_kind);
     return ZK_OK;
@@ -1503,6 +1510,7 @@ int zk_tail_create(int device, uint32_t log_n_tail, uint32_t log_b, uint32_t shi
 
 int zk_tail_run(zk_ctx* c, const uint32_t* d_layer0, void* src_stream, zk_channel* chan, int hash_kind,
                 uint32_t* betas_out, uint8_t* roots_out, uint32_t* free_term_out) {
+    if (hash_kind == ZK_HASH_BLAKE2S) return fail(ZK_ERR_INVALID, "zk_tail_run: %s", kNoBlake2s);
     if (!c || !c->tail || !d_layer0 || !chan || !betas_out || !roots_out || !free_term_out)
         return fail(ZK_ERR_INVALID, "zk_tail_run: bad argument");
     if (hash_kind != ZK_HASH_SHA256 && hash_kind != ZK_HASH_FIELD) return fail(ZK_ERR_INVALID, "zk_tail_run: unknown hash %d", hash_kind);
@@ -1677,11 +1685,12 @@ int zk_dev_gather(const uint32_t* d_src, const uint64_t* d_offsets, uint32_t cou
 
 // ---- stand-alone primitives --------------------------------------------------------
 int zk_dev_merkle_build_ex(const uint32_t* d_vals, uint32_t log_m, uint32_t* d_nodes, void* stream, int hash_kind) {
-    if (!d_vals || !d_nodes || log_m > 30 || (hash_kind != 0 && hash_kind != 1)) return fail(ZK_ERR_INVALID, "zk_dev_merkle_build: bad argument");
+    if (!d_vals || !d_nodes || log_m > 30 || hash_kind < ZK_HASH_SHA256 || hash_kind > ZK_HASH_BLAKE2S) return fail(ZK_ERR_INVALID, "zk_dev_merkle_build: bad argument");
     HIPCHK(launch_merkle_build(d_vals, log_m, d_nodes, (hipStream_t)stream, dev_prof(), MailArgs{}, hash_kind));
     return ZK_OK;
 }
 int zk_dev_merkle_build_interleaved(const uint32_t* d_recv, uint32_t log_parts, uint32_t log_cnt, uint32_t* d_nodes, void* stream, int hash_kind) {
+    if (hash_kind == ZK_HASH_BLAKE2S) return fail(ZK_ERR_INVALID, "zk_dev_merkle_build_interleaved: %s", kNoBlake2s);
     if (!d_recv || !d_nodes || log_parts + log_cnt > 30 || (hash_kind != 0 && hash_kind != 1))
         return fail(ZK_ERR_INVALID, "zk_dev_merkle_build_interleaved: bad argument");
     HIPCHK(launch_merkle_build_interleaved(d_recv, log_parts, log_cnt, d_nodes, (hipStream_t)stream, dev_prof(), hash_kind));
@@ -1837,6 +1846,7 @@ void committer_drop_pending(zk_committer* k) {
 // thread hashes the levels above and a stream-ordered copy completes d_nodes (merkle.rs:14-51 either way).
 int zk_dev_merkle_commit(zk_committer* k, const uint32_t* d_src, uint32_t log_parts, uint32_t log_cnt, uint32_t* d_nodes, void* stream,
                          int hash_kind, uint8_t root_out[32]) {
+    if (hash_kind == ZK_HASH_BLAKE2S) return fail(ZK_ERR_INVALID, "zk_dev_merkle_commit: %s", kNoBlake2s);
     if (!k || !d_src || !d_nodes || !root_out || log_parts + log_cnt > 30 || (hash_kind != 0 && hash_kind != 1))
         return fail(ZK_ERR_INVALID, "zk_dev_merkle_commit: bad argument");
     HIPCHK(hipSetDevice(k->device));
@@ -1862,6 +1872,7 @@ namespace zk {
 namespace impl {
 int dev_compose_block_commit(zk_committer* k, const zk_dom* glob, ComposeBlockArgs geom, uint32_t first, uint32_t last, const uint32_t alpha_raw[3],
                              uint32_t* d_nodes, hipStream_t s, int hash_kind, uint8_t root_out[32], int (*enqueued)(void*), void* user) {
+    if (hash_kind == ZK_HASH_BLAKE2S) return fail(ZK_ERR_INVALID, "dev_compose_block_commit: %s", kNoBlake2s);
     if (!k || !glob || !geom.a.f || !geom.a.inv_xm1 || !geom.halo || !d_nodes || !root_out || (hash_kind != 0 && hash_kind != 1) ||
         geom.log_m > 30 || geom.lg + geom.log_cnt > geom.log_m)
         return fail(ZK_ERR_INVALID, "dev_compose_block_commit: bad argument");
@@ -1891,6 +1902,7 @@ int dev_compose_block_commit(zk_committer* k, const zk_dom* glob, ComposeBlockAr
 // whole tree down to depth `top` on the device, the rest on the calling thread, root returned.
 int zk_dev_merkle_commit_finish(zk_committer* k, uint32_t* d_nodes, uint32_t log_m, uint32_t log_chunks, void* stream, int hash_kind,
                                 uint8_t root_out[32]) {
+    if (hash_kind == ZK_HASH_BLAKE2S) return fail(ZK_ERR_INVALID, "zk_dev_merkle_commit_finish: %s", kNoBlake2s);
     if (!k || !d_nodes || !root_out || log_m > 30 || log_chunks > 10 || log_chunks > log_m || (hash_kind != 0 && hash_kind != 1))
         return fail(ZK_ERR_INVALID, "zk_dev_merkle_commit_finish: bad argument");
     HIPCHK(hipSetDevice(k->device));
@@ -1907,6 +1919,7 @@ int zk_dev_merkle_commit_finish(zk_committer* k, uint32_t* d_nodes, uint32_t log
 
 int zk_dev_merkle_build_chunk(const uint32_t* d_recv, uint32_t log_parts, uint32_t log_cnt, uint32_t* d_nodes, uint32_t log_m,
                               uint32_t chunk, void* stream, int hash_kind) {
+    if (hash_kind == ZK_HASH_BLAKE2S) return fail(ZK_ERR_INVALID, "zk_dev_merkle_build_chunk: %s", kNoBlake2s);
     if (!d_recv || !d_nodes || log_m > 30 || log_parts + log_cnt > log_m || (hash_kind != 0 && hash_kind != 1) ||
         chunk >= (1u << (log_m - log_parts - log_cnt)))
         return fail(ZK_ERR_INVALID, "zk_dev_merkle_build_chunk: bad argument");
@@ -1914,6 +1927,7 @@ int zk_dev_merkle_build_chunk(const uint32_t* d_recv, uint32_t log_parts, uint32
     return ZK_OK;
 }
 int zk_dev_merkle_finish(uint32_t* d_nodes, uint32_t log_m, uint32_t log_chunks, void* stream, int hash_kind) {
+    if (hash_kind == ZK_HASH_BLAKE2S) return fail(ZK_ERR_INVALID, "zk_dev_merkle_finish: %s", kNoBlake2s);
     if (!d_nodes || log_m > 30 || log_chunks > 10 || log_chunks > log_m || (hash_kind != 0 && hash_kind != 1))
         return fail(ZK_ERR_INVALID, "zk_dev_merkle_finish: bad argument");
     HIPCHK(launch_merkle_finish(d_nodes, log_m, log_chunks, (hipStream_t)stream, dev_prof(), hash_kind));
@@ -1942,7 +1956,7 @@ int zk_merkle_build_host(int device, const uint32_t* vals, size_t m, uint8_t* no
 
 int zk_merkle_build_host_ex(int device, const uint32_t* vals, size_t m, uint8_t* nodes_out, int hash_kind) {
     if (!vals || !nodes_out) return fail(ZK_ERR_INVALID, "zk_merkle_build_host: null argument");
-    if (hash_kind != 0 && hash_kind != 1) return fail(ZK_ERR_INVALID, "zk_merkle_build_host: unknown hash %d", hash_kind);
+    if (hash_kind < ZK_HASH_SHA256 || hash_kind > ZK_HASH_BLAKE2S) return fail(ZK_ERR_INVALID, "zk_merkle_build_host: unknown hash %d", hash_kind);
     if (m == 0 || (m & (m - 1)) || m > ((size_t)1 << 30))      // merkle.rs:16-21 asserts a power of two
         return fail(ZK_ERR_INVALID, "zk_merkle_build_host: size %zu is not a power of two (merkle.rs:18)", m);
     uint32_t log_m = 0;
@@ -1969,7 +1983,7 @@ int zk_merkle_build_host_ex(int device, const uint32_t* vals, size_t m, uint8_t*
 // Roofline probe: the compiled inner hash in a dependent chain, `launches` launches back to back (steady state,
 // no residency tail), waves_per_simd resident waves on every SIMD.  Measurement only.
 int zk_probe_hash_chain(int device, int hash_kind, uint32_t waves_per_simd, uint32_t hashes, uint32_t launches, zk_chain_probe* out) {
-    if (!out || (hash_kind != ZK_HASH_SHA256 && hash_kind != ZK_HASH_FIELD) || waves_per_simd < 1 || waves_per_simd > 8 || !hashes || !launches)
+    if (!out || hash_kind < ZK_HASH_SHA256 || hash_kind > ZK_HASH_BLAKE2S || waves_per_simd < 1 || waves_per_simd > 8 || !hashes || !launches)
         return fail(ZK_ERR_INVALID, "zk_probe_hash_chain: bad argument");
     if (!abi_bytes(out, "zk_probe_hash_chain")) return ZK_ERR_INVALID;
     zk_chain_probe* const user_out = out;

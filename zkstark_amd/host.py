@@ -12,7 +12,15 @@ from . import _lib
 from ._lib import ZkError, check
 
 P = 3221225473  # main.rs:13
-HASHES = {"sha256": 0, "field": 1}   # Merkle hash: the reference's SHA-256, or the field-native one (configs[4])
+# Merkle hash: the reference's SHA-256, the field-native one (configs[4]), or BLAKE2s-256 (RFC 7693; one compression per tree node).
+# "blake2s" is taken by Context, Merkle, Proof.verify, compute_root_from_path, compute_root_from_coset and probe_hash_chain.
+HASHES = {"sha256": 0, "field": 1, "blake2s": 2}
+
+
+def _no_blake2s(who, hash):
+    """BatchContext, Verifier and ShardContext have no BLAKE2s yet (their C setters refuse it too)."""
+    if hash == "blake2s":
+        raise ValueError(f"{who}: hash='blake2s' is not built for this class yet (Context, Merkle and Proof.verify take it)")
 
 
 def _u32arr(a):
@@ -163,8 +171,13 @@ class Proof:
 
     data_len = expected_len
 
+    def _general(self):
+        """Folded, coset-leaf, stopped and BLAKE2s proofs go through the general entry points (zk_verify_check and zk_verify_fold keep
+        the two hashes they were defined with: a BLAKE2s proof of any setting is verified by zk_verify_stop)."""
+        return self.fold_log != 1 or self.coset_leaves or self.stop_log or self.hash == "blake2s"
+
     def _verify_general(self, strict, out):
-        if self.stop_log:
+        if self.stop_log or self.hash == "blake2s":
             return _lib.load().zk_verify_stop(self.data, len(self.data), self.state if strict else None, self.log_n, self.log_blowup,
                                               self.public_last, HASHES[self.hash], self.queries, self.grind_bits, self.fold_log,
                                               int(self.coset_leaves), self.stop_log, C.byref(out))
@@ -176,7 +189,7 @@ class Proof:
         """strict=True also replays the channel: challenges must come from the transcript and `state`
         must be its final state (the reference trusts the proof for both, proof.rs:22-37); with grind_bits > 0 it also
         checks the proof-of-work nonce."""
-        if self.fold_log != 1 or self.coset_leaves or self.stop_log:  # folded by 2^fold_log between commitments (zk_ctx_set_fold), coset leaves, early stop
+        if self._general():  # folded by 2^fold_log between commitments (zk_ctx_set_fold), coset leaves, early stop, BLAKE2s
             check(self._verify_general(strict, C.c_int32()))
             return
         if self.grind_bits:
@@ -191,7 +204,7 @@ class Proof:
         """The number of the check the CPU verifier stops at (zk_verify_grind): 0 = accepted; otherwise what verify()'s
         error names.  Never raises for a rejected proof."""
         out = C.c_int32()
-        if self.fold_log != 1 or self.coset_leaves or self.stop_log:
+        if self._general():
             rc = self._verify_general(strict, out)
         else:
             rc = _lib.load().zk_verify_grind(self.data, len(self.data), self.state if strict else None, self.log_n, self.log_blowup,
@@ -523,6 +536,7 @@ class BatchContext:
         """fold_log: FRI folding factor 2^fold_log between commitments for every proof of the batch (zk_batch_set_fold; 1 = the
         reference).  coset_leaves: one coset per Merkle leaf of the FRI trees (zk_batch_set_coset_leaves).  stop_log: every proof stops
         FRI at a polynomial of degree < 2^stop_log and sends its coefficients (zk_batch_set_fri_stop; 0 = fold to a constant)."""
+        _no_blake2s("BatchContext", hash)
         self.log_n, self.log_blowup, self.log_batch, self.hash, self.queries = log_n, log_blowup, log_batch, hash, queries
         self.grind_bits, self.fold_log = grind_bits, 1
         self.coset_leaves = False
@@ -631,6 +645,7 @@ class Verifier:
         """fold_log: the FRI folding factor 2^fold_log of the proofs to check (zk_verifier_set_fold; 1 = the reference).
         coset_leaves: the proofs were made with coset leaves (zk_verifier_set_coset_leaves; Context(coset_leaves=True)).
         stop_log: the proofs stop FRI early at a polynomial of 2^stop_log coefficients (zk_verifier_set_fri_stop; Context(stop_log=))."""
+        _no_blake2s("Verifier", hash)
         self.log_n, self.log_blowup, self.hash, self.queries, self.grind_bits = log_n, log_blowup, hash, queries, grind_bits
         self.fold_log = 1
         self.coset_leaves = False
@@ -755,6 +770,7 @@ class ShardContext:
     def __init__(self, log_n, log_blowup, rank, world, unique_id=None, device=0, transport=None, min_layer_log=0, min_chunk_log=0,
                  overlap_min_log=0, force_collectives=False, no_root_board=False, hash="sha256", queries=1, plain_collectives=False,
                  single_build_stream=False, single_communicator=False, timeout_s=0.0, exchange_cp=False, peer_copy=False):
+        _no_blake2s("ShardContext", hash)
         self.log_n, self.log_blowup, self.rank, self.world = log_n, log_blowup, rank, world
         self.hash, self.queries = hash, queries
         self._transport = transport                      # keeps the callbacks alive
