@@ -15,18 +15,27 @@ LATENCY_LOG = 17           # ZK_MERKLE_LATENCY_LOG: throughput launches while a 
 FIELD_ROW_MAX = 16         # ZK_FIELD_ROW_MAX_NODES: field levels of <= this many nodes per workgroup use the 16-lane row form
 FIELD_QUAD_MAX = 64        # ZK_FIELD_QUAD_MAX_NODES: ... of <= this many, the quad form
 FIELD_ROW_LEAF_MAX = 32    # ZK_FIELD_ROW_LEAF_MAX: a workgroup with <= this many field leaves hashes them in the row form
+WG_THREADS = 256           # kWgThreads: threads of a merkle_wg_kernel workgroup
 WG_MAX_LOG = 10            # kWgMaxLog: levels of one merkle_wg_kernel phase, and nodes a continuation holds (2^10)
 CONTINUE_US = 6.0          # kContinueUs
 LAUNCH_US = 10.0           # kLaunchUs
 CONTINUATION = True        # ZK_MERKLE_CONTINUATION
-SHA, FIELD = 0, 1          # hash_kind
+SHA, FIELD, B2S = 0, 1, 2  # hash_kind
+# BLAKE2s one lane per hash: its instruction counts (csrc/kernels.hpp) times the time per instruction of the SHA-256 one-lane entries,
+# in the operation order of kernels.hip -- the planner compares costs with a strict <, so the doubles must be the same bit for bit
+B2S_INNER_OPS, SHA_INNER_OPS = 987.0, 2293.0        # kB2sInnerOps, kShaInnerOps
+B2S_LEAF_OPS, SHA_LEAF_OPS = 954.0, 1259.0          # kB2sLeafOps, kShaLeafOps
+B2S_LEVEL_US = B2S_INNER_OPS * 4.6 / SHA_INNER_OPS  # kB2sLevelUs
+B2S_LEAF_US = B2S_LEAF_OPS * 2.6 / SHA_LEAF_OPS     # kB2sLeafUs
 
 
 def wg_level_us(w, h):
     """wg_level_us: one workgroup's microseconds for a level of w nodes."""
     if w == 0:
         return 0.0
-    if h:
+    if h == B2S:
+        return float((w + 255) // 256) * B2S_LEVEL_US
+    if h == FIELD:
         if w <= FIELD_ROW_MAX:
             return float((w + 15) // 16) * 3.7
         if w <= FIELD_QUAD_MAX:
@@ -40,10 +49,10 @@ def wg_phase_us(leaf, cnt_log, levels, h, blocks):
     cnt = 1 << cnt_log
     if not leaf:
         us = 1.0
-    elif h:
+    elif h == FIELD:
         us = float((cnt + 15) // 16) * 3.7 if cnt <= FIELD_ROW_LEAF_MAX else float((cnt + 255) // 256) * 10.8
     else:
-        us = float((cnt + 255) // 256) * 2.6
+        us = float((cnt + 255) // 256) * (B2S_LEAF_US if h == B2S else 2.6)
     for t in range(1, levels + 1):
         us += wg_level_us(cnt >> t, h)
     return us * float(blocks) / 256.0 if blocks > 256 else us
@@ -141,15 +150,21 @@ def chunk_plans(log_m, log_chunks, h, lat=LATENCY_LOG, counter=False, top=0):
 
 
 def level_form(w, h):
-    """The form merkle_wg_kernel hashes a level of w nodes per workgroup in."""
-    if h:
+    """The form merkle_wg_kernel hashes a level of w nodes per workgroup in.  BLAKE2s has the one-lane form only; "lane2" names
+    its levels of more than 256 nodes per workgroup, where a thread hashes two nodes (a1 in the kernel)."""
+    if h == B2S:
+        return "lane2" if w > WG_THREADS else "lane"
+    if h == FIELD:
         return "row" if w <= FIELD_ROW_MAX else "quad" if w <= FIELD_QUAD_MAX else "lane"
     return "quad" if w <= 64 else "split" if w <= 128 else "lane"
 
 
 def forms(launches, h):
     """The code paths the launches take: ("sub", "leaf" | "inner", k), ("leaf", "row" | "lane") for the leaf hashes of a
-    merkle_wg_kernel launch, and (phase, form) for every level it hashes (phase 1: the continuation)."""
+    merkle_wg_kernel launch, and (phase, form) for every level it hashes (phase 1: the continuation).  BLAKE2s, whose levels
+    have one form, also names the edges of the lane path: ("leaf", "lane4") for a leaf phase of more than 256 leaves per
+    workgroup (a thread keeps several fetched inputs: kPer > 1 in use), and ("load", phase, "one" | "many") for the first load
+    of an inner-mode launch (phase 0) and of the continuation (phase 1) of at most / more than 256 digests."""
     fs = set()
     for la in launches:
         if la.kind == "sub":
@@ -157,7 +172,14 @@ def forms(launches, h):
             continue
         cnt = 1 << la.k
         if la.leaf:
-            fs.add(("leaf", "row" if h and cnt <= FIELD_ROW_LEAF_MAX else "lane"))
+            if h == B2S:
+                fs.add(("leaf", "lane4" if cnt > WG_THREADS else "lane"))
+            else:
+                fs.add(("leaf", "row" if h == FIELD and cnt <= FIELD_ROW_LEAF_MAX else "lane"))
+        elif h == B2S:
+            fs.add(("load", 0, "many" if cnt > WG_THREADS else "one"))
+        if h == B2S and la.j2:
+            fs.add(("load", 1, "many" if (1 << (la.span - la.k)) > WG_THREADS else "one"))
         for t in range(1, la.k + 1):
             fs.add((0, level_form(cnt >> t, h)))
         for t in range(1, la.j2 + 1):
@@ -175,7 +197,7 @@ def profile(launches):
 
 
 # ---- the grid of tests/test_gpu_merkle_plans.py ---------------------------------------------------------------------------
-MAX_LOG = {SHA: 22, FIELD: 20}       # largest tree per hash
+MAX_LOG = {SHA: 22, FIELD: 20, B2S: 20}   # largest tree per hash
 LATS = range(17, 11, -1)             # zk_dev_set_merkle_latency_log values the grid sweeps (the default first)
 TOPS = (0, 1, 3, 8)                  # committer hand-over depths (zk_committer_set_top; SHA-256 only)
 
@@ -184,13 +206,14 @@ def _wg_shape(launches):
     return tuple((la.leaf, la.span, la.k, la.j2) for la in launches if la.kind == "wg")
 
 
-def latency_shapes(h, counter, top=0):
+def latency_shapes(h, counter, top=0, leaf_mode=True):
     """The smallest (log_m, lat) for every distinct latency phase (the merkle_wg_kernel launches, their (j, j2) splits and
     whether they hash the leaves) that trees up to MAX_LOG[h] leaves reach for lat in LATS."""
     seen = {}
     for log_m in range(MAX_LOG[h] + 1):
         for lat in LATS:
-            seen.setdefault((_wg_shape(plan(log_m, h, counter, top, lat)), min(top, log_m) if top < log_m else 0), (log_m, lat))
+            shape = _wg_shape(plan(log_m, h, counter, top, lat, leaf_mode=leaf_mode))
+            seen.setdefault((shape, min(top, log_m) if top < log_m else 0), (log_m, lat))
     return sorted(seen.values())
 
 
@@ -219,6 +242,23 @@ def commit_cases(h):
     return sorted(out)
 
 
+def context_cases(h):
+    """Whole trees with a counter that only a context builds (BLAKE2s: zk_dev_merkle_commit refuses the hash), through
+    Context.merkle_commit(0): (log_m, lat).  The smallest context has a layer 0 of 2^3 values; the smaller trees with a counter
+    are the last FRI trees of a proof (tests/test_gpu_merkle_plans.py: the context trees after a second trace)."""
+    return [(log_m, lat) for log_m, lat in latency_shapes(h, True) if log_m >= 3]
+
+
+def coset_cases(h):
+    """Trees with coset leaves through Context.merkle_commit(0, coset_steps): one coset_leaf_hash_kernel launch, then the
+    inner-mode build with a counter: (steps, log_m, lat) for a tree of 2^log_m leaves over 2^(log_m + steps) values.  Every
+    latency phase of inner mode, and below a switch at 2^12 an inner throughput launch of k = 1 .. 4 levels; every steps in
+    both groups."""
+    out = {(1 + log_m % 3, log_m, lat) for log_m, lat in latency_shapes(h, True, leaf_mode=False) if log_m >= 1}
+    out |= {(1, 13, 12), (2, 14, 12), (3, 15, 12), (2, 16, 12)}
+    return sorted(out)
+
+
 def chunk_cases(h):
     """zk_dev_merkle_build_chunk for every chunk, then the finish pass: (log_m, log_chunks, lat, log_parts, top); top None =
     zk_dev_merkle_finish, else zk_dev_merkle_commit_finish with that committer top."""
@@ -236,6 +276,11 @@ def chunk_cases(h):
     return out
 
 
+# BLAKE2s forms that no latency log of LATS reaches: the smallest whole tree with a counter at a raised log for each
+# (tests/test_merkle_plans.py names them)
+B2S_RAISED_CASES = [(19, 19), (20, 20)]
+
+
 def chunk_launches(h, log_m, log_chunks, lat, top):
     chunks, fin = chunk_plans(log_m, log_chunks, h, lat, counter=top is not None, top=top or 0)
     return [la for c in chunks for la in c] + fin
@@ -246,6 +291,12 @@ def grid_forms(h):
     fs = set()
     for log_m, lat in build_cases(h):
         fs |= forms(plan(log_m, h, False, 0, lat), h)
+    if h == B2S:                                          # no committer and no chunks for this hash: the context grids instead
+        for log_m, lat in context_cases(h) + B2S_RAISED_CASES:
+            fs |= forms(plan(log_m, h, True, 0, lat), h)
+        for _, log_m, lat in coset_cases(h):
+            fs |= forms(plan(log_m, h, True, 0, lat, leaf_mode=False), h)
+        return fs
     for log_m, lat, top, _ in commit_cases(h):
         fs |= forms(plan(log_m, h, True, top, lat), h)
     for log_m, lc, lat, _, top in chunk_cases(h):
@@ -256,8 +307,16 @@ def grid_forms(h):
 @functools.lru_cache(maxsize=None)
 def all_forms(h, lats=range(12, 25)):
     """Every form the planner reaches for hash h: whole trees of 2^0 .. 2^30 leaves with and without a counter, every committer
-    top, every latency log the library accepts, and chunked builds."""
+    top, every latency log the library accepts, and chunked builds.  BLAKE2s has neither tops nor chunks: whole trees with and
+    without a counter, from the leaves and (below a coset-leaf launch) in inner mode."""
     fs = set()
+    if h == B2S:
+        for log_m in range(31):
+            for lat in lats:
+                for counter in (False, True):
+                    for leaf_mode in (True, False):
+                        fs |= forms(plan(log_m, h, counter, 0, lat, leaf_mode=leaf_mode), h)
+        return fs
     for log_m in range(31):
         for lat in lats:
             for counter in (False, True):

@@ -1,7 +1,8 @@
 """BLAKE2s-256 as a Merkle hash on the GPU (ZK_HASH_BLAKE2S): every node of trees built by the latency kernel alone and
 by b2s_subtree_kernel in both modes and at every k, against hashlib.blake2s; whole proofs of the one-call provers against
-tests/blake2s_ref.py, byte for byte with the final state and every committed tree; one live context walked through the three hashes;
-and the entry points that refuse the hash.  Equality everywhere."""
+tests/blake2s_ref.py, byte for byte with the final state and every committed tree -- up to 2^17-leaf trees, with the switch lowered so
+that the fused leaf sources run at every k, and with early launch; one live context walked through the three hashes; and the entry
+points that refuse the hash.  Equality everywhere.  (Every launch plan, node for node: tests/test_gpu_merkle_plans.py.)"""
 import ctypes as C
 import functools
 
@@ -103,6 +104,14 @@ CASES = [  # log_n, log_b, switch (0: default), K, coset, D, q, bits
     pytest.param(10, 3, 0, 3, True, 0, 1, 0, id="K3-coset"),
     pytest.param(10, 3, 0, 3, True, 3, 1, 0, id="K3-coset-D3"),
     pytest.param(10, 3, 0, 1, False, 0, 3, 8, id="q3-grind8"),
+    # 2^17-leaf trees: the largest the latency kernel takes alone (j = 9, j2 = 8), every continuation split below; seven queries
+    pytest.param(14, 3, 0, 1, False, 0, 7, 0, id="14-3-q7"),
+    # switch at 2^12: PlainSrc and ComposeSrc leaf launches of k = 4 with an inner launch of k = 1 above them, FoldSrc leaf launches of
+    # k = 4, 3, 2, 1 on the 2^16 .. 2^13-leaf trees
+    pytest.param(14, 3, 12, 1, False, 0, 1, 0, id="14-3-switch12"),
+    # coset trees above the switch inside a proof: coset_leaf_hash_kernel<2, S>, then inner throughput launches
+    pytest.param(13, 3, 12, 2, True, 0, 1, 0, id="13-3-switch12-K2-coset"),
+    pytest.param(13, 3, 12, 3, True, 3, 1, 0, id="13-3-switch12-K3-coset-D3"),
 ]
 
 
@@ -119,6 +128,31 @@ def test_zk_prove_is_the_reference_proof(zk, orc, log_n, log_b, lat, K, coset, D
             _assert_trees(ctx, ref, log_n, K, coset, D)
             again = ctx.prove(trace)                                  # a second proof on the same context
             _assert_proof(ctx, again, ref, "second proof")
+
+
+A1_OTHER = 2718281
+
+
+@pytest.mark.parametrize("log_n,log_b,lat", [pytest.param(10, 3, 0, id="10-3"), pytest.param(14, 3, 12, id="14-3-switch12")])
+def test_early_launch_is_the_reference_proof(zk, orc, log_n, log_b, lat):
+    """zk_ctx_set_early_launch with BLAKE2s: round r + 1's fold + commit launches (FoldSrc through merkle_wg_kernel<.., 2>, and at the
+    lowered switch through b2s_subtree_kernel) are enqueued behind the gate word and read their challenge when they run.  The gated proof
+    is the reference proof, so is a second proof of another trace on the same gated context, and so is the proof with the gate off again."""
+    lib = zk.load()
+    n = 1 << log_n
+    ref, ref_other = blake2s_ref.proof(orc, log_n, log_b), blake2s_ref.proof(orc, log_n, log_b, a1=A1_OTHER)
+    assert ref.data != ref_other.data
+    with _latency_log(lib, lat):
+        with zk.Context(log_n, log_b, hash="blake2s") as ctx:
+            assert ctx.set_early_launch(True) is True and lib.zk_ctx_get_early_launch(ctx._h) == 1   # not silently off
+            _assert_proof(ctx, ctx.prove(_trace(n)), ref, "gated proof")
+            _assert_trees(ctx, ref, log_n, 1, False, 0)
+            _assert_proof(ctx, ctx.prove(_trace(n, A1_OTHER)), ref_other, "gated proof of a second trace")
+            _assert_trees(ctx, ref_other, log_n, 1, False, 0)
+            assert lib.zk_ctx_get_early_launch(ctx._h) == 1
+            assert ctx.set_early_launch(False) is False
+            _assert_proof(ctx, ctx.prove(_trace(n)), ref, "the gate off again")
+            _assert_trees(ctx, ref, log_n, 1, False, 0)
 
 
 def test_channel_resident_and_many(zk, orc):

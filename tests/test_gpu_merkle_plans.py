@@ -8,9 +8,13 @@ separate stores in every form (tests/merkle_plans.py names the forms).  So every
     algorithmic bytes per kernel class are checked against what the mirror predicts;
   - the trees of a context and of a batch after a proof of a SECOND trace, so that a node that is no longer stored still holds
     the first trace's value and fails.
+BLAKE2s (its throughput kernel is a copy, not an instance, of merkle_subtree_kernel) is held to hashlib.blake2s
+(tests/blake2s_ref.py) in the same way: the plain build on the same grid, and -- the committer and the chunk builds refuse the
+hash -- the plans with a counter through a context's stand-alone commitments, with and without coset leaves.
 """
 import ctypes as C
 
+import blake2s_ref
 import merkle_plans as mp
 import numpy as np
 import pytest
@@ -18,26 +22,33 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 P = 3221225473
-HASH_NAMES = {mp.SHA: "sha256", mp.FIELD: "field"}
+HASH_NAMES = {mp.SHA: "sha256", mp.FIELD: "field", mp.B2S: "blake2s"}
+HASH_OF = {name: h for h, name in HASH_NAMES.items()}
 MERKLE_CLASSES = ("merkle_leaf", "merkle_inner", "merkle_top")
 GUARD_NODES = 64
 
 
 class Heaps:
     """Oracle heaps over the grid's leaves, one per (hash, log_m), kept for the cases that share them.  The oracle's hash is
-    selected per heap and set back to SHA-256 afterwards."""
+    selected per heap and set back to SHA-256 afterwards.  The oracle has no BLAKE2s: those heaps are hashlib's
+    (blake2s_ref.tree), over leaves that are any 32-bit word, 0 and 0xffffffff among them."""
 
     def __init__(self, orc):
         self.orc, self.cache = orc, {}
 
     @staticmethod
-    def leaves(log_m):
-        v = np.random.default_rng(5150 + log_m).integers(0, P, size=1 << log_m, dtype=np.uint64).astype(np.uint32)
+    def leaves(log_m, h=mp.SHA):
+        top = 1 << 32 if h == mp.B2S else P
+        v = np.random.default_rng(5150 + log_m).integers(0, top, size=1 << log_m, dtype=np.uint64).astype(np.uint32)
         v[0] = 0
-        v[-1] = P - 1
+        v[-1] = top - 1
         return v
 
-    def build(self, h, vals):
+    def build(self, h, vals, steps=0):
+        """steps: coset leaves of 2^steps values (BLAKE2s only here)."""
+        if h == mp.B2S:
+            return blake2s_ref.tree(vals, steps)
+        assert steps == 0
         self.orc.set_hash(h)
         try:
             return self.orc.merkle_build(vals)
@@ -49,7 +60,7 @@ class Heaps:
         if key not in self.cache:
             if len(self.cache) >= 6:
                 self.cache.pop(min(self.cache, key=lambda k: k[1]))      # keep the big ones: the grid revisits them
-            self.cache[key] = self.build(h, self.leaves(log_m))
+            self.cache[key] = self.build(h, self.leaves(log_m, h))
         return self.cache[key]
 
 
@@ -166,14 +177,14 @@ def interleave(vals, log_parts):
 
 
 # ---- device-buffer entry points -------------------------------------------------------------------------------------------
-def cases(fn):
-    return [pytest.param(h, *c, id=f"{HASH_NAMES[h]}-" + "-".join(map(str, c))) for h in (mp.SHA, mp.FIELD) for c in fn(h)]
+def cases(fn, hashes=(mp.SHA, mp.FIELD)):
+    return [pytest.param(h, *c, id=f"{HASH_NAMES[h]}-" + "-".join(map(str, c))) for h in hashes for c in fn(h)]
 
 
-@pytest.mark.parametrize("h,log_m,lat", cases(mp.build_cases))
+@pytest.mark.parametrize("h,log_m,lat", cases(mp.build_cases, (mp.SHA, mp.FIELD, mp.B2S)))
 def test_build_ex_every_node(zk, dev, heaps, h, log_m, lat):
     """zk_dev_merkle_build_ex: no counter, so the latency phase runs plain launches of <= 10 levels (Merkle.new's plan)."""
-    vals = dev.upload(Heaps.leaves(log_m))
+    vals = dev.upload(Heaps.leaves(log_m, h))
     t, poison = dev.poisoned(log_m)
     with latency_log(dev, lat):
         dev.stats()
@@ -262,15 +273,27 @@ TRACE_A, TRACE_B = 3141592, 2718281
     ("field", 10, 3, None, True, 7),
     ("field", 13, 3, None, False, 1),
     ("field", 15, 3, None, True, 1),
+    ("blake2s", 2, 1, None, False, 1),
+    ("blake2s", 6, 2, None, False, 1),
+    ("blake2s", 10, 3, None, True, 7),
+    ("blake2s", 13, 3, None, False, 1),
+    ("blake2s", 14, 3, None, True, 7),         # 2^17 leaves: the largest tree the latency kernel takes alone; the fused fold trees
+                                               # below it run every continuation split from 2^16 down
+    ("blake2s", 15, 3, None, False, 1),        # 2^18: a throughput launch first
 ])
-def test_context_trees_every_node_after_a_second_trace(zk, orc, heaps, hash_name, log_n, log_b, host_levels, early, q):
+def test_context_trees_every_node_after_a_second_trace(zk, orc, heaps, monkeypatch, hash_name, log_n, log_b, host_levels, early, q):
     """Every node of trees 0 .. R+1 after proofs of trace A then trace B on one context (the host top and tail, early launch,
-    several queries): a node the second proof fails to store keeps trace A's value."""
-    h = mp.SHA if hash_name == "sha256" else mp.FIELD
+    several queries): a node the second proof fails to store keeps trace A's value.  A BLAKE2s proof is verified by
+    zk_verify_stop, whatever its settings: the strict verification at the end must get there."""
+    h = HASH_OF[hash_name]
     n = 1 << log_n
+    lib = zk.load()
+    real_verify_stop, stop_calls = lib.zk_verify_stop, []
+    monkeypatch.setattr(lib, "zk_verify_stop", lambda *a: (stop_calls.append(a[6]), real_verify_stop(*a))[1])
     with zk.Context(log_n, log_b, hash=hash_name, queries=q, host_levels=host_levels) as ctx:
         if early:
-            ctx.set_early_launch(True)
+            on = ctx.set_early_launch(True)
+            assert on or h != mp.B2S, "the gate stayed off: the BLAKE2s launches behind it would not run"
         ctx.prove(zk.trace_fibsq(n - 1, 1, TRACE_A))
         proof = ctx.prove(zk.trace_fibsq(n - 1, 1, TRACE_B))
         for tr in range(log_n + 2):
@@ -278,12 +301,13 @@ def test_context_trees_every_node_after_a_second_trace(zk, orc, heaps, hash_name
         assert [bytes(ctx.merkle_nodes(tr, 0, 1)[0]) for tr in range(log_n + 2)] == \
             [bytes(r) for r in ctx.last_transcript().roots[:log_n + 2]]
     proof.verify(strict=True)
+    assert stop_calls == ([mp.B2S] if h == mp.B2S else [])
 
 
 @pytest.mark.parametrize("hash_name,log_n,log_b", [("sha256", 10, 3), ("sha256", 15, 3), ("field", 10, 3), ("field", 14, 3)])
 def test_context_stage_commit_every_node(zk, orc, heaps, hash_name, log_n, log_b):
     """The stage-by-stage path: lde, merkle_commit(0), then every node of tree 0 (after a whole proof of another trace)."""
-    h = mp.SHA if hash_name == "sha256" else mp.FIELD
+    h = HASH_OF[hash_name]
     n = 1 << log_n
     with zk.Context(log_n, log_b, hash=hash_name) as ctx:
         ctx.prove(zk.trace_fibsq(n - 1, 1, TRACE_A))
@@ -293,6 +317,63 @@ def test_context_stage_commit_every_node(zk, orc, heaps, hash_name, log_n, log_b
         want = heaps.build(h, ctx.layer_read(0))
         assert root == bytes(want[0])
         assert_nodes(ctx.merkle_nodes(0), want, f"{hash_name} stage commit ({log_n}, {log_b})")
+
+
+def context_shape(log_m):
+    """(log_n, log_blowup) of the context whose layer 0 has 2^log_m values (log_m >= 3; n = 8 is refused, the blow-up is 2 .. 32)."""
+    log_b = 3 if log_m >= 7 or log_m == 5 else 2 if log_m in (4, 6) else 1
+    return log_m - log_b, log_b
+
+
+def context_profile(ctx):
+    return {c: (v["launches"], v["bytes"]) for c, v in ctx.kernel_stats().items() if c in MERKLE_CLASSES}
+
+
+def staged_layer0(zk, ctx, log_n):
+    """A whole proof of trace A, then trace B up to its layer 0, with the Merkle classes profiled from there on."""
+    n = 1 << log_n
+    ctx.prove(zk.trace_fibsq(n - 1, 1, TRACE_A))
+    ctx.trace_upload(zk.trace_fibsq(n - 1, 1, TRACE_B))
+    ctx.set_profiling(MERKLE_CLASSES)
+    ctx.lde()
+    ctx.kernel_stats()
+
+
+@pytest.mark.parametrize("log_m,lat", [pytest.param(*c, id="-".join(map(str, c))) for c in mp.context_cases(mp.B2S) + mp.B2S_RAISED_CASES])
+def test_blake2s_context_commit_runs_the_predicted_plan(zk, dev, heaps, log_m, lat):
+    """Whole BLAKE2s trees with a counter (the continuation; only a context reaches it for this hash): merkle_commit(0) on a layer of
+    2^log_m values runs the launches and bytes the mirror predicts -- the bytes of a latency launch depend on its split -- and every
+    node is hashlib's, after a whole proof of another trace."""
+    log_n, log_b = context_shape(log_m)
+    what = f"blake2s context commit 2^{log_m} lat {lat}"
+    with latency_log(dev, lat), zk.Context(log_n, log_b, hash="blake2s") as ctx:
+        staged_layer0(zk, ctx, log_n)
+        root = ctx.merkle_commit(0)
+        want_profile = mp.profile(mp.plan(log_m, mp.B2S, counter=True, lat=lat))
+        assert context_profile(ctx) == {c: want_profile.get(c, (0, 0.0)) for c in MERKLE_CLASSES}, f"{what}: the library ran another plan than the mirror's"
+        want = heaps.build(mp.B2S, ctx.layer_read(0))
+        assert root == bytes(want[0]), what
+        assert_nodes(ctx.merkle_nodes(0), want, what)
+
+
+@pytest.mark.parametrize("steps,log_m,lat", [pytest.param(*c, id="-".join(map(str, c))) for c in mp.coset_cases(mp.B2S)])
+def test_blake2s_context_coset_commit_runs_the_predicted_plan(zk, dev, heaps, steps, log_m, lat):
+    """BLAKE2s trees with coset leaves: merkle_commit(0, coset_steps) is one coset_leaf_hash_kernel<2, steps> launch, then the inner-mode
+    build with a counter -- below a switch at 2^12 a throughput launch of k = 1 .. 4 levels first, then the latency kernel in inner mode
+    with a continuation.  Profile and every node, as above."""
+    log_len = log_m + steps
+    log_n, log_b = context_shape(log_len)
+    what = f"blake2s context coset commit 2^{log_m} leaves of 2^{steps} lat {lat}"
+    with latency_log(dev, lat), zk.Context(log_n, log_b, hash="blake2s") as ctx:
+        staged_layer0(zk, ctx, log_n)
+        root = ctx.merkle_commit(0, coset_steps=steps)
+        want_profile = mp.profile(mp.plan(log_m, mp.B2S, counter=True, lat=lat, leaf_mode=False))
+        assert "merkle_leaf" not in want_profile                   # inner mode: the only leaf launch is the coset one
+        want_profile["merkle_leaf"] = (1, 4.0 * float(1 << log_len) + 32.0 * float(1 << log_m))
+        assert context_profile(ctx) == {c: want_profile.get(c, (0, 0.0)) for c in MERKLE_CLASSES}, f"{what}: the library ran another plan than the mirror's"
+        want = heaps.build(mp.B2S, ctx.layer_read(0), steps)
+        assert root == bytes(want[0]), what
+        assert_nodes(ctx.merkle_nodes(0, coset_steps=steps), want, what)
 
 
 def test_bulk_node_reads_agree_and_refuse_bad_ranges(zk, orc):
@@ -333,7 +414,7 @@ def proof_subtree(batch_nodes, log_batch, p, log_m):
 def test_batch_trees_every_node_after_a_second_batch(zk, orc, heaps, hash_name, log_n, log_b, log_batch):
     """Every node of every proof's tree in the batch heaps (fused composition / fold leaves, the host-built levels that
     scatter_kernel copies back) after a batch of other seeds on the same batch context."""
-    h = mp.SHA if hash_name == "sha256" else mp.FIELD
+    h = HASH_OF[hash_name]
     batch = 1 << log_batch
     with zk.BatchContext(log_n, log_b, log_batch, hash=hash_name) as bc:
         for base in (TRACE_A, TRACE_B):
