@@ -439,7 +439,10 @@ int zk_batch_public_last(const zk_batch *b, uint32_t *out);
  * breaks the constraints. */
 int zk_batch_prove(zk_batch *b, uint8_t *proofs_out, size_t stride, uint8_t *states_out);
 /* Nodes [first, first + count) of batch tree `tree` (a heap over batch * m_l leaves; proof p's tree is the subtree under node
- * 2^log_batch - 1 + p), 32 bytes each as zk_merkle_node.  Complete after zk_batch_prove; ZK_ERR_STATE for a tree id that the last
+ * 2^log_batch - 1 + p), 32 bytes each as zk_merkle_node.  Complete after zk_batch_prove that succeeded (after one that failed with
+ * ZK_ERR_CHECK the tree levels built on the host threads were never copied to the device: the nodes read then are not that run's).  The
+ * nodes 0 .. 2^log_batch - 2 above the per-proof roots belong to no proof; the prover never builds them, this call hashes them on the
+ * host from the per-proof roots, with the Merkle hash of the last zk_batch_prove.  ZK_ERR_STATE for a tree id that the last
  * proof, folded by zk_batch_set_fold, did not build.  A tree the last proof built with coset leaves of 2^steps values is addressed by
  * its own heap: 2 * batch * (len >> steps) - 1 nodes, anything beyond is ZK_ERR_INVALID; the batch remembers the steps of each tree per
  * proof, so a later plain proof has full-size heaps again. */

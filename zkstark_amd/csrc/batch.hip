@@ -62,6 +62,7 @@ struct zk_batch {
     uint32_t fold = 1;                // FRI folding factor 2^fold between commitments (zk_batch_set_fold; 1 = the reference)
     uint32_t stop = 0;                // early stop D (zk_batch_set_fri_stop; 0 = fold down to a constant, the reference)
     uint32_t proved_fold = 1, proved_stop = 0;   // ... of the last zk_batch_prove, whose skipped_trees these are:
+    int proved_hash = 0;              // ... and the Merkle hash its trees were built with (zk_batch_merkle_nodes hashes the levels above the roots)
     uint64_t skipped_trees = 0;       // bit id: that proof built no tree (and no layer) `id`
     uint32_t* d_work = nullptr;       // [batch][8] per-proof constants of the multi-fold (allocated by the first fold > 1, coset leaves or early stop)
     uint32_t *d_final = nullptr, *h_final = nullptr;   // [batch][1 + 2^stop]: count of high coefficients, final polynomial (stop > 0; h_: pinned)
@@ -492,6 +493,9 @@ int zk_batch_public_last(const zk_batch* b, uint32_t* out) {
 
 // Nodes [first, first + count) of batch tree `tree` (a heap over batch * m_l leaves; proof p's tree is the subtree under node
 // 2^log_batch - 1 + p).  Complete after zk_batch_prove: its last launches copy the host-built levels in (scatter_kernel).
+// The log_batch levels ABOVE the per-proof roots belong to no proof and no launch builds them (MailArgs.top = log_batch): the nodes
+// 0 .. 2^log_batch - 2 are hashed here, on the host, from the per-proof roots with the hash of the proof that built the tree.
+// After a zk_batch_prove that FAILED (ZK_ERR_CHECK) the host-built levels were never copied in: the nodes are not that run's.
 // A tree the last proof built with coset leaves of 2^steps values has m_l = len >> steps leaves per proof: its own, smaller heap.
 int zk_batch_merkle_nodes(zk_batch* b, uint32_t tree, size_t first, size_t count, uint8_t* out) {
     if (!b || (!out && count)) return fail(ZK_ERR_INVALID, "zk_batch_merkle_nodes: null argument");
@@ -503,7 +507,15 @@ int zk_batch_merkle_nodes(zk_batch* b, uint32_t tree, size_t first, size_t count
     if (first > heap || count > heap - first) return fail(ZK_ERR_INVALID, "zk_batch_merkle_nodes: out of range");
     if ((b->skipped_trees >> tree) & 1)
         return fail(ZK_ERR_STATE, "zk_batch_merkle_nodes: tree %u was not built by the last proof (fold_log %u, fri_stop %u)", tree, b->proved_fold, b->proved_stop);
-    return merkle_nodes_to_host(b->device, b->stream, b->d_trees + b->tree_off[tree], first, count, out);
+    const uint32_t* d_heap = b->d_trees + b->tree_off[tree];
+    const size_t top = b->batch - 1;                                      // nodes above the per-proof roots
+    if (first >= top || !count) return merkle_nodes_to_host(b->device, b->stream, d_heap, first, count, out);
+    std::vector<uint8_t> up((2 * b->batch - 1) * 32);
+    if (int rc = merkle_nodes_to_host(b->device, b->stream, d_heap, top, b->batch, up.data() + 32 * top)) return rc;
+    for (size_t i = top; i-- > 0;) host_node_hash(up.data() + 32 * (2 * i + 1), up.data() + 32 * (2 * i + 2), up.data() + 32 * i, b->proved_hash);
+    const size_t n_top = count < top - first ? count : top - first;
+    memcpy(out, up.data() + 32 * first, 32 * n_top);
+    return merkle_nodes_to_host(b->device, b->stream, d_heap, first + n_top, count - n_top, out + 32 * n_top);
 }
 
 // generate_proof (prover.rs:9-293) for every resident trace.  proofs_out: [batch][stride] bytes, stride >=
@@ -551,7 +563,7 @@ int zk_batch_prove(zk_batch* b, uint8_t* proofs_out, size_t stride, uint8_t* sta
     // f = LDE of every trace, committed (prover.rs:60-85)
     if ((rc = dom_lde(d, b->d_trace, b->d_coef, b->d_layers + b->layer_off[0], b->stream, nullptr, (uint32_t)nb))) return rc;
     b->stage_used = 0; b->n_segs = 0; b->seg_words = 0;
-    b->skipped_trees = 0; b->proved_fold = K; b->proved_stop = stop;
+    b->skipped_trees = 0; b->proved_fold = K; b->proved_stop = stop; b->proved_hash = hash;
     memset(b->tree_steps, 0, sizeof b->tree_steps);
     HIPCHK(launch_merkle_build(b->d_layers + b->layer_off[0], L + lb, b->d_trees + b->tree_off[0], b->stream, nullptr, bmail(b, L), hash));
     // proof-independent part of the composition constants (compose_args with alpha = 1)

@@ -615,7 +615,8 @@ class BatchContext:
 
     def merkle_nodes(self, tree, first=0, count=None, coset_steps=0):
         """Nodes of batch tree `tree`: a heap over batch * m_l leaves whose node 2^log_batch - 1 + p roots proof p's tree.
-        coset_steps: what the last proof built the tree with (m_l = layer_size >> coset_steps leaves per proof)."""
+        coset_steps: what the last proof built the tree with (m_l = layer_size >> coset_steps leaves per proof).  The nodes above the
+        per-proof roots belong to no proof: the call hashes them on the host from the roots."""
         m = ((1 << (self.log_n + self.log_blowup)) >> max(tree - 1, 0)) >> coset_steps
         return _read_nodes(_lib.load().zk_batch_merkle_nodes, self._h, tree, 2 * m * self.batch - 1, first, count)
 
