@@ -245,6 +245,30 @@ int zk_ctx_get_coset_leaves(const zk_ctx *ctx);
 int zk_ctx_set_fri_stop(zk_ctx *ctx, uint32_t stop_log);
 uint32_t zk_ctx_get_fri_stop(const zk_ctx *ctx);
 int zk_ctx_final_poly(const zk_ctx *ctx, uint32_t *out, size_t cap, size_t *count);
+/* Merkle caps: cap_log = c, default 0 (with 0 every byte, launch and allocation is what it was); 0 <= c <= 8, anything else is
+ * ZK_ERR_INVALID and the setting is unchanged; a zk_tail_create context answers ZK_ERR_STATE.  Valid with every hash, fold_log, leaf
+ * format, stop_log, query count, grinding, host-levels setting and early launch, in zk_prove, zk_prove_resident, zk_prove_channel and
+ * zk_prove_many.  A tree over 2^lg leaves (a coset leaf counts once) is committed by the 2^ce digests of depth ce = min(c, lg - 1) --
+ * heap nodes 2^ce - 1 .. 2^(ce+1) - 2, left to right, 32 bytes each in the byte form of a root, ONE channel commit -- in place of its root:
+ * f, cp (or group 0's input tree), every group output that gets a tree, and the never-opened last tree when stop_log = 0.  A path into the
+ * tree carries the lg - ce siblings from the leaf up to depth ce + 1, behind a u64 count of lg - ce; the verifier hashes upward lg - ce times
+ * and compares with cap entry leaf >> (lg - ce).  Nothing above depth ce is hashed by the device, the host thread or the verifier: the
+ * build is handed over at depth max(ce, the host's share) and the host reduces from there down to ce only.  Length:
+ * zk_proof_data_len_cap; verifier: zk_verify_cap.  The cap pays with several queries only: the head grows by 32 (2^ce - 1) bytes per
+ * tree, each path shrinks by 32 ce.
+ * After a proof with c > 0: zk_last_transcript's roots[id] is all zero for a tree with ce > 0 and zk_ctx_merkle_cap has its digests; the
+ * heap of such a tree above depth ce is not defined (it may hold an earlier proof's nodes), so zk_merkle_node / zk_merkle_nodes of an
+ * index above the cap and zk_merkle_path of that tree return ZK_ERR_STATE.  The stage-by-stage API (zk_merkle_commit*, zk_dev_*)
+ * ignores the setting and builds whole trees.
+ * zk_verifier_* checks such proofs in batches with zk_verifier_set_merkle_cap.
+ * NOT covered: zk_batch_*, zk_shard_* and zk_tail_* have no cap setting yet.
+ * zk_ctx_get_merkle_cap: the current c, 0 for a null context.  zk_ctx_merkle_cap_log: the ce tree `tree` was last built down to.
+ * zk_ctx_merkle_cap: what the last one-call proof committed for `tree`, 32 * 2^ce bytes (ce = 0: the root); ZK_ERR_BUFFER if out_len is
+ * smaller, ZK_ERR_STATE before the first proof or for a tree the proof did not build. */
+int zk_ctx_set_merkle_cap(zk_ctx *ctx, uint32_t cap_log);
+uint32_t zk_ctx_get_merkle_cap(const zk_ctx *ctx);
+uint32_t zk_ctx_merkle_cap_log(const zk_ctx *ctx, uint32_t tree);
+int zk_ctx_merkle_cap(const zk_ctx *ctx, uint32_t tree, uint8_t *out, size_t out_len);
 /* The HIP stream every stage is enqueued on (hipStream_t). */
 void *zk_ctx_stream(zk_ctx *ctx);
 
@@ -480,6 +504,11 @@ size_t zk_proof_data_len_coset(uint32_t log_n, uint32_t log_blowup, uint32_t n_q
  * zk_proof_data_len_fold / _coset return.  0 for a fold_log outside 1..3 or a stop_log outside the limits of zk_ctx_set_fri_stop. */
 size_t zk_proof_data_len_stop(uint32_t log_n, uint32_t log_blowup, uint32_t n_queries, uint32_t grind_bits, uint32_t fold_log,
                               int coset_leaves, uint32_t stop_log);
+/* Proofs made with zk_ctx_set_merkle_cap(cap_log = c): zk_proof_data_len_stop of the other arguments, plus 32 (2^ce - 1) per committed
+ * tree, minus 32 ce per path into it, with ce = min(c, lg - 1) for a tree of 2^lg leaves.  cap_log = 0: what zk_proof_data_len_stop
+ * returns.  0 where that returns 0, or for cap_log > 8. */
+size_t zk_proof_data_len_cap(uint32_t log_n, uint32_t log_blowup, uint32_t n_queries, uint32_t grind_bits, uint32_t fold_log,
+                             int coset_leaves, uint32_t stop_log, uint32_t cap_log);
 /* Proof-of-work search (zk_ctx_set_grinding): the smallest nonce >= start whose SHA-256(state || le64(nonce)) begins with
  * grind_bits zero bits (0..32; 0 gives start), on the GPU (zk_grind) or on <= 16 host threads (zk_grind_host; threads is
  * clamped to 1..16).  Gives up with an error naming grind_bits after 2^44 nonces.  A zk_channel user grinds on
@@ -538,6 +567,17 @@ int zk_verify_stop(const uint8_t *proof, size_t len, const uint8_t *state, uint3
                    int hash_kind, uint32_t n_queries, uint32_t grind_bits, uint32_t fold_log, int coset_leaves, uint32_t stop_log,
                    int32_t *check_out);
 
+/* zk_verify_stop for proofs made with zk_ctx_set_merkle_cap(cap_log = c), every hash.  Each root of the header is the tree's 2^ce digests,
+ * each path has lg - ce digests (another count: -3 / -(200+j), as ever) and is compared with cap entry leaf >> (lg - ce); a path that does
+ * not reach its entry gets the check number the same path gets for missing the root.  Not strict (state == NULL): only the entries a
+ * path lands in are tested.  A changed entry that no path lands in is caught by the strict replay alone, which commits each cap in one
+ * piece, with the number a changed root gets there (the first challenge after it).  With c > 0 a proof whose length is not
+ * zk_proof_data_len_cap of the arguments is rejected with -1, strict or not; cap_log > 8 is ZK_ERR_INVALID.  cap_log = 0 gives every
+ * input the number zk_verify_stop gives it (the same code path). */
+int zk_verify_cap(const uint8_t *proof, size_t len, const uint8_t *state, uint32_t log_n, uint32_t log_blowup, uint32_t public_last,
+                  int hash_kind, uint32_t n_queries, uint32_t grind_bits, uint32_t fold_log, int coset_leaves, uint32_t stop_log,
+                  uint32_t cap_log, int32_t *check_out);
+
 /* A verifier for many proofs of one size (log_n, log_blowup: the sizes zk_verify_queries accepts).  It owns its streams and
  * device buffers (grown on demand) and a pinned staging buffer.  One verifier is used from one host thread at a time. */
 typedef struct zk_verifier zk_verifier;
@@ -574,6 +614,16 @@ int zk_verifier_get_coset_leaves(const zk_verifier *v);
  * Not run or timed on a GPU yet (tools/verify_bench.py --stop is the tool; DESIGN.md 7d "Early stop"). */
 int zk_verifier_set_fri_stop(zk_verifier *v, uint32_t stop_log);
 uint32_t zk_verifier_get_fri_stop(const zk_verifier *v);
+/* Proofs made with zk_ctx_set_merkle_cap(cap_log = c): default 0, 0 <= c <= 8 (anything else: ZK_ERR_INVALID, the setting unchanged), from
+ * the next zk_verifier_run on; it combines with every fold_log, leaf format, stop_log, query count, grinding and both hashes of this
+ * class.  zk_verifier_run then takes zk_proof_data_len_cap(log_n, log_blowup, q, grind_bits, fold_log, coset_leaves, D, c) bytes per proof
+ * and checks_out[i] is what zk_verify_cap gives proof i with the same arguments, for EVERY input, strict or not: a path is hashed
+ * lg - ce times and compared with the cap entry it lands in, the strict replay commits each cap in one piece, a proof of another cap is
+ * rejected with the number zk_verify_cap gives those bytes, and proofs whose path counts differ from the fixed layout go to the CPU
+ * verifier with c.  Kernels of their own read the per-tree layout from a table in the launch arguments (csrc/verify.hip); with c = 0
+ * lengths, results and launches are what they were.  zk_verifier_get_merkle_cap: the current c, 0 for a null verifier. */
+int zk_verifier_set_merkle_cap(zk_verifier *v, uint32_t cap_log);
+uint32_t zk_verifier_get_merkle_cap(const zk_verifier *v);
 /* count proofs at proofs + i*stride, each exactly zk_proof_data_len_fold(log_n, log_blowup, q, grind_bits, fold_log) bytes (with
  * the defaults zk_proof_data_len_queries(log_n, log_blowup, q); with coset leaves zk_proof_data_len_coset of the same arguments;
  * with an early stop zk_proof_data_len_stop; stride >= that, any alignment); states: count*32 bytes, or NULL = not strict;

@@ -19,7 +19,11 @@ down to a constant), all interleaved in the same rounds.  The stopped proofs com
 CPU side is zk_verify_stop, and every distinct proof is first checked with zk_verify_stop (strict) before it is timed; a result is
 named NAME_kK[_coset]_dD.
 
-    python tools/verify_bench.py [--steps 20] [--warmup 3] [--profile] [--only NAME,...] [--fold 1,2,3 --blocks 5] [--coset] [--stop 0,4,8]
+--cap C0,C1,... measures every setting of the other options once per listed cap_log (Verifier(cap_log=c); 0 = roots), all interleaved in
+the same rounds.  The capped proofs come from the one-call prover (Context(cap_log=c)), the CPU side is zk_verify_cap, every distinct
+proof is first checked with it (strict), and proof_bytes is zk_proof_data_len_cap; a result is named NAME_kK[_coset][_dD]_cC.
+
+    python tools/verify_bench.py [--steps 20] [--warmup 3] [--profile] [--only NAME,...] [--fold 1,2,3 --blocks 5] [--coset] [--stop 0,4,8] [--cap 0,4,8]
 """
 import argparse
 import concurrent.futures
@@ -61,12 +65,12 @@ _cache = {}
 _checked = set()
 
 
-def proofs_for(log_n, log_b, q, hash, count, fold=1, coset=False, stop=None):
+def proofs_for(log_n, log_b, q, hash, count, fold=1, coset=False, stop=None, cap=None):
     """(data [count, len] uint8, states [count, 32], public_last [count]) of valid proofs.  stop: None, or D of --stop (every distinct
     proof is then checked with zk_verify_stop on the CPU, strict, before anything is timed)."""
-    key = (log_n, log_b, q, hash, fold, coset, stop or 0)
-    if key not in _cache and (coset or stop):         # the one-call prover, one trace at a time
-        with zk.Context(log_n, log_b, hash=hash, queries=q, fold_log=fold, coset_leaves=coset, stop_log=stop or 0) as ctx:
+    key = (log_n, log_b, q, hash, fold, coset, stop or 0, cap or 0)
+    if key not in _cache and (coset or stop or cap):  # the one-call prover, one trace at a time
+        with zk.Context(log_n, log_b, hash=hash, queries=q, fold_log=fold, coset_leaves=coset, stop_log=stop or 0, cap_log=cap or 0) as ctx:
             ps = [ctx.prove(zk.trace_fibsq((1 << log_n) - 1, 1, 3141592 + p)) for p in range(64 if log_n <= 10 else (8 if log_n <= 17 else 2))]
         _cache[key] = (np.stack([np.frombuffer(p.data, dtype=np.uint8) for p in ps]), np.stack([np.frombuffer(p.state, dtype=np.uint8) for p in ps]),
                        np.array([p.public_last & 0xFFFFFFFF for p in ps], dtype=np.uint32))
@@ -76,12 +80,12 @@ def proofs_for(log_n, log_b, q, hash, count, fold=1, coset=False, stop=None):
             bc.gen_fibsq([1] * bc.batch, [3141592 + p for p in range(bc.batch)])
             data, states = bc.prove_raw()
             _cache[key] = (data, states, bc.public_last())
-    if stop is not None and key not in _checked:
+    if (stop is not None or cap is not None) and key not in _checked:
         data, states, last = _cache[key]
         check = C.c_int32(1)
         for i in range(len(data)):
-            rc = _lib.load().zk_verify_stop(data[i].ctypes.data, data.shape[1], states[i].ctypes.data, log_n, log_b, int(last[i]), zk.host.HASHES[hash], q, 0,
-                                            fold, int(coset), stop, C.byref(check))
+            rc = _lib.load().zk_verify_cap(data[i].ctypes.data, data.shape[1], states[i].ctypes.data, log_n, log_b, int(last[i]), zk.host.HASHES[hash], q, 0,
+                                           fold, int(coset), stop or 0, cap or 0, C.byref(check))
             assert rc == 0 and check.value == 0, (key, i, rc, check.value)
         _checked.add(key)
     data, states, last = _cache[key]
@@ -96,9 +100,10 @@ def gpu_times(shape, steps, warmup, folds=(1,), blocks=1):
     vs, ts = {}, {K: [] for K in folds}
     try:
         for K in folds:
-            fold, coset, stop = (K + (None,))[:3] if isinstance(K, tuple) else (K, False, None)
-            data, states, last = proofs_for(log_n, log_b, q, hash, count, fold, coset, stop)
-            vs[K] = (zk.Verifier(log_n, log_b, hash=hash, queries=q, fold_log=fold, coset_leaves=coset, stop_log=stop or 0), data, states if strict else None, last)
+            fold, coset, stop, cap = (K + (None, None))[:4] if isinstance(K, tuple) else (K, False, None, None)
+            data, states, last = proofs_for(log_n, log_b, q, hash, count, fold, coset, stop, cap)
+            vs[K] = (zk.Verifier(log_n, log_b, hash=hash, queries=q, fold_log=fold, coset_leaves=coset, stop_log=stop or 0, cap_log=cap or 0), data,
+                     states if strict else None, last)
             for _ in range(warmup):
                 assert (vs[K][0].verify_raw(data, last, vs[K][2]) == 0).all()
         for _ in range(blocks):
@@ -114,9 +119,9 @@ def gpu_times(shape, steps, warmup, folds=(1,), blocks=1):
     return ts
 
 
-def cpu_ms(shape, threads, fold=1, coset=False, stop=None):
+def cpu_ms(shape, threads, fold=1, coset=False, stop=None, cap=None):
     log_n, log_b, q, hash, count, strict = shape
-    data, states, last = proofs_for(log_n, log_b, q, hash, count, fold, coset, stop)
+    data, states, last = proofs_for(log_n, log_b, q, hash, count, fold, coset, stop, cap)
     lib = _lib.load()
     hk = zk.host.HASHES[hash]
     plen = data.shape[1]
@@ -124,6 +129,8 @@ def cpu_ms(shape, threads, fold=1, coset=False, stop=None):
     check = C.c_int32 * 1
 
     def one(r):
+        if cap is not None:
+            return lib.zk_verify_cap(r[0], plen, r[1], log_n, log_b, r[2], hk, q, 0, fold, int(coset), stop or 0, cap, check())
         if stop is not None:
             return lib.zk_verify_stop(r[0], plen, r[1], log_n, log_b, r[2], hk, q, 0, fold, int(coset), stop, check())
         if coset:
@@ -177,26 +184,29 @@ def main():
     ap.add_argument("--blocks", type=int, default=1, help="rounds over the K of --fold, each of --steps calls per K")
     ap.add_argument("--coset", action="store_true", help="every K with coset leaves off and on, interleaved")
     ap.add_argument("--stop", default="", help="early-stop D to measure, e.g. 0,4,8: every K and leaf format once per D, interleaved")
+    ap.add_argument("--cap", default="", help="Merkle cap_log to measure, e.g. 0,4,8: every other setting once per cap, interleaved")
     a = ap.parse_args()
     folds = tuple(int(k) for k in a.fold.split(","))
     if a.inner:                                       # under rocprofv3: the timed GPU calls of one shape only
         gpu_times(SHAPES[a.inner], a.steps, 1, ((folds[0], True),) if a.coset else folds[:1])
         return
     stops = tuple(int(d) for d in a.stop.split(",")) if a.stop else (None,)
-    settings = tuple((K, on, D) for K in folds for on in ((False, True) if a.coset else (False,)) for D in stops)
+    caps = tuple(int(c) for c in a.cap.split(",")) if a.cap else (None,)
+    settings = tuple((K, on, D, c) for K in folds for on in ((False, True) if a.coset else (False,)) for D in stops for c in caps)
     names = [n for n in SHAPES if not a.only or n in a.only.split(",")]
     res = {}
     for name in names:
         shape = SHAPES[name]
         times = gpu_times(shape, a.steps, a.warmup, settings, a.blocks)
-        for K, on, D in settings:
-            ts = sorted(times[K, on, D])
-            c1 = cpu_ms(shape, 1, K, on, D)
-            c16 = cpu_ms(shape, 16, K, on, D)
-            key = (name if folds == (1,) and not a.coset and not a.stop else f"{name}_k{K}") + ("_coset" if on else "") + ("" if D is None else f"_d{D}")
+        for K, on, D, cap in settings:
+            ts = sorted(times[K, on, D, cap])
+            c1 = cpu_ms(shape, 1, K, on, D, cap)
+            c16 = cpu_ms(shape, 16, K, on, D, cap)
+            key = ((name if folds == (1,) and not a.coset and not a.stop and not a.cap else f"{name}_k{K}") + ("_coset" if on else "")
+                   + ("" if D is None else f"_d{D}") + ("" if cap is None else f"_c{cap}"))
             res[key] = {"log_n": shape[0], "log_blowup": shape[1], "queries": shape[2], "hash": shape[3], "count": shape[4],
-                        "strict": shape[5], "fold_log": K, "coset_leaves": on, "stop_log": D or 0,
-                        "proof_bytes": int(_lib.load().zk_proof_data_len_stop(shape[0], shape[1], shape[2], 0, K, int(on), D or 0)),
+                        "strict": shape[5], "fold_log": K, "coset_leaves": on, "stop_log": D or 0, "cap_log": cap or 0,
+                        "proof_bytes": int(_lib.load().zk_proof_data_len_cap(shape[0], shape[1], shape[2], 0, K, int(on), D or 0, cap or 0)),
                         "gpu_ms_median": round(ts[len(ts) // 2], 4), "gpu_ms_min": round(ts[0], 4), "gpu_ms_max": round(ts[-1], 4),
                         "cpu_1t_ms": round(c1, 3), "cpu_16t_ms": round(c16, 3),
                         "speedup_vs_16t": round(c16 / ts[len(ts) // 2], 2)}
@@ -206,7 +216,7 @@ def main():
             if name in PROFILED and name in res:
                 res[name]["kernels_ms_per_call"] = profile(name, 5)
     cross = {n: res[n] for n in ("2e24_q1_strict_1", "2e24_q1_strict_8", "2e24_q1_strict_16", "2e24_q1_strict_64") if n in res}
-    line = {"tool": "verify_bench", "build_hash": _lib.build_hash(), "steps": a.steps, "warmup": a.warmup, "fold": list(folds), "coset": a.coset, "stop": [d for d in stops if d is not None], "blocks": a.blocks, "shapes": res,
+    line = {"tool": "verify_bench", "build_hash": _lib.build_hash(), "steps": a.steps, "warmup": a.warmup, "fold": list(folds), "coset": a.coset, "stop": [d for d in stops if d is not None], "cap": [c for c in caps if c is not None], "blocks": a.blocks, "shapes": res,
             "crossover_2e24_strict": {n: {"count": r["count"], "gpu_ms": r["gpu_ms_median"], "cpu_16t_ms": r["cpu_16t_ms"]} for n, r in cross.items()}}
     print(json.dumps(line), flush=True)
 

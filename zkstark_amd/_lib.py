@@ -149,6 +149,12 @@ SYMBOLS = {
     "zk_ctx_final_poly": (_int, [_vp, _vp, _sz, C.POINTER(_sz)]),
     "zk_fri_final_poly": (_int, [_vp, _u32, _u32, _vp, C.POINTER(_u32)]),
     "zk_proof_data_len_stop": (_sz, [_u32, _u32, _u32, _u32, _u32, _int, _u32]),
+    "zk_ctx_set_merkle_cap": (_int, [_vp, _u32]),
+    "zk_ctx_get_merkle_cap": (_u32, [_vp]),
+    "zk_ctx_merkle_cap_log": (_u32, [_vp, _u32]),
+    "zk_ctx_merkle_cap": (_int, [_vp, _u32, _vp, _sz]),
+    "zk_proof_data_len_cap": (_sz, [_u32, _u32, _u32, _u32, _u32, _int, _u32, _u32]),
+    "zk_verify_cap": (_int, [_vp, _sz, _vp, _u32, _u32, _u32, _int, _u32, _u32, _u32, _int, _u32, _u32, C.POINTER(C.c_int32)]),
     "zk_verify_stop": (_int, [_vp, _sz, _vp, _u32, _u32, _u32, _int, _u32, _u32, _u32, _int, _u32, C.POINTER(C.c_int32)]),
     "zk_dev_fri_fold_multi": (_int, [_vp, _vp, _vp, _u32, _u32, _u32, _u32, _vp]),
     "zk_dev_fri_fold_multi_batch": (_int, [_vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _u32, _vp]),
@@ -197,6 +203,8 @@ SYMBOLS = {
     "zk_verifier_get_coset_leaves": (_int, [_vp]),
     "zk_verifier_set_fri_stop": (_int, [_vp, _u32]),
     "zk_verifier_get_fri_stop": (_u32, [_vp]),
+    "zk_verifier_set_merkle_cap": (_int, [_vp, _u32]),
+    "zk_verifier_get_merkle_cap": (_u32, [_vp]),
     "zk_verifier_run": (_int, [_vp, _vp, _sz, _sz, _vp, _vp, _vp]),
     "zk_merkle_build_host_ex": (_int, [_int, _vp, _sz, _vp, _int]),
     "zk_dev_merkle_build_ex": (_int, [_vp, _u32, _vp, _vp, _int]),

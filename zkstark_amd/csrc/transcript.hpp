@@ -142,6 +142,40 @@ inline size_t proof_data_len(uint32_t log_n, uint32_t log_b, uint32_t q = 1, uin
     return head + (grind ? 8 : 0) + (size_t)q * per_query;
 }
 
+// ---- Merkle caps ----------------------------------------------------------------------------------------------
+// cap = c in 0..kMaxCapLog: a tree over 2^lg leaves (coset leaves count as one) is committed by the 2^ce digests of depth
+// ce = min(c, lg - 1) -- heap nodes 2^ce - 1 .. 2^(ce+1) - 2, left to right, 32 bytes each, ONE commit -- in place of its root, and a
+// path into it carries the lg - ce siblings from the leaf up to depth ce + 1 (the u64 count in front is lg - ce).  The verifier hashes
+// upward lg - ce times and compares with cap entry leaf >> (lg - ce).  ce = 0 is the root: a cap-0 proof is the format above, byte for
+// byte.  Every committed tree takes part: f, the tree over every group's input layer, and the never-opened last tree when stop = 0.
+// A path that misses its cap entry gets the check number it gets for missing the root.  verify_proof tests only the entries a path
+// lands in; a changed entry that no path lands in is caught by verify_transcript alone (the challenge after it, as for a changed root).
+constexpr uint32_t kMaxCapLog = 8;
+inline uint32_t cap_eff(uint32_t cap, uint32_t lg) { return cap < lg - 1 ? cap : lg - 1; }   // lg >= 1 for every committed tree
+// log2 of the leaf count of the tree over the input layer of group j < G (tree id 1 + jK), or, for j = G, of the last layer's tree
+inline uint32_t group_tree_log(uint32_t log_n, uint32_t log_b, uint32_t fold, bool coset, uint32_t stop, uint32_t j) {
+    const uint32_t Rp = log_n - stop, L = log_n + log_b, G = fold_groups(Rp, fold);
+    if (j >= G) return L - Rp;
+    return L - j * fold - (coset ? fold_steps(Rp, fold, j) : 0);
+}
+// proof_data_len, plus 32 (2^ce - 1) in the head per committed tree, minus 32 ce per path into it
+inline size_t proof_data_len_cap(uint32_t log_n, uint32_t log_b, uint32_t q, uint32_t grind, uint32_t fold, bool coset, uint32_t stop, uint32_t cap) {
+    const size_t len = proof_data_len(log_n, log_b, q, grind, fold, coset, stop);
+    if (!cap) return len;
+    const uint32_t Rp = log_n - stop, G = fold_groups(Rp, fold);
+    const uint32_t cf = cap_eff(cap, log_n + log_b);
+    size_t head = (size_t)32 * (((size_t)1 << cf) - 1), per_query = (size_t)3 * 32 * cf;
+    for (uint32_t j = 0; j <= G; ++j) {
+        if (j == G && stop) break;                            // a stopped proof has no tree over its last layer
+        const uint32_t ce = cap_eff(cap, group_tree_log(log_n, log_b, fold, coset, stop, j));
+        head += (size_t)32 * (((size_t)1 << ce) - 1);
+        if (j == G) break;
+        const size_t paths = (coset ? 1 : (size_t)1 << fold_steps(Rp, fold, j)) + (j == 0 && !coset ? 1 : 0);   // + cp(x)
+        per_query += paths * 32 * ce;
+    }
+    return len + head - (size_t)q * per_query;
+}
+
 // ---- grinding (DESIGN.md "Grinding"; the reference has none) -------------------------------------------------------------
 // After the free term, with channel state S, the prover commits le64(w) for the smallest w >= 0 such that SHA-256(S || le64(w))
 // starts with g zero bits (MSB-first from byte 0, as get_u32 reads the state).  The commit itself computes that hash, so the
@@ -233,11 +267,14 @@ inline void compute_root_from_path(uint32_t element, size_t index, const uint8_t
 // stop > 0 (early stop, above): the groups are those of log_n - stop rounds, the header ends with the 2^stop coefficients in place of
 // the last root and the free term, and the last group's fold -(100 + (G' - 1)) is compared with p(x^(2^R')) -- Horner over the
 // coefficients, each reduced % P on reading, as raw challenges are.
+// cap > 0 (Merkle caps, above): every root of the header is 2^ce digests, the path lengths expected are lg - ce, and a path is
+// compared with the cap entry it lands in, under the check number it has for the root.  A proof of another length: -1.
 inline int verify_proof(const uint8_t* data, size_t len, uint32_t log_n, uint32_t log_b, uint32_t public_last, int hash = 0, uint32_t q = 1,
-                        uint32_t grind = 0, uint32_t fold = 1, bool coset = false, uint32_t stop = 0) {
+                        uint32_t grind = 0, uint32_t fold = 1, bool coset = false, uint32_t stop = 0, uint32_t cap = 0) {
     if (log_n < 2 || log_b < 1 || log_n + log_b > 30 || q < 1 || q > 64 || grind > kMaxGrindBits || fold < 1 || fold > kMaxFoldLog) return -1;
     if (!stop_ok(log_n, log_b, stop)) return -1;
-    if (stop && len != proof_data_len(log_n, log_b, q, grind, fold, coset, stop)) return -1;   // a stopped proof of another length: -1, strict or not
+    if (cap > kMaxCapLog) return -1;
+    if ((stop || cap) && len != proof_data_len_cap(log_n, log_b, q, grind, fold, coset, stop, cap)) return -1;   // a stopped or capped proof of another length: -1, strict or not
     const uint32_t Rp = log_n - stop;
     const int nf = coset ? 3 : 4;                            // f(x), f(gx), f(g^2 x) and, with one-value leaves, cp(x)
     const size_t n = (size_t)1 << log_n, B = (size_t)1 << log_b, N = n << log_b, L = log_n + log_b;
@@ -263,11 +300,14 @@ inline int verify_proof(const uint8_t* data, size_t len, uint32_t log_n, uint32_
         return take(32 * plen);
     };
     // proof.rs:20-46
-    const uint8_t* f_root = take(32);
+    uint32_t ce[41];                                         // ce[j]: the effective cap of roots[j]'s tree; cf: of f's
+    const uint32_t cf = cap_eff(cap, (uint32_t)L);
+    for (uint32_t j = 0; j <= G; ++j) ce[j] = cap_eff(cap, group_tree_log(log_n, log_b, fold, coset, stop, j));
+    const uint8_t* f_root = take((size_t)32 << cf);
     uint32_t alpha[3] = {take32(), take32(), take32()};
-    const uint8_t* roots[40]; uint32_t betas[40];            // roots[j]: the tree over the INPUT layer of group j (roots[G]: the last layer)
-    roots[0] = take(32);
-    for (uint32_t j = 0; j < G; ++j) { betas[j] = take32(); roots[j + 1] = (stop && j + 1 == G) ? nullptr : take(32); }
+    const uint8_t* roots[41]; uint32_t betas[40];            // roots[j]: the tree over the INPUT layer of group j (roots[G]: the last layer)
+    roots[0] = take((size_t)32 << ce[0]);
+    for (uint32_t j = 0; j < G; ++j) { betas[j] = take32(); roots[j + 1] = (stop && j + 1 == G) ? nullptr : take((size_t)32 << ce[j + 1]); }
     const uint8_t* coefs = stop ? take((size_t)4 << stop) : nullptr;
     uint32_t free_term = stop ? 0 : take32();
     if (grind) take(8);                                   // the nonce
@@ -308,12 +348,18 @@ inline int verify_proof(const uint8_t* data, size_t len, uint32_t log_n, uint32_
             if (cp0 != fv[3]) return -2;
         }
         uint8_t root[32];
-        for (int i = 0; i < nf; ++i) if (fpl[i] != L) return -3;
+        // the path of leaf `idx` (s slots) climbs plen levels and must land on entry idx >> plen of the tree's cap (cap 0: on the root)
+        auto misses = [&](const uint32_t* slots, size_t s, size_t idx, const uint8_t* path, size_t plen, const uint8_t* entries) -> bool {
+            compute_root_from_coset(slots, s, idx & (((size_t)1 << plen) - 1), path, plen, root, hash);
+            return memcmp(root, entries + 32 * (idx >> plen), 32) != 0;
+        };
+        for (int i = 0; i < 3; ++i) if (fpl[i] != L - cf) return -3;
+        if (!coset && fpl[3] != L - ce[0]) return -3;
         // proof.rs:80-95
-        compute_root_from_path(fv[0], tp, fp[0], fpl[0], root, hash);         if (memcmp(root, f_root, 32)) return -4;
-        compute_root_from_path(fv[1], tp + B, fp[1], fpl[1], root, hash);     if (memcmp(root, f_root, 32)) return -5;
-        compute_root_from_path(fv[2], tp + 2 * B, fp[2], fpl[2], root, hash); if (memcmp(root, f_root, 32)) return -6;
-        if (!coset) { compute_root_from_path(fv[3], tp, fp[3], fpl[3], root, hash); if (memcmp(root, roots[0], 32)) return -7; }
+        if (misses(&fv[0], 1, tp, fp[0], fpl[0], f_root)) return -4;
+        if (misses(&fv[1], 1, tp + B, fp[1], fpl[1], f_root)) return -5;
+        if (misses(&fv[2], 1, tp + 2 * B, fp[2], fpl[2], f_root)) return -6;
+        if (!coset && misses(&fv[3], 1, tp, fp[3], fpl[3], roots[0])) return -7;
         // proof.rs:101-126: the s opened values of a group folded pairwise (t with t + s/2, then again)
         const uint32_t inv2 = invmod(2);
         for (uint32_t j = 0; j < G; ++j) {
@@ -350,16 +396,13 @@ inline int verify_proof(const uint8_t* data, size_t len, uint32_t log_n, uint32_
         for (uint32_t j = 0; j < G; ++j) {
             const uint32_t r0 = j * fold, steps = fold_steps(Rp, fold, j), s = 1u << steps;
             if (coset) {
-                if (lpl[j][0] != L - r0 - steps) return -(int)(200 + j);
-                compute_root_from_coset(lv[j], s, tp & (((size_t)1 << (L - r0 - steps)) - 1), lp[j][0], lpl[j][0], root, hash);
-                if (memcmp(root, roots[j], 32)) return -(int)(300 + j);
+                if (lpl[j][0] != L - r0 - steps - ce[j]) return -(int)(200 + j);
+                if (misses(lv[j], s, tp & (((size_t)1 << (L - r0 - steps)) - 1), lp[j][0], lpl[j][0], roots[j])) return -(int)(300 + j);
                 continue;
             }
-            for (uint32_t t = 0; t < s; ++t) if (lpl[j][t] != L - r0) return -(int)(200 + j);
-            for (uint32_t t = 0; t < s; ++t) {
-                compute_root_from_path(lv[j][t], coset_leaf(tp, (uint32_t)L - r0, steps, t), lp[j][t], lpl[j][t], root, hash);
-                if (memcmp(root, roots[j], 32)) return t == 0 ? -(int)(300 + j) : -(int)(400 + j);
-            }
+            for (uint32_t t = 0; t < s; ++t) if (lpl[j][t] != L - r0 - ce[j]) return -(int)(200 + j);
+            for (uint32_t t = 0; t < s; ++t)
+                if (misses(&lv[j][t], 1, coset_leaf(tp, (uint32_t)L - r0, steps, t), lp[j][t], lpl[j][t], roots[j])) return t == 0 ? -(int)(300 + j) : -(int)(400 + j);
         }
     }
     if (left != 0) return -8;
@@ -375,13 +418,16 @@ inline int verify_proof(const uint8_t* data, size_t len, uint32_t log_n, uint32_
 // Returns 0, or -(1000 + k) for the k-th challenge / -1998 for a grinding nonce whose hash has fewer than `grind` leading zero
 // bits (checked after the betas and before the first query challenge; it does not advance k) / -1999 for the state.
 // stop > 0: 3 + G' + q challenges; the coefficients are one commit, in the place of the last root and the free term.
+// cap > 0: every root commit is one commit of the tree's 2^ce digests, and a tuple's paths are ce digests shorter.
 inline int verify_transcript(const uint8_t* data, size_t len, const uint8_t state[32], uint32_t log_n, uint32_t log_b, uint32_t q = 1,
-                             uint32_t grind = 0, uint32_t fold = 1, bool coset = false, uint32_t stop = 0) {
+                             uint32_t grind = 0, uint32_t fold = 1, bool coset = false, uint32_t stop = 0, uint32_t cap = 0) {
     if (log_n < 2 || log_b < 1 || log_n + log_b > 30 || grind > kMaxGrindBits || fold < 1 || fold > kMaxFoldLog) return -1;
     if (!stop_ok(log_n, log_b, stop)) return -1;
     const size_t L = log_n + log_b;
     const uint32_t Rp = log_n - stop, G = fold_groups(Rp, fold);
-    if (q < 1 || q > 64 || len != proof_data_len(log_n, log_b, q, grind, fold, coset, stop)) return -1;
+    if (cap > kMaxCapLog || q < 1 || q > 64 || len != proof_data_len_cap(log_n, log_b, q, grind, fold, coset, stop, cap)) return -1;
+    const uint32_t cf = cap_eff(cap, (uint32_t)L);
+    auto ce = [&](uint32_t j) { return cap_eff(cap, group_tree_log(log_n, log_b, fold, coset, stop, j)); };
     Channel ch;
     const uint8_t* p = data;
     int k = 0;
@@ -394,12 +440,12 @@ inline int verify_transcript(const uint8_t* data, size_t len, const uint8_t stat
         commit(4);
         return true;
     };
-    commit(32);                                             // f_eval root
+    commit((size_t)32 << cf);                               // f_eval root (cap: its 2^ce digests, one commit, here and below)
     for (int i = 0; i < 3; ++i) if (!challenge()) return -(1000 + k);
-    commit(32);                                             // cp root
+    commit((size_t)32 << ce(0));                            // cp root
     for (uint32_t j = 0; j < G; ++j) {
         if (!challenge()) return -(1000 + k);               // the group's beta
-        if (!stop || j + 1 < G) commit(32);                 // root of the group's output
+        if (!stop || j + 1 < G) commit((size_t)32 << ce(j + 1));   // root of the group's output
     }
     commit(stop ? (size_t)4 << stop : 4);                   // free term, or the final polynomial's coefficients
     if (grind) {                                            // nonce: the commit is SHA-256(S || le64(w))
@@ -409,10 +455,10 @@ inline int verify_transcript(const uint8_t* data, size_t len, const uint8_t stat
     }
     for (uint32_t j = 0; j < q; ++j) if (!challenge()) return -(1000 + k);   // queries
     for (uint32_t j = 0; j < q; ++j) {
-        for (int i = 0; i < (coset ? 3 : 4); ++i) commit(Channel::group_bytes(1, L));
+        for (int i = 0; i < (coset ? 3 : 4); ++i) commit(Channel::group_bytes(1, L - (i < 3 ? cf : ce(0))));
         for (uint32_t gi = 0; gi < G; ++gi) {
             const size_t steps = fold_steps(Rp, fold, gi);
-            commit(Channel::group_bytes((size_t)1 << steps, L - (size_t)gi * fold - (coset ? steps : 0), coset));
+            commit(Channel::group_bytes((size_t)1 << steps, L - (size_t)gi * fold - (coset ? steps : 0) - ce(gi), coset));
         }
     }
     if (memcmp(ch.state, state, 32)) return -1999;

@@ -37,6 +37,17 @@
 // instance of its own (the instances without it are the code they were): the last group's fold is compared with p(x^(2^R')) by
 // Horner over the coefficients, each reduced % P on reading, canonical against canonical; and the transcript schedule has no last
 // root and commits the 2^D words in one piece where the free term was.
+//
+// Merkle caps (zk_verifier_set_merkle_cap, c = 1..8; verify_transcript, then verify_proof, with cap = c; any K, leaf format and D): every
+// root of the header is the tree's 2^ce digests and every path is ce digests shorter, with ce = min(c, lg - 1) per tree, so the small trees of
+// a proof have caps of their own and no offset keeps its closed form.  The layout is still fixed once the path counts have their values; the
+// host lays it out once per run into a table of at most 32 trees that travels with the launch arguments (CapLayout): per group the first word
+// of its opening, the digests of its paths, the header word of its beta and of the cap of its input tree.  Three kernels of their own read
+// it (verify_cap_algebra_kernel, verify_cap_paths_kernel, verify_cap_transcript_kernel: the kernels above are the code they were): one
+// instance per leaf format covers K = 1..3 and D (K = 1 is G = R groups of two values), a path walks lg - ce levels and is compared with
+// cap entry leaf >> (lg - ce), the transcript commits the 8 * 2^ce words of a cap in one piece.  Slot and tree are uniform per blockIdx.y, so
+// all lanes of a wave still walk paths of one length.  The order keys are those of a folded proof (5 + 9G per query) or of a coset proof
+// (4 + 2G).  No scratch and no LDS.
 #include <cstdio>
 #include <cstring>
 #include <mutex>
@@ -126,8 +137,8 @@ __device__ __forceinline__ uint32_t coset_rot(const VerifyArgs& a, uint32_t tp, 
 
 // proof.rs:63-77: the composition polynomial at x from f(x), f(gx), f(g^2 x), against the raw cp(x) of the proof: the value of
 // the fourth tuple, or, with coset leaves, slot rot0 of group 0's leaf, which starts where that tuple would
-__device__ __forceinline__ bool cp0_matches(const VerifyArgs& a, const uint32_t* pr, uint32_t p, uint32_t fq, uint32_t x, uint32_t rot0 = 0u) {
-    const uint32_t fb = 3u + 8u * a.L;
+// fb: words of an f tuple, aw: the header word of alpha0 (a root in front of it: 3 + 8 L and 8; a cap: CapLayout)
+__device__ __forceinline__ bool cp0_matches_at(const VerifyArgs& a, const uint32_t* pr, uint32_t p, uint32_t fq, uint32_t x, uint32_t rot0, uint32_t fb, uint32_t aw) {
     const uint32_t f_x = pr[fq] % P, f_gx = pr[fq + fb] % P, f_ggx = pr[fq + 2u * fb] % P, cp_raw = pr[fq + 3u * fb + rot0];
     const uint32_t p0 = dmul(sub(f_x, 1u), dinv(sub(x, 1u)));
     const uint32_t p1 = dmul(sub(f_x, a.pub[p] % P), dinv(sub(x, a.gm2)));
@@ -136,20 +147,25 @@ __device__ __forceinline__ bool cp0_matches(const VerifyArgs& a, const uint32_t*
     for (uint32_t i = 0; i < a.log_n; ++i) xn = dmul(xn, xn);
     const uint32_t den = dmul(sub(xn, 1u), dinv(dmul(dmul(sub(x, a.gm3), sub(x, a.gm2)), sub(x, a.gm1))));
     const uint32_t p2 = dmul(num, dinv(den));
-    const uint32_t cp0 = add(add(dmul(pr[8] % P, p0), dmul(pr[9] % P, p1)), dmul(pr[10] % P, p2));
+    const uint32_t cp0 = add(add(dmul(pr[aw] % P, p0), dmul(pr[aw + 1u] % P, p1)), dmul(pr[aw + 2u] % P, p2));
     return cp0 == cp_raw;
+}
+__device__ __forceinline__ bool cp0_matches(const VerifyArgs& a, const uint32_t* pr, uint32_t p, uint32_t fq, uint32_t x, uint32_t rot0 = 0u) {
+    return cp0_matches_at(a, pr, p, fq, x, rot0, 3u + 8u * a.L, 8u);
 }
 
 // Early stop: p(xs) for xs = x^(2^R'), the point of the stopped layer, by Horner from the highest of the 2^D coefficients; each is
 // reduced % P on reading (verify_proof does the same), the result is canonical.  xs goes to Montgomery form once, so a step is one
 // mont_mul (canonical * Montgomery = canonical) and one add.  Every lane of a proof reads the same <= 256 words.
-__device__ __forceinline__ uint32_t final_poly_at(const VerifyArgs& a, const uint32_t* pr, uint32_t xs) {
-    const uint32_t* c = pr + 11u + 9u * a.G;
+__device__ __forceinline__ uint32_t final_poly_from(const VerifyArgs& a, const uint32_t* c, uint32_t xs) {
     const uint32_t xm = mont_mul(xs, R2);
     uint32_t acc = 0u;
 #pragma unroll 1
     for (uint32_t k = 1u << a.D; k-- > 0u;) acc = add(mont_mul(acc, xm), c[k] % P);
     return acc;
+}
+__device__ __forceinline__ uint32_t final_poly_at(const VerifyArgs& a, const uint32_t* pr, uint32_t xs) {
+    return final_poly_from(a, pr + 11u + 9u * a.G, xs);
 }
 // ... for the grouped kernels, which carry only the inverse power of x: R' <= 29 squarings of x give the forward one
 __device__ __forceinline__ uint32_t final_poly_at_power(const VerifyArgs& a, const uint32_t* pr, uint32_t x) {
@@ -560,6 +576,211 @@ __global__ void __launch_bounds__(kVerifyThreads) verify_transcript_kernel(Verif
     a.tcode[p] = code;
 }
 
+// ---- Merkle caps (the file header) ---------------------------------------------------------------------------------------------
+// The layout of a capped proof, in 32-bit words.  Group j < G opens the tree over its input layer; entry G of capw / capn is the tree over
+// the last layer (D = 0), which nothing opens.  a.K, a.G, a.ls describe the groups as for a folded proof, K = 1 included.
+constexpr uint32_t kCapTrees = 32;
+struct CapLayout {
+    uint32_t fplen, fwords;     // an f path has L - ce_f digests; an f tuple 3 + 8 fplen words
+    uint32_t cpplen, cpwords;   // one-value leaves: the cp(x) tuple, a path into the tree of group 0
+    uint32_t fcapn, aw, ftw;    // words of f's cap (it starts the proof); header word of alpha0; of the free term / the coefficients
+    uint32_t bw[kCapTrees];     // header word of group j's beta
+    uint32_t capw[kCapTrees];   // header word of the cap of the tree over group j's input layer
+    uint32_t capn[kCapTrees];   // its words: 8 * 2^ce
+    uint32_t plen[kCapTrees];   // digests of a path into that tree: lg - ce
+    uint32_t gw[kCapTrees];     // first word of group j's opening, counted from the first word of the query
+};
+struct VerifyCapArgs {
+    VerifyArgs a;
+    CapLayout t;
+};
+
+__device__ __forceinline__ uint32_t cap_group_steps(const VerifyArgs& a, uint32_t j) { return j + 1u < a.G ? a.K : a.ls; }
+
+// (1) with caps: one lane per (proof, query).  Path counts, the cp0 relation (-2) and the G fold comparisons (-(100 + j)), for every K
+// (the steps of a group select the unrolled fold) and D (a.D != 0: the last comparison is against p(x^(2^R))).
+template <bool COSET>
+__global__ void __launch_bounds__(kVerifyThreads) verify_cap_algebra_kernel(VerifyCapArgs ca) {
+    const VerifyArgs& a = ca.a;
+    const CapLayout& t = ca.t;
+    const uint64_t lane = (uint64_t)blockIdx.x * kVerifyThreads + threadIdx.x;
+    if (lane >= (uint64_t)a.count * a.q) return;
+    const uint32_t p = (uint32_t)(lane / a.q), qk = (uint32_t)(lane % a.q);
+    const uint32_t* pr = a.proofs + (size_t)p * a.words;
+    const uint32_t keys = COSET ? 4u + 2u * a.G : 5u + 9u * a.G, first = COSET ? 4u : 5u;
+    const uint32_t fq = a.qbase + qk * a.per_q;
+    bool ok = true;
+    for (uint32_t j = 0; j < 3; ++j) {
+        const uint32_t* c = pr + fq + j * t.fwords + 1u;
+        ok = ok && c[0] == t.fplen && c[1] == 0u;
+    }
+    if constexpr (!COSET) {
+        const uint32_t* c = pr + fq + 3u * t.fwords + 1u;
+        ok = ok && c[0] == t.cpplen && c[1] == 0u;
+    }
+#pragma unroll 1
+    for (uint32_t j = 0; j < a.G; ++j) {
+        const uint32_t s = 1u << cap_group_steps(a, j), len = t.plen[j];
+        const uint32_t* c = pr + fq + t.gw[j] + s;
+        if constexpr (COSET) ok = ok && c[0] == len && c[1] == 0u;
+        else for (uint32_t u = 0; u < s; ++u) ok = ok && c[u * (2u + 8u * len)] == len && c[u * (2u + 8u * len) + 1u] == 0u;
+    }
+    if (!ok) { a.malformed[p] = 1u; return; }
+
+    const uint32_t tp = query_tp(a, pr, qk);
+    const uint32_t x = dmul(GEN_W, dpow(a.h, tp));
+    int32_t key = kNoFailure;
+    if (!cp0_matches_at(a, pr, p, fq, x, COSET ? coset_rot(a, tp, 0u) : 0u, t.fwords, t.aw)) key = (int32_t)(qk * keys);
+    uint32_t ixk = dinv(x);                               // x = 5 h^tp is never zero: the one inversion of this lane's folds
+#pragma unroll 1
+    for (uint32_t j = 0; j < a.G && key == kNoFailure; ++j) {
+        const uint32_t* vals = pr + fq + t.gw[j];
+        const uint32_t beta = pr[t.bw[j]] % P, rot = COSET ? coset_rot(a, tp, j) : 0u, steps = cap_group_steps(a, j);
+        uint32_t calc;
+        if (steps == 3u) calc = fold_group<3>(a, vals, beta, ixk, rot);
+        else if (steps == 2u) calc = fold_group<2>(a, vals, beta, ixk, rot);
+        else calc = fold_group<1>(a, vals, beta, ixk, rot);
+        uint32_t expect;
+        if (j + 1u < a.G) expect = pr[fq + t.gw[j + 1u] + (COSET ? coset_rot(a, tp, j + 1u) : 0u)];
+        else if (a.D) {
+            uint32_t xs = x;
+#pragma unroll 1
+            for (uint32_t i = 0; i < a.R; ++i) xs = dmul(xs, xs);
+            expect = final_poly_from(a, pr + t.ftw, xs);
+        } else expect = pr[t.ftw];
+        if (calc != expect) key = (int32_t)(qk * keys + first + j);
+    }
+    if (key != kNoFailure) atomicMin(&a.best[p], key);
+}
+
+// (2) with caps: one lane per (proof, query, path slot), the slots of verify_paths_kernel<.., FOLD> (4 + sum s_j) or of
+// verify_coset_paths_kernel (3 + G).  A path climbs plen = lg - ce levels from the leaf's position inside the sub-tree of its cap entry
+// and is compared with entry idx >> plen of the tree's cap.  plen depends on the slot alone: uniform over the wave.
+template <int HASH, bool COSET>
+__global__ void __launch_bounds__(kVerifyThreads) verify_cap_paths_kernel(VerifyCapArgs ca) {
+    const VerifyArgs& a = ca.a;
+    const CapLayout& t = ca.t;
+    const uint32_t p = blockIdx.x * kVerifyThreads + threadIdx.x;
+    if (p >= a.count) return;
+    const uint32_t slots = COSET ? 3u + a.G : 4u + ((a.G - 1u) << a.K) + (1u << a.ls);
+    const uint32_t qk = blockIdx.y / slots, slot = blockIdx.y % slots;
+    const uint32_t* pr = a.proofs + (size_t)p * a.words;
+    const uint32_t tp = query_tp(a, pr, qk);
+    const uint32_t fq = a.qbase + qk * a.per_q;
+    uint32_t val_w, path_w, plen, idx, capw, pos, s = 1u;
+    if (slot < 3u) {                                      // f(x), f(gx), f(g^2 x) against f's cap
+        val_w = fq + slot * t.fwords;
+        path_w = val_w + 3u;
+        plen = t.fplen;
+        idx = tp + slot * a.B;
+        capw = 0u;
+        pos = 1u + slot;
+    } else if (!COSET && slot == 3u) {                    // cp(x) against the cap of group 0's tree
+        val_w = fq + 3u * t.fwords;
+        path_w = val_w + 3u;
+        plen = t.cpplen;
+        idx = tp;
+        capw = t.capw[0];
+        pos = 4u;
+    } else if constexpr (COSET) {                         // the leaf of group j from its s_j slot words
+        const uint32_t j = slot - 3u, steps = cap_group_steps(a, j);
+        s = 1u << steps;
+        val_w = fq + t.gw[j];
+        path_w = val_w + s + 2u;
+        plen = t.plen[j];
+        idx = tp & ((1u << (a.L - j * a.K - steps)) - 1u);
+        capw = t.capw[j];
+        pos = 4u + a.G + j;
+    } else {                                              // value u of group j at (tp % size + u size / s) % size
+        const uint32_t j = (slot - 4u) >> a.K, u = (slot - 4u) & ((1u << a.K) - 1u);
+        const uint32_t gs = 1u << cap_group_steps(a, j), gw = fq + t.gw[j], size = a.N >> (j * a.K);
+        plen = t.plen[j];
+        val_w = gw + u;
+        path_w = gw + gs + u * (2u + 8u * plen) + 2u;
+        idx = (tp % size + u * (size / gs)) % size;
+        capw = t.capw[j];
+        pos = 5u + a.G + 8u * j + u;
+    }
+    Digest cur;
+    if constexpr (COSET) cur = coset_vleaf<HASH>(pr + val_w, s);
+    else cur = vleaf<HASH>(pr[val_w]);
+    uint32_t node = (idx & ((1u << plen) - 1u)) + (1u << plen) - 1u;   // heap index inside the sub-tree of the cap entry
+    for (uint32_t lvl = 0; lvl < plen; ++lvl) {
+        Digest sib;
+        const uint32_t* sp = pr + path_w + 8u * lvl;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) sib.w[i] = be_word(sp + i);
+        const bool right = (node & 1u) == 0u;             // an even heap index is a right child
+        Digest l, r;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) { l.w[i] = right ? sib.w[i] : cur.w[i]; r.w[i] = right ? cur.w[i] : sib.w[i]; }
+        cur = vinner<HASH>(l, r);
+        node = (node - (right ? 2u : 1u)) >> 1;
+    }
+    const uint32_t* entry = pr + capw + 8u * (idx >> plen);   // idx < 2^lg, so the entry is one of the cap's 2^ce
+    bool same = true;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) same = same && cur.w[i] == be_word(entry + i);
+    if (!same) atomicMin(&a.best[p], (int32_t)(qk * (COSET ? 4u + 2u * a.G : 5u + 9u * a.G) + pos));
+}
+
+// (3) with caps (strict only): one lane per proof, the schedule of verify_transcript_kernel with every root commit widened to the cap's
+// words and every tuple shortened to its paths' digests; D != 0 drops the last root and commits the 2^D coefficients where the free term was.
+template <bool COSET>
+__global__ void __launch_bounds__(kVerifyThreads) verify_cap_transcript_kernel(VerifyCapArgs ca) {
+    const VerifyArgs& a = ca.a;
+    const CapLayout& t = ca.t;
+    constexpr uint32_t NF = COSET ? 3u : 4u;              // f tuples per query
+    const uint32_t p = blockIdx.x * kVerifyThreads + threadIdx.x;
+    if (p >= a.count) return;
+    const uint32_t* pr = a.proofs + (size_t)p * a.words;
+    uint32_t st[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) st[i] = 0u;
+    const uint32_t R = a.G, q = a.q;
+    // steps: f cap | 3 alphas | cap 0 | R x (beta, cap j + 1) | free term | [nonce] | q query raws | q x (NF f tuples, R groups)
+    // D != 0: the last beta has no cap after it, and the step of the free term commits the 2^D coefficients
+    const uint32_t gs = a.gw ? 1u : 0u;
+    const uint32_t ft = (a.D ? 4u : 5u) + 2u * R;
+    const uint32_t head = ft + 1u + gs + q;
+    const uint32_t steps = head + q * (NF + R);
+    uint32_t cur = 0, k = 0;
+    int32_t code = 0;
+    for (uint32_t s = 0; s < steps; ++s) {
+        bool chal = false;
+        uint32_t nw;
+        if (s < head) {
+            chal = (s >= 1u && s <= 3u) || (s >= 5u && s < ft && ((s - 5u) & 1u) == 0u) || s >= ft + 1u + gs;
+            if (chal) nw = 1u;
+            else if (s == 0u) nw = t.fcapn;
+            else if (s < ft) nw = t.capn[(s - 4u) >> 1];  // s = 4: the tree of group 0; s = 6 + 2j: of group j + 1 (the last layer's: entry G)
+            else nw = s == ft ? 1u << a.D : 2u;           // D = 0: the free term, one word
+        } else {
+            const uint32_t u = (s - head) % (NF + R);
+            if (u < 3u) nw = t.fwords;
+            else if (!COSET && u == 3u) nw = t.cpwords;
+            else {
+                const uint32_t j = u - NF, gsteps = cap_group_steps(a, j);
+                nw = COSET ? (1u << gsteps) + 2u + 8u * t.plen[j] : (3u + 8u * t.plen[j]) << gsteps;
+            }
+        }
+        if (chal) {                                       // state word 0 (big-endian bytes 0..3) against the little-endian u32 here
+            ++k;
+            if (st[0] != pr[cur]) { code = -(int32_t)(1000u + k); break; }
+        }
+        commit_words(st, pr + cur, nw);
+        cur += nw;
+        if (gs && s == ft + 1u && (st[0] & a.gmask) != 0u) { code = -1998; break; }   // SHA-256(S || le64(w)) is the new state
+    }
+    if (code == 0) {
+        bool same = true;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) same = same && st[i] == be_word(a.states + (size_t)p * 8u + i);
+        if (!same) code = -1999;
+    }
+    a.tcode[p] = code;
+}
+
 std::mutex g_consts_mu;
 bool g_consts_done[64] = {false};
 
@@ -614,6 +835,7 @@ struct zk_verifier {
     int hash = ZK_HASH_SHA256;
     bool coset = false;                                // proofs with coset leaves (zk_verifier_set_coset_leaves)
     uint32_t stop = 0;                                 // early stop D (zk_verifier_set_fri_stop): the proofs carry 2^D coefficients
+    uint32_t cap_log = 0;                              // Merkle caps c (zk_verifier_set_merkle_cap): every tree is committed at depth min(c, lg - 1)
     hipStream_t stream = nullptr, tstream = nullptr;   // paths + algebra; transcript (runs beside them)
     hipEvent_t ev_in = nullptr, ev_t = nullptr;
     uint8_t* d_buf = nullptr;                          // proofs, public_last, states, then the three per-proof results
@@ -682,8 +904,34 @@ int verifier_chunk(zk_verifier* v, const uint8_t* proofs, size_t stride, size_t 
         if (coset) a.per_q += (1u << steps) + 2u + 8u * (L - j * K - steps);
         else a.per_q += (3u + 8u * (L - j * K)) << steps;   // K = 1: 6 + 16 (L - j)
     }
-    if (a.qbase + (size_t)q * a.per_q != len / 4) return fail(ZK_ERR_STATE, "zk_verifier_run: the layout does not add up to the proof length");
     a.K = K; a.G = G; a.ls = fold_steps(R, K, G - 1u);
+    CapLayout t{};
+    if (v->cap_log) {                                      // Merkle caps: the same fields, each tree with its own cap depth (CapLayout)
+        if (G + 1u > kCapTrees) return fail(ZK_ERR_STATE, "zk_verifier_run: more than %u trees", kCapTrees);
+        const uint32_t cf = cap_eff(v->cap_log, L);
+        auto ce = [&](uint32_t j) { return cap_eff(v->cap_log, group_tree_log(log_n, log_b, K, coset, D, j)); };
+        t.fplen = L - cf; t.fwords = 3u + 8u * t.fplen;
+        t.cpplen = L - ce(0); t.cpwords = 3u + 8u * t.cpplen;
+        uint32_t w = t.fcapn = 8u << cf;
+        t.aw = w; w += 3u;
+        t.capw[0] = w; t.capn[0] = 8u << ce(0); w += t.capn[0];
+        for (uint32_t j = 0; j < G; ++j) {
+            t.bw[j] = w++;
+            if (D && j + 1u == G) break;                   // a stopped proof has no tree over its last layer
+            t.capw[j + 1u] = w; t.capn[j + 1u] = 8u << ce(j + 1u); w += t.capn[j + 1u];
+        }
+        t.ftw = w; w += D ? 1u << D : 1u;
+        a.qbase = w + a.gw + q;
+        uint32_t off = 3u * t.fwords + (coset ? 0u : t.cpwords);
+        for (uint32_t j = 0; j < G; ++j) {
+            const uint32_t steps = fold_steps(R, K, j);
+            t.plen[j] = group_tree_log(log_n, log_b, K, coset, D, j) - ce(j);
+            t.gw[j] = off;
+            off += coset ? (1u << steps) + 2u + 8u * t.plen[j] : (3u + 8u * t.plen[j]) << steps;
+        }
+        a.per_q = off;
+    }
+    if (a.qbase + (size_t)q * a.per_q != len / 4) return fail(ZK_ERR_STATE, "zk_verifier_run: the layout does not add up to the proof length");
     const uint32_t w = invmod(powmod(a.h, (uint64_t)a.N >> 3));
     a.inv2m = to_mont(a.inv2); a.wm1 = to_mont(w); a.wm2 = to_mont(mulmod(w, w)); a.wm3 = to_mont(mulmod(mulmod(w, w), w));
 
@@ -694,10 +942,14 @@ int verifier_chunk(zk_verifier* v, const uint8_t* proofs, size_t stride, size_t 
     HIPCHK(hipMemsetAsync(a.malformed, 0, count * 4, v->stream));
     HIPCHK(hipMemsetAsync(a.tcode, 0, count * 4, v->stream));
     const uint32_t gx = (uint32_t)((count + kVerifyThreads - 1) / kVerifyThreads);
+    const VerifyCapArgs ca{a, t};
     if (states) {                                      // the transcript chains run beside the paths: cost = max of the two
         HIPCHK(hipEventRecord(v->ev_in, v->stream));
         HIPCHK(hipStreamWaitEvent(v->tstream, v->ev_in, 0));
-        if (D) {
+        if (v->cap_log) {
+            if (coset) hipLaunchKernelGGL(verify_cap_transcript_kernel<true>, dim3(gx), dim3(kVerifyThreads), 0, v->tstream, ca);
+            else hipLaunchKernelGGL(verify_cap_transcript_kernel<false>, dim3(gx), dim3(kVerifyThreads), 0, v->tstream, ca);
+        } else if (D) {
             if (coset) hipLaunchKernelGGL((verify_transcript_kernel<true, true, true>), dim3(gx), dim3(kVerifyThreads), 0, v->tstream, a);
             else if (K == 1) hipLaunchKernelGGL((verify_transcript_kernel<false, false, true>), dim3(gx), dim3(kVerifyThreads), 0, v->tstream, a);
             else hipLaunchKernelGGL((verify_transcript_kernel<true, false, true>), dim3(gx), dim3(kVerifyThreads), 0, v->tstream, a);
@@ -709,7 +961,10 @@ int verifier_chunk(zk_verifier* v, const uint8_t* proofs, size_t stride, size_t 
     }
     const uint64_t lanes = (uint64_t)count * q;
     const dim3 agrid((uint32_t)((lanes + kVerifyThreads - 1) / kVerifyThreads));
-    if (D) {                                           // the STOP instances: the last group against the final polynomial
+    if (v->cap_log) {                                      // one instance per leaf format covers every K and D
+        if (coset) hipLaunchKernelGGL(verify_cap_algebra_kernel<true>, agrid, dim3(kVerifyThreads), 0, v->stream, ca);
+        else hipLaunchKernelGGL(verify_cap_algebra_kernel<false>, agrid, dim3(kVerifyThreads), 0, v->stream, ca);
+    } else if (D) {                                           // the STOP instances: the last group against the final polynomial
         if (coset) {
             if (K == 1) hipLaunchKernelGGL((verify_coset_algebra_kernel<1, true>), agrid, dim3(kVerifyThreads), 0, v->stream, a);
             else if (K == 2) hipLaunchKernelGGL((verify_coset_algebra_kernel<2, true>), agrid, dim3(kVerifyThreads), 0, v->stream, a);
@@ -726,7 +981,14 @@ int verifier_chunk(zk_verifier* v, const uint8_t* proofs, size_t stride, size_t 
     else hipLaunchKernelGGL(verify_fold_algebra_kernel<3>, agrid, dim3(kVerifyThreads), 0, v->stream, a);
     HIPCHK(hipGetLastError());
     const bool sha = v->hash == ZK_HASH_SHA256;
-    if (coset) {
+    if (v->cap_log) {
+        const dim3 pgrid(gx, q * (coset ? 3u + G : 4u + ((G - 1u) << K) + (1u << a.ls)));
+        if (coset) {
+            if (sha) hipLaunchKernelGGL((verify_cap_paths_kernel<0, true>), pgrid, dim3(kVerifyThreads), 0, v->stream, ca);
+            else hipLaunchKernelGGL((verify_cap_paths_kernel<1, true>), pgrid, dim3(kVerifyThreads), 0, v->stream, ca);
+        } else if (sha) hipLaunchKernelGGL((verify_cap_paths_kernel<0, false>), pgrid, dim3(kVerifyThreads), 0, v->stream, ca);
+        else hipLaunchKernelGGL((verify_cap_paths_kernel<1, false>), pgrid, dim3(kVerifyThreads), 0, v->stream, ca);
+    } else if (coset) {
         const dim3 pgrid(gx, q * (3u + G));
         if (sha) hipLaunchKernelGGL(verify_coset_paths_kernel<0>, pgrid, dim3(kVerifyThreads), 0, v->stream, a);
         else hipLaunchKernelGGL(verify_coset_paths_kernel<1>, pgrid, dim3(kVerifyThreads), 0, v->stream, a);
@@ -752,9 +1014,9 @@ int verifier_chunk(zk_verifier* v, const uint8_t* proofs, size_t stride, size_t 
         int32_t c;
         if (states && tcode[i]) c = tcode[i];
         else if (malformed[i])                             // garbage only
-            c = verify_proof(proofs + i * stride, len, log_n, log_b, public_last[i], v->hash, q, v->grind, K, coset, D);
+            c = verify_proof(proofs + i * stride, len, log_n, log_b, public_last[i], v->hash, q, v->grind, K, coset, D, v->cap_log);
         else if (best[i] == kNoFailure) c = 0;
-        else c = coset ? coset_key_to_check(best[i], G) : K == 1 ? key_to_check(best[i], R) : fold_key_to_check(best[i], G);
+        else c = coset ? coset_key_to_check(best[i], G) : (K == 1 && !v->cap_log) ? key_to_check(best[i], R) : fold_key_to_check(best[i], G);
         checks_out[i] = c;
     }
     return ZK_OK;
@@ -846,6 +1108,15 @@ int zk_verifier_set_fri_stop(zk_verifier* v, uint32_t stop_log) {
 
 uint32_t zk_verifier_get_fri_stop(const zk_verifier* v) { return v ? v->stop : 0u; }
 
+int zk_verifier_set_merkle_cap(zk_verifier* v, uint32_t cap_log) {
+    if (!v) return fail(ZK_ERR_INVALID, "null verifier");
+    if (cap_log > kMaxCapLog) return fail(ZK_ERR_INVALID, "zk_verifier_set_merkle_cap: need cap_log <= %u (got %u)", kMaxCapLog, cap_log);
+    v->cap_log = cap_log;
+    return ZK_OK;
+}
+
+uint32_t zk_verifier_get_merkle_cap(const zk_verifier* v) { return v ? v->cap_log : 0u; }
+
 int zk_verifier_set_coset_leaves(zk_verifier* v, int on) {
     if (!v) return fail(ZK_ERR_INVALID, "null verifier");
     v->coset = on != 0;
@@ -859,7 +1130,7 @@ int zk_verifier_run(zk_verifier* v, const uint8_t* proofs, size_t stride, size_t
     if (!v) return fail(ZK_ERR_INVALID, "null verifier");
     if (count == 0) return ZK_OK;
     if (!proofs || !public_last || !checks_out) return fail(ZK_ERR_INVALID, "zk_verifier_run: null argument");
-    const size_t len = proof_data_len(v->log_n, v->log_b, v->queries, v->grind, v->fold, v->coset, v->stop);
+    const size_t len = proof_data_len_cap(v->log_n, v->log_b, v->queries, v->grind, v->fold, v->coset, v->stop, v->cap_log);
     if (stride < len) return fail(ZK_ERR_INVALID, "zk_verifier_run: stride %zu < proof length %zu", stride, len);
     if (count > SIZE_MAX / stride) return fail(ZK_ERR_INVALID, "zk_verifier_run: count * stride overflows");
     HIPCHK(hipSetDevice(v->device));

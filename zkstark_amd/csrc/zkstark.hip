@@ -126,6 +126,13 @@ struct zk_ctx {
     uint32_t* d_final = nullptr;        // 1 + 2^kFinalPolyMaxLog words, allocated by the first call that needs it
     std::vector<uint32_t> final_poly;   // the last proof's coefficients (stop = 0: the free term)
     int hash = 0;                      // Merkle hash (zk_hash_kind): 0 = SHA-256 (reference), 1 = field-native (configs[4]), 2 = BLAKE2s-256
+    // Merkle caps (zk_ctx_set_merkle_cap; transcript.hpp): a one-call proof commits the 2^ce digests of depth ce = min(cap, lg - 1) of
+    // every tree and builds nothing above them.  cap_now: the setting while a one-call proof runs, 0 otherwise (the stage-by-stage
+    // API builds whole trees).  tree_cap[t]: the depth tree t was last built down to (set by whatever built it); nodes above it are
+    // not defined.  cap_digests[t]: what the last proof committed for tree t when tree_cap[t] > 0.
+    uint32_t cap = 0, cap_now = 0;
+    uint8_t tree_cap[40] = {};
+    std::vector<uint8_t> cap_digests[40];
     // opt-in reference self-checks (zk_ctx_set_checks; prover.rs:64-66, :148-159, :169, :228-251)
     bool checks = false;
     uint32_t* d_check = nullptr;        // N words of scratch + 2 result words
@@ -194,6 +201,13 @@ uint32_t top_of(const zk_ctx* c, uint32_t tree) {
     const uint32_t lg = tree_log(c, tree);                            // coset trees are up to 8x smaller: the rule below is about leaves
     return lg > c->host_top ? c->host_top : lg - 1;                 // a smaller tree hands over one level below its leaves
 }
+// The depth a one-call proof commits tree `tree` at (0: its root), and the depth its build is handed over at: the deeper of that and
+// the host's share.  Between the two the host hashes (SHA-256 only: top_of is 0 for the other hashes); above the cap nobody does.
+uint32_t cap_of(const zk_ctx* c, uint32_t tree) { return c->cap_now ? cap_eff(c->cap_now, tree_log(c, tree)) : 0; }
+uint32_t hand_of(const zk_ctx* c, uint32_t tree) {
+    const uint32_t h = top_of(c, tree), ce = cap_of(c, tree);
+    return h > ce ? h : ce;
+}
 // What the commit launch of `tree` posts to the host.  host = true (one-call flows): the digests of depth
 // host_top instead of the root, and for the layer with 2^(host_tail+1) values the values too -- the host
 // folds on from there.
@@ -209,8 +223,10 @@ MailArgs mail_of(zk_ctx* c, uint32_t tree, bool host, bool feed_tail = true, uin
     m.seq = ++c->mail_seq;
     c->tree_seq[tree] = m.seq;
     m.counter = c->d_counter;
-    m.top = host ? top_of(c, tree) : 0;
-    if (feed_tail && c->fold == 1 && !c->coset && !c->stop && m.top && c->host_tail && tree >= 1 && layer_log(c, tree) == c->host_tail + 1) {
+    const uint32_t host_levels = host ? top_of(c, tree) : 0;
+    c->tree_cap[tree] = (uint8_t)(host ? cap_of(c, tree) : 0);
+    m.top = host ? hand_of(c, tree) : 0;
+    if (feed_tail && c->fold == 1 && !c->coset && !c->stop && host_levels && c->host_tail && tree >= 1 && layer_log(c, tree) == c->host_tail + 1) {
         m.dump_src = c->d_layers + c->layer_off[tree];
         m.dump_log = c->host_tail + 1;
         m.vals_off = (uint32_t)kMailValsOff;
@@ -274,11 +290,39 @@ int stage_seg(zk_ctx* c, const uint32_t* src, size_t dst, size_t words, uint32_t
     return ZK_OK;
 }
 
-// Result of the commit launch of `tree`: either the root itself, or the 2^host_top digests of depth
-// host_top, which this thread reduces to the root (merkle.rs:40-46) and keeps for the scatter.
+// read_commit for a tree committed at depth ce > 0 and handed over at depth H >= ce.
+int read_commit_cap(zk_ctx* c, uint32_t tree, uint32_t H, uint32_t ce, uint8_t root[32]) {
+    const size_t cnt = (size_t)1 << H, first = ((size_t)1 << ce) - 1, ncap = (size_t)1 << ce;
+    uint32_t* nodes = stage_alloc(c, (2 * cnt - 1) * 8);       // heap positions as in read_commit; [0, first) stays unused
+    if (!nodes) return fail(ZK_ERR_STATE, "host staging buffer exhausted");
+    int rc = wait_mail(c, c->tree_seq[tree]);
+    if (rc) return rc;
+    double t0 = now_us();
+    memcpy(nodes + 8 * (cnt - 1), c->h_mailbox + kMailDigests, cnt * 32);
+    if (H > ce) {                                              // the 2^ce sub-trees below the cap entries, each down from depth H
+        if (c->pool) c->pool->run(ncap, 1, [&](size_t sub) { host_sha_reduce_sub(nodes, H, ce, sub); });
+        else for (size_t sub = 0; sub < ncap; ++sub) host_sha_reduce_sub(nodes, H, ce, sub);
+    }
+    std::vector<uint8_t>& cd = c->cap_digests[tree];
+    cd.resize(32 * ncap);
+    for (size_t i = 0; i < ncap; ++i) digest_words_to_bytes(nodes + 8 * (first + i), cd.data() + 32 * i);
+    memset(root, 0, 32);
+    c->t_host_hash += now_us() - t0;
+    if (c->tail_have && c->tail_log == layer_log(c, tree) && tree >= 1) {     // this launch dumped its leaves (mail_of)
+        c->tail_vals.assign(c->h_mailbox + kMailValsOff, c->h_mailbox + kMailValsOff + ((size_t)1 << c->tail_log));
+    }
+    c->host_nodes[tree] = nodes;
+    c->host_node_cnt[tree] = 2 * cnt - 1;                 // open_path never asks for a node above depth ce
+    return H > ce ? stage_seg(c, nodes + 8 * first, c->tree_off[tree] + 8 * first, (cnt - 1 - first) * 8, 0) : (int)ZK_OK;
+}
+
+// Result of the commit launch of `tree`: either the root itself, or the 2^H digests of the hand-over depth H, which this thread
+// reduces to the root (merkle.rs:40-46) and keeps for the scatter.  With a cap at depth ce > 0 the reduction stops there (nothing to
+// do when H = ce), cap_digests[tree] gets the 2^ce digests and `root` is zeroed; nodes above depth ce are neither built nor staged.
 int read_commit(zk_ctx* c, uint32_t tree, uint8_t root[32]) {
-    const uint32_t H = top_of(c, tree);
+    const uint32_t H = hand_of(c, tree), ce = cap_of(c, tree);
     if (!H) return read_root(c, tree, root);
+    if (ce) return read_commit_cap(c, tree, H, ce, root);
     const size_t cnt = (size_t)1 << H;
     uint32_t* nodes = stage_alloc(c, (2 * cnt - 1) * 8);
     if (!nodes) return fail(ZK_ERR_STATE, "host staging buffer exhausted");
@@ -330,6 +374,13 @@ int host_fold_commit(zk_ctx* c, uint32_t round, uint32_t beta_raw, uint8_t root[
     c->tail_log = log_out;
     c->t_host_hash += now_us() - t_begin;
     c->tree_steps[2 + round] = 0;
+    c->tree_cap[2 + round] = (uint8_t)cap_of(c, 2 + round);   // the small tree is built whole; the cap is read out of it
+    if (const uint32_t ce = c->tree_cap[2 + round]) {
+        std::vector<uint8_t>& cd = c->cap_digests[2 + round];
+        cd.resize((size_t)32 << ce);
+        for (size_t i = 0; i < ((size_t)1 << ce); ++i) digest_words_to_bytes(nodes + 8 * (((size_t)1 << ce) - 1 + i), cd.data() + 32 * i);
+        memset(root, 0, 32);
+    }
     c->host_vals[2 + round] = vals;
     c->host_nodes[2 + round] = nodes;
     c->host_node_cnt[2 + round] = 2 * half - 1;
@@ -377,6 +428,13 @@ void release_gated_fold(zk_ctx* c, uint32_t round, uint32_t beta_raw) {
 struct GateGuard {
     zk_ctx* c;
     ~GateGuard() { if (c->gate_pending) release_gate(c, 0u); }
+};
+
+// The cap setting holds for the trees a one-call proof builds, and for nothing else.
+struct CapScope {
+    zk_ctx* c;
+    explicit CapScope(zk_ctx* ctx) : c(ctx) { c->cap_now = c->tail ? 0 : c->cap; }
+    ~CapScope() { c->cap_now = 0; }
 };
 
 void begin_proof(zk_ctx* c) {
@@ -524,8 +582,9 @@ void open_val(zk_ctx* c, uint32_t layer, size_t x) {
     if (c->host_vals[layer]) c->fetch_vals[c->open_vi++] = c->host_vals[layer] + x;
     else { c->fetch_vdev[c->open_vi++] = (uint32_t)c->open_nv; c->h_gather_off[c->open_nv++] = (uint64_t)c->layer_off[layer] + x; }
 }
-void open_path(zk_ctx* c, uint32_t tree, size_t m, size_t leaf) {          // merkle.rs:54-71: the sibling at every depth
-    for (size_t i = leaf + m - 1; i != 0; i = (i - 1) >> 1) {
+void open_path(zk_ctx* c, uint32_t tree, size_t m, size_t leaf) {          // merkle.rs:54-71: the sibling at every depth below the cap
+    const size_t stop_at = ((size_t)2 << c->tree_cap[tree]) - 2;            // the last node of the cap's depth (cap 0: the root)
+    for (size_t i = leaf + m - 1; i > stop_at; i = (i - 1) >> 1) {
         const size_t nd = (i & 1) ? i + 1 : i - 1;
         if (nd < c->host_node_cnt[tree]) c->fetch_nodes.push_back(c->host_nodes[tree] + 8 * nd);
         else { c->fetch_nodes.push_back(c->h_gather_out + 8 * c->open_ndg); ++c->open_ndg; c->fetch_ditems.push_back((uint64_t)c->tree_off[tree] + (uint64_t)nd * 8); }
@@ -549,6 +608,14 @@ int open_wait(zk_ctx* c) {
     return wait_mail(c, c->mail_seq);
 }
 
+// The commitment of tree `tree`, once read_commit or host_fold_commit has it: the root (prover.rs:85), or with a cap at depth
+// ce > 0 the 2^ce digests in ONE commit; info.roots[tree] stays zero then (zk_ctx_merkle_cap has the digests).
+void commit_tree(zk_ctx* c, Channel& ch, uint32_t tree, const uint8_t root[32]) {
+    if (c->tree_cap[tree]) { ch.commit_bytes(c->cap_digests[tree].data(), c->cap_digests[tree].size()); return; }
+    ch.commit_hash(root);
+    memcpy(c->info.roots[tree], root, 32);
+}
+
 // FRI rounds of a proof folded by 2^fold between commitments (fold > 1; DESIGN.md "Folding factor"): per group of
 // `steps` rounds one challenge, one pass of the multi-fold kernel (prover.rs:201-211, steps times), one tree (prover.rs:214) over
 // its output, one root (prover.rs:224).  Every layer is folded on the device (no host FRI tail); tree tops go to the host as usual.
@@ -570,10 +637,7 @@ int prove_fold_rounds(zk_ctx* c, Channel& ch) {
         if (!stopped && ((rc = do_merkle(c, id, true, false, leaf_steps)) || (rc = read_commit(c, id, root)))) return rc;
         const size_t deg = c->n >> (r0 + steps);
         if (c->checks && (rc = check_degree(c, id, (uint32_t)deg - (deg ? 1 : 0), "prover.rs:228-251 (FRI layer degree)"))) return rc;
-        if (!stopped) {
-            ch.commit_hash(root);
-            memcpy(c->info.roots[id], root, 32);
-        }
+        if (!stopped) commit_tree(c, ch, id, root);
         for (uint32_t l = 2 + r0; l < id; ++l) { c->skipped_layers |= (uint64_t)1 << l; c->skipped_trees |= (uint64_t)1 << l; }
     }
     if (c->stop) {
@@ -657,10 +721,10 @@ int prove_finish(zk_ctx* c, Channel& ch, HostLaps& lap) {
         vsrc += s; dsrc += (one_leaf ? 1 : s) * plen;
     };
     for (uint32_t q = 0; q < Q; ++q) {
-        for (int k = 0; k < (coset ? 3 : 4); ++k) tuple(1, Lp, false);                        // (u32, AuthPath): prover.rs:274-277
+        for (int k = 0; k < (coset ? 3 : 4); ++k) tuple(1, Lp - c->tree_cap[k < 3 ? 0 : 1], false);   // (u32, AuthPath): prover.rs:274-277
         for (uint32_t j = 0; j < G; ++j) {                                                    // prover.rs:280-289, per group
             const size_t steps = fold_steps(R, K, j);
-            tuple((size_t)1 << steps, Lp - (size_t)j * K - (coset ? steps : 0), coset);
+            tuple((size_t)1 << steps, Lp - (size_t)j * K - (coset ? steps : 0) - c->tree_cap[1 + j * K], coset);   // paths end below the cap
         }
     }
     lap("decommit host hashing");
@@ -677,7 +741,8 @@ int prove_resident(zk_ctx* c, Channel& ch) {
     static const bool timing = getenv("ZK_HOST_TIMING") != nullptr;
     HostLaps lap{timing};
     const uint32_t R = c->R;
-    ch.data.reserve(ch.data.size() + proof_data_len(c->log_n, c->log_b, c->queries, c->grind, c->fold, c->coset, c->stop));
+    ch.data.reserve(ch.data.size() + proof_data_len_cap(c->log_n, c->log_b, c->queries, c->grind, c->fold, c->coset, c->stop, c->cap));
+    CapScope cap_scope{c};                                // the trees of this proof stop at the cap; every other builder makes whole trees
     c->skipped_layers = c->skipped_trees = 0;
     uint8_t root[32];
     int rc;
@@ -690,8 +755,7 @@ int prove_resident(zk_ctx* c, Channel& ch) {
     if (c->checks && ((rc = checks_alloc(c)) || (rc = check_interpolant(c)))) return rc;   // prover.rs:64-66
     if ((rc = do_merkle(c, 0, true))) return rc;          // prover.rs:81
     if ((rc = read_commit(c, 0, root))) return rc;
-    ch.commit_hash(root);                                 // prover.rs:85
-    memcpy(c->info.roots[0], root, 32);
+    commit_tree(c, ch, 0, root);                          // prover.rs:85
     uint32_t alpha[3];
     for (int i = 0; i < 3; ++i) alpha[i] = c->info.alpha_raw[i] = ch.get_u32();   // prover.rs:163-165
     if (c->coset) {                                       // prover.rs:166-176, then the tree with group 0's cosets as leaves
@@ -700,8 +764,7 @@ int prove_resident(zk_ctx* c, Channel& ch) {
     if (can_gate(c, 0) && (rc = enqueue_gated_fold(c, 0))) return rc;   // early launch: round 0 queued before cp's digests are waited for
     if ((rc = read_commit(c, 1, root))) return rc;
     if (c->checks && (rc = check_degree(c, 1, (uint32_t)c->n - 1, "prover.rs:148-159/:169 (exact divisions, deg cp = n - 1)"))) return rc;
-    ch.commit_hash(root);                                 // prover.rs:180
-    memcpy(c->info.roots[1], root, 32);
+    commit_tree(c, ch, 1, root);                          // prover.rs:180
     if (c->fold > 1 || c->coset || c->stop) {
         if ((rc = prove_fold_rounds(c, ch))) return rc;
     } else for (uint32_t r = 0; r < R; ++r) {             // prover.rs:198-225
@@ -719,8 +782,7 @@ int prove_resident(zk_ctx* c, Channel& ch) {
             if ((rc = read_commit(c, 2 + r, root))) return rc;
         }
         if (c->checks && (rc = check_degree(c, 2 + r, (uint32_t)(c->n >> (r + 1)) - ((c->n >> (r + 1)) ? 1 : 0), "prover.rs:228-251 (FRI layer degree)"))) return rc;
-        ch.commit_hash(root);                             // prover.rs:224
-        memcpy(c->info.roots[2 + r], root, 32);
+        commit_tree(c, ch, 2 + r, root);                  // prover.rs:224
     }
     lap("lde .. last root");
     if (timing) fprintf(stderr, "[zk timing]   of which: waiting for the device %.1f us, host hashing (tops + tail) %.1f us\n", c->t_wait, c->t_host_hash);
@@ -1075,6 +1137,29 @@ int zk_ctx_final_poly(const zk_ctx* c, uint32_t* out, size_t cap, size_t* count)
     memcpy(out, c->final_poly.data(), c->final_poly.size() * 4);
     return ZK_OK;
 }
+// Merkle caps (include/zkstark_amd.h): from the next one-call proof on.  A capped proof opens fewer nodes and stages fewer host-built
+// ones than a plain proof, so every buffer suffices.
+int zk_ctx_set_merkle_cap(zk_ctx* c, uint32_t cap_log) {
+    if (!c) return fail(ZK_ERR_INVALID, "null context");
+    if (c->tail) return fail(ZK_ERR_STATE, "zk_ctx_set_merkle_cap: FRI-tail context");
+    if (cap_log > kMaxCapLog) return fail(ZK_ERR_INVALID, "zk_ctx_set_merkle_cap: need cap_log <= %u (got %u)", kMaxCapLog, cap_log);
+    c->cap = cap_log;
+    return ZK_OK;
+}
+uint32_t zk_ctx_get_merkle_cap(const zk_ctx* c) { return c ? c->cap : 0; }
+// What the last one-call proof committed for `tree`: 2^ce digests of 32 bytes (ce = 0: the root).
+uint32_t zk_ctx_merkle_cap_log(const zk_ctx* c, uint32_t tree) { return c && tree <= c->R + 1 ? c->tree_cap[tree] : 0; }
+int zk_ctx_merkle_cap(const zk_ctx* c, uint32_t tree, uint8_t* out, size_t out_len) {
+    if (!c || !out) return fail(ZK_ERR_INVALID, "zk_ctx_merkle_cap: null argument");
+    if (tree > c->R + 1) return fail(ZK_ERR_INVALID, "zk_ctx_merkle_cap: tree %u out of range", tree);
+    if (c->final_poly.empty()) return fail(ZK_ERR_STATE, "zk_ctx_merkle_cap: no proof made yet");
+    if ((c->skipped_trees >> tree) & 1) return fail(ZK_ERR_STATE, "zk_ctx_merkle_cap: tree %u was not built by the last proof (fold_log %u, fri_stop %u)", tree, c->fold, c->stop);
+    const uint32_t ce = c->tree_cap[tree];
+    const uint8_t* src = ce ? c->cap_digests[tree].data() : c->info.roots[tree];
+    if (((size_t)32 << ce) > out_len) return fail(ZK_ERR_BUFFER, "zk_ctx_merkle_cap: %zu bytes, room for %zu", (size_t)32 << ce, out_len);
+    memcpy(out, src, (size_t)32 << ce);
+    return ZK_OK;
+}
 int zk_ctx_set_queries(zk_ctx* c, uint32_t n_queries) {
     if (!c) return fail(ZK_ERR_INVALID, "null context");
     if (n_queries < 1 || n_queries > kMaxQueries) return fail(ZK_ERR_INVALID, "zk_ctx_set_queries: need 1 <= n_queries <= %u", kMaxQueries);
@@ -1292,6 +1377,7 @@ int zk_merkle_node(zk_ctx* c, uint32_t tree, size_t index, uint8_t out[32]) {
     if (!c || !out) return fail(ZK_ERR_INVALID, "zk_merkle_node: null argument");
     if (tree > c->R + 1 || index >= 2 * tree_leaves(c, tree) - 1) return fail(ZK_ERR_INVALID, "zk_merkle_node: out of range");
     if ((c->skipped_trees >> tree) & 1) return fail(ZK_ERR_STATE, "zk_merkle_node: tree %u was not built by the last proof (fold_log %u, fri_stop %u)", tree, c->fold, c->stop);
+    if (index + 1 < ((size_t)1 << c->tree_cap[tree])) return fail(ZK_ERR_STATE, "zk_merkle_node: node %zu of tree %u lies above its Merkle cap (depth %u): the last proof did not build it", index, tree, c->tree_cap[tree]);
     HIPCHK(hipSetDevice(c->device));
     if (int prc = settle_pending(c)) return prc;
     HIPCHK(hipMemcpyAsync(c->h_small, c->d_trees + c->tree_off[tree] + index * 8, 32, hipMemcpyDeviceToHost, c->stream));
@@ -1305,6 +1391,7 @@ int zk_merkle_nodes(zk_ctx* c, uint32_t tree, size_t first, size_t count, uint8_
     if (tree > c->R + 1 || first > 2 * tree_leaves(c, tree) - 1 || count > 2 * tree_leaves(c, tree) - 1 - first)
         return fail(ZK_ERR_INVALID, "zk_merkle_nodes: out of range");
     if ((c->skipped_trees >> tree) & 1) return fail(ZK_ERR_STATE, "zk_merkle_nodes: tree %u was not built by the last proof (fold_log %u, fri_stop %u)", tree, c->fold, c->stop);
+    if (count && first + 1 < ((size_t)1 << c->tree_cap[tree])) return fail(ZK_ERR_STATE, "zk_merkle_nodes: node %zu of tree %u lies above its Merkle cap (depth %u): the last proof did not build it", first, tree, c->tree_cap[tree]);
     HIPCHK(hipSetDevice(c->device));
     if (int prc = settle_pending(c)) return prc;
     return merkle_nodes_to_host(c->device, c->stream, c->d_trees + c->tree_off[tree], first, count, out);
@@ -1314,6 +1401,7 @@ int zk_merkle_path(zk_ctx* c, uint32_t tree, size_t leaf, uint8_t* out, size_t* 
     if (!c || !out) return fail(ZK_ERR_INVALID, "zk_merkle_path: null argument");
     if (tree > c->R + 1 || leaf >= tree_leaves(c, tree)) return fail(ZK_ERR_INVALID, "zk_merkle_path: out of range");
     if ((c->skipped_trees >> tree) & 1) return fail(ZK_ERR_STATE, "zk_merkle_path: tree %u was not built by the last proof (fold_log %u, fri_stop %u)", tree, c->fold, c->stop);
+    if (c->tree_cap[tree]) return fail(ZK_ERR_STATE, "zk_merkle_path: tree %u was built down to its Merkle cap only (depth %u): a whole path does not exist", tree, c->tree_cap[tree]);
     HIPCHK(hipSetDevice(c->device));
     if (int prc = settle_pending(c)) return prc;
     std::vector<size_t> nodes;
@@ -1394,12 +1482,13 @@ int zk_last_transcript(const zk_ctx* c, zk_transcript_info* out) {
 // apart (replay_note not null), "transcript replay failed at check N" + replay_note.
 static int verify_entry(const char* who, const uint8_t* proof, size_t len, const uint8_t* state, uint32_t log_n, uint32_t log_b,
                         uint32_t public_last, int hash_kind, uint32_t q, uint32_t grind, uint32_t fold, int32_t* check_out,
-                        const char* replay_note, const char* reject_note, bool coset = false, uint32_t stop = 0) {
+                        const char* replay_note, const char* reject_note, bool coset = false, uint32_t stop = 0, uint32_t cap = 0) {
     if (hash_kind != ZK_HASH_SHA256 && hash_kind != ZK_HASH_FIELD && hash_kind != ZK_HASH_BLAKE2S) return fail(ZK_ERR_INVALID, "%s: unknown hash %d", who, hash_kind);
     if (fold < 1 || fold > kMaxFoldLog) return fail(ZK_ERR_INVALID, "%s: need 1 <= fold_log <= %u (got %u)", who, kMaxFoldLog, fold);
-    int rc = state ? verify_transcript(proof, len, state, log_n, log_b, q, grind, fold, coset, stop) : 0;
+    if (cap > kMaxCapLog) return fail(ZK_ERR_INVALID, "%s: need cap_log <= %u (got %u)", who, kMaxCapLog, cap);
+    int rc = state ? verify_transcript(proof, len, state, log_n, log_b, q, grind, fold, coset, stop, cap) : 0;
     const bool in_replay = rc != 0;
-    if (!rc) rc = verify_proof(proof, len, log_n, log_b, public_last, hash_kind, q, grind, fold, coset, stop);
+    if (!rc) rc = verify_proof(proof, len, log_n, log_b, public_last, hash_kind, q, grind, fold, coset, stop, cap);
     if (check_out) *check_out = rc;
     if (!rc) return ZK_OK;
     if (in_replay && replay_note) return fail(ZK_ERR_VERIFY, "transcript replay failed at check %d%s", rc, replay_note);
@@ -1455,6 +1544,14 @@ int zk_verify_stop(const uint8_t* proof, size_t len, const uint8_t* state, uint3
     return verify_entry("zk_verify_stop", proof, len, state, log_n, log_b, public_last, hash_kind, n_queries, grind_bits, fold_log, check_out, nullptr, "",
                         coset_leaves != 0, stop_log);
 }
+// zk_verify_stop for proofs with Merkle caps (transcript.hpp "Merkle caps"); cap_log = 0 is zk_verify_stop
+int zk_verify_cap(const uint8_t* proof, size_t len, const uint8_t* state, uint32_t log_n, uint32_t log_b, uint32_t public_last,
+                  int hash_kind, uint32_t n_queries, uint32_t grind_bits, uint32_t fold_log, int coset_leaves, uint32_t stop_log, uint32_t cap_log,
+                  int32_t* check_out) {
+    if (!proof || !check_out) return fail(ZK_ERR_INVALID, "zk_verify_cap: null argument");
+    return verify_entry("zk_verify_cap", proof, len, state, log_n, log_b, public_last, hash_kind, n_queries, grind_bits, fold_log, check_out, nullptr, "",
+                        coset_leaves != 0, stop_log, cap_log);
+}
 
 size_t zk_proof_size(size_t data_len) { return 48 + data_len; }   // proof.rs:151-154: size_of::<Proof>() = 32 + 16
 size_t zk_proof_data_len_fold(uint32_t log_n, uint32_t log_b, uint32_t n_queries, uint32_t grind_bits, uint32_t fold_log) {
@@ -1468,6 +1565,11 @@ size_t zk_proof_data_len_coset(uint32_t log_n, uint32_t log_b, uint32_t n_querie
 size_t zk_proof_data_len_stop(uint32_t log_n, uint32_t log_b, uint32_t n_queries, uint32_t grind_bits, uint32_t fold_log, int coset_leaves, uint32_t stop_log) {
     if (fold_log < 1 || fold_log > kMaxFoldLog || !stop_ok(log_n, log_b, stop_log)) return 0;
     return proof_data_len(log_n, log_b, n_queries, grind_bits, fold_log, coset_leaves != 0, stop_log);
+}
+size_t zk_proof_data_len_cap(uint32_t log_n, uint32_t log_b, uint32_t n_queries, uint32_t grind_bits, uint32_t fold_log, int coset_leaves, uint32_t stop_log,
+                             uint32_t cap_log) {
+    if (fold_log < 1 || fold_log > kMaxFoldLog || !stop_ok(log_n, log_b, stop_log) || cap_log > kMaxCapLog) return 0;
+    return proof_data_len_cap(log_n, log_b, n_queries, grind_bits, fold_log, coset_leaves != 0, stop_log, cap_log);
 }
 size_t zk_proof_data_len_grind(uint32_t log_n, uint32_t log_b, uint32_t n_queries, uint32_t grind_bits) {
     return zk_proof_data_len_fold(log_n, log_b, n_queries, grind_bits, 1);

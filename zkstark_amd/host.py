@@ -153,8 +153,9 @@ class Proof:
     """proof.rs:5-154.  verify() raises ZkError where the reference panics."""
 
     def __init__(self, state, data, log_n=10, log_blowup=3, public_last=2338775057, hash="sha256", queries=1, grind_bits=0,
-                 fold_log=1, coset_leaves=False, stop_log=0):   # proof.rs:11
+                 fold_log=1, coset_leaves=False, stop_log=0, cap_log=0):   # proof.rs:11
         self.state, self.data = bytes(state), bytes(data)
+        self.cap_log = cap_log                       # made with zk_ctx_set_merkle_cap: zk_verify_cap, zk_proof_data_len_cap
         self.stop_log = stop_log                     # made with zk_ctx_set_fri_stop: zk_verify_stop, zk_proof_data_len_stop
         self.log_n, self.log_blowup, self.public_last = log_n, log_blowup, public_last
         self.hash, self.queries, self.grind_bits, self.fold_log = hash, queries, grind_bits, fold_log
@@ -162,7 +163,10 @@ class Proof:
 
     def expected_len(self):
         """The length the format gives a proof of this shape (zk_proof_data_len_fold / zk_proof_data_len_coset; stopped early:
-        zk_proof_data_len_stop)."""
+        zk_proof_data_len_stop; with Merkle caps: zk_proof_data_len_cap)."""
+        if self.cap_log:
+            return _lib.load().zk_proof_data_len_cap(self.log_n, self.log_blowup, self.queries, self.grind_bits, self.fold_log,
+                                                     int(self.coset_leaves), self.stop_log, self.cap_log)
         if self.stop_log:
             return _lib.load().zk_proof_data_len_stop(self.log_n, self.log_blowup, self.queries, self.grind_bits, self.fold_log,
                                                       int(self.coset_leaves), self.stop_log)
@@ -174,9 +178,13 @@ class Proof:
     def _general(self):
         """Folded, coset-leaf, stopped and BLAKE2s proofs go through the general entry points (zk_verify_check and zk_verify_fold keep
         the two hashes they were defined with: a BLAKE2s proof of any setting is verified by zk_verify_stop)."""
-        return self.fold_log != 1 or self.coset_leaves or self.stop_log or self.hash == "blake2s"
+        return self.fold_log != 1 or self.coset_leaves or self.stop_log or self.cap_log or self.hash == "blake2s"
 
     def _verify_general(self, strict, out):
+        if self.cap_log:                             # Merkle caps: the one entry point that takes cap_log
+            return _lib.load().zk_verify_cap(self.data, len(self.data), self.state if strict else None, self.log_n, self.log_blowup,
+                                             self.public_last, HASHES[self.hash], self.queries, self.grind_bits, self.fold_log,
+                                             int(self.coset_leaves), self.stop_log, self.cap_log, C.byref(out))
         if self.stop_log or self.hash == "blake2s":
             return _lib.load().zk_verify_stop(self.data, len(self.data), self.state if strict else None, self.log_n, self.log_blowup,
                                               self.public_last, HASHES[self.hash], self.queries, self.grind_bits, self.fold_log,
@@ -295,14 +303,16 @@ class Context:
     """Device-resident prover state for one (log_n, log_blowup): zk_ctx."""
 
     def __init__(self, log_n=10, log_blowup=3, device=0, hash="sha256", queries=1, host_levels=None, grind_bits=0, fold_log=1,
-                 coset_leaves=False, stop_log=0):
-        """host_levels: (top_log, tail_log) of zk_ctx_set_host_levels; None = the library default.  grind_bits: proof-of-work
+                 coset_leaves=False, stop_log=0, cap_log=0):
+        """cap_log: commit every tree by its 2^cap_log digests of depth cap_log and open paths that much shorter (zk_ctx_set_merkle_cap;
+        0 = roots).  host_levels: (top_log, tail_log) of zk_ctx_set_host_levels; None = the library default.  grind_bits: proof-of-work
         bits before the query draw (zk_ctx_set_grinding; 0 = none).  fold_log: FRI folding factor 2^fold_log between commitments
         (zk_ctx_set_fold; 1 = the reference).  coset_leaves: one coset per Merkle leaf of the FRI trees (zk_ctx_set_coset_leaves).
         stop_log: stop FRI at a polynomial of degree < 2^stop_log and send its coefficients (zk_ctx_set_fri_stop; 0 = fold to a constant)."""
         self.fold_log = fold_log
         self.coset_leaves = False
         self.stop_log = 0
+        self.cap_log = 0
         self.log_n, self.log_blowup, self.device, self.hash, self.queries = log_n, log_blowup, device, hash, queries
         self.grind_bits = grind_bits
         self.n, self.B = 1 << log_n, 1 << log_blowup
@@ -323,6 +333,20 @@ class Context:
             self.set_coset_leaves(True)
         if stop_log:
             self.set_fri_stop(stop_log)
+        if cap_log:
+            self.set_merkle_cap(cap_log)
+
+    def set_merkle_cap(self, cap_log):
+        """zk_ctx_set_merkle_cap: from the next one-call proof on, a tree of 2^lg leaves is committed by the 2^ce digests of depth
+        ce = min(cap_log, lg - 1) and its paths carry lg - ce digests (0: roots, the reference)."""
+        check(_lib.load().zk_ctx_set_merkle_cap(self._h, cap_log))
+        self.cap_log = cap_log
+
+    def merkle_cap(self, tree):
+        """zk_ctx_merkle_cap: the digests the last one-call proof committed for `tree`, a [2^ce, 32] uint8 array (ce = 0: the root)."""
+        out = np.zeros((1 << _lib.load().zk_ctx_merkle_cap_log(self._h, tree), 32), dtype=np.uint8)
+        check(_lib.load().zk_ctx_merkle_cap(self._h, tree, out.ctypes.data_as(C.c_void_p), out.size))
+        return out
 
     def set_coset_leaves(self, on=True):
         """zk_ctx_set_coset_leaves: from the next proof on, a group opens one leaf of 2^steps values and one path."""
@@ -348,6 +372,9 @@ class Context:
         return out, high.value
 
     def _proof_cap(self):
+        if self.cap_log:
+            return _lib.load().zk_proof_data_len_cap(self.log_n, self.log_blowup, self.queries, self.grind_bits, self.fold_log,
+                                                     int(self.coset_leaves), self.stop_log, self.cap_log)
         if self.stop_log:
             return _lib.load().zk_proof_data_len_stop(self.log_n, self.log_blowup, self.queries, self.grind_bits, self.fold_log,
                                                       int(self.coset_leaves), self.stop_log)
@@ -465,7 +492,7 @@ class Context:
             check(_lib.load().zk_prove(self._h, _ptr(t), len(t), buf, cap, C.byref(n), st))
         info = self.last_transcript()
         return Proof(st.raw, buf.raw[:n.value], self.log_n, self.log_blowup, info.public_last, self.hash, self.queries, self.grind_bits,
-                     self.fold_log, self.coset_leaves, self.stop_log)
+                     self.fold_log, self.coset_leaves, self.stop_log, self.cap_log)
 
     def prove_channel(self, channel):
         """generate_proof(channel) (prover.rs:9) in one C call on the caller's Channel (zk_prove_channel): the
@@ -473,7 +500,7 @@ class Context:
         check(_lib.load().zk_prove_channel(self._h, channel._h))
         proof = channel.finalize(self.log_n, self.log_blowup, self.last_transcript().public_last)
         proof.grind_bits, proof.fold_log, proof.coset_leaves = self.grind_bits, self.fold_log, self.coset_leaves
-        proof.stop_log = self.stop_log
+        proof.stop_log, proof.cap_log = self.stop_log, self.cap_log
         return proof
 
     def set_host_levels(self, top_log, tail_log):
@@ -523,7 +550,7 @@ def prove_many(ctxs):
     out = []
     for i, c in enumerate(ctxs):
         out.append(Proof(states[i].tobytes(), data[i, :lens[i]].tobytes(), c.log_n, c.log_blowup, c.last_transcript().public_last,
-                         c.hash, c.queries, c.grind_bits, c.fold_log, c.coset_leaves, c.stop_log))
+                         c.hash, c.queries, c.grind_bits, c.fold_log, c.coset_leaves, c.stop_log, c.cap_log))
     return out
 
 
@@ -642,8 +669,10 @@ class Verifier:
     """Many proofs of one size checked at once on the GPU (zk_verifier_*).  Every result is the number Proof.check gives for
     that proof: 0 = accepted, otherwise the CPU verifier's check number."""
 
-    def __init__(self, log_n, log_blowup, device=0, hash="sha256", queries=1, grind_bits=0, fold_log=1, coset_leaves=False, stop_log=0):
-        """fold_log: the FRI folding factor 2^fold_log of the proofs to check (zk_verifier_set_fold; 1 = the reference).
+    def __init__(self, log_n, log_blowup, device=0, hash="sha256", queries=1, grind_bits=0, fold_log=1, coset_leaves=False, stop_log=0,
+                 cap_log=0):
+        """cap_log: the proofs commit every tree by 2^cap_log digests (zk_verifier_set_merkle_cap; Context(cap_log=)).
+        fold_log: the FRI folding factor 2^fold_log of the proofs to check (zk_verifier_set_fold; 1 = the reference).
         coset_leaves: the proofs were made with coset leaves (zk_verifier_set_coset_leaves; Context(coset_leaves=True)).
         stop_log: the proofs stop FRI early at a polynomial of 2^stop_log coefficients (zk_verifier_set_fri_stop; Context(stop_log=))."""
         _no_blake2s("Verifier", hash)
@@ -651,6 +680,7 @@ class Verifier:
         self.fold_log = 1
         self.coset_leaves = False
         self.stop_log = 0
+        self.cap_log = 0
         self._h = C.c_void_p()
         check(_lib.load().zk_verifier_create(device, log_n, log_blowup, C.byref(self._h)))
         if hash != "sha256":
@@ -665,6 +695,13 @@ class Verifier:
             self.set_coset_leaves(True)
         if stop_log:
             self.set_fri_stop(stop_log)
+        if cap_log:
+            self.set_merkle_cap(cap_log)
+
+    def set_merkle_cap(self, cap_log):
+        """zk_verifier_set_merkle_cap: from the next run on, check proofs whose trees are committed by 2^cap_log digests (0: by roots)."""
+        check(_lib.load().zk_verifier_set_merkle_cap(self._h, cap_log))
+        self.cap_log = cap_log
 
     def set_fri_stop(self, stop_log):
         """zk_verifier_set_fri_stop: from the next run on, check proofs that send the final polynomial's 2^stop_log coefficients
@@ -694,6 +731,9 @@ class Verifier:
 
     @property
     def proof_len(self):
+        if self.cap_log:
+            return _lib.load().zk_proof_data_len_cap(self.log_n, self.log_blowup, self.queries, self.grind_bits, self.fold_log,
+                                                     int(self.coset_leaves), self.stop_log, self.cap_log)
         if self.stop_log:
             return _lib.load().zk_proof_data_len_stop(self.log_n, self.log_blowup, self.queries, self.grind_bits, self.fold_log,
                                                       int(self.coset_leaves), self.stop_log)
@@ -736,6 +776,8 @@ class Verifier:
                                   f"this verifier is set to {names[self.coset_leaves]}")
             if getattr(p, "stop_log", 0) != self.stop_log:
                 raise ZkError(-1, f"verify: proof {i} was made with stop_log {getattr(p, 'stop_log', 0)}, this verifier is set to stop_log {self.stop_log}")
+            if getattr(p, "cap_log", 0) != self.cap_log:
+                raise ZkError(-1, f"verify: proof {i} was made with cap_log {getattr(p, 'cap_log', 0)}, this verifier is set to cap_log {self.cap_log}")
             if len(p.data) != plen:
                 raise ZkError(-1, f"verify: proof {i} has {len(p.data)} bytes, this verifier takes {plen}")
             data[i] = np.frombuffer(p.data, dtype=np.uint8)
