@@ -261,7 +261,8 @@ int zk_ctx_final_poly(const zk_ctx *ctx, uint32_t *out, size_t cap, size_t *coun
  * index above the cap and zk_merkle_path of that tree return ZK_ERR_STATE.  The stage-by-stage API (zk_merkle_commit*, zk_dev_*)
  * ignores the setting and builds whole trees.
  * zk_verifier_* checks such proofs in batches with zk_verifier_set_merkle_cap.
- * NOT covered: zk_batch_*, zk_shard_* and zk_tail_* have no cap setting yet.
+ * zk_batch_* makes the same proofs in batches with zk_batch_set_merkle_cap.
+ * NOT covered: zk_shard_* and zk_tail_* have no cap setting yet.
  * zk_ctx_get_merkle_cap: the current c, 0 for a null context.  zk_ctx_merkle_cap_log: the ce tree `tree` was last built down to.
  * zk_ctx_merkle_cap: what the last one-call proof committed for `tree`, 32 * 2^ce bytes (ce = 0: the root); ZK_ERR_BUFFER if out_len is
  * smaller, ZK_ERR_STATE before the first proof or for a tree the proof did not build. */
@@ -443,6 +444,25 @@ int zk_batch_get_coset_leaves(const zk_batch *b);
  * zk_batch_get_fri_stop: the current D, 0 for a null batch. */
 int zk_batch_set_fri_stop(zk_batch *b, uint32_t stop_log);
 uint32_t zk_batch_get_fri_stop(const zk_batch *b);
+/* Merkle caps in the batched prover (zk_ctx_set_merkle_cap has the format): cap_log = c, default 0, 0 <= c <= 8 (anything else:
+ * ZK_ERR_INVALID, the setting unchanged), from the next zk_batch_prove on; refused with ZK_ERR_STATE while a zk_batch_prove or another
+ * setter runs.  It combines with every fold_log, leaf format, stop_log, query count, grinding, host-levels setting and both hashes of
+ * this class, and every proof of the batch is byte for byte the one zk_ctx_set_merkle_cap(c) + zk_prove makes of the same trace:
+ * zk_proof_data_len_cap bytes (the stride of zk_batch_prove), checked with zk_verify_cap or zk_verifier_set_merkle_cap.  With c = 0
+ * every byte, launch and allocation is what it was.  log_batch = 0 forwards to zk_ctx_set_merkle_cap.
+ * In the batch heap of a tree (zk_batch_merkle_nodes) the cap of proof p is the 2^ce nodes from 2^(log_batch + ce) - 1 + p 2^ce on,
+ * ce = min(c, lg - 1) for 2^lg leaves per proof.  Nothing above depth log_batch + ce is built by the device or the host: after a
+ * zk_batch_prove with ce > 0 for a tree, zk_batch_merkle_nodes of an index below 2^(log_batch + ce) - 1 returns ZK_ERR_STATE.  A cap of
+ * more than 2^10 digests per batch is posted to a pinned buffer of 64 + 32 * 2^(log_batch + ce of the f tree) bytes which the setter
+ * allocates (counted in zk_batch_device_bytes) and c = 0 or zk_batch_destroy frees; on ZK_ERR_NOMEM the batch keeps its setting.
+ * zk_batch_get_merkle_cap: the current c, 0 for a null batch.  zk_batch_merkle_cap_log: the ce of tree `tree` in the last zk_batch_prove.
+ * zk_batch_merkle_cap: what proof `proof` of the last zk_batch_prove committed for `tree`, 32 * 2^ce bytes (an uncapped tree: its root);
+ * ZK_ERR_INVALID for a tree or proof out of range, ZK_ERR_BUFFER if out_len is smaller, ZK_ERR_STATE before the first proof or for a
+ * tree the proof did not build. */
+int zk_batch_set_merkle_cap(zk_batch *b, uint32_t cap_log);
+uint32_t zk_batch_get_merkle_cap(const zk_batch *b);
+uint32_t zk_batch_merkle_cap_log(const zk_batch *b, uint32_t tree);
+int zk_batch_merkle_cap(zk_batch *b, uint32_t tree, size_t proof, uint8_t *out, size_t out_len);
 /* on = 0: every tree level of the batch on the device (default: the host threads hash the top levels of each proof's
  * trees when the CPU has SHA extensions, as zk_ctx_set_host_levels).  Results are identical. */
 int zk_batch_set_host_levels(zk_batch *b, int on);

@@ -199,6 +199,10 @@ SYMBOLS = {
     "zk_batch_get_coset_leaves": (_int, [_vp]),
     "zk_batch_set_fri_stop": (_int, [_vp, _u32]),
     "zk_batch_get_fri_stop": (_u32, [_vp]),
+    "zk_batch_set_merkle_cap": (_int, [_vp, _u32]),
+    "zk_batch_get_merkle_cap": (_u32, [_vp]),
+    "zk_batch_merkle_cap_log": (_u32, [_vp, _u32]),
+    "zk_batch_merkle_cap": (_int, [_vp, _u32, _sz, _vp, _sz]),
     "zk_verifier_set_coset_leaves": (_int, [_vp, _int]),
     "zk_verifier_get_coset_leaves": (_int, [_vp]),
     "zk_verifier_set_fri_stop": (_int, [_vp, _u32]),

@@ -68,6 +68,15 @@ struct zk_batch {
     uint32_t *d_final = nullptr, *h_final = nullptr;   // [batch][1 + 2^stop]: count of high coefficients, final polynomial (stop > 0; h_: pinned)
     bool coset = false;               // coset leaves (zk_batch_set_coset_leaves): from the next zk_batch_prove on
     uint8_t tree_steps[34] = {0};     // tree id of the last zk_batch_prove: its leaves hold 2^tree_steps values (0: one-value leaves)
+    // Merkle caps (zk_batch_set_merkle_cap; transcript.hpp): every proof commits the 2^ce digests of depth ce = min(cap, lg - 1) of each of
+    // its trees, i.e. the batch heap is built down to depth lb + ce and nothing above is hashed.  tree_cap[t]: the ce of tree t in the
+    // last zk_batch_prove.  h_cap / d_cap: pinned, mapped, 16 + 8 * 2^(lb + ce of the f tree) words in the mailbox's layout, for the
+    // hand-overs the mailbox cannot hold (lb + ce > kMaxHostLog); allocated by the setter only when the f tree needs it.
+    uint32_t cap = 0;
+    uint8_t tree_cap[34] = {0};
+    bool proved = false;              // a zk_batch_prove has run: tree_cap, tree_steps and skipped_trees describe it
+    uint32_t *h_cap = nullptr, *d_cap = nullptr;
+    size_t cap_words = 0;
     Grinder* grinder = nullptr;       // one launch grinds for every proof of the batch (created by the setter above kGrindHostMaxBits)
     int hash = 0;                    // Merkle hash: 0 = SHA-256 (reference), 1 = field-native
     std::vector<uint32_t> first, last;
@@ -104,11 +113,39 @@ uint32_t bextra(const zk_batch* b, uint32_t log_m) {
     if (h > log_m - 1) h = log_m - 1;
     return h >= 3 ? h : 0;                               // two levels are not worth a hand-over
 }
-MailArgs bmail(zk_batch* b, uint32_t log_m) {
+// How the build of a tree whose proofs commit it at depth ce (0: their roots) reaches the host.  Through the mailbox at depth
+// lb + max(ce, host share) of the batch heap when that fits (ce = 0: what it always was); the host then hashes from its share down
+// to ce (h levels, 0 when the cap is at or below the share).  Otherwise the host's share is dropped: the build ends at depth lb + ce
+// without a mailbox and launch_digest_level_post copies that level into h_cap.  top: the depth the build ends at.
+struct Hand { uint32_t top, h; bool mailbox; };
+Hand bhand(const zk_batch* b, uint32_t ce, uint32_t log_m) {
+    const uint32_t h = bextra(b, log_m), deep = h > ce ? h : ce;
+    if (b->lb + deep <= kMaxHostLog) return Hand{b->lb + deep, h > ce ? h : 0, true};
+    return Hand{b->lb + ce, 0, false};
+}
+// cap > 0: the 16 + 8 * 2^(lb + ce) words of h_cap when the f tree (the deepest cap of a proof) does not fit the mailbox, else 0
+size_t bcap_words(const zk_batch* b, uint32_t cap) {
+    const uint32_t e = b->lb + cap_eff(cap, b->L);
+    return cap && e > kMaxHostLog ? kMailDigests + ((size_t)8 << e) : 0;
+}
+// Hand-over of the commit launch of `tree` (2^log_m leaves per proof): records the depth its proofs commit it at.
+MailArgs bmail(zk_batch* b, uint32_t tree, uint32_t log_m) {
     MailArgs m;
     if (b->counters_dirty) { (void)hipMemsetAsync(b->d_counter, 0, 64, b->stream); b->counters_dirty = false; }
-    m.mailbox = b->d_mail; m.seq = ++b->mail_seq; m.counter = b->d_counter; m.top = b->lb + bextra(b, log_m);
+    const uint32_t ce = b->cap ? cap_eff(b->cap, log_m) : 0;
+    const Hand hd = bhand(b, ce, log_m);
+    b->tree_cap[tree] = (uint8_t)ce;
+    m.seq = ++b->mail_seq; m.top = hd.top;
+    if (hd.mailbox) { m.mailbox = b->d_mail; m.counter = b->d_counter; }   // else: no mailbox, no continuation; bpost follows the build
     return m;
+}
+// Behind the build of `tree`: a cap deeper than the mailbox holds is posted by a launch of its own (the flag is the mailbox's).
+int bpost(zk_batch* b, uint32_t tree, uint32_t log_m) {
+    const Hand hd = bhand(b, b->tree_cap[tree], log_m);
+    if (hd.mailbox) return ZK_OK;
+    if (!b->h_cap || kMailDigests + ((size_t)8 << hd.top) > b->cap_words) return fail(ZK_ERR_STATE, "zk_batch_prove: no buffer for a cap of 2^%u digests", hd.top);
+    HIPCHK(launch_digest_level_post(b->d_trees + b->tree_off[tree], hd.top, b->d_cap + kMailDigests, b->d_mail, b->mail_seq, b->d_counter, b->stream, nullptr));
+    return ZK_OK;
 }
 // Proof-of-work nonce of every proof after its free term (DESIGN.md "Grinding"), committed to its channel: one thread per proof for
 // small g, else one launch per chunk for all proofs still searching.
@@ -132,41 +169,44 @@ int bwait_roots(zk_batch* b) {
     if (rc) b->counters_dirty = true;                     // see zk_ctx::counters_dirty (zkstark.hip)
     return rc;
 }
-// After bwait_roots: hashes the `extra` host levels of every proof's tree `tree` and returns where the roots
-// are ([batch][8] state words): the mailbox itself when the device went all the way.
+// After bwait_roots: hashes the host's levels of every proof's tree `tree`, from its share h down to the depth ce the proofs commit
+// (0: their roots), and returns where those digests are ([batch][2^ce][8] state words): the posted ones themselves when the device
+// went all the way.
 const uint32_t* bfinish_roots(zk_batch* b, uint32_t tree, uint32_t log_m) {
-    const uint32_t h = bextra(b, log_m);
-    const uint32_t* posted = b->h_mail + kMailDigests;
+    const uint32_t ce = b->tree_cap[tree];
+    const Hand hd = bhand(b, ce, log_m);
+    const uint32_t h = hd.h;
+    const uint32_t* posted = (hd.mailbox ? b->h_mail : b->h_cap) + kMailDigests;
     if (!h) return posted;
     const size_t nb = b->batch;
-    // stage[d], d < h: [proof][2^d] digests = level lb + d of the batch heap
+    // stage[d], ce <= d < h: [proof][2^d] digests = level lb + d of the batch heap
     std::vector<uint32_t*> lvl(h + 1);
-    for (uint32_t dd = 0; dd < h; ++dd) {
+    for (uint32_t dd = ce; dd < h; ++dd) {
         lvl[dd] = b->h_stage + b->stage_used;
         b->stage_used += (nb << dd) * 8;
     }
     lvl[h] = const_cast<uint32_t*>(posted);
     b->pool->run(nb, 1, [&](size_t p) {
-        for (uint32_t dd = h; dd-- > 0;) {
+        for (uint32_t dd = h; dd-- > ce;) {
             const uint32_t* child = lvl[dd + 1] + ((p << (dd + 1)) * 8);
             uint32_t* out = lvl[dd] + ((p << dd) * 8);
             host_sha_inner_run(child, out, (size_t)1 << dd);
         }
     });
-    for (uint32_t dd = 0; dd < h; ++dd) {
+    for (uint32_t dd = ce; dd < h; ++dd) {
         b->h_segs[b->n_segs++] = ScatterSeg{(uint64_t)(lvl[dd] - b->h_stage),
                                             (uint64_t)b->tree_off[tree] + ((((uint64_t)1 << (b->lb + dd)) - 1) * 8),
                                             (uint32_t)((nb << dd) * 8), 0};
         b->seg_words += (double)((nb << dd) * 8);
     }
-    return lvl[0];
+    return lvl[ce];
 }
 
 // values and path digests one query opens (transcript.hpp: for_each_opening)
-void bopenings(const zk_batch* b, uint32_t fold, bool coset, uint32_t stop, size_t* vals, size_t* digs) {
+void bopenings(const zk_batch* b, uint32_t fold, bool coset, uint32_t stop, uint32_t cap, size_t* vals, size_t* digs) {
     *vals = *digs = 0;
     for_each_opening(b->log_n, b->log_b, fold, 0, [&](uint32_t, uint32_t log_leaves, size_t, uint32_t slots_log) {
-        *vals += (size_t)1 << slots_log; *digs += log_leaves;
+        *vals += (size_t)1 << slots_log; *digs += log_leaves - cap_eff(cap, log_leaves);   // a path ends below its tree's cap
     }, coset, stop);
 }
 // gather buffers for q queries per proof (offsets in, values + digests out; device and pinned host copies), for the current fold
@@ -184,10 +224,10 @@ int balloc_gather(zk_batch* b, uint32_t q) {
     return ZK_OK;
 }
 
-// The batch goes to (fold, coset, stop): d_work for the multi-fold (every fold > 1, and every fold with coset leaves or an early stop),
-// the [batch][1 + 2^stop] tables of the final polynomials, the gather buffers for what a query of that format opens.  On failure the
-// batch keeps its settings and the buffers they need.
-int bset_format(zk_batch* b, uint32_t fold, bool coset, uint32_t stop, const char* who) {
+// The batch goes to (fold, coset, stop, cap): d_work for the multi-fold (every fold > 1, and every fold with coset leaves or an early stop),
+// the [batch][1 + 2^stop] tables of the final polynomials, the gather buffers for what a query of that format opens, the pinned buffer
+// for caps the mailbox cannot hold.  On failure the batch keeps its settings and the buffers they need.
+int bset_format(zk_batch* b, uint32_t fold, bool coset, uint32_t stop, uint32_t cap, const char* who) {
     HIPCHK(hipSetDevice(b->device));
     HIPCHK(hipStreamSynchronize(b->stream));
     if ((fold > 1 || coset || stop) && !b->d_work) {
@@ -202,14 +242,32 @@ int bset_format(zk_batch* b, uint32_t fold, bool coset, uint32_t stop, const cha
         if (e == hipSuccess && (e = hipHostMalloc((void**)&nh_final, final_bytes(stop))) != hipSuccess) { (void)hipFree(nd_final); nd_final = nullptr; }
         if (e != hipSuccess) return fail(ZK_ERR_NOMEM, "%s: allocating %zu bytes for the final polynomials failed: %s", who, final_bytes(stop), hipGetErrorString(e));
     }
+    const size_t cap_words = bcap_words(b, cap);
+    uint32_t *nh_cap = nullptr, *nd_cap = nullptr;
+    if (cap_words && cap_words != b->cap_words) {
+        hipError_t e = hipHostMalloc((void**)&nh_cap, cap_words * 4, hipHostMallocMapped | hipHostMallocCoherent);
+        if (e == hipSuccess && (e = hipHostGetDevicePointer((void**)&nd_cap, nh_cap, 0)) != hipSuccess) (void)hipHostFree(nh_cap);
+        if (e != hipSuccess) {
+            if (nd_final) (void)hipFree(nd_final);
+            if (nh_final) (void)hipHostFree(nh_final);
+            return fail(ZK_ERR_NOMEM, "%s: allocating %zu pinned bytes for the Merkle caps failed: %s", who, cap_words * 4, hipGetErrorString(e));
+        }
+    }
     const size_t old_vals = b->per_proof_vals, old_digs = b->per_proof_digs;
-    bopenings(b, fold, coset, stop, &b->per_proof_vals, &b->per_proof_digs);
+    bopenings(b, fold, coset, stop, cap, &b->per_proof_vals, &b->per_proof_digs);
     if (int rc = balloc_gather(b, b->queries)) {          // the old buffers are gone: put back what the old format needs, or fail again later
         b->per_proof_vals = old_vals; b->per_proof_digs = old_digs;
         (void)balloc_gather(b, b->queries);
         if (nd_final) (void)hipFree(nd_final);
         if (nh_final) (void)hipHostFree(nh_final);
+        if (nh_cap) (void)hipHostFree(nh_cap);
         return rc;
+    }
+    if (cap_words != b->cap_words) {                      // cap 0, or a cap the mailbox holds, gives the buffer back
+        if (b->h_cap) (void)hipHostFree(b->h_cap);
+        b->device_bytes += cap_words * 4;
+        b->device_bytes -= b->cap_words * 4;
+        b->h_cap = nh_cap; b->d_cap = nd_cap; b->cap_words = cap_words;
     }
     if (stop != b->stop) {                                // stop = 0 gives the tables back
         if (b->d_final) (void)hipFree(b->d_final);
@@ -218,7 +276,7 @@ int bset_format(zk_batch* b, uint32_t fold, bool coset, uint32_t stop, const cha
         b->device_bytes -= final_bytes(b->stop);
         b->d_final = nd_final; b->h_final = nh_final;
     }
-    b->fold = fold; b->coset = coset; b->stop = stop;
+    b->fold = fold; b->coset = coset; b->stop = stop; b->cap = cap;
     return ZK_OK;
 }
 
@@ -240,7 +298,7 @@ int zk_batch_destroy(zk_batch* b) {
     for (void* p : {(void*)b->d_trace, (void*)b->d_coef, (void*)b->d_layers, (void*)b->d_trees, (void*)b->d_seed, (void*)b->d_chal,
                     (void*)b->d_counter, (void*)b->d_goff, (void*)b->d_gout, (void*)b->d_work, (void*)b->d_final})
         if (p) (void)hipFree(p);
-    for (void* p : {(void*)b->h_chal, (void*)b->h_mail, (void*)b->h_goff, (void*)b->h_gout, (void*)b->h_last, (void*)b->h_stage, (void*)b->h_final})
+    for (void* p : {(void*)b->h_chal, (void*)b->h_mail, (void*)b->h_goff, (void*)b->h_gout, (void*)b->h_last, (void*)b->h_stage, (void*)b->h_final, (void*)b->h_cap})
         if (p) (void)hipHostFree(p);
     grinder_destroy(b->grinder);                         // on b->stream: before the stream goes
     if (b->stream) (void)hipStreamDestroy(b->stream);
@@ -299,7 +357,7 @@ int zk_batch_create(int device, uint32_t log_n, uint32_t log_b, uint32_t log_bat
         return bail(rc);
     HIPCHK_B(hipMemsetAsync(b->d_counter, 0, 64, b->stream));
     HIPCHK_B(hipMemsetAsync(b->d_trace, 0, b->batch * b->n * 4, b->stream));
-    bopenings(b, 1, false, 0, &b->per_proof_vals, &b->per_proof_digs);
+    bopenings(b, 1, false, 0, 0, &b->per_proof_vals, &b->per_proof_digs);
     if ((rc = balloc_gather(b, 1))) return bail(rc);
     HIPCHK_B(hipHostMalloc((void**)&b->h_chal, b->batch * sizeof(BatchChal)));
     HIPCHK_B(hipHostMalloc((void**)&b->h_last, b->batch * (b->B > 2 ? b->B : 2) * 4));
@@ -400,7 +458,7 @@ int zk_batch_set_fold(zk_batch* b, uint32_t fold_log) {
         return ZK_OK;
     }
     if (fold_log == b->fold) return ZK_OK;
-    return bset_format(b, fold_log, b->coset, b->stop, "zk_batch_set_fold");
+    return bset_format(b, fold_log, b->coset, b->stop, b->cap, "zk_batch_set_fold");
 }
 uint32_t zk_batch_get_fold(const zk_batch* b) { return b ? b->fold : 0; }
 // Coset leaves (include/zkstark_amd.h): from the next zk_batch_prove on.  A coset proof opens fewer nodes and other values than a plain
@@ -414,7 +472,7 @@ int zk_batch_set_coset_leaves(zk_batch* b, int on) {
         return ZK_OK;
     }
     if ((on != 0) == b->coset) return ZK_OK;
-    return bset_format(b, b->fold, on != 0, b->stop, "zk_batch_set_coset_leaves");
+    return bset_format(b, b->fold, on != 0, b->stop, b->cap, "zk_batch_set_coset_leaves");
 }
 int zk_batch_get_coset_leaves(const zk_batch* b) { return b && b->coset ? 1 : 0; }
 // Early stop (include/zkstark_amd.h): from the next zk_batch_prove on.  A stopped proof opens only the groups of log_n - stop_log rounds,
@@ -432,9 +490,29 @@ int zk_batch_set_fri_stop(zk_batch* b, uint32_t stop_log) {
         return ZK_OK;
     }
     if (stop_log == b->stop) return ZK_OK;
-    return bset_format(b, b->fold, b->coset, stop_log, "zk_batch_set_fri_stop");
+    return bset_format(b, b->fold, b->coset, stop_log, b->cap, "zk_batch_set_fri_stop");
 }
 uint32_t zk_batch_get_fri_stop(const zk_batch* b) { return b ? b->stop : 0; }
+// Merkle caps (include/zkstark_amd.h): from the next zk_batch_prove on.  A capped proof opens shorter paths, so the gather buffers are
+// re-sized here; a cap that lies deeper in the batch heap than the mailbox holds gets its pinned buffer here, not inside the first proof.
+int zk_batch_set_merkle_cap(zk_batch* b, uint32_t cap_log) {
+    if (!b) return fail(ZK_ERR_INVALID, "null batch");
+    ZK_BATCH_EXCLUSIVE(b, "zk_batch_set_merkle_cap");
+    if (cap_log > kMaxCapLog) return fail(ZK_ERR_INVALID, "zk_batch_set_merkle_cap: need cap_log <= %u (got %u)", kMaxCapLog, cap_log);
+    if (b->single) {
+        if (int rc = zk_ctx_set_merkle_cap(b->single, cap_log)) return rc;
+        b->cap = cap_log;
+        return ZK_OK;
+    }
+    if (cap_log == b->cap) return ZK_OK;
+    return bset_format(b, b->fold, b->coset, b->stop, cap_log, "zk_batch_set_merkle_cap");
+}
+uint32_t zk_batch_get_merkle_cap(const zk_batch* b) { return b ? b->cap : 0; }
+uint32_t zk_batch_merkle_cap_log(const zk_batch* b, uint32_t tree) {
+    if (!b) return 0;
+    if (b->single) return zk_ctx_merkle_cap_log(b->single, tree);
+    return tree <= b->R + 1 ? b->tree_cap[tree] : 0;
+}
 size_t zk_batch_device_bytes(const zk_batch* b) { return b ? b->device_bytes : 0; }
 
 // traces: [batch][n-1] canonical residues on the host (prover.rs:32-39 per proof)
@@ -507,6 +585,9 @@ int zk_batch_merkle_nodes(zk_batch* b, uint32_t tree, size_t first, size_t count
     if (first > heap || count > heap - first) return fail(ZK_ERR_INVALID, "zk_batch_merkle_nodes: out of range");
     if ((b->skipped_trees >> tree) & 1)
         return fail(ZK_ERR_STATE, "zk_batch_merkle_nodes: tree %u was not built by the last proof (fold_log %u, fri_stop %u)", tree, b->proved_fold, b->proved_stop);
+    if (count && b->tree_cap[tree] && first + 1 < ((size_t)1 << (b->lb + b->tree_cap[tree])))
+        return fail(ZK_ERR_STATE, "zk_batch_merkle_nodes: node %zu of tree %u lies above its Merkle cap (depth %u): the last proof did not build it", first, tree,
+                    b->lb + b->tree_cap[tree]);
     const uint32_t* d_heap = b->d_trees + b->tree_off[tree];
     const size_t top = b->batch - 1;                                      // nodes above the per-proof roots
     if (first >= top || !count) return merkle_nodes_to_host(b->device, b->stream, d_heap, first, count, out);
@@ -516,6 +597,23 @@ int zk_batch_merkle_nodes(zk_batch* b, uint32_t tree, size_t first, size_t count
     const size_t n_top = count < top - first ? count : top - first;
     memcpy(out, up.data() + 32 * first, 32 * n_top);
     return merkle_nodes_to_host(b->device, b->stream, d_heap, first + n_top, count - n_top, out + 32 * n_top);
+}
+
+// What proof `proof` of the last zk_batch_prove committed for `tree`: the 2^ce digests of depth ce of its tree, nodes
+// 2^(lb + ce) - 1 + proof 2^ce .. of the batch heap, which the device built or the scatter copied in (ce = 0: its root).
+int zk_batch_merkle_cap(zk_batch* b, uint32_t tree, size_t proof, uint8_t* out, size_t out_len) {
+    if (!b || !out) return fail(ZK_ERR_INVALID, "zk_batch_merkle_cap: null argument");
+    if (b->single) return proof == 0 ? zk_ctx_merkle_cap(b->single, tree, out, out_len) : fail(ZK_ERR_INVALID, "zk_batch_merkle_cap: proof %zu out of range", proof);
+    if (tree > b->R + 1) return fail(ZK_ERR_INVALID, "zk_batch_merkle_cap: tree %u out of range", tree);
+    if (proof >= b->batch) return fail(ZK_ERR_INVALID, "zk_batch_merkle_cap: proof %zu out of range", proof);
+    BusyScope busy(b);
+    if (!busy.mine) return fail(ZK_ERR_STATE, "zk_batch_merkle_cap: a zk_batch_prove is running on this batch");
+    if (!b->proved) return fail(ZK_ERR_STATE, "zk_batch_merkle_cap: no proof made yet");
+    if ((b->skipped_trees >> tree) & 1)
+        return fail(ZK_ERR_STATE, "zk_batch_merkle_cap: tree %u was not built by the last proof (fold_log %u, fri_stop %u)", tree, b->proved_fold, b->proved_stop);
+    const uint32_t ce = b->tree_cap[tree];
+    if (((size_t)32 << ce) > out_len) return fail(ZK_ERR_BUFFER, "zk_batch_merkle_cap: %zu bytes, room for %zu", (size_t)32 << ce, out_len);
+    return merkle_nodes_to_host(b->device, b->stream, b->d_trees + b->tree_off[tree], (((size_t)1 << (b->lb + ce)) - 1) + (proof << ce), (size_t)1 << ce, out);
 }
 
 // generate_proof (prover.rs:9-293) for every resident trace.  proofs_out: [batch][stride] bytes, stride >=
@@ -535,7 +633,7 @@ int zk_batch_prove(zk_batch* b, uint8_t* proofs_out, size_t stride, uint8_t* sta
     const uint32_t K = b->fold;
     const bool coset = b->coset;
     const uint32_t stop = b->stop;
-    const size_t plen = proof_data_len(b->log_n, b->log_b, Q, b->grind, K, coset, stop);
+    const size_t plen = proof_data_len_cap(b->log_n, b->log_b, Q, b->grind, K, coset, stop, b->cap);
     if (stride < plen) return fail(ZK_ERR_BUFFER, "zk_batch_prove: stride %zu < proof length %zu", stride, plen);
     if (b->single) {
         size_t len = 0;
@@ -560,12 +658,26 @@ int zk_batch_prove(zk_batch* b, uint8_t* proofs_out, size_t stride, uint8_t* sta
         T0 = t;
     };
     auto wait_roots = [&]() { double t = now_us(); int r = bwait_roots(b); t_wait += now_us() - t; return r; };
+    // What proof p commits for a tree (prover.rs:85, :180, :224): the 2^ce digests of depth ce in ONE commit (ce = 0: the root).
+    // from: [batch][2^ce][8] state words (bfinish_roots).
+    double t_caps = 0;
+    auto commit_tree = [&](size_t p, const uint32_t* from, uint32_t ce) {
+        uint8_t cb[32 << kMaxCapLog];
+        const uint32_t* w = from + ((p << ce) * 8);
+        for (size_t i = 0; i < ((size_t)1 << ce); ++i) digest_words_to_bytes(w + 8 * i, cb + 32 * i);
+        ch[p].commit_bytes(cb, (size_t)32 << ce);
+    };
+    // the pool's share of a commit round that hashes caps (ZK_HOST_TIMING)
+    auto cap_lap = [&](uint32_t ce, double t) { if (timing && ce) t_caps += now_us() - t; };
     // f = LDE of every trace, committed (prover.rs:60-85)
     if ((rc = dom_lde(d, b->d_trace, b->d_coef, b->d_layers + b->layer_off[0], b->stream, nullptr, (uint32_t)nb))) return rc;
     b->stage_used = 0; b->n_segs = 0; b->seg_words = 0;
     b->skipped_trees = 0; b->proved_fold = K; b->proved_stop = stop; b->proved_hash = hash;
     memset(b->tree_steps, 0, sizeof b->tree_steps);
-    HIPCHK(launch_merkle_build(b->d_layers + b->layer_off[0], L + lb, b->d_trees + b->tree_off[0], b->stream, nullptr, bmail(b, L), hash));
+    memset(b->tree_cap, 0, sizeof b->tree_cap);
+    b->proved = true;
+    HIPCHK(launch_merkle_build(b->d_layers + b->layer_off[0], L + lb, b->d_trees + b->tree_off[0], b->stream, nullptr, bmail(b, 0, L), hash));
+    if ((rc = bpost(b, 0, L))) return rc;
     // proof-independent part of the composition constants (compose_args with alpha = 1)
     ComposeBatchArgs ca;
     {
@@ -576,30 +688,36 @@ int zk_batch_prove(zk_batch* b, uint8_t* proofs_out, size_t stride, uint8_t* sta
     const uint32_t g2 = mulmod(d->g, d->g);
     if ((rc = wait_roots())) return rc;
     const uint32_t* roots = bfinish_roots(b, 0, L);
+    double tc = timing ? now_us() : 0;
     b->pool->run(nb, 16, [&](size_t p) {
-        uint8_t root[32];
-        digest_words_to_bytes(roots + 8 * p, root);
-        ch[p].commit_hash(root);                                          // prover.rs:85
+        commit_tree(p, roots, b->tree_cap[0]);                            // prover.rs:85
         uint32_t a0 = ch[p].get_u32() % P, a1 = ch[p].get_u32() % P, a2 = ch[p].get_u32() % P;   // prover.rs:163-165
         BatchChal& c = b->h_chal[p];
         c.first = b->first[p]; c.last = b->last[p];
         c.alpha0_mont = to_mont(a0); c.alpha1g2_mont = to_mont(mulmod(a1, g2)); c.alpha2_mont = to_mont(a2);
     });
+    cap_lap(b->tree_cap[0], tc);
     if ((rc = bchal_upload(b))) return rc;
     if (coset) {                                                          // prover.rs:166-176, then the tree with group 0's cosets as leaves
         const uint32_t s0 = fold_steps(Rp, K, 0);
         HIPCHK(launch_compose_batch(ca, lb, b->stream, nullptr));
         b->tree_steps[1] = (uint8_t)s0;
         HIPCHK(launch_merkle_build_coset_batch(b->d_layers + b->layer_off[1], L, s0, lb, b->d_trees + b->tree_off[1], b->stream, nullptr,
-                                               bmail(b, L - s0), hash));
-    } else
-    HIPCHK(launch_compose_merkle_batch(ca, lb, b->d_trees + b->tree_off[1], b->stream, nullptr, bmail(b, L), hash));   // prover.rs:166-176
+                                               bmail(b, 1, L - s0), hash));
+        if ((rc = bpost(b, 1, L - s0))) return rc;
+    } else {
+        HIPCHK(launch_compose_merkle_batch(ca, lb, b->d_trees + b->tree_off[1], b->stream, nullptr, bmail(b, 1, L), hash));   // prover.rs:166-176
+        if ((rc = bpost(b, 1, L))) return rc;
+    }
     const bool fused = K == 1 && !coset && !stop;                         // the fold inside the leaf hashing of its tree
     for (uint32_t r0 = 0;;) {                                             // per group; tree 1 + r0 is the last one committed
         if ((rc = wait_roots())) return rc;
         roots = bfinish_roots(b, 1 + r0, L - r0 - b->tree_steps[1 + r0]);   // tree 1 + r0: 2^(L - r0) values per proof, 2^tree_steps per leaf
+        const uint32_t ce = b->tree_cap[1 + r0];                          // ... committed by its 2^ce digests of depth ce
+        tc = timing ? now_us() : 0;
         if (r0 == R) {
-            b->pool->run(nb, 32, [&](size_t p) { uint8_t root[32]; digest_words_to_bytes(roots + 8 * p, root); ch[p].commit_hash(root); });
+            b->pool->run(nb, 32, [&](size_t p) { commit_tree(p, roots, ce); });
+            cap_lap(ce, tc);
             break;
         }
         const uint32_t steps = Rp - r0 < K ? Rp - r0 : K, id = 1 + r0 + steps;
@@ -607,18 +725,18 @@ int zk_batch_prove(zk_batch* b, uint8_t* proofs_out, size_t stride, uint8_t* sta
         // K = 1: the fold constant is reduced on the host; K > 1: the challenge goes up RAW and is reduced on the device
         const uint32_t winv_half = fused ? mulmod(invmod(powmod(d->shift, (uint64_t)1 << r0)), invmod(2)) : 0;
         b->pool->run(nb, 32, [&](size_t p) {
-            uint8_t root[32];
-            digest_words_to_bytes(roots + 8 * p, root);
-            ch[p].commit_hash(root);                                      // prover.rs:180 / :224
+            commit_tree(p, roots, ce);                                    // prover.rs:180 / :224
             const uint32_t beta = ch[p].get_u32();                        // prover.rs:200, once per group
             b->h_chal[p].c_mont = fused ? to_mont(mulmod(beta % P, winv_half)) : beta;
         });
+        cap_lap(ce, tc);
         if ((rc = bchal_upload(b))) return rc;
         if (fused) {
             FoldBatchArgs fa;
             if ((rc = fold_args(d, b->d_layers + b->layer_off[1 + r0], b->d_layers + b->layer_off[id], L - r0, r0, 0, fa.a))) return rc;
             fa.chal = b->d_chal;
-            HIPCHK(launch_fold_merkle_batch(fa, lb, b->d_trees + b->tree_off[id], b->stream, nullptr, bmail(b, L - r0 - 1), hash));   // prover.rs:201-214
+            HIPCHK(launch_fold_merkle_batch(fa, lb, b->d_trees + b->tree_off[id], b->stream, nullptr, bmail(b, id, L - r0 - 1), hash));   // prover.rs:201-214
+            if ((rc = bpost(b, id, L - r0 - 1))) return rc;
         } else {
             if ((rc = dom_fold_multi_batch(d, b->d_layers + b->layer_off[1 + r0], b->d_layers + b->layer_off[id], L - r0, r0, steps, &b->d_chal->c_mont,
                                            (uint32_t)(sizeof(BatchChal) / 4), b->d_work, (uint32_t)nb, b->stream, nullptr))) return rc;   // prover.rs:201-211, steps times
@@ -632,15 +750,17 @@ int zk_batch_prove(zk_batch* b, uint8_t* proofs_out, size_t stride, uint8_t* sta
             if (leaf_steps) {
                 b->tree_steps[id] = (uint8_t)leaf_steps;
                 HIPCHK(launch_merkle_build_coset_batch(b->d_layers + b->layer_off[id], L - r0 - steps, leaf_steps, lb, b->d_trees + b->tree_off[id],
-                                                       b->stream, nullptr, bmail(b, L - r0 - steps - leaf_steps), hash));
+                                                       b->stream, nullptr, bmail(b, id, L - r0 - steps - leaf_steps), hash));
             } else
             HIPCHK(launch_merkle_build(b->d_layers + b->layer_off[id], L - r0 - steps + lb, b->d_trees + b->tree_off[id], b->stream, nullptr,
-                                       bmail(b, L - r0 - steps), hash));      // prover.rs:214
+                                       bmail(b, id, L - r0 - steps), hash));      // prover.rs:214
+            if ((rc = bpost(b, id, L - r0 - steps - leaf_steps))) return rc;
         }
         r0 += steps;
     }
     lap("lde .. last roots");
     if (timing) fprintf(stderr, "[zk batch timing]   of which waiting for the device %.1f us\n", t_wait);
+    if (timing && b->cap) fprintf(stderr, "[zk batch timing]   of which host threads hashing cap commits %.1f us\n", t_caps);
     const size_t ncoef = (size_t)1 << stop, frow = ncoef + 1;             // early stop: a row of h_final is (count, c_0 .. c_(2^stop - 1))
     if (stop) {
         // final polynomials: layer 1 + Rp holds 2^(stop + log_b) values per proof; every coefficient of degree >= 2^stop must be zero
@@ -690,6 +810,7 @@ int zk_batch_prove(zk_batch* b, uint8_t* proofs_out, size_t stride, uint8_t* sta
             nodes.clear();
             path_nodes((size_t)1 << log_m, leaf, nodes);
             uint32_t dd = log_m;                                          // path_nodes walks from the leaf level up
+            nodes.resize(log_m - b->tree_cap[tree]);                      // ... and the path ends below the tree's cap
             for (size_t nd : nodes) {
                 size_t i = nd - (((size_t)1 << dd) - 1);
                 *dofs++ = (uint64_t)b->tree_off[tree] + (uint64_t)((((size_t)1 << (lb + dd)) - 1) + (p << dd) + i) * 8;
@@ -723,10 +844,10 @@ int zk_batch_prove(zk_batch* b, uint8_t* proofs_out, size_t stride, uint8_t* sta
             vals += s; dw += 8 * (one_leaf ? 1 : s) * pl;
         };
         for (uint32_t q = 0; q < Q; ++q) {
-            for (int k = 0; k < (coset ? 3 : 4); ++k) tuple(1, L, false);                                              // prover.rs:274-277
+            for (int k = 0; k < (coset ? 3 : 4); ++k) tuple(1, L - b->tree_cap[k < 3 ? 0 : 1], false);                 // prover.rs:274-277
             for (uint32_t j = 0, G = fold_groups(Rp, K); j < G; ++j) {                                                 // prover.rs:280-289
                 const uint32_t steps = fold_steps(Rp, K, j);
-                tuple((size_t)1 << steps, L - j * K - (coset ? steps : 0), coset);
+                tuple((size_t)1 << steps, L - j * K - (coset ? steps : 0) - b->tree_cap[1 + j * K], coset);            // paths end below the cap
             }
         }
         if (ch[p].data.size() != plen) { bad.store(1); return; }

@@ -1694,7 +1694,15 @@ static hipError_t merkle_build_t(SRC src, double src_bytes, uint32_t log_m, uint
     // a chunk build (tp_floor != 0) runs the subtree kernels down to that ABSOLUTE depth and stops there;
     // launch_merkle_finish builds everything above it once, for the whole tree
     const bool throughput_only = tp_floor != 0;
-    const uint32_t floor_depth = throughput_only ? tp_floor : stop + kMerkleLatencyLog;
+    // top > 0 (whole trees only): the build ends at depth `top`, whose 2^top digests go to the mailbox and the
+    // levels above are hashed by the host (host_sha.hpp; batches: those digests are the per-proof roots).  Without a mailbox the
+    // build just ends there (a batch's caps deeper than the mailbox holds: launch_digest_level_post posts them), wherever `top`
+    // lies: at or below the latency switch the throughput launches run down to `top` and the latency phase has nothing left.
+    MailArgs mail = mail_in;
+    if (stop != 0 || mail.top >= log_m) mail.top = 0;
+    const uint32_t end = stop == 0 ? mail.top : stop;
+    const uint32_t latency_depth = stop + kMerkleLatencyLog > end ? stop + kMerkleLatencyLog : end;
+    const uint32_t floor_depth = throughput_only ? tp_floor : latency_depth;
     while (depth > floor_depth) {
         uint32_t k = depth - floor_depth;
         if (k > merkle_max_k()) k = merkle_max_k();
@@ -1717,12 +1725,9 @@ static hipError_t merkle_build_t(SRC src, double src_bytes, uint32_t log_m, uint
         leaf = false;
         depth -= k;
     }
-    if (throughput_only) return hipGetLastError();
-    // top > 0 (whole trees only): the build ends at depth `top`, whose 2^top digests go to the mailbox and the
-    // levels above are hashed by the host (host_sha.hpp; batches: those digests are the per-proof roots)
-    MailArgs mail = mail_in;
-    if (stop != 0 || mail.top >= log_m) mail.top = 0;
-    const uint32_t end = stop == 0 ? mail.top : stop;
+    // the latency phase is skipped when the throughput launches have reached `end` (a tree of ONE leaf has had none: its leaf
+    // is hashed by the launch below, as ever)
+    if (throughput_only || (depth < log_m && depth <= end)) return hipGetLastError();
     auto launch_wg = [&](uint32_t j, uint32_t j2) {
         const uint32_t span = depth - stop;
         const uint32_t blocks = 1u << (span - j);
@@ -2265,6 +2270,44 @@ hipError_t launch_fetch(const uint32_t* layers, const uint32_t* trees, const uin
     if (blocks == 0) blocks = 1;
     if (blocks > 64) blocks = 64;
     hipLaunchKernelGGL(fetch_kernel, dim3(blocks), dim3(kFetchThreads), 0, s, layers, trees, items, nv, ndg, out, mailbox, seq, counter);
+    return hipGetLastError();
+}
+
+// One whole level of a heap for the host: the 2^level_log digests of depth level_log are contiguous (nodes + (2^level_log - 1) * 8,
+// 2^(level_log + 3) words) and go to host-mapped memory with 16-byte accesses on both sides; the flag follows them by fetch_kernel's
+// protocol.  A launch of its own behind the build on the same stream: the kernel boundary has made every node visible, so ordinary
+// loads do.  Workgroups: the link (PCIe Gen5 x16, 63 GB/s) has to be kept full of posted writes; at a round trip of a few
+// microseconds that is a few hundred KiB in flight, and 64 workgroups of 256 lanes hold 256 KiB per trip -- the same width
+// fetch_kernel uses at most.  More workgroups only add arrivals on the counter; a level of <= 2^9 digests takes one.
+constexpr int kPostThreads = 256;
+constexpr uint32_t kPostMaxBlocks = 64, kPostQuadsPerBlock = 1024;
+__global__ __launch_bounds__(kPostThreads) void digest_level_post_kernel(const uint4* __restrict__ src, uint4* __restrict__ dst, uint32_t quads,
+                                                                         uint32_t* flag, uint32_t seq, uint32_t* counter) {
+    const uint32_t stride = gridDim.x * kPostThreads;
+    for (uint32_t i = blockIdx.x * kPostThreads + threadIdx.x; i < quads; i += stride) dst[i] = src[i];
+    __threadfence_system();                                       // this thread's digests are in host memory ...
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        bool last = true;
+        if (gridDim.x > 1) {                                      // ... and so are everybody else's
+            last = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1;
+            if (last) __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        if (last) __hip_atomic_store(flag, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+}
+
+hipError_t launch_digest_level_post(const uint32_t* nodes, uint32_t level_log, uint32_t* host_digests, uint32_t* flag, uint32_t seq,
+                                    uint32_t* counter, hipStream_t s, Profiler* prof) {
+    if (level_log > 28 || !nodes || !host_digests || !flag || !counter) return hipErrorInvalidValue;
+    const uint32_t quads = 2u << level_log;                       // two 16-byte halves per digest
+    ScopedKernelTimer tm(prof, K_GATHER, 64.0 * (double)((size_t)1 << level_log), s);
+    uint32_t blocks = (quads + kPostQuadsPerBlock - 1) / kPostQuadsPerBlock;
+    if (blocks > kPostMaxBlocks) blocks = kPostMaxBlocks;
+    // (2^level_log - 1) * 8 words is 32 (2^level_log - 1) bytes: 16-byte aligned, as the heap and the host buffer are
+    hipLaunchKernelGGL(digest_level_post_kernel, dim3(blocks), dim3(kPostThreads), 0, s,
+                       reinterpret_cast<const uint4*>(nodes + (((size_t)1 << level_log) - 1) * 8), reinterpret_cast<uint4*>(host_digests), quads, flag, seq,
+                       counter);
     return hipGetLastError();
 }
 

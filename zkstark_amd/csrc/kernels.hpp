@@ -362,5 +362,11 @@ hipError_t launch_gather(const uint32_t* src, const uint64_t* offsets, uint32_t 
 // zeroed device word, as in MailArgs); the host polls instead of synchronising the stream.
 hipError_t launch_fetch(const uint32_t* layers, const uint32_t* trees, const uint64_t* items, uint32_t nv, uint32_t ndg, uint32_t* out,
                         uint32_t* mailbox, uint32_t seq, uint32_t* counter, hipStream_t s, Profiler* prof = nullptr);
+// The 2^level_log digests of depth level_log of a heap (contiguous: nodes + (2^level_log - 1) * 8) copied to host-mapped memory,
+// then *flag = seq behind them (fetch_kernel's protocol; counter: one zeroed device word).  For hand-overs wider than a mailbox
+// (kMaxHostLog): the build ends at that depth without a mailbox (MailArgs{nullptr, top = level_log}) and this launch follows it on
+// the same stream.  host_digests needs 2^(level_log + 3) words, 16-byte aligned; level_log <= 28.
+hipError_t launch_digest_level_post(const uint32_t* nodes, uint32_t level_log, uint32_t* host_digests, uint32_t* flag, uint32_t seq,
+                                    uint32_t* counter, hipStream_t s, Profiler* prof = nullptr);
 
 }  // namespace zk

@@ -559,15 +559,18 @@ class BatchContext:
     launch over the whole batch; each proof has its own channel and is byte-identical to Context.prove()."""
 
     def __init__(self, log_n=10, log_blowup=3, log_batch=4, device=0, hash="sha256", queries=1, grind_bits=0, fold_log=1, coset_leaves=False,
-                 stop_log=0):
+                 stop_log=0, cap_log=0):
         """fold_log: FRI folding factor 2^fold_log between commitments for every proof of the batch (zk_batch_set_fold; 1 = the
         reference).  coset_leaves: one coset per Merkle leaf of the FRI trees (zk_batch_set_coset_leaves).  stop_log: every proof stops
-        FRI at a polynomial of degree < 2^stop_log and sends its coefficients (zk_batch_set_fri_stop; 0 = fold to a constant)."""
+        FRI at a polynomial of degree < 2^stop_log and sends its coefficients (zk_batch_set_fri_stop; 0 = fold to a constant).
+        cap_log: every proof commits each tree by its 2^cap_log digests of depth cap_log and opens paths that much shorter
+        (zk_batch_set_merkle_cap; 0 = roots)."""
         _no_blake2s("BatchContext", hash)
         self.log_n, self.log_blowup, self.log_batch, self.hash, self.queries = log_n, log_blowup, log_batch, hash, queries
         self.grind_bits, self.fold_log = grind_bits, 1
         self.coset_leaves = False
         self.stop_log = 0
+        self.cap_log = 0
         self.n, self.batch = 1 << log_n, 1 << log_batch
         self._h = C.c_void_p()
         check(_lib.load().zk_batch_create(device, log_n, log_blowup, log_batch, C.byref(self._h)))
@@ -583,6 +586,20 @@ class BatchContext:
             self.set_coset_leaves(True)
         if stop_log:
             self.set_fri_stop(stop_log)
+        if cap_log:
+            self.set_merkle_cap(cap_log)
+
+    def set_merkle_cap(self, cap_log):
+        """zk_batch_set_merkle_cap: from the next zk_batch_prove on, every proof commits a tree of 2^lg leaves by the 2^ce digests of
+        depth ce = min(cap_log, lg - 1) and its paths carry lg - ce digests (0: roots, the reference)."""
+        check(_lib.load().zk_batch_set_merkle_cap(self._h, cap_log))
+        self.cap_log = cap_log
+
+    def merkle_cap(self, tree, proof):
+        """zk_batch_merkle_cap: the digests proof `proof` of the last prove committed for `tree`, a [2^ce, 32] uint8 array (ce = 0: its root)."""
+        out = np.zeros((1 << _lib.load().zk_batch_merkle_cap_log(self._h, tree), 32), dtype=np.uint8)
+        check(_lib.load().zk_batch_merkle_cap(self._h, tree, proof, out.ctypes.data_as(C.c_void_p), out.size))
+        return out
 
     def set_fri_stop(self, stop_log):
         """zk_batch_set_fri_stop: from the next zk_batch_prove on, every proof folds only log_n - stop_log rounds and commits the
@@ -602,6 +619,9 @@ class BatchContext:
 
     @property
     def proof_len(self):
+        if self.cap_log:
+            return _lib.load().zk_proof_data_len_cap(self.log_n, self.log_blowup, self.queries, self.grind_bits, self.fold_log,
+                                                     int(self.coset_leaves), self.stop_log, self.cap_log)
         if self.stop_log:
             return _lib.load().zk_proof_data_len_stop(self.log_n, self.log_blowup, self.queries, self.grind_bits, self.fold_log,
                                                       int(self.coset_leaves), self.stop_log)
@@ -659,7 +679,7 @@ class BatchContext:
         data, states = self.prove_raw()
         last = self.public_last()
         return [Proof(states[p].tobytes(), data[p].tobytes(), self.log_n, self.log_blowup, int(last[p]), self.hash, self.queries,
-                      self.grind_bits, self.fold_log, self.coset_leaves, self.stop_log) for p in range(self.batch)]
+                      self.grind_bits, self.fold_log, self.coset_leaves, self.stop_log, self.cap_log) for p in range(self.batch)]
 
 
 _ERR_VERIFY = -6
