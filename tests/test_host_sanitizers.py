@@ -7,6 +7,8 @@ import subprocess
 
 import pytest
 
+import cap_ref
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -27,20 +29,32 @@ def checker(tmp_path_factory):
     return exe
 
 
-@pytest.mark.parametrize("log_n,log_b,hash_kind", [(6, 2, 0), (10, 3, 0), (5, 1, 1)])
-def test_verifier_memory_safety(orc, checker, tmp_path, log_n, log_b, hash_kind):
-    try:
-        orc.set_hash(hash_kind)
-        r = orc.prove(log_n, log_b, want_vectors=False)
-    finally:
-        orc.set_hash(0)
-    assert r.rc == 0
+# settings: None = the reference's format through the lax verifier alone; (q, K, coset, D, c, grind) = that format (tests/cap_ref.py builds
+# the proof) through the replay and then the proof checks, with the proof's state.  The checker also walks ProofFormat's own grid.
+@pytest.mark.parametrize("log_n,log_b,hash_kind,settings", [
+    pytest.param(6, 2, 0, None, id="6-2-0"), pytest.param(10, 3, 0, None, id="10-3-0"), pytest.param(5, 1, 1, None, id="5-1-1"),
+    pytest.param(6, 3, 0, (3, 3, True, 2, 2, 4), id="every-setting")])
+def test_verifier_memory_safety(orc, checker, tmp_path, log_n, log_b, hash_kind, settings):
+    extra = []
+    if settings is None:
+        try:
+            orc.set_hash(hash_kind)
+            r = orc.prove(log_n, log_b, want_vectors=False)
+        finally:
+            orc.set_hash(0)
+        assert r.rc == 0
+        data, public_last = r.proof, r.public_last
+    else:
+        q, K, coset, D, c, grind = settings
+        ref = cap_ref.proof(orc, log_n, log_b, q, hash_kind, K, coset, D, c, bits=grind)
+        data, public_last = ref.data, ref.public_last
+        extra = [str(q), str(grind), str(K), str(int(coset)), str(D), str(c), bytes(ref.state).hex()]
     p = tmp_path / "proof.bin"
-    p.write_bytes(r.proof)
-    out = subprocess.run([checker, str(p), str(log_n), str(log_b), str(r.public_last), str(hash_kind)],
+    p.write_bytes(data)
+    out = subprocess.run([checker, str(p), str(log_n), str(log_b), str(public_last), str(hash_kind)] + extra,
                          capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stdout + out.stderr
-    assert "ok: valid accepted" in out.stdout
+    assert "format self-check" in out.stdout and "ok: valid accepted" in out.stdout
 
 
 @pytest.mark.parametrize("san", ["thread", "address,undefined"])

@@ -57,22 +57,19 @@ struct zk_batch {
     uint32_t *d_gout = nullptr, *h_gout = nullptr;
     uint32_t* h_last = nullptr;       // pinned: [batch][B] last layer / [batch] last trace values
     size_t per_proof_vals = 0, per_proof_digs = 0;   // per query
-    uint32_t queries = 1;             // decommitment queries per proof (1 = the reference, prover.rs:263)
-    uint32_t grind = 0;               // proof-of-work bits (zk_batch_set_grinding)
-    uint32_t fold = 1;                // FRI folding factor 2^fold between commitments (zk_batch_set_fold; 1 = the reference)
-    uint32_t stop = 0;                // early stop D (zk_batch_set_fri_stop; 0 = fold down to a constant, the reference)
+    // The format of the next zk_batch_prove (transcript.hpp), one field per setter: q (1 = the reference, prover.rs:263), grind, fold
+    // (1 = the reference), coset, stop (0 = fold down to a constant, the reference) and cap
+    ProofFormat fmt;
     uint32_t proved_fold = 1, proved_stop = 0;   // ... of the last zk_batch_prove, whose skipped_trees these are:
     int proved_hash = 0;              // ... and the Merkle hash its trees were built with (zk_batch_merkle_nodes hashes the levels above the roots)
     uint64_t skipped_trees = 0;       // bit id: that proof built no tree (and no layer) `id`
     uint32_t* d_work = nullptr;       // [batch][8] per-proof constants of the multi-fold (allocated by the first fold > 1, coset leaves or early stop)
     uint32_t *d_final = nullptr, *h_final = nullptr;   // [batch][1 + 2^stop]: count of high coefficients, final polynomial (stop > 0; h_: pinned)
-    bool coset = false;               // coset leaves (zk_batch_set_coset_leaves): from the next zk_batch_prove on
     uint8_t tree_steps[34] = {0};     // tree id of the last zk_batch_prove: its leaves hold 2^tree_steps values (0: one-value leaves)
-    // Merkle caps (zk_batch_set_merkle_cap; transcript.hpp): every proof commits the 2^ce digests of depth ce = min(cap, lg - 1) of each of
+    // Merkle caps (transcript.hpp): every proof commits the 2^ce digests of depth ce = min(cap, lg - 1) of each of
     // its trees, i.e. the batch heap is built down to depth lb + ce and nothing above is hashed.  tree_cap[t]: the ce of tree t in the
     // last zk_batch_prove.  h_cap / d_cap: pinned, mapped, 16 + 8 * 2^(lb + ce of the f tree) words in the mailbox's layout, for the
     // hand-overs the mailbox cannot hold (lb + ce > kMaxHostLog); allocated by the setter only when the f tree needs it.
-    uint32_t cap = 0;
     uint8_t tree_cap[34] = {0};
     bool proved = false;              // a zk_batch_prove has run: tree_cap, tree_steps and skipped_trees describe it
     uint32_t *h_cap = nullptr, *d_cap = nullptr;
@@ -124,15 +121,15 @@ Hand bhand(const zk_batch* b, uint32_t ce, uint32_t log_m) {
     return Hand{b->lb + ce, 0, false};
 }
 // cap > 0: the 16 + 8 * 2^(lb + ce) words of h_cap when the f tree (the deepest cap of a proof) does not fit the mailbox, else 0
-size_t bcap_words(const zk_batch* b, uint32_t cap) {
-    const uint32_t e = b->lb + cap_eff(cap, b->L);
-    return cap && e > kMaxHostLog ? kMailDigests + ((size_t)8 << e) : 0;
+size_t bcap_words(const zk_batch* b, const ProofFormat& f) {
+    const uint32_t e = b->lb + f.f_cap();
+    return f.cap && e > kMaxHostLog ? kMailDigests + ((size_t)8 << e) : 0;
 }
 // Hand-over of the commit launch of `tree` (2^log_m leaves per proof): records the depth its proofs commit it at.
 MailArgs bmail(zk_batch* b, uint32_t tree, uint32_t log_m) {
     MailArgs m;
     if (b->counters_dirty) { (void)hipMemsetAsync(b->d_counter, 0, 64, b->stream); b->counters_dirty = false; }
-    const uint32_t ce = b->cap ? cap_eff(b->cap, log_m) : 0;
+    const uint32_t ce = b->fmt.cap ? cap_eff(b->fmt.cap, log_m) : 0;
     const Hand hd = bhand(b, ce, log_m);
     b->tree_cap[tree] = (uint8_t)ce;
     m.seq = ++b->mail_seq; m.top = hd.top;
@@ -151,15 +148,15 @@ int bpost(zk_batch* b, uint32_t tree, uint32_t log_m) {
 // small g, else one launch per chunk for all proofs still searching.
 int bgrind(zk_batch* b, std::vector<Channel>& ch) {
     const size_t nb = ch.size();
-    if (b->grind <= kGrindHostMaxBits || !b->grinder) {
+    if (b->fmt.grind <= kGrindHostMaxBits || !b->grinder) {
         std::atomic<int> bad{0};
-        b->pool->run(nb, 1, [&](size_t p) { uint64_t w; if (grind_channel(nullptr, ch[p], b->grind, &w)) bad.store(1); });
+        b->pool->run(nb, 1, [&](size_t p) { uint64_t w; if (grind_channel(nullptr, ch[p], b->fmt.grind, &w)) bad.store(1); });
         return bad.load() ? fail(ZK_ERR_HIP, "zk_batch_prove: grinding failed") : (int)ZK_OK;
     }
     std::vector<uint8_t> states(32 * nb);
     std::vector<uint64_t> w(nb);
     for (size_t p = 0; p < nb; ++p) memcpy(states.data() + 32 * p, ch[p].state, 32);
-    if (int rc = grind_device(b->grinder, states.data(), nb, b->grind, 0, w.data())) return rc;
+    if (int rc = grind_device(b->grinder, states.data(), nb, b->fmt.grind, 0, w.data())) return rc;
     b->pool->run(nb, 16, [&](size_t p) { grind_commit(ch[p], w[p]); });
     return ZK_OK;
 }
@@ -202,12 +199,10 @@ const uint32_t* bfinish_roots(zk_batch* b, uint32_t tree, uint32_t log_m) {
     return lvl[ce];
 }
 
-// values and path digests one query opens (transcript.hpp: for_each_opening)
-void bopenings(const zk_batch* b, uint32_t fold, bool coset, uint32_t stop, uint32_t cap, size_t* vals, size_t* digs) {
+// values and path digests one query opens
+void bopenings(const ProofFormat& f, size_t* vals, size_t* digs) {
     *vals = *digs = 0;
-    for_each_opening(b->log_n, b->log_b, fold, 0, [&](uint32_t, uint32_t log_leaves, size_t, uint32_t slots_log) {
-        *vals += (size_t)1 << slots_log; *digs += log_leaves - cap_eff(cap, log_leaves);   // a path ends below its tree's cap
-    }, coset, stop);
+    f.for_each_tuple([&](size_t s, size_t plen, bool one_leaf) { *vals += s; *digs += (one_leaf ? 1 : s) * plen; });
 }
 // gather buffers for q queries per proof (offsets in, values + digests out; device and pinned host copies), for the current fold
 int balloc_gather(zk_batch* b, uint32_t q) {
@@ -220,29 +215,31 @@ int balloc_gather(zk_batch* b, uint32_t q) {
     HIPCHK(hipMalloc((void**)&b->d_gout, out_words * 4));
     HIPCHK(hipHostMalloc((void**)&b->h_goff, slots * 8));
     HIPCHK(hipHostMalloc((void**)&b->h_gout, out_words * 4));
-    b->queries = q;
+    b->fmt.q = q;
     return ZK_OK;
 }
 
-// The batch goes to (fold, coset, stop, cap): d_work for the multi-fold (every fold > 1, and every fold with coset leaves or an early stop),
-// the [batch][1 + 2^stop] tables of the final polynomials, the gather buffers for what a query of that format opens, the pinned buffer
-// for caps the mailbox cannot hold.  On failure the batch keeps its settings and the buffers they need.
-int bset_format(zk_batch* b, uint32_t fold, bool coset, uint32_t stop, uint32_t cap, const char* who) {
+// The batch goes to the format `next` (fold, coset, stop, cap; q and grind have setters of their own): d_work for the multi-fold (every
+// fold > 1, and every fold with coset leaves or an early stop), the [batch][1 + 2^stop] tables of the final polynomials, the gather buffers
+// for what a query of that format opens, the pinned buffer for caps the mailbox cannot hold.  On failure the batch keeps its settings
+// and the buffers they need.
+int bset_format(zk_batch* b, const ProofFormat& next, const char* who) {
+    const uint32_t stop = next.stop;
     HIPCHK(hipSetDevice(b->device));
     HIPCHK(hipStreamSynchronize(b->stream));
-    if ((fold > 1 || coset || stop) && !b->d_work) {
+    if ((next.fold > 1 || next.coset || stop) && !b->d_work) {
         hipError_t e = hipMalloc((void**)&b->d_work, b->batch * 8 * 4);
         if (e != hipSuccess) return fail(ZK_ERR_NOMEM, "%s: hipMalloc(%zu) failed: %s", who, b->batch * 32, hipGetErrorString(e));
         b->device_bytes += b->batch * 32;
     }
     auto final_bytes = [&](uint32_t D) { return D ? b->batch * (((size_t)1 << D) + 1) * 4 : (size_t)0; };
     uint32_t *nd_final = nullptr, *nh_final = nullptr;    // the new tables first: the old ones stay until nothing can fail any more
-    if (stop && stop != b->stop) {
+    if (stop && stop != b->fmt.stop) {
         hipError_t e = hipMalloc((void**)&nd_final, final_bytes(stop));
         if (e == hipSuccess && (e = hipHostMalloc((void**)&nh_final, final_bytes(stop))) != hipSuccess) { (void)hipFree(nd_final); nd_final = nullptr; }
         if (e != hipSuccess) return fail(ZK_ERR_NOMEM, "%s: allocating %zu bytes for the final polynomials failed: %s", who, final_bytes(stop), hipGetErrorString(e));
     }
-    const size_t cap_words = bcap_words(b, cap);
+    const size_t cap_words = bcap_words(b, next);
     uint32_t *nh_cap = nullptr, *nd_cap = nullptr;
     if (cap_words && cap_words != b->cap_words) {
         hipError_t e = hipHostMalloc((void**)&nh_cap, cap_words * 4, hipHostMallocMapped | hipHostMallocCoherent);
@@ -254,10 +251,10 @@ int bset_format(zk_batch* b, uint32_t fold, bool coset, uint32_t stop, uint32_t 
         }
     }
     const size_t old_vals = b->per_proof_vals, old_digs = b->per_proof_digs;
-    bopenings(b, fold, coset, stop, cap, &b->per_proof_vals, &b->per_proof_digs);
-    if (int rc = balloc_gather(b, b->queries)) {          // the old buffers are gone: put back what the old format needs, or fail again later
+    bopenings(next, &b->per_proof_vals, &b->per_proof_digs);
+    if (int rc = balloc_gather(b, b->fmt.q)) {            // the old buffers are gone: put back what the old format needs, or fail again later
         b->per_proof_vals = old_vals; b->per_proof_digs = old_digs;
-        (void)balloc_gather(b, b->queries);
+        (void)balloc_gather(b, b->fmt.q);
         if (nd_final) (void)hipFree(nd_final);
         if (nh_final) (void)hipHostFree(nh_final);
         if (nh_cap) (void)hipHostFree(nh_cap);
@@ -269,14 +266,14 @@ int bset_format(zk_batch* b, uint32_t fold, bool coset, uint32_t stop, uint32_t 
         b->device_bytes -= b->cap_words * 4;
         b->h_cap = nh_cap; b->d_cap = nd_cap; b->cap_words = cap_words;
     }
-    if (stop != b->stop) {                                // stop = 0 gives the tables back
+    if (stop != b->fmt.stop) {                            // stop = 0 gives the tables back
         if (b->d_final) (void)hipFree(b->d_final);
         if (b->h_final) (void)hipHostFree(b->h_final);
         b->device_bytes += final_bytes(stop);
-        b->device_bytes -= final_bytes(b->stop);
+        b->device_bytes -= final_bytes(b->fmt.stop);
         b->d_final = nd_final; b->h_final = nh_final;
     }
-    b->fold = fold; b->coset = coset; b->stop = stop; b->cap = cap;
+    b->fmt = next;
     return ZK_OK;
 }
 
@@ -316,6 +313,7 @@ int zk_batch_create(int device, uint32_t log_n, uint32_t log_b, uint32_t log_bat
     zk_batch* b = new (std::nothrow) zk_batch();
     if (!b) return fail(ZK_ERR_NOMEM, "out of host memory");
     b->device = device;
+    b->fmt.log_n = log_n; b->fmt.log_b = log_b;
     b->log_n = log_n; b->log_b = log_b; b->lb = log_batch; b->L = log_n + log_b; b->R = log_n;
     b->n = (size_t)1 << log_n; b->B = (size_t)1 << log_b; b->N = b->n << log_b; b->batch = (size_t)1 << log_batch;
     int rc = ZK_OK;
@@ -357,7 +355,7 @@ int zk_batch_create(int device, uint32_t log_n, uint32_t log_b, uint32_t log_bat
         return bail(rc);
     HIPCHK_B(hipMemsetAsync(b->d_counter, 0, 64, b->stream));
     HIPCHK_B(hipMemsetAsync(b->d_trace, 0, b->batch * b->n * 4, b->stream));
-    bopenings(b, 1, false, 0, 0, &b->per_proof_vals, &b->per_proof_digs);
+    bopenings(b->fmt, &b->per_proof_vals, &b->per_proof_digs);
     if ((rc = balloc_gather(b, 1))) return bail(rc);
     HIPCHK_B(hipHostMalloc((void**)&b->h_chal, b->batch * sizeof(BatchChal)));
     HIPCHK_B(hipHostMalloc((void**)&b->h_last, b->batch * (b->B > 2 ? b->B : 2) * 4));
@@ -419,10 +417,10 @@ int zk_batch_set_queries(zk_batch* b, uint32_t n_queries) {
     if (!b) return fail(ZK_ERR_INVALID, "null batch");
     ZK_BATCH_EXCLUSIVE(b, "zk_batch_set_queries");
     if (n_queries < 1 || n_queries > 16) return fail(ZK_ERR_INVALID, "zk_batch_set_queries: need 1 <= n_queries <= 16");
-    if (b->single) { b->queries = n_queries; return zk_ctx_set_queries(b->single, n_queries); }
+    if (b->single) { b->fmt.q = n_queries; return zk_ctx_set_queries(b->single, n_queries); }
     HIPCHK(hipSetDevice(b->device));
     HIPCHK(hipStreamSynchronize(b->stream));
-    return n_queries == b->queries ? (int)ZK_OK : balloc_gather(b, n_queries);
+    return n_queries == b->fmt.q ? (int)ZK_OK : balloc_gather(b, n_queries);
 }
 int zk_batch_set_hash(zk_batch* b, int hash_kind) {
     // refused before the handle is looked at: no setting of this class takes it
@@ -438,12 +436,12 @@ int zk_batch_set_grinding(zk_batch* b, uint32_t grind_bits) {
     if (!b) return fail(ZK_ERR_INVALID, "null batch");
     ZK_BATCH_EXCLUSIVE(b, "zk_batch_set_grinding");
     if (grind_bits > kMaxGrindBits) return fail(ZK_ERR_INVALID, "zk_batch_set_grinding: need grind_bits <= %u (got %u)", kMaxGrindBits, grind_bits);
-    if (b->single) { b->grind = grind_bits; return zk_ctx_set_grinding(b->single, grind_bits); }
+    if (b->single) { b->fmt.grind = grind_bits; return zk_ctx_set_grinding(b->single, grind_bits); }
     if (grind_bits > kGrindHostMaxBits && !b->grinder) {
         HIPCHK(hipSetDevice(b->device));
         if (int rc = grinder_create(b->device, b->stream, (uint32_t)b->batch, &b->grinder)) return rc;
     }
-    b->grind = grind_bits;
+    b->fmt.grind = grind_bits;
     return ZK_OK;
 }
 // FRI folding factor 2^fold_log between commitments (include/zkstark_amd.h).  A query of a folded proof opens 2^steps values and paths
@@ -454,13 +452,15 @@ int zk_batch_set_fold(zk_batch* b, uint32_t fold_log) {
     if (fold_log < 1 || fold_log > kMaxFoldLog) return fail(ZK_ERR_INVALID, "zk_batch_set_fold: need 1 <= fold_log <= %u (got %u)", kMaxFoldLog, fold_log);
     if (b->single) {
         if (int rc = zk_ctx_set_fold(b->single, fold_log)) return rc;
-        b->fold = fold_log;
+        b->fmt.fold = fold_log;
         return ZK_OK;
     }
-    if (fold_log == b->fold) return ZK_OK;
-    return bset_format(b, fold_log, b->coset, b->stop, b->cap, "zk_batch_set_fold");
+    if (fold_log == b->fmt.fold) return ZK_OK;
+    ProofFormat next = b->fmt;
+    next.fold = fold_log;
+    return bset_format(b, next, "zk_batch_set_fold");
 }
-uint32_t zk_batch_get_fold(const zk_batch* b) { return b ? b->fold : 0; }
+uint32_t zk_batch_get_fold(const zk_batch* b) { return b ? b->fmt.fold : 0; }
 // Coset leaves (include/zkstark_amd.h): from the next zk_batch_prove on.  A coset proof opens fewer nodes and other values than a plain
 // one, so the gather buffers are re-sized here; every fold, 1 included, then runs on the multi-fold and needs d_work.
 int zk_batch_set_coset_leaves(zk_batch* b, int on) {
@@ -468,13 +468,15 @@ int zk_batch_set_coset_leaves(zk_batch* b, int on) {
     ZK_BATCH_EXCLUSIVE(b, "zk_batch_set_coset_leaves");
     if (b->single) {
         if (int rc = zk_ctx_set_coset_leaves(b->single, on)) return rc;
-        b->coset = on != 0;
+        b->fmt.coset = on != 0;
         return ZK_OK;
     }
-    if ((on != 0) == b->coset) return ZK_OK;
-    return bset_format(b, b->fold, on != 0, b->stop, b->cap, "zk_batch_set_coset_leaves");
+    if ((on != 0) == b->fmt.coset) return ZK_OK;
+    ProofFormat next = b->fmt;
+    next.coset = on != 0;
+    return bset_format(b, next, "zk_batch_set_coset_leaves");
 }
-int zk_batch_get_coset_leaves(const zk_batch* b) { return b && b->coset ? 1 : 0; }
+int zk_batch_get_coset_leaves(const zk_batch* b) { return b && b->fmt.coset ? 1 : 0; }
 // Early stop (include/zkstark_amd.h): from the next zk_batch_prove on.  A stopped proof opens only the groups of log_n - stop_log rounds,
 // so the gather buffers are re-sized here; every fold, 1 included, then runs on the multi-fold and needs d_work, and the tables of the
 // final polynomials are allocated for this stop_log.
@@ -486,13 +488,15 @@ int zk_batch_set_fri_stop(zk_batch* b, uint32_t stop_log) {
                     kMaxStopLog, b->log_n - 1, kMaxStopLayerLog, stop_log);
     if (b->single) {
         if (int rc = zk_ctx_set_fri_stop(b->single, stop_log)) return rc;
-        b->stop = stop_log;
+        b->fmt.stop = stop_log;
         return ZK_OK;
     }
-    if (stop_log == b->stop) return ZK_OK;
-    return bset_format(b, b->fold, b->coset, stop_log, b->cap, "zk_batch_set_fri_stop");
+    if (stop_log == b->fmt.stop) return ZK_OK;
+    ProofFormat next = b->fmt;
+    next.stop = stop_log;
+    return bset_format(b, next, "zk_batch_set_fri_stop");
 }
-uint32_t zk_batch_get_fri_stop(const zk_batch* b) { return b ? b->stop : 0; }
+uint32_t zk_batch_get_fri_stop(const zk_batch* b) { return b ? b->fmt.stop : 0; }
 // Merkle caps (include/zkstark_amd.h): from the next zk_batch_prove on.  A capped proof opens shorter paths, so the gather buffers are
 // re-sized here; a cap that lies deeper in the batch heap than the mailbox holds gets its pinned buffer here, not inside the first proof.
 int zk_batch_set_merkle_cap(zk_batch* b, uint32_t cap_log) {
@@ -501,13 +505,15 @@ int zk_batch_set_merkle_cap(zk_batch* b, uint32_t cap_log) {
     if (cap_log > kMaxCapLog) return fail(ZK_ERR_INVALID, "zk_batch_set_merkle_cap: need cap_log <= %u (got %u)", kMaxCapLog, cap_log);
     if (b->single) {
         if (int rc = zk_ctx_set_merkle_cap(b->single, cap_log)) return rc;
-        b->cap = cap_log;
+        b->fmt.cap = cap_log;
         return ZK_OK;
     }
-    if (cap_log == b->cap) return ZK_OK;
-    return bset_format(b, b->fold, b->coset, b->stop, cap_log, "zk_batch_set_merkle_cap");
+    if (cap_log == b->fmt.cap) return ZK_OK;
+    ProofFormat next = b->fmt;
+    next.cap = cap_log;
+    return bset_format(b, next, "zk_batch_set_merkle_cap");
 }
-uint32_t zk_batch_get_merkle_cap(const zk_batch* b) { return b ? b->cap : 0; }
+uint32_t zk_batch_get_merkle_cap(const zk_batch* b) { return b ? b->fmt.cap : 0; }
 uint32_t zk_batch_merkle_cap_log(const zk_batch* b, uint32_t tree) {
     if (!b) return 0;
     if (b->single) return zk_ctx_merkle_cap_log(b->single, tree);
@@ -628,12 +634,11 @@ int zk_batch_prove(zk_batch* b, uint8_t* proofs_out, size_t stride, uint8_t* sta
     if (!b->have_traces) return fail(ZK_ERR_STATE, "zk_batch_prove: no traces");
     BusyScope busy(b);
     if (!busy.mine) return fail(ZK_ERR_STATE, "zk_batch_prove: another zk_batch_prove is running on this batch");
-    const uint32_t Q = b->queries;
+    const ProofFormat f = b->fmt;
+    const uint32_t Q = f.q, K = f.fold, stop = f.stop, G = f.groups();
     const int hash = b->hash;
-    const uint32_t K = b->fold;
-    const bool coset = b->coset;
-    const uint32_t stop = b->stop;
-    const size_t plen = proof_data_len_cap(b->log_n, b->log_b, Q, b->grind, K, coset, stop, b->cap);
+    const bool coset = f.coset;
+    const size_t plen = f.data_len();
     if (stride < plen) return fail(ZK_ERR_BUFFER, "zk_batch_prove: stride %zu < proof length %zu", stride, plen);
     if (b->single) {
         size_t len = 0;
@@ -644,7 +649,7 @@ int zk_batch_prove(zk_batch* b, uint8_t* proofs_out, size_t stride, uint8_t* sta
     HIPCHK(hipSetDevice(b->device));
     const size_t nb = b->batch, N = b->N, B = b->B;
     const uint32_t R = b->R, L = b->L, lb = b->lb;
-    const uint32_t Rp = R - stop;                                         // folded rounds (early stop: the groups are those of Rp)
+    const uint32_t Rp = f.rounds();                                       // folded rounds (early stop: the groups are those of Rp)
     const zk_dom* d = b->dom;
     std::vector<Channel> ch(nb);
     for (auto& c : ch) c.data.reserve(plen);
@@ -699,7 +704,7 @@ int zk_batch_prove(zk_batch* b, uint8_t* proofs_out, size_t stride, uint8_t* sta
     cap_lap(b->tree_cap[0], tc);
     if ((rc = bchal_upload(b))) return rc;
     if (coset) {                                                          // prover.rs:166-176, then the tree with group 0's cosets as leaves
-        const uint32_t s0 = fold_steps(Rp, K, 0);
+        const uint32_t s0 = f.steps(0);
         HIPCHK(launch_compose_batch(ca, lb, b->stream, nullptr));
         b->tree_steps[1] = (uint8_t)s0;
         HIPCHK(launch_merkle_build_coset_batch(b->d_layers + b->layer_off[1], L, s0, lb, b->d_trees + b->tree_off[1], b->stream, nullptr,
@@ -710,18 +715,19 @@ int zk_batch_prove(zk_batch* b, uint8_t* proofs_out, size_t stride, uint8_t* sta
         if ((rc = bpost(b, 1, L))) return rc;
     }
     const bool fused = K == 1 && !coset && !stop;                         // the fold inside the leaf hashing of its tree
-    for (uint32_t r0 = 0;;) {                                             // per group; tree 1 + r0 is the last one committed
+    for (uint32_t j = 0;; ++j) {                                          // per group; tree 1 + r0 is the last one committed
+        const uint32_t r0 = f.round0(j);
         if ((rc = wait_roots())) return rc;
         roots = bfinish_roots(b, 1 + r0, L - r0 - b->tree_steps[1 + r0]);   // tree 1 + r0: 2^(L - r0) values per proof, 2^tree_steps per leaf
         const uint32_t ce = b->tree_cap[1 + r0];                          // ... committed by its 2^ce digests of depth ce
         tc = timing ? now_us() : 0;
-        if (r0 == R) {
+        if (j == G) {
             b->pool->run(nb, 32, [&](size_t p) { commit_tree(p, roots, ce); });
             cap_lap(ce, tc);
             break;
         }
-        const uint32_t steps = Rp - r0 < K ? Rp - r0 : K, id = 1 + r0 + steps;
-        const bool stopped = stop && r0 + steps == Rp;                    // the layer the proofs stop at: no tree
+        const uint32_t steps = f.steps(j), id = f.tree_id(j + 1);
+        const bool stopped = stop && j + 1 == G;                          // the layer the proofs stop at: no tree
         // K = 1: the fold constant is reduced on the host; K > 1: the challenge goes up RAW and is reduced on the device
         const uint32_t winv_half = fused ? mulmod(invmod(powmod(d->shift, (uint64_t)1 << r0)), invmod(2)) : 0;
         b->pool->run(nb, 32, [&](size_t p) {
@@ -741,7 +747,7 @@ int zk_batch_prove(zk_batch* b, uint8_t* proofs_out, size_t stride, uint8_t* sta
             if ((rc = dom_fold_multi_batch(d, b->d_layers + b->layer_off[1 + r0], b->d_layers + b->layer_off[id], L - r0, r0, steps, &b->d_chal->c_mont,
                                            (uint32_t)(sizeof(BatchChal) / 4), b->d_work, (uint32_t)nb, b->stream, nullptr))) return rc;   // prover.rs:201-211, steps times
             // coset leaves: this tree is the one over the NEXT group's input, its leaves are that group's cosets (the last layer: one value)
-            const uint32_t leaf_steps = coset && r0 + steps < Rp ? (Rp - r0 - steps < K ? Rp - r0 - steps : K) : 0;
+            const uint32_t leaf_steps = f.slots_log(j + 1);
             for (uint32_t l = 2 + r0; l < id; ++l) b->skipped_trees |= (uint64_t)1 << l;
             if (stopped) {
                 for (uint32_t l = id; l <= R + 1; ++l) b->skipped_trees |= (uint64_t)1 << l;
@@ -756,11 +762,10 @@ int zk_batch_prove(zk_batch* b, uint8_t* proofs_out, size_t stride, uint8_t* sta
                                        bmail(b, id, L - r0 - steps), hash));      // prover.rs:214
             if ((rc = bpost(b, id, L - r0 - steps - leaf_steps))) return rc;
         }
-        r0 += steps;
     }
     lap("lde .. last roots");
     if (timing) fprintf(stderr, "[zk batch timing]   of which waiting for the device %.1f us\n", t_wait);
-    if (timing && b->cap) fprintf(stderr, "[zk batch timing]   of which host threads hashing cap commits %.1f us\n", t_caps);
+    if (timing && f.cap) fprintf(stderr, "[zk batch timing]   of which host threads hashing cap commits %.1f us\n", t_caps);
     const size_t ncoef = (size_t)1 << stop, frow = ncoef + 1;             // early stop: a row of h_final is (count, c_0 .. c_(2^stop - 1))
     if (stop) {
         // final polynomials: layer 1 + Rp holds 2^(stop + log_b) values per proof; every coefficient of degree >= 2^stop must be zero
@@ -794,13 +799,13 @@ int zk_batch_prove(zk_batch* b, uint8_t* proofs_out, size_t stride, uint8_t* sta
     const size_t nv = Q * b->per_proof_vals, ndg = Q * b->per_proof_digs;     // per proof, all its queries
     uint64_t* voff = b->h_goff;
     uint64_t* doff = b->h_goff + nb * nv;
-    if (b->grind) {                                                       // free terms, then the nonces of all proofs at once
+    if (b->fmt.grind) {                                                   // free terms, then the nonces of all proofs at once
         b->pool->run(nb, 16, [&](size_t p) { commit_final(p); });
         if ((rc = bgrind(b, ch))) return rc;
         lap("grind");
     }
     b->pool->run(nb, 16, [&](size_t p) {
-        if (!b->grind) commit_final(p);
+        if (!b->fmt.grind) commit_final(p);
         uint32_t qraw[kMaxQueries];
         for (uint32_t k = 0; k < Q; ++k) qraw[k] = ch[p].get_u32();       // prover.rs:263 (x Q)
         uint64_t* vo = voff + p * nv;
@@ -818,11 +823,11 @@ int zk_batch_prove(zk_batch* b, uint8_t* proofs_out, size_t stride, uint8_t* sta
             }
         };
         for (uint32_t k = 0; k < Q; ++k)                                  // layer l is stored proof-major: proof p's values at p * len
-            for_each_opening(b->log_n, b->log_b, K, (size_t)qraw[k] % (N - 2 * B), [&](uint32_t layer, uint32_t log_leaves, size_t leaf, uint32_t slots_log) {
+            f.for_each_opening((size_t)qraw[k] % (N - 2 * B), [&](uint32_t layer, uint32_t log_leaves, size_t leaf, uint32_t slots_log) {
                 for (size_t u = 0; u < ((size_t)1 << slots_log); ++u)     // the slots of one leaf (one value unless coset leaves)
                     *vo++ = b->layer_off[layer] + (p << (log_leaves + slots_log)) + leaf + (u << log_leaves);
                 add_path(layer, log_leaves, leaf);
-            }, coset, stop);
+            });
     });
     lap("queries + opening offsets");
     const size_t tv = nb * nv, td = nb * ndg;
@@ -837,19 +842,13 @@ int zk_batch_prove(zk_batch* b, uint8_t* proofs_out, size_t stride, uint8_t* sta
     b->pool->run(nb, 4, [&](size_t p) {
         const uint32_t* vals = b->h_gout + p * nv;
         const uint32_t* dw = b->h_gout + tv + p * ndg * 8;
-        std::vector<uint8_t> buf(Channel::group_bytes((size_t)1 << fold_steps(Rp, K, 0), L));   // one buffer per proof: the first group's tuple is the largest
+        std::vector<uint8_t> buf(Channel::group_bytes((size_t)1 << f.steps(0), L, false));   // one buffer per proof: the first group's tuple is the largest
         auto tuple = [&](size_t s, size_t pl, bool one_leaf) {
             ch[p].commit_group(buf.data(), s, pl, [&](size_t t) { return vals[t]; }, [&](size_t i, uint8_t* out) { digest_words_to_bytes(dw + 8 * i, out); },
                                one_leaf);
             vals += s; dw += 8 * (one_leaf ? 1 : s) * pl;
         };
-        for (uint32_t q = 0; q < Q; ++q) {
-            for (int k = 0; k < (coset ? 3 : 4); ++k) tuple(1, L - b->tree_cap[k < 3 ? 0 : 1], false);                 // prover.rs:274-277
-            for (uint32_t j = 0, G = fold_groups(Rp, K); j < G; ++j) {                                                 // prover.rs:280-289
-                const uint32_t steps = fold_steps(Rp, K, j);
-                tuple((size_t)1 << steps, L - j * K - (coset ? steps : 0) - b->tree_cap[1 + j * K], coset);            // paths end below the cap
-            }
-        }
+        for (uint32_t q = 0; q < Q; ++q) f.for_each_tuple(tuple);         // prover.rs:274-277, then per group prover.rs:280-289
         if (ch[p].data.size() != plen) { bad.store(1); return; }
         memcpy(proofs_out + p * stride, ch[p].data.data(), plen);          // channel.rs:34-36
         memcpy(states_out + 32 * p, ch[p].state, 32);

@@ -725,7 +725,7 @@ int prove(zk_shard* s, Channel& ch) {
     s->stats.chunked_layers = 0;
     reset_timing(s);
     committer_drop_pending(s->committer);
-    ch.data.reserve(ch.data.size() + proof_data_len(s->log_n, s->log_b, s->queries));
+    ch.data.reserve(ch.data.size() + ProofFormat{.log_n = s->log_n, .log_b = s->log_b, .q = s->queries}.data_len());
     if ((rc = do_lde(s))) return rc;                                              // prover.rs:60-70
     if (s->cp_from_f)                                                              // what every block's neighbour needs of my shard
         HIPCHK(launch_halo_pack(layer_ptr(s, 0), s->d_halo_send, L - 2 * lg, lg, (uint32_t)((2 * s->B) >> lg), s->stream));

@@ -47,8 +47,8 @@ struct Channel {
     // a group of a folded proof.  buf: group_bytes(s, plen) bytes of the caller's, reused from tuple to tuple; val(t) gives value
     // t, digest(i, out) writes digest i of the s * plen (path t starts at t * plen) as 32 bytes.
     // coset (coset leaves, below): the s values are the slots of ONE leaf, in slot order, and ONE path of plen digests follows them.
-    static size_t group_bytes(size_t s, size_t plen, bool coset = false) { return 4 * s + (coset ? 1 : s) * (8 + 32 * plen); }
-    template <class Val, class Dig> void commit_group(uint8_t* buf, size_t s, size_t plen, Val val, Dig digest, bool coset = false) {
+    static size_t group_bytes(size_t s, size_t plen, bool coset) { return 4 * s + (coset ? 1 : s) * (8 + 32 * plen); }
+    template <class Val, class Dig> void commit_group(uint8_t* buf, size_t s, size_t plen, Val val, Dig digest, bool coset) {
         uint8_t* p = buf;
         for (size_t t = 0; t < s; ++t, p += 4) {
             const uint32_t v = val(t);
@@ -62,13 +62,13 @@ struct Channel {
     }
     // ... from values and paths that already lie as bytes (the sharded prover's decommitment): s = 1 and s = 2
     void commit_val_path(uint32_t val, const uint8_t* path, size_t plen) {
-        std::vector<uint8_t> b(group_bytes(1, plen));
-        commit_group(b.data(), 1, plen, [&](size_t) { return val; }, [&](size_t i, uint8_t* out) { memcpy(out, path + 32 * i, 32); });
+        std::vector<uint8_t> b(group_bytes(1, plen, false));
+        commit_group(b.data(), 1, plen, [&](size_t) { return val; }, [&](size_t i, uint8_t* out) { memcpy(out, path + 32 * i, 32); }, false);
     }
     void commit_pair_paths(uint32_t v0, uint32_t v1, const uint8_t* p0, const uint8_t* p1, size_t plen) {
-        std::vector<uint8_t> b(group_bytes(2, plen));
+        std::vector<uint8_t> b(group_bytes(2, plen, false));
         commit_group(b.data(), 2, plen, [&](size_t t) { return t ? v1 : v0; },
-                     [&](size_t i, uint8_t* out) { memcpy(out, i < plen ? p0 + 32 * i : p1 + 32 * (i - plen), 32); });
+                     [&](size_t i, uint8_t* out) { memcpy(out, i < plen ? p0 + 32 * i : p1 + 32 * (i - plen), 32); }, false);
     }
 };
 
@@ -100,87 +100,103 @@ struct Channel {
 // degree bound of the final polynomial holds by construction (2^D coefficients ARE a polynomial of degree < 2^D).
 constexpr uint32_t kMaxFoldLog = 3;
 constexpr uint32_t kMaxStopLog = 8, kMaxStopLayerLog = 12;   // the stopped layer (2^(D + log_b) values) fits one workgroup's LDS
+constexpr uint32_t kMaxGrindBits = 32;
 // D = 0, or 1 <= D <= 8 with at least one folded round and a stopped layer of at most 2^12 values
 inline bool stop_ok(uint32_t log_n, uint32_t log_b, uint32_t stop) {
     return stop == 0 || (stop <= kMaxStopLog && stop + 1 <= log_n && stop + log_b <= kMaxStopLayerLog);
 }
-inline uint32_t fold_groups(uint32_t R, uint32_t fold) { return (R + fold - 1) / fold; }
-inline uint32_t fold_steps(uint32_t R, uint32_t fold, uint32_t group) { const uint32_t r0 = group * fold; return R - r0 < fold ? R - r0 : fold; }
 // Leaf t of the coset a group with `steps` rounds opens in its input layer of 2^log_len values, for the query index x.
 inline size_t coset_leaf(size_t x, uint32_t log_len, uint32_t steps, uint32_t t) {
     const size_t len = (size_t)1 << log_len;
     return (x % len + t * (len >> steps)) % len;
 }
-// The openings of one query in wire order, for x = query raw % (N - 2B): f at x, x + B, x + 2B (layer 0) and cp at x (layer 1),
-// one tuple each (prover.rs:266-277), then per group the s coset leaves of its input layer 1 + r0, one tuple per group.
-// An opening is one LEAF and its path: open(layer id, log2 of the tree's leaf count = digests of the path, leaf index, slots_log);
-// the leaf holds the 2^slots_log values layer[leaf + u 2^(log2 leaf count)], u < 2^slots_log (0: a one-value leaf).
-// coset: no cp opening, and a group is one leaf of s slots.
-// stop: only the groups of the log_n - stop folded rounds are opened.
-template <class Open> inline void for_each_opening(uint32_t log_n, uint32_t log_b, uint32_t fold, size_t x, Open open, bool coset = false, uint32_t stop = 0) {
-    const uint32_t L = log_n + log_b, Rp = log_n - stop, G = fold_groups(Rp, fold);
-    const size_t B = (size_t)1 << log_b;
-    open(0u, L, x, 0u); open(0u, L, x + B, 0u); open(0u, L, x + 2 * B, 0u);
-    if (!coset) open(1u, L, x, 0u);
-    for (uint32_t j = 0; j < G; ++j) {
-        const uint32_t r0 = j * fold, steps = fold_steps(Rp, fold, j);
-        if (coset) open(1u + r0, L - r0 - steps, x % ((size_t)1 << (L - r0 - steps)), steps);
-        else for (uint32_t t = 0; t < (1u << steps); ++t) open(1u + r0, L - r0, coset_leaf(x, L - r0, steps, t), 0u);
-    }
-}
-// fold must be in 1..kMaxFoldLog and stop_ok(log_n, log_b, stop) must hold (the callers check both).
-inline size_t proof_data_len(uint32_t log_n, uint32_t log_b, uint32_t q = 1, uint32_t grind = 0, uint32_t fold = 1, bool coset = false, uint32_t stop = 0) {
-    const uint32_t Rp = log_n - stop;
-    const size_t L = log_n + log_b, G = fold_groups(Rp, fold);
-    size_t per_query = 4 + (coset ? 3 : 4) * Channel::group_bytes(1, L);
-    for (uint32_t j = 0; j < G; ++j) {
-        const size_t steps = fold_steps(Rp, fold, j);
-        per_query += Channel::group_bytes((size_t)1 << steps, L - (size_t)j * fold - (coset ? steps : 0), coset);
-    }
-    // stop > 0: the last root and the free term give way to the 2^stop coefficients
-    const size_t head = stop ? 32 + 12 + 32 + (G - 1) * 36 + 4 + ((size_t)4 << stop) : 32 + 12 + 32 + G * 36 + 4;
-    return head + (grind ? 8 : 0) + (size_t)q * per_query;
-}
-
-// ---- Merkle caps ----------------------------------------------------------------------------------------------
-// cap = c in 0..kMaxCapLog: a tree over 2^lg leaves (coset leaves count as one) is committed by the 2^ce digests of depth
-// ce = min(c, lg - 1) -- heap nodes 2^ce - 1 .. 2^(ce+1) - 2, left to right, 32 bytes each, ONE commit -- in place of its root, and a
-// path into it carries the lg - ce siblings from the leaf up to depth ce + 1 (the u64 count in front is lg - ce).  The verifier hashes
-// upward lg - ce times and compares with cap entry leaf >> (lg - ce).  ce = 0 is the root: a cap-0 proof is the format above, byte for
-// byte.  Every committed tree takes part: f, the tree over every group's input layer, and the never-opened last tree when stop = 0.
-// A path that misses its cap entry gets the check number it gets for missing the root.  verify_proof tests only the entries a path
-// lands in; a changed entry that no path lands in is caught by verify_transcript alone (the challenge after it, as for a changed root).
+// cap = c in 0..kMaxCapLog, Merkle caps: a tree over 2^lg leaves (coset leaves count as one) is committed by the 2^ce
+// digests of depth ce = min(c, lg - 1) -- heap nodes 2^ce - 1 .. 2^(ce+1) - 2, left to right, 32 bytes each, ONE commit -- in place of
+// its root, and a path into it carries the lg - ce siblings from the leaf up to depth ce + 1 (the u64 count in front is lg - ce).  The
+// verifier hashes upward lg - ce times and compares with cap entry leaf >> (lg - ce).  ce = 0 is the root: a cap-0 proof is the format
+// above, byte for byte.  Every committed tree takes part: f, the tree over every group's input layer, and the never-opened last tree
+// when stop = 0.  A path that misses its cap entry gets the check number it gets for missing the root.  verify_proof tests only the
+// entries a path lands in; a changed entry that no path lands in is caught by verify_transcript alone (the challenge after it, as for a
+// changed root).
 constexpr uint32_t kMaxCapLog = 8;
 inline uint32_t cap_eff(uint32_t cap, uint32_t lg) { return cap < lg - 1 ? cap : lg - 1; }   // lg >= 1 for every committed tree
-// log2 of the leaf count of the tree over the input layer of group j < G (tree id 1 + jK), or, for j = G, of the last layer's tree
-inline uint32_t group_tree_log(uint32_t log_n, uint32_t log_b, uint32_t fold, bool coset, uint32_t stop, uint32_t j) {
-    const uint32_t Rp = log_n - stop, L = log_n + log_b, G = fold_groups(Rp, fold);
-    if (j >= G) return L - Rp;
-    return L - j * fold - (coset ? fold_steps(Rp, fold, j) : 0);
-}
-// proof_data_len, plus 32 (2^ce - 1) in the head per committed tree, minus 32 ce per path into it
-inline size_t proof_data_len_cap(uint32_t log_n, uint32_t log_b, uint32_t q, uint32_t grind, uint32_t fold, bool coset, uint32_t stop, uint32_t cap) {
-    const size_t len = proof_data_len(log_n, log_b, q, grind, fold, coset, stop);
-    if (!cap) return len;
-    const uint32_t Rp = log_n - stop, G = fold_groups(Rp, fold);
-    const uint32_t cf = cap_eff(cap, log_n + log_b);
-    size_t head = (size_t)32 * (((size_t)1 << cf) - 1), per_query = (size_t)3 * 32 * cf;
-    for (uint32_t j = 0; j <= G; ++j) {
-        if (j == G && stop) break;                            // a stopped proof has no tree over its last layer
-        const uint32_t ce = cap_eff(cap, group_tree_log(log_n, log_b, fold, coset, stop, j));
-        head += (size_t)32 * (((size_t)1 << ce) - 1);
-        if (j == G) break;
-        const size_t paths = (coset ? 1 : (size_t)1 << fold_steps(Rp, fold, j)) + (j == 0 && !coset ? 1 : 0);   // + cp(x)
-        per_query += paths * 32 * ce;
+
+// One proof format: the settings above and everything that follows from them.  The Merkle hash and public_last are not part of it.
+// The wire order is written down twice, here and nowhere else: for_each_head (the header) and for_each_tuple (one query); lengths,
+// provers and verifiers walk those.  A new setting is a field and a line in a walk.
+struct ProofFormat {
+    uint32_t log_n = 0, log_b = 0, q = 1, grind = 0, fold = 1;
+    bool coset = false;
+    uint32_t stop = 0, cap = 0;
+
+    // what verify_proof and verify_transcript take (they answer -1 to anything else); every member below assumes it
+    bool ok() const {
+        return log_n >= 2 && log_b >= 1 && log_n + log_b <= 30 && q >= 1 && q <= 64 && grind <= kMaxGrindBits && fold >= 1 && fold <= kMaxFoldLog &&
+               stop_ok(log_n, log_b, stop) && cap <= kMaxCapLog;
     }
-    return len + head - (size_t)q * per_query;
-}
+    // ---- geometry.  Group j < G folds the rounds round0(j) .. round0(j) + steps(j) - 1; tree j is the one over its INPUT layer.
+    // j = G: the last layer (round0 = rounds, steps = 0), whose tree has one-value leaves and exists only when stop = 0.
+    uint32_t L() const { return log_n + log_b; }
+    uint32_t rounds() const { return log_n - stop; }                         // the folded rounds R'
+    uint32_t groups() const { return (rounds() + fold - 1) / fold; }
+    uint32_t round0(uint32_t j) const { return j * fold < rounds() ? j * fold : rounds(); }
+    uint32_t steps(uint32_t j) const { return rounds() - round0(j) < fold ? rounds() - round0(j) : fold; }
+    uint32_t tree_id(uint32_t j) const { return 1 + round0(j); }             // layer and tree ids: 0 = f, 1 = cp, 1 + r = after r rounds
+    uint32_t slots_log(uint32_t j) const { return coset ? steps(j) : 0; }    // log2 of the values per leaf of tree j
+    uint32_t tree_log(uint32_t j) const { return L() - round0(j) - slots_log(j); }   // log2 of its leaf count
+    bool last_tree() const { return stop == 0; }
+    uint32_t f_cap() const { return cap_eff(cap, L()); }                     // the depth a tree is committed at ...
+    uint32_t tree_cap(uint32_t j) const { return cap_eff(cap, tree_log(j)); }
+    size_t f_path() const { return (size_t)L() - f_cap(); }                  // ... and the digests of a path into it
+    size_t tree_path(uint32_t j) const { return (size_t)tree_log(j) - tree_cap(j); }
+
+    // ---- the header in wire order: fn(what, j, bytes) -> bool, false ends the walk (and is returned).  kAlphas, kBeta and kRaws are
+    // challenges of 4 bytes each (3, 1 and q of them), everything else is ONE commit.  kTree j: the commitment of tree j.
+    enum Head { kFTree, kAlphas, kTree, kBeta, kFinal, kNonce, kRaws };
+    template <class Fn> bool for_each_head(Fn fn) const {
+        const uint32_t G = groups();
+        if (!fn(kFTree, 0u, (size_t)32 << f_cap()) || !fn(kAlphas, 0u, (size_t)12) || !fn(kTree, 0u, (size_t)32 << tree_cap(0))) return false;
+        for (uint32_t j = 0; j < G; ++j) {
+            if (!fn(kBeta, j, (size_t)4)) return false;                      // group j's challenge, then the tree over its output
+            if ((j + 1 < G || last_tree()) && !fn(kTree, j + 1, (size_t)32 << tree_cap(j + 1))) return false;
+        }
+        if (!fn(kFinal, 0u, stop ? (size_t)4 << stop : (size_t)4)) return false;   // the free term, or the 2^stop coefficients
+        if (grind && !fn(kNonce, 0u, (size_t)8)) return false;
+        return fn(kRaws, 0u, (size_t)4 * q);
+    }
+    // ---- the tuples of one query in wire order: fn(s values, digests per path, one_leaf) as Channel::commit_group takes them.
+    // f(x), f(gx), f(g^2 x) and, with one-value leaves, cp(x); then one tuple per group.
+    template <class Fn> void for_each_tuple(Fn fn) const {
+        for (int i = 0; i < (coset ? 3 : 4); ++i) fn((size_t)1, i < 3 ? f_path() : tree_path(0), false);
+        for (uint32_t j = 0, G = groups(); j < G; ++j) fn((size_t)1 << steps(j), tree_path(j), coset);
+    }
+    // ---- the openings of one query in the same order, for x = query raw % (N - 2B): f at x, x + B, x + 2B (layer 0) and cp at x
+    // (layer 1) (prover.rs:266-277), then per group the s coset leaves of its input layer.  An opening is one LEAF and its path:
+    // open(layer id, log2 of the tree's leaf count, leaf index, slots_log); the leaf holds the 2^slots_log values
+    // layer[leaf + u 2^(log2 leaf count)], u < 2^slots_log (0: a one-value leaf).  Both provers rely on this leaf order.
+    template <class Open> void for_each_opening(size_t x, Open open) const {
+        const size_t B = (size_t)1 << log_b;
+        open(0u, L(), x, 0u); open(0u, L(), x + B, 0u); open(0u, L(), x + 2 * B, 0u);
+        if (!coset) open(1u, L(), x, 0u);
+        for (uint32_t j = 0, G = groups(); j < G; ++j) {
+            const uint32_t lg = tree_log(j), st = steps(j);
+            if (coset) open(tree_id(j), lg, x % ((size_t)1 << lg), st);
+            else for (uint32_t t = 0; t < (1u << st); ++t) open(tree_id(j), lg, coset_leaf(x, lg, st, t), 0u);
+        }
+    }
+    // bytes of a proof: the header, then q queries
+    size_t data_len() const {
+        size_t head = 0, per_query = 0;
+        for_each_head([&](Head, uint32_t, size_t bytes) { head += bytes; return true; });
+        for_each_tuple([&](size_t s, size_t plen, bool one_leaf) { per_query += Channel::group_bytes(s, plen, one_leaf); });
+        return head + (size_t)q * per_query;
+    }
+};
 
 // ---- grinding (DESIGN.md "Grinding"; the reference has none) -------------------------------------------------------------
 // After the free term, with channel state S, the prover commits le64(w) for the smallest w >= 0 such that SHA-256(S || le64(w))
 // starts with g zero bits (MSB-first from byte 0, as get_u32 reads the state).  The commit itself computes that hash, so the
 // bits are those of the channel state right after the nonce is committed.
-constexpr uint32_t kMaxGrindBits = 32;
 constexpr uint64_t kGrindLimit = (uint64_t)1 << 44;      // a search gives up after this many nonces
 // Digest word 0 of SHA-256(state || le64(w)): one compression of a single block.
 inline uint32_t grind_word0(const uint8_t state[32], uint64_t w) {
@@ -269,16 +285,13 @@ inline void compute_root_from_path(uint32_t element, size_t index, const uint8_t
 // coefficients, each reduced % P on reading, as raw challenges are.
 // cap > 0 (Merkle caps, above): every root of the header is 2^ce digests, the path lengths expected are lg - ce, and a path is
 // compared with the cap entry it lands in, under the check number it has for the root.  A proof of another length: -1.
-inline int verify_proof(const uint8_t* data, size_t len, uint32_t log_n, uint32_t log_b, uint32_t public_last, int hash = 0, uint32_t q = 1,
-                        uint32_t grind = 0, uint32_t fold = 1, bool coset = false, uint32_t stop = 0, uint32_t cap = 0) {
-    if (log_n < 2 || log_b < 1 || log_n + log_b > 30 || q < 1 || q > 64 || grind > kMaxGrindBits || fold < 1 || fold > kMaxFoldLog) return -1;
-    if (!stop_ok(log_n, log_b, stop)) return -1;
-    if (cap > kMaxCapLog) return -1;
-    if ((stop || cap) && len != proof_data_len_cap(log_n, log_b, q, grind, fold, coset, stop, cap)) return -1;   // a stopped or capped proof of another length: -1, strict or not
-    const uint32_t Rp = log_n - stop;
-    const int nf = coset ? 3 : 4;                            // f(x), f(gx), f(g^2 x) and, with one-value leaves, cp(x)
-    const size_t n = (size_t)1 << log_n, B = (size_t)1 << log_b, N = n << log_b, L = log_n + log_b;
-    const uint32_t G = fold_groups(Rp, fold);
+inline int verify_proof(const uint8_t* data, size_t len, const ProofFormat& fmt, uint32_t public_last, int hash) {
+    if (!fmt.ok()) return -1;
+    if ((fmt.stop || fmt.cap) && len != fmt.data_len()) return -1;   // a stopped or capped proof of another length: -1, strict or not
+    const bool coset = fmt.coset;
+    const uint32_t nf = coset ? 3 : 4;                       // f(x), f(gx), f(g^2 x) and, with one-value leaves, cp(x)
+    const size_t n = (size_t)1 << fmt.log_n, B = (size_t)1 << fmt.log_b, N = n << fmt.log_b;
+    const uint32_t L = fmt.L(), G = fmt.groups();
     const uint8_t* p = data;
     size_t left = len;
     bool bad = false;
@@ -299,38 +312,44 @@ inline int verify_proof(const uint8_t* data, size_t len, uint32_t log_n, uint32_
         plen = (size_t)c;
         return take(32 * plen);
     };
-    // proof.rs:20-46
-    uint32_t ce[41];                                         // ce[j]: the effective cap of roots[j]'s tree; cf: of f's
-    const uint32_t cf = cap_eff(cap, (uint32_t)L);
-    for (uint32_t j = 0; j <= G; ++j) ce[j] = cap_eff(cap, group_tree_log(log_n, log_b, fold, coset, stop, j));
-    const uint8_t* f_root = take((size_t)32 << cf);
-    uint32_t alpha[3] = {take32(), take32(), take32()};
-    const uint8_t* roots[41]; uint32_t betas[40];            // roots[j]: the tree over the INPUT layer of group j (roots[G]: the last layer)
-    roots[0] = take((size_t)32 << ce[0]);
-    for (uint32_t j = 0; j < G; ++j) { betas[j] = take32(); roots[j + 1] = (stop && j + 1 == G) ? nullptr : take((size_t)32 << ce[j + 1]); }
-    const uint8_t* coefs = stop ? take((size_t)4 << stop) : nullptr;
-    uint32_t free_term = stop ? 0 : take32();
-    if (grind) take(8);                                   // the nonce
-    uint32_t test_raws[64];
-    for (uint32_t k = 0; k < q; ++k) test_raws[k] = take32();
-    const uint32_t g = root_of_unity(log_n), h = root_of_unity((uint32_t)L);
-    for (uint32_t qk = 0; qk < q; ++qk) {
-        const uint32_t test_raw = test_raws[qk];
-        uint32_t fv[4]; const uint8_t* fp[4]; size_t fpl[4] = {0, 0, 0, 0};
-        for (int i = 0; i < nf; ++i) { fv[i] = take32(); fp[i] = take_path(fpl[i]); }
-        uint32_t lv[40][8]; const uint8_t* lp[40][8]; size_t lpl[40][8];
-        for (uint32_t j = 0; j < G; ++j) {
-            const uint32_t s = 1u << fold_steps(Rp, fold, j);
-            for (uint32_t t = 0; t < s; ++t) lv[j][t] = take32();
-            for (uint32_t t = 0; t < (coset ? 1u : s); ++t) { lpl[j][t] = 0; lp[j][t] = take_path(lpl[j][t]); }
+    auto le32 = [](const uint8_t* r) { return (uint32_t)r[0] | ((uint32_t)r[1] << 8) | ((uint32_t)r[2] << 16) | ((uint32_t)r[3] << 24); };
+    // proof.rs:20-46.  roots[j]: the commitment of the tree over the INPUT layer of group j (roots[G]: the last layer)
+    const uint8_t *f_root = nullptr, *alphas = nullptr, *final_term = nullptr, *raws = nullptr, *roots[41] = {nullptr}, *betas[40];
+    fmt.for_each_head([&](ProofFormat::Head what, uint32_t j, size_t bytes) {
+        const uint8_t* r = take(bytes);
+        switch (what) {
+            case ProofFormat::kFTree: f_root = r; break;
+            case ProofFormat::kAlphas: alphas = r; break;
+            case ProofFormat::kTree: roots[j] = r; break;
+            case ProofFormat::kBeta: betas[j] = r; break;
+            case ProofFormat::kFinal: final_term = r; break;   // the free term, or the coefficients
+            case ProofFormat::kNonce: break;
+            case ProofFormat::kRaws: raws = r; break;
         }
+        return true;
+    });
+    if (bad) return -1;
+    const uint32_t alpha[3] = {le32(alphas), le32(alphas + 4), le32(alphas + 8)};
+    const uint32_t g = root_of_unity(fmt.log_n), h = root_of_unity(L);
+    for (uint32_t qk = 0; qk < fmt.q; ++qk) {
+        uint32_t fv[4]; const uint8_t* fp[4]; size_t fpl[4] = {0, 0, 0, 0};
+        uint32_t lv[40][8]; const uint8_t* lp[40][8]; size_t lpl[40][8];
+        uint32_t i = 0;                                      // tuple i: an f / cp tuple, then group i - nf
+        fmt.for_each_tuple([&](size_t s, size_t, bool one_leaf) {
+            uint32_t* v = i < nf ? &fv[i] : lv[i - nf];
+            const uint8_t** path = i < nf ? &fp[i] : lp[i - nf];
+            size_t* plen = i < nf ? &fpl[i] : lpl[i - nf];
+            for (size_t t = 0; t < s; ++t) v[t] = take32();
+            for (size_t t = 0; t < (one_leaf ? 1 : s); ++t) { plen[t] = 0; path[t] = take_path(plen[t]); }
+            ++i;
+        });
         if (bad) return -1;
         // proof.rs:49-60
-        const size_t tp = (size_t)test_raw % (N - 2 * B);
+        const size_t tp = (size_t)le32(raws + 4 * qk) % (N - 2 * B);
         // value t of group j: as sent, or slot (rot + t) % s of the group's leaf
         auto group_val = [&](uint32_t j, uint32_t t) -> uint32_t {
             if (!coset) return lv[j][t];
-            const uint32_t steps = fold_steps(Rp, fold, j), lg = (uint32_t)L - j * fold;
+            const uint32_t steps = fmt.steps(j), lg = L - fmt.round0(j);
             const size_t rot = (tp & (((size_t)1 << lg) - 1)) >> (lg - steps);
             return lv[j][(rot + t) & ((1u << steps) - 1u)];
         };
@@ -353,8 +372,8 @@ inline int verify_proof(const uint8_t* data, size_t len, uint32_t log_n, uint32_
             compute_root_from_coset(slots, s, idx & (((size_t)1 << plen) - 1), path, plen, root, hash);
             return memcmp(root, entries + 32 * (idx >> plen), 32) != 0;
         };
-        for (int i = 0; i < 3; ++i) if (fpl[i] != L - cf) return -3;
-        if (!coset && fpl[3] != L - ce[0]) return -3;
+        for (int k = 0; k < 3; ++k) if (fpl[k] != fmt.f_path()) return -3;
+        if (!coset && fpl[3] != fmt.tree_path(0)) return -3;
         // proof.rs:80-95
         if (misses(&fv[0], 1, tp, fp[0], fpl[0], f_root)) return -4;
         if (misses(&fv[1], 1, tp + B, fp[1], fpl[1], f_root)) return -5;
@@ -363,12 +382,12 @@ inline int verify_proof(const uint8_t* data, size_t len, uint32_t log_n, uint32_
         // proof.rs:101-126: the s opened values of a group folded pairwise (t with t + s/2, then again)
         const uint32_t inv2 = invmod(2);
         for (uint32_t j = 0; j < G; ++j) {
-            const uint32_t r0 = j * fold, steps = fold_steps(Rp, fold, j);
+            const uint32_t r0 = fmt.round0(j), steps = fmt.steps(j);
             uint32_t cnt = 1u << steps, v[8];
             for (uint32_t t = 0; t < cnt; ++t) v[t] = group_val(j, t) % P;
             uint32_t xk = powmod(x, (uint64_t)1 << r0);                        // the point of index tp % len in layer r0
             uint32_t om = powmod(h, (uint64_t)N >> steps);                     // index + len / s: the point times a primitive s-th root of unity
-            uint32_t bk = betas[j] % P;
+            uint32_t bk = le32(betas[j]) % P;
             for (uint32_t k = 0; k < steps; ++k) {
                 cnt >>= 1;
                 uint32_t pt = xk;
@@ -380,29 +399,24 @@ inline int verify_proof(const uint8_t* data, size_t len, uint32_t log_n, uint32_
                 }
                 xk = mulmod(xk, xk); om = mulmod(om, om); bk = mulmod(bk, bk);
             }
-            uint32_t expect = (j + 1 < G) ? group_val(j + 1, 0) : free_term;
-            if (stop && j + 1 == G) {                                          // p at the point of the stopped layer, x^(2^R')
-                const uint32_t xs = powmod(x, (uint64_t)1 << Rp);
-                expect = 0;
-                for (size_t k = (size_t)1 << stop; k-- > 0; ) {
-                    const uint8_t* cb = coefs + 4 * k;
-                    const uint32_t ck = ((uint32_t)cb[0] | ((uint32_t)cb[1] << 8) | ((uint32_t)cb[2] << 16) | ((uint32_t)cb[3] << 24)) % P;
-                    expect = add(mulmod(expect, xs), ck);
-                }
+            uint32_t expect = (j + 1 < G) ? group_val(j + 1, 0) : fmt.stop ? 0 : le32(final_term);
+            if (fmt.stop && j + 1 == G) {                                      // p at the point of the stopped layer, x^(2^R')
+                const uint32_t xs = powmod(x, (uint64_t)1 << fmt.rounds());
+                for (size_t k = (size_t)1 << fmt.stop; k-- > 0; ) expect = add(mulmod(expect, xs), le32(final_term + 4 * k) % P);
             }
             if (v[0] != expect) return -(int)(100 + j);
         }
         // proof.rs:129-148
         for (uint32_t j = 0; j < G; ++j) {
-            const uint32_t r0 = j * fold, steps = fold_steps(Rp, fold, j), s = 1u << steps;
+            const uint32_t lg = fmt.tree_log(j), steps = fmt.steps(j), s = 1u << steps;
             if (coset) {
-                if (lpl[j][0] != L - r0 - steps - ce[j]) return -(int)(200 + j);
-                if (misses(lv[j], s, tp & (((size_t)1 << (L - r0 - steps)) - 1), lp[j][0], lpl[j][0], roots[j])) return -(int)(300 + j);
+                if (lpl[j][0] != fmt.tree_path(j)) return -(int)(200 + j);
+                if (misses(lv[j], s, tp & (((size_t)1 << lg) - 1), lp[j][0], lpl[j][0], roots[j])) return -(int)(300 + j);
                 continue;
             }
-            for (uint32_t t = 0; t < s; ++t) if (lpl[j][t] != L - r0 - ce[j]) return -(int)(200 + j);
+            for (uint32_t t = 0; t < s; ++t) if (lpl[j][t] != fmt.tree_path(j)) return -(int)(200 + j);
             for (uint32_t t = 0; t < s; ++t)
-                if (misses(&lv[j][t], 1, coset_leaf(tp, (uint32_t)L - r0, steps, t), lp[j][t], lpl[j][t], roots[j])) return t == 0 ? -(int)(300 + j) : -(int)(400 + j);
+                if (misses(&lv[j][t], 1, coset_leaf(tp, lg, steps, t), lp[j][t], lpl[j][t], roots[j])) return t == 0 ? -(int)(300 + j) : -(int)(400 + j);
         }
     }
     if (left != 0) return -8;
@@ -419,18 +433,11 @@ inline int verify_proof(const uint8_t* data, size_t len, uint32_t log_n, uint32_
 // bits (checked after the betas and before the first query challenge; it does not advance k) / -1999 for the state.
 // stop > 0: 3 + G' + q challenges; the coefficients are one commit, in the place of the last root and the free term.
 // cap > 0: every root commit is one commit of the tree's 2^ce digests, and a tuple's paths are ce digests shorter.
-inline int verify_transcript(const uint8_t* data, size_t len, const uint8_t state[32], uint32_t log_n, uint32_t log_b, uint32_t q = 1,
-                             uint32_t grind = 0, uint32_t fold = 1, bool coset = false, uint32_t stop = 0, uint32_t cap = 0) {
-    if (log_n < 2 || log_b < 1 || log_n + log_b > 30 || grind > kMaxGrindBits || fold < 1 || fold > kMaxFoldLog) return -1;
-    if (!stop_ok(log_n, log_b, stop)) return -1;
-    const size_t L = log_n + log_b;
-    const uint32_t Rp = log_n - stop, G = fold_groups(Rp, fold);
-    if (cap > kMaxCapLog || q < 1 || q > 64 || len != proof_data_len_cap(log_n, log_b, q, grind, fold, coset, stop, cap)) return -1;
-    const uint32_t cf = cap_eff(cap, (uint32_t)L);
-    auto ce = [&](uint32_t j) { return cap_eff(cap, group_tree_log(log_n, log_b, fold, coset, stop, j)); };
+inline int verify_transcript(const uint8_t* data, size_t len, const uint8_t state[32], const ProofFormat& fmt) {
+    if (!fmt.ok() || len != fmt.data_len()) return -1;
     Channel ch;
     const uint8_t* p = data;
-    int k = 0;
+    int k = 0, rc = 0;
     auto commit = [&](size_t n) { ch.commit_bytes(p, n); p += n; };
     auto challenge = [&]() -> bool {
         uint32_t expect = ((uint32_t)ch.state[0] << 24) | ((uint32_t)ch.state[1] << 16) | ((uint32_t)ch.state[2] << 8) | ch.state[3];
@@ -440,27 +447,20 @@ inline int verify_transcript(const uint8_t* data, size_t len, const uint8_t stat
         commit(4);
         return true;
     };
-    commit((size_t)32 << cf);                               // f_eval root (cap: its 2^ce digests, one commit, here and below)
-    for (int i = 0; i < 3; ++i) if (!challenge()) return -(1000 + k);
-    commit((size_t)32 << ce(0));                            // cp root
-    for (uint32_t j = 0; j < G; ++j) {
-        if (!challenge()) return -(1000 + k);               // the group's beta
-        if (!stop || j + 1 < G) commit((size_t)32 << ce(j + 1));   // root of the group's output
-    }
-    commit(stop ? (size_t)4 << stop : 4);                   // free term, or the final polynomial's coefficients
-    if (grind) {                                            // nonce: the commit is SHA-256(S || le64(w))
-        commit(8);
-        const uint32_t w0 = ((uint32_t)ch.state[0] << 24) | ((uint32_t)ch.state[1] << 16) | ((uint32_t)ch.state[2] << 8) | ch.state[3];
-        if (!grind_word_ok(w0, grind)) return -1998;
-    }
-    for (uint32_t j = 0; j < q; ++j) if (!challenge()) return -(1000 + k);   // queries
-    for (uint32_t j = 0; j < q; ++j) {
-        for (int i = 0; i < (coset ? 3 : 4); ++i) commit(Channel::group_bytes(1, L - (i < 3 ? cf : ce(0))));
-        for (uint32_t gi = 0; gi < G; ++gi) {
-            const size_t steps = fold_steps(Rp, fold, gi);
-            commit(Channel::group_bytes((size_t)1 << steps, L - (size_t)gi * fold - (coset ? steps : 0) - ce(gi), coset));
+    fmt.for_each_head([&](ProofFormat::Head what, uint32_t, size_t bytes) {
+        if (what == ProofFormat::kAlphas || what == ProofFormat::kBeta || what == ProofFormat::kRaws) {
+            for (size_t i = 0; i < bytes; i += 4) if (!challenge()) { rc = -(1000 + k); return false; }
+            return true;
         }
-    }
+        commit(bytes);                                      // a root (cap: its 2^ce digests), the free term or the coefficients, the nonce
+        if (what == ProofFormat::kNonce) {                  // the commit is SHA-256(S || le64(w))
+            const uint32_t w0 = ((uint32_t)ch.state[0] << 24) | ((uint32_t)ch.state[1] << 16) | ((uint32_t)ch.state[2] << 8) | ch.state[3];
+            if (!grind_word_ok(w0, fmt.grind)) { rc = -1998; return false; }
+        }
+        return true;
+    });
+    if (rc) return rc;
+    for (uint32_t j = 0; j < fmt.q; ++j) fmt.for_each_tuple([&](size_t s, size_t plen, bool one_leaf) { commit(Channel::group_bytes(s, plen, one_leaf)); });
     if (memcmp(ch.state, state, 32)) return -1999;
     return 0;
 }

@@ -72,7 +72,7 @@ __constant__ FieldHashConsts64 g_vfh_consts64;
 constexpr int32_t kNoFailure = 0x7f7f7f7f;   // the memset pattern of the per-proof key: above every order key
 constexpr uint32_t kVerifyThreads = 64;      // one wave per workgroup: the proofs of a batch spread over as many SIMDs as possible
 
-// Where the fields of a proof sit (in 32-bit words; every field of the wire format is 4-byte aligned and proof_data_len is a
+// Where the fields of a proof sit (in 32-bit words; every field of the wire format is 4-byte aligned and ProofFormat::data_len is a
 // multiple of 4), for the fixed layout.
 struct VerifyArgs {
     const uint32_t* proofs;     // [count][words]
@@ -831,11 +831,8 @@ int32_t coset_key_to_check(int32_t key, uint32_t G) {
 
 struct zk_verifier {
     int device = 0;
-    uint32_t log_n = 0, log_b = 0, queries = 1, grind = 0, fold = 1;
+    zk::ProofFormat fmt;                               // the format of the proofs (transcript.hpp), one field per setter
     int hash = ZK_HASH_SHA256;
-    bool coset = false;                                // proofs with coset leaves (zk_verifier_set_coset_leaves)
-    uint32_t stop = 0;                                 // early stop D (zk_verifier_set_fri_stop): the proofs carry 2^D coefficients
-    uint32_t cap_log = 0;                              // Merkle caps c (zk_verifier_set_merkle_cap): every tree is committed at depth min(c, lg - 1)
     hipStream_t stream = nullptr, tstream = nullptr;   // paths + algebra; transcript (runs beside them)
     hipEvent_t ev_in = nullptr, ev_t = nullptr;
     uint8_t* d_buf = nullptr;                          // proofs, public_last, states, then the three per-proof results
@@ -868,10 +865,10 @@ int verifier_reserve(zk_verifier* v, size_t chunk, size_t len) {
 // One chunk of proofs: stage, copy in, three kernels, copy the per-proof results out, decide each proof.
 int verifier_chunk(zk_verifier* v, const uint8_t* proofs, size_t stride, size_t count, const uint8_t* states, const uint32_t* public_last,
                    int32_t* checks_out, size_t len) {
-    const uint32_t log_n = v->log_n, log_b = v->log_b, q = v->queries, D = v->stop, L = log_n + log_b;
-    const uint32_t R = log_n - D;                      // the folded rounds (early stop: R', and G' groups below)
-    const uint32_t K = v->fold, G = fold_groups(R, K);
-    const bool coset = v->coset;
+    const ProofFormat& f = v->fmt;
+    const uint32_t log_n = f.log_n, log_b = f.log_b, q = f.q, D = f.stop, L = f.L();
+    const uint32_t R = f.rounds(), K = f.fold, G = f.groups();   // the folded rounds (early stop: R', and G' groups)
+    const bool coset = f.coset;
     // inputs: [count][len] proofs, [count] public_last, [count][32] states, packed into the pinned staging buffer
     uint8_t* hp = v->h_in;
     if (stride == len) memcpy(hp, proofs, count * len);
@@ -894,46 +891,40 @@ int verifier_chunk(zk_verifier* v, const uint8_t* proofs, size_t stride, size_t 
     a.h = root_of_unity(L);
     const uint32_t g = root_of_unity(log_n);
     a.gm1 = invmod(g); a.gm2 = mulmod(a.gm1, a.gm1); a.gm3 = mulmod(a.gm2, a.gm1); a.inv2 = invmod(2);
-    a.gw = v->grind ? 2u : 0u;
-    a.gmask = v->grind ? ~0u << (32u - v->grind) : 0u;
+    a.gw = f.grind ? 2u : 0u;
+    a.gmask = f.grind ? ~0u << (32u - f.grind) : 0u;
     a.D = D;
-    a.qbase = (D ? 11u + 9u * G + (1u << D) : 20u + 9u * G) + a.gw + q;   // D > 0: no last root, the coefficients for the free term
-    a.per_q = (coset ? 3u : 4u) * (3u + 8u * L);
-    for (uint32_t j = 0; j < G; ++j) {
-        const uint32_t steps = fold_steps(R, K, j);
-        if (coset) a.per_q += (1u << steps) + 2u + 8u * (L - j * K - steps);
-        else a.per_q += (3u + 8u * (L - j * K)) << steps;   // K = 1: 6 + 16 (L - j)
-    }
-    a.K = K; a.G = G; a.ls = fold_steps(R, K, G - 1u);
+    a.K = K; a.G = G; a.ls = f.steps(G - 1u);
+    // Where the fields sit, in words, from one pass over the header and one over a query (transcript.hpp); the kernels without caps
+    // take only qbase and per_q from it and know the rest in closed form, the cap kernels read all of it (CapLayout)
+    if (G + 1u > kCapTrees) return fail(ZK_ERR_STATE, "zk_verifier_run: more than %u trees", kCapTrees);
     CapLayout t{};
-    if (v->cap_log) {                                      // Merkle caps: the same fields, each tree with its own cap depth (CapLayout)
-        if (G + 1u > kCapTrees) return fail(ZK_ERR_STATE, "zk_verifier_run: more than %u trees", kCapTrees);
-        const uint32_t cf = cap_eff(v->cap_log, L);
-        auto ce = [&](uint32_t j) { return cap_eff(v->cap_log, group_tree_log(log_n, log_b, K, coset, D, j)); };
-        t.fplen = L - cf; t.fwords = 3u + 8u * t.fplen;
-        t.cpplen = L - ce(0); t.cpwords = 3u + 8u * t.cpplen;
-        uint32_t w = t.fcapn = 8u << cf;
-        t.aw = w; w += 3u;
-        t.capw[0] = w; t.capn[0] = 8u << ce(0); w += t.capn[0];
-        for (uint32_t j = 0; j < G; ++j) {
-            t.bw[j] = w++;
-            if (D && j + 1u == G) break;                   // a stopped proof has no tree over its last layer
-            t.capw[j + 1u] = w; t.capn[j + 1u] = 8u << ce(j + 1u); w += t.capn[j + 1u];
+    uint32_t w = 0;
+    f.for_each_head([&](ProofFormat::Head what, uint32_t j, size_t bytes) {
+        switch (what) {
+            case ProofFormat::kFTree: t.fcapn = (uint32_t)(bytes / 4); break;
+            case ProofFormat::kAlphas: t.aw = w; break;
+            case ProofFormat::kTree: t.capw[j] = w; t.capn[j] = (uint32_t)(bytes / 4); break;
+            case ProofFormat::kBeta: t.bw[j] = w; break;
+            case ProofFormat::kFinal: t.ftw = w; break;
+            case ProofFormat::kNonce: case ProofFormat::kRaws: break;
         }
-        t.ftw = w; w += D ? 1u << D : 1u;
-        a.qbase = w + a.gw + q;
-        uint32_t off = 3u * t.fwords + (coset ? 0u : t.cpwords);
-        for (uint32_t j = 0; j < G; ++j) {
-            const uint32_t steps = fold_steps(R, K, j);
-            t.plen[j] = group_tree_log(log_n, log_b, K, coset, D, j) - ce(j);
-            t.gw[j] = off;
-            off += coset ? (1u << steps) + 2u + 8u * t.plen[j] : (3u + 8u * t.plen[j]) << steps;
-        }
-        a.per_q = off;
-    }
+        w += (uint32_t)(bytes / 4);
+        return true;
+    });
+    a.qbase = w;
+    t.fplen = (uint32_t)f.f_path(); t.fwords = 3u + 8u * t.fplen;
+    t.cpplen = (uint32_t)f.tree_path(0); t.cpwords = 3u + 8u * t.cpplen;
+    uint32_t tuple = 0, off = 0;
+    f.for_each_tuple([&](size_t s, size_t plen, bool one_leaf) {
+        if (tuple >= (coset ? 3u : 4u)) { t.plen[tuple - (coset ? 3u : 4u)] = (uint32_t)plen; t.gw[tuple - (coset ? 3u : 4u)] = off; }
+        off += (uint32_t)(Channel::group_bytes(s, plen, one_leaf) / 4);
+        ++tuple;
+    });
+    a.per_q = off;
     if (a.qbase + (size_t)q * a.per_q != len / 4) return fail(ZK_ERR_STATE, "zk_verifier_run: the layout does not add up to the proof length");
-    const uint32_t w = invmod(powmod(a.h, (uint64_t)a.N >> 3));
-    a.inv2m = to_mont(a.inv2); a.wm1 = to_mont(w); a.wm2 = to_mont(mulmod(w, w)); a.wm3 = to_mont(mulmod(mulmod(w, w), w));
+    const uint32_t w8 = invmod(powmod(a.h, (uint64_t)a.N >> 3));
+    a.inv2m = to_mont(a.inv2); a.wm1 = to_mont(w8); a.wm2 = to_mont(mulmod(w8, w8)); a.wm3 = to_mont(mulmod(mulmod(w8, w8), w8));
 
     HIPCHK(hipMemcpyAsync(d, hp, count * len, hipMemcpyHostToDevice, v->stream));
     HIPCHK(hipMemcpyAsync(d_pub, hp + count * len, count * 4, hipMemcpyHostToDevice, v->stream));
@@ -946,7 +937,7 @@ int verifier_chunk(zk_verifier* v, const uint8_t* proofs, size_t stride, size_t 
     if (states) {                                      // the transcript chains run beside the paths: cost = max of the two
         HIPCHK(hipEventRecord(v->ev_in, v->stream));
         HIPCHK(hipStreamWaitEvent(v->tstream, v->ev_in, 0));
-        if (v->cap_log) {
+        if (v->fmt.cap) {
             if (coset) hipLaunchKernelGGL(verify_cap_transcript_kernel<true>, dim3(gx), dim3(kVerifyThreads), 0, v->tstream, ca);
             else hipLaunchKernelGGL(verify_cap_transcript_kernel<false>, dim3(gx), dim3(kVerifyThreads), 0, v->tstream, ca);
         } else if (D) {
@@ -961,7 +952,7 @@ int verifier_chunk(zk_verifier* v, const uint8_t* proofs, size_t stride, size_t 
     }
     const uint64_t lanes = (uint64_t)count * q;
     const dim3 agrid((uint32_t)((lanes + kVerifyThreads - 1) / kVerifyThreads));
-    if (v->cap_log) {                                      // one instance per leaf format covers every K and D
+    if (v->fmt.cap) {                                      // one instance per leaf format covers every K and D
         if (coset) hipLaunchKernelGGL(verify_cap_algebra_kernel<true>, agrid, dim3(kVerifyThreads), 0, v->stream, ca);
         else hipLaunchKernelGGL(verify_cap_algebra_kernel<false>, agrid, dim3(kVerifyThreads), 0, v->stream, ca);
     } else if (D) {                                           // the STOP instances: the last group against the final polynomial
@@ -981,7 +972,7 @@ int verifier_chunk(zk_verifier* v, const uint8_t* proofs, size_t stride, size_t 
     else hipLaunchKernelGGL(verify_fold_algebra_kernel<3>, agrid, dim3(kVerifyThreads), 0, v->stream, a);
     HIPCHK(hipGetLastError());
     const bool sha = v->hash == ZK_HASH_SHA256;
-    if (v->cap_log) {
+    if (v->fmt.cap) {
         const dim3 pgrid(gx, q * (coset ? 3u + G : 4u + ((G - 1u) << K) + (1u << a.ls)));
         if (coset) {
             if (sha) hipLaunchKernelGGL((verify_cap_paths_kernel<0, true>), pgrid, dim3(kVerifyThreads), 0, v->stream, ca);
@@ -1014,9 +1005,9 @@ int verifier_chunk(zk_verifier* v, const uint8_t* proofs, size_t stride, size_t 
         int32_t c;
         if (states && tcode[i]) c = tcode[i];
         else if (malformed[i])                             // garbage only
-            c = verify_proof(proofs + i * stride, len, log_n, log_b, public_last[i], v->hash, q, v->grind, K, coset, D, v->cap_log);
+            c = verify_proof(proofs + i * stride, len, f, public_last[i], v->hash);
         else if (best[i] == kNoFailure) c = 0;
-        else c = coset ? coset_key_to_check(best[i], G) : (K == 1 && !v->cap_log) ? key_to_check(best[i], R) : fold_key_to_check(best[i], G);
+        else c = coset ? coset_key_to_check(best[i], G) : (K == 1 && !v->fmt.cap) ? key_to_check(best[i], R) : fold_key_to_check(best[i], G);
         checks_out[i] = c;
     }
     return ZK_OK;
@@ -1051,7 +1042,7 @@ int zk_verifier_create(int device, uint32_t log_n, uint32_t log_b, zk_verifier**
     HIPCHK(hipSetDevice(device));
     zk_verifier* v = new (std::nothrow) zk_verifier();
     if (!v) return fail(ZK_ERR_NOMEM, "out of host memory");
-    v->device = device; v->log_n = log_n; v->log_b = log_b;
+    v->device = device; v->fmt.log_n = log_n; v->fmt.log_b = log_b;
     hipError_t e = hipStreamCreateWithFlags(&v->stream, hipStreamNonBlocking);
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&v->tstream, hipStreamNonBlocking);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&v->ev_in, hipEventDisableTiming);
@@ -1068,14 +1059,14 @@ int zk_verifier_create(int device, uint32_t log_n, uint32_t log_b, zk_verifier**
 int zk_verifier_set_queries(zk_verifier* v, uint32_t n_queries) {
     if (!v) return fail(ZK_ERR_INVALID, "null verifier");
     if (n_queries < 1 || n_queries > kMaxQueries) return fail(ZK_ERR_INVALID, "zk_verifier_set_queries: need 1 <= n_queries <= %u", kMaxQueries);
-    v->queries = n_queries;
+    v->fmt.q = n_queries;
     return ZK_OK;
 }
 
 int zk_verifier_set_grinding(zk_verifier* v, uint32_t grind_bits) {
     if (!v) return fail(ZK_ERR_INVALID, "null verifier");
     if (grind_bits > kMaxGrindBits) return fail(ZK_ERR_INVALID, "zk_verifier_set_grinding: need grind_bits <= %u (got %u)", kMaxGrindBits, grind_bits);
-    v->grind = grind_bits;
+    v->fmt.grind = grind_bits;
     return ZK_OK;
 }
 
@@ -1091,46 +1082,46 @@ int zk_verifier_set_hash(zk_verifier* v, int hash_kind) {
 int zk_verifier_set_fold(zk_verifier* v, uint32_t fold_log) {
     if (!v) return fail(ZK_ERR_INVALID, "null verifier");
     if (fold_log < 1 || fold_log > kMaxFoldLog) return fail(ZK_ERR_INVALID, "zk_verifier_set_fold: need 1 <= fold_log <= %u (got %u)", kMaxFoldLog, fold_log);
-    v->fold = fold_log;
+    v->fmt.fold = fold_log;
     return ZK_OK;
 }
 
-uint32_t zk_verifier_get_fold(const zk_verifier* v) { return v ? v->fold : 0u; }
+uint32_t zk_verifier_get_fold(const zk_verifier* v) { return v ? v->fmt.fold : 0u; }
 
 int zk_verifier_set_fri_stop(zk_verifier* v, uint32_t stop_log) {
     if (!v) return fail(ZK_ERR_INVALID, "null verifier");
-    if (!stop_ok(v->log_n, v->log_b, stop_log))
+    if (!stop_ok(v->fmt.log_n, v->fmt.log_b, stop_log))
         return fail(ZK_ERR_INVALID, "zk_verifier_set_fri_stop: need stop_log 0, or 1 <= stop_log <= %u with stop_log <= log_n - 1 and stop_log + log_blowup <= %u (got %u for %u, %u)",
-                    kMaxStopLog, kMaxStopLayerLog, stop_log, v->log_n, v->log_b);
-    v->stop = stop_log;
+                    kMaxStopLog, kMaxStopLayerLog, stop_log, v->fmt.log_n, v->fmt.log_b);
+    v->fmt.stop = stop_log;
     return ZK_OK;
 }
 
-uint32_t zk_verifier_get_fri_stop(const zk_verifier* v) { return v ? v->stop : 0u; }
+uint32_t zk_verifier_get_fri_stop(const zk_verifier* v) { return v ? v->fmt.stop : 0u; }
 
 int zk_verifier_set_merkle_cap(zk_verifier* v, uint32_t cap_log) {
     if (!v) return fail(ZK_ERR_INVALID, "null verifier");
     if (cap_log > kMaxCapLog) return fail(ZK_ERR_INVALID, "zk_verifier_set_merkle_cap: need cap_log <= %u (got %u)", kMaxCapLog, cap_log);
-    v->cap_log = cap_log;
+    v->fmt.cap = cap_log;
     return ZK_OK;
 }
 
-uint32_t zk_verifier_get_merkle_cap(const zk_verifier* v) { return v ? v->cap_log : 0u; }
+uint32_t zk_verifier_get_merkle_cap(const zk_verifier* v) { return v ? v->fmt.cap : 0u; }
 
 int zk_verifier_set_coset_leaves(zk_verifier* v, int on) {
     if (!v) return fail(ZK_ERR_INVALID, "null verifier");
-    v->coset = on != 0;
+    v->fmt.coset = on != 0;
     return ZK_OK;
 }
 
-int zk_verifier_get_coset_leaves(const zk_verifier* v) { return v && v->coset ? 1 : 0; }
+int zk_verifier_get_coset_leaves(const zk_verifier* v) { return v && v->fmt.coset ? 1 : 0; }
 
 int zk_verifier_run(zk_verifier* v, const uint8_t* proofs, size_t stride, size_t count, const uint8_t* states, const uint32_t* public_last,
                     int32_t* checks_out) {
     if (!v) return fail(ZK_ERR_INVALID, "null verifier");
     if (count == 0) return ZK_OK;
     if (!proofs || !public_last || !checks_out) return fail(ZK_ERR_INVALID, "zk_verifier_run: null argument");
-    const size_t len = proof_data_len_cap(v->log_n, v->log_b, v->queries, v->grind, v->fold, v->coset, v->stop, v->cap_log);
+    const size_t len = v->fmt.data_len();
     if (stride < len) return fail(ZK_ERR_INVALID, "zk_verifier_run: stride %zu < proof length %zu", stride, len);
     if (count > SIZE_MAX / stride) return fail(ZK_ERR_INVALID, "zk_verifier_run: count * stride overflows");
     HIPCHK(hipSetDevice(v->device));

@@ -109,28 +109,27 @@ struct zk_ctx {
     double t_wait = 0, t_host_hash = 0, t_launch = 0;   // ZK_HOST_TIMING: where the host thread spends a proof
     bool tail = false;                  // FRI-tail context (zk_tail_*): no trace / LDE / composition
     uint32_t hinv_host = 0;             // 1 / h (the host-side FRI rounds step through its powers)
-    uint32_t queries = 1;               // decommitment queries (1 = the reference, prover.rs:263)
-    uint32_t grind = 0;                 // proof-of-work bits before the query draw (zk_ctx_set_grinding; 0 = none, the reference)
+    // The format of the next one-call proof (transcript.hpp), one field per setter: q (1 = the reference, prover.rs:263), grind
+    // (zk_ctx_set_grinding), fold (zk_ctx_set_fold; 1 = the reference, prover.rs:198-225), coset (zk_ctx_set_coset_leaves), stop
+    // (zk_ctx_set_fri_stop) and cap (zk_ctx_set_merkle_cap)
+    ProofFormat fmt;
     Grinder* grinder = nullptr;         // device search on this context's stream (created by the setter when grind > kGrindHostMaxBits)
-    // FRI folding factor 2^fold between commitments (zk_ctx_set_fold; 1 = the reference, prover.rs:198-225).  skipped_*: bit id set =
-    // the last proof did not materialise layer / tree id (read-outs of it answer ZK_ERR_STATE until a stage call writes it)
-    uint32_t fold = 1;
+    // skipped_*: bit id set = the last proof did not materialise layer / tree id (folded, or stopped early: read-outs of it answer
+    // ZK_ERR_STATE until a stage call writes it)
     uint64_t skipped_layers = 0, skipped_trees = 0;
-    // Coset leaves (zk_ctx_set_coset_leaves; transcript.hpp): the tree over a group's input layer has one leaf per opened coset.
+    // Coset leaves (transcript.hpp): the tree over a group's input layer has one leaf per opened coset.
     // tree_steps[t]: tree t as it lies in d_trees has 2^tree_steps[t] values per leaf (0: one-value leaves), set by whatever built it
-    bool coset = false;
     uint8_t tree_steps[40] = {};
-    // Early stop (zk_ctx_set_fri_stop; transcript.hpp): only the first R - stop rounds are folded; the last group's output gets no tree,
+    // Early stop (transcript.hpp): only the first R - stop rounds are folded; the last group's output gets no tree,
     // its 2^stop coefficients (fri_final_poly_kernel -> d_final: one count word, then the coefficients) are committed instead
-    uint32_t stop = 0;
     uint32_t* d_final = nullptr;        // 1 + 2^kFinalPolyMaxLog words, allocated by the first call that needs it
     std::vector<uint32_t> final_poly;   // the last proof's coefficients (stop = 0: the free term)
     int hash = 0;                      // Merkle hash (zk_hash_kind): 0 = SHA-256 (reference), 1 = field-native (configs[4]), 2 = BLAKE2s-256
-    // Merkle caps (zk_ctx_set_merkle_cap; transcript.hpp): a one-call proof commits the 2^ce digests of depth ce = min(cap, lg - 1) of
-    // every tree and builds nothing above them.  cap_now: the setting while a one-call proof runs, 0 otherwise (the stage-by-stage
+    // Merkle caps (transcript.hpp): a one-call proof commits the 2^ce digests of depth ce = min(cap, lg - 1) of
+    // every tree and builds nothing above them.  cap_now: fmt.cap while a one-call proof runs, 0 otherwise (the stage-by-stage
     // API builds whole trees).  tree_cap[t]: the depth tree t was last built down to (set by whatever built it); nodes above it are
     // not defined.  cap_digests[t]: what the last proof committed for tree t when tree_cap[t] > 0.
-    uint32_t cap = 0, cap_now = 0;
+    uint32_t cap_now = 0;
     uint8_t tree_cap[40] = {};
     std::vector<uint8_t> cap_digests[40];
     // opt-in reference self-checks (zk_ctx_set_checks; prover.rs:64-66, :148-159, :169, :228-251)
@@ -226,7 +225,7 @@ MailArgs mail_of(zk_ctx* c, uint32_t tree, bool host, bool feed_tail = true, uin
     const uint32_t host_levels = host ? top_of(c, tree) : 0;
     c->tree_cap[tree] = (uint8_t)(host ? cap_of(c, tree) : 0);
     m.top = host ? hand_of(c, tree) : 0;
-    if (feed_tail && c->fold == 1 && !c->coset && !c->stop && host_levels && c->host_tail && tree >= 1 && layer_log(c, tree) == c->host_tail + 1) {
+    if (feed_tail && c->fmt.fold == 1 && !c->fmt.coset && !c->fmt.stop && host_levels && c->host_tail && tree >= 1 && layer_log(c, tree) == c->host_tail + 1) {
         m.dump_src = c->d_layers + c->layer_off[tree];
         m.dump_log = c->host_tail + 1;
         m.vals_off = (uint32_t)kMailValsOff;
@@ -401,7 +400,7 @@ int fri_round_commit(zk_ctx* c, uint32_t round, uint32_t beta_raw, uint8_t root[
 bool round_on_host(const zk_ctx* c, uint32_t round) {
     return c->hash == 0 && c->host_top && c->host_tail && c->L >= c->host_tail + 1 && c->L - round <= c->host_tail + 1;
 }
-bool can_gate(const zk_ctx* c, uint32_t round) { return c->fold == 1 && !c->coset && !c->stop && c->early && c->early_ok && !c->checks && round < c->R && !round_on_host(c, round); }
+bool can_gate(const zk_ctx* c, uint32_t round) { return c->fmt.fold == 1 && !c->fmt.coset && !c->fmt.stop && c->early && c->early_ok && !c->checks && round < c->R && !round_on_host(c, round); }
 // The launches of do_fold_commit(round), enqueued behind a wait on the gate word; their one challenge-dependent constant is read
 // from a parameter slot the host fills in release_gated_fold.
 int enqueue_gated_fold(zk_ctx* c, uint32_t round) {
@@ -433,7 +432,7 @@ struct GateGuard {
 // The cap setting holds for the trees a one-call proof builds, and for nothing else.
 struct CapScope {
     zk_ctx* c;
-    explicit CapScope(zk_ctx* ctx) : c(ctx) { c->cap_now = c->tail ? 0 : c->cap; }
+    explicit CapScope(zk_ctx* ctx) : c(ctx) { c->cap_now = c->tail ? 0 : c->fmt.cap; }
     ~CapScope() { c->cap_now = 0; }
 };
 
@@ -475,15 +474,15 @@ int final_alloc(zk_ctx* c) {
 // Early stop: the 2^stop coefficients of the polynomial layer 1 + R - stop evaluates, through one launch and one small copy; the
 // analogue of the prover.rs:238 check is that every coefficient of degree >= 2^stop is zero.
 int final_poly_value(zk_ctx* c) {
-    const uint32_t Rp = c->R - c->stop;
-    const size_t cnt = (size_t)1 << c->stop;
+    const uint32_t Rp = c->fmt.rounds();
+    const size_t cnt = (size_t)1 << c->fmt.stop;
     int rc = final_alloc(c);
     if (rc) return rc;
     if ((rc = dom_final_poly(c->dom, c->d_layers + c->layer_off[1 + Rp], c->d_final, c->L - Rp, Rp, (uint32_t)cnt, c->stream, prof_of(c)))) return rc;
     HIPCHK(hipMemcpyAsync(c->h_small, c->d_final, (cnt + 1) * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     if (c->h_small[0])
-        return fail(ZK_ERR_CHECK, "final FRI layer has degree >= 2^%u: trace does not satisfy the constraints (%u non-zero coefficients above; cf. prover.rs:238)", c->stop, c->h_small[0]);
+        return fail(ZK_ERR_CHECK, "final FRI layer has degree >= 2^%u: trace does not satisfy the constraints (%u non-zero coefficients above; cf. prover.rs:238)", c->fmt.stop, c->h_small[0]);
     c->final_poly.assign(c->h_small + 1, c->h_small + 1 + cnt);
     return ZK_OK;
 }
@@ -624,23 +623,23 @@ void commit_tree(zk_ctx* c, Channel& ch, uint32_t tree, const uint8_t root[32]) 
 // Early stop (any fold and leaf format comes here): the groups are those of the first R - stop rounds, and the last group's output
 // gets no tree and no root -- prove_finish commits its coefficients; ids past it are not materialised.
 int prove_fold_rounds(zk_ctx* c, Channel& ch) {
-    const uint32_t R = c->R - c->stop, K = c->fold;
+    const ProofFormat& f = c->fmt;
+    const uint32_t R = f.rounds(), G = f.groups();
     uint8_t root[32];
     int rc;
-    for (uint32_t r0 = 0; r0 < R; r0 += K) {
-        const uint32_t steps = R - r0 < K ? R - r0 : K, id = 1 + r0 + steps;
+    for (uint32_t j = 0; j < G; ++j) {
+        const uint32_t r0 = f.round0(j), steps = f.steps(j), id = f.tree_id(j + 1);
         const uint32_t beta = c->info.beta_raw[r0] = ch.get_u32();            // prover.rs:200, once per group
         if ((rc = dom_fold_multi(c->dom, c->d_layers + c->layer_off[1 + r0], c->d_layers + c->layer_off[id], c->L - r0, r0, steps, beta,
                                  c->stream, prof_of(c)))) return rc;
-        const uint32_t leaf_steps = c->coset && r0 + steps < R ? (R - r0 - steps < K ? R - r0 - steps : K) : 0;
-        const bool stopped = c->stop && r0 + steps == R;                        // the layer the proof stops at: no tree
-        if (!stopped && ((rc = do_merkle(c, id, true, false, leaf_steps)) || (rc = read_commit(c, id, root)))) return rc;
+        const bool stopped = f.stop && j + 1 == G;                              // the layer the proof stops at: no tree
+        if (!stopped && ((rc = do_merkle(c, id, true, false, f.slots_log(j + 1))) || (rc = read_commit(c, id, root)))) return rc;
         const size_t deg = c->n >> (r0 + steps);
         if (c->checks && (rc = check_degree(c, id, (uint32_t)deg - (deg ? 1 : 0), "prover.rs:228-251 (FRI layer degree)"))) return rc;
         if (!stopped) commit_tree(c, ch, id, root);
         for (uint32_t l = 2 + r0; l < id; ++l) { c->skipped_layers |= (uint64_t)1 << l; c->skipped_trees |= (uint64_t)1 << l; }
     }
-    if (c->stop) {
+    if (f.stop) {
         c->skipped_trees |= (uint64_t)1 << (1 + R);
         for (uint32_t l = 2 + R; l <= c->R + 1; ++l) { c->skipped_layers |= (uint64_t)1 << l; c->skipped_trees |= (uint64_t)1 << l; }
     }
@@ -662,10 +661,11 @@ struct HostLaps {
 // Everything after the last root, for every folding factor: the free term (prover.rs:254), grinding, the query draw (prover.rs:263)
 // and the decommitment (prover.rs:266-289) in the order of for_each_opening, one commit_group per tuple (transcript.hpp).
 int prove_finish(zk_ctx* c, Channel& ch, HostLaps& lap) {
-    const uint32_t R = c->R - c->stop, K = c->fold, Q = c->queries, G = fold_groups(R, K);   // early stop: the groups of the folded rounds
-    const size_t B = c->B, N = c->N, Lp = c->L;
+    const ProofFormat& f = c->fmt;
+    const uint32_t Q = f.q;
+    const size_t B = c->B, N = c->N;
     int rc;
-    if (c->stop) {                                        // the final polynomial's coefficients, one commit (transcript.hpp "stop")
+    if (c->fmt.stop) {                                        // the final polynomial's coefficients, one commit (transcript.hpp "stop")
         if ((rc = final_poly_value(c))) return rc;
         c->info.free_term = c->final_poly[0];
         std::vector<uint8_t>& cb = c->commit_buf;
@@ -681,10 +681,10 @@ int prove_finish(zk_ctx* c, Channel& ch, HostLaps& lap) {
         ch.commit_u32(free_term);                         // prover.rs:254
         c->final_poly.assign(1, free_term);
     }
-    if (c->grind) {                                       // proof of work on the state after the free term (DESIGN.md "Grinding")
+    if (c->fmt.grind) {                                       // proof of work on the state after the free term (DESIGN.md "Grinding")
         uint64_t w = 0;
-        if ((rc = grind_channel(c->grinder, ch, c->grind, &w))) return rc;
-        c->info.grind_bits = c->grind;
+        if ((rc = grind_channel(c->grinder, ch, c->fmt.grind, &w))) return rc;
+        c->info.grind_bits = c->fmt.grind;
         c->info.grind_nonce = w;
         lap("grind");
     }
@@ -698,14 +698,13 @@ int prove_finish(zk_ctx* c, Channel& ch, HostLaps& lap) {
     // mailbox flag behind them: no copy commands, no stream synchronisation.  The scatter that completes the device
     // arrays with the host-built parts is enqueued behind it, off the proof's critical path.
     size_t per_query = 0;
-    const bool coset = c->coset;
-    for_each_opening(c->log_n, c->log_b, K, 0, [&](uint32_t, uint32_t, size_t, uint32_t slots_log) { per_query += (size_t)1 << slots_log; }, coset, c->stop);
+    f.for_each_tuple([&](size_t s, size_t, bool) { per_query += s; });
     open_begin(c, (size_t)Q * per_query);
     for (uint32_t k = 0; k < Q; ++k)
-        for_each_opening(c->log_n, c->log_b, K, (size_t)qraws[k] % (N - 2 * B), [&](uint32_t layer, uint32_t log_leaves, size_t leaf, uint32_t slots_log) {
+        f.for_each_opening((size_t)qraws[k] % (N - 2 * B), [&](uint32_t layer, uint32_t log_leaves, size_t leaf, uint32_t slots_log) {
             for (size_t u = 0; u < ((size_t)1 << slots_log); ++u) open_val(c, layer, leaf + (u << log_leaves));
             open_path(c, layer, (size_t)1 << log_leaves, leaf);
-        }, coset, c->stop);
+        });
     if ((rc = open_launch(c))) return rc;
     if ((rc = flush_host_parts(c))) return rc;            // completes the device arrays, behind the fetch: off the critical path
     lap("free term + fetch enqueue");
@@ -714,19 +713,13 @@ int prove_finish(zk_ctx* c, Channel& ch, HostLaps& lap) {
     const uint32_t* const* vsrc = c->fetch_vals.data();
     const uint32_t* const* dsrc = c->fetch_nodes.data();
     std::vector<uint8_t>& buf = c->commit_buf;            // reused from proof to proof; the first group's tuple is the largest
-    buf.resize(Channel::group_bytes((size_t)1 << fold_steps(R, K, 0), Lp));
+    buf.resize(Channel::group_bytes((size_t)1 << f.steps(0), f.L(), false));
     auto tuple = [&](size_t s, size_t plen, bool one_leaf) {
         ch.commit_group(buf.data(), s, plen, [&](size_t t) { return *vsrc[t]; },
                         [&](size_t i, uint8_t* out) { digest_words_to_bytes(dsrc[i], out); }, one_leaf);
         vsrc += s; dsrc += (one_leaf ? 1 : s) * plen;
     };
-    for (uint32_t q = 0; q < Q; ++q) {
-        for (int k = 0; k < (coset ? 3 : 4); ++k) tuple(1, Lp - c->tree_cap[k < 3 ? 0 : 1], false);   // (u32, AuthPath): prover.rs:274-277
-        for (uint32_t j = 0; j < G; ++j) {                                                    // prover.rs:280-289, per group
-            const size_t steps = fold_steps(R, K, j);
-            tuple((size_t)1 << steps, Lp - (size_t)j * K - (coset ? steps : 0) - c->tree_cap[1 + j * K], coset);   // paths end below the cap
-        }
-    }
+    for (uint32_t q = 0; q < Q; ++q) f.for_each_tuple(tuple);   // (u32, AuthPath): prover.rs:274-277, then per group: prover.rs:280-289
     lap("decommit host hashing");
     return ZK_OK;                                         // the proof is the channel: channel.rs:34-36
 }
@@ -741,7 +734,7 @@ int prove_resident(zk_ctx* c, Channel& ch) {
     static const bool timing = getenv("ZK_HOST_TIMING") != nullptr;
     HostLaps lap{timing};
     const uint32_t R = c->R;
-    ch.data.reserve(ch.data.size() + proof_data_len_cap(c->log_n, c->log_b, c->queries, c->grind, c->fold, c->coset, c->stop, c->cap));
+    ch.data.reserve(ch.data.size() + c->fmt.data_len());
     CapScope cap_scope{c};                                // the trees of this proof stop at the cap; every other builder makes whole trees
     c->skipped_layers = c->skipped_trees = 0;
     uint8_t root[32];
@@ -758,14 +751,14 @@ int prove_resident(zk_ctx* c, Channel& ch) {
     commit_tree(c, ch, 0, root);                          // prover.rs:85
     uint32_t alpha[3];
     for (int i = 0; i < 3; ++i) alpha[i] = c->info.alpha_raw[i] = ch.get_u32();   // prover.rs:163-165
-    if (c->coset) {                                       // prover.rs:166-176, then the tree with group 0's cosets as leaves
-        if ((rc = do_compose(c, alpha)) || (rc = do_merkle(c, 1, true, false, fold_steps(R - c->stop, c->fold, 0)))) return rc;
+    if (c->fmt.coset) {                                       // prover.rs:166-176, then the tree with group 0's cosets as leaves
+        if ((rc = do_compose(c, alpha)) || (rc = do_merkle(c, 1, true, false, c->fmt.steps(0)))) return rc;
     } else if ((rc = do_compose_commit(c, alpha))) return rc;    // prover.rs:166-176 (composition fused into the leaf hashing)
     if (can_gate(c, 0) && (rc = enqueue_gated_fold(c, 0))) return rc;   // early launch: round 0 queued before cp's digests are waited for
     if ((rc = read_commit(c, 1, root))) return rc;
     if (c->checks && (rc = check_degree(c, 1, (uint32_t)c->n - 1, "prover.rs:148-159/:169 (exact divisions, deg cp = n - 1)"))) return rc;
     commit_tree(c, ch, 1, root);                          // prover.rs:180
-    if (c->fold > 1 || c->coset || c->stop) {
+    if (c->fmt.fold > 1 || c->fmt.coset || c->fmt.stop) {
         if ((rc = prove_fold_rounds(c, ch))) return rc;
     } else for (uint32_t r = 0; r < R; ++r) {             // prover.rs:198-225
         uint32_t beta = c->info.beta_raw[r] = ch.get_u32();   // prover.rs:200
@@ -927,6 +920,7 @@ static int ctx_make(int device, uint32_t log_n, uint32_t log_b, uint32_t shift, 
     if (!c) return fail(ZK_ERR_NOMEM, "out of host memory");
     c->device = device;
     c->log_n = log_n; c->log_b = log_b; c->L = log_n + log_b;
+    c->fmt.log_n = log_n; c->fmt.log_b = log_b;
     c->n = (size_t)1 << log_n; c->B = (size_t)1 << log_b; c->N = c->n << log_b;
     c->R = log_n;
     int rc = ZK_OK;
@@ -1065,15 +1059,16 @@ int zk_ctx_set_early_launch(zk_ctx* c, int on) {
     c->early = on != 0;
     return ZK_OK;
 }
-int zk_ctx_get_early_launch(const zk_ctx* c) { return c && c->early && c->early_ok && c->fold == 1 && !c->coset && !c->stop ? 1 : 0; }
+int zk_ctx_get_early_launch(const zk_ctx* c) { return c && c->early && c->early_ok && c->fmt.fold == 1 && !c->fmt.coset && !c->fmt.stop ? 1 : 0; }
 // FRI folding factor 2^fold_log between commitments (include/zkstark_amd.h).  A query of a folded proof opens 2^fold_log values and
 // paths per group: the decommitment buffers grow here, not inside the first proof.
 int zk_ctx_set_fold(zk_ctx* c, uint32_t fold_log) {
     if (!c) return fail(ZK_ERR_INVALID, "null context");
     if (c->tail) return fail(ZK_ERR_STATE, "zk_ctx_set_fold: FRI-tail context");
     if (fold_log < 1 || fold_log > kMaxFoldLog) return fail(ZK_ERR_INVALID, "zk_ctx_set_fold: need 1 <= fold_log <= %u (got %u)", kMaxFoldLog, fold_log);
-    size_t opened = 4;
-    for (uint32_t r0 = 0; r0 < c->R; r0 += fold_log) opened += (size_t)1 << (c->R - r0 < fold_log ? c->R - r0 : fold_log);
+    const ProofFormat widest{.log_n = c->log_n, .log_b = c->log_b, .fold = fold_log};   // one-value leaves, no early stop, no cap: it opens the most
+    size_t opened = 0;
+    widest.for_each_tuple([&](size_t s, size_t, bool) { opened += s; });
     const size_t cap = (size_t)kMaxQueries * opened * (c->L + 1) + 64;
     if (cap > c->gather_cap) {
         HIPCHK(hipSetDevice(c->device));
@@ -1100,19 +1095,19 @@ int zk_ctx_set_fold(zk_ctx* c, uint32_t fold_log) {
         c->device_bytes += (cap - c->gather_cap) * 40;
         c->gather_cap = cap;
     }
-    c->fold = fold_log;
+    c->fmt.fold = fold_log;
     return ZK_OK;
 }
-uint32_t zk_ctx_get_fold(const zk_ctx* c) { return c ? c->fold : 0; }
+uint32_t zk_ctx_get_fold(const zk_ctx* c) { return c ? c->fmt.fold : 0; }
 // Coset leaves (include/zkstark_amd.h): from the next proof on.  A coset proof opens fewer nodes than a plain one, so the
 // decommitment buffers of the current folding factor suffice.
 int zk_ctx_set_coset_leaves(zk_ctx* c, int on) {
     if (!c) return fail(ZK_ERR_INVALID, "null context");
     if (c->tail) return fail(ZK_ERR_STATE, "zk_ctx_set_coset_leaves: FRI-tail context");
-    c->coset = on != 0;
+    c->fmt.coset = on != 0;
     return ZK_OK;
 }
-int zk_ctx_get_coset_leaves(const zk_ctx* c) { return c && c->coset ? 1 : 0; }
+int zk_ctx_get_coset_leaves(const zk_ctx* c) { return c && c->fmt.coset ? 1 : 0; }
 // Early stop (include/zkstark_amd.h): from the next proof on.  A stopped proof opens fewer nodes than a full one, so the decommitment
 // buffers suffice; the kernel's output buffer is allocated here, not inside the first proof.
 int zk_ctx_set_fri_stop(zk_ctx* c, uint32_t stop_log) {
@@ -1125,10 +1120,10 @@ int zk_ctx_set_fri_stop(zk_ctx* c, uint32_t stop_log) {
         HIPCHK(hipSetDevice(c->device));
         if (int rc = final_alloc(c)) return rc;
     }
-    c->stop = stop_log;
+    c->fmt.stop = stop_log;
     return ZK_OK;
 }
-uint32_t zk_ctx_get_fri_stop(const zk_ctx* c) { return c ? c->stop : 0; }
+uint32_t zk_ctx_get_fri_stop(const zk_ctx* c) { return c ? c->fmt.stop : 0; }
 int zk_ctx_final_poly(const zk_ctx* c, uint32_t* out, size_t cap, size_t* count) {
     if (!c || !count || (!out && cap)) return fail(ZK_ERR_INVALID, "zk_ctx_final_poly: null argument");
     if (c->final_poly.empty()) return fail(ZK_ERR_STATE, "zk_ctx_final_poly: no proof made yet");
@@ -1143,17 +1138,17 @@ int zk_ctx_set_merkle_cap(zk_ctx* c, uint32_t cap_log) {
     if (!c) return fail(ZK_ERR_INVALID, "null context");
     if (c->tail) return fail(ZK_ERR_STATE, "zk_ctx_set_merkle_cap: FRI-tail context");
     if (cap_log > kMaxCapLog) return fail(ZK_ERR_INVALID, "zk_ctx_set_merkle_cap: need cap_log <= %u (got %u)", kMaxCapLog, cap_log);
-    c->cap = cap_log;
+    c->fmt.cap = cap_log;
     return ZK_OK;
 }
-uint32_t zk_ctx_get_merkle_cap(const zk_ctx* c) { return c ? c->cap : 0; }
+uint32_t zk_ctx_get_merkle_cap(const zk_ctx* c) { return c ? c->fmt.cap : 0; }
 // What the last one-call proof committed for `tree`: 2^ce digests of 32 bytes (ce = 0: the root).
 uint32_t zk_ctx_merkle_cap_log(const zk_ctx* c, uint32_t tree) { return c && tree <= c->R + 1 ? c->tree_cap[tree] : 0; }
 int zk_ctx_merkle_cap(const zk_ctx* c, uint32_t tree, uint8_t* out, size_t out_len) {
     if (!c || !out) return fail(ZK_ERR_INVALID, "zk_ctx_merkle_cap: null argument");
     if (tree > c->R + 1) return fail(ZK_ERR_INVALID, "zk_ctx_merkle_cap: tree %u out of range", tree);
     if (c->final_poly.empty()) return fail(ZK_ERR_STATE, "zk_ctx_merkle_cap: no proof made yet");
-    if ((c->skipped_trees >> tree) & 1) return fail(ZK_ERR_STATE, "zk_ctx_merkle_cap: tree %u was not built by the last proof (fold_log %u, fri_stop %u)", tree, c->fold, c->stop);
+    if ((c->skipped_trees >> tree) & 1) return fail(ZK_ERR_STATE, "zk_ctx_merkle_cap: tree %u was not built by the last proof (fold_log %u, fri_stop %u)", tree, c->fmt.fold, c->fmt.stop);
     const uint32_t ce = c->tree_cap[tree];
     const uint8_t* src = ce ? c->cap_digests[tree].data() : c->info.roots[tree];
     if (((size_t)32 << ce) > out_len) return fail(ZK_ERR_BUFFER, "zk_ctx_merkle_cap: %zu bytes, room for %zu", (size_t)32 << ce, out_len);
@@ -1163,7 +1158,7 @@ int zk_ctx_merkle_cap(const zk_ctx* c, uint32_t tree, uint8_t* out, size_t out_l
 int zk_ctx_set_queries(zk_ctx* c, uint32_t n_queries) {
     if (!c) return fail(ZK_ERR_INVALID, "null context");
     if (n_queries < 1 || n_queries > kMaxQueries) return fail(ZK_ERR_INVALID, "zk_ctx_set_queries: need 1 <= n_queries <= %u", kMaxQueries);
-    c->queries = n_queries;
+    c->fmt.q = n_queries;
     return ZK_OK;
 }
 int zk_ctx_set_grinding(zk_ctx* c, uint32_t grind_bits) {
@@ -1174,7 +1169,7 @@ int zk_ctx_set_grinding(zk_ctx* c, uint32_t grind_bits) {
         HIPCHK(hipSetDevice(c->device));
         if (int rc = grinder_create(c->device, c->stream, 1, &c->grinder)) return rc;
     }
-    c->grind = grind_bits;
+    c->fmt.grind = grind_bits;
     return ZK_OK;
 }
 
@@ -1352,7 +1347,7 @@ int zk_fri_final_poly(zk_ctx* c, uint32_t layer, uint32_t bound, uint32_t* coef_
 int zk_layer_read(zk_ctx* c, uint32_t layer, size_t offset, size_t count, uint32_t* out) {
     if (!c || (!out && count)) return fail(ZK_ERR_INVALID, "zk_layer_read: null argument");
     if (layer > c->R + 1 || offset + count > layer_size(c, layer)) return fail(ZK_ERR_INVALID, "zk_layer_read: out of range");
-    if ((c->skipped_layers >> layer) & 1) return fail(ZK_ERR_STATE, "zk_layer_read: layer %u was not materialised by the last proof (fold_log %u, fri_stop %u)", layer, c->fold, c->stop);
+    if ((c->skipped_layers >> layer) & 1) return fail(ZK_ERR_STATE, "zk_layer_read: layer %u was not materialised by the last proof (fold_log %u, fri_stop %u)", layer, c->fmt.fold, c->fmt.stop);
     HIPCHK(hipSetDevice(c->device));
     if (int prc = settle_pending(c)) return prc;
     HIPCHK(hipMemcpyAsync(out, c->d_layers + c->layer_off[layer] + offset, count * 4, hipMemcpyDeviceToHost, c->stream));
@@ -1376,7 +1371,7 @@ int zk_layer_write(zk_ctx* c, uint32_t layer, size_t offset, size_t count, const
 int zk_merkle_node(zk_ctx* c, uint32_t tree, size_t index, uint8_t out[32]) {
     if (!c || !out) return fail(ZK_ERR_INVALID, "zk_merkle_node: null argument");
     if (tree > c->R + 1 || index >= 2 * tree_leaves(c, tree) - 1) return fail(ZK_ERR_INVALID, "zk_merkle_node: out of range");
-    if ((c->skipped_trees >> tree) & 1) return fail(ZK_ERR_STATE, "zk_merkle_node: tree %u was not built by the last proof (fold_log %u, fri_stop %u)", tree, c->fold, c->stop);
+    if ((c->skipped_trees >> tree) & 1) return fail(ZK_ERR_STATE, "zk_merkle_node: tree %u was not built by the last proof (fold_log %u, fri_stop %u)", tree, c->fmt.fold, c->fmt.stop);
     if (index + 1 < ((size_t)1 << c->tree_cap[tree])) return fail(ZK_ERR_STATE, "zk_merkle_node: node %zu of tree %u lies above its Merkle cap (depth %u): the last proof did not build it", index, tree, c->tree_cap[tree]);
     HIPCHK(hipSetDevice(c->device));
     if (int prc = settle_pending(c)) return prc;
@@ -1390,7 +1385,7 @@ int zk_merkle_nodes(zk_ctx* c, uint32_t tree, size_t first, size_t count, uint8_
     if (!c || (!out && count)) return fail(ZK_ERR_INVALID, "zk_merkle_nodes: null argument");
     if (tree > c->R + 1 || first > 2 * tree_leaves(c, tree) - 1 || count > 2 * tree_leaves(c, tree) - 1 - first)
         return fail(ZK_ERR_INVALID, "zk_merkle_nodes: out of range");
-    if ((c->skipped_trees >> tree) & 1) return fail(ZK_ERR_STATE, "zk_merkle_nodes: tree %u was not built by the last proof (fold_log %u, fri_stop %u)", tree, c->fold, c->stop);
+    if ((c->skipped_trees >> tree) & 1) return fail(ZK_ERR_STATE, "zk_merkle_nodes: tree %u was not built by the last proof (fold_log %u, fri_stop %u)", tree, c->fmt.fold, c->fmt.stop);
     if (count && first + 1 < ((size_t)1 << c->tree_cap[tree])) return fail(ZK_ERR_STATE, "zk_merkle_nodes: node %zu of tree %u lies above its Merkle cap (depth %u): the last proof did not build it", first, tree, c->tree_cap[tree]);
     HIPCHK(hipSetDevice(c->device));
     if (int prc = settle_pending(c)) return prc;
@@ -1400,7 +1395,7 @@ int zk_merkle_nodes(zk_ctx* c, uint32_t tree, size_t first, size_t count, uint8_
 int zk_merkle_path(zk_ctx* c, uint32_t tree, size_t leaf, uint8_t* out, size_t* path_len) {
     if (!c || !out) return fail(ZK_ERR_INVALID, "zk_merkle_path: null argument");
     if (tree > c->R + 1 || leaf >= tree_leaves(c, tree)) return fail(ZK_ERR_INVALID, "zk_merkle_path: out of range");
-    if ((c->skipped_trees >> tree) & 1) return fail(ZK_ERR_STATE, "zk_merkle_path: tree %u was not built by the last proof (fold_log %u, fri_stop %u)", tree, c->fold, c->stop);
+    if ((c->skipped_trees >> tree) & 1) return fail(ZK_ERR_STATE, "zk_merkle_path: tree %u was not built by the last proof (fold_log %u, fri_stop %u)", tree, c->fmt.fold, c->fmt.stop);
     if (c->tree_cap[tree]) return fail(ZK_ERR_STATE, "zk_merkle_path: tree %u was built down to its Merkle cap only (depth %u): a whole path does not exist", tree, c->tree_cap[tree]);
     HIPCHK(hipSetDevice(c->device));
     if (int prc = settle_pending(c)) return prc;
@@ -1480,15 +1475,14 @@ int zk_last_transcript(const zk_ctx* c, zk_transcript_info* out) {
 // transcript replay first when a state is given, then the proof checks (transcript.hpp).  The check number goes to *check_out
 // (if any) and into the message: "proof rejected at check N" + reject_note, or, for the entry points that tell a failed replay
 // apart (replay_note not null), "transcript replay failed at check N" + replay_note.
-static int verify_entry(const char* who, const uint8_t* proof, size_t len, const uint8_t* state, uint32_t log_n, uint32_t log_b,
-                        uint32_t public_last, int hash_kind, uint32_t q, uint32_t grind, uint32_t fold, int32_t* check_out,
-                        const char* replay_note, const char* reject_note, bool coset = false, uint32_t stop = 0, uint32_t cap = 0) {
+static int verify_entry(const char* who, const uint8_t* proof, size_t len, const uint8_t* state, const ProofFormat& fmt, uint32_t public_last,
+                        int hash_kind, int32_t* check_out, const char* replay_note, const char* reject_note) {
     if (hash_kind != ZK_HASH_SHA256 && hash_kind != ZK_HASH_FIELD && hash_kind != ZK_HASH_BLAKE2S) return fail(ZK_ERR_INVALID, "%s: unknown hash %d", who, hash_kind);
-    if (fold < 1 || fold > kMaxFoldLog) return fail(ZK_ERR_INVALID, "%s: need 1 <= fold_log <= %u (got %u)", who, kMaxFoldLog, fold);
-    if (cap > kMaxCapLog) return fail(ZK_ERR_INVALID, "%s: need cap_log <= %u (got %u)", who, kMaxCapLog, cap);
-    int rc = state ? verify_transcript(proof, len, state, log_n, log_b, q, grind, fold, coset, stop, cap) : 0;
+    if (fmt.fold < 1 || fmt.fold > kMaxFoldLog) return fail(ZK_ERR_INVALID, "%s: need 1 <= fold_log <= %u (got %u)", who, kMaxFoldLog, fmt.fold);
+    if (fmt.cap > kMaxCapLog) return fail(ZK_ERR_INVALID, "%s: need cap_log <= %u (got %u)", who, kMaxCapLog, fmt.cap);
+    int rc = state ? verify_transcript(proof, len, state, fmt) : 0;
     const bool in_replay = rc != 0;
-    if (!rc) rc = verify_proof(proof, len, log_n, log_b, public_last, hash_kind, q, grind, fold, coset, stop, cap);
+    if (!rc) rc = verify_proof(proof, len, fmt, public_last, hash_kind);
     if (check_out) *check_out = rc;
     if (!rc) return ZK_OK;
     if (in_replay && replay_note) return fail(ZK_ERR_VERIFY, "transcript replay failed at check %d%s", rc, replay_note);
@@ -1498,7 +1492,7 @@ static const char kProofRs[] = " (proof.rs:15-149)";
 
 int zk_verify_ex(const uint8_t* proof, size_t len, uint32_t log_n, uint32_t log_b, uint32_t public_last, int hash_kind) {
     if (!proof) return fail(ZK_ERR_INVALID, "zk_verify: null proof");
-    return verify_entry("zk_verify", proof, len, nullptr, log_n, log_b, public_last, hash_kind, 1, 0, 1, nullptr, nullptr, kProofRs);
+    return verify_entry("zk_verify", proof, len, nullptr, ProofFormat{.log_n = log_n, .log_b = log_b}, public_last, hash_kind, nullptr, nullptr, kProofRs);
 }
 int zk_verify(const uint8_t* proof, size_t len, uint32_t log_n, uint32_t log_b, uint32_t public_last) {
     return zk_verify_ex(proof, len, log_n, log_b, public_last, ZK_HASH_SHA256);
@@ -1506,18 +1500,20 @@ int zk_verify(const uint8_t* proof, size_t len, uint32_t log_n, uint32_t log_b, 
 int zk_verify_queries(const uint8_t* proof, size_t len, const uint8_t* state, uint32_t log_n, uint32_t log_b, uint32_t public_last,
                       int hash_kind, uint32_t n_queries) {
     if (!proof) return fail(ZK_ERR_INVALID, "zk_verify_queries: null proof");
-    return verify_entry("zk_verify_queries", proof, len, state, log_n, log_b, public_last, hash_kind, n_queries, 0, 1, nullptr, "", kProofRs);
+    return verify_entry("zk_verify_queries", proof, len, state, ProofFormat{.log_n = log_n, .log_b = log_b, .q = n_queries}, public_last, hash_kind, nullptr, "", kProofRs);
 }
 int zk_verify_strict(const uint8_t* proof, size_t len, const uint8_t state[32], uint32_t log_n, uint32_t log_b, uint32_t public_last) {
     if (!proof || !state) return fail(ZK_ERR_INVALID, "zk_verify_strict: null argument");
-    return verify_entry("zk_verify", proof, len, state, log_n, log_b, public_last, ZK_HASH_SHA256, 1, 0, 1, nullptr,
+    return verify_entry("zk_verify", proof, len, state, ProofFormat{.log_n = log_n, .log_b = log_b}, public_last, ZK_HASH_SHA256, nullptr,
                         " (challenge not derived from the transcript, or final state mismatch)", kProofRs);
 }
-// zk_verify_grind and zk_verify_check speak as "zk_verify_check" in their argument errors
+// zk_verify_cap is the general entry point; the older ones are its settings at their defaults, under their own names in argument errors
+// (zk_verify_grind and zk_verify_check speak as "zk_verify_check")
 int zk_verify_grind(const uint8_t* proof, size_t len, const uint8_t* state, uint32_t log_n, uint32_t log_b, uint32_t public_last,
                     int hash_kind, uint32_t n_queries, uint32_t grind_bits, int32_t* check_out) {
     if (!proof || !check_out) return fail(ZK_ERR_INVALID, "zk_verify_check: null argument");
-    return verify_entry("zk_verify_check", proof, len, state, log_n, log_b, public_last, hash_kind, n_queries, grind_bits, 1, check_out, nullptr, "");
+    return verify_entry("zk_verify_check", proof, len, state, ProofFormat{.log_n = log_n, .log_b = log_b, .q = n_queries, .grind = grind_bits}, public_last, hash_kind,
+                        check_out, nullptr, "");
 }
 int zk_verify_check(const uint8_t* proof, size_t len, const uint8_t* state, uint32_t log_n, uint32_t log_b, uint32_t public_last,
                     int hash_kind, uint32_t n_queries, int32_t* check_out) {
@@ -1529,47 +1525,54 @@ int zk_verify_fold(const uint8_t* proof, size_t len, const uint8_t* state, uint3
                    int hash_kind, uint32_t n_queries, uint32_t grind_bits, uint32_t fold_log, int32_t* check_out) {
     if (!proof || !check_out) return fail(ZK_ERR_INVALID, "zk_verify_fold: null argument");
     if (hash_kind == ZK_HASH_BLAKE2S) return fail(ZK_ERR_INVALID, "zk_verify_fold: BLAKE2s (hash 2) proofs are verified by zk_verify_stop");
-    return verify_entry("zk_verify_fold", proof, len, state, log_n, log_b, public_last, hash_kind, n_queries, grind_bits, fold_log, check_out, nullptr, "");
+    return verify_entry("zk_verify_fold", proof, len, state, ProofFormat{.log_n = log_n, .log_b = log_b, .q = n_queries, .grind = grind_bits, .fold = fold_log},
+                        public_last, hash_kind, check_out, nullptr, "");
 }
 // zk_verify_fold for proofs made with coset leaves (transcript.hpp)
 int zk_verify_coset(const uint8_t* proof, size_t len, const uint8_t* state, uint32_t log_n, uint32_t log_b, uint32_t public_last,
                     int hash_kind, uint32_t n_queries, uint32_t grind_bits, uint32_t fold_log, int32_t* check_out) {
     if (!proof || !check_out) return fail(ZK_ERR_INVALID, "zk_verify_coset: null argument");
-    return verify_entry("zk_verify_coset", proof, len, state, log_n, log_b, public_last, hash_kind, n_queries, grind_bits, fold_log, check_out, nullptr, "", true);
+    return verify_entry("zk_verify_coset", proof, len, state,
+                        ProofFormat{.log_n = log_n, .log_b = log_b, .q = n_queries, .grind = grind_bits, .fold = fold_log, .coset = true}, public_last, hash_kind,
+                        check_out, nullptr, "");
 }
 // zk_verify_fold / zk_verify_coset for proofs that stop FRI early (transcript.hpp "stop"); stop_log = 0 is those two
 int zk_verify_stop(const uint8_t* proof, size_t len, const uint8_t* state, uint32_t log_n, uint32_t log_b, uint32_t public_last,
                    int hash_kind, uint32_t n_queries, uint32_t grind_bits, uint32_t fold_log, int coset_leaves, uint32_t stop_log, int32_t* check_out) {
     if (!proof || !check_out) return fail(ZK_ERR_INVALID, "zk_verify_stop: null argument");
-    return verify_entry("zk_verify_stop", proof, len, state, log_n, log_b, public_last, hash_kind, n_queries, grind_bits, fold_log, check_out, nullptr, "",
-                        coset_leaves != 0, stop_log);
+    return verify_entry("zk_verify_stop", proof, len, state,
+                        ProofFormat{.log_n = log_n, .log_b = log_b, .q = n_queries, .grind = grind_bits, .fold = fold_log, .coset = coset_leaves != 0, .stop = stop_log},
+                        public_last, hash_kind, check_out, nullptr, "");
 }
 // zk_verify_stop for proofs with Merkle caps (transcript.hpp "Merkle caps"); cap_log = 0 is zk_verify_stop
 int zk_verify_cap(const uint8_t* proof, size_t len, const uint8_t* state, uint32_t log_n, uint32_t log_b, uint32_t public_last,
                   int hash_kind, uint32_t n_queries, uint32_t grind_bits, uint32_t fold_log, int coset_leaves, uint32_t stop_log, uint32_t cap_log,
                   int32_t* check_out) {
     if (!proof || !check_out) return fail(ZK_ERR_INVALID, "zk_verify_cap: null argument");
-    return verify_entry("zk_verify_cap", proof, len, state, log_n, log_b, public_last, hash_kind, n_queries, grind_bits, fold_log, check_out, nullptr, "",
-                        coset_leaves != 0, stop_log, cap_log);
+    return verify_entry("zk_verify_cap", proof, len, state,
+                        ProofFormat{.log_n = log_n, .log_b = log_b, .q = n_queries, .grind = grind_bits, .fold = fold_log, .coset = coset_leaves != 0, .stop = stop_log,
+                                    .cap = cap_log},
+                        public_last, hash_kind, check_out, nullptr, "");
 }
 
 size_t zk_proof_size(size_t data_len) { return 48 + data_len; }   // proof.rs:151-154: size_of::<Proof>() = 32 + 16
 size_t zk_proof_data_len_fold(uint32_t log_n, uint32_t log_b, uint32_t n_queries, uint32_t grind_bits, uint32_t fold_log) {
     if (fold_log < 1 || fold_log > kMaxFoldLog) return 0;
-    return proof_data_len(log_n, log_b, n_queries, grind_bits, fold_log);
+    return ProofFormat{.log_n = log_n, .log_b = log_b, .q = n_queries, .grind = grind_bits, .fold = fold_log}.data_len();
 }
 size_t zk_proof_data_len_coset(uint32_t log_n, uint32_t log_b, uint32_t n_queries, uint32_t grind_bits, uint32_t fold_log) {
     if (fold_log < 1 || fold_log > kMaxFoldLog) return 0;
-    return proof_data_len(log_n, log_b, n_queries, grind_bits, fold_log, true);
+    return ProofFormat{.log_n = log_n, .log_b = log_b, .q = n_queries, .grind = grind_bits, .fold = fold_log, .coset = true}.data_len();
 }
 size_t zk_proof_data_len_stop(uint32_t log_n, uint32_t log_b, uint32_t n_queries, uint32_t grind_bits, uint32_t fold_log, int coset_leaves, uint32_t stop_log) {
     if (fold_log < 1 || fold_log > kMaxFoldLog || !stop_ok(log_n, log_b, stop_log)) return 0;
-    return proof_data_len(log_n, log_b, n_queries, grind_bits, fold_log, coset_leaves != 0, stop_log);
+    return ProofFormat{.log_n = log_n, .log_b = log_b, .q = n_queries, .grind = grind_bits, .fold = fold_log, .coset = coset_leaves != 0, .stop = stop_log}.data_len();
 }
 size_t zk_proof_data_len_cap(uint32_t log_n, uint32_t log_b, uint32_t n_queries, uint32_t grind_bits, uint32_t fold_log, int coset_leaves, uint32_t stop_log,
                              uint32_t cap_log) {
     if (fold_log < 1 || fold_log > kMaxFoldLog || !stop_ok(log_n, log_b, stop_log) || cap_log > kMaxCapLog) return 0;
-    return proof_data_len_cap(log_n, log_b, n_queries, grind_bits, fold_log, coset_leaves != 0, stop_log, cap_log);
+    return ProofFormat{.log_n = log_n, .log_b = log_b, .q = n_queries, .grind = grind_bits, .fold = fold_log, .coset = coset_leaves != 0, .stop = stop_log, .cap = cap_log}
+        .data_len();
 }
 size_t zk_proof_data_len_grind(uint32_t log_n, uint32_t log_b, uint32_t n_queries, uint32_t grind_bits) {
     return zk_proof_data_len_fold(log_n, log_b, n_queries, grind_bits, 1);

@@ -23,6 +23,12 @@ def _no_blake2s(who, hash):
         raise ValueError(f"{who}: hash='blake2s' is not built for this class yet (Context, Merkle and Proof.verify take it)")
 
 
+def _proof_data_len(o):
+    """Bytes of a proof in the format of `o` (a Proof, Context, BatchContext or Verifier).  zk_proof_data_len_cap is the general
+    entry point: cap 0, stop 0 and one-value leaves are the older formats byte for byte."""
+    return _lib.load().zk_proof_data_len_cap(o.log_n, o.log_blowup, o.queries, o.grind_bits, o.fold_log, int(o.coset_leaves), o.stop_log, o.cap_log)
+
+
 def _u32arr(a):
     return np.ascontiguousarray(a, dtype=np.uint32)
 
@@ -162,16 +168,8 @@ class Proof:
         self.coset_leaves = bool(coset_leaves)       # made with zk_ctx_set_coset_leaves: zk_verify_coset, zk_proof_data_len_coset
 
     def expected_len(self):
-        """The length the format gives a proof of this shape (zk_proof_data_len_fold / zk_proof_data_len_coset; stopped early:
-        zk_proof_data_len_stop; with Merkle caps: zk_proof_data_len_cap)."""
-        if self.cap_log:
-            return _lib.load().zk_proof_data_len_cap(self.log_n, self.log_blowup, self.queries, self.grind_bits, self.fold_log,
-                                                     int(self.coset_leaves), self.stop_log, self.cap_log)
-        if self.stop_log:
-            return _lib.load().zk_proof_data_len_stop(self.log_n, self.log_blowup, self.queries, self.grind_bits, self.fold_log,
-                                                      int(self.coset_leaves), self.stop_log)
-        fn = _lib.load().zk_proof_data_len_coset if self.coset_leaves else _lib.load().zk_proof_data_len_fold
-        return fn(self.log_n, self.log_blowup, self.queries, self.grind_bits, self.fold_log)
+        """The length the format gives a proof of this shape."""
+        return _proof_data_len(self)
 
     data_len = expected_len
 
@@ -372,14 +370,7 @@ class Context:
         return out, high.value
 
     def _proof_cap(self):
-        if self.cap_log:
-            return _lib.load().zk_proof_data_len_cap(self.log_n, self.log_blowup, self.queries, self.grind_bits, self.fold_log,
-                                                     int(self.coset_leaves), self.stop_log, self.cap_log)
-        if self.stop_log:
-            return _lib.load().zk_proof_data_len_stop(self.log_n, self.log_blowup, self.queries, self.grind_bits, self.fold_log,
-                                                      int(self.coset_leaves), self.stop_log)
-        fn = _lib.load().zk_proof_data_len_coset if self.coset_leaves else _lib.load().zk_proof_data_len_fold
-        return fn(self.log_n, self.log_blowup, self.queries, self.grind_bits, self.fold_log)
+        return _proof_data_len(self)
 
     def set_fold(self, fold_log):
         """zk_ctx_set_fold: fold by 2^fold_log (1..3) between commitments from the next proof on."""
@@ -619,14 +610,7 @@ class BatchContext:
 
     @property
     def proof_len(self):
-        if self.cap_log:
-            return _lib.load().zk_proof_data_len_cap(self.log_n, self.log_blowup, self.queries, self.grind_bits, self.fold_log,
-                                                     int(self.coset_leaves), self.stop_log, self.cap_log)
-        if self.stop_log:
-            return _lib.load().zk_proof_data_len_stop(self.log_n, self.log_blowup, self.queries, self.grind_bits, self.fold_log,
-                                                      int(self.coset_leaves), self.stop_log)
-        fn = _lib.load().zk_proof_data_len_coset if self.coset_leaves else _lib.load().zk_proof_data_len_fold
-        return fn(self.log_n, self.log_blowup, self.queries, self.grind_bits, self.fold_log)
+        return _proof_data_len(self)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -751,14 +735,7 @@ class Verifier:
 
     @property
     def proof_len(self):
-        if self.cap_log:
-            return _lib.load().zk_proof_data_len_cap(self.log_n, self.log_blowup, self.queries, self.grind_bits, self.fold_log,
-                                                     int(self.coset_leaves), self.stop_log, self.cap_log)
-        if self.stop_log:
-            return _lib.load().zk_proof_data_len_stop(self.log_n, self.log_blowup, self.queries, self.grind_bits, self.fold_log,
-                                                      int(self.coset_leaves), self.stop_log)
-        fn = _lib.load().zk_proof_data_len_coset if self.coset_leaves else _lib.load().zk_proof_data_len_fold
-        return fn(self.log_n, self.log_blowup, self.queries, self.grind_bits, self.fold_log)
+        return _proof_data_len(self)
 
     def verify_raw(self, data, public_last, states=None):
         """data: [count, stride] uint8 (stride >= proof_len; BatchContext.prove_raw()'s array as it is), public_last: [count],
