@@ -482,6 +482,17 @@ int zk_batch_public_last(const zk_batch *b, uint32_t *out);
  * fold_log); with coset leaves zk_proof_data_len_coset of the same arguments; with an early stop zk_proof_data_len_stop).  Fails with ZK_ERR_CHECK, naming the proof, if a trace
  * breaks the constraints. */
 int zk_batch_prove(zk_batch *b, uint8_t *proofs_out, size_t stride, uint8_t *states_out);
+/* ONE proof of the M = 2^log_batch resident traces (a "shared proof"), with the batch's current settings: the f trees of
+ * zk_batch_prove, committed together, then a single FRI over the sum of the M composition polynomials, each taken with its own three
+ * alphas and its own public_last.  Wire format: the 2^(log_batch + ce_f) digests of the f heap (statement p's cap: entries p 2^ce_f
+ * onwards) in one commit, 3M alphas statement-major, then the header of a single proof from cp on; per query the three f tuples of every
+ * statement in turn, then the cp tuple and the group tuples of a single proof.  *proof_len = zk_proof_data_len_shared of the settings
+ * (also when the buffer is too small: ZK_ERR_BUFFER); state_out: the Channel.state.  Checked with zk_verify_shared and the
+ * zk_batch_public_last values.  ZK_ERR_INVALID for log_batch = 0 (a batch of one makes a plain proof) or > 8, ZK_ERR_STATE while another
+ * call runs on the batch, ZK_ERR_CHECK if some trace of the batch breaks the constraints (the sum does not tell which).  Afterwards
+ * tree 0 answers zk_batch_merkle_nodes / zk_batch_merkle_cap as after zk_batch_prove; the ids >= 1 answer ZK_ERR_STATE until the next
+ * zk_batch_prove. */
+int zk_batch_prove_shared(zk_batch *b, uint8_t *proof_out, size_t cap, size_t *proof_len, uint8_t state_out[32]);
 /* Nodes [first, first + count) of batch tree `tree` (a heap over batch * m_l leaves; proof p's tree is the subtree under node
  * 2^log_batch - 1 + p), 32 bytes each as zk_merkle_node.  Complete after zk_batch_prove that succeeded (after one that failed with
  * ZK_ERR_CHECK the tree levels built on the host threads were never copied to the device: the nodes read then are not that run's).  The
@@ -529,6 +540,11 @@ size_t zk_proof_data_len_stop(uint32_t log_n, uint32_t log_blowup, uint32_t n_qu
  * returns.  0 where that returns 0, or for cap_log > 8. */
 size_t zk_proof_data_len_cap(uint32_t log_n, uint32_t log_blowup, uint32_t n_queries, uint32_t grind_bits, uint32_t fold_log,
                              int coset_leaves, uint32_t stop_log, uint32_t cap_log);
+/* Shared proofs of M = 2^log_batch statements (zk_batch_prove_shared): zk_proof_data_len_cap of the other arguments, plus
+ * 32 (M - 1) 2^ce_f + 12 (M - 1) in the head and 3 (M - 1) (12 + 32 (L - ce_f)) per query, ce_f = min(c, L - 1).  log_batch = 0: what
+ * zk_proof_data_len_cap returns.  0 where that returns 0, or for log_batch > 8. */
+size_t zk_proof_data_len_shared(uint32_t log_n, uint32_t log_blowup, uint32_t n_queries, uint32_t grind_bits, uint32_t fold_log,
+                                int coset_leaves, uint32_t stop_log, uint32_t cap_log, uint32_t log_batch);
 /* Proof-of-work search (zk_ctx_set_grinding): the smallest nonce >= start whose SHA-256(state || le64(nonce)) begins with
  * grind_bits zero bits (0..32; 0 gives start), on the GPU (zk_grind) or on <= 16 host threads (zk_grind_host; threads is
  * clamped to 1..16).  Gives up with an error naming grind_bits after 2^44 nonces.  A zk_channel user grinds on
@@ -597,6 +613,16 @@ int zk_verify_stop(const uint8_t *proof, size_t len, const uint8_t *state, uint3
 int zk_verify_cap(const uint8_t *proof, size_t len, const uint8_t *state, uint32_t log_n, uint32_t log_blowup, uint32_t public_last,
                   int hash_kind, uint32_t n_queries, uint32_t grind_bits, uint32_t fold_log, int coset_leaves, uint32_t stop_log,
                   uint32_t cap_log, int32_t *check_out);
+
+/* zk_verify_cap for a shared proof of M = 2^log_batch statements (zk_batch_prove_shared), hashes 0..2; public_last: M values.  The same
+ * code as zk_verify_cap with the statements summed: -2 compares sum_p (alpha0_p p0_p + alpha1_p p1_p + alpha2_p p2_p) at x with the cp
+ * value opened (coset leaves: group 0's value 0); -3 covers the 3M f path lengths and cp's; -4 / -5 / -6 the path of f_p(x) / f_p(gx) /
+ * f_p(g^2 x) of the first failing tuple in wire order, each into its entry of statement p's cap; -7, -8 and -(100+j) on as ever.  A
+ * proof whose length is not zk_proof_data_len_shared of the arguments: -1, strict or not.  The strict replay counts 3M + G + q
+ * challenges in -(1000+k) and commits the f level in one piece.  log_batch outside 1..8: *check_out = -1 and ZK_ERR_INVALID. */
+int zk_verify_shared(const uint8_t *proof, size_t len, const uint8_t *state, uint32_t log_n, uint32_t log_blowup,
+                     const uint32_t *public_last, uint32_t log_batch, int hash_kind, uint32_t n_queries, uint32_t grind_bits,
+                     uint32_t fold_log, int coset_leaves, uint32_t stop_log, uint32_t cap_log, int32_t *check_out);
 
 /* A verifier for many proofs of one size (log_n, log_blowup: the sizes zk_verify_queries accepts).  It owns its streams and
  * device buffers (grown on demand) and a pinned staging buffer.  One verifier is used from one host thread at a time. */

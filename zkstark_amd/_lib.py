@@ -226,6 +226,9 @@ SYMBOLS = {
     "zk_batch_gen_fibsq": (_int, [_vp, _vp, _vp]),
     "zk_batch_public_last": (_int, [_vp, _vp]),
     "zk_batch_prove": (_int, [_vp, _vp, _sz, _vp]),
+    "zk_batch_prove_shared": (_int, [_vp, _vp, _sz, C.POINTER(_sz), _vp]),
+    "zk_proof_data_len_shared": (_sz, [_u32, _u32, _u32, _u32, _u32, _int, _u32, _u32, _u32]),
+    "zk_verify_shared": (_int, [_vp, _sz, _vp, _u32, _u32, _vp, _u32, _int, _u32, _u32, _u32, _int, _u32, _u32, C.POINTER(C.c_int32)]),
     "zk_batch_merkle_nodes": (_int, [_vp, _u32, _sz, _sz, _vp]),
     "zk_committer_create": (_int, [_int, C.POINTER(_vp)]),
     "zk_committer_destroy": (_int, [_vp]),

@@ -103,9 +103,11 @@ uint32_t blayer_log(const zk_batch* b, uint32_t layer) { return layer == 0 ? b->
 
 // Levels of each proof's tree (over 2^log_m leaves) that the host hashes: as many as the mailbox holds
 // (2^kMaxHostLog digests for the whole batch), none for the field hash or without SHA extensions.
-uint32_t bextra(const zk_batch* b, uint32_t log_m) {
-    if (!b->host_levels || b->hash != 0 || b->lb >= kMaxHostLog || log_m < 2) return 0;
-    uint32_t h = kMaxHostLog - b->lb;
+// lb, here and in the helpers below: the width of the stage, log2 of the trees built side by side -- b->lb for zk_batch_prove and the f
+// tree of a shared proof, 0 for the one FRI of a shared proof (zk_batch_prove_shared), which uses proof 0's share of every layer and heap.
+uint32_t bextra(const zk_batch* b, uint32_t log_m, uint32_t lb) {
+    if (!b->host_levels || b->hash != 0 || lb >= kMaxHostLog || log_m < 2) return 0;
+    uint32_t h = kMaxHostLog - lb;
     if (h > 8) h = 8;                                    // <= 255 nodes per proof on one thread (~8 us), as the single prover
     if (h > log_m - 1) h = log_m - 1;
     return h >= 3 ? h : 0;                               // two levels are not worth a hand-over
@@ -115,10 +117,10 @@ uint32_t bextra(const zk_batch* b, uint32_t log_m) {
 // to ce (h levels, 0 when the cap is at or below the share).  Otherwise the host's share is dropped: the build ends at depth lb + ce
 // without a mailbox and launch_digest_level_post copies that level into h_cap.  top: the depth the build ends at.
 struct Hand { uint32_t top, h; bool mailbox; };
-Hand bhand(const zk_batch* b, uint32_t ce, uint32_t log_m) {
-    const uint32_t h = bextra(b, log_m), deep = h > ce ? h : ce;
-    if (b->lb + deep <= kMaxHostLog) return Hand{b->lb + deep, h > ce ? h : 0, true};
-    return Hand{b->lb + ce, 0, false};
+Hand bhand(const zk_batch* b, uint32_t ce, uint32_t log_m, uint32_t lb) {
+    const uint32_t h = bextra(b, log_m, lb), deep = h > ce ? h : ce;
+    if (lb + deep <= kMaxHostLog) return Hand{lb + deep, h > ce ? h : 0, true};
+    return Hand{lb + ce, 0, false};
 }
 // cap > 0: the 16 + 8 * 2^(lb + ce) words of h_cap when the f tree (the deepest cap of a proof) does not fit the mailbox, else 0
 size_t bcap_words(const zk_batch* b, const ProofFormat& f) {
@@ -126,19 +128,19 @@ size_t bcap_words(const zk_batch* b, const ProofFormat& f) {
     return f.cap && e > kMaxHostLog ? kMailDigests + ((size_t)8 << e) : 0;
 }
 // Hand-over of the commit launch of `tree` (2^log_m leaves per proof): records the depth its proofs commit it at.
-MailArgs bmail(zk_batch* b, uint32_t tree, uint32_t log_m) {
+MailArgs bmail(zk_batch* b, uint32_t tree, uint32_t log_m, uint32_t lb) {
     MailArgs m;
     if (b->counters_dirty) { (void)hipMemsetAsync(b->d_counter, 0, 64, b->stream); b->counters_dirty = false; }
     const uint32_t ce = b->fmt.cap ? cap_eff(b->fmt.cap, log_m) : 0;
-    const Hand hd = bhand(b, ce, log_m);
+    const Hand hd = bhand(b, ce, log_m, lb);
     b->tree_cap[tree] = (uint8_t)ce;
     m.seq = ++b->mail_seq; m.top = hd.top;
     if (hd.mailbox) { m.mailbox = b->d_mail; m.counter = b->d_counter; }   // else: no mailbox, no continuation; bpost follows the build
     return m;
 }
 // Behind the build of `tree`: a cap deeper than the mailbox holds is posted by a launch of its own (the flag is the mailbox's).
-int bpost(zk_batch* b, uint32_t tree, uint32_t log_m) {
-    const Hand hd = bhand(b, b->tree_cap[tree], log_m);
+int bpost(zk_batch* b, uint32_t tree, uint32_t log_m, uint32_t lb) {
+    const Hand hd = bhand(b, b->tree_cap[tree], log_m, lb);
     if (hd.mailbox) return ZK_OK;
     if (!b->h_cap || kMailDigests + ((size_t)8 << hd.top) > b->cap_words) return fail(ZK_ERR_STATE, "zk_batch_prove: no buffer for a cap of 2^%u digests", hd.top);
     HIPCHK(launch_digest_level_post(b->d_trees + b->tree_off[tree], hd.top, b->d_cap + kMailDigests, b->d_mail, b->mail_seq, b->d_counter, b->stream, nullptr));
@@ -169,13 +171,13 @@ int bwait_roots(zk_batch* b) {
 // After bwait_roots: hashes the host's levels of every proof's tree `tree`, from its share h down to the depth ce the proofs commit
 // (0: their roots), and returns where those digests are ([batch][2^ce][8] state words): the posted ones themselves when the device
 // went all the way.
-const uint32_t* bfinish_roots(zk_batch* b, uint32_t tree, uint32_t log_m) {
+const uint32_t* bfinish_roots(zk_batch* b, uint32_t tree, uint32_t log_m, uint32_t lb) {
     const uint32_t ce = b->tree_cap[tree];
-    const Hand hd = bhand(b, ce, log_m);
+    const Hand hd = bhand(b, ce, log_m, lb);
     const uint32_t h = hd.h;
     const uint32_t* posted = (hd.mailbox ? b->h_mail : b->h_cap) + kMailDigests;
     if (!h) return posted;
-    const size_t nb = b->batch;
+    const size_t nb = (size_t)1 << lb;
     // stage[d], ce <= d < h: [proof][2^d] digests = level lb + d of the batch heap
     std::vector<uint32_t*> lvl(h + 1);
     for (uint32_t dd = ce; dd < h; ++dd) {
@@ -192,7 +194,7 @@ const uint32_t* bfinish_roots(zk_batch* b, uint32_t tree, uint32_t log_m) {
     });
     for (uint32_t dd = ce; dd < h; ++dd) {
         b->h_segs[b->n_segs++] = ScatterSeg{(uint64_t)(lvl[dd] - b->h_stage),
-                                            (uint64_t)b->tree_off[tree] + ((((uint64_t)1 << (b->lb + dd)) - 1) * 8),
+                                            (uint64_t)b->tree_off[tree] + ((((uint64_t)1 << (lb + dd)) - 1) * 8),
                                             (uint32_t)((nb << dd) * 8), 0};
         b->seg_words += (double)((nb << dd) * 8);
     }
@@ -681,8 +683,8 @@ int zk_batch_prove(zk_batch* b, uint8_t* proofs_out, size_t stride, uint8_t* sta
     memset(b->tree_steps, 0, sizeof b->tree_steps);
     memset(b->tree_cap, 0, sizeof b->tree_cap);
     b->proved = true;
-    HIPCHK(launch_merkle_build(b->d_layers + b->layer_off[0], L + lb, b->d_trees + b->tree_off[0], b->stream, nullptr, bmail(b, 0, L), hash));
-    if ((rc = bpost(b, 0, L))) return rc;
+    HIPCHK(launch_merkle_build(b->d_layers + b->layer_off[0], L + lb, b->d_trees + b->tree_off[0], b->stream, nullptr, bmail(b, 0, L, lb), hash));
+    if ((rc = bpost(b, 0, L, lb))) return rc;
     // proof-independent part of the composition constants (compose_args with alpha = 1)
     ComposeBatchArgs ca;
     {
@@ -692,7 +694,7 @@ int zk_batch_prove(zk_batch* b, uint8_t* proofs_out, size_t stride, uint8_t* sta
     }
     const uint32_t g2 = mulmod(d->g, d->g);
     if ((rc = wait_roots())) return rc;
-    const uint32_t* roots = bfinish_roots(b, 0, L);
+    const uint32_t* roots = bfinish_roots(b, 0, L, lb);
     double tc = timing ? now_us() : 0;
     b->pool->run(nb, 16, [&](size_t p) {
         commit_tree(p, roots, b->tree_cap[0]);                            // prover.rs:85
@@ -708,17 +710,17 @@ int zk_batch_prove(zk_batch* b, uint8_t* proofs_out, size_t stride, uint8_t* sta
         HIPCHK(launch_compose_batch(ca, lb, b->stream, nullptr));
         b->tree_steps[1] = (uint8_t)s0;
         HIPCHK(launch_merkle_build_coset_batch(b->d_layers + b->layer_off[1], L, s0, lb, b->d_trees + b->tree_off[1], b->stream, nullptr,
-                                               bmail(b, 1, L - s0), hash));
-        if ((rc = bpost(b, 1, L - s0))) return rc;
+                                               bmail(b, 1, L - s0, lb), hash));
+        if ((rc = bpost(b, 1, L - s0, lb))) return rc;
     } else {
-        HIPCHK(launch_compose_merkle_batch(ca, lb, b->d_trees + b->tree_off[1], b->stream, nullptr, bmail(b, 1, L), hash));   // prover.rs:166-176
-        if ((rc = bpost(b, 1, L))) return rc;
+        HIPCHK(launch_compose_merkle_batch(ca, lb, b->d_trees + b->tree_off[1], b->stream, nullptr, bmail(b, 1, L, lb), hash));   // prover.rs:166-176
+        if ((rc = bpost(b, 1, L, lb))) return rc;
     }
     const bool fused = K == 1 && !coset && !stop;                         // the fold inside the leaf hashing of its tree
     for (uint32_t j = 0;; ++j) {                                          // per group; tree 1 + r0 is the last one committed
         const uint32_t r0 = f.round0(j);
         if ((rc = wait_roots())) return rc;
-        roots = bfinish_roots(b, 1 + r0, L - r0 - b->tree_steps[1 + r0]);   // tree 1 + r0: 2^(L - r0) values per proof, 2^tree_steps per leaf
+        roots = bfinish_roots(b, 1 + r0, L - r0 - b->tree_steps[1 + r0], lb);   // tree 1 + r0: 2^(L - r0) values per proof, 2^tree_steps per leaf
         const uint32_t ce = b->tree_cap[1 + r0];                          // ... committed by its 2^ce digests of depth ce
         tc = timing ? now_us() : 0;
         if (j == G) {
@@ -741,8 +743,8 @@ int zk_batch_prove(zk_batch* b, uint8_t* proofs_out, size_t stride, uint8_t* sta
             FoldBatchArgs fa;
             if ((rc = fold_args(d, b->d_layers + b->layer_off[1 + r0], b->d_layers + b->layer_off[id], L - r0, r0, 0, fa.a))) return rc;
             fa.chal = b->d_chal;
-            HIPCHK(launch_fold_merkle_batch(fa, lb, b->d_trees + b->tree_off[id], b->stream, nullptr, bmail(b, id, L - r0 - 1), hash));   // prover.rs:201-214
-            if ((rc = bpost(b, id, L - r0 - 1))) return rc;
+            HIPCHK(launch_fold_merkle_batch(fa, lb, b->d_trees + b->tree_off[id], b->stream, nullptr, bmail(b, id, L - r0 - 1, lb), hash));   // prover.rs:201-214
+            if ((rc = bpost(b, id, L - r0 - 1, lb))) return rc;
         } else {
             if ((rc = dom_fold_multi_batch(d, b->d_layers + b->layer_off[1 + r0], b->d_layers + b->layer_off[id], L - r0, r0, steps, &b->d_chal->c_mont,
                                            (uint32_t)(sizeof(BatchChal) / 4), b->d_work, (uint32_t)nb, b->stream, nullptr))) return rc;   // prover.rs:201-211, steps times
@@ -756,11 +758,11 @@ int zk_batch_prove(zk_batch* b, uint8_t* proofs_out, size_t stride, uint8_t* sta
             if (leaf_steps) {
                 b->tree_steps[id] = (uint8_t)leaf_steps;
                 HIPCHK(launch_merkle_build_coset_batch(b->d_layers + b->layer_off[id], L - r0 - steps, leaf_steps, lb, b->d_trees + b->tree_off[id],
-                                                       b->stream, nullptr, bmail(b, id, L - r0 - steps - leaf_steps), hash));
+                                                       b->stream, nullptr, bmail(b, id, L - r0 - steps - leaf_steps, lb), hash));
             } else
             HIPCHK(launch_merkle_build(b->d_layers + b->layer_off[id], L - r0 - steps + lb, b->d_trees + b->tree_off[id], b->stream, nullptr,
-                                       bmail(b, id, L - r0 - steps), hash));      // prover.rs:214
-            if ((rc = bpost(b, id, L - r0 - steps - leaf_steps))) return rc;
+                                       bmail(b, id, L - r0 - steps, lb), hash));      // prover.rs:214
+            if ((rc = bpost(b, id, L - r0 - steps - leaf_steps, lb))) return rc;
         }
     }
     lap("lde .. last roots");
@@ -855,6 +857,172 @@ int zk_batch_prove(zk_batch* b, uint8_t* proofs_out, size_t stride, uint8_t* sta
     });
     lap("decommit hashing + copy out");
     if (bad.load()) return fail(ZK_ERR_STATE, "zk_batch_prove: unexpected proof length");
+    return ZK_OK;
+}
+
+// ONE proof of the batch's 2^log_batch resident traces (transcript.hpp "lb"): the f trees of zk_batch_prove, then one FRI over
+// CP = sum_p cp_p.  f: the LDE and the heap over all f layers are zk_batch_prove's launches, and the level they hand over is committed
+// once.  3 alphas per statement go into the BatchChal table; launch_compose_sum_batch writes CP into the first N words of layer 1.
+// From there on the stages of zk_batch_prove run at width one (lb = 0 in every launch and helper): proof 0's share of each layer slot
+// and heap, h_chal[0].c_mont for the challenge, row 0 of the final-polynomial table.  The gather buffers of the batch always hold a
+// shared proof's openings (3M f tuples and one set of group tuples per query against M sets of both).
+// Afterwards tree 0 is the batch's f heap as ever; the ids >= 1 hold one statement's worth and are reported as not built.
+int zk_batch_prove_shared(zk_batch* b, uint8_t* proof_out, size_t cap, size_t* proof_len, uint8_t state_out[32]) {
+    if (!b || !proof_out || !proof_len || !state_out) return fail(ZK_ERR_INVALID, "zk_batch_prove_shared: null argument");
+    if (b->single || b->lb > kMaxSharedLog)
+        return fail(ZK_ERR_INVALID, "zk_batch_prove_shared: need 1 <= log_batch <= %u (got %u): a batch of one makes a plain proof (zk_batch_prove)", kMaxSharedLog, b->lb);
+    if (!b->have_traces) return fail(ZK_ERR_STATE, "zk_batch_prove_shared: no traces");
+    BusyScope busy(b);
+    if (!busy.mine) return fail(ZK_ERR_STATE, "zk_batch_prove_shared: another call (zk_batch_prove or a setter) is running on this batch");
+    ProofFormat f = b->fmt;
+    f.lb = b->lb;
+    const uint32_t Q = f.q, K = f.fold, stop = f.stop, G = f.groups(), lb = b->lb;
+    const int hash = b->hash;
+    const bool coset = f.coset;
+    const size_t plen = f.data_len();
+    *proof_len = plen;
+    if (cap < plen) return fail(ZK_ERR_BUFFER, "zk_batch_prove_shared: buffer of %zu bytes < proof length %zu", cap, plen);
+    size_t nv = 0, ndg = 0;                                               // values and digests the Q queries open
+    bopenings(f, &nv, &ndg);
+    nv *= Q; ndg *= Q;
+    if (nv + ndg > b->batch * Q * (b->per_proof_vals + b->per_proof_digs)) return fail(ZK_ERR_STATE, "zk_batch_prove_shared: gather buffers too small");
+    HIPCHK(hipSetDevice(b->device));
+    const size_t nb = b->batch, N = b->N, B = b->B;
+    const uint32_t R = b->R, L = b->L, Rp = f.rounds();
+    const zk_dom* d = b->dom;
+    Channel ch;
+    ch.data.reserve(plen);
+    int rc;
+    auto commit_level = [&](const uint32_t* from, size_t count) {       // `count` digests (state words) in ONE commit
+        std::vector<uint8_t> cb(32 * count);
+        for (size_t i = 0; i < count; ++i) digest_words_to_bytes(from + 8 * i, cb.data() + 32 * i);
+        ch.commit_bytes(cb.data(), cb.size());
+    };
+    // f of every statement, committed together (prover.rs:60-85): zk_batch_prove's launches
+    if ((rc = dom_lde(d, b->d_trace, b->d_coef, b->d_layers + b->layer_off[0], b->stream, nullptr, (uint32_t)nb))) return rc;
+    b->stage_used = 0; b->n_segs = 0; b->seg_words = 0;
+    b->skipped_trees = ~(uint64_t)1;                                      // only tree 0 is the batch's
+    b->proved_fold = K; b->proved_stop = stop; b->proved_hash = hash;
+    memset(b->tree_steps, 0, sizeof b->tree_steps);
+    memset(b->tree_cap, 0, sizeof b->tree_cap);
+    b->proved = true;
+    HIPCHK(launch_merkle_build(b->d_layers + b->layer_off[0], L + lb, b->d_trees + b->tree_off[0], b->stream, nullptr, bmail(b, 0, L, lb), hash));
+    if ((rc = bpost(b, 0, L, lb))) return rc;
+    ComposeBatchArgs ca;
+    {
+        const uint32_t one[3] = {1, 1, 1};
+        if ((rc = compose_args(d, b->d_layers + b->layer_off[0], b->d_layers + b->layer_off[1], 0, 0, one, ca.a))) return rc;
+        ca.chal = b->d_chal;
+    }
+    const uint32_t g2 = mulmod(d->g, d->g);
+    if ((rc = bwait_roots(b))) return rc;
+    const uint32_t* roots = bfinish_roots(b, 0, L, lb);
+    commit_level(roots, nb << b->tree_cap[0]);
+    for (size_t p = 0; p < nb; ++p) {                                     // prover.rs:163-165 per statement, statement-major
+        const uint32_t a0 = ch.get_u32() % P, a1 = ch.get_u32() % P, a2 = ch.get_u32() % P;
+        BatchChal& c = b->h_chal[p];
+        c.first = b->first[p]; c.last = b->last[p];
+        c.alpha0_mont = to_mont(a0); c.alpha1g2_mont = to_mont(mulmod(a1, g2)); c.alpha2_mont = to_mont(a2);
+    }
+    if ((rc = bchal_upload(b))) return rc;
+    HIPCHK(launch_compose_sum_batch(ca, lb, b->stream, nullptr));         // CP: the first N words of layer 1
+    const uint32_t s0 = f.slots_log(0);
+    b->tree_steps[1] = (uint8_t)s0;
+    if (s0) HIPCHK(launch_merkle_build_coset_batch(b->d_layers + b->layer_off[1], L, s0, 0, b->d_trees + b->tree_off[1], b->stream, nullptr, bmail(b, 1, L - s0, 0), hash));
+    else HIPCHK(launch_merkle_build(b->d_layers + b->layer_off[1], L, b->d_trees + b->tree_off[1], b->stream, nullptr, bmail(b, 1, L, 0), hash));
+    if ((rc = bpost(b, 1, L - s0, 0))) return rc;
+    const bool fused = K == 1 && !coset && !stop;
+    for (uint32_t j = 0;; ++j) {                                          // zk_batch_prove's loop over the groups, one proof wide
+        const uint32_t r0 = f.round0(j);
+        if ((rc = bwait_roots(b))) return rc;
+        roots = bfinish_roots(b, 1 + r0, L - r0 - b->tree_steps[1 + r0], 0);
+        commit_level(roots, (size_t)1 << b->tree_cap[1 + r0]);            // prover.rs:180 / :224
+        if (j == G) break;
+        const uint32_t steps = f.steps(j), id = f.tree_id(j + 1);
+        const uint32_t beta = ch.get_u32();                               // prover.rs:200, once per group
+        b->h_chal[0].c_mont = fused ? to_mont(mulmod(beta % P, mulmod(invmod(powmod(d->shift, (uint64_t)1 << r0)), invmod(2)))) : beta;
+        HIPCHK(hipMemcpyAsync(b->d_chal, b->h_chal, sizeof(BatchChal), hipMemcpyHostToDevice, b->stream));
+        if (fused) {
+            FoldBatchArgs fa;
+            if ((rc = fold_args(d, b->d_layers + b->layer_off[1 + r0], b->d_layers + b->layer_off[id], L - r0, r0, 0, fa.a))) return rc;
+            fa.chal = b->d_chal;
+            HIPCHK(launch_fold_merkle_batch(fa, 0, b->d_trees + b->tree_off[id], b->stream, nullptr, bmail(b, id, L - r0 - 1, 0), hash));
+            if ((rc = bpost(b, id, L - r0 - 1, 0))) return rc;
+            continue;
+        }
+        if ((rc = dom_fold_multi_batch(d, b->d_layers + b->layer_off[1 + r0], b->d_layers + b->layer_off[id], L - r0, r0, steps, &b->d_chal->c_mont,
+                                       (uint32_t)(sizeof(BatchChal) / 4), b->d_work, 1u, b->stream, nullptr))) return rc;
+        if (stop && j + 1 == G) break;                                    // the layer the proof stops at: no tree
+        const uint32_t leaf_steps = f.slots_log(j + 1);
+        b->tree_steps[id] = (uint8_t)leaf_steps;
+        if (leaf_steps) HIPCHK(launch_merkle_build_coset_batch(b->d_layers + b->layer_off[id], L - r0 - steps, leaf_steps, 0, b->d_trees + b->tree_off[id], b->stream,
+                                                               nullptr, bmail(b, id, L - r0 - steps - leaf_steps, 0), hash));
+        else HIPCHK(launch_merkle_build(b->d_layers + b->layer_off[id], L - r0 - steps, b->d_trees + b->tree_off[id], b->stream, nullptr,
+                                        bmail(b, id, L - r0 - steps, 0), hash));
+        if ((rc = bpost(b, id, L - r0 - steps - leaf_steps, 0))) return rc;
+    }
+    static const char kWhich[] = "some trace of the batch does not satisfy the constraints (the sum does not tell which)";
+    if (stop) {                                                           // the final polynomial of the sum: row 0 of the tables
+        const size_t ncoef = (size_t)1 << stop;
+        if ((rc = dom_final_poly_batch(d, b->d_layers + b->layer_off[1 + Rp], b->d_final, L - Rp, Rp, (uint32_t)ncoef, 1u, b->stream, nullptr))) return rc;
+        HIPCHK(hipMemcpyAsync(b->h_final, b->d_final, (ncoef + 1) * 4, hipMemcpyDeviceToHost, b->stream));
+        HIPCHK(hipStreamSynchronize(b->stream));
+        if (b->h_final[0])
+            return fail(ZK_ERR_CHECK, "zk_batch_prove_shared: final FRI layer has degree >= 2^%u (%u non-zero coefficients above): %s", stop, b->h_final[0], kWhich);
+        uint8_t cb[4 << kMaxStopLog];
+        for (size_t k = 0; k < ncoef; ++k)
+            for (int i = 0; i < 4; ++i) cb[4 * k + i] = (uint8_t)(b->h_final[1 + k] >> (8 * i));
+        ch.commit_bytes(cb, 4 * ncoef);
+    } else {                                                              // prover.rs:238, :251, :254
+        HIPCHK(hipMemcpyAsync(b->h_last, b->d_layers + b->layer_off[1 + R], B * 4, hipMemcpyDeviceToHost, b->stream));
+        HIPCHK(hipStreamSynchronize(b->stream));
+        for (size_t i = 1; i < B; ++i)
+            if (b->h_last[i] != b->h_last[0]) return fail(ZK_ERR_CHECK, "zk_batch_prove_shared: last FRI layer is not constant (prover.rs:238): %s", kWhich);
+        ch.commit_u32(b->h_last[0]);
+    }
+    if (f.grind) {
+        std::vector<Channel> one(1, ch);
+        if ((rc = bgrind(b, one))) return rc;
+        ch = one[0];
+    }
+    uint32_t qraw[kMaxQueries];
+    for (uint32_t k = 0; k < Q; ++k) qraw[k] = ch.get_u32();              // prover.rs:263
+    // the openings: layer 0 and tree 0 at the batch's width (leaf = (p << L) + index), everything else at width one
+    uint64_t *vo = b->h_goff, *dofs = b->h_goff + nv;
+    std::vector<size_t> nodes;
+    for (uint32_t k = 0; k < Q; ++k)
+        f.for_each_opening((size_t)qraw[k] % (N - 2 * B), [&](uint32_t layer, uint32_t log_leaves, size_t leaf, uint32_t slots_log) {
+            const uint32_t w = layer == 0 ? lb : 0;
+            const size_t p = leaf >> log_leaves, at = leaf & (((size_t)1 << log_leaves) - 1);   // p = 0 unless layer 0
+            for (size_t u = 0; u < ((size_t)1 << slots_log); ++u) *vo++ = b->layer_off[layer] + (p << (log_leaves + slots_log)) + at + (u << log_leaves);
+            nodes.clear();
+            path_nodes((size_t)1 << log_leaves, at, nodes);
+            nodes.resize(log_leaves - b->tree_cap[layer]);
+            uint32_t dd = log_leaves;
+            for (size_t nd : nodes) {
+                const size_t i = nd - (((size_t)1 << dd) - 1);
+                *dofs++ = (uint64_t)b->tree_off[layer] + (uint64_t)((((size_t)1 << (w + dd)) - 1) + (p << dd) + i) * 8;
+                --dd;
+            }
+        });
+    if ((size_t)(vo - b->h_goff) != nv || (size_t)(dofs - b->h_goff) != nv + ndg) return fail(ZK_ERR_STATE, "zk_batch_prove_shared: unexpected number of openings");
+    HIPCHK(hipMemcpyAsync(b->d_goff, b->h_goff, (nv + ndg) * 8, hipMemcpyHostToDevice, b->stream));
+    HIPCHK(launch_scatter(b->d_stage, b->d_segs, b->n_segs, b->seg_words, b->d_trees, nullptr, b->stream, nullptr));   // host-built levels
+    HIPCHK(launch_gather(b->d_layers, b->d_goff, (uint32_t)nv, 1, b->d_gout, b->stream, nullptr));
+    HIPCHK(launch_gather(b->d_trees, b->d_goff + nv, (uint32_t)ndg, 8, b->d_gout + nv, b->stream, nullptr));
+    HIPCHK(hipMemcpyAsync(b->h_gout, b->d_gout, (nv + ndg * 8) * 4, hipMemcpyDeviceToHost, b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    const uint32_t* vals = b->h_gout;
+    const uint32_t* dw = b->h_gout + nv;
+    std::vector<uint8_t> buf(Channel::group_bytes((size_t)1 << f.steps(0), L, false));
+    for (uint32_t q = 0; q < Q; ++q)
+        f.for_each_tuple([&](size_t s, size_t pl, bool one_leaf) {
+            ch.commit_group(buf.data(), s, pl, [&](size_t t) { return vals[t]; }, [&](size_t i, uint8_t* out) { digest_words_to_bytes(dw + 8 * i, out); }, one_leaf);
+            vals += s; dw += 8 * (one_leaf ? 1 : s) * pl;
+        });
+    if (ch.data.size() != plen) return fail(ZK_ERR_STATE, "zk_batch_prove_shared: unexpected proof length");
+    memcpy(proof_out, ch.data.data(), plen);
+    memcpy(state_out, ch.state, 32);
     return ZK_OK;
 }
 

@@ -451,6 +451,111 @@ hipError_t launch_compose_batch(const ComposeBatchArgs& a, uint32_t log_batch, h
     return hipGetLastError();
 }
 
+// CP = sum_b cp_b (mod P) of a proof-major batch, for the shared proof (transcript.hpp "lb"): a.cp[i], i < N, from a.f = [batch][N].
+// The denominators of the three constraints, x and the vanishing product depend on i alone, so they are taken once per i and the sum
+// runs over the numerators:
+//   CP(i) = inv0 S0 + inv2 S1 + y S2,  S0 = sum_b alpha0_b (f_b[i] - first_b),  S1 = sum_b alpha1g2_b (f_b[i] - last_b),
+//   S2 = sum_b alpha2_b (f_b[i+2B] - f_b[i+B]^2 - f_b[i]^2)
+// with compose_eval's Montgomery scales: S0 and S1 are canonical sums, S2 carries R^-1 and y = V / (x^n - 1) R^2.  Per statement that is
+// three loads and six multiplications per value; chal[b] is read wave-uniformly (b is the loop counter).
+__device__ __forceinline__ void compose_sum_term(uint32_t f0, uint32_t f1, uint32_t f2, uint32_t first, uint32_t last, uint32_t al0, uint32_t al1g2,
+                                                 uint32_t al2, uint32_t& s0, uint32_t& s1, uint32_t& s2) {
+    s0 = add(s0, mont_mul(sub(f0, first), al0));
+    s1 = add(s1, mont_mul(sub(f0, last), al1g2));
+    const uint32_t num = sub(sub(mont_mul(f2, 1u), mont_mul(f1, f1)), mont_mul(f0, f0));
+    s2 = add(s2, mont_mul(num, al2));
+}
+__device__ __forceinline__ uint32_t compose_sum_finish(const ComposeArgs& a, uint32_t s0, uint32_t s1, uint32_t s2, uint32_t inv0, uint32_t inv2, uint32_t x,
+                                                       uint32_t zz) {
+    const uint32_t v3 = mont_mul(mont_mul(sub(x, a.gm3_mont), sub(x, a.gm2_mont)), sub(x, a.gm1_mont));
+    return add(add(mont_mul(s0, inv0), mont_mul(s1, inv2)), mont_mul(s2, mont_mul(v3, zz)));
+}
+// vec: four consecutive i per thread with 16-byte accesses and compose_kernel4's taps (whole vectors for B >= 4, windows of the vectors
+// at i and i + 4 for B = 1, 2); the next statement's vectors are loaded before the arithmetic of the current one.  !vec (logN < 4, or
+// unaligned pointers): one i per thread.
+__global__ __launch_bounds__(256) void compose_sum_batch_kernel(ComposeArgs a, const BatchChal* __restrict__ chal, uint32_t batch, uint32_t vec) {
+    const size_t N = (size_t)1 << a.logN;
+    const uint32_t B = 1u << a.log_b;
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (!vec) {
+        if (t >= N) return;
+        const size_t i1 = (t + B) & (N - 1), i2 = (t + 2 * (size_t)B) & (N - 1);
+        uint32_t s0 = 0, s1 = 0, s2 = 0;
+        for (uint32_t b = 0; b < batch; ++b) {
+            const uint32_t* f = a.f + ((size_t)b << a.logN);
+            compose_sum_term(f[t], f[i1], f[i2], chal[b].first, chal[b].last, chal[b].alpha0_mont, chal[b].alpha1g2_mont, chal[b].alpha2_mont, s0, s1, s2);
+        }
+        const uint32_t x = mont_mul(pow_lookup(a.htab, (uint32_t)t), a.w_mont);
+        a.cp[t] = compose_sum_finish(a, s0, s1, s2, a.inv_xm1[t], a.inv_xm1[i2], x, a.zz[t & (B - 1)]);
+        return;
+    }
+    const size_t i = t * 4;
+    if (i >= N) return;
+    const uint4* fv = reinterpret_cast<const uint4*>(a.f);
+    const uint4* iv = reinterpret_cast<const uint4*>(a.inv_xm1);
+    const bool wide = B >= 4;
+    // q2: the third vector of a statement (B < 4: the window needs two, and the third is the second again)
+    const size_t q0 = i >> 2, q1 = ((i + (wide ? B : 4u)) & (N - 1)) >> 2, q2 = wide ? ((i + 2 * (size_t)B) & (N - 1)) >> 2 : q1, stride = N >> 2;
+    uint32_t inv0[4], inv2[4], zz[4];
+    {
+        const uint4 w0 = iv[q0];
+        inv0[0] = w0.x; inv0[1] = w0.y; inv0[2] = w0.z; inv0[3] = w0.w;
+        if (wide) {
+            const uint4 w2 = iv[q2];   // wide: q2 is the vector at i + 2B
+            inv2[0] = w2.x; inv2[1] = w2.y; inv2[2] = w2.z; inv2[3] = w2.w;
+            const uint32_t z0 = (uint32_t)i & (B - 1);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) zz[k] = a.zz[z0 + k];
+        } else {
+            const uint4 w1 = iv[q1];
+            const uint32_t iw[8] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w};
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                inv2[k] = B == 1 ? iw[k + 2] : iw[k + 4];
+                zz[k] = B == 1 ? a.zz[0] : a.zz[k & 1];
+            }
+        }
+    }
+    uint32_t s0[4] = {0, 0, 0, 0}, s1[4] = {0, 0, 0, 0}, s2[4] = {0, 0, 0, 0};
+    uint4 c0 = fv[q0], c1 = fv[q1], c2 = fv[q2];
+    for (uint32_t b = 0; b < batch; ++b) {
+        uint4 n0 = c0, n1 = c1, n2 = c2;
+        if (b + 1 < batch) {                                  // the next statement's loads, in flight across this one's arithmetic
+            const size_t nx = (size_t)(b + 1) * stride;
+            n0 = fv[nx + q0]; n1 = fv[nx + q1]; n2 = fv[nx + q2];
+        }
+        const uint32_t first = chal[b].first, last = chal[b].last, al0 = chal[b].alpha0_mont, al1g2 = chal[b].alpha1g2_mont, al2 = chal[b].alpha2_mont;
+        const uint32_t fw[8] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w};
+        const uint32_t f2w[4] = {c2.x, c2.y, c2.z, c2.w};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const uint32_t f1 = wide ? fw[4 + k] : B == 1 ? fw[k + 1] : fw[k + 2];
+            const uint32_t f2 = wide ? f2w[k] : B == 1 ? fw[k + 2] : fw[k + 4];
+            compose_sum_term(fw[k], f1, f2, first, last, al0, al1g2, al2, s0[k], s1[k], s2[k]);
+        }
+        c0 = n0; c1 = n1; c2 = n2;
+    }
+    uint32_t x = mont_mul(pow_lookup(a.htab, (uint32_t)i), a.w_mont);
+    const uint32_t h = pow_lookup(a.htab, 1u);
+    uint32_t r[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        r[k] = compose_sum_finish(a, s0[k], s1[k], s2[k], inv0[k], inv2[k], x, zz[k]);
+        if (k < 3) x = mont_mul(x, h);
+    }
+    reinterpret_cast<uint4*>(a.cp)[i >> 2] = make_uint4(r[0], r[1], r[2], r[3]);
+}
+hipError_t launch_compose_sum_batch(const ComposeBatchArgs& a, uint32_t log_batch, hipStream_t s, Profiler* prof) {
+    if (!a.chal || a.a.logN + log_batch > 32) return hipErrorInvalidValue;
+    const size_t N = (size_t)1 << a.a.logN;
+    const uint32_t batch = 1u << log_batch;
+    ScopedKernelTimer tm(prof, K_COMPOSE, 4.0 * (double)N * (double)batch + 4.0 * (double)N, s);   // read every f once, write CP once
+    const bool aligned = ((reinterpret_cast<uintptr_t>(a.a.f) | reinterpret_cast<uintptr_t>(a.a.inv_xm1) | reinterpret_cast<uintptr_t>(a.a.cp)) & 15u) == 0;
+    const uint32_t vec = a.a.logN >= 4 && aligned;
+    hipLaunchKernelGGL(compose_sum_batch_kernel, dim3((uint32_t)(((vec ? N / 4 : N) + 255) / 256)), dim3(256), 0, s, a.a, a.chal, batch, vec);
+    return hipGetLastError();
+}
+
 // ===========================================================================
 // FRI fold
 // ===========================================================================

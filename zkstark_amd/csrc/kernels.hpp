@@ -338,6 +338,9 @@ hipError_t launch_fold_merkle_batch(const FoldBatchArgs& a, uint32_t log_batch, 
 // cp of the whole batch without a tree (coset leaves: the tree over cp is launch_merkle_build_coset_batch's): a.a.cp[b N + i], the
 // arithmetic of launch_compose_merkle_batch's leaf source
 hipError_t launch_compose_batch(const ComposeBatchArgs& a, uint32_t log_batch, hipStream_t s, Profiler* prof = nullptr);
+// The shared proof (transcript.hpp "lb"): a.a.cp[i] = sum over the batch of cp_b[i] (mod P), i < N, from a.a.f = [batch][N] and each
+// statement's own constants in a.chal; the denominators are factored out of the sum.  Reads 4 batch N bytes, writes 4 N.
+hipError_t launch_compose_sum_batch(const ComposeBatchArgs& a, uint32_t log_batch, hipStream_t s, Profiler* prof = nullptr);
 // Coset leaves over a proof-major batch (vals: [batch][2^log_len], steps 1..3 < log_len): proof p's tree has m = 2^(log_len - steps)
 // leaves, leaf c holding vals[(p << log_len) + c + u m], u < 2^steps; the trees are the bottom of one heap over batch * m leaves
 // (nodes: (2 batch m - 1) * 8 words) whose nodes of depth log_batch are the per-proof roots (mail.top as for the other batch builds).

@@ -119,6 +119,16 @@ inline size_t coset_leaf(size_t x, uint32_t log_len, uint32_t steps, uint32_t t)
 // entries a path lands in; a changed entry that no path lands in is caught by verify_transcript alone (the challenge after it, as for a
 // changed root).
 constexpr uint32_t kMaxCapLog = 8;
+// lb = log_batch in 0..kMaxSharedLog, the shared proof: ONE proof of M = 2^lb statements of one size, statement p being
+// fibsq with its own public_last[p].  lb = 0 is the format above, byte for byte.  The M trace polynomials f_p are committed together: the
+// header opens with the 2^(lb + ce_f) digests of depth lb + ce_f of the heap over all M f layers (statement p's cap: entries p 2^ce_f
+// onwards; ONE commit), then 3M alphas, statement-major.  From cp on the header is a single proof's, over CP = sum_p cp_p (mod P), cp_p
+// the composition of statement p with its own three alphas and its own public_last.  Per query the three f tuples of statement 0, then
+// of statement 1, ... (each a value and f_path() digests into statement p's subtree), then the cp tuple and the group tuples as ever.
+// verify_proof: -2 compares sum_p (alpha0_p p0_p + alpha1_p p1_p + alpha2_p p2_p) at x with the cp value opened; -3 covers the 3M f path
+// lengths (and cp's); -4 / -5 / -6 the path of f_p(x) / f_p(gx) / f_p(g^2 x) of the first failing tuple in wire order; the rest as ever.
+// verify_transcript counts 3M + G + q challenges; 3 * 256 + 30 + 64 keeps -(1000 + k) clear of -1998.
+constexpr uint32_t kMaxSharedLog = 8;
 inline uint32_t cap_eff(uint32_t cap, uint32_t lg) { return cap < lg - 1 ? cap : lg - 1; }   // lg >= 1 for every committed tree
 
 // One proof format: the settings above and everything that follows from them.  The Merkle hash and public_last are not part of it.
@@ -128,11 +138,12 @@ struct ProofFormat {
     uint32_t log_n = 0, log_b = 0, q = 1, grind = 0, fold = 1;
     bool coset = false;
     uint32_t stop = 0, cap = 0;
+    uint32_t lb = 0;                                                         // shared proof of 2^lb statements (0: a plain proof)
 
     // what verify_proof and verify_transcript take (they answer -1 to anything else); every member below assumes it
     bool ok() const {
         return log_n >= 2 && log_b >= 1 && log_n + log_b <= 30 && q >= 1 && q <= 64 && grind <= kMaxGrindBits && fold >= 1 && fold <= kMaxFoldLog &&
-               stop_ok(log_n, log_b, stop) && cap <= kMaxCapLog;
+               stop_ok(log_n, log_b, stop) && cap <= kMaxCapLog && lb <= kMaxSharedLog;
     }
     // ---- geometry.  Group j < G folds the rounds round0(j) .. round0(j) + steps(j) - 1; tree j is the one over its INPUT layer.
     // j = G: the last layer (round0 = rounds, steps = 0), whose tree has one-value leaves and exists only when stop = 0.
@@ -151,11 +162,12 @@ struct ProofFormat {
     size_t tree_path(uint32_t j) const { return (size_t)tree_log(j) - tree_cap(j); }
 
     // ---- the header in wire order: fn(what, j, bytes) -> bool, false ends the walk (and is returned).  kAlphas, kBeta and kRaws are
-    // challenges of 4 bytes each (3, 1 and q of them), everything else is ONE commit.  kTree j: the commitment of tree j.
+    // challenges of 4 bytes each (3 per statement, 1 and q of them), everything else is ONE commit.  kTree j: the commitment of tree j.
+    // kFTree: the caps of all 2^lb statements' f trees, statement-major, in one commit.
     enum Head { kFTree, kAlphas, kTree, kBeta, kFinal, kNonce, kRaws };
     template <class Fn> bool for_each_head(Fn fn) const {
         const uint32_t G = groups();
-        if (!fn(kFTree, 0u, (size_t)32 << f_cap()) || !fn(kAlphas, 0u, (size_t)12) || !fn(kTree, 0u, (size_t)32 << tree_cap(0))) return false;
+        if (!fn(kFTree, 0u, (size_t)32 << (lb + f_cap())) || !fn(kAlphas, 0u, (size_t)12 << lb) || !fn(kTree, 0u, (size_t)32 << tree_cap(0))) return false;
         for (uint32_t j = 0; j < G; ++j) {
             if (!fn(kBeta, j, (size_t)4)) return false;                      // group j's challenge, then the tree over its output
             if ((j + 1 < G || last_tree()) && !fn(kTree, j + 1, (size_t)32 << tree_cap(j + 1))) return false;
@@ -165,18 +177,23 @@ struct ProofFormat {
         return fn(kRaws, 0u, (size_t)4 * q);
     }
     // ---- the tuples of one query in wire order: fn(s values, digests per path, one_leaf) as Channel::commit_group takes them.
-    // f(x), f(gx), f(g^2 x) and, with one-value leaves, cp(x); then one tuple per group.
+    // f(x), f(gx), f(g^2 x) of every statement and, with one-value leaves, cp(x); then one tuple per group.
     template <class Fn> void for_each_tuple(Fn fn) const {
-        for (int i = 0; i < (coset ? 3 : 4); ++i) fn((size_t)1, i < 3 ? f_path() : tree_path(0), false);
+        for (size_t i = 0; i < ((size_t)3 << lb); ++i) fn((size_t)1, f_path(), false);
+        if (!coset) fn((size_t)1, tree_path(0), false);
         for (uint32_t j = 0, G = groups(); j < G; ++j) fn((size_t)1 << steps(j), tree_path(j), coset);
     }
     // ---- the openings of one query in the same order, for x = query raw % (N - 2B): f at x, x + B, x + 2B (layer 0) and cp at x
     // (layer 1) (prover.rs:266-277), then per group the s coset leaves of its input layer.  An opening is one LEAF and its path:
     // open(layer id, log2 of the tree's leaf count, leaf index, slots_log); the leaf holds the 2^slots_log values
     // layer[leaf + u 2^(log2 leaf count)], u < 2^slots_log (0: a one-value leaf).  Both provers rely on this leaf order.
+    // Shared proof: statement p's f openings are the leaves (p << L) + x .. of layer 0, i.e. of the proof-major [2^lb][N] array.
     template <class Open> void for_each_opening(size_t x, Open open) const {
         const size_t B = (size_t)1 << log_b;
-        open(0u, L(), x, 0u); open(0u, L(), x + B, 0u); open(0u, L(), x + 2 * B, 0u);
+        for (size_t p = 0; p < ((size_t)1 << lb); ++p) {
+            const size_t at = (p << L()) + x;
+            open(0u, L(), at, 0u); open(0u, L(), at + B, 0u); open(0u, L(), at + 2 * B, 0u);
+        }
         if (!coset) open(1u, L(), x, 0u);
         for (uint32_t j = 0, G = groups(); j < G; ++j) {
             const uint32_t lg = tree_log(j), st = steps(j);
@@ -285,11 +302,14 @@ inline void compute_root_from_path(uint32_t element, size_t index, const uint8_t
 // coefficients, each reduced % P on reading, as raw challenges are.
 // cap > 0 (Merkle caps, above): every root of the header is 2^ce digests, the path lengths expected are lg - ce, and a path is
 // compared with the cap entry it lands in, under the check number it has for the root.  A proof of another length: -1.
-inline int verify_proof(const uint8_t* data, size_t len, const ProofFormat& fmt, uint32_t public_last, int hash) {
+// lb > 0 (the shared proof, above): public_last holds 2^lb values; the f tuples are 3 per statement, fv[3 p + k], and the cp value is
+// fv[3 M].  lb = 0: one statement, fv[0..3] as ever.
+inline int verify_proof(const uint8_t* data, size_t len, const ProofFormat& fmt, const uint32_t* public_last, int hash) {
     if (!fmt.ok()) return -1;
-    if ((fmt.stop || fmt.cap) && len != fmt.data_len()) return -1;   // a stopped or capped proof of another length: -1, strict or not
+    if ((fmt.stop || fmt.cap || fmt.lb) && len != fmt.data_len()) return -1;   // a stopped, capped or shared proof of another length: -1, strict or not
     const bool coset = fmt.coset;
-    const uint32_t nf = coset ? 3 : 4;                       // f(x), f(gx), f(g^2 x) and, with one-value leaves, cp(x)
+    const size_t M = (size_t)1 << fmt.lb;
+    const uint32_t ncp = 3 * (uint32_t)M, nf = ncp + (coset ? 0 : 1);   // f(x), f(gx), f(g^2 x) per statement and, with one-value leaves, cp(x)
     const size_t n = (size_t)1 << fmt.log_n, B = (size_t)1 << fmt.log_b, N = n << fmt.log_b;
     const uint32_t L = fmt.L(), G = fmt.groups();
     const uint8_t* p = data;
@@ -329,10 +349,10 @@ inline int verify_proof(const uint8_t* data, size_t len, const ProofFormat& fmt,
         return true;
     });
     if (bad) return -1;
-    const uint32_t alpha[3] = {le32(alphas), le32(alphas + 4), le32(alphas + 8)};
     const uint32_t g = root_of_unity(fmt.log_n), h = root_of_unity(L);
     for (uint32_t qk = 0; qk < fmt.q; ++qk) {
-        uint32_t fv[4]; const uint8_t* fp[4]; size_t fpl[4] = {0, 0, 0, 0};
+        uint32_t fv[3 * (1u << kMaxSharedLog) + 1]; const uint8_t* fp[3 * (1u << kMaxSharedLog) + 1]; size_t fpl[3 * (1u << kMaxSharedLog) + 1];
+        for (uint32_t t = 0; t <= ncp; ++t) fpl[t] = 0;
         uint32_t lv[40][8]; const uint8_t* lp[40][8]; size_t lpl[40][8];
         uint32_t i = 0;                                      // tuple i: an f / cp tuple, then group i - nf
         fmt.for_each_tuple([&](size_t s, size_t, bool one_leaf) {
@@ -353,18 +373,24 @@ inline int verify_proof(const uint8_t* data, size_t len, const ProofFormat& fmt,
             const size_t rot = (tp & (((size_t)1 << lg) - 1)) >> (lg - steps);
             return lv[j][(rot + t) & ((1u << steps) - 1u)];
         };
-        if (coset) fv[3] = group_val(0, 0);
+        if (coset) fv[ncp] = group_val(0, 0);
         const uint32_t x = mulmod(GEN_W, powmod(h, tp));
-        {   // proof.rs:63-77
-            uint32_t f_x = fv[0] % P, f_gx = fv[1] % P, f_ggx = fv[2] % P;
-            uint32_t gm1 = invmod(g), gm2 = mulmod(gm1, gm1), gm3 = mulmod(gm2, gm1);
-            uint32_t p0 = mulmod(sub(f_x, 1), invmod(sub(x, 1)));
-            uint32_t p1 = mulmod(sub(f_x, public_last % P), invmod(sub(x, gm2)));
-            uint32_t num = sub(sub(f_ggx, mulmod(f_gx, f_gx)), mulmod(f_x, f_x));
-            uint32_t den = mulmod(sub(powmod(x, n), 1), invmod(mulmod(mulmod(sub(x, gm3), sub(x, gm2)), sub(x, gm1))));
-            uint32_t p2 = mulmod(num, invmod(den));
-            uint32_t cp0 = add(add(mulmod(alpha[0] % P, p0), mulmod(alpha[1] % P, p1)), mulmod(alpha[2] % P, p2));
-            if (cp0 != fv[3]) return -2;
+        {   // proof.rs:63-77, summed over the statements (the denominators depend on x alone)
+            const uint32_t gm1 = invmod(g), gm2 = mulmod(gm1, gm1), gm3 = mulmod(gm2, gm1);
+            const uint32_t i0 = invmod(sub(x, 1)), i1 = invmod(sub(x, gm2));
+            const uint32_t den = mulmod(sub(powmod(x, n), 1), invmod(mulmod(mulmod(sub(x, gm3), sub(x, gm2)), sub(x, gm1))));
+            const uint32_t i2 = invmod(den);
+            uint32_t cp0 = 0;
+            for (size_t s = 0; s < M; ++s) {
+                const uint8_t* al = alphas + 12 * s;
+                uint32_t f_x = fv[3 * s] % P, f_gx = fv[3 * s + 1] % P, f_ggx = fv[3 * s + 2] % P;
+                uint32_t p0 = mulmod(sub(f_x, 1), i0);
+                uint32_t p1 = mulmod(sub(f_x, public_last[s] % P), i1);
+                uint32_t num = sub(sub(f_ggx, mulmod(f_gx, f_gx)), mulmod(f_x, f_x));
+                uint32_t p2 = mulmod(num, i2);
+                cp0 = add(cp0, add(add(mulmod(le32(al) % P, p0), mulmod(le32(al + 4) % P, p1)), mulmod(le32(al + 8) % P, p2)));
+            }
+            if (cp0 != fv[ncp]) return -2;
         }
         uint8_t root[32];
         // the path of leaf `idx` (s slots) climbs plen levels and must land on entry idx >> plen of the tree's cap (cap 0: on the root)
@@ -372,13 +398,16 @@ inline int verify_proof(const uint8_t* data, size_t len, const ProofFormat& fmt,
             compute_root_from_coset(slots, s, idx & (((size_t)1 << plen) - 1), path, plen, root, hash);
             return memcmp(root, entries + 32 * (idx >> plen), 32) != 0;
         };
-        for (int k = 0; k < 3; ++k) if (fpl[k] != fmt.f_path()) return -3;
-        if (!coset && fpl[3] != fmt.tree_path(0)) return -3;
-        // proof.rs:80-95
-        if (misses(&fv[0], 1, tp, fp[0], fpl[0], f_root)) return -4;
-        if (misses(&fv[1], 1, tp + B, fp[1], fpl[1], f_root)) return -5;
-        if (misses(&fv[2], 1, tp + 2 * B, fp[2], fpl[2], f_root)) return -6;
-        if (!coset && misses(&fv[3], 1, tp, fp[3], fpl[3], roots[0])) return -7;
+        for (uint32_t k = 0; k < ncp; ++k) if (fpl[k] != fmt.f_path()) return -3;
+        if (!coset && fpl[ncp] != fmt.tree_path(0)) return -3;
+        // proof.rs:80-95; statement s's paths land in its own 2^ce entries of the f commitment
+        for (size_t s = 0; s < M; ++s) {
+            const uint8_t* cap_s = f_root + ((size_t)32 << fmt.f_cap()) * s;
+            if (misses(&fv[3 * s], 1, tp, fp[3 * s], fpl[3 * s], cap_s)) return -4;
+            if (misses(&fv[3 * s + 1], 1, tp + B, fp[3 * s + 1], fpl[3 * s + 1], cap_s)) return -5;
+            if (misses(&fv[3 * s + 2], 1, tp + 2 * B, fp[3 * s + 2], fpl[3 * s + 2], cap_s)) return -6;
+        }
+        if (!coset && misses(&fv[ncp], 1, tp, fp[ncp], fpl[ncp], roots[0])) return -7;
         // proof.rs:101-126: the s opened values of a group folded pairwise (t with t + s/2, then again)
         const uint32_t inv2 = invmod(2);
         for (uint32_t j = 0; j < G; ++j) {
@@ -422,6 +451,9 @@ inline int verify_proof(const uint8_t* data, size_t len, const ProofFormat& fmt,
     if (left != 0) return -8;
     return 0;
 }
+inline int verify_proof(const uint8_t* data, size_t len, const ProofFormat& fmt, uint32_t public_last, int hash) {
+    return fmt.lb ? -1 : verify_proof(data, len, fmt, &public_last, hash);   // one statement
+}
 
 // the reference verifier reads the challenges out of the proof
 // (proof.rs:22-37) and never checks Proof.state (proof.rs:6); the author flags this as unfinished
@@ -433,6 +465,7 @@ inline int verify_proof(const uint8_t* data, size_t len, const ProofFormat& fmt,
 // bits (checked after the betas and before the first query challenge; it does not advance k) / -1999 for the state.
 // stop > 0: 3 + G' + q challenges; the coefficients are one commit, in the place of the last root and the free term.
 // cap > 0: every root commit is one commit of the tree's 2^ce digests, and a tuple's paths are ce digests shorter.
+// lb > 0: 3 * 2^lb + G + q challenges; the f level is one commit, each of the 3 * 2^lb f tuples of a query one commit.
 inline int verify_transcript(const uint8_t* data, size_t len, const uint8_t state[32], const ProofFormat& fmt) {
     if (!fmt.ok() || len != fmt.data_len()) return -1;
     Channel ch;

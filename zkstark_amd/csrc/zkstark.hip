@@ -1475,7 +1475,8 @@ int zk_last_transcript(const zk_ctx* c, zk_transcript_info* out) {
 // transcript replay first when a state is given, then the proof checks (transcript.hpp).  The check number goes to *check_out
 // (if any) and into the message: "proof rejected at check N" + reject_note, or, for the entry points that tell a failed replay
 // apart (replay_note not null), "transcript replay failed at check N" + replay_note.
-static int verify_entry(const char* who, const uint8_t* proof, size_t len, const uint8_t* state, const ProofFormat& fmt, uint32_t public_last,
+// public_last: one value per statement of the format (2^fmt.lb; a plain proof has one).
+static int verify_entry(const char* who, const uint8_t* proof, size_t len, const uint8_t* state, const ProofFormat& fmt, const uint32_t* public_last,
                         int hash_kind, int32_t* check_out, const char* replay_note, const char* reject_note) {
     if (hash_kind != ZK_HASH_SHA256 && hash_kind != ZK_HASH_FIELD && hash_kind != ZK_HASH_BLAKE2S) return fail(ZK_ERR_INVALID, "%s: unknown hash %d", who, hash_kind);
     if (fmt.fold < 1 || fmt.fold > kMaxFoldLog) return fail(ZK_ERR_INVALID, "%s: need 1 <= fold_log <= %u (got %u)", who, kMaxFoldLog, fmt.fold);
@@ -1492,7 +1493,7 @@ static const char kProofRs[] = " (proof.rs:15-149)";
 
 int zk_verify_ex(const uint8_t* proof, size_t len, uint32_t log_n, uint32_t log_b, uint32_t public_last, int hash_kind) {
     if (!proof) return fail(ZK_ERR_INVALID, "zk_verify: null proof");
-    return verify_entry("zk_verify", proof, len, nullptr, ProofFormat{.log_n = log_n, .log_b = log_b}, public_last, hash_kind, nullptr, nullptr, kProofRs);
+    return verify_entry("zk_verify", proof, len, nullptr, ProofFormat{.log_n = log_n, .log_b = log_b}, &public_last, hash_kind, nullptr, nullptr, kProofRs);
 }
 int zk_verify(const uint8_t* proof, size_t len, uint32_t log_n, uint32_t log_b, uint32_t public_last) {
     return zk_verify_ex(proof, len, log_n, log_b, public_last, ZK_HASH_SHA256);
@@ -1500,11 +1501,11 @@ int zk_verify(const uint8_t* proof, size_t len, uint32_t log_n, uint32_t log_b, 
 int zk_verify_queries(const uint8_t* proof, size_t len, const uint8_t* state, uint32_t log_n, uint32_t log_b, uint32_t public_last,
                       int hash_kind, uint32_t n_queries) {
     if (!proof) return fail(ZK_ERR_INVALID, "zk_verify_queries: null proof");
-    return verify_entry("zk_verify_queries", proof, len, state, ProofFormat{.log_n = log_n, .log_b = log_b, .q = n_queries}, public_last, hash_kind, nullptr, "", kProofRs);
+    return verify_entry("zk_verify_queries", proof, len, state, ProofFormat{.log_n = log_n, .log_b = log_b, .q = n_queries}, &public_last, hash_kind, nullptr, "", kProofRs);
 }
 int zk_verify_strict(const uint8_t* proof, size_t len, const uint8_t state[32], uint32_t log_n, uint32_t log_b, uint32_t public_last) {
     if (!proof || !state) return fail(ZK_ERR_INVALID, "zk_verify_strict: null argument");
-    return verify_entry("zk_verify", proof, len, state, ProofFormat{.log_n = log_n, .log_b = log_b}, public_last, ZK_HASH_SHA256, nullptr,
+    return verify_entry("zk_verify", proof, len, state, ProofFormat{.log_n = log_n, .log_b = log_b}, &public_last, ZK_HASH_SHA256, nullptr,
                         " (challenge not derived from the transcript, or final state mismatch)", kProofRs);
 }
 // zk_verify_cap is the general entry point; the older ones are its settings at their defaults, under their own names in argument errors
@@ -1512,7 +1513,7 @@ int zk_verify_strict(const uint8_t* proof, size_t len, const uint8_t state[32], 
 int zk_verify_grind(const uint8_t* proof, size_t len, const uint8_t* state, uint32_t log_n, uint32_t log_b, uint32_t public_last,
                     int hash_kind, uint32_t n_queries, uint32_t grind_bits, int32_t* check_out) {
     if (!proof || !check_out) return fail(ZK_ERR_INVALID, "zk_verify_check: null argument");
-    return verify_entry("zk_verify_check", proof, len, state, ProofFormat{.log_n = log_n, .log_b = log_b, .q = n_queries, .grind = grind_bits}, public_last, hash_kind,
+    return verify_entry("zk_verify_check", proof, len, state, ProofFormat{.log_n = log_n, .log_b = log_b, .q = n_queries, .grind = grind_bits}, &public_last, hash_kind,
                         check_out, nullptr, "");
 }
 int zk_verify_check(const uint8_t* proof, size_t len, const uint8_t* state, uint32_t log_n, uint32_t log_b, uint32_t public_last,
@@ -1526,14 +1527,14 @@ int zk_verify_fold(const uint8_t* proof, size_t len, const uint8_t* state, uint3
     if (!proof || !check_out) return fail(ZK_ERR_INVALID, "zk_verify_fold: null argument");
     if (hash_kind == ZK_HASH_BLAKE2S) return fail(ZK_ERR_INVALID, "zk_verify_fold: BLAKE2s (hash 2) proofs are verified by zk_verify_stop");
     return verify_entry("zk_verify_fold", proof, len, state, ProofFormat{.log_n = log_n, .log_b = log_b, .q = n_queries, .grind = grind_bits, .fold = fold_log},
-                        public_last, hash_kind, check_out, nullptr, "");
+                        &public_last, hash_kind, check_out, nullptr, "");
 }
 // zk_verify_fold for proofs made with coset leaves (transcript.hpp)
 int zk_verify_coset(const uint8_t* proof, size_t len, const uint8_t* state, uint32_t log_n, uint32_t log_b, uint32_t public_last,
                     int hash_kind, uint32_t n_queries, uint32_t grind_bits, uint32_t fold_log, int32_t* check_out) {
     if (!proof || !check_out) return fail(ZK_ERR_INVALID, "zk_verify_coset: null argument");
     return verify_entry("zk_verify_coset", proof, len, state,
-                        ProofFormat{.log_n = log_n, .log_b = log_b, .q = n_queries, .grind = grind_bits, .fold = fold_log, .coset = true}, public_last, hash_kind,
+                        ProofFormat{.log_n = log_n, .log_b = log_b, .q = n_queries, .grind = grind_bits, .fold = fold_log, .coset = true}, &public_last, hash_kind,
                         check_out, nullptr, "");
 }
 // zk_verify_fold / zk_verify_coset for proofs that stop FRI early (transcript.hpp "stop"); stop_log = 0 is those two
@@ -1542,7 +1543,7 @@ int zk_verify_stop(const uint8_t* proof, size_t len, const uint8_t* state, uint3
     if (!proof || !check_out) return fail(ZK_ERR_INVALID, "zk_verify_stop: null argument");
     return verify_entry("zk_verify_stop", proof, len, state,
                         ProofFormat{.log_n = log_n, .log_b = log_b, .q = n_queries, .grind = grind_bits, .fold = fold_log, .coset = coset_leaves != 0, .stop = stop_log},
-                        public_last, hash_kind, check_out, nullptr, "");
+                        &public_last, hash_kind, check_out, nullptr, "");
 }
 // zk_verify_stop for proofs with Merkle caps (transcript.hpp "Merkle caps"); cap_log = 0 is zk_verify_stop
 int zk_verify_cap(const uint8_t* proof, size_t len, const uint8_t* state, uint32_t log_n, uint32_t log_b, uint32_t public_last,
@@ -1552,6 +1553,21 @@ int zk_verify_cap(const uint8_t* proof, size_t len, const uint8_t* state, uint32
     return verify_entry("zk_verify_cap", proof, len, state,
                         ProofFormat{.log_n = log_n, .log_b = log_b, .q = n_queries, .grind = grind_bits, .fold = fold_log, .coset = coset_leaves != 0, .stop = stop_log,
                                     .cap = cap_log},
+                        &public_last, hash_kind, check_out, nullptr, "");
+}
+// zk_verify_cap for ONE proof of 2^log_batch statements (transcript.hpp "lb"); public_last: one value per statement.
+// log_batch outside 1..8 is refused with check -1: a batch of one is a plain proof and goes to zk_verify_cap.
+int zk_verify_shared(const uint8_t* proof, size_t len, const uint8_t* state, uint32_t log_n, uint32_t log_b, const uint32_t* public_last,
+                     uint32_t log_batch, int hash_kind, uint32_t n_queries, uint32_t grind_bits, uint32_t fold_log, int coset_leaves, uint32_t stop_log,
+                     uint32_t cap_log, int32_t* check_out) {
+    if (!proof || !check_out || !public_last) return fail(ZK_ERR_INVALID, "zk_verify_shared: null argument");
+    if (log_batch < 1 || log_batch > kMaxSharedLog) {
+        *check_out = -1;
+        return fail(ZK_ERR_INVALID, "zk_verify_shared: need 1 <= log_batch <= %u (got %u)", kMaxSharedLog, log_batch);
+    }
+    return verify_entry("zk_verify_shared", proof, len, state,
+                        ProofFormat{.log_n = log_n, .log_b = log_b, .q = n_queries, .grind = grind_bits, .fold = fold_log, .coset = coset_leaves != 0, .stop = stop_log,
+                                    .cap = cap_log, .lb = log_batch},
                         public_last, hash_kind, check_out, nullptr, "");
 }
 
@@ -1572,6 +1588,14 @@ size_t zk_proof_data_len_cap(uint32_t log_n, uint32_t log_b, uint32_t n_queries,
                              uint32_t cap_log) {
     if (fold_log < 1 || fold_log > kMaxFoldLog || !stop_ok(log_n, log_b, stop_log) || cap_log > kMaxCapLog) return 0;
     return ProofFormat{.log_n = log_n, .log_b = log_b, .q = n_queries, .grind = grind_bits, .fold = fold_log, .coset = coset_leaves != 0, .stop = stop_log, .cap = cap_log}
+        .data_len();
+}
+// log_batch = 0: zk_proof_data_len_cap
+size_t zk_proof_data_len_shared(uint32_t log_n, uint32_t log_b, uint32_t n_queries, uint32_t grind_bits, uint32_t fold_log, int coset_leaves, uint32_t stop_log,
+                                uint32_t cap_log, uint32_t log_batch) {
+    if (fold_log < 1 || fold_log > kMaxFoldLog || !stop_ok(log_n, log_b, stop_log) || cap_log > kMaxCapLog || log_batch > kMaxSharedLog) return 0;
+    return ProofFormat{.log_n = log_n, .log_b = log_b, .q = n_queries, .grind = grind_bits, .fold = fold_log, .coset = coset_leaves != 0, .stop = stop_log, .cap = cap_log,
+                       .lb = log_batch}
         .data_len();
 }
 size_t zk_proof_data_len_grind(uint32_t log_n, uint32_t log_b, uint32_t n_queries, uint32_t grind_bits) {

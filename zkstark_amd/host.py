@@ -23,10 +23,12 @@ def _no_blake2s(who, hash):
         raise ValueError(f"{who}: hash='blake2s' is not built for this class yet (Context, Merkle and Proof.verify take it)")
 
 
-def _proof_data_len(o):
-    """Bytes of a proof in the format of `o` (a Proof, Context, BatchContext or Verifier).  zk_proof_data_len_cap is the general
-    entry point: cap 0, stop 0 and one-value leaves are the older formats byte for byte."""
-    return _lib.load().zk_proof_data_len_cap(o.log_n, o.log_blowup, o.queries, o.grind_bits, o.fold_log, int(o.coset_leaves), o.stop_log, o.cap_log)
+def _proof_data_len(o, log_batch=0):
+    """Bytes of a proof in the format of `o` (a Proof, Context, BatchContext or Verifier).  zk_proof_data_len_shared is the general
+    entry point: log_batch 0 (one statement per proof), cap 0, stop 0 and one-value leaves are the older formats byte for byte.
+    log_batch > 0: ONE shared proof of 2^log_batch statements (BatchContext.prove_shared)."""
+    return _lib.load().zk_proof_data_len_shared(o.log_n, o.log_blowup, o.queries, o.grind_bits, o.fold_log, int(o.coset_leaves), o.stop_log, o.cap_log,
+                                                log_batch)
 
 
 def _u32arr(a):
@@ -665,8 +667,54 @@ class BatchContext:
         return [Proof(states[p].tobytes(), data[p].tobytes(), self.log_n, self.log_blowup, int(last[p]), self.hash, self.queries,
                       self.grind_bits, self.fold_log, self.coset_leaves, self.stop_log, self.cap_log) for p in range(self.batch)]
 
+    def prove_shared(self):
+        """zk_batch_prove_shared: ONE SharedProof of the batch's resident traces with the current settings."""
+        plen = _proof_data_len(self, self.log_batch)
+        data = np.zeros(max(plen, 1), dtype=np.uint8)
+        state = np.zeros(32, dtype=np.uint8)
+        got = C.c_size_t()
+        check(_lib.load().zk_batch_prove_shared(self._h, _ptr(data), plen, C.byref(got), _ptr(state)))
+        return SharedProof(state.tobytes(), data[:got.value].tobytes(), self.log_n, self.log_blowup, self.log_batch, self.public_last(), self.hash,
+                           self.queries, self.grind_bits, self.fold_log, self.coset_leaves, self.stop_log, self.cap_log)
+
 
 _ERR_VERIFY = -6
+
+
+class SharedProof:
+    """ONE proof of the 2^log_batch statements of a batch (BatchContext.prove_shared, zk_batch_prove_shared): the f trees are committed
+    together, one FRI runs over the sum of the composition polynomials.  public_last: one value per statement."""
+
+    def __init__(self, state, data, log_n, log_blowup, log_batch, public_last, hash="sha256", queries=1, grind_bits=0, fold_log=1,
+                 coset_leaves=False, stop_log=0, cap_log=0):
+        self.state, self.data = bytes(state), bytes(data)
+        self.log_n, self.log_blowup, self.log_batch = log_n, log_blowup, log_batch
+        self.public_last = _u32arr(public_last)
+        self.hash, self.queries, self.grind_bits, self.fold_log = hash, queries, grind_bits, fold_log
+        self.coset_leaves, self.stop_log, self.cap_log = bool(coset_leaves), stop_log, cap_log
+
+    def expected_len(self):
+        """The length the format gives a shared proof of this shape."""
+        return _proof_data_len(self, self.log_batch)
+
+    def _verify(self, strict, out):
+        if len(self.public_last) != 1 << self.log_batch:
+            raise ZkError(-1, f"expected {1 << self.log_batch} public_last values")
+        return _lib.load().zk_verify_shared(self.data, len(self.data), self.state if strict else None, self.log_n, self.log_blowup,
+                                            _ptr(self.public_last), self.log_batch, HASHES[self.hash], self.queries, self.grind_bits,
+                                            self.fold_log, int(self.coset_leaves), self.stop_log, self.cap_log, C.byref(out))
+
+    def verify(self, strict=False):
+        """Raises ZkError for a rejected proof; strict=True replays the channel first."""
+        check(self._verify(strict, C.c_int32()))
+
+    def check(self, strict=False):
+        """The number of the check zk_verify_shared stops at: 0 = accepted.  Never raises for a rejected proof."""
+        out = C.c_int32()
+        rc = self._verify(strict, out)
+        if rc not in (_lib.ZK_OK, _ERR_VERIFY) and not out.value:
+            check(rc)
+        return out.value
 
 
 class Verifier:
