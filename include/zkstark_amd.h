@@ -975,6 +975,39 @@ int zk_dev_set_merkle_latency_log(uint32_t log_nodes);
 /* Byte view of nodes stored as state words: out[32] for node `index`. */
 int zk_dev_merkle_node(const uint32_t *d_nodes, size_t index, uint8_t out[32], void *stream);
 
+/* ---- row leaves of a shared proof ------------------------------------------------------------------------------
+ * A shared proof (zk_batch_prove_shared) with row leaves commits the M = 2^log_batch trace polynomials as ONE tree over N leaves, leaf i
+ * holding the row (f_0[i], .., f_{M-1}[i]): the header opens with that tree's 2^ce_f digests of depth ce_f = min(c, L - 1) in one commit
+ * (cap 0: one root), the 3M alphas and the rest of the header are unchanged; per query three tuples -- the rows x, x + B, x + 2B, each
+ * the M values in statement order, a u64 count and ONE path of L - ce_f digests -- then the cp tuple and the group tuples as ever.
+ * SHA-256 and the field hash only (no prover makes BLAKE2s row leaves). */
+/* From the next zk_batch_prove_shared on (zk_batch_prove does not look at it; off at creation).  ZK_ERR_STATE while a call runs on the
+ * batch.  After a shared proof with row leaves tree 0 is the one tree over the rows, not the batch's f heap: it answers
+ * zk_batch_merkle_nodes / zk_batch_merkle_cap with ZK_ERR_STATE until the next zk_batch_prove or shared proof without row leaves. */
+int zk_batch_set_shared_rows(zk_batch *b, int on);
+int zk_batch_get_shared_rows(const zk_batch *b);
+/* zk_proof_data_len_shared with row leaves: zk_proof_data_len_cap of the other arguments plus 12 (M - 1) (1 + q) -- the further alphas
+ * and 4 (M - 1) more value bytes in each of the 3 q row tuples.  row_leaves = 0: zk_proof_data_len_shared.  0 where that returns 0, or
+ * for row_leaves with log_batch = 0. */
+size_t zk_proof_data_len_shared_rows(uint32_t log_n, uint32_t log_blowup, uint32_t n_queries, uint32_t grind_bits, uint32_t fold_log,
+                                     int coset_leaves, uint32_t stop_log, uint32_t cap_log, uint32_t log_batch, int row_leaves);
+/* zk_verify_shared for proofs with row leaves; row_leaves = 0 runs the same lines and gives every input zk_verify_shared's answer.
+ * With row leaves: -1 sizes, layout, any length other than zk_proof_data_len_shared_rows of the arguments; -2 the sum over the statements
+ * at x (f_p(x) is value p of row x) against the cp value opened; -3 the three row path lengths and cp's; -4 / -5 / -6 the path of row
+ * x / x + B / x + 2B against cap entry leaf >> (L - ce_f); all others as ever.  The strict replay commits the f cap in one piece and
+ * counts 3M + G + q challenges.  row_leaves with log_batch outside 1..8 or with hash_kind 2 (BLAKE2s): *check_out = -1 and
+ * ZK_ERR_INVALID. */
+int zk_verify_shared_rows(const uint8_t *proof, size_t len, const uint8_t *state, uint32_t log_n, uint32_t log_blowup,
+                          const uint32_t *public_last, uint32_t log_batch, int hash_kind, uint32_t n_queries, uint32_t grind_bits,
+                          uint32_t fold_log, int coset_leaves, uint32_t stop_log, uint32_t cap_log, int row_leaves, int32_t *check_out);
+/* The digest of a row leaf of m values (m a power of two, 1 .. 256), hash_kind 0 or 1.  SHA-256: the digest of the 4m-byte message, each
+ * value 4 bytes big-endian, in statement order.  Field hash: m <= 8 the coset leaf, compress(v_0 .. v_{m-1}, 0, .., 0, m); m >= 16 the
+ * chain c_0 = compress(v_0 .. v_7, 0, .., 0, m), c_k = compress(c_{k-1} || v_8k .. v_8k+7), k < m / 8, whose last link is the digest. */
+int zk_row_leaf_hash(const uint32_t *values, uint32_t m, int hash_kind, uint8_t out[32]);
+/* The tree of a shared proof with row leaves, stand-alone: d_vals: [2^log_batch][2^log_len] u32 on the device (1 <= log_batch <= 8,
+ * 1 <= log_len, log_len + log_batch <= 30), d_nodes: (2^(log_len + 1) - 1) * 8 u32 state words in heap order; hash_kind 0 or 1. */
+int zk_dev_merkle_build_rows(const uint32_t *d_vals, uint32_t log_len, uint32_t log_batch, uint32_t *d_nodes, void *stream, int hash_kind);
+
 #ifdef __cplusplus
 }
 #endif

@@ -229,6 +229,12 @@ SYMBOLS = {
     "zk_batch_prove_shared": (_int, [_vp, _vp, _sz, C.POINTER(_sz), _vp]),
     "zk_proof_data_len_shared": (_sz, [_u32, _u32, _u32, _u32, _u32, _int, _u32, _u32, _u32]),
     "zk_verify_shared": (_int, [_vp, _sz, _vp, _u32, _u32, _vp, _u32, _int, _u32, _u32, _u32, _int, _u32, _u32, C.POINTER(C.c_int32)]),
+    "zk_batch_set_shared_rows": (_int, [_vp, _int]),
+    "zk_batch_get_shared_rows": (_int, [_vp]),
+    "zk_proof_data_len_shared_rows": (_sz, [_u32, _u32, _u32, _u32, _u32, _int, _u32, _u32, _u32, _int]),
+    "zk_verify_shared_rows": (_int, [_vp, _sz, _vp, _u32, _u32, _vp, _u32, _int, _u32, _u32, _u32, _int, _u32, _u32, _int, C.POINTER(C.c_int32)]),
+    "zk_row_leaf_hash": (_int, [_vp, _u32, _int, _vp]),
+    "zk_dev_merkle_build_rows": (_int, [_vp, _u32, _u32, _vp, _vp, _int]),
     "zk_batch_merkle_nodes": (_int, [_vp, _u32, _sz, _sz, _vp]),
     "zk_committer_create": (_int, [_int, C.POINTER(_vp)]),
     "zk_committer_destroy": (_int, [_vp]),

@@ -72,6 +72,8 @@ struct zk_batch {
     // hand-overs the mailbox cannot hold (lb + ce > kMaxHostLog); allocated by the setter only when the f tree needs it.
     uint8_t tree_cap[34] = {0};
     bool proved = false;              // a zk_batch_prove has run: tree_cap, tree_steps and skipped_trees describe it
+    bool shared_rows = false;         // the next zk_batch_prove_shared commits f as row leaves (zk_batch_set_shared_rows)
+    bool rows_tree0 = false;          // the last proof was one: tree 0 holds the tree over the rows, not the batch's f heap
     uint32_t *h_cap = nullptr, *d_cap = nullptr;
     size_t cap_words = 0;
     Grinder* grinder = nullptr;       // one launch grinds for every proof of the batch (created by the setter above kGrindHostMaxBits)
@@ -516,6 +518,15 @@ int zk_batch_set_merkle_cap(zk_batch* b, uint32_t cap_log) {
     return bset_format(b, next, "zk_batch_set_merkle_cap");
 }
 uint32_t zk_batch_get_merkle_cap(const zk_batch* b) { return b ? b->fmt.cap : 0; }
+// Row leaves (include/zkstark_amd.h): from the next zk_batch_prove_shared on; zk_batch_prove does not look at it.  A query of such a proof
+// opens as many values and fewer digests than one of a shared proof without, so the gather buffers stay as they are.
+int zk_batch_set_shared_rows(zk_batch* b, int on) {
+    if (!b) return fail(ZK_ERR_INVALID, "null batch");
+    ZK_BATCH_EXCLUSIVE(b, "zk_batch_set_shared_rows");
+    b->shared_rows = on != 0;
+    return ZK_OK;
+}
+int zk_batch_get_shared_rows(const zk_batch* b) { return b && b->shared_rows ? 1 : 0; }
 uint32_t zk_batch_merkle_cap_log(const zk_batch* b, uint32_t tree) {
     if (!b) return 0;
     if (b->single) return zk_ctx_merkle_cap_log(b->single, tree);
@@ -591,6 +602,7 @@ int zk_batch_merkle_nodes(zk_batch* b, uint32_t tree, size_t first, size_t count
     if (!busy.mine) return fail(ZK_ERR_STATE, "zk_batch_merkle_nodes: a zk_batch_prove is running on this batch");
     const size_t heap = 2 * (blayer_size(b, tree) >> b->tree_steps[tree]) * b->batch - 1;   // read under the flag: a running proof rewrites tree_steps
     if (first > heap || count > heap - first) return fail(ZK_ERR_INVALID, "zk_batch_merkle_nodes: out of range");
+    if (tree == 0 && b->rows_tree0) return fail(ZK_ERR_STATE, "zk_batch_merkle_nodes: the last proof committed f as row leaves: tree 0 is not the batch's f heap");
     if ((b->skipped_trees >> tree) & 1)
         return fail(ZK_ERR_STATE, "zk_batch_merkle_nodes: tree %u was not built by the last proof (fold_log %u, fri_stop %u)", tree, b->proved_fold, b->proved_stop);
     if (count && b->tree_cap[tree] && first + 1 < ((size_t)1 << (b->lb + b->tree_cap[tree])))
@@ -617,6 +629,7 @@ int zk_batch_merkle_cap(zk_batch* b, uint32_t tree, size_t proof, uint8_t* out, 
     BusyScope busy(b);
     if (!busy.mine) return fail(ZK_ERR_STATE, "zk_batch_merkle_cap: a zk_batch_prove is running on this batch");
     if (!b->proved) return fail(ZK_ERR_STATE, "zk_batch_merkle_cap: no proof made yet");
+    if (tree == 0 && b->rows_tree0) return fail(ZK_ERR_STATE, "zk_batch_merkle_cap: the last proof committed f as row leaves: tree 0 is not the batch's f heap");
     if ((b->skipped_trees >> tree) & 1)
         return fail(ZK_ERR_STATE, "zk_batch_merkle_cap: tree %u was not built by the last proof (fold_log %u, fri_stop %u)", tree, b->proved_fold, b->proved_stop);
     const uint32_t ce = b->tree_cap[tree];
@@ -682,7 +695,7 @@ int zk_batch_prove(zk_batch* b, uint8_t* proofs_out, size_t stride, uint8_t* sta
     b->skipped_trees = 0; b->proved_fold = K; b->proved_stop = stop; b->proved_hash = hash;
     memset(b->tree_steps, 0, sizeof b->tree_steps);
     memset(b->tree_cap, 0, sizeof b->tree_cap);
-    b->proved = true;
+    b->proved = true; b->rows_tree0 = false;
     HIPCHK(launch_merkle_build(b->d_layers + b->layer_off[0], L + lb, b->d_trees + b->tree_off[0], b->stream, nullptr, bmail(b, 0, L, lb), hash));
     if ((rc = bpost(b, 0, L, lb))) return rc;
     // proof-independent part of the composition constants (compose_args with alpha = 1)
@@ -867,6 +880,9 @@ int zk_batch_prove(zk_batch* b, uint8_t* proofs_out, size_t stride, uint8_t* sta
 // and heap, h_chal[0].c_mont for the challenge, row 0 of the final-polynomial table.  The gather buffers of the batch always hold a
 // shared proof's openings (3M f tuples and one set of group tuples per query against M sets of both).
 // Afterwards tree 0 is the batch's f heap as ever; the ids >= 1 hold one statement's worth and are reported as not built.
+// Row leaves (zk_batch_set_shared_rows; transcript.hpp "rows"): the f stage runs at width one too -- ONE tree over the N rows
+// of layer 0 from launch_merkle_build_rows, handed over, posted and finished like cp's tree -- and a query opens three leaves of M slots
+// in it.  Tree 0 is then that tree (2N - 1 nodes at tree_off[0]), not the batch's heap, and is reported as not built.
 int zk_batch_prove_shared(zk_batch* b, uint8_t* proof_out, size_t cap, size_t* proof_len, uint8_t state_out[32]) {
     if (!b || !proof_out || !proof_len || !state_out) return fail(ZK_ERR_INVALID, "zk_batch_prove_shared: null argument");
     if (b->single || b->lb > kMaxSharedLog)
@@ -876,6 +892,7 @@ int zk_batch_prove_shared(zk_batch* b, uint8_t* proof_out, size_t cap, size_t* p
     if (!busy.mine) return fail(ZK_ERR_STATE, "zk_batch_prove_shared: another call (zk_batch_prove or a setter) is running on this batch");
     ProofFormat f = b->fmt;
     f.lb = b->lb;
+    f.rows = b->shared_rows;
     const uint32_t Q = f.q, K = f.fold, stop = f.stop, G = f.groups(), lb = b->lb;
     const int hash = b->hash;
     const bool coset = f.coset;
@@ -885,7 +902,7 @@ int zk_batch_prove_shared(zk_batch* b, uint8_t* proof_out, size_t cap, size_t* p
     size_t nv = 0, ndg = 0;                                               // values and digests the Q queries open
     bopenings(f, &nv, &ndg);
     nv *= Q; ndg *= Q;
-    if (nv + ndg > b->batch * Q * (b->per_proof_vals + b->per_proof_digs)) return fail(ZK_ERR_STATE, "zk_batch_prove_shared: gather buffers too small");
+    if (nv + ndg > b->batch * Q * (b->per_proof_vals + b->per_proof_digs) || nv + 8 * ndg > b->batch * Q * (b->per_proof_vals + 8 * b->per_proof_digs)) return fail(ZK_ERR_STATE, "zk_batch_prove_shared: gather buffers too small");
     HIPCHK(hipSetDevice(b->device));
     const size_t nb = b->batch, N = b->N, B = b->B;
     const uint32_t R = b->R, L = b->L, Rp = f.rounds();
@@ -905,9 +922,11 @@ int zk_batch_prove_shared(zk_batch* b, uint8_t* proof_out, size_t cap, size_t* p
     b->proved_fold = K; b->proved_stop = stop; b->proved_hash = hash;
     memset(b->tree_steps, 0, sizeof b->tree_steps);
     memset(b->tree_cap, 0, sizeof b->tree_cap);
-    b->proved = true;
-    HIPCHK(launch_merkle_build(b->d_layers + b->layer_off[0], L + lb, b->d_trees + b->tree_off[0], b->stream, nullptr, bmail(b, 0, L, lb), hash));
-    if ((rc = bpost(b, 0, L, lb))) return rc;
+    b->proved = true; b->rows_tree0 = f.rows;
+    const uint32_t fw = f.rows ? 0 : lb;                                  // width of the f stage: row leaves make ONE tree of N leaves
+    if (f.rows) HIPCHK(launch_merkle_build_rows(b->d_layers + b->layer_off[0], L, lb, b->d_trees + b->tree_off[0], b->stream, nullptr, bmail(b, 0, L, 0), hash));
+    else HIPCHK(launch_merkle_build(b->d_layers + b->layer_off[0], L + lb, b->d_trees + b->tree_off[0], b->stream, nullptr, bmail(b, 0, L, lb), hash));
+    if ((rc = bpost(b, 0, L, fw))) return rc;
     ComposeBatchArgs ca;
     {
         const uint32_t one[3] = {1, 1, 1};
@@ -916,8 +935,8 @@ int zk_batch_prove_shared(zk_batch* b, uint8_t* proof_out, size_t cap, size_t* p
     }
     const uint32_t g2 = mulmod(d->g, d->g);
     if ((rc = bwait_roots(b))) return rc;
-    const uint32_t* roots = bfinish_roots(b, 0, L, lb);
-    commit_level(roots, nb << b->tree_cap[0]);
+    const uint32_t* roots = bfinish_roots(b, 0, L, fw);
+    commit_level(roots, ((size_t)1 << fw) << b->tree_cap[0]);
     for (size_t p = 0; p < nb; ++p) {                                     // prover.rs:163-165 per statement, statement-major
         const uint32_t a0 = ch.get_u32() % P, a1 = ch.get_u32() % P, a2 = ch.get_u32() % P;
         BatchChal& c = b->h_chal[p];
@@ -987,12 +1006,13 @@ int zk_batch_prove_shared(zk_batch* b, uint8_t* proof_out, size_t cap, size_t* p
     }
     uint32_t qraw[kMaxQueries];
     for (uint32_t k = 0; k < Q; ++k) qraw[k] = ch.get_u32();              // prover.rs:263
-    // the openings: layer 0 and tree 0 at the batch's width (leaf = (p << L) + index), everything else at width one
+    // the openings: layer 0 and tree 0 at the batch's width (leaf = (p << L) + index; row leaves: at width one, 2^lb slots a leaf),
+    // everything else at width one
     uint64_t *vo = b->h_goff, *dofs = b->h_goff + nv;
     std::vector<size_t> nodes;
     for (uint32_t k = 0; k < Q; ++k)
         f.for_each_opening((size_t)qraw[k] % (N - 2 * B), [&](uint32_t layer, uint32_t log_leaves, size_t leaf, uint32_t slots_log) {
-            const uint32_t w = layer == 0 ? lb : 0;
+            const uint32_t w = layer == 0 ? fw : 0;
             const size_t p = leaf >> log_leaves, at = leaf & (((size_t)1 << log_leaves) - 1);   // p = 0 unless layer 0
             for (size_t u = 0; u < ((size_t)1 << slots_log); ++u) *vo++ = b->layer_off[layer] + (p << (log_leaves + slots_log)) + at + (u << log_leaves);
             nodes.clear();
@@ -1014,7 +1034,9 @@ int zk_batch_prove_shared(zk_batch* b, uint8_t* proof_out, size_t cap, size_t* p
     HIPCHK(hipStreamSynchronize(b->stream));
     const uint32_t* vals = b->h_gout;
     const uint32_t* dw = b->h_gout + nv;
-    std::vector<uint8_t> buf(Channel::group_bytes((size_t)1 << f.steps(0), L, false));
+    size_t widest = Channel::group_bytes((size_t)1 << f.steps(0), L, false);   // the first group's tuple, or a row of 2^lb values
+    if (f.rows && Channel::group_bytes(nb, L, true) > widest) widest = Channel::group_bytes(nb, L, true);
+    std::vector<uint8_t> buf(widest);
     for (uint32_t q = 0; q < Q; ++q)
         f.for_each_tuple([&](size_t s, size_t pl, bool one_leaf) {
             ch.commit_group(buf.data(), s, pl, [&](size_t t) { return vals[t]; }, [&](size_t i, uint8_t* out) { digest_words_to_bytes(dw + 8 * i, out); }, one_leaf);

@@ -151,6 +151,22 @@ ZK_HD Digest fieldhash_coset_leaf(const uint32_t* v, uint32_t k, const FieldHash
     fh_compress(in, d.w, c);
     return d;
 }
+// Leaf of a row of m values (row leaves of a shared proof, transcript.hpp "rows"; m a power of two <= 256).  m <= 8: the coset leaf.
+// m >= 16: a chain over chunks of 8 values, c_0 = compress(v_0 .. v_7, 0, .., 0, m) (word 15 = m: the length, as the coset leaf has it),
+// c_k = compress(c_{k-1}.w[0..8) || v_8k .. v_8k+7) for k = 1 .. m / 8 - 1 (the inner node's shape); the digest is the last c_k.
+ZK_HD Digest fieldhash_row_leaf(const uint32_t* v, uint32_t m, const FieldHashConsts& c) {
+    if (m <= 8) return fieldhash_coset_leaf(v, m, c);
+    uint32_t in[kFhT] = {0};
+    for (int i = 0; i < 8; ++i) in[i] = v[i];
+    in[kFhT - 1] = m;
+    Digest d;
+    fh_compress(in, d.w, c);
+    for (uint32_t k = 1; k < m / 8; ++k) {
+        for (int i = 0; i < 8; ++i) { in[i] = d.w[i]; in[8 + i] = v[8 * k + i]; }
+        fh_compress(in, d.w, c);
+    }
+    return d;
+}
 ZK_HD Digest fieldhash_inner(const Digest& l, const Digest& r, const FieldHashConsts& c) {
     uint32_t in[kFhT];
 #pragma unroll

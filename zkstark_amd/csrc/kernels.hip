@@ -1991,6 +1991,126 @@ hipError_t launch_merkle_build_coset_batch(const uint32_t* vals, uint32_t log_le
     if (e != hipSuccess) return e;
     return merkle_build_t(PlainSrc{nullptr}, 0.0, log_m, nodes, s, prof, mail, hash, log_m, 0, false);   // mail.top: the per-proof roots or below
 }
+// ---- row leaves of a shared proof (transcript.hpp "rows") -------------------------------------------------------
+// ONE tree over the 2^log_len rows of a proof-major batch (vals: [M][2^log_len], M = 2^LB): leaf i holds vals[(p << log_len) + i],
+// p < M, in statement order, and its digest goes to heap position 2^log_len - 1 + i.  The walk is coset_leaf_hash_kernel's: a lane owns
+// the leaves i, i + stride, ..., every lane of a wave makes the same number of trips, and each of its M loads is one coalesced run
+// across the wave.  LB <= 3: the row is a coset leaf of M slots, one compression (coset_leaf_digest).  LB >= 4: the row is streamed
+// in blocks of 16 (SHA-256: one message block) or 8 values (field hash: one chunk of fieldhash_row_leaf's chain); the next block --
+// of this leaf, or the first of the lane's next leaf -- is loaded before the current one is compressed, and only the chaining state
+// lives across blocks: 16 + 16 (8 + 8) message words and 8 state words, no scratch, no LDS.  The block loop is not unrolled, so a
+// leaf kernel holds ONE inlined data compression whatever M; the SHA-256 padding block (0x80000000, 0, .., 0, 32 M) is a constant
+// message per M and its whole schedule folds at compile time (a second compression of 64 rounds without a schedule).
+template <int HASH, int LB>
+__global__ __launch_bounds__(kCosetThreads) void row_leaf_hash_kernel(const uint32_t* __restrict__ vals, uint32_t log_len, uint32_t* __restrict__ nodes) {
+    constexpr int M = 1 << LB;
+    const size_t leaves = (size_t)1 << log_len;                  // also the distance between two values of a row
+    const size_t stride = (size_t)gridDim.x * kCosetThreads;     // a power of two <= leaves, or one workgroup: every lane of a wave makes the same trips
+    size_t c = (size_t)blockIdx.x * kCosetThreads + threadIdx.x;
+    if (c >= leaves) return;
+    if constexpr (LB <= 3) {
+        uint32_t v[M], nx[M] = {};
+#pragma unroll
+        for (int u = 0; u < M; ++u) v[u] = vals[c + (size_t)u * leaves];
+        bool more;
+#pragma unroll 1
+        do {
+            const size_t cn = c + stride;
+            more = cn < leaves;
+            if (more) {
+#pragma unroll
+                for (int u = 0; u < M; ++u) nx[u] = vals[cn + (size_t)u * leaves];
+            }
+            store_digest(nodes, leaves - 1 + c, coset_leaf_digest<HASH, M>(v));
+#pragma unroll
+            for (int u = 0; u < M; ++u) v[u] = nx[u];
+            c = cn;
+        } while (more);
+    } else {
+        constexpr int CH = HASH == ZK_HASH_FIELD ? 8 : 16;       // values per compression
+        constexpr int NB = M / CH;                               // data blocks of a leaf
+        uint32_t cur[CH], nx[CH] = {};
+#pragma unroll
+        for (int u = 0; u < CH; ++u) cur[u] = vals[c + (size_t)u * leaves];
+        bool more;
+#pragma unroll 1
+        do {
+            const size_t cn = c + stride;
+            more = cn < leaves;
+            Digest d;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) d.w[i] = HASH == ZK_HASH_FIELD ? 0u : SHA_IV[i];
+#pragma unroll 1
+            for (int k = 0; k < NB; ++k) {
+                const bool last = k + 1 == NB;
+                if (!last || more) {                             // block k + 1 of this leaf, or block 0 of the next one
+                    const uint32_t* src = last ? vals + cn : vals + c + (size_t)(k + 1) * CH * leaves;
+#pragma unroll
+                    for (int u = 0; u < CH; ++u) nx[u] = src[(size_t)u * leaves];
+                }
+                if constexpr (HASH == ZK_HASH_FIELD) {
+                    uint32_t in[kFhT];
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) {
+                        in[i] = k == 0 ? cur[i] : d.w[i];
+                        in[8 + i] = k == 0 ? (i == 7 ? (uint32_t)M : 0u) : cur[i];
+                    }
+                    fh64_compress(in, d.w, g_fh_consts64);
+                } else {
+                    sha256_compress(d.w, cur);
+                }
+#pragma unroll
+                for (int u = 0; u < CH; ++u) cur[u] = nx[u];
+            }
+            if constexpr (HASH != ZK_HASH_FIELD) {
+                uint32_t pad[16] = {0x80000000u, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 32u * M};
+                sha256_compress(d.w, pad);
+            }
+            store_digest(nodes, leaves - 1 + c, d);
+            c = cn;
+        } while (more);
+    }
+}
+template <int HASH>
+static void row_leaf_launch(const uint32_t* vals, uint32_t log_len, uint32_t log_batch, uint32_t* nodes, uint32_t blocks, hipStream_t s) {
+    const dim3 g(blocks), b(kCosetThreads);
+    switch (log_batch) {
+        case 1: hipLaunchKernelGGL((row_leaf_hash_kernel<HASH, 1>), g, b, 0, s, vals, log_len, nodes); break;
+        case 2: hipLaunchKernelGGL((row_leaf_hash_kernel<HASH, 2>), g, b, 0, s, vals, log_len, nodes); break;
+        case 3: hipLaunchKernelGGL((row_leaf_hash_kernel<HASH, 3>), g, b, 0, s, vals, log_len, nodes); break;
+        case 4: hipLaunchKernelGGL((row_leaf_hash_kernel<HASH, 4>), g, b, 0, s, vals, log_len, nodes); break;
+        case 5: hipLaunchKernelGGL((row_leaf_hash_kernel<HASH, 5>), g, b, 0, s, vals, log_len, nodes); break;
+        case 6: hipLaunchKernelGGL((row_leaf_hash_kernel<HASH, 6>), g, b, 0, s, vals, log_len, nodes); break;
+        case 7: hipLaunchKernelGGL((row_leaf_hash_kernel<HASH, 7>), g, b, 0, s, vals, log_len, nodes); break;
+        default: hipLaunchKernelGGL((row_leaf_hash_kernel<HASH, 8>), g, b, 0, s, vals, log_len, nodes); break;
+    }
+}
+// compressions of one row leaf of 2^log_batch values (transcript.hpp "rows")
+static double row_leaf_compressions(uint32_t log_batch, int hash) {
+    if (log_batch <= 3) return 1.0;
+    return hash == ZK_HASH_FIELD ? (double)(1u << (log_batch - 3)) : (double)((1u << (log_batch - 4)) + 1u);
+}
+hipError_t launch_merkle_build_rows(const uint32_t* vals, uint32_t log_len, uint32_t log_batch, uint32_t* nodes, hipStream_t s, Profiler* prof,
+                                    const MailArgs& mail, int hash) {
+    if (log_batch < 1 || log_batch > 8 || log_len < 1 || log_len + log_batch > 32) return hipErrorInvalidValue;
+    if (hash != ZK_HASH_SHA256 && hash != ZK_HASH_FIELD) return hipErrorInvalidValue;   // no BLAKE2s row leaf (transcript.hpp "rows")
+    if (hash == ZK_HASH_FIELD) {
+        hipError_t e = ensure_fieldhash_consts();
+        if (e != hipSuccess) return e;
+    }
+    const size_t leaves = (size_t)1 << log_len;
+    const size_t lanes = leaves > 4 * (size_t)kCosetThreads ? leaves / 4 : leaves;   // up to four leaves per lane, as the coset launches
+    const uint32_t blocks = (uint32_t)((lanes + kCosetThreads - 1) / kCosetThreads);
+    {
+        ScopedKernelTimer tm(prof, K_MERKLE_LEAF, 4.0 * (double)((size_t)1 << (log_len + log_batch)) + 32.0 * (double)leaves, s,
+                             (double)leaves * row_leaf_compressions(log_batch, hash) * hash_leaf_ops(hash));
+        if (hash == ZK_HASH_FIELD) row_leaf_launch<1>(vals, log_len, log_batch, nodes, blocks, s);
+        else row_leaf_launch<0>(vals, log_len, log_batch, nodes, blocks, s);
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    return merkle_build_t(PlainSrc{nullptr}, 0.0, log_len, nodes, s, prof, mail, hash, log_len, 0, false);
+}
 // commitment of a block whose leaves are still in all-to-all order (no interleave pass, no block buffer)
 hipError_t launch_merkle_build_interleaved(const uint32_t* recv, uint32_t log_parts, uint32_t log_cnt, uint32_t* nodes, hipStream_t s,
                                            Profiler* prof, int hash, const MailArgs& mail) {

@@ -346,6 +346,13 @@ hipError_t launch_compose_sum_batch(const ComposeBatchArgs& a, uint32_t log_batc
 // (nodes: (2 batch m - 1) * 8 words) whose nodes of depth log_batch are the per-proof roots (mail.top as for the other batch builds).
 hipError_t launch_merkle_build_coset_batch(const uint32_t* vals, uint32_t log_len, uint32_t steps, uint32_t log_batch, uint32_t* nodes, hipStream_t s,
                                            Profiler* prof, const MailArgs& mail, int hash);
+// Row leaves of a shared proof (transcript.hpp "rows"): ONE tree over the 2^log_len rows of a proof-major batch (vals: [2^log_batch][2^log_len],
+// 1 <= log_batch <= 8), leaf i holding vals[(p << log_len) + i], p < 2^log_batch (nodes: (2^(log_len + 1) - 1) * 8 words).  The leaves come
+// from row_leaf_hash_kernel (profiled as K_MERKLE_LEAF: 4 B per value read, 32 B per leaf written, one leaf = 1 compression up to 8 values,
+// M / 16 + 1 of SHA-256 or M / 8 of the field hash from 16 on), the levels above from the inner-mode build; mail as for a single tree of
+// 2^log_len leaves.  SHA-256 and the field hash only.
+hipError_t launch_merkle_build_rows(const uint32_t* vals, uint32_t log_len, uint32_t log_batch, uint32_t* nodes, hipStream_t s, Profiler* prof,
+                                    const MailArgs& mail, int hash);
 
 // batch traces of prover.rs:32-39, one lane per trace: out[t*stride + i], i < count (stride 0 = count)
 hipError_t launch_trace_fibsq_batch(const uint32_t* a0, const uint32_t* a1, uint32_t batch, uint32_t count, uint32_t* out, hipStream_t s,

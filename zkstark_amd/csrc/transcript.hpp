@@ -129,6 +129,16 @@ constexpr uint32_t kMaxCapLog = 8;
 // lengths (and cp's); -4 / -5 / -6 the path of f_p(x) / f_p(gx) / f_p(g^2 x) of the first failing tuple in wire order; the rest as ever.
 // verify_transcript counts 3M + G + q challenges; 3 * 256 + 30 + 64 keeps -(1000 + k) clear of -1998.
 constexpr uint32_t kMaxSharedLog = 8;
+// rows = row leaves of a shared proof (needs 1 <= lb; off = the format above).  The M trace polynomials are committed as ONE
+// tree over N leaves, leaf i holding the row (f_0[i], .., f_{M-1}[i]): the proof-major array [M][N] read as one layer of M N values whose
+// leaves hold 2^lb slots, slot u = layer[i + u N].  The header opens with that tree's cap, the 2^ce_f digests of depth ce_f = min(c, L - 1)
+// (ONE commit; cap 0: one root), then the 3M alphas as ever.  Per query three tuples -- the rows x, x + B, x + 2B -- each the M values of the
+// row in statement order, a u64 count and ONE path of L - ce_f digests; then the cp tuple and the group tuples as ever.  Leaf hash of a row
+// (host_coset_leaf_hash with s = M): SHA-256 of the 4M-byte message, 4 bytes big-endian per value (M <= 8: the coset leaf's one block;
+// M >= 16: M / 16 data blocks and one padding block); field hash: fieldhash_row_leaf (fieldhash.hpp; M <= 8: the coset leaf, M >= 16 a chain
+// of M / 8 compressions).  No BLAKE2s: no prover makes such a proof.  verify_proof: -2 as ever (f_p(x) is value p of row x); -3 covers the
+// three row path lengths (and cp's); -4 / -5 / -6 the path of row x / x + B / x + 2B against cap entry leaf >> (L - ce_f).  The length is a
+// single proof's plus 12 (M - 1) (1 + q): the further alphas and 4 (M - 1) more value bytes in each of the 3 q row tuples.
 inline uint32_t cap_eff(uint32_t cap, uint32_t lg) { return cap < lg - 1 ? cap : lg - 1; }   // lg >= 1 for every committed tree
 
 // One proof format: the settings above and everything that follows from them.  The Merkle hash and public_last are not part of it.
@@ -139,11 +149,12 @@ struct ProofFormat {
     bool coset = false;
     uint32_t stop = 0, cap = 0;
     uint32_t lb = 0;                                                         // shared proof of 2^lb statements (0: a plain proof)
+    bool rows = false;                                                       // ... whose f values are committed as row leaves (needs lb >= 1)
 
     // what verify_proof and verify_transcript take (they answer -1 to anything else); every member below assumes it
     bool ok() const {
         return log_n >= 2 && log_b >= 1 && log_n + log_b <= 30 && q >= 1 && q <= 64 && grind <= kMaxGrindBits && fold >= 1 && fold <= kMaxFoldLog &&
-               stop_ok(log_n, log_b, stop) && cap <= kMaxCapLog && lb <= kMaxSharedLog;
+               stop_ok(log_n, log_b, stop) && cap <= kMaxCapLog && lb <= kMaxSharedLog && (!rows || lb >= 1);
     }
     // ---- geometry.  Group j < G folds the rounds round0(j) .. round0(j) + steps(j) - 1; tree j is the one over its INPUT layer.
     // j = G: the last layer (round0 = rounds, steps = 0), whose tree has one-value leaves and exists only when stop = 0.
@@ -163,11 +174,11 @@ struct ProofFormat {
 
     // ---- the header in wire order: fn(what, j, bytes) -> bool, false ends the walk (and is returned).  kAlphas, kBeta and kRaws are
     // challenges of 4 bytes each (3 per statement, 1 and q of them), everything else is ONE commit.  kTree j: the commitment of tree j.
-    // kFTree: the caps of all 2^lb statements' f trees, statement-major, in one commit.
+    // kFTree: the caps of all 2^lb statements' f trees, statement-major, in one commit; rows: the cap of the one tree over the rows.
     enum Head { kFTree, kAlphas, kTree, kBeta, kFinal, kNonce, kRaws };
     template <class Fn> bool for_each_head(Fn fn) const {
         const uint32_t G = groups();
-        if (!fn(kFTree, 0u, (size_t)32 << (lb + f_cap())) || !fn(kAlphas, 0u, (size_t)12 << lb) || !fn(kTree, 0u, (size_t)32 << tree_cap(0))) return false;
+        if (!fn(kFTree, 0u, (size_t)32 << ((rows ? 0 : lb) + f_cap())) || !fn(kAlphas, 0u, (size_t)12 << lb) || !fn(kTree, 0u, (size_t)32 << tree_cap(0))) return false;
         for (uint32_t j = 0; j < G; ++j) {
             if (!fn(kBeta, j, (size_t)4)) return false;                      // group j's challenge, then the tree over its output
             if ((j + 1 < G || last_tree()) && !fn(kTree, j + 1, (size_t)32 << tree_cap(j + 1))) return false;
@@ -177,9 +188,11 @@ struct ProofFormat {
         return fn(kRaws, 0u, (size_t)4 * q);
     }
     // ---- the tuples of one query in wire order: fn(s values, digests per path, one_leaf) as Channel::commit_group takes them.
-    // f(x), f(gx), f(g^2 x) of every statement and, with one-value leaves, cp(x); then one tuple per group.
+    // f(x), f(gx), f(g^2 x) of every statement (rows: the three rows of 2^lb values, one leaf each) and, with one-value leaves, cp(x);
+    // then one tuple per group.
     template <class Fn> void for_each_tuple(Fn fn) const {
-        for (size_t i = 0; i < ((size_t)3 << lb); ++i) fn((size_t)1, f_path(), false);
+        if (rows) for (int k = 0; k < 3; ++k) fn((size_t)1 << lb, f_path(), true);
+        else for (size_t i = 0; i < ((size_t)3 << lb); ++i) fn((size_t)1, f_path(), false);
         if (!coset) fn((size_t)1, tree_path(0), false);
         for (uint32_t j = 0, G = groups(); j < G; ++j) fn((size_t)1 << steps(j), tree_path(j), coset);
     }
@@ -187,10 +200,12 @@ struct ProofFormat {
     // (layer 1) (prover.rs:266-277), then per group the s coset leaves of its input layer.  An opening is one LEAF and its path:
     // open(layer id, log2 of the tree's leaf count, leaf index, slots_log); the leaf holds the 2^slots_log values
     // layer[leaf + u 2^(log2 leaf count)], u < 2^slots_log (0: a one-value leaf).  Both provers rely on this leaf order.
-    // Shared proof: statement p's f openings are the leaves (p << L) + x .. of layer 0, i.e. of the proof-major [2^lb][N] array.
+    // Shared proof: statement p's f openings are the leaves (p << L) + x .. of layer 0, i.e. of the proof-major [2^lb][N] array; rows:
+    // the leaves x, x + B, x + 2B of the tree over that array's N rows, 2^lb slots each.
     template <class Open> void for_each_opening(size_t x, Open open) const {
         const size_t B = (size_t)1 << log_b;
-        for (size_t p = 0; p < ((size_t)1 << lb); ++p) {
+        if (rows) { open(0u, L(), x, lb); open(0u, L(), x + B, lb); open(0u, L(), x + 2 * B, lb); }
+        else for (size_t p = 0; p < ((size_t)1 << lb); ++p) {
             const size_t at = (p << L()) + x;
             open(0u, L(), at, 0u); open(0u, L(), at + B, 0u); open(0u, L(), at + 2 * B, 0u);
         }
@@ -261,11 +276,13 @@ inline void host_node_hash(const uint8_t* l, const uint8_t* r, uint8_t out[32], 
     Sha256 h; h.update(l, 32); h.update(r, 32); h.finalize(out);
 }
 
-// Leaf of s <= 8 slots (coset leaves, above); s = 1 is host_leaf_hash.
+// Leaf of s <= 8 slots (coset leaves, above; s = 1 is host_leaf_hash) or of a row of s <= 2^kMaxSharedLog values (row leaves, above: a
+// power of two; SHA-256 and the field hash only -- a BLAKE2s leaf has at most 8 slots).
 inline void host_coset_leaf_hash(const uint32_t* slots, size_t s, uint8_t out[32], int hash) {
-    if (hash == ZK_HASH_BLAKE2S) { digest_words_to_bytes(blake2s_coset_leaf(slots, s).w, out); return; }
-    if (hash == ZK_HASH_FIELD) { digest_words_to_bytes(fieldhash_coset_leaf(slots, (uint32_t)s, host_fieldhash_consts()).w, out); return; }
-    uint8_t be[32];
+    if (hash == ZK_HASH_BLAKE2S) { digest_words_to_bytes(blake2s_coset_leaf(slots, s < 8 ? s : 8).w, out); return; }
+    if (hash == ZK_HASH_FIELD) { digest_words_to_bytes(fieldhash_row_leaf(slots, (uint32_t)s, host_fieldhash_consts()).w, out); return; }
+    uint8_t be[4 << kMaxSharedLog];
+    if (s > ((size_t)1 << kMaxSharedLog)) s = (size_t)1 << kMaxSharedLog;
     for (size_t u = 0; u < s; ++u) { be[4 * u] = (uint8_t)(slots[u] >> 24); be[4 * u + 1] = (uint8_t)(slots[u] >> 16); be[4 * u + 2] = (uint8_t)(slots[u] >> 8); be[4 * u + 3] = (uint8_t)slots[u]; }
     Sha256 h; h.update(be, 4 * s); h.finalize(out);
 }
@@ -304,12 +321,15 @@ inline void compute_root_from_path(uint32_t element, size_t index, const uint8_t
 // compared with the cap entry it lands in, under the check number it has for the root.  A proof of another length: -1.
 // lb > 0 (the shared proof, above): public_last holds 2^lb values; the f tuples are 3 per statement, fv[3 p + k], and the cp value is
 // fv[3 M].  lb = 0: one statement, fv[0..3] as ever.
+// rows (row leaves, above): three f tuples of M values each, row k at fv[k M ..]; f_p at x + k B is fv[k M + p].  BLAKE2s: -1.
 inline int verify_proof(const uint8_t* data, size_t len, const ProofFormat& fmt, const uint32_t* public_last, int hash) {
-    if (!fmt.ok()) return -1;
+    if (!fmt.ok() || (fmt.rows && hash == ZK_HASH_BLAKE2S)) return -1;
     if ((fmt.stop || fmt.cap || fmt.lb) && len != fmt.data_len()) return -1;   // a stopped, capped or shared proof of another length: -1, strict or not
     const bool coset = fmt.coset;
     const size_t M = (size_t)1 << fmt.lb;
-    const uint32_t ncp = 3 * (uint32_t)M, nf = ncp + (coset ? 0 : 1);   // f(x), f(gx), f(g^2 x) per statement and, with one-value leaves, cp(x)
+    const bool rows = fmt.rows;
+    const uint32_t ncp = 3 * (uint32_t)M;                               // f(x), f(gx), f(g^2 x) per statement: the f values of a query
+    const uint32_t nft = rows ? 3 : ncp, nf = nft + (coset ? 0 : 1);    // ... in nft tuples; nf with the cp(x) tuple of one-value leaves
     const size_t n = (size_t)1 << fmt.log_n, B = (size_t)1 << fmt.log_b, N = n << fmt.log_b;
     const uint32_t L = fmt.L(), G = fmt.groups();
     const uint8_t* p = data;
@@ -352,11 +372,11 @@ inline int verify_proof(const uint8_t* data, size_t len, const ProofFormat& fmt,
     const uint32_t g = root_of_unity(fmt.log_n), h = root_of_unity(L);
     for (uint32_t qk = 0; qk < fmt.q; ++qk) {
         uint32_t fv[3 * (1u << kMaxSharedLog) + 1]; const uint8_t* fp[3 * (1u << kMaxSharedLog) + 1]; size_t fpl[3 * (1u << kMaxSharedLog) + 1];
-        for (uint32_t t = 0; t <= ncp; ++t) fpl[t] = 0;
+        for (uint32_t t = 0; t <= nft; ++t) fpl[t] = 0;
         uint32_t lv[40][8]; const uint8_t* lp[40][8]; size_t lpl[40][8];
         uint32_t i = 0;                                      // tuple i: an f / cp tuple, then group i - nf
         fmt.for_each_tuple([&](size_t s, size_t, bool one_leaf) {
-            uint32_t* v = i < nf ? &fv[i] : lv[i - nf];
+            uint32_t* v = i < nf ? &fv[!rows ? i : i < 3 ? i * M : ncp] : lv[i - nf];   // the cp value is fv[3 M] either way
             const uint8_t** path = i < nf ? &fp[i] : lp[i - nf];
             size_t* plen = i < nf ? &fpl[i] : lpl[i - nf];
             for (size_t t = 0; t < s; ++t) v[t] = take32();
@@ -383,7 +403,8 @@ inline int verify_proof(const uint8_t* data, size_t len, const ProofFormat& fmt,
             uint32_t cp0 = 0;
             for (size_t s = 0; s < M; ++s) {
                 const uint8_t* al = alphas + 12 * s;
-                uint32_t f_x = fv[3 * s] % P, f_gx = fv[3 * s + 1] % P, f_ggx = fv[3 * s + 2] % P;
+                const size_t at = rows ? s : 3 * s, step = rows ? M : 1;
+                uint32_t f_x = fv[at] % P, f_gx = fv[at + step] % P, f_ggx = fv[at + 2 * step] % P;
                 uint32_t p0 = mulmod(sub(f_x, 1), i0);
                 uint32_t p1 = mulmod(sub(f_x, public_last[s] % P), i1);
                 uint32_t num = sub(sub(f_ggx, mulmod(f_gx, f_gx)), mulmod(f_x, f_x));
@@ -398,16 +419,18 @@ inline int verify_proof(const uint8_t* data, size_t len, const ProofFormat& fmt,
             compute_root_from_coset(slots, s, idx & (((size_t)1 << plen) - 1), path, plen, root, hash);
             return memcmp(root, entries + 32 * (idx >> plen), 32) != 0;
         };
-        for (uint32_t k = 0; k < ncp; ++k) if (fpl[k] != fmt.f_path()) return -3;
-        if (!coset && fpl[ncp] != fmt.tree_path(0)) return -3;
-        // proof.rs:80-95; statement s's paths land in its own 2^ce entries of the f commitment
-        for (size_t s = 0; s < M; ++s) {
+        for (uint32_t k = 0; k < nft; ++k) if (fpl[k] != fmt.f_path()) return -3;
+        if (!coset && fpl[nft] != fmt.tree_path(0)) return -3;
+        // proof.rs:80-95; statement s's paths land in its own 2^ce entries of the f commitment (rows: row k is ONE leaf of M slots)
+        for (uint32_t k = 0; rows && k < 3; ++k)
+            if (misses(&fv[k * M], M, tp + k * B, fp[k], fpl[k], f_root)) return -(int)(4 + k);
+        for (size_t s = 0; !rows && s < M; ++s) {
             const uint8_t* cap_s = f_root + ((size_t)32 << fmt.f_cap()) * s;
             if (misses(&fv[3 * s], 1, tp, fp[3 * s], fpl[3 * s], cap_s)) return -4;
             if (misses(&fv[3 * s + 1], 1, tp + B, fp[3 * s + 1], fpl[3 * s + 1], cap_s)) return -5;
             if (misses(&fv[3 * s + 2], 1, tp + 2 * B, fp[3 * s + 2], fpl[3 * s + 2], cap_s)) return -6;
         }
-        if (!coset && misses(&fv[ncp], 1, tp, fp[ncp], fpl[ncp], roots[0])) return -7;
+        if (!coset && misses(&fv[ncp], 1, tp, fp[nft], fpl[nft], roots[0])) return -7;
         // proof.rs:101-126: the s opened values of a group folded pairwise (t with t + s/2, then again)
         const uint32_t inv2 = invmod(2);
         for (uint32_t j = 0; j < G; ++j) {
@@ -466,6 +489,7 @@ inline int verify_proof(const uint8_t* data, size_t len, const ProofFormat& fmt,
 // stop > 0: 3 + G' + q challenges; the coefficients are one commit, in the place of the last root and the free term.
 // cap > 0: every root commit is one commit of the tree's 2^ce digests, and a tuple's paths are ce digests shorter.
 // lb > 0: 3 * 2^lb + G + q challenges; the f level is one commit, each of the 3 * 2^lb f tuples of a query one commit.
+// rows: the same challenges; the f cap is one commit, each of the three row tuples of a query one commit.
 inline int verify_transcript(const uint8_t* data, size_t len, const uint8_t state[32], const ProofFormat& fmt) {
     if (!fmt.ok() || len != fmt.data_len()) return -1;
     Channel ch;

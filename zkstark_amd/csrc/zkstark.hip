@@ -1570,6 +1570,27 @@ int zk_verify_shared(const uint8_t* proof, size_t len, const uint8_t* state, uin
                                     .cap = cap_log, .lb = log_batch},
                         public_last, hash_kind, check_out, nullptr, "");
 }
+// zk_verify_shared with ProofFormat::rows (transcript.hpp "rows"); row_leaves = 0 is zk_verify_shared, line for line.
+int zk_verify_shared_rows(const uint8_t* proof, size_t len, const uint8_t* state, uint32_t log_n, uint32_t log_b, const uint32_t* public_last,
+                          uint32_t log_batch, int hash_kind, uint32_t n_queries, uint32_t grind_bits, uint32_t fold_log, int coset_leaves, uint32_t stop_log,
+                          uint32_t cap_log, int row_leaves, int32_t* check_out) {
+    if (!row_leaves)
+        return zk_verify_shared(proof, len, state, log_n, log_b, public_last, log_batch, hash_kind, n_queries, grind_bits, fold_log, coset_leaves, stop_log, cap_log,
+                                check_out);
+    if (!proof || !check_out || !public_last) return fail(ZK_ERR_INVALID, "zk_verify_shared_rows: null argument");
+    if (log_batch < 1 || log_batch > kMaxSharedLog) {
+        *check_out = -1;
+        return fail(ZK_ERR_INVALID, "zk_verify_shared_rows: row leaves need 1 <= log_batch <= %u (got %u)", kMaxSharedLog, log_batch);
+    }
+    if (hash_kind == ZK_HASH_BLAKE2S) {
+        *check_out = -1;
+        return fail(ZK_ERR_INVALID, "zk_verify_shared_rows: no BLAKE2s (hash 2) row leaves: no prover makes such a proof");
+    }
+    return verify_entry("zk_verify_shared_rows", proof, len, state,
+                        ProofFormat{.log_n = log_n, .log_b = log_b, .q = n_queries, .grind = grind_bits, .fold = fold_log, .coset = coset_leaves != 0, .stop = stop_log,
+                                    .cap = cap_log, .lb = log_batch, .rows = true},
+                        public_last, hash_kind, check_out, nullptr, "");
+}
 
 size_t zk_proof_size(size_t data_len) { return 48 + data_len; }   // proof.rs:151-154: size_of::<Proof>() = 32 + 16
 size_t zk_proof_data_len_fold(uint32_t log_n, uint32_t log_b, uint32_t n_queries, uint32_t grind_bits, uint32_t fold_log) {
@@ -1596,6 +1617,15 @@ size_t zk_proof_data_len_shared(uint32_t log_n, uint32_t log_b, uint32_t n_queri
     if (fold_log < 1 || fold_log > kMaxFoldLog || !stop_ok(log_n, log_b, stop_log) || cap_log > kMaxCapLog || log_batch > kMaxSharedLog) return 0;
     return ProofFormat{.log_n = log_n, .log_b = log_b, .q = n_queries, .grind = grind_bits, .fold = fold_log, .coset = coset_leaves != 0, .stop = stop_log, .cap = cap_log,
                        .lb = log_batch}
+        .data_len();
+}
+// row_leaves = 0: zk_proof_data_len_shared
+size_t zk_proof_data_len_shared_rows(uint32_t log_n, uint32_t log_b, uint32_t n_queries, uint32_t grind_bits, uint32_t fold_log, int coset_leaves, uint32_t stop_log,
+                                     uint32_t cap_log, uint32_t log_batch, int row_leaves) {
+    if (fold_log < 1 || fold_log > kMaxFoldLog || !stop_ok(log_n, log_b, stop_log) || cap_log > kMaxCapLog || log_batch > kMaxSharedLog) return 0;
+    if (row_leaves && log_batch < 1) return 0;
+    return ProofFormat{.log_n = log_n, .log_b = log_b, .q = n_queries, .grind = grind_bits, .fold = fold_log, .coset = coset_leaves != 0, .stop = stop_log, .cap = cap_log,
+                       .lb = log_batch, .rows = row_leaves != 0}
         .data_len();
 }
 size_t zk_proof_data_len_grind(uint32_t log_n, uint32_t log_b, uint32_t n_queries, uint32_t grind_bits) {
@@ -1816,6 +1846,20 @@ int zk_dev_gather(const uint32_t* d_src, const uint64_t* d_offsets, uint32_t cou
 int zk_dev_merkle_build_ex(const uint32_t* d_vals, uint32_t log_m, uint32_t* d_nodes, void* stream, int hash_kind) {
     if (!d_vals || !d_nodes || log_m > 30 || hash_kind < ZK_HASH_SHA256 || hash_kind > ZK_HASH_BLAKE2S) return fail(ZK_ERR_INVALID, "zk_dev_merkle_build: bad argument");
     HIPCHK(launch_merkle_build(d_vals, log_m, d_nodes, (hipStream_t)stream, dev_prof(), MailArgs{}, hash_kind));
+    return ZK_OK;
+}
+// the tree of a shared proof with row leaves (transcript.hpp "rows"): all 2^(log_len + 1) - 1 nodes
+int zk_dev_merkle_build_rows(const uint32_t* d_vals, uint32_t log_len, uint32_t log_batch, uint32_t* d_nodes, void* stream, int hash_kind) {
+    if (!d_vals || !d_nodes || log_batch < 1 || log_batch > kMaxSharedLog || log_len < 1 || log_len + log_batch > 30)
+        return fail(ZK_ERR_INVALID, "zk_dev_merkle_build_rows: need 1 <= log_batch <= %u, 1 <= log_len and log_len + log_batch <= 30", kMaxSharedLog);
+    if (hash_kind != ZK_HASH_SHA256 && hash_kind != ZK_HASH_FIELD) return fail(ZK_ERR_INVALID, "zk_dev_merkle_build_rows: row leaves take hash 0 or 1 (got %d)", hash_kind);
+    HIPCHK(launch_merkle_build_rows(d_vals, log_len, log_batch, d_nodes, (hipStream_t)stream, dev_prof(), MailArgs{}, hash_kind));
+    return ZK_OK;
+}
+int zk_row_leaf_hash(const uint32_t* values, uint32_t m, int hash_kind, uint8_t out[32]) {
+    if (!values || !out || m < 1 || m > (1u << kMaxSharedLog) || (m & (m - 1))) return fail(ZK_ERR_INVALID, "zk_row_leaf_hash: need a power of two 1 <= m <= %u values", 1u << kMaxSharedLog);
+    if (hash_kind != ZK_HASH_SHA256 && hash_kind != ZK_HASH_FIELD) return fail(ZK_ERR_INVALID, "zk_row_leaf_hash: row leaves take hash 0 or 1 (got %d)", hash_kind);
+    host_coset_leaf_hash(values, m, out, hash_kind);
     return ZK_OK;
 }
 int zk_dev_merkle_build_interleaved(const uint32_t* d_recv, uint32_t log_parts, uint32_t log_cnt, uint32_t* d_nodes, void* stream, int hash_kind) {

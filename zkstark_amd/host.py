@@ -23,10 +23,13 @@ def _no_blake2s(who, hash):
         raise ValueError(f"{who}: hash='blake2s' is not built for this class yet (Context, Merkle and Proof.verify take it)")
 
 
-def _proof_data_len(o, log_batch=0):
+def _proof_data_len(o, log_batch=0, rows=False):
     """Bytes of a proof in the format of `o` (a Proof, Context, BatchContext or Verifier).  zk_proof_data_len_shared is the general
     entry point: log_batch 0 (one statement per proof), cap 0, stop 0 and one-value leaves are the older formats byte for byte.
-    log_batch > 0: ONE shared proof of 2^log_batch statements (BatchContext.prove_shared)."""
+    log_batch > 0: ONE shared proof of 2^log_batch statements (BatchContext.prove_shared); rows: with row leaves."""
+    if rows:
+        return _lib.load().zk_proof_data_len_shared_rows(o.log_n, o.log_blowup, o.queries, o.grind_bits, o.fold_log, int(o.coset_leaves), o.stop_log,
+                                                         o.cap_log, log_batch, 1)
     return _lib.load().zk_proof_data_len_shared(o.log_n, o.log_blowup, o.queries, o.grind_bits, o.fold_log, int(o.coset_leaves), o.stop_log, o.cap_log,
                                                 log_batch)
 
@@ -552,8 +555,9 @@ class BatchContext:
     launch over the whole batch; each proof has its own channel and is byte-identical to Context.prove()."""
 
     def __init__(self, log_n=10, log_blowup=3, log_batch=4, device=0, hash="sha256", queries=1, grind_bits=0, fold_log=1, coset_leaves=False,
-                 stop_log=0, cap_log=0):
-        """fold_log: FRI folding factor 2^fold_log between commitments for every proof of the batch (zk_batch_set_fold; 1 = the
+                 stop_log=0, cap_log=0, shared_rows=False):
+        """shared_rows: prove_shared() commits the traces as row leaves, one f tree and three f paths per query (zk_batch_set_shared_rows).
+        fold_log: FRI folding factor 2^fold_log between commitments for every proof of the batch (zk_batch_set_fold; 1 = the
         reference).  coset_leaves: one coset per Merkle leaf of the FRI trees (zk_batch_set_coset_leaves).  stop_log: every proof stops
         FRI at a polynomial of degree < 2^stop_log and sends its coefficients (zk_batch_set_fri_stop; 0 = fold to a constant).
         cap_log: every proof commits each tree by its 2^cap_log digests of depth cap_log and opens paths that much shorter
@@ -564,6 +568,7 @@ class BatchContext:
         self.coset_leaves = False
         self.stop_log = 0
         self.cap_log = 0
+        self.shared_rows = False
         self.n, self.batch = 1 << log_n, 1 << log_batch
         self._h = C.c_void_p()
         check(_lib.load().zk_batch_create(device, log_n, log_blowup, log_batch, C.byref(self._h)))
@@ -581,6 +586,14 @@ class BatchContext:
             self.set_fri_stop(stop_log)
         if cap_log:
             self.set_merkle_cap(cap_log)
+        if shared_rows:
+            self.set_shared_rows(True)
+
+    def set_shared_rows(self, on=True):
+        """zk_batch_set_shared_rows: from the next prove_shared() on, the 2^log_batch trace polynomials are committed as ONE tree whose leaf i
+        holds the row (f_0[i], .., f_{M-1}[i]); a query opens three rows and three paths whatever the batch.  prove() does not look at it."""
+        check(_lib.load().zk_batch_set_shared_rows(self._h, int(bool(on))))
+        self.shared_rows = bool(_lib.load().zk_batch_get_shared_rows(self._h))
 
     def set_merkle_cap(self, cap_log):
         """zk_batch_set_merkle_cap: from the next zk_batch_prove on, every proof commits a tree of 2^lg leaves by the 2^ce digests of
@@ -669,13 +682,13 @@ class BatchContext:
 
     def prove_shared(self):
         """zk_batch_prove_shared: ONE SharedProof of the batch's resident traces with the current settings."""
-        plen = _proof_data_len(self, self.log_batch)
+        plen = _proof_data_len(self, self.log_batch, self.shared_rows)
         data = np.zeros(max(plen, 1), dtype=np.uint8)
         state = np.zeros(32, dtype=np.uint8)
         got = C.c_size_t()
         check(_lib.load().zk_batch_prove_shared(self._h, _ptr(data), plen, C.byref(got), _ptr(state)))
         return SharedProof(state.tobytes(), data[:got.value].tobytes(), self.log_n, self.log_blowup, self.log_batch, self.public_last(), self.hash,
-                           self.queries, self.grind_bits, self.fold_log, self.coset_leaves, self.stop_log, self.cap_log)
+                           self.queries, self.grind_bits, self.fold_log, self.coset_leaves, self.stop_log, self.cap_log, self.shared_rows)
 
 
 _ERR_VERIFY = -6
@@ -683,23 +696,29 @@ _ERR_VERIFY = -6
 
 class SharedProof:
     """ONE proof of the 2^log_batch statements of a batch (BatchContext.prove_shared, zk_batch_prove_shared): the f trees are committed
-    together, one FRI runs over the sum of the composition polynomials.  public_last: one value per statement."""
+    together, one FRI runs over the sum of the composition polynomials.  public_last: one value per statement.  shared_rows: the f values
+    are committed as row leaves (BatchContext(shared_rows=True)) and the proof is checked by zk_verify_shared_rows."""
 
     def __init__(self, state, data, log_n, log_blowup, log_batch, public_last, hash="sha256", queries=1, grind_bits=0, fold_log=1,
-                 coset_leaves=False, stop_log=0, cap_log=0):
+                 coset_leaves=False, stop_log=0, cap_log=0, shared_rows=False):
         self.state, self.data = bytes(state), bytes(data)
         self.log_n, self.log_blowup, self.log_batch = log_n, log_blowup, log_batch
         self.public_last = _u32arr(public_last)
         self.hash, self.queries, self.grind_bits, self.fold_log = hash, queries, grind_bits, fold_log
         self.coset_leaves, self.stop_log, self.cap_log = bool(coset_leaves), stop_log, cap_log
+        self.shared_rows = bool(shared_rows)
 
     def expected_len(self):
         """The length the format gives a shared proof of this shape."""
-        return _proof_data_len(self, self.log_batch)
+        return _proof_data_len(self, self.log_batch, self.shared_rows)
 
     def _verify(self, strict, out):
         if len(self.public_last) != 1 << self.log_batch:
             raise ZkError(-1, f"expected {1 << self.log_batch} public_last values")
+        if self.shared_rows:
+            return _lib.load().zk_verify_shared_rows(self.data, len(self.data), self.state if strict else None, self.log_n, self.log_blowup,
+                                                     _ptr(self.public_last), self.log_batch, HASHES[self.hash], self.queries, self.grind_bits,
+                                                     self.fold_log, int(self.coset_leaves), self.stop_log, self.cap_log, 1, C.byref(out))
         return _lib.load().zk_verify_shared(self.data, len(self.data), self.state if strict else None, self.log_n, self.log_blowup,
                                             _ptr(self.public_last), self.log_batch, HASHES[self.hash], self.queries, self.grind_bits,
                                             self.fold_log, int(self.coset_leaves), self.stop_log, self.cap_log, C.byref(out))
