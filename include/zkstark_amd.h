@@ -670,6 +670,21 @@ uint32_t zk_verifier_get_fri_stop(const zk_verifier *v);
  * lengths, results and launches are what they were.  zk_verifier_get_merkle_cap: the current c, 0 for a null verifier. */
 int zk_verifier_set_merkle_cap(zk_verifier *v, uint32_t cap_log);
 uint32_t zk_verifier_get_merkle_cap(const zk_verifier *v);
+/* Shared proofs made with zk_batch_prove_shared (log_batch = lb: ONE proof of M = 2^lb statements), with or without row leaves
+ * (zk_batch_set_shared_rows): lb 0..8, default 0 = plain proofs; row_leaves (any non-zero value: on) needs lb >= 1.  An lb out of
+ * range, row leaves with lb 0 or a null verifier: ZK_ERR_INVALID and the setting unchanged.  From the next zk_verifier_run on (a verifier
+ * may change it between runs); it combines with every query count, grinding, fold_log, leaf format, stop_log, cap_log and both hashes of
+ * this class.  zk_verifier_run then takes zk_proof_data_len_shared_rows(log_n, log_blowup, q, grind_bits, fold_log, coset_leaves, D, c,
+ * lb, row_leaves) bytes per proof and public_last[count][M], statement-major per proof, and checks_out[i] is what zk_verify_shared_rows
+ * gives proof i with the same arguments, for EVERY input, strict or not.  Kernels of their own (csrc/verify.hip "shared proofs"): the
+ * -2 relation is summed over the statements on one lane per (proof, query); the f paths run one lane per (proof, statement), or with row
+ * leaves one lane per proof, each row hashed as zk_row_leaf_hash hashes it; the strict replay is one lane per proof.  Proofs whose path
+ * counts differ from the fixed layout go to the CPU verifier with their M public values.  With lb = 0 lengths, results and launches are
+ * what they were.  zk_verifier_get_shared: the current lb, 0 for a null verifier; zk_verifier_get_shared_rows: 1 or 0, 0 for a null
+ * verifier. */
+int zk_verifier_set_shared(zk_verifier *v, uint32_t log_batch, int row_leaves);
+uint32_t zk_verifier_get_shared(const zk_verifier *v);
+int zk_verifier_get_shared_rows(const zk_verifier *v);
 /* count proofs at proofs + i*stride, each exactly zk_proof_data_len_fold(log_n, log_blowup, q, grind_bits, fold_log) bytes (with
  * the defaults zk_proof_data_len_queries(log_n, log_blowup, q); with coset leaves zk_proof_data_len_coset of the same arguments;
  * with an early stop zk_proof_data_len_stop; stride >= that, any alignment); states: count*32 bytes, or NULL = not strict;

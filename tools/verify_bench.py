@@ -23,7 +23,16 @@ named NAME_kK[_coset]_dD.
 the same rounds.  The capped proofs come from the one-call prover (Context(cap_log=c)), the CPU side is zk_verify_cap, every distinct
 proof is first checked with it (strict), and proof_bytes is zk_proof_data_len_cap; a result is named NAME_kK[_coset][_dD]_cC.
 
+--shared LB[,LB...] [--rows] measures shared proofs of 2^LB statements each (Verifier(log_batch=LB, shared_rows=--rows)) over the shapes
+of SHARED_SHAPES: K = 1 with one-value leaves and K = 3 with coset leaves, the query counts of --queries (1 and 16, the most the batched
+prover makes), strict.  The proofs come from
+BatchContext.prove_shared (two distinct ones per setting, tiled), each checked with zk_verify_shared_rows (strict) before it is timed.  The
+yardstick is zk_verify_shared_rows on a 16-thread pool in this process: per setting, --blocks rounds of --steps GPU calls and one pass
+of the pool, in turn, so that drift falls on both alike; both are reported as medians, a result is named NAME_lbLB[_rows]_kK[_coset]_qQ.
+A shape whose batch does not fit the device is reported with its error.
+
     python tools/verify_bench.py [--steps 20] [--warmup 3] [--profile] [--only NAME,...] [--fold 1,2,3 --blocks 5] [--coset] [--stop 0,4,8] [--cap 0,4,8]
+    python tools/verify_bench.py --shared 3,6 [--rows] [--queries 1,16] [--steps 3 --blocks 3] [--only NAME,...]
 """
 import argparse
 import concurrent.futures
@@ -60,6 +69,8 @@ SHAPES = {
     "2e24_q1_strict_8": (21, 3, 1, "sha256", 8, True),
     "2e24_q1_strict_64": (21, 3, 1, "sha256", 64, True),
 }
+# --shared: name: (log_n, log_b, count)
+SHARED_SHAPES = {"2e13_1024": (10, 3, 1024), "2e20_64": (17, 3, 64), "2e24_16": (21, 3, 16)}
 PROFILED = ["ref_strict_1024", "ref_plain_1024", "2e20_strict_1024", "2e24_q1_strict_16", "2e24_q16_strict_16", "ref_field_strict_1024"]
 _cache = {}
 _checked = set()
@@ -173,6 +184,70 @@ def profile(name, steps):
     return stats
 
 
+def shared_result(log_n, log_b, count, lb, rows, K, coset, q, steps, warmup, blocks):
+    """One --shared setting: GPU calls and 16-thread CPU passes over the same `count` proofs, in turn."""
+    lib = _lib.load()
+    kw = dict(queries=q, fold_log=K, coset_leaves=coset)
+    with zk.BatchContext(log_n, log_b, log_batch=lb, shared_rows=rows, **kw) as bc:
+        ps = []
+        for r in range(2):
+            bc.gen_fibsq([1] * bc.batch, [3141592 + r * bc.batch + p for p in range(bc.batch)])
+            ps.append(bc.prove_shared())
+    for p in ps:
+        assert p.check(strict=True) == 0
+    idx = np.arange(count) % len(ps)
+    data = np.ascontiguousarray(np.stack([np.frombuffer(p.data, dtype=np.uint8) for p in ps])[idx])
+    states = np.ascontiguousarray(np.stack([np.frombuffer(p.state, dtype=np.uint8) for p in ps])[idx])
+    last = np.ascontiguousarray(np.stack([np.asarray(p.public_last, dtype=np.uint32) for p in ps])[idx])
+    plen = data.shape[1]
+    jobs = [(data[i].ctypes.data, states[i].ctypes.data, last[i].ctypes.data) for i in range(count)]
+    check = C.c_int32 * 1
+
+    def one(r):
+        return lib.zk_verify_shared_rows(r[0], plen, r[1], log_n, log_b, r[2], lb, 0, q, 0, K, int(coset), 0, 0, int(rows), check())
+
+    gpu, cpu = [], []
+    with zk.Verifier(log_n, log_b, log_batch=lb, shared_rows=rows, **kw) as v, concurrent.futures.ThreadPoolExecutor(16) as ex:
+        assert v.proof_len == plen
+        for _ in range(warmup):
+            assert (v.verify_raw(data, last, states) == 0).all()
+        list(ex.map(one, jobs[:16]))
+        for _ in range(blocks):
+            for _ in range(steps):
+                t0 = time.perf_counter()
+                v.verify_raw(data, last, states)
+                gpu.append((time.perf_counter() - t0) * 1e3)
+            t0 = time.perf_counter()
+            rcs = list(ex.map(one, jobs, chunksize=max(1, count // 64)))
+            cpu.append((time.perf_counter() - t0) * 1e3)
+            assert all(rc == 0 for rc in rcs)
+    gpu.sort()
+    cpu.sort()
+    return {"log_n": log_n, "log_blowup": log_b, "count": count, "log_batch": lb, "shared_rows": rows, "fold_log": K, "coset_leaves": coset, "queries": q,
+            "strict": True, "proof_bytes": plen, "gpu_ms_median": round(gpu[len(gpu) // 2], 4), "gpu_ms_min": round(gpu[0], 4), "gpu_ms_max": round(gpu[-1], 4),
+            "cpu_16t_ms_median": round(cpu[len(cpu) // 2], 3), "cpu_16t_ms_min": round(cpu[0], 3),
+            "speedup_vs_16t": round(cpu[len(cpu) // 2] / gpu[len(gpu) // 2], 2)}
+
+
+def shared_main(a):
+    lbs = tuple(int(x) for x in a.shared.split(","))
+    res = {}
+    for name, (log_n, log_b, count) in SHARED_SHAPES.items():
+        if a.only and name not in a.only.split(","):
+            continue
+        for lb in lbs:
+            for K, coset in ((1, False), (3, True)):
+                for q in (int(x) for x in a.queries.split(",")):
+                    key = f"{name}_lb{lb}" + ("_rows" if a.rows else "") + f"_k{K}" + ("_coset" if coset else "") + f"_q{q}"
+                    try:
+                        res[key] = shared_result(log_n, log_b, count, lb, a.rows, K, coset, q, a.steps, a.warmup, a.blocks)
+                    except (zk.ZkError, MemoryError) as e:
+                        res[key] = {"error": str(e)[:200]}
+                    print(f"# {key}: {res[key]}", file=sys.stderr, flush=True)
+    print(json.dumps({"tool": "verify_bench", "build_hash": _lib.build_hash(), "steps": a.steps, "warmup": a.warmup, "blocks": a.blocks, "shared": list(lbs),
+                      "rows": a.rows, "shapes": res}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=20)
@@ -185,7 +260,13 @@ def main():
     ap.add_argument("--coset", action="store_true", help="every K with coset leaves off and on, interleaved")
     ap.add_argument("--stop", default="", help="early-stop D to measure, e.g. 0,4,8: every K and leaf format once per D, interleaved")
     ap.add_argument("--cap", default="", help="Merkle cap_log to measure, e.g. 0,4,8: every other setting once per cap, interleaved")
+    ap.add_argument("--shared", default="", help="log_batch of shared proofs to measure, e.g. 3,6 (the shapes of SHARED_SHAPES)")
+    ap.add_argument("--rows", action="store_true", help="with --shared: proofs with row leaves")
+    ap.add_argument("--queries", default="1,16", help="with --shared: the query counts to measure (the batched prover makes at most 16)")
     a = ap.parse_args()
+    if a.shared:
+        shared_main(a)
+        return
     folds = tuple(int(k) for k in a.fold.split(","))
     if a.inner:                                       # under rocprofv3: the timed GPU calls of one shape only
         gpu_times(SHAPES[a.inner], a.steps, 1, ((folds[0], True),) if a.coset else folds[:1])

@@ -48,6 +48,26 @@
 // cap entry leaf >> (lg - ce), the transcript commits the 8 * 2^ce words of a cap in one piece.  Slot and tree are uniform per blockIdx.y, so
 // all lanes of a wave still walk paths of one length.  The order keys are those of a folded proof (5 + 9G per query) or of a coset proof
 // (4 + 2G).  No scratch and no LDS.
+//
+// Shared proofs (zk_verifier_set_shared, lb = 1..8, with or without row leaves; verify_transcript, then verify_proof, with lb / rows; any K,
+// leaf format, D and cap): ONE proof of M = 2^lb statements, M public values per proof.  A shared proof always takes the table (cap 0: ce = 0,
+// one digest per cap); the table also says how many f tuples a query has (nft = 3M, or 3 rows), how long one is, and where statement p's share
+// of the f commitment starts.  Five kernels of their own (the kernels above are the code they were; two of the five are further instances of
+// the cap kernels' bodies):
+//   * verify_shared_algebra_kernel, one lane per (proof, query): the counts of the cp tuple, the groups and the three rows, the -2 relation
+//     summed over the M statements as verify_proof sums it (three inversions per lane, three multiplications by alpha per statement), the G
+//     fold comparisons of the cap kernel;
+//   * verify_shared_f_paths_kernel (one-value leaves), one lane per (proof, statement) and blockIdx.y = (query, k): shared batches are few
+//     proofs of many statements, so the statement is on the lane.  Each lane checks the count of its own tuple before it walks L - ce_f levels;
+//   * verify_shared_row_paths_kernel (row leaves), one lane per proof and blockIdx.y = (query, row): the row's leaf is host_coset_leaf_hash
+//     with s = M bit for bit -- the coset leaf up to M = 8, streamed SHA-256 blocks or the field hash's chain from M = 16 on;
+//   * verify_shared_paths_kernel: the cp tuple and the group paths, the slots >= 3 of verify_cap_paths_kernel behind the nft f tuples;
+//   * verify_shared_transcript_kernel (strict), one lane per proof: the f commitment in one commit, 3M alphas, nft f tuples per query.  This
+//     chain is serial in the proof's length, which with one-value leaves grows with M q.
+// The order keys are query * keys + position in verify_proof's visiting order: 0 (-2), 1 + 3p + k (-(4 + k) for statement p; rows: 1 + k),
+// with one-value leaves nft + 1 (-7), then the G fold comparisons, then the group paths as for a folded (8 per group) or a coset proof (1 per
+// group); keys = nft + 2 + 9G, or nft + 1 + 2G with coset leaves (shared_key_to_check).  atomicMin makes the first failing tuple in wire order
+// the result whichever lane finishes first.  No scratch, no LDS, at most 116 VGPRs.
 #include <cstdio>
 #include <cstring>
 #include <mutex>
@@ -589,6 +609,12 @@ struct CapLayout {
     uint32_t capn[kCapTrees];   // its words: 8 * 2^ce
     uint32_t plen[kCapTrees];   // digests of a path into that tree: lg - ce
     uint32_t gw[kCapTrees];     // first word of group j's opening, counted from the first word of the query
+    // shared proofs (ProofFormat::lb / rows; the kernels of a plain proof read none of these).  fwords is then the words of ONE f tuple,
+    // 3 + 8 fplen for a statement's value or 2^lb + 2 + 8 fplen for a row, and the cp tuple (coset: group 0) follows the nft f tuples
+    uint32_t nft;               // f tuples per query: 3 * 2^lb, or 3 rows
+    uint32_t fshare;            // words of one statement's share of the f commitment: 8 * 2^ce_f (rows: unused, one cap for all)
+    uint32_t lb;                // log2 of the statements of a proof
+    uint32_t keys;              // order keys per query (shared_key_to_check): nft + 2 + 9G, or nft + 1 + 2G with coset leaves
 };
 struct VerifyCapArgs {
     VerifyArgs a;
@@ -656,14 +682,19 @@ __global__ void __launch_bounds__(kVerifyThreads) verify_cap_algebra_kernel(Veri
 // (2) with caps: one lane per (proof, query, path slot), the slots of verify_paths_kernel<.., FOLD> (4 + sum s_j) or of
 // verify_coset_paths_kernel (3 + G).  A path climbs plen = lg - ce levels from the leaf's position inside the sub-tree of its cap entry
 // and is compared with entry idx >> plen of the tree's cap.  plen depends on the slot alone: uniform over the wave.
-template <int HASH, bool COSET>
-__global__ void __launch_bounds__(kVerifyThreads) verify_cap_paths_kernel(VerifyCapArgs ca) {
+// SHARED (a shared proof, below): the f tuples have kernels of their own, so the slots start at 3 (blockIdx.y counts from there), the
+// cp tuple and the groups follow the nft f tuples, and the order keys are the shared ones (shared_key_to_check).
+template <int HASH, bool COSET, bool SHARED>
+__device__ __forceinline__ void verify_cap_paths(const VerifyCapArgs& ca) {
     const VerifyArgs& a = ca.a;
     const CapLayout& t = ca.t;
     const uint32_t p = blockIdx.x * kVerifyThreads + threadIdx.x;
     if (p >= a.count) return;
-    const uint32_t slots = COSET ? 3u + a.G : 4u + ((a.G - 1u) << a.K) + (1u << a.ls);
-    const uint32_t qk = blockIdx.y / slots, slot = blockIdx.y % slots;
+    const uint32_t slots = (COSET ? 3u + a.G : 4u + ((a.G - 1u) << a.K) + (1u << a.ls)) - (SHARED ? 3u : 0u);
+    const uint32_t qk = blockIdx.y / slots, slot = blockIdx.y % slots + (SHARED ? 3u : 0u);
+    const uint32_t nft = SHARED ? t.nft : 3u;
+    // where the keys of the fold comparisons start: after -2, the f tuples and (one-value leaves) cp(x)
+    const uint32_t first = SHARED ? nft + (COSET ? 1u : 2u) : COSET ? 4u : 5u;
     const uint32_t* pr = a.proofs + (size_t)p * a.words;
     const uint32_t tp = query_tp(a, pr, qk);
     const uint32_t fq = a.qbase + qk * a.per_q;
@@ -676,12 +707,12 @@ __global__ void __launch_bounds__(kVerifyThreads) verify_cap_paths_kernel(Verify
         capw = 0u;
         pos = 1u + slot;
     } else if (!COSET && slot == 3u) {                    // cp(x) against the cap of group 0's tree
-        val_w = fq + 3u * t.fwords;
+        val_w = fq + nft * t.fwords;
         path_w = val_w + 3u;
         plen = t.cpplen;
         idx = tp;
         capw = t.capw[0];
-        pos = 4u;
+        pos = first - 1u;
     } else if constexpr (COSET) {                         // the leaf of group j from its s_j slot words
         const uint32_t j = slot - 3u, steps = cap_group_steps(a, j);
         s = 1u << steps;
@@ -690,7 +721,7 @@ __global__ void __launch_bounds__(kVerifyThreads) verify_cap_paths_kernel(Verify
         plen = t.plen[j];
         idx = tp & ((1u << (a.L - j * a.K - steps)) - 1u);
         capw = t.capw[j];
-        pos = 4u + a.G + j;
+        pos = first + a.G + j;
     } else {                                              // value u of group j at (tp % size + u size / s) % size
         const uint32_t j = (slot - 4u) >> a.K, u = (slot - 4u) & ((1u << a.K) - 1u);
         const uint32_t gs = 1u << cap_group_steps(a, j), gw = fq + t.gw[j], size = a.N >> (j * a.K);
@@ -699,7 +730,7 @@ __global__ void __launch_bounds__(kVerifyThreads) verify_cap_paths_kernel(Verify
         path_w = gw + gs + u * (2u + 8u * plen) + 2u;
         idx = (tp % size + u * (size / gs)) % size;
         capw = t.capw[j];
-        pos = 5u + a.G + 8u * j + u;
+        pos = first + a.G + 8u * j + u;
     }
     Digest cur;
     if constexpr (COSET) cur = coset_vleaf<HASH>(pr + val_w, s);
@@ -721,16 +752,20 @@ __global__ void __launch_bounds__(kVerifyThreads) verify_cap_paths_kernel(Verify
     bool same = true;
 #pragma unroll
     for (int i = 0; i < 8; ++i) same = same && cur.w[i] == be_word(entry + i);
-    if (!same) atomicMin(&a.best[p], (int32_t)(qk * (COSET ? 4u + 2u * a.G : 5u + 9u * a.G) + pos));
+    if (!same) atomicMin(&a.best[p], (int32_t)(qk * (first + (COSET ? 2u : 9u) * a.G) + pos));
 }
+template <int HASH, bool COSET>
+__global__ void __launch_bounds__(kVerifyThreads) verify_cap_paths_kernel(VerifyCapArgs ca) { verify_cap_paths<HASH, COSET, false>(ca); }
 
 // (3) with caps (strict only): one lane per proof, the schedule of verify_transcript_kernel with every root commit widened to the cap's
 // words and every tuple shortened to its paths' digests; D != 0 drops the last root and commits the 2^D coefficients where the free term was.
-template <bool COSET>
-__global__ void __launch_bounds__(kVerifyThreads) verify_cap_transcript_kernel(VerifyCapArgs ca) {
+// SHARED (a shared proof, below): na = 3 * 2^lb alphas after the f commitment, and nft f tuples (rows: 3) in front of a query's cp tuple.
+template <bool COSET, bool SHARED>
+__device__ __forceinline__ void verify_cap_transcript(const VerifyCapArgs& ca) {
     const VerifyArgs& a = ca.a;
     const CapLayout& t = ca.t;
-    constexpr uint32_t NF = COSET ? 3u : 4u;              // f tuples per query
+    const uint32_t na = SHARED ? 3u << t.lb : 3u, nft = SHARED ? t.nft : 3u;
+    const uint32_t NF = nft + (COSET ? 0u : 1u);          // f tuples per query, cp(x) included
     const uint32_t p = blockIdx.x * kVerifyThreads + threadIdx.x;
     if (p >= a.count) return;
     const uint32_t* pr = a.proofs + (size_t)p * a.words;
@@ -741,7 +776,7 @@ __global__ void __launch_bounds__(kVerifyThreads) verify_cap_transcript_kernel(V
     // steps: f cap | 3 alphas | cap 0 | R x (beta, cap j + 1) | free term | [nonce] | q query raws | q x (NF f tuples, R groups)
     // D != 0: the last beta has no cap after it, and the step of the free term commits the 2^D coefficients
     const uint32_t gs = a.gw ? 1u : 0u;
-    const uint32_t ft = (a.D ? 4u : 5u) + 2u * R;
+    const uint32_t ft = na + (a.D ? 1u : 2u) + 2u * R;
     const uint32_t head = ft + 1u + gs + q;
     const uint32_t steps = head + q * (NF + R);
     uint32_t cur = 0, k = 0;
@@ -750,15 +785,15 @@ __global__ void __launch_bounds__(kVerifyThreads) verify_cap_transcript_kernel(V
         bool chal = false;
         uint32_t nw;
         if (s < head) {
-            chal = (s >= 1u && s <= 3u) || (s >= 5u && s < ft && ((s - 5u) & 1u) == 0u) || s >= ft + 1u + gs;
+            chal = (s >= 1u && s <= na) || (s >= na + 2u && s < ft && ((s - na - 2u) & 1u) == 0u) || s >= ft + 1u + gs;
             if (chal) nw = 1u;
             else if (s == 0u) nw = t.fcapn;
-            else if (s < ft) nw = t.capn[(s - 4u) >> 1];  // s = 4: the tree of group 0; s = 6 + 2j: of group j + 1 (the last layer's: entry G)
+            else if (s < ft) nw = t.capn[(s - na - 1u) >> 1];   // s = na + 1: the tree of group 0; s = na + 3 + 2j: of group j + 1 (the last layer's: entry G)
             else nw = s == ft ? 1u << a.D : 2u;           // D = 0: the free term, one word
         } else {
             const uint32_t u = (s - head) % (NF + R);
-            if (u < 3u) nw = t.fwords;
-            else if (!COSET && u == 3u) nw = t.cpwords;
+            if (u < nft) nw = t.fwords;
+            else if (!COSET && u == nft) nw = t.cpwords;
             else {
                 const uint32_t j = u - NF, gsteps = cap_group_steps(a, j);
                 nw = COSET ? (1u << gsteps) + 2u + 8u * t.plen[j] : (3u + 8u * t.plen[j]) << gsteps;
@@ -780,6 +815,234 @@ __global__ void __launch_bounds__(kVerifyThreads) verify_cap_transcript_kernel(V
     }
     a.tcode[p] = code;
 }
+template <bool COSET>
+__global__ void __launch_bounds__(kVerifyThreads) verify_cap_transcript_kernel(VerifyCapArgs ca) { verify_cap_transcript<COSET, false>(ca); }
+
+// ---- shared proofs (the file header) ---------------------------------------------------------------------------------------------
+// The order keys of a shared proof, per query (verify_proof's visiting order): 0 (-2), 1 + 3p + k (the path of statement p's f(g^k x),
+// -(4 + k); rows: 1 + k, the path of row k), then with one-value leaves nft + 1 (-7), then the G fold comparisons and the group paths as
+// for a folded (9G keys) or a coset proof (2G keys).
+__device__ __forceinline__ uint32_t shared_first(const CapLayout& t, bool coset) { return t.nft + (coset ? 1u : 2u); }   // the key of group 0's fold
+__device__ __forceinline__ uint32_t shared_keys(const VerifyArgs& a, const CapLayout& t, bool coset) {
+    return shared_first(t, coset) + (coset ? 2u : 9u) * a.G;
+}
+
+// (1) of a shared proof: one lane per (proof, query).  The path counts of the cp tuple and the groups, and with rows those of the three
+// rows (the plain f tuples check their own: verify_shared_f_paths_kernel); the -2 relation summed over the 2^lb statements; the G fold
+// comparisons of verify_cap_algebra_kernel.  The denominators of -2 depend on x alone: the sums of alpha_i times numerator_i over the
+// statements are kept Montgomery-scaled (one mont_mul per term) and meet the three inverses, scaled the other way, once at the end.  All
+// residues are canonical, so the sum equals verify_proof's bit for bit.
+template <bool COSET, bool ROWS>
+__global__ void __launch_bounds__(kVerifyThreads) verify_shared_algebra_kernel(VerifyCapArgs ca) {
+    const VerifyArgs& a = ca.a;
+    const CapLayout& t = ca.t;
+    const uint64_t lane = (uint64_t)blockIdx.x * kVerifyThreads + threadIdx.x;
+    if (lane >= (uint64_t)a.count * a.q) return;
+    const uint32_t p = (uint32_t)(lane / a.q), qk = (uint32_t)(lane % a.q);
+    const uint32_t* pr = a.proofs + (size_t)p * a.words;
+    const uint32_t M = 1u << t.lb;
+    const uint32_t keys = shared_keys(a, t, COSET), first = shared_first(t, COSET);
+    const uint32_t fq = a.qbase + qk * a.per_q, cpw = fq + t.nft * t.fwords;   // cpw: the cp tuple, or group 0's leaf
+    bool ok = true;
+    if constexpr (ROWS) {
+        for (uint32_t k = 0; k < 3; ++k) {
+            const uint32_t* c = pr + fq + k * t.fwords + M;
+            ok = ok && c[0] == t.fplen && c[1] == 0u;
+        }
+    }
+    if constexpr (!COSET) ok = ok && pr[cpw + 1u] == t.cpplen && pr[cpw + 2u] == 0u;
+#pragma unroll 1
+    for (uint32_t j = 0; j < a.G; ++j) {
+        const uint32_t s = 1u << cap_group_steps(a, j), len = t.plen[j];
+        const uint32_t* c = pr + fq + t.gw[j] + s;
+        if constexpr (COSET) ok = ok && c[0] == len && c[1] == 0u;
+        else for (uint32_t u = 0; u < s; ++u) ok = ok && c[u * (2u + 8u * len)] == len && c[u * (2u + 8u * len) + 1u] == 0u;
+    }
+    if (!ok) { a.malformed[p] = 1u; return; }
+
+    const uint32_t tp = query_tp(a, pr, qk);
+    const uint32_t x = dmul(GEN_W, dpow(a.h, tp));
+    int32_t key = kNoFailure;
+    {   // proof.rs:63-77 summed over the statements, as verify_proof sums it
+        uint32_t xn = x;
+        for (uint32_t i = 0; i < a.log_n; ++i) xn = dmul(xn, xn);
+        const uint32_t den = dmul(sub(xn, 1u), dinv(dmul(dmul(sub(x, a.gm3), sub(x, a.gm2)), sub(x, a.gm1))));
+        // inverse * R^2: a sum of mont_mul(alpha, numerator) terms (each product / R) times this, by mont_mul, is the canonical product
+        const uint32_t i0 = mont_mul(mont_mul(dinv(sub(x, 1u)), R2), R2), i1 = mont_mul(mont_mul(dinv(sub(x, a.gm2)), R2), R2);
+        const uint32_t i2 = mont_mul(mont_mul(dinv(den), R2), R2);
+        const uint32_t* pub = a.pub + (size_t)p * M;
+        const uint32_t fstep = ROWS ? 1u : 3u * t.fwords, kstep = t.fwords;   // from statement to statement, from f(g^k x) to f(g^(k+1) x)
+        uint32_t s0 = 0u, s1 = 0u, s2 = 0u;
+#pragma unroll 2
+        for (uint32_t s = 0; s < M; ++s) {
+            const uint32_t* fv = pr + fq + s * fstep;
+            const uint32_t* al = pr + t.aw + 3u * s;
+            const uint32_t f_x = fv[0] % P, f_gx = fv[kstep] % P, f_ggx = fv[2u * kstep] % P;
+            const uint32_t num = sub(sub(f_ggx, dmul(f_gx, f_gx)), dmul(f_x, f_x));
+            s0 = add(s0, mont_mul(al[0] % P, sub(f_x, 1u)));
+            s1 = add(s1, mont_mul(al[1] % P, sub(f_x, pub[s] % P)));
+            s2 = add(s2, mont_mul(al[2] % P, num));
+        }
+        const uint32_t cp0 = add(add(mont_mul(s0, i0), mont_mul(s1, i1)), mont_mul(s2, i2));
+        if (cp0 != pr[cpw + (COSET ? coset_rot(a, tp, 0u) : 0u)]) key = (int32_t)(qk * keys);
+    }
+    uint32_t ixk = dinv(x);                               // x = 5 h^tp is never zero: the one inversion of this lane's folds
+#pragma unroll 1
+    for (uint32_t j = 0; j < a.G && key == kNoFailure; ++j) {
+        const uint32_t* vals = pr + fq + t.gw[j];
+        const uint32_t beta = pr[t.bw[j]] % P, rot = COSET ? coset_rot(a, tp, j) : 0u, steps = cap_group_steps(a, j);
+        uint32_t calc;
+        if (steps == 3u) calc = fold_group<3>(a, vals, beta, ixk, rot);
+        else if (steps == 2u) calc = fold_group<2>(a, vals, beta, ixk, rot);
+        else calc = fold_group<1>(a, vals, beta, ixk, rot);
+        uint32_t expect;
+        if (j + 1u < a.G) expect = pr[fq + t.gw[j + 1u] + (COSET ? coset_rot(a, tp, j + 1u) : 0u)];
+        else if (a.D) {
+            uint32_t xs = x;
+#pragma unroll 1
+            for (uint32_t i = 0; i < a.R; ++i) xs = dmul(xs, xs);
+            expect = final_poly_from(a, pr + t.ftw, xs);
+        } else expect = pr[t.ftw];
+        if (calc != expect) key = (int32_t)(qk * keys + first + j);
+    }
+    if (key != kNoFailure) atomicMin(&a.best[p], key);
+}
+
+// One path of one-value or coset / row leaves from digest `cur` of leaf idx: plen levels up inside the sub-tree of its cap entry, then
+// the comparison with entry idx >> plen of the cap at `cap` (the walk of verify_cap_paths).
+template <int HASH>
+__device__ __forceinline__ bool path_misses(Digest cur, const uint32_t* path, uint32_t plen, uint32_t idx, const uint32_t* cap) {
+    uint32_t node = (idx & ((1u << plen) - 1u)) + (1u << plen) - 1u;   // heap index inside the sub-tree of the cap entry
+    for (uint32_t lvl = 0; lvl < plen; ++lvl) {
+        Digest sib;
+        const uint32_t* sp = path + 8u * lvl;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) sib.w[i] = be_word(sp + i);
+        const bool right = (node & 1u) == 0u;             // an even heap index is a right child
+        Digest l, r;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) { l.w[i] = right ? sib.w[i] : cur.w[i]; r.w[i] = right ? cur.w[i] : sib.w[i]; }
+        cur = vinner<HASH>(l, r);
+        node = (node - (right ? 2u : 1u)) >> 1;
+    }
+    const uint32_t* entry = cap + 8u * (idx >> plen);
+    bool same = true;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) same = same && cur.w[i] == be_word(entry + i);
+    return !same;
+}
+
+// (2a) the f paths of a shared proof with one-value leaves: one lane per (proof, statement), blockIdx.y = query * 3 + k.  A shared batch
+// is few proofs of many statements, so the statement is on the lane: one proof of 64 statements fills a wave, and every lane walks
+// L - ce_f levels.  Tuple 3p + k of the query holds f_p(g^k x); its path lands in statement p's share of the f commitment.  Each lane
+// checks the u64 count of its own tuple (the algebra kernel does not) before it walks.
+template <int HASH>
+__global__ void __launch_bounds__(kVerifyThreads) verify_shared_f_paths_kernel(VerifyCapArgs ca) {
+    const VerifyArgs& a = ca.a;
+    const CapLayout& t = ca.t;
+    const uint64_t lane = (uint64_t)blockIdx.x * kVerifyThreads + threadIdx.x;
+    if (lane >= ((uint64_t)a.count << t.lb)) return;
+    const uint32_t p = (uint32_t)(lane >> t.lb), st = (uint32_t)lane & ((1u << t.lb) - 1u);
+    const uint32_t qk = blockIdx.y / 3u, k = blockIdx.y % 3u;
+    const uint32_t* pr = a.proofs + (size_t)p * a.words;
+    const uint32_t* tup = pr + a.qbase + qk * a.per_q + (3u * st + k) * t.fwords;
+    if (tup[1] != t.fplen || tup[2] != 0u) { a.malformed[p] = 1u; return; }
+    const uint32_t idx = query_tp(a, pr, qk) + k * a.B;
+    if (path_misses<HASH>(vleaf<HASH>(tup[0]), tup + 3u, t.fplen, idx, pr + st * t.fshare))
+        atomicMin(&a.best[p], (int32_t)(qk * t.keys + 1u + 3u * st + k));
+}
+
+// The digest of a row of M = 2^lb values, bit for bit host_coset_leaf_hash (transcript.hpp), raw words >= P included.  M <= 8: the coset
+// leaf.  M >= 16, SHA-256: M / 16 data blocks (a value is its big-endian message word), then the padding block; field hash: the chain of
+// fieldhash_row_leaf, M / 8 compressions with word 15 = M in the first (row_path_misses).  The block loop is not unrolled; the next
+// SHA-256 block is loaded before the current one is compressed, and only the chaining state lives across blocks (row_leaf_hash_kernel,
+// with the values contiguous here).  M is the same for every lane of a launch.
+template <int HASH>
+__device__ __forceinline__ Digest row_vleaf(const uint32_t* vals, uint32_t M) {
+    static_assert(HASH == 0, "the field hash's row leaf is part of its path walk: row_path_misses");
+    if (M <= 8u) return coset_vleaf<HASH>(vals, M);
+    Digest d;
+    {
+        const uint32_t nb = M / 16u;
+        uint32_t cur[16], nx[16];
+#pragma unroll
+        for (int u = 0; u < 16; ++u) { cur[u] = vals[u]; nx[u] = 0u; }
+#pragma unroll
+        for (int i = 0; i < 8; ++i) d.w[i] = SHA_IV[i];
+#pragma unroll 1
+        for (uint32_t k = 0; k < nb; ++k) {
+            if (k + 1u < nb) {
+                const uint32_t* src = vals + 16u * (k + 1u);
+#pragma unroll
+                for (int u = 0; u < 16; ++u) nx[u] = src[u];
+            }
+            sha256_compress(d.w, cur);
+#pragma unroll
+            for (int u = 0; u < 16; ++u) cur[u] = nx[u];
+        }
+        uint32_t pad[16] = {0x80000000u, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 32u * M};
+        sha256_compress(d.w, pad);
+    }
+    return d;
+}
+
+// The path of a row: its leaf, plen levels up, the comparison with cap entry idx >> plen.  The field hash's leaf is one loop of
+// max(M / 8, 1) compressions whose first trip is the first chunk (v_0 .. v_7, or with M < 8 the M values and zeros; then 0, .., 0, M), so
+// the kernel holds two inlined compressions, the leaf's and the inner node's, as the paths kernels of one-value leaves do.
+// pr: the proof; roww: the first word of the row tuple (M values, the count, plen digests), the same for every lane; the cap is at word 0.
+template <int HASH>
+__device__ __forceinline__ bool row_path_misses(const uint32_t* pr, uint32_t roww, uint32_t M, uint32_t plen, uint32_t idx) {
+    if constexpr (HASH == 0) return path_misses<0>(row_vleaf<0>(pr + roww, M), pr + roww + M + 2u, plen, idx, pr);
+    else {
+        const uint32_t nb = M > 8u ? M / 8u : 1u;
+        Digest cur;
+        uint32_t in[kFhT];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {                     // M < 8: the words past the values are the count and the path, loaded but not used
+            const uint32_t w = pr[roww + (uint32_t)i];
+            in[i] = (uint32_t)i < M ? w : 0u;
+            in[8 + i] = i == 7 ? M : 0u;
+        }
+        uint32_t k = 1u;
+#pragma unroll 1
+        for (;;) {
+            fh64_compress(in, cur.w, g_vfh_consts64);
+            if (k >= nb) break;
+            const uint32_t* src = pr + roww + 8u * k;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) { in[i] = cur.w[i]; in[8 + i] = src[i]; }
+            ++k;
+        }
+        return path_misses<1>(cur, pr + roww + M + 2u, plen, idx, pr);
+    }
+}
+
+// (2b) the f paths of a shared proof with row leaves: one lane per proof, blockIdx.y = query * 3 + k.  Row k of the query -- M values, a
+// count (the algebra kernel checks it), L - ce_f digests -- is ONE leaf at index tp + k B of the one tree over the rows.
+// The second launch bound asks for five waves per SIMD, the occupancy of the other field-hash paths kernels (88 VGPRs): without it the
+// sixteen S-boxes of the leaf chain's full rounds are interleaved up to 130 VGPRs.
+template <int HASH>
+__global__ void __launch_bounds__(kVerifyThreads, 5) verify_shared_row_paths_kernel(VerifyCapArgs ca) {
+    const VerifyArgs& a = ca.a;
+    const CapLayout& t = ca.t;
+    const uint32_t p = blockIdx.x * kVerifyThreads + threadIdx.x;
+    if (p >= a.count) return;
+    const uint32_t qk = blockIdx.y / 3u, k = blockIdx.y % 3u, M = 1u << t.lb;
+    const uint32_t* pr = a.proofs + (size_t)p * a.words;
+    const uint32_t idx = query_tp(a, pr, qk) + k * a.B;
+    if (row_path_misses<HASH>(pr, a.qbase + qk * a.per_q + k * t.fwords, M, t.fplen, idx))
+        atomicMin(&a.best[p], (int32_t)(qk * t.keys + 1u + k));
+}
+
+// (2c) the cp tuple and the group paths of a shared proof: the slots >= 3 of verify_cap_paths_kernel, behind the nft f tuples.
+template <int HASH, bool COSET>
+__global__ void __launch_bounds__(kVerifyThreads) verify_shared_paths_kernel(VerifyCapArgs ca) { verify_cap_paths<HASH, COSET, true>(ca); }
+
+// (3) of a shared proof (strict only): one lane per proof; the f commitment is one commit of all its words, 3 * 2^lb alphas follow it,
+// and a query commits its nft f tuples one by one.  The chain is serial in the proof's length: with one-value leaves that is 3 * 2^lb
+// tuples per query.
+template <bool COSET>
+__global__ void __launch_bounds__(kVerifyThreads) verify_shared_transcript_kernel(VerifyCapArgs ca) { verify_cap_transcript<COSET, true>(ca); }
 
 std::mutex g_consts_mu;
 bool g_consts_done[64] = {false};
@@ -825,6 +1088,17 @@ int32_t coset_key_to_check(int32_t key, uint32_t G) {
     if (pos < 4 + G) return -(int32_t)(100u + (pos - 4u));
     return -(int32_t)(300u + (pos - 4u - G));
 }
+// The same for the keys of a shared proof: nft f tuples per query (3 per statement, or 3 rows) in front of the cp tuple and the groups.
+int32_t shared_key_to_check(int32_t key, uint32_t nft, uint32_t G, bool coset) {
+    const uint32_t first = nft + (coset ? 1u : 2u), pos = (uint32_t)key % (first + (coset ? 2u : 9u) * G);
+    if (pos == 0) return -2;
+    if (pos <= nft) return -(int32_t)(4u + (pos - 1u) % 3u);   // -4 .. -6 of statement (pos - 1) / 3, or of row pos - 1
+    if (pos < first) return -7;                           // one-value leaves only
+    if (pos < first + G) return -(int32_t)(100u + (pos - first));
+    if (coset) return -(int32_t)(300u + (pos - first - G));
+    const uint32_t j = (pos - first - G) / 8u, t = (pos - first - G) % 8u;
+    return -(int32_t)((t ? 400u : 300u) + j);
+}
 
 }  // namespace
 }  // namespace zk
@@ -845,9 +1119,10 @@ namespace {
 
 size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
-int verifier_reserve(zk_verifier* v, size_t chunk, size_t len) {
-    const size_t in_bytes = chunk * (len + 4 + 32);
-    const size_t dev_bytes = align256(chunk * len) + align256(chunk * 4) + align256(chunk * 32) + 3 * align256(chunk * 4);
+// pub: the bytes of a proof's public values, 4 per statement
+int verifier_reserve(zk_verifier* v, size_t chunk, size_t len, size_t pub) {
+    const size_t in_bytes = chunk * (len + pub + 32);
+    const size_t dev_bytes = align256(chunk * len) + align256(chunk * pub) + align256(chunk * 32) + 3 * align256(chunk * 4);
     if (chunk <= v->cap && in_bytes <= v->cap_in && dev_bytes <= v->cap_out) return ZK_OK;
     HIPCHK(hipStreamSynchronize(v->stream));
     HIPCHK(hipStreamSynchronize(v->tstream));
@@ -868,16 +1143,17 @@ int verifier_chunk(zk_verifier* v, const uint8_t* proofs, size_t stride, size_t 
     const ProofFormat& f = v->fmt;
     const uint32_t log_n = f.log_n, log_b = f.log_b, q = f.q, D = f.stop, L = f.L();
     const uint32_t R = f.rounds(), K = f.fold, G = f.groups();   // the folded rounds (early stop: R', and G' groups)
-    const bool coset = f.coset;
-    // inputs: [count][len] proofs, [count] public_last, [count][32] states, packed into the pinned staging buffer
+    const bool coset = f.coset, shared = f.lb != 0;
+    const size_t pub = (size_t)4 << f.lb;                  // bytes of a proof's public values
+    // inputs: [count][len] proofs, [count][2^lb] public_last, [count][32] states, packed into the pinned staging buffer
     uint8_t* hp = v->h_in;
     if (stride == len) memcpy(hp, proofs, count * len);
     else for (size_t i = 0; i < count; ++i) memcpy(hp + i * len, proofs + i * stride, len);
-    memcpy(hp + count * len, public_last, count * 4);
-    if (states) memcpy(hp + count * len + count * 4, states, count * 32);
+    memcpy(hp + count * len, public_last, count * pub);
+    if (states) memcpy(hp + count * len + count * pub, states, count * 32);
     uint8_t* d = v->d_buf;
     uint8_t* d_pub = d + align256(count * len);
-    uint8_t* d_states = d_pub + align256(count * 4);
+    uint8_t* d_states = d_pub + align256(count * pub);
     uint8_t* d_res = d_states + align256(count * 32);
     VerifyArgs a{};
     a.proofs = reinterpret_cast<const uint32_t*>(d);
@@ -913,11 +1189,15 @@ int verifier_chunk(zk_verifier* v, const uint8_t* proofs, size_t stride, size_t 
         return true;
     });
     a.qbase = w;
-    t.fplen = (uint32_t)f.f_path(); t.fwords = 3u + 8u * t.fplen;
+    t.fplen = (uint32_t)f.f_path();
+    t.fwords = (uint32_t)(Channel::group_bytes(f.rows ? (size_t)1 << f.lb : 1, t.fplen, f.rows) / 4);   // 3 + 8 fplen, or a row's 2^lb + 2 + 8 fplen
     t.cpplen = (uint32_t)f.tree_path(0); t.cpwords = 3u + 8u * t.cpplen;
+    t.lb = f.lb; t.nft = f.rows ? 3u : 3u << f.lb; t.fshare = f.rows ? 0u : 8u << f.f_cap();
+    t.keys = t.nft + (coset ? 1u + 2u * G : 2u + 9u * G);
+    const uint32_t nf = t.nft + (coset ? 0u : 1u);         // the tuples in front of group 0: the f tuples and, with one-value leaves, cp(x)
     uint32_t tuple = 0, off = 0;
     f.for_each_tuple([&](size_t s, size_t plen, bool one_leaf) {
-        if (tuple >= (coset ? 3u : 4u)) { t.plen[tuple - (coset ? 3u : 4u)] = (uint32_t)plen; t.gw[tuple - (coset ? 3u : 4u)] = off; }
+        if (tuple >= nf) { t.plen[tuple - nf] = (uint32_t)plen; t.gw[tuple - nf] = off; }
         off += (uint32_t)(Channel::group_bytes(s, plen, one_leaf) / 4);
         ++tuple;
     });
@@ -927,8 +1207,8 @@ int verifier_chunk(zk_verifier* v, const uint8_t* proofs, size_t stride, size_t 
     a.inv2m = to_mont(a.inv2); a.wm1 = to_mont(w8); a.wm2 = to_mont(mulmod(w8, w8)); a.wm3 = to_mont(mulmod(mulmod(w8, w8), w8));
 
     HIPCHK(hipMemcpyAsync(d, hp, count * len, hipMemcpyHostToDevice, v->stream));
-    HIPCHK(hipMemcpyAsync(d_pub, hp + count * len, count * 4, hipMemcpyHostToDevice, v->stream));
-    if (states) HIPCHK(hipMemcpyAsync(d_states, hp + count * len + count * 4, count * 32, hipMemcpyHostToDevice, v->stream));
+    HIPCHK(hipMemcpyAsync(d_pub, hp + count * len, count * pub, hipMemcpyHostToDevice, v->stream));
+    if (states) HIPCHK(hipMemcpyAsync(d_states, hp + count * len + count * pub, count * 32, hipMemcpyHostToDevice, v->stream));
     HIPCHK(hipMemsetAsync(a.best, 0x7f, count * 4, v->stream));
     HIPCHK(hipMemsetAsync(a.malformed, 0, count * 4, v->stream));
     HIPCHK(hipMemsetAsync(a.tcode, 0, count * 4, v->stream));
@@ -937,7 +1217,10 @@ int verifier_chunk(zk_verifier* v, const uint8_t* proofs, size_t stride, size_t 
     if (states) {                                      // the transcript chains run beside the paths: cost = max of the two
         HIPCHK(hipEventRecord(v->ev_in, v->stream));
         HIPCHK(hipStreamWaitEvent(v->tstream, v->ev_in, 0));
-        if (v->fmt.cap) {
+        if (shared) {                                  // a shared proof takes the table whatever its cap
+            if (coset) hipLaunchKernelGGL(verify_shared_transcript_kernel<true>, dim3(gx), dim3(kVerifyThreads), 0, v->tstream, ca);
+            else hipLaunchKernelGGL(verify_shared_transcript_kernel<false>, dim3(gx), dim3(kVerifyThreads), 0, v->tstream, ca);
+        } else if (v->fmt.cap) {
             if (coset) hipLaunchKernelGGL(verify_cap_transcript_kernel<true>, dim3(gx), dim3(kVerifyThreads), 0, v->tstream, ca);
             else hipLaunchKernelGGL(verify_cap_transcript_kernel<false>, dim3(gx), dim3(kVerifyThreads), 0, v->tstream, ca);
         } else if (D) {
@@ -952,7 +1235,13 @@ int verifier_chunk(zk_verifier* v, const uint8_t* proofs, size_t stride, size_t 
     }
     const uint64_t lanes = (uint64_t)count * q;
     const dim3 agrid((uint32_t)((lanes + kVerifyThreads - 1) / kVerifyThreads));
-    if (v->fmt.cap) {                                      // one instance per leaf format covers every K and D
+    if (shared) {
+        if (coset) {
+            if (f.rows) hipLaunchKernelGGL((verify_shared_algebra_kernel<true, true>), agrid, dim3(kVerifyThreads), 0, v->stream, ca);
+            else hipLaunchKernelGGL((verify_shared_algebra_kernel<true, false>), agrid, dim3(kVerifyThreads), 0, v->stream, ca);
+        } else if (f.rows) hipLaunchKernelGGL((verify_shared_algebra_kernel<false, true>), agrid, dim3(kVerifyThreads), 0, v->stream, ca);
+        else hipLaunchKernelGGL((verify_shared_algebra_kernel<false, false>), agrid, dim3(kVerifyThreads), 0, v->stream, ca);
+    } else if (v->fmt.cap) {                               // one instance per leaf format covers every K and D
         if (coset) hipLaunchKernelGGL(verify_cap_algebra_kernel<true>, agrid, dim3(kVerifyThreads), 0, v->stream, ca);
         else hipLaunchKernelGGL(verify_cap_algebra_kernel<false>, agrid, dim3(kVerifyThreads), 0, v->stream, ca);
     } else if (D) {                                           // the STOP instances: the last group against the final polynomial
@@ -972,7 +1261,25 @@ int verifier_chunk(zk_verifier* v, const uint8_t* proofs, size_t stride, size_t 
     else hipLaunchKernelGGL(verify_fold_algebra_kernel<3>, agrid, dim3(kVerifyThreads), 0, v->stream, a);
     HIPCHK(hipGetLastError());
     const bool sha = v->hash == ZK_HASH_SHA256;
-    if (v->fmt.cap) {
+    if (shared) {
+        // the f tuples: three rows per query with the proof on the lane, or 3 * 2^lb tuples with the (proof, statement) on the lane
+        if (f.rows) {
+            const dim3 fgrid(gx, 3u * q);
+            if (sha) hipLaunchKernelGGL(verify_shared_row_paths_kernel<0>, fgrid, dim3(kVerifyThreads), 0, v->stream, ca);
+            else hipLaunchKernelGGL(verify_shared_row_paths_kernel<1>, fgrid, dim3(kVerifyThreads), 0, v->stream, ca);
+        } else {
+            const dim3 fgrid((uint32_t)((((uint64_t)count << f.lb) + kVerifyThreads - 1) / kVerifyThreads), 3u * q);
+            if (sha) hipLaunchKernelGGL(verify_shared_f_paths_kernel<0>, fgrid, dim3(kVerifyThreads), 0, v->stream, ca);
+            else hipLaunchKernelGGL(verify_shared_f_paths_kernel<1>, fgrid, dim3(kVerifyThreads), 0, v->stream, ca);
+        }
+        HIPCHK(hipGetLastError());
+        const dim3 pgrid(gx, q * (coset ? G : 1u + ((G - 1u) << K) + (1u << a.ls)));   // the cp tuple and the groups
+        if (coset) {
+            if (sha) hipLaunchKernelGGL((verify_shared_paths_kernel<0, true>), pgrid, dim3(kVerifyThreads), 0, v->stream, ca);
+            else hipLaunchKernelGGL((verify_shared_paths_kernel<1, true>), pgrid, dim3(kVerifyThreads), 0, v->stream, ca);
+        } else if (sha) hipLaunchKernelGGL((verify_shared_paths_kernel<0, false>), pgrid, dim3(kVerifyThreads), 0, v->stream, ca);
+        else hipLaunchKernelGGL((verify_shared_paths_kernel<1, false>), pgrid, dim3(kVerifyThreads), 0, v->stream, ca);
+    } else if (v->fmt.cap) {
         const dim3 pgrid(gx, q * (coset ? 3u + G : 4u + ((G - 1u) << K) + (1u << a.ls)));
         if (coset) {
             if (sha) hipLaunchKernelGGL((verify_cap_paths_kernel<0, true>), pgrid, dim3(kVerifyThreads), 0, v->stream, ca);
@@ -1005,8 +1312,9 @@ int verifier_chunk(zk_verifier* v, const uint8_t* proofs, size_t stride, size_t 
         int32_t c;
         if (states && tcode[i]) c = tcode[i];
         else if (malformed[i])                             // garbage only
-            c = verify_proof(proofs + i * stride, len, f, public_last[i], v->hash);
+            c = verify_proof(proofs + i * stride, len, f, public_last + (i << f.lb), v->hash);
         else if (best[i] == kNoFailure) c = 0;
+        else if (shared) c = shared_key_to_check(best[i], t.nft, G, coset);
         else c = coset ? coset_key_to_check(best[i], G) : (K == 1 && !v->fmt.cap) ? key_to_check(best[i], R) : fold_key_to_check(best[i], G);
         checks_out[i] = c;
     }
@@ -1116,6 +1424,19 @@ int zk_verifier_set_coset_leaves(zk_verifier* v, int on) {
 
 int zk_verifier_get_coset_leaves(const zk_verifier* v) { return v && v->fmt.coset ? 1 : 0; }
 
+int zk_verifier_set_shared(zk_verifier* v, uint32_t log_batch, int row_leaves) {
+    if (!v) return fail(ZK_ERR_INVALID, "null verifier");
+    if (log_batch > kMaxSharedLog) return fail(ZK_ERR_INVALID, "zk_verifier_set_shared: need log_batch <= %u (got %u)", kMaxSharedLog, log_batch);
+    if (row_leaves && log_batch < 1) return fail(ZK_ERR_INVALID, "zk_verifier_set_shared: row leaves need log_batch >= 1");
+    v->fmt.lb = log_batch;
+    v->fmt.rows = row_leaves != 0;
+    return ZK_OK;
+}
+
+uint32_t zk_verifier_get_shared(const zk_verifier* v) { return v ? v->fmt.lb : 0u; }
+
+int zk_verifier_get_shared_rows(const zk_verifier* v) { return v && v->fmt.rows ? 1 : 0; }
+
 int zk_verifier_run(zk_verifier* v, const uint8_t* proofs, size_t stride, size_t count, const uint8_t* states, const uint32_t* public_last,
                     int32_t* checks_out) {
     if (!v) return fail(ZK_ERR_INVALID, "null verifier");
@@ -1130,10 +1451,11 @@ int zk_verifier_run(zk_verifier* v, const uint8_t* proofs, size_t stride, size_t
     if (chunk > 65536) chunk = 65536;
     if (chunk < 1) chunk = 1;
     if (chunk > count) chunk = count;
-    if (int rc = verifier_reserve(v, chunk, len)) return rc;
+    const uint32_t lb = v->fmt.lb;                      // public_last: [count][2^lb], statement-major per proof
+    if (int rc = verifier_reserve(v, chunk, len, (size_t)4 << lb)) return rc;
     for (size_t i = 0; i < count; i += chunk) {
         const size_t c = count - i < chunk ? count - i : chunk;
-        if (int rc = verifier_chunk(v, proofs + i * stride, stride, c, states ? states + 32 * i : nullptr, public_last + i, checks_out + i, len))
+        if (int rc = verifier_chunk(v, proofs + i * stride, stride, c, states ? states + 32 * i : nullptr, public_last + (i << lb), checks_out + i, len))
             return rc;
     }
     for (size_t i = 0; i < count; ++i)

@@ -741,8 +741,10 @@ class Verifier:
     that proof: 0 = accepted, otherwise the CPU verifier's check number."""
 
     def __init__(self, log_n, log_blowup, device=0, hash="sha256", queries=1, grind_bits=0, fold_log=1, coset_leaves=False, stop_log=0,
-                 cap_log=0):
-        """cap_log: the proofs commit every tree by 2^cap_log digests (zk_verifier_set_merkle_cap; Context(cap_log=)).
+                 cap_log=0, log_batch=0, shared_rows=False):
+        """log_batch, shared_rows: the proofs are shared proofs of 2^log_batch statements each (BatchContext.prove_shared), with row leaves
+        when shared_rows (zk_verifier_set_shared; 0: plain proofs).
+        cap_log: the proofs commit every tree by 2^cap_log digests (zk_verifier_set_merkle_cap; Context(cap_log=)).
         fold_log: the FRI folding factor 2^fold_log of the proofs to check (zk_verifier_set_fold; 1 = the reference).
         coset_leaves: the proofs were made with coset leaves (zk_verifier_set_coset_leaves; Context(coset_leaves=True)).
         stop_log: the proofs stop FRI early at a polynomial of 2^stop_log coefficients (zk_verifier_set_fri_stop; Context(stop_log=))."""
@@ -752,6 +754,7 @@ class Verifier:
         self.coset_leaves = False
         self.stop_log = 0
         self.cap_log = 0
+        self.log_batch, self.shared_rows = 0, False
         self._h = C.c_void_p()
         check(_lib.load().zk_verifier_create(device, log_n, log_blowup, C.byref(self._h)))
         if hash != "sha256":
@@ -768,6 +771,14 @@ class Verifier:
             self.set_fri_stop(stop_log)
         if cap_log:
             self.set_merkle_cap(cap_log)
+        if log_batch or shared_rows:
+            self.set_shared(log_batch, shared_rows)
+
+    def set_shared(self, log_batch, rows=False):
+        """zk_verifier_set_shared: from the next run on, check shared proofs of 2^log_batch statements each (0: plain proofs), committed
+        as row leaves when rows.  public_last is then 2^log_batch values per proof."""
+        check(_lib.load().zk_verifier_set_shared(self._h, log_batch, int(bool(rows))))
+        self.log_batch, self.shared_rows = log_batch, bool(rows)
 
     def set_merkle_cap(self, cap_log):
         """zk_verifier_set_merkle_cap: from the next run on, check proofs whose trees are committed by 2^cap_log digests (0: by roots)."""
@@ -802,18 +813,19 @@ class Verifier:
 
     @property
     def proof_len(self):
-        return _proof_data_len(self)
+        return _proof_data_len(self, self.log_batch, self.shared_rows)
 
     def verify_raw(self, data, public_last, states=None):
-        """data: [count, stride] uint8 (stride >= proof_len; BatchContext.prove_raw()'s array as it is), public_last: [count],
-        states: [count, 32] uint8 or None (not strict).  Returns the check numbers as an int32 array of length count."""
+        """data: [count, stride] uint8 (stride >= proof_len; BatchContext.prove_raw()'s array as it is), public_last: [count], or for
+        shared proofs [count, 2^log_batch] (or flat, statement-major per proof), states: [count, 32] uint8 or None (not strict).
+        Returns the check numbers as an int32 array of length count."""
         data = np.ascontiguousarray(data, dtype=np.uint8)
         if data.ndim != 2:
             raise ZkError(-1, "verify_raw: data must be [count, stride]")
         count, stride = data.shape
-        last = _u32arr(public_last)
-        if len(last) != count:
-            raise ZkError(-1, f"verify_raw: {len(last)} public_last values for {count} proofs")
+        last = _u32arr(np.asarray(public_last).reshape(-1))
+        if len(last) != count << self.log_batch:
+            raise ZkError(-1, f"verify_raw: {len(last)} public_last values for {count} proofs of {1 << self.log_batch} statement(s)")
         st = None
         if states is not None:
             st = np.ascontiguousarray(states, dtype=np.uint8)
@@ -827,7 +839,7 @@ class Verifier:
 
     def verify(self, proofs, strict=True):
         """proofs: a list of Proof of this verifier's size, folding factor, leaf format and early stop (their data, state and public_last
-        are used)."""
+        are used); with log_batch > 0 a list of SharedProof of 2^log_batch statements each."""
         proofs = list(proofs)
         plen = self.proof_len
         data = np.zeros((len(proofs), plen), dtype=np.uint8)
@@ -842,10 +854,18 @@ class Verifier:
                 raise ZkError(-1, f"verify: proof {i} was made with stop_log {getattr(p, 'stop_log', 0)}, this verifier is set to stop_log {self.stop_log}")
             if getattr(p, "cap_log", 0) != self.cap_log:
                 raise ZkError(-1, f"verify: proof {i} was made with cap_log {getattr(p, 'cap_log', 0)}, this verifier is set to cap_log {self.cap_log}")
+            if getattr(p, "log_batch", 0) != self.log_batch:
+                raise ZkError(-1, f"verify: proof {i} was made with log_batch {getattr(p, 'log_batch', 0)}, this verifier is set to log_batch {self.log_batch}")
+            if bool(getattr(p, "shared_rows", False)) != self.shared_rows:
+                raise ZkError(-1, f"verify: proof {i} was made with shared_rows {bool(getattr(p, 'shared_rows', False))}, "
+                                  f"this verifier is set to shared_rows {self.shared_rows}")
             if len(p.data) != plen:
                 raise ZkError(-1, f"verify: proof {i} has {len(p.data)} bytes, this verifier takes {plen}")
             data[i] = np.frombuffer(p.data, dtype=np.uint8)
-        last = np.array([p.public_last & 0xFFFFFFFF for p in proofs], dtype=np.uint32)
+        if self.log_batch:
+            last = np.array([np.asarray(p.public_last, dtype=np.uint32) for p in proofs], dtype=np.uint32).reshape(len(proofs), -1)
+        else:
+            last = np.array([p.public_last & 0xFFFFFFFF for p in proofs], dtype=np.uint32)
         states = np.array([np.frombuffer(p.state, dtype=np.uint8) for p in proofs], dtype=np.uint8).reshape(len(proofs), 32) if strict else None
         return self.verify_raw(data, last, states)
 
