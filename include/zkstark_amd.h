@@ -117,6 +117,14 @@ uint32_t zk_field_generator(void);                   /* field.rs:52-86: the same
 uint32_t zk_field_root_of_unity(uint32_t log_order); /* prover.rs:48-49 */
 uint32_t zk_field_order(uint32_t a);                 /* field.rs:45-49 (via P-1 = 3*2^30, not brute force) */
 
+/* ---- the quadratic extension E = F_P[u] / (u^2 - 5) on the host ------------
+ * 5 = zk_field_generator() is a non-residue.  An element is a pair (c0, c1) = c0 + c1 u;
+ * (a0 + a1 u)(b0 + b1 u) = (a0 b0 + 5 a1 b1) + (a0 b1 + a1 b0) u.  Inputs are any u32 (reduced mod P as zk_field_* reduce),
+ * results canonical; out may alias an input.  ZK_OK or ZK_ERR_INVALID (null argument; the inverse of zero). */
+int zk_ext_mul(const uint32_t a[2], const uint32_t b[2], uint32_t out[2]);
+int zk_ext_inv(const uint32_t a[2], uint32_t out[2]);
+int zk_ext_pow(const uint32_t a[2], uint64_t e, uint32_t out[2]);
+
 /* ---- context ------------------------------------------------------------- */
 /* Allocates HBM for a proof with trace group size n = 2^log_n and blow-up
  * B = 2^log_blowup (reference literals: 10 and 3, prover.rs:48-57), builds the
@@ -267,6 +275,23 @@ int zk_ctx_final_poly(const zk_ctx *ctx, uint32_t *out, size_t cap, size_t *coun
  * zk_ctx_merkle_cap: what the last one-call proof committed for `tree`, 32 * 2^ce bytes (ce = 0: the root); ZK_ERR_BUFFER if out_len is
  * smaller, ZK_ERR_STATE before the first proof or for a tree the proof did not build. */
 int zk_ctx_set_merkle_cap(zk_ctx *ctx, uint32_t cap_log);
+/* Challenges in the quadratic extension E = F_P[u] / (u^2 - 5) (zk_ext_*; DESIGN.md 7j fixes the format): ext_log = 1, default 0, from the
+ * next one-call proof on (zk_prove, zk_prove_resident, zk_prove_channel, zk_prove_many), with every fold_log, leaf format, fri_stop,
+ * merkle_cap, query count, grinding, hashes 0 and 1 and host levels.  The trace and f stay in the base field; the alphas, cp, every beta
+ * and every FRI layer are in E.  With ext on every folding factor and leaf format takes the grouped round loop (no fused leaf launches,
+ * early launch or host FRI tail), the trees over cp and the FRI layers are row trees over the layer's two planes, and the reference
+ * self-checks (zk_ctx_set_checks) hold both planes to the degree bound.  The setter sizes the second planes and the decommitment buffers
+ * when called, both ways: with ext_log = 0 zk_ctx_device_bytes, every launch and every byte are what they were.  It drops the layers of
+ * the last proof.  ZK_ERR_INVALID for ext_log > 1 (2, the quartic extension, is reserved) and for ext_log = 1 with BLAKE2s, which has no
+ * row leaf (zk_ctx_set_hash(2) with ext on is refused the same way); ZK_ERR_STATE while a proof runs on the context (a proof started
+ * while the setter runs gets ZK_ERR_STATE instead).  After an ext proof zk_last_transcript holds component 0 of every challenge in the
+ * fields it has, zk_ctx_ext_challenges the component-1 raws (alpha0.c1, alpha1.c1, alpha2.c1, then one per group; *count = 0 after a
+ * base-field proof), zk_ctx_final_poly the words of the free term or the coefficients in wire order, and layers with id >= 1 are not
+ * materialised for zk_layer_read (ZK_ERR_STATE).  Proofs: zk_proof_data_len_ext bytes, checked by zk_verify_ext.
+ * The stage-by-stage context API (zk_compose, zk_fri_fold, zk_merkle_commit, ...) stays base-field. */
+int zk_ctx_set_ext(zk_ctx *ctx, uint32_t ext_log);
+uint32_t zk_ctx_get_ext(const zk_ctx *ctx);
+int zk_ctx_ext_challenges(const zk_ctx *ctx, uint32_t *out, size_t cap, size_t *count);
 uint32_t zk_ctx_get_merkle_cap(const zk_ctx *ctx);
 uint32_t zk_ctx_merkle_cap_log(const zk_ctx *ctx, uint32_t tree);
 int zk_ctx_merkle_cap(const zk_ctx *ctx, uint32_t tree, uint8_t *out, size_t out_len);
@@ -540,6 +565,12 @@ size_t zk_proof_data_len_stop(uint32_t log_n, uint32_t log_blowup, uint32_t n_qu
  * returns.  0 where that returns 0, or for cap_log > 8. */
 size_t zk_proof_data_len_cap(uint32_t log_n, uint32_t log_blowup, uint32_t n_queries, uint32_t grind_bits, uint32_t fold_log,
                              int coset_leaves, uint32_t stop_log, uint32_t cap_log);
+/* Proofs with challenges in the quadratic extension E (ext_log = 1; zk_ext_*): zk_proof_data_len_cap of the other arguments
+ * with 24 bytes of alphas for 12, 8 per beta for 4, twice the bytes of the free term or of the coefficients, and 4 more bytes per value of cp
+ * or of a FRI layer opened (the three f values of a query are unchanged).  ext_log = 0: what zk_proof_data_len_cap returns.  0 where that
+ * returns 0, or for ext_log > 1 (2, the quartic extension, is reserved). */
+size_t zk_proof_data_len_ext(uint32_t log_n, uint32_t log_blowup, uint32_t n_queries, uint32_t grind_bits, uint32_t fold_log,
+                             int coset_leaves, uint32_t stop_log, uint32_t cap_log, uint32_t ext_log);
 /* Shared proofs of M = 2^log_batch statements (zk_batch_prove_shared): zk_proof_data_len_cap of the other arguments, plus
  * 32 (M - 1) 2^ce_f + 12 (M - 1) in the head and 3 (M - 1) (12 + 32 (L - ce_f)) per query, ce_f = min(c, L - 1).  log_batch = 0: what
  * zk_proof_data_len_cap returns.  0 where that returns 0, or for log_batch > 8. */
@@ -613,6 +644,16 @@ int zk_verify_stop(const uint8_t *proof, size_t len, const uint8_t *state, uint3
 int zk_verify_cap(const uint8_t *proof, size_t len, const uint8_t *state, uint32_t log_n, uint32_t log_blowup, uint32_t public_last,
                   int hash_kind, uint32_t n_queries, uint32_t grind_bits, uint32_t fold_log, int coset_leaves, uint32_t stop_log,
                   uint32_t cap_log, int32_t *check_out);
+
+/* zk_verify_cap for proofs whose challenges, composition polynomial and FRI layers lie in E = F_P[u] / (u^2 - 5) (ext_log = 1; DESIGN.md 7j
+ * fixes the format), hashes 0 and 1.  The check numbers are zk_verify_cap's, one for one; a comparison of values of E (-2, a group's fold
+ * -(100+j), the last fold against the free term or the final polynomial) fails when either component differs; the strict replay counts
+ * 6 + 2G + q challenges.  Anything that is not zk_proof_data_len_ext bytes long: -1, strict or not.  ext_log = 0 is zk_verify_cap (the same
+ * code path); ext_log > 1, and ext_log = 1 with BLAKE2s (which has no row leaf), are ZK_ERR_INVALID with *check_out = -1.
+ * The one-call prover makes such proofs with zk_ctx_set_ext(ctx, 1). */
+int zk_verify_ext(const uint8_t *proof, size_t len, const uint8_t *state, uint32_t log_n, uint32_t log_blowup, uint32_t public_last,
+                  int hash_kind, uint32_t n_queries, uint32_t grind_bits, uint32_t fold_log, int coset_leaves, uint32_t stop_log,
+                  uint32_t cap_log, uint32_t ext_log, int32_t *check_out);
 
 /* zk_verify_cap for a shared proof of M = 2^log_batch statements (zk_batch_prove_shared), hashes 0..2; public_last: M values.  The same
  * code as zk_verify_cap with the statements summed: -2 compares sum_p (alpha0_p p0_p + alpha1_p p1_p + alpha2_p p2_p) at x with the cp
@@ -935,6 +976,18 @@ int zk_dev_fri_fold(const zk_dom *dom, const uint32_t *d_in, uint32_t *d_out, ui
  * 2^(log_m-steps) values of layer round + steps (round + steps <= log_n).  steps = 1 is zk_dev_fri_fold. */
 int zk_dev_fri_fold_multi(const zk_dom *dom, const uint32_t *d_in, uint32_t *d_out, uint32_t log_m, uint32_t round,
                           uint32_t steps, uint32_t beta_raw, void *stream);
+/* The composition and the group fold with challenges in E = F_P[u] / (u^2 - 5) (zk_ext_*).  A layer of len values of
+ * E is two planes: component 0 at words [0, len), component 1 at [len, 2 len); f stays in the base field.
+ * zk_dev_compose_ext: alpha_raw = alpha0.c0, alpha0.c1, alpha1.c0, alpha1.c1, alpha2.c0, alpha2.c1 (raws, reduced mod P); d_cp takes
+ * 2 N words, and plane j is what zk_dev_compose gives with (alpha0.cj, alpha1.cj, alpha2.cj) -- in one pass over f.
+ * zk_dev_fri_fold_multi_ext: d_in = 2 * 2^log_m words, d_out = 2 * 2^(log_m-steps); beta_raw = (c0, c1), the challenges beta,
+ * beta^2, beta^4 squared in E; steps = 1..3.  With beta_raw[1] = 0 each plane is zk_dev_fri_fold_multi of that plane.
+ * The one-call prover runs them with zk_ctx_set_ext(ctx, 1); the stage-by-stage context API, the batched and sharded provers and the GPU
+ * verifier are base-field; zk_verify_ext is the CPU verifier of the format. */
+int zk_dev_compose_ext(const zk_dom *dom, const uint32_t *d_f, uint32_t *d_cp, uint32_t first, uint32_t last,
+                       const uint32_t alpha_raw[6], void *stream);
+int zk_dev_fri_fold_multi_ext(const zk_dom *dom, const uint32_t *d_in, uint32_t *d_out, uint32_t log_m, uint32_t round,
+                              uint32_t steps, const uint32_t beta_raw[2], void *stream);
 /* zk_dev_fri_fold_multi over a proof-major batch: d_in = [batch][2^log_m], d_out = [batch][2^(log_m-steps)], proof b folded with
  * its own challenge d_beta_raw[b] (raw u32 values on the device; values >= P are accepted and reduced).  d_work: 8 * batch words of
  * caller scratch for the per-proof constants.  Stream-ordered: two launches, no allocation, no host synchronisation.  Any

@@ -116,6 +116,14 @@ SYMBOLS = {
     "zk_field_generator": (_u32, []),
     "zk_field_root_of_unity": (_u32, [_u32]),
     "zk_field_order": (_u32, [_u32]),
+    "zk_ctx_set_ext": (_int, [_vp, _u32]),
+    "zk_ctx_get_ext": (_u32, [_vp]),
+    "zk_ctx_ext_challenges": (_int, [_vp, C.POINTER(_u32), _sz, C.POINTER(_sz)]),
+    "zk_ext_mul": (_int, [C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32)]),
+    "zk_ext_inv": (_int, [C.POINTER(_u32), C.POINTER(_u32)]),
+    "zk_ext_pow": (_int, [C.POINTER(_u32), C.c_uint64, C.POINTER(_u32)]),
+    "zk_dev_compose_ext": (_int, [_vp, _vp, _vp, _u32, _u32, C.POINTER(_u32), _vp]),
+    "zk_dev_fri_fold_multi_ext": (_int, [_vp, _vp, _vp, _u32, _u32, _u32, C.POINTER(_u32), _vp]),
     "zk_dev_trace_fibsq_batch": (_int, [_vp, _vp, _u32, _u32, _vp, _vp]),
     "zk_trace_fibsq_batch_host": (_int, [_int, _vp, _vp, _u32, _u32, _vp]),
     "zk_ctx_create": (_int, [_int, _u32, _u32, C.POINTER(_vp)]),
@@ -155,6 +163,8 @@ SYMBOLS = {
     "zk_ctx_merkle_cap": (_int, [_vp, _u32, _vp, _sz]),
     "zk_proof_data_len_cap": (_sz, [_u32, _u32, _u32, _u32, _u32, _int, _u32, _u32]),
     "zk_verify_cap": (_int, [_vp, _sz, _vp, _u32, _u32, _u32, _int, _u32, _u32, _u32, _int, _u32, _u32, C.POINTER(C.c_int32)]),
+    "zk_proof_data_len_ext": (_sz, [_u32, _u32, _u32, _u32, _u32, _int, _u32, _u32, _u32]),
+    "zk_verify_ext": (_int, [_vp, _sz, _vp, _u32, _u32, _u32, _int, _u32, _u32, _u32, _int, _u32, _u32, _u32, C.POINTER(C.c_int32)]),
     "zk_verify_stop": (_int, [_vp, _sz, _vp, _u32, _u32, _u32, _int, _u32, _u32, _u32, _int, _u32, C.POINTER(C.c_int32)]),
     "zk_dev_fri_fold_multi": (_int, [_vp, _vp, _vp, _u32, _u32, _u32, _u32, _vp]),
     "zk_dev_fri_fold_multi_batch": (_int, [_vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _u32, _vp]),

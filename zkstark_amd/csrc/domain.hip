@@ -223,6 +223,22 @@ int dom_compose(const zk_dom* d, const uint32_t* d_f, uint32_t* d_cp, uint32_t f
     return ZK_OK;
 }
 
+// cp over E (ext.hpp): alpha_raw = alpha0.c0, alpha0.c1, alpha1.c0, alpha1.c1, alpha2.c0, alpha2.c1, the order they are drawn in;
+// d_cp takes two planes of N words.  Component 0 is set up by compose_args itself, so plane 0 is dom_compose's cp for it.
+int dom_compose_ext(const zk_dom* d, const uint32_t* d_f, uint32_t* d_cp, uint32_t first, uint32_t last, const uint32_t alpha_raw[6],
+                    hipStream_t s, Profiler* prof) {
+    const uint32_t c0[3] = {alpha_raw[0], alpha_raw[2], alpha_raw[4]}, c1[3] = {alpha_raw[1], alpha_raw[3], alpha_raw[5]};
+    ComposeExtArgs e;
+    ComposeArgs one;
+    int rc = compose_args(d, d_f, d_cp, first, last, c0, e.a);
+    if (!rc) rc = compose_args(d, d_f, d_cp, first, last, c1, one);
+    if (rc) return rc;
+    e.alpha0_mont1 = one.alpha0_mont; e.alpha1g2_mont1 = one.alpha1g2_mont;
+    for (size_t r = 0; r < 32; ++r) e.zz1[r] = one.zz[r];
+    HIPCHK(launch_compose_ext(e, s, prof));
+    return ZK_OK;
+}
+
 // polynomial.rs:385-400 + prover.rs:204-211 in evaluation form: layer of 2^log_m values at
 // x_i = (shift h^i)^(2^round) -> 2^(log_m-1) values.
 int fold_args(const zk_dom* d, const uint32_t* d_in, uint32_t* d_out, uint32_t log_m, uint32_t round, uint32_t beta_raw, FoldArgs& a) {
@@ -292,6 +308,36 @@ int dom_fold_multi(const zk_dom* d, const uint32_t* d_in, uint32_t* d_out, uint3
     int rc = fold_multi_args(d, d_in, d_out, log_m, round, steps, beta_raw, a);
     if (rc) return rc;
     HIPCHK(launch_fri_fold_multi(a, s, prof));
+    return ZK_OK;
+}
+
+// The group fold over E (ext.hpp): values and the challenge beta = (beta_raw[0], beta_raw[1]) in E, squared in E between the steps;
+// d_in is two planes of 2^log_m words, d_out two planes of 2^(log_m - steps).  The root-of-unity part of every constant is
+// fold_multi_args' with beta = 1; steps = 1 takes the same kernel (there is no separate one-round form over E).
+int fold_multi_ext_args(const zk_dom* d, const uint32_t* d_in, uint32_t* d_out, uint32_t log_m, uint32_t round, uint32_t steps,
+                        const uint32_t beta_raw[2], FoldMultiExtArgs& a) {
+    FoldMultiArgs b;
+    if (int rc = fold_multi_args(d, d_in, d_out, log_m, round, steps, 1u, b)) return rc;
+    a = FoldMultiExtArgs{};
+    a.in = d_in; a.out = d_out; a.log_m = log_m; a.round = round; a.steps = steps;
+    a.hinv = b.hinv; a.scale_mont = b.scale_mont;
+    const uint32_t S = 1u << steps;
+    Ext bk = ext_reduce(beta_raw[0], beta_raw[1]);                             // beta^(2^k)
+    for (uint32_t k = 0; k < steps; ++k) {
+        for (uint32_t t = 0; t < (S >> (k + 1)); ++t) {
+            const uint32_t j = S - (S >> k) + t, root = mont_mul(b.c_mont[j], 1u);   // back from Montgomery form
+            a.c[j] = ext_const(Ext{mulmod(bk.c0, root), mulmod(bk.c1, root)});
+        }
+        bk = ext_mul(bk, bk);
+    }
+    return ZK_OK;
+}
+int dom_fold_multi_ext(const zk_dom* d, const uint32_t* d_in, uint32_t* d_out, uint32_t log_m, uint32_t round, uint32_t steps,
+                       const uint32_t beta_raw[2], hipStream_t s, Profiler* prof) {
+    FoldMultiExtArgs a;
+    int rc = fold_multi_ext_args(d, d_in, d_out, log_m, round, steps, beta_raw, a);
+    if (rc) return rc;
+    HIPCHK(launch_fri_fold_multi_ext(a, s, prof));
     return ZK_OK;
 }
 

@@ -181,6 +181,14 @@ int fold_multi_args(const zk_dom* d, const uint32_t* d_in, uint32_t* d_out, uint
                     FoldMultiArgs& a);
 int dom_fold_multi(const zk_dom* d, const uint32_t* d_in, uint32_t* d_out, uint32_t log_m, uint32_t round, uint32_t steps, uint32_t beta_raw,
                    hipStream_t s, Profiler* prof = nullptr);
+// The composition and the group fold over E = GF(P)[u] / (u^2 - 5) (ext.hpp): challenges are pairs of raws (c0, c1),
+// a layer of len values of E is two planes of len words, f stays in the base field
+int dom_compose_ext(const zk_dom* d, const uint32_t* d_f, uint32_t* d_cp, uint32_t first, uint32_t last, const uint32_t alpha_raw[6],
+                    hipStream_t s, Profiler* prof = nullptr);
+int fold_multi_ext_args(const zk_dom* d, const uint32_t* d_in, uint32_t* d_out, uint32_t log_m, uint32_t round, uint32_t steps,
+                        const uint32_t beta_raw[2], FoldMultiExtArgs& a);
+int dom_fold_multi_ext(const zk_dom* d, const uint32_t* d_in, uint32_t* d_out, uint32_t log_m, uint32_t round, uint32_t steps,
+                       const uint32_t beta_raw[2], hipStream_t s, Profiler* prof = nullptr);
 // The interpolant of FRI layer 1 + round (2^log_m <= 4096 values) as monomial coefficients: d_out[1 + k] = c_k, d_out[0] = how many
 // c_k with k >= bound are non-zero (fri_final_poly_kernel); polys > 1: one workgroup per layer, strides in words
 int dom_final_poly(const zk_dom* d, const uint32_t* d_in, uint32_t* d_out, uint32_t log_m, uint32_t round, uint32_t bound, hipStream_t s,

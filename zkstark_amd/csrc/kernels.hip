@@ -433,6 +433,93 @@ hipError_t launch_compose(const ComposeArgs& a, hipStream_t s, Profiler* prof) {
     return hipGetLastError();
 }
 
+// ---- cp over E (ComposeExtArgs) ----------------------------------------------------------------------------------
+// cp = alpha0 p0 + alpha1 p1 + alpha2 p2 with the alphas in E and p0, p1, p2 in the base field: the operands are fetched once and the
+// three quotient terms formed once, then each plane takes its own three products.  compose_eval's t2 = num * (v3 * zz) is taken as
+// (num * v3) * zz here -- the same residue, and the product that does not depend on the component is shared -- so a value costs 14
+// Montgomery multiplications where compose_eval has 11, and plane j is compose_eval with component j of the alphas word for word.
+__device__ __forceinline__ Ext compose_ext_eval(const ComposeExtArgs& e, uint32_t f0, uint32_t f1, uint32_t f2, uint32_t inv0, uint32_t inv2,
+                                                    uint32_t x, uint32_t zz0, uint32_t zz1) {
+    const ComposeArgs& a = e.a;
+    const uint32_t q0 = mont_mul(sub(f0, a.first), inv0);
+    const uint32_t q1 = mont_mul(sub(f0, a.last), inv2);
+    const uint32_t v3 = mont_mul(mont_mul(sub(x, a.gm3_mont), sub(x, a.gm2_mont)), sub(x, a.gm1_mont));   // V*R
+    const uint32_t num = sub(sub(mont_mul(f2, 1u), mont_mul(f1, f1)), mont_mul(f0, f0));
+    const uint32_t nv = mont_mul(num, v3);
+    Ext r;
+    r.c0 = add(add(mont_mul(q0, a.alpha0_mont), mont_mul(q1, a.alpha1g2_mont)), mont_mul(nv, zz0));
+    r.c1 = add(add(mont_mul(q0, e.alpha0_mont1), mont_mul(q1, e.alpha1g2_mont1)), mont_mul(nv, zz1));
+    return r;
+}
+
+__global__ __launch_bounds__(256) void compose_ext_kernel(ComposeExtArgs e) {
+    const ComposeArgs& a = e.a;
+    const size_t N = (size_t)1 << a.logN;
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N) return;
+    const ComposeRaw r = compose_fetch(a, a.f, i);
+    const uint32_t x = mont_mul(mont_mul(r.x_hi, r.x_lo), a.w_mont);
+    const Ext v = compose_ext_eval(e, r.f0, r.f1, r.f2, r.inv0, r.inv2, x, r.zz, e.zz1[i & ((1u << a.log_b) - 1)]);
+    a.cp[i] = v.c0;
+    a.cp[N + i] = v.c1;
+}
+
+// compose_kernel4's fetches and taps (whole vectors for B >= 4, windows for B = 1, 2), one 16-byte store per plane
+__global__ __launch_bounds__(256) void compose_ext_kernel4(ComposeExtArgs e) {
+    const ComposeArgs& a = e.a;
+    const size_t N = (size_t)1 << a.logN;
+    const uint32_t B = 1u << a.log_b;
+    const size_t i = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+    if (i >= N) return;
+    const uint4* fv = reinterpret_cast<const uint4*>(a.f);
+    const uint4* iv = reinterpret_cast<const uint4*>(a.inv_xm1);
+    uint32_t f0[4], f1[4], f2[4], inv0[4], inv2[4], zz0[4], zz1[4];
+    const uint4 v0 = fv[i >> 2], w0 = iv[i >> 2];
+    f0[0] = v0.x; f0[1] = v0.y; f0[2] = v0.z; f0[3] = v0.w;
+    inv0[0] = w0.x; inv0[1] = w0.y; inv0[2] = w0.z; inv0[3] = w0.w;
+    if (B >= 4) {
+        const uint4 v1 = fv[((i + B) & (N - 1)) >> 2], v2 = fv[((i + 2 * (size_t)B) & (N - 1)) >> 2], w2 = iv[((i + 2 * (size_t)B) & (N - 1)) >> 2];
+        f1[0] = v1.x; f1[1] = v1.y; f1[2] = v1.z; f1[3] = v1.w;
+        f2[0] = v2.x; f2[1] = v2.y; f2[2] = v2.z; f2[3] = v2.w;
+        inv2[0] = w2.x; inv2[1] = w2.y; inv2[2] = w2.z; inv2[3] = w2.w;
+        const uint32_t z0 = (uint32_t)i & (B - 1);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { zz0[k] = a.zz[z0 + k]; zz1[k] = e.zz1[z0 + k]; }
+    } else {
+        const uint4 v1 = fv[((i + 4) & (N - 1)) >> 2], w1 = iv[((i + 4) & (N - 1)) >> 2];
+        const uint32_t fw[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
+        const uint32_t iw[8] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            f1[k] = B == 1 ? fw[k + 1] : fw[k + 2];
+            f2[k] = B == 1 ? fw[k + 2] : fw[k + 4];
+            inv2[k] = B == 1 ? iw[k + 2] : iw[k + 4];
+            zz0[k] = B == 1 ? a.zz[0] : a.zz[k & 1];
+            zz1[k] = B == 1 ? e.zz1[0] : e.zz1[k & 1];
+        }
+    }
+    uint32_t x = mont_mul(pow_lookup(a.htab, (uint32_t)i), a.w_mont);
+    const uint32_t h = pow_lookup(a.htab, 1u);
+    Ext r[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        r[k] = compose_ext_eval(e, f0[k], f1[k], f2[k], inv0[k], inv2[k], x, zz0[k], zz1[k]);
+        if (k < 3) x = mont_mul(x, h);
+    }
+    reinterpret_cast<uint4*>(a.cp)[i >> 2] = make_uint4(r[0].c0, r[1].c0, r[2].c0, r[3].c0);
+    reinterpret_cast<uint4*>(a.cp)[(N + i) >> 2] = make_uint4(r[0].c1, r[1].c1, r[2].c1, r[3].c1);
+}
+
+hipError_t launch_compose_ext(const ComposeExtArgs& e, hipStream_t s, Profiler* prof) {
+    const ComposeArgs& a = e.a;
+    const size_t N = (size_t)1 << a.logN;
+    ScopedKernelTimer tm(prof, K_COMPOSE, 12.0 * (double)N, s);   // read f once, write two planes
+    const bool aligned = ((reinterpret_cast<uintptr_t>(a.f) | reinterpret_cast<uintptr_t>(a.inv_xm1) | reinterpret_cast<uintptr_t>(a.cp)) & 15u) == 0;
+    if (a.logN >= 4 && aligned) hipLaunchKernelGGL(compose_ext_kernel4, dim3((uint32_t)((N / 4 + 255) / 256)), dim3(256), 0, s, e);
+    else hipLaunchKernelGGL(compose_ext_kernel, dim3((uint32_t)((N + 255) / 256)), dim3(256), 0, s, e);
+    return hipGetLastError();
+}
+
 // cp of a proof-major batch, stored only (the batched prover with coset leaves: the tree over cp then has group 0's cosets as
 // leaves, which the fused one-value leaf source cannot hash): value b * N + i = cp_b[i] with proof b's own trace constants and
 // challenges, the arithmetic of ComposeBatchSrc.
@@ -690,6 +777,86 @@ hipError_t launch_fri_fold_multi(const FoldMultiArgs& a, hipStream_t s, Profiler
     if (a.steps == 1) fold_multi_launch<1>(a, q, wide, s);
     else if (a.steps == 2) fold_multi_launch<2>(a, q, wide, s);
     else fold_multi_launch<3>(a, q, wide, s);
+    return hipGetLastError();
+}
+
+// ---- the same butterfly over E (FoldMultiExtArgs) -------------------------------------------------------------------
+// Values and challenge constants in E, the point in the base field: (u - w) is scaled by xinv^(2^k) (two multiplications), then taken
+// times the constant of E (four and two additions, ext_mul_const).  With a challenge (beta0, 0) every constant has c1 = 0 and each
+// plane is fold_multi_core of that plane.
+template <int STEPS>
+__device__ __forceinline__ Ext fold_multi_ext_core(const ExtConst (&c)[7], uint32_t scale_mont, Ext (&v)[1 << STEPS], uint32_t xinv) {
+    constexpr int S = 1 << STEPS;
+#pragma unroll
+    for (int k = 0; k < STEPS; ++k) {
+        const int cnt = S >> (k + 1);
+#pragma unroll
+        for (int t = 0; t < cnt; ++t) {
+            const Ext u = v[t], w = v[t + cnt];
+            v[t] = ext_add(ext_add(u, w), ext_mul_const(ext_scale(ext_sub(u, w), xinv), c[S - (S >> k) + t]));
+        }
+        if (k + 1 < STEPS) xinv = mont_mul(xinv, xinv);
+    }
+    return ext_scale(v[0], scale_mont);
+}
+
+template <int STEPS>
+__global__ __launch_bounds__(256) void fri_fold_multi_ext_kernel1(FoldMultiExtArgs a) {
+    constexpr int S = 1 << STEPS;
+    const size_t m = (size_t)1 << a.log_m, q = m >> STEPS;
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= q) return;
+    Ext v[S];
+#pragma unroll
+    for (int t = 0; t < S; ++t) v[t] = Ext{a.in[i + t * q], a.in[m + i + t * q]};
+    const Ext r = fold_multi_ext_core<STEPS>(a.c, a.scale_mont, v, pow_lookup(a.hinv, (uint32_t)(i << a.round)));
+    a.out[i] = r.c0;
+    a.out[q + i] = r.c1;
+}
+
+// four consecutive outputs per thread: S coalesced 16-byte loads and one 16-byte store per plane; x^-1 advances by h^(-2^r).  The
+// STEPS = 3 instance holds its sixteen loads in registers (81 VGPRs as built, no scratch: DESIGN.md 7j), so every instance takes four.
+template <int STEPS>
+__global__ __launch_bounds__(256) void fri_fold_multi_ext_kernel(FoldMultiExtArgs a) {
+    constexpr int S = 1 << STEPS;
+    const size_t m = (size_t)1 << a.log_m, q = m >> STEPS;
+    const size_t i = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+    if (i >= q) return;
+    uint4 l0[S], l1[S];
+#pragma unroll
+    for (int t = 0; t < S; ++t) {
+        l0[t] = reinterpret_cast<const uint4*>(a.in)[(i + t * q) >> 2];
+        l1[t] = reinterpret_cast<const uint4*>(a.in)[(m + i + t * q) >> 2];
+    }
+    uint32_t xinv = pow_lookup(a.hinv, (uint32_t)(i << a.round));
+    const uint32_t step = pow_lookup(a.hinv, 1u << a.round);
+    Ext r[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        Ext v[S];
+#pragma unroll
+        for (int t = 0; t < S; ++t)
+            v[t] = e == 0 ? Ext{l0[t].x, l1[t].x} : e == 1 ? Ext{l0[t].y, l1[t].y} : e == 2 ? Ext{l0[t].z, l1[t].z} : Ext{l0[t].w, l1[t].w};
+        r[e] = fold_multi_ext_core<STEPS>(a.c, a.scale_mont, v, xinv);
+        if (e < 3) xinv = mont_mul(xinv, step);
+    }
+    reinterpret_cast<uint4*>(a.out)[i >> 2] = make_uint4(r[0].c0, r[1].c0, r[2].c0, r[3].c0);
+    reinterpret_cast<uint4*>(a.out)[(q + i) >> 2] = make_uint4(r[0].c1, r[1].c1, r[2].c1, r[3].c1);
+}
+
+template <int STEPS>
+static void fold_multi_ext_launch(const FoldMultiExtArgs& a, size_t q, bool wide, hipStream_t s) {
+    if (wide) hipLaunchKernelGGL(fri_fold_multi_ext_kernel<STEPS>, dim3((uint32_t)((q / 4 + 255) / 256)), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(fri_fold_multi_ext_kernel1<STEPS>, dim3((uint32_t)((q + 255) / 256)), dim3(256), 0, s, a);
+}
+hipError_t launch_fri_fold_multi_ext(const FoldMultiExtArgs& a, hipStream_t s, Profiler* prof) {
+    if (a.steps < 1 || a.steps > 3 || a.log_m < a.steps) return hipErrorInvalidValue;
+    const size_t m = (size_t)1 << a.log_m, q = m >> a.steps;
+    ScopedKernelTimer tm(prof, K_FOLD, 8.0 * (double)(m + q), s);   // read two planes of m words, write two of m / S
+    const bool wide = q >= 4 && ((reinterpret_cast<uintptr_t>(a.in) | reinterpret_cast<uintptr_t>(a.out)) & 15u) == 0;
+    if (a.steps == 1) fold_multi_ext_launch<1>(a, q, wide, s);
+    else if (a.steps == 2) fold_multi_ext_launch<2>(a, q, wide, s);
+    else fold_multi_ext_launch<3>(a, q, wide, s);
     return hipGetLastError();
 }
 

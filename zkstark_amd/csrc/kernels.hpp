@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/zkstark_amd.h"   // zk_hash_kind: what every `int hash` below holds
+#include "ext.hpp"
 
 namespace zk {
 
@@ -190,6 +191,18 @@ struct ComposeArgs {
 };
 hipError_t launch_compose(const ComposeArgs& a, hipStream_t s, Profiler* prof = nullptr);
 
+// cp over E (ext.hpp): the alphas are elements of E, the quotients stay in the base field, so component j of cp is the
+// base composition with (alpha0.cj, alpha1.cj, alpha2.cj).  `a` carries component 0 exactly as launch_compose takes it; the fields
+// here are component 1.  a.cp is 2 N words: plane 0 at [0, N), plane 1 at [N, 2 N).  One pass: f, the tables and the three quotient
+// terms are taken once per value.
+struct ComposeExtArgs {
+    ComposeArgs a;
+    uint32_t alpha0_mont1;    // alpha0.c1
+    uint32_t alpha1g2_mont1;  // alpha1.c1 * g^2
+    uint32_t zz1[32];         // B entries: alpha2.c1 / (x^n - 1) * R^2
+};
+hipError_t launch_compose_ext(const ComposeExtArgs& a, hipStream_t s, Profiler* prof = nullptr);
+
 // cp over ONE RANK'S BLOCK of a sharded proof, computed from the block of f this rank received for the commitment of f
 // (DESIGN.md section 6): position t < 2^log_m of the block is x = w h^(e0 + t); f at t, t + B, t + 2B is read through the
 // all-to-all order of the receive buffer (leaf t of chunk c = t >> (lg + log_cnt): piece (t mod G) of that chunk, word
@@ -232,6 +245,18 @@ struct FoldMultiArgs {
     uint32_t c_mont[7];
 };
 hipError_t launch_fri_fold_multi(const FoldMultiArgs& a, hipStream_t s, Profiler* prof = nullptr);
+// The same butterfly over E (ext.hpp): values and challenge in E, the points in the base field.  in = two planes of m
+// words (component 0 at [0, m), component 1 at [m, 2 m)), out = two planes of m / S words.  c[j] is FoldMultiArgs::c_mont[j] with
+// beta^(2^k) taken in E, as a constant of E.
+struct FoldMultiExtArgs {
+    const uint32_t* in;   // 2 m words
+    uint32_t* out;        // 2 m / S words
+    uint32_t log_m, round, steps;
+    PowTable hinv;        // h^-1 table, order 2^L
+    uint32_t scale_mont;  // 2^-steps
+    ExtConst c[7];
+};
+hipError_t launch_fri_fold_multi_ext(const FoldMultiExtArgs& a, hipStream_t s, Profiler* prof = nullptr);
 // The same for a proof-major batch: a.in = [batch][m], a.out = [batch][m / S], proof b folds with its own challenge
 // beta_raw[b * beta_stride] (a raw u32, reduced mod P on the device).  a.c_mont holds only the root-of-unity part of each constant;
 // a one-lane-per-proof launch ahead of the fold writes cb[8 b + j] = beta_b^(2^k) * a.c_mont[j] (Montgomery form), which the fold

@@ -9,10 +9,12 @@
 #include <stdint.h>
 #include <string.h>
 
+#include <type_traits>
 #include <vector>
 
 #include "../../include/zkstark_amd.h"
 #include "blake2s.hpp"
+#include "ext.hpp"
 #include "field.hpp"
 #include "fieldhash.hpp"
 #include "sha256.hpp"
@@ -48,9 +50,10 @@ struct Channel {
     // t, digest(i, out) writes digest i of the s * plen (path t starts at t * plen) as 32 bytes.
     // coset (coset leaves, below): the s values are the slots of ONE leaf, in slot order, and ONE path of plen digests follows them.
     static size_t group_bytes(size_t s, size_t plen, bool coset) { return 4 * s + (coset ? 1 : s) * (8 + 32 * plen); }
-    template <class Val, class Dig> void commit_group(uint8_t* buf, size_t s, size_t plen, Val val, Dig digest, bool coset) {
+    // words: value words per opening (2 for values of E, "ext" below: val(t), t < s * words, in wire order); buf: that many bytes more
+    template <class Val, class Dig> void commit_group(uint8_t* buf, size_t s, size_t plen, Val val, Dig digest, bool coset, uint32_t words = 1) {
         uint8_t* p = buf;
-        for (size_t t = 0; t < s; ++t, p += 4) {
+        for (size_t t = 0; t < s * words; ++t, p += 4) {
             const uint32_t v = val(t);
             for (int i = 0; i < 4; ++i) p[i] = (uint8_t)(v >> (8 * i));
         }
@@ -139,6 +142,16 @@ constexpr uint32_t kMaxSharedLog = 8;
 // of M / 8 compressions).  No BLAKE2s: no prover makes such a proof.  verify_proof: -2 as ever (f_p(x) is value p of row x); -3 covers the
 // three row path lengths (and cp's); -4 / -5 / -6 the path of row x / x + B / x + 2B against cap entry leaf >> (L - ce_f).  The length is a
 // single proof's plus 12 (M - 1) (1 + q): the further alphas and 4 (M - 1) more value bytes in each of the 3 q row tuples.
+// ext = 1, challenges in the quadratic extension E = F_P[u] / (u^2 - 5) (ext.hpp; 0 = the format above, byte for byte; needs lb = 0).
+// The trace and f stay in the base field; the alphas, cp, every beta and every FRI layer are in E.  A challenge is two get_u32 draws in a row,
+// c0 then c1: the alphas are alpha0.c0, alpha0.c1, alpha1.c0, .. (24 bytes), a group's beta 8 bytes.  cp = alpha0 p0 + alpha1 p1 + alpha2 p2 with
+// the base-field quotients, so component j of cp is the base composition with the component-j alphas; a group folds with beta, beta^2, beta^4
+// squared in E, the points in the base field.  The leaf over the slots u < S of a layer with id >= 1 holds 2 S words, the S component-0 words in
+// slot order, then the S component-1 words, hashed as a row of 2 S values (host_coset_leaf_hash; no BLAKE2s); the never-opened last tree has
+// leaves of 2 words.  On the wire every cp or group tuple sends, where it sent s value words, 2 s: the s component-0 words, then the s
+// component-1 words; counts and paths as ever, the three f tuples unchanged.  kFinal: c0 then c1 of the free term (8 bytes), or the 2^stop
+// component-0 coefficients, then the 2^stop component-1 coefficients.  verify_proof_ext keeps verify_proof's check numbers one for one; a
+// comparison of values of E fails when either component differs.  verify_transcript counts 6 + 2G + q challenges.  Another length: -1.
 inline uint32_t cap_eff(uint32_t cap, uint32_t lg) { return cap < lg - 1 ? cap : lg - 1; }   // lg >= 1 for every committed tree
 
 // One proof format: the settings above and everything that follows from them.  The Merkle hash and public_last are not part of it.
@@ -150,11 +163,12 @@ struct ProofFormat {
     uint32_t stop = 0, cap = 0;
     uint32_t lb = 0;                                                         // shared proof of 2^lb statements (0: a plain proof)
     bool rows = false;                                                       // ... whose f values are committed as row leaves (needs lb >= 1)
+    uint32_t ext = 0;                                                        // challenges, cp and the FRI layers in the extension of degree 2^ext (0 or 1)
 
     // what verify_proof and verify_transcript take (they answer -1 to anything else); every member below assumes it
     bool ok() const {
         return log_n >= 2 && log_b >= 1 && log_n + log_b <= 30 && q >= 1 && q <= 64 && grind <= kMaxGrindBits && fold >= 1 && fold <= kMaxFoldLog &&
-               stop_ok(log_n, log_b, stop) && cap <= kMaxCapLog && lb <= kMaxSharedLog && (!rows || lb >= 1);
+               stop_ok(log_n, log_b, stop) && cap <= kMaxCapLog && lb <= kMaxSharedLog && (!rows || lb >= 1) && ext <= 1 && (!ext || lb == 0);
     }
     // ---- geometry.  Group j < G folds the rounds round0(j) .. round0(j) + steps(j) - 1; tree j is the one over its INPUT layer.
     // j = G: the last layer (round0 = rounds, steps = 0), whose tree has one-value leaves and exists only when stop = 0.
@@ -178,23 +192,29 @@ struct ProofFormat {
     enum Head { kFTree, kAlphas, kTree, kBeta, kFinal, kNonce, kRaws };
     template <class Fn> bool for_each_head(Fn fn) const {
         const uint32_t G = groups();
-        if (!fn(kFTree, 0u, (size_t)32 << ((rows ? 0 : lb) + f_cap())) || !fn(kAlphas, 0u, (size_t)12 << lb) || !fn(kTree, 0u, (size_t)32 << tree_cap(0))) return false;
+        if (!fn(kFTree, 0u, (size_t)32 << ((rows ? 0 : lb) + f_cap())) || !fn(kAlphas, 0u, (size_t)12 << (lb + ext)) || !fn(kTree, 0u, (size_t)32 << tree_cap(0))) return false;
         for (uint32_t j = 0; j < G; ++j) {
-            if (!fn(kBeta, j, (size_t)4)) return false;                      // group j's challenge, then the tree over its output
+            if (!fn(kBeta, j, (size_t)4 << ext)) return false;                     // group j's challenge, then the tree over its output
             if ((j + 1 < G || last_tree()) && !fn(kTree, j + 1, (size_t)32 << tree_cap(j + 1))) return false;
         }
-        if (!fn(kFinal, 0u, stop ? (size_t)4 << stop : (size_t)4)) return false;   // the free term, or the 2^stop coefficients
+        if (!fn(kFinal, 0u, (size_t)4 << (stop + ext))) return false;           // the free term, or the 2^stop coefficients (ext: per component)
         if (grind && !fn(kNonce, 0u, (size_t)8)) return false;
         return fn(kRaws, 0u, (size_t)4 * q);
     }
     // ---- the tuples of one query in wire order: fn(s values, digests per path, one_leaf) as Channel::commit_group takes them.
     // f(x), f(gx), f(g^2 x) of every statement (rows: the three rows of 2^lb values, one leaf each) and, with one-value leaves, cp(x);
-    // then one tuple per group.
+    // then one tuple per group.  A walker that knows of ext takes a fourth argument, the words per value of the tuple (1 for the f tuples,
+    // 2^ext for cp and the groups: tuple_bytes); the provers and the GPU verifier, which have no such setting, take three.
+    template <class Fn> static void tuple(Fn& fn, size_t s, size_t plen, bool one_leaf, uint32_t words) {
+        if constexpr (std::is_invocable_v<Fn&, size_t, size_t, bool, uint32_t>) fn(s, plen, one_leaf, words);
+        else fn(s, plen, one_leaf);
+    }
+    static size_t tuple_bytes(size_t s, size_t plen, bool one_leaf, uint32_t words) { return Channel::group_bytes(s, plen, one_leaf) + 4 * s * (words - 1); }
     template <class Fn> void for_each_tuple(Fn fn) const {
-        if (rows) for (int k = 0; k < 3; ++k) fn((size_t)1 << lb, f_path(), true);
-        else for (size_t i = 0; i < ((size_t)3 << lb); ++i) fn((size_t)1, f_path(), false);
-        if (!coset) fn((size_t)1, tree_path(0), false);
-        for (uint32_t j = 0, G = groups(); j < G; ++j) fn((size_t)1 << steps(j), tree_path(j), coset);
+        if (rows) for (int k = 0; k < 3; ++k) tuple(fn, (size_t)1 << lb, f_path(), true, 1u);
+        else for (size_t i = 0; i < ((size_t)3 << lb); ++i) tuple(fn, (size_t)1, f_path(), false, 1u);
+        if (!coset) tuple(fn, (size_t)1, tree_path(0), false, 1u << ext);
+        for (uint32_t j = 0, G = groups(); j < G; ++j) tuple(fn, (size_t)1 << steps(j), tree_path(j), coset, 1u << ext);
     }
     // ---- the openings of one query in the same order, for x = query raw % (N - 2B): f at x, x + B, x + 2B (layer 0) and cp at x
     // (layer 1) (prover.rs:266-277), then per group the s coset leaves of its input layer.  An opening is one LEAF and its path:
@@ -220,7 +240,7 @@ struct ProofFormat {
     size_t data_len() const {
         size_t head = 0, per_query = 0;
         for_each_head([&](Head, uint32_t, size_t bytes) { head += bytes; return true; });
-        for_each_tuple([&](size_t s, size_t plen, bool one_leaf) { per_query += Channel::group_bytes(s, plen, one_leaf); });
+        for_each_tuple([&](size_t s, size_t plen, bool one_leaf, uint32_t words) { per_query += tuple_bytes(s, plen, one_leaf, words); });
         return head + (size_t)q * per_query;
     }
 };
@@ -322,8 +342,10 @@ inline void compute_root_from_path(uint32_t element, size_t index, const uint8_t
 // lb > 0 (the shared proof, above): public_last holds 2^lb values; the f tuples are 3 per statement, fv[3 p + k], and the cp value is
 // fv[3 M].  lb = 0: one statement, fv[0..3] as ever.
 // rows (row leaves, above): three f tuples of M values each, row k at fv[k M ..]; f_p at x + k B is fv[k M + p].  BLAKE2s: -1.
+inline int verify_proof_ext(const uint8_t* data, size_t len, const ProofFormat& fmt, uint32_t public_last, int hash);
 inline int verify_proof(const uint8_t* data, size_t len, const ProofFormat& fmt, const uint32_t* public_last, int hash) {
     if (!fmt.ok() || (fmt.rows && hash == ZK_HASH_BLAKE2S)) return -1;
+    if (fmt.ext) return verify_proof_ext(data, len, fmt, public_last[0], hash);   // ext = 0 is the code below, untouched
     if ((fmt.stop || fmt.cap || fmt.lb) && len != fmt.data_len()) return -1;   // a stopped, capped or shared proof of another length: -1, strict or not
     const bool coset = fmt.coset;
     const size_t M = (size_t)1 << fmt.lb;
@@ -478,6 +500,149 @@ inline int verify_proof(const uint8_t* data, size_t len, const ProofFormat& fmt,
     return fmt.lb ? -1 : verify_proof(data, len, fmt, &public_last, hash);   // one statement
 }
 
+// verify_proof for ext = 1 (the format above, "ext"): one statement, the same walk and the same check numbers, values of cp and of the FRI
+// layers in E.  Words are reduced % P before arithmetic and compared unreduced, as there; two values of E differ when either component does.
+inline int verify_proof_ext(const uint8_t* data, size_t len, const ProofFormat& fmt, uint32_t public_last, int hash) {
+    if (!fmt.ok() || fmt.ext != 1 || hash == ZK_HASH_BLAKE2S || len != fmt.data_len()) return -1;
+    const bool coset = fmt.coset;
+    const size_t n = (size_t)1 << fmt.log_n, B = (size_t)1 << fmt.log_b, N = n << fmt.log_b;
+    const uint32_t L = fmt.L(), G = fmt.groups();
+    const uint8_t* p = data;
+    size_t left = len;
+    bool bad = false;
+    auto take = [&](size_t k) -> const uint8_t* {
+        if (left < k) { bad = true; return nullptr; }
+        const uint8_t* r = p; p += k; left -= k; return r;
+    };
+    auto le32 = [](const uint8_t* r) { return (uint32_t)r[0] | ((uint32_t)r[1] << 8) | ((uint32_t)r[2] << 16) | ((uint32_t)r[3] << 24); };
+    auto take32 = [&]() -> uint32_t { const uint8_t* r = take(4); return r ? le32(r) : 0; };
+    auto take_path = [&](size_t& plen) -> const uint8_t* {
+        const uint8_t* r = take(8);
+        if (!r) return nullptr;
+        uint64_t c = 0;
+        for (int i = 0; i < 8; ++i) c |= (uint64_t)r[i] << (8 * i);
+        if (c > 64) { bad = true; return nullptr; }
+        plen = (size_t)c;
+        return take(32 * plen);
+    };
+    const uint8_t *f_root = nullptr, *alphas = nullptr, *final_term = nullptr, *raws = nullptr, *roots[41] = {nullptr}, *betas[40];
+    fmt.for_each_head([&](ProofFormat::Head what, uint32_t j, size_t bytes) {
+        const uint8_t* r = take(bytes);
+        switch (what) {
+            case ProofFormat::kFTree: f_root = r; break;
+            case ProofFormat::kAlphas: alphas = r; break;      // alpha0.c0, alpha0.c1, alpha1.c0, ..
+            case ProofFormat::kTree: roots[j] = r; break;
+            case ProofFormat::kBeta: betas[j] = r; break;      // c0, c1
+            case ProofFormat::kFinal: final_term = r; break;   // c0, c1 of the free term, or the coefficients plane by plane
+            case ProofFormat::kNonce: break;
+            case ProofFormat::kRaws: raws = r; break;
+        }
+        return true;
+    });
+    if (bad) return -1;
+    const uint32_t g = root_of_unity(fmt.log_n), h = root_of_unity(L);
+    for (uint32_t qk = 0; qk < fmt.q; ++qk) {
+        uint32_t fv[3], cpw[2] = {0, 0}; const uint8_t* fp[4]; size_t fpl[4] = {0, 0, 0, 0};
+        uint32_t lw[40][16]; const uint8_t* lp[40][8]; size_t lpl[40][8];   // group j's words as sent: s component-0 words, then s component-1 words
+        uint32_t i = 0;
+        const uint32_t nf = coset ? 3 : 4;
+        fmt.for_each_tuple([&](size_t s, size_t, bool one_leaf, uint32_t words) {
+            uint32_t* v = i < 3 ? &fv[i] : i < nf ? cpw : lw[i - nf];
+            const uint8_t** path = i < nf ? &fp[i] : lp[i - nf];
+            size_t* plen = i < nf ? &fpl[i] : lpl[i - nf];
+            for (size_t t = 0; t < s * words; ++t) v[t] = take32();
+            for (size_t t = 0; t < (one_leaf ? 1 : s); ++t) { plen[t] = 0; path[t] = take_path(plen[t]); }
+            ++i;
+        });
+        if (bad) return -1;
+        const size_t tp = (size_t)le32(raws + 4 * qk) % (N - 2 * B);
+        // value t of group j, unreduced: as sent, or slot (rot + t) % s of the group's leaf
+        auto group_val = [&](uint32_t j, uint32_t t) -> Ext {
+            const uint32_t steps = fmt.steps(j), s = 1u << steps;
+            if (!coset) return Ext{lw[j][t], lw[j][s + t]};
+            const uint32_t lg = L - fmt.round0(j);
+            const size_t rot = (tp & (((size_t)1 << lg) - 1)) >> (lg - steps);
+            const uint32_t u = (uint32_t)(rot + t) & (s - 1u);
+            return Ext{lw[j][u], lw[j][s + u]};
+        };
+        if (coset) { const Ext c = group_val(0, 0); cpw[0] = c.c0; cpw[1] = c.c1; }
+        const uint32_t x = mulmod(GEN_W, powmod(h, tp));
+        {   // proof.rs:63-77 with the alphas in E: component j of cp takes the component-j alphas
+            const uint32_t gm1 = invmod(g), gm2 = mulmod(gm1, gm1), gm3 = mulmod(gm2, gm1);
+            const uint32_t i0 = invmod(sub(x, 1)), i1 = invmod(sub(x, gm2));
+            const uint32_t den = mulmod(sub(powmod(x, n), 1), invmod(mulmod(mulmod(sub(x, gm3), sub(x, gm2)), sub(x, gm1))));
+            const uint32_t i2 = invmod(den);
+            const uint32_t f_x = fv[0] % P, f_gx = fv[1] % P, f_ggx = fv[2] % P;
+            const uint32_t p0 = mulmod(sub(f_x, 1), i0), p1 = mulmod(sub(f_x, public_last % P), i1);
+            const uint32_t p2 = mulmod(sub(sub(f_ggx, mulmod(f_gx, f_gx)), mulmod(f_x, f_x)), i2);
+            for (uint32_t c = 0; c < 2; ++c) {
+                const uint8_t* al = alphas + 4 * c;
+                const uint32_t cp0 = add(add(mulmod(le32(al) % P, p0), mulmod(le32(al + 8) % P, p1)), mulmod(le32(al + 16) % P, p2));
+                if (cp0 != cpw[c]) return -2;
+            }
+        }
+        uint8_t root[32];
+        auto misses = [&](const uint32_t* words, size_t count, size_t idx, const uint8_t* path, size_t plen, const uint8_t* entries) -> bool {
+            compute_root_from_coset(words, count, idx & (((size_t)1 << plen) - 1), path, plen, root, hash);
+            return memcmp(root, entries + 32 * (idx >> plen), 32) != 0;
+        };
+        for (uint32_t k = 0; k < 3; ++k) if (fpl[k] != fmt.f_path()) return -3;
+        if (!coset && fpl[3] != fmt.tree_path(0)) return -3;
+        if (misses(&fv[0], 1, tp, fp[0], fpl[0], f_root)) return -4;
+        if (misses(&fv[1], 1, tp + B, fp[1], fpl[1], f_root)) return -5;
+        if (misses(&fv[2], 1, tp + 2 * B, fp[2], fpl[2], f_root)) return -6;
+        if (!coset && misses(cpw, 2, tp, fp[3], fpl[3], roots[0])) return -7;      // the leaf of one value of E: its two words
+        const uint32_t inv2 = invmod(2);
+        for (uint32_t j = 0; j < G; ++j) {
+            const uint32_t r0 = fmt.round0(j), steps = fmt.steps(j);
+            uint32_t cnt = 1u << steps;
+            Ext v[8];
+            for (uint32_t t = 0; t < cnt; ++t) { const Ext w = group_val(j, t); v[t] = ext_reduce(w.c0, w.c1); }
+            uint32_t xk = powmod(x, (uint64_t)1 << r0);
+            uint32_t om = powmod(h, (uint64_t)N >> steps);
+            Ext bk = ext_reduce(le32(betas[j]), le32(betas[j] + 4));
+            for (uint32_t k = 0; k < steps; ++k) {
+                cnt >>= 1;
+                uint32_t pt = xk;
+                for (uint32_t t = 0; t < cnt; ++t) {
+                    const uint32_t i2x = invmod(mulmod(pt, 2));
+                    const Ext sum = ext_add(v[t], v[t + cnt]), dif = ext_sub(v[t], v[t + cnt]);
+                    const Ext gx{mulmod(sum.c0, inv2), mulmod(sum.c1, inv2)}, hx{mulmod(dif.c0, i2x), mulmod(dif.c1, i2x)};
+                    v[t] = ext_add(gx, ext_mul(bk, hx));
+                    pt = mulmod(pt, om);
+                }
+                xk = mulmod(xk, xk); om = mulmod(om, om); bk = ext_mul(bk, bk);
+            }
+            Ext expect;
+            if (j + 1 < G) expect = group_val(j + 1, 0);
+            else if (!fmt.stop) expect = Ext{le32(final_term), le32(final_term + 4)};
+            else {                                                               // Horner over the coefficients of E at the base-field point x^(2^R')
+                const uint32_t xs = powmod(x, (uint64_t)1 << fmt.rounds());
+                const size_t nc = (size_t)1 << fmt.stop;
+                expect = Ext{0u, 0u};
+                for (size_t k = nc; k-- > 0; )
+                    expect = Ext{add(mulmod(expect.c0, xs), le32(final_term + 4 * k) % P), add(mulmod(expect.c1, xs), le32(final_term + 4 * (nc + k)) % P)};
+            }
+            if (!ext_eq(v[0], expect)) return -(int)(100 + j);
+        }
+        for (uint32_t j = 0; j < G; ++j) {
+            const uint32_t lg = fmt.tree_log(j), steps = fmt.steps(j), s = 1u << steps;
+            if (coset) {
+                if (lpl[j][0] != fmt.tree_path(j)) return -(int)(200 + j);
+                if (misses(lw[j], 2 * s, tp & (((size_t)1 << lg) - 1), lp[j][0], lpl[j][0], roots[j])) return -(int)(300 + j);   // the leaf's own message
+                continue;
+            }
+            for (uint32_t t = 0; t < s; ++t) if (lpl[j][t] != fmt.tree_path(j)) return -(int)(200 + j);
+            for (uint32_t t = 0; t < s; ++t) {
+                const uint32_t pair[2] = {lw[j][t], lw[j][s + t]};
+                if (misses(pair, 2, coset_leaf(tp, lg, steps, t), lp[j][t], lpl[j][t], roots[j])) return t == 0 ? -(int)(300 + j) : -(int)(400 + j);
+            }
+        }
+    }
+    if (left != 0) return -8;
+    return 0;
+}
+
 // the reference verifier reads the challenges out of the proof
 // (proof.rs:22-37) and never checks Proof.state (proof.rs:6); the author flags this as unfinished
 // (readme.md:1).  This replays the Fiat-Shamir channel over the proof bytes in the prover's commit
@@ -517,7 +682,7 @@ inline int verify_transcript(const uint8_t* data, size_t len, const uint8_t stat
         return true;
     });
     if (rc) return rc;
-    for (uint32_t j = 0; j < fmt.q; ++j) fmt.for_each_tuple([&](size_t s, size_t plen, bool one_leaf) { commit(Channel::group_bytes(s, plen, one_leaf)); });
+    for (uint32_t j = 0; j < fmt.q; ++j) fmt.for_each_tuple([&](size_t s, size_t plen, bool one_leaf, uint32_t words) { commit(ProofFormat::tuple_bytes(s, plen, one_leaf, words)); });
     if (memcmp(ch.state, state, 32)) return -1999;
     return 0;
 }

@@ -124,6 +124,13 @@ struct zk_ctx {
     // its 2^stop coefficients (fri_final_poly_kernel -> d_final: one count word, then the coefficients) are committed instead
     uint32_t* d_final = nullptr;        // 1 + 2^kFinalPolyMaxLog words, allocated by the first call that needs it
     std::vector<uint32_t> final_poly;   // the last proof's coefficients (stop = 0: the free term)
+    // Challenges in E (transcript.hpp "ext").  With fmt.ext = 1 the layers with id >= 1 of a one-call proof are two planes each
+    // and lie behind the base layers in d_layers, from word ext_base on (zk_ctx_set_ext sizes d_layers and the gather buffers both ways);
+    // ext_chal: the component-1 raws of the last proof's challenges (three alphas, then one per group).  gather_floor: the gather
+    // capacity the context has with ext off.  busy: a proof or zk_ctx_set_ext holds the context.
+    size_t ext_base = 0, layer_words = 0, gather_floor = 0;
+    std::vector<uint32_t> ext_chal;
+    std::atomic<bool> busy{false};
     int hash = 0;                      // Merkle hash (zk_hash_kind): 0 = SHA-256 (reference), 1 = field-native (configs[4]), 2 = BLAKE2s-256
     // Merkle caps (transcript.hpp): a one-call proof commits the 2^ce digests of depth ce = min(cap, lg - 1) of
     // every tree and builds nothing above them.  cap_now: fmt.cap while a one-call proof runs, 0 otherwise (the stage-by-stage
@@ -164,6 +171,15 @@ uint32_t tree_log(const zk_ctx* c, uint32_t tree) { return layer_log(c, tree) - 
 size_t tree_leaves(const zk_ctx* c, uint32_t tree) { return (size_t)1 << tree_log(c, tree); }
 
 Profiler* prof_of(zk_ctx* c) { return c->prof.mask ? &c->prof : nullptr; }
+
+// Layer id >= 1 of an ext proof: two planes of layer_size words, component 0 first
+size_t ext_off(const zk_ctx* c, uint32_t id) { return c->ext_base + 2 * (c->layer_off[id] - c->layer_off[1]); }
+uint32_t* ext_layer(zk_ctx* c, uint32_t id) { return c->d_layers + ext_off(c, id); }
+struct BusyScope {
+    zk_ctx* c; bool mine;
+    explicit BusyScope(zk_ctx* ctx) : c(ctx), mine(!ctx->busy.exchange(true, std::memory_order_acquire)) {}
+    ~BusyScope() { if (mine) c->busy.store(false, std::memory_order_release); }
+};
 
 // Resolves pending event pairs into the per-class accumulators (synchronises on them).
 void collect_kernel_stats(zk_ctx* c) {
@@ -530,14 +546,16 @@ int check_interpolant(zk_ctx* c) {
 }
 // Degree of the polynomial whose evaluations are `layer` (1 = cp_0, 2 + r = FRI layer r + 1) is exactly want_deg:
 // prover.rs:148-159 + :169 for cp (every division exact <=> deg cp = n - 1), :228-251 for the FRI layers.
-int check_degree(zk_ctx* c, uint32_t layer, uint32_t want_deg, const char* cite) {
+// plane: one plane of an ext layer in place of the base layer (never on the host), held to the bound only: a value of E has the
+// degree when either of its planes does
+int check_degree(zk_ctx* c, uint32_t layer, uint32_t want_deg, const char* cite, const uint32_t* plane = nullptr) {
     const uint32_t lg = layer_log(c, layer);
     const size_t m = (size_t)1 << lg;
-    const uint32_t* src = c->d_layers + c->layer_off[layer];
+    const uint32_t* src = plane ? plane : c->d_layers + c->layer_off[layer];
     if (lg <= 10) {
         // small layer: values to the host (or already there), plain inverse DFT of the coset-evaluations' sequence
         std::vector<uint32_t> v(m);
-        if (c->tail_have && c->tail_log == lg && layer >= 2) v.assign(c->tail_vals.begin(), c->tail_vals.begin() + m);
+        if (!plane && c->tail_have && c->tail_log == lg && layer >= 2) v.assign(c->tail_vals.begin(), c->tail_vals.begin() + m);
         else {
             HIPCHK(hipMemcpyAsync(v.data(), src, m * 4, hipMemcpyDeviceToHost, c->stream));
             HIPCHK(hipStreamSynchronize(c->stream));
@@ -548,7 +566,7 @@ int check_degree(zk_ctx* c, uint32_t layer, uint32_t want_deg, const char* cite)
             for (size_t i = 0; i < m; ++i) { acc = add(acc, mulmod(v[i], x)); x = mulmod(x, step); }
             if (k > want_deg && acc != 0)
                 return fail(ZK_ERR_CHECK, "self-check %s failed: layer %u has a non-zero coefficient of degree %zu > %u", cite, layer, k, want_deg);
-            if (k == want_deg && acc == 0)
+            if (k == want_deg && acc == 0 && !plane)
                 return fail(ZK_ERR_CHECK, "self-check %s failed: layer %u has degree below %u", cite, layer, want_deg);
         }
         return ZK_OK;
@@ -563,7 +581,7 @@ int check_degree(zk_ctx* c, uint32_t layer, uint32_t want_deg, const char* cite)
     HIPCHK(hipMemcpyAsync(h, res, 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     if (h[0]) return fail(ZK_ERR_CHECK, "self-check %s failed: layer %u has %u non-zero coefficients of degree > %u (a division left a remainder)", cite, layer, h[0], want_deg);
-    if (!h[1]) return fail(ZK_ERR_CHECK, "self-check %s failed: layer %u has degree below %u", cite, layer, want_deg);
+    if (!h[1] && !plane) return fail(ZK_ERR_CHECK, "self-check %s failed: layer %u has degree below %u", cite, layer, want_deg);
     return ZK_OK;
 }
 
@@ -580,6 +598,9 @@ void open_begin(zk_ctx* c, size_t nvals) {
 void open_val(zk_ctx* c, uint32_t layer, size_t x) {
     if (c->host_vals[layer]) c->fetch_vals[c->open_vi++] = c->host_vals[layer] + x;
     else { c->fetch_vdev[c->open_vi++] = (uint32_t)c->open_nv; c->h_gather_off[c->open_nv++] = (uint64_t)c->layer_off[layer] + x; }
+}
+void open_word(zk_ctx* c, size_t off) {                                     // a word of d_layers that only the device holds
+    c->fetch_vdev[c->open_vi++] = (uint32_t)c->open_nv; c->h_gather_off[c->open_nv++] = (uint64_t)off;
 }
 void open_path(zk_ctx* c, uint32_t tree, size_t m, size_t leaf) {          // merkle.rs:54-71: the sibling at every depth below the cap
     const size_t stop_at = ((size_t)2 << c->tree_cap[tree]) - 2;            // the last node of the cap's depth (cap 0: the root)
@@ -646,6 +667,78 @@ int prove_fold_rounds(zk_ctx* c, Channel& ch) {
     return ZK_OK;
 }
 
+// ---- the one-call prover with challenges in E (transcript.hpp "ext") -----------------------------------------------------------
+// Tree over layer `id` of E with 2^steps slots per leaf: the row tree of the [2 * 2^steps][len >> steps] array the two planes are
+int do_merkle_ext(zk_ctx* c, uint32_t id, uint32_t steps) {
+    HIPCHK(launch_merkle_build_rows(ext_layer(c, id), layer_log(c, id) - steps, steps + 1, c->d_trees + c->tree_off[id], c->stream, prof_of(c),
+                                    mail_of(c, id, true, false, steps), c->hash));
+    return ZK_OK;
+}
+int check_degree_ext(zk_ctx* c, uint32_t id, uint32_t want_deg, const char* cite) {
+    int rc = check_degree(c, id, want_deg, cite, ext_layer(c, id));
+    return rc ? rc : check_degree(c, id, want_deg, cite, ext_layer(c, id) + layer_size(c, id));
+}
+// cp and the groups of a proof over E, from the alphas to the last root: every K and leaf format takes the grouped loop
+int prove_ext_rounds(zk_ctx* c, Channel& ch) {
+    const ProofFormat& f = c->fmt;
+    const uint32_t R = f.rounds(), G = f.groups();
+    uint8_t root[32];
+    int rc;
+    uint32_t alpha[6];
+    c->ext_chal.clear();
+    for (int i = 0; i < 6; ++i) {                             // alpha0.c0, alpha0.c1, alpha1.c0, ..
+        alpha[i] = ch.get_u32();
+        if (i & 1) c->ext_chal.push_back(alpha[i]); else c->info.alpha_raw[i / 2] = alpha[i];
+    }
+    if ((rc = dom_compose_ext(c->dom, c->d_layers + c->layer_off[0], ext_layer(c, 1), c->first, c->last, alpha, c->stream, prof_of(c)))) return rc;
+    if ((rc = do_merkle_ext(c, 1, f.slots_log(0))) || (rc = read_commit(c, 1, root))) return rc;
+    if (c->checks && (rc = check_degree_ext(c, 1, (uint32_t)c->n - 1, "prover.rs:148-159/:169 (exact divisions, deg cp = n - 1)"))) return rc;
+    commit_tree(c, ch, 1, root);
+    for (uint32_t j = 0; j < G; ++j) {
+        const uint32_t r0 = f.round0(j), steps = f.steps(j), id = f.tree_id(j + 1);
+        const uint32_t beta[2] = {ch.get_u32(), ch.get_u32()};
+        c->info.beta_raw[r0] = beta[0];
+        c->ext_chal.push_back(beta[1]);
+        if ((rc = dom_fold_multi_ext(c->dom, ext_layer(c, 1 + r0), ext_layer(c, id), c->L - r0, r0, steps, beta, c->stream, prof_of(c)))) return rc;
+        const bool stopped = f.stop && j + 1 == G;
+        if (!stopped && ((rc = do_merkle_ext(c, id, f.slots_log(j + 1))) || (rc = read_commit(c, id, root)))) return rc;
+        const size_t deg = c->n >> (r0 + steps);
+        if (c->checks && (rc = check_degree_ext(c, id, (uint32_t)deg - (deg ? 1 : 0), "prover.rs:228-251 (FRI layer degree)"))) return rc;
+        if (!stopped) commit_tree(c, ch, id, root);
+        for (uint32_t l = 2 + r0; l < id; ++l) c->skipped_trees |= (uint64_t)1 << l;
+    }
+    if (f.stop) for (uint32_t l = 1 + R; l <= c->R + 1; ++l) c->skipped_trees |= (uint64_t)1 << l;
+    for (uint32_t l = 1; l <= c->R + 1; ++l) c->skipped_layers |= (uint64_t)1 << l;   // the base-field layers are not written: the planes are
+    return ZK_OK;
+}
+// kFinal of a proof over E into c->final_poly: (c0, c1) of the free term, or the 2^stop coefficients of plane 0, then of plane 1
+int ext_final_value(zk_ctx* c) {
+    const ProofFormat& f = c->fmt;
+    const uint32_t Rp = f.rounds();
+    if (!f.stop) {
+        HIPCHK(hipMemcpyAsync(c->h_small, ext_layer(c, 1 + c->R), 2 * c->B * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        for (size_t plane = 0; plane < 2; ++plane)
+            for (size_t i = 1; i < c->B; ++i)
+                if (c->h_small[plane * c->B + i] != c->h_small[plane * c->B])
+                    return fail(ZK_ERR_CHECK, "last FRI layer is not constant (prover.rs:238): trace does not satisfy the constraints");
+        c->final_poly = {c->h_small[0], c->h_small[c->B]};
+        return ZK_OK;
+    }
+    const size_t cnt = (size_t)1 << f.stop;
+    int rc = final_alloc(c);
+    if (rc) return rc;
+    if ((rc = dom_final_poly_batch(c->dom, ext_layer(c, 1 + Rp), c->d_final, c->L - Rp, Rp, (uint32_t)cnt, 2, c->stream, prof_of(c)))) return rc;
+    HIPCHK(hipMemcpyAsync(c->h_small, c->d_final, 2 * (cnt + 1) * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (c->h_small[0] || c->h_small[cnt + 1])
+        return fail(ZK_ERR_CHECK, "final FRI layer has degree >= 2^%u: trace does not satisfy the constraints (%u non-zero coefficients above; cf. prover.rs:238)", f.stop,
+                    c->h_small[0] + c->h_small[cnt + 1]);
+    c->final_poly.assign(c->h_small + 1, c->h_small + 1 + cnt);
+    c->final_poly.insert(c->final_poly.end(), c->h_small + cnt + 2, c->h_small + 2 * cnt + 2);
+    return ZK_OK;
+}
+
 // ZK_HOST_TIMING=1: the host time between named points of a proof, on stderr
 struct HostLaps {
     const bool on;
@@ -665,7 +758,15 @@ int prove_finish(zk_ctx* c, Channel& ch, HostLaps& lap) {
     const uint32_t Q = f.q;
     const size_t B = c->B, N = c->N;
     int rc;
-    if (c->fmt.stop) {                                        // the final polynomial's coefficients, one commit (transcript.hpp "stop")
+    if (f.ext) {                                              // c0 then c1 of the free term, or the coefficients plane by plane: one commit
+        if ((rc = ext_final_value(c))) return rc;
+        c->info.free_term = c->final_poly[0];
+        std::vector<uint8_t>& cb = c->commit_buf;
+        cb.resize(4 * c->final_poly.size());
+        for (size_t k = 0; k < c->final_poly.size(); ++k)
+            for (int i = 0; i < 4; ++i) cb[4 * k + i] = (uint8_t)(c->final_poly[k] >> (8 * i));
+        ch.commit_bytes(cb.data(), cb.size());
+    } else if (c->fmt.stop) {                                 // the final polynomial's coefficients, one commit (transcript.hpp "stop")
         if ((rc = final_poly_value(c))) return rc;
         c->info.free_term = c->final_poly[0];
         std::vector<uint8_t>& cb = c->commit_buf;
@@ -698,11 +799,14 @@ int prove_finish(zk_ctx* c, Channel& ch, HostLaps& lap) {
     // mailbox flag behind them: no copy commands, no stream synchronisation.  The scatter that completes the device
     // arrays with the host-built parts is enqueued behind it, off the proof's critical path.
     size_t per_query = 0;
-    f.for_each_tuple([&](size_t s, size_t, bool) { per_query += s; });
+    f.for_each_tuple([&](size_t s, size_t, bool, uint32_t words) { per_query += s * words; });
     open_begin(c, (size_t)Q * per_query);
     for (uint32_t k = 0; k < Q; ++k)
         f.for_each_opening((size_t)qraws[k] % (N - 2 * B), [&](uint32_t layer, uint32_t log_leaves, size_t leaf, uint32_t slots_log) {
-            for (size_t u = 0; u < ((size_t)1 << slots_log); ++u) open_val(c, layer, leaf + (u << log_leaves));
+            if (f.ext && layer >= 1) {                        // a leaf of E: its component-0 slots, then its component-1 slots
+                for (size_t plane = 0; plane < 2; ++plane)
+                    for (size_t u = 0; u < ((size_t)1 << slots_log); ++u) open_word(c, ext_off(c, layer) + plane * layer_size(c, layer) + leaf + (u << log_leaves));
+            } else for (size_t u = 0; u < ((size_t)1 << slots_log); ++u) open_val(c, layer, leaf + (u << log_leaves));
             open_path(c, layer, (size_t)1 << log_leaves, leaf);
         });
     if ((rc = open_launch(c))) return rc;
@@ -713,11 +817,12 @@ int prove_finish(zk_ctx* c, Channel& ch, HostLaps& lap) {
     const uint32_t* const* vsrc = c->fetch_vals.data();
     const uint32_t* const* dsrc = c->fetch_nodes.data();
     std::vector<uint8_t>& buf = c->commit_buf;            // reused from proof to proof; the first group's tuple is the largest
-    buf.resize(Channel::group_bytes((size_t)1 << f.steps(0), f.L(), false));
-    auto tuple = [&](size_t s, size_t plen, bool one_leaf) {
-        ch.commit_group(buf.data(), s, plen, [&](size_t t) { return *vsrc[t]; },
-                        [&](size_t i, uint8_t* out) { digest_words_to_bytes(dsrc[i], out); }, one_leaf);
-        vsrc += s; dsrc += (one_leaf ? 1 : s) * plen;
+    buf.resize(ProofFormat::tuple_bytes((size_t)1 << f.steps(0), f.L(), false, 1u << f.ext));
+    // the values were fetched opening by opening (for a value of E: c0, c1); a tuple of s openings sends the s c0 words, then the s c1 words
+    auto tuple = [&](size_t s, size_t plen, bool one_leaf, uint32_t words) {
+        ch.commit_group(buf.data(), s, plen, [&](size_t t) { return *vsrc[words == 2 && !one_leaf ? (t % s) * 2 + t / s : t]; },
+                        [&](size_t i, uint8_t* out) { digest_words_to_bytes(dsrc[i], out); }, one_leaf, words);
+        vsrc += s * words; dsrc += (one_leaf ? 1 : s) * plen;
     };
     for (uint32_t q = 0; q < Q; ++q) f.for_each_tuple(tuple);   // (u32, AuthPath): prover.rs:274-277, then per group: prover.rs:280-289
     lap("decommit host hashing");
@@ -731,6 +836,8 @@ int prove_finish(zk_ctx* c, Channel& ch, HostLaps& lap) {
 // one-value leaf source cannot hash) and every K takes prove_fold_rounds.  Early stop: every K takes prove_fold_rounds too.
 int prove_resident(zk_ctx* c, Channel& ch) {
     if (!c->have_trace) return fail(ZK_ERR_STATE, "zk_prove_resident: no trace uploaded");
+    BusyScope busy(c);
+    if (!busy.mine) return fail(ZK_ERR_STATE, "zk_prove_resident: the context is held by another proof or by zk_ctx_set_ext");
     static const bool timing = getenv("ZK_HOST_TIMING") != nullptr;
     HostLaps lap{timing};
     const uint32_t R = c->R;
@@ -740,6 +847,7 @@ int prove_resident(zk_ctx* c, Channel& ch) {
     uint8_t root[32];
     int rc;
     memset(&c->info, 0, sizeof c->info);
+    c->ext_chal.clear();
     c->info.public_last = c->last;
     c->pending_top = false;                               // a pending stand-alone tree top: every tree is rebuilt below
     begin_proof(c);
@@ -749,6 +857,11 @@ int prove_resident(zk_ctx* c, Channel& ch) {
     if ((rc = do_merkle(c, 0, true))) return rc;          // prover.rs:81
     if ((rc = read_commit(c, 0, root))) return rc;
     commit_tree(c, ch, 0, root);                          // prover.rs:85
+    if (c->fmt.ext) {
+        if ((rc = prove_ext_rounds(c, ch))) return rc;
+        lap("lde .. last root");
+        return prove_finish(c, ch, lap);
+    }
     uint32_t alpha[3];
     for (int i = 0; i < 3; ++i) alpha[i] = c->info.alpha_raw[i] = ch.get_u32();   // prover.rs:163-165
     if (c->fmt.coset) {                                       // prover.rs:166-176, then the tree with group 0's cosets as leaves
@@ -859,6 +972,27 @@ uint32_t zk_field_rem(uint32_t a, uint32_t rhs) {
     if (rhs == 0) { fail(ZK_ERR_INVALID, "zk_field_rem: remainder by zero (field.rs:89-94 panics)"); return 0; }
     return (a % P) % rhs;
 }
+// E = GF(P)[u] / (u^2 - 5) (ext.hpp): (c0, c1) pairs, any u32 in (reduced mod P as zk_field_* reduce), canonical out; out may alias an input
+int zk_ext_mul(const uint32_t a[2], const uint32_t b[2], uint32_t out[2]) {
+    if (!a || !b || !out) return fail(ZK_ERR_INVALID, "zk_ext_mul: null argument");
+    const Ext r = ext_mul(ext_reduce(a[0], a[1]), ext_reduce(b[0], b[1]));
+    out[0] = r.c0; out[1] = r.c1;
+    return ZK_OK;
+}
+int zk_ext_inv(const uint32_t a[2], uint32_t out[2]) {
+    if (!a || !out) return fail(ZK_ERR_INVALID, "zk_ext_inv: null argument");
+    const Ext v = ext_reduce(a[0], a[1]);
+    if (ext_is_zero(v)) return fail(ZK_ERR_INVALID, "zk_ext_inv: zero has no inverse");
+    const Ext r = ext_inv(v);
+    out[0] = r.c0; out[1] = r.c1;
+    return ZK_OK;
+}
+int zk_ext_pow(const uint32_t a[2], uint64_t e, uint32_t out[2]) {
+    if (!a || !out) return fail(ZK_ERR_INVALID, "zk_ext_pow: null argument");
+    const Ext r = ext_pow(ext_reduce(a[0], a[1]), e);
+    out[0] = r.c0; out[1] = r.c1;
+    return ZK_OK;
+}
 // field.rs:52-86 Gf::generator(): the first x >= 2 with x^((P-1)/q) != 1 for every prime factor q of P - 1.  Searched as the
 // reference searches it (unique prime factors by trial division, then candidates in order), once; the kernels use the
 // constant GEN_W, which this search must -- and does -- return (5; pinned by tests/test_cabi.py).
@@ -945,7 +1079,7 @@ static int ctx_make(int device, uint32_t log_n, uint32_t log_b, uint32_t shift, 
         c->layer_len.push_back(layer_size(c, l));
         off += layer_size(c, l);
     }
-    size_t layer_words = off;
+    const size_t layer_words = c->layer_words = off;
     off = 0;
     for (uint32_t l = 0; l <= c->R + 1; ++l) {
         c->tree_off.push_back(off);
@@ -956,7 +1090,7 @@ static int ctx_make(int device, uint32_t log_n, uint32_t log_b, uint32_t shift, 
     if ((rc = dmalloc(c, &c->d_coef, 2 * c->n * 4))) return bail(rc);
     if ((rc = dmalloc(c, &c->d_layers, layer_words * 4))) return bail(rc);
     if ((rc = dmalloc(c, &c->d_trees, tree_words * 4))) return bail(rc);
-    c->gather_cap = (size_t)kMaxQueries * (4 + 2 * c->R) * (c->L + 1) + 64;
+    c->gather_cap = c->gather_floor = (size_t)kMaxQueries * (4 + 2 * c->R) * (c->L + 1) + 64;
     if ((rc = dmalloc(c, &c->d_gather_off, c->gather_cap * 8))) return bail(rc);
     if ((rc = dmalloc(c, &c->d_gather_out, c->gather_cap * 32))) return bail(rc);
     HIPCHK_C(hipHostMalloc((void**)&c->h_gather_off, c->gather_cap * 8, hipHostMallocMapped | hipHostMallocCoherent));
@@ -1062,6 +1196,40 @@ int zk_ctx_set_early_launch(zk_ctx* c, int on) {
 int zk_ctx_get_early_launch(const zk_ctx* c) { return c && c->early && c->early_ok && c->fmt.fold == 1 && !c->fmt.coset && !c->fmt.stop ? 1 : 0; }
 // FRI folding factor 2^fold_log between commitments (include/zkstark_amd.h).  A query of a folded proof opens 2^fold_log values and
 // paths per group: the decommitment buffers grow here, not inside the first proof.
+// The decommitment buffers hold `cap` items (8 bytes of work list and 32 of result each, on the device and pinned); with ext off they only
+// grow (gather_floor), with ext on they also hold the second word of every opened value of E and go back to the floor when it is set off.
+static int fit_gather(zk_ctx* c, const char* who) {
+    size_t opened = 0;
+    const ProofFormat widest{.log_n = c->log_n, .log_b = c->log_b, .fold = c->fmt.fold};   // one-value leaves, no early stop, no cap: it opens the most
+    widest.for_each_tuple([&](size_t s, size_t, bool) { opened += s; });
+    const size_t with_ext = c->fmt.ext ? (size_t)kMaxQueries * opened * (c->L + 2) + 64 : 0;
+    const size_t cap = with_ext > c->gather_floor ? with_ext : c->gather_floor;
+    if (cap == c->gather_cap) return ZK_OK;
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    uint64_t *d_off = nullptr, *h_off = nullptr, *dm_off = nullptr;
+    uint32_t *d_out = nullptr, *h_out = nullptr, *dm_out = nullptr;
+    hipError_t e = hipMalloc((void**)&d_off, cap * 8);
+    if (e == hipSuccess) e = hipMalloc((void**)&d_out, cap * 32);
+    if (e == hipSuccess) e = hipHostMalloc((void**)&h_off, cap * 8, hipHostMallocMapped | hipHostMallocCoherent);
+    if (e == hipSuccess) e = hipHostMalloc((void**)&h_out, cap * 32, hipHostMallocMapped | hipHostMallocCoherent);
+    if (e == hipSuccess) e = hipHostGetDevicePointer((void**)&dm_off, h_off, 0);
+    if (e == hipSuccess) e = hipHostGetDevicePointer((void**)&dm_out, h_out, 0);
+    if (e != hipSuccess) {
+        if (d_off) (void)hipFree(d_off);
+        if (d_out) (void)hipFree(d_out);
+        if (h_off) (void)hipHostFree(h_off);
+        if (h_out) (void)hipHostFree(h_out);
+        return fail(ZK_ERR_NOMEM, "%s: decommitment buffers: %s", who, hipGetErrorString(e));
+    }
+    (void)hipFree(c->d_gather_off); (void)hipFree(c->d_gather_out);
+    (void)hipHostFree(c->h_gather_off); (void)hipHostFree(c->h_gather_out);
+    c->d_gather_off = d_off; c->d_gather_out = d_out; c->h_gather_off = h_off; c->h_gather_out = h_out;
+    c->dm_gather_off = dm_off; c->dm_gather_out = dm_out;
+    c->device_bytes = c->device_bytes + cap * 40 - c->gather_cap * 40;
+    c->gather_cap = cap;
+    return ZK_OK;
+}
 int zk_ctx_set_fold(zk_ctx* c, uint32_t fold_log) {
     if (!c) return fail(ZK_ERR_INVALID, "null context");
     if (c->tail) return fail(ZK_ERR_STATE, "zk_ctx_set_fold: FRI-tail context");
@@ -1070,32 +1238,49 @@ int zk_ctx_set_fold(zk_ctx* c, uint32_t fold_log) {
     size_t opened = 0;
     widest.for_each_tuple([&](size_t s, size_t, bool) { opened += s; });
     const size_t cap = (size_t)kMaxQueries * opened * (c->L + 1) + 64;
-    if (cap > c->gather_cap) {
-        HIPCHK(hipSetDevice(c->device));
-        HIPCHK(hipStreamSynchronize(c->stream));
-        uint64_t *d_off = nullptr, *h_off = nullptr, *dm_off = nullptr;
-        uint32_t *d_out = nullptr, *h_out = nullptr, *dm_out = nullptr;
-        hipError_t e = hipMalloc((void**)&d_off, cap * 8);
-        if (e == hipSuccess) e = hipMalloc((void**)&d_out, cap * 32);
-        if (e == hipSuccess) e = hipHostMalloc((void**)&h_off, cap * 8, hipHostMallocMapped | hipHostMallocCoherent);
-        if (e == hipSuccess) e = hipHostMalloc((void**)&h_out, cap * 32, hipHostMallocMapped | hipHostMallocCoherent);
-        if (e == hipSuccess) e = hipHostGetDevicePointer((void**)&dm_off, h_off, 0);
-        if (e == hipSuccess) e = hipHostGetDevicePointer((void**)&dm_out, h_out, 0);
-        if (e != hipSuccess) {
-            if (d_off) (void)hipFree(d_off);
-            if (d_out) (void)hipFree(d_out);
-            if (h_off) (void)hipHostFree(h_off);
-            if (h_out) (void)hipHostFree(h_out);
-            return fail(ZK_ERR_NOMEM, "zk_ctx_set_fold: decommitment buffers: %s", hipGetErrorString(e));
-        }
-        (void)hipFree(c->d_gather_off); (void)hipFree(c->d_gather_out);
-        (void)hipHostFree(c->h_gather_off); (void)hipHostFree(c->h_gather_out);
-        c->d_gather_off = d_off; c->d_gather_out = d_out; c->h_gather_off = h_off; c->h_gather_out = h_out;
-        c->dm_gather_off = dm_off; c->dm_gather_out = dm_out;
-        c->device_bytes += (cap - c->gather_cap) * 40;
-        c->gather_cap = cap;
-    }
+    const uint32_t before = c->fmt.fold;
+    const size_t floor_before = c->gather_floor;
+    if (cap > c->gather_floor) c->gather_floor = cap;
     c->fmt.fold = fold_log;
+    if (int rc = fit_gather(c, "zk_ctx_set_fold")) { c->fmt.fold = before; c->gather_floor = floor_before; return rc; }
+    return ZK_OK;
+}
+// Challenges in E (include/zkstark_amd.h): from the next one-call proof on.  Sizes the second planes and the gather buffers
+// here, both ways: with ext off every allocation is what it was.
+int zk_ctx_set_ext(zk_ctx* c, uint32_t ext_log) {
+    if (!c) return fail(ZK_ERR_INVALID, "null context");
+    if (c->tail) return fail(ZK_ERR_STATE, "zk_ctx_set_ext: FRI-tail context");
+    if (ext_log > 1) return fail(ZK_ERR_INVALID, "zk_ctx_set_ext: ext_log must be 0 or 1 (got %u; 2, the quartic extension, is reserved)", ext_log);
+    if (ext_log && c->hash == ZK_HASH_BLAKE2S) return fail(ZK_ERR_INVALID, "zk_ctx_set_ext: ext_log = 1 and BLAKE2s (hash 2) do not combine: BLAKE2s has no row leaf");
+    BusyScope busy(c);
+    if (!busy.mine) return fail(ZK_ERR_STATE, "zk_ctx_set_ext: a proof is running on this context");
+    if (ext_log == c->fmt.ext) return ZK_OK;
+    HIPCHK(hipSetDevice(c->device));
+    if (int rc = settle_pending(c)) return rc;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    const size_t planes = ext_log ? 2 * (c->layer_words - c->N) : 0, words = c->layer_words + planes;
+    uint32_t* fresh = nullptr;
+    hipError_t e = hipMalloc((void**)&fresh, words * 4);
+    if (e != hipSuccess) return fail(ZK_ERR_NOMEM, "zk_ctx_set_ext: hipMalloc(%zu) failed: %s", words * 4, hipGetErrorString(e));
+    const uint32_t before = c->fmt.ext;
+    c->fmt.ext = ext_log;
+    if (int rc = fit_gather(c, "zk_ctx_set_ext")) { c->fmt.ext = before; (void)hipFree(fresh); return rc; }
+    (void)hipFree(c->d_layers);                               // the layers of the last proof go with it: every proof writes its own
+    c->d_layers = fresh;
+    c->device_bytes = c->device_bytes + words * 4 - (c->layer_words + (before ? 2 * (c->layer_words - c->N) : 0)) * 4;
+    c->ext_base = ext_log ? c->layer_words : 0;
+    c->have_lde = false;
+    for (uint32_t l = 0; l <= c->R + 1; ++l) { c->skipped_layers |= (uint64_t)1 << l; c->skipped_trees |= (uint64_t)1 << l; }
+    return ZK_OK;
+}
+uint32_t zk_ctx_get_ext(const zk_ctx* c) { return c ? c->fmt.ext : 0; }
+// The component-1 raws of the last proof's challenges: alpha0.c1, alpha1.c1, alpha2.c1, then one per group (zk_last_transcript has the
+// component-0 raws in the fields it always had); *count = 0 after a proof with ext off.
+int zk_ctx_ext_challenges(const zk_ctx* c, uint32_t* out, size_t cap, size_t* count) {
+    if (!c || !count || (!out && cap)) return fail(ZK_ERR_INVALID, "zk_ctx_ext_challenges: null argument");
+    *count = c->ext_chal.size();
+    if (c->ext_chal.size() > cap) return fail(ZK_ERR_BUFFER, "zk_ctx_ext_challenges: %zu raws, room for %zu", c->ext_chal.size(), cap);
+    if (!c->ext_chal.empty()) memcpy(out, c->ext_chal.data(), c->ext_chal.size() * 4);
     return ZK_OK;
 }
 uint32_t zk_ctx_get_fold(const zk_ctx* c) { return c ? c->fmt.fold : 0; }
@@ -1203,6 +1388,7 @@ int zk_ctx_set_hash(zk_ctx* c, int hash_kind) {
     if (hash_kind != ZK_HASH_SHA256 && hash_kind != ZK_HASH_FIELD && hash_kind != ZK_HASH_BLAKE2S)
         return fail(ZK_ERR_INVALID, "zk_ctx_set_hash: unknown hash %d", hash_kind);
     if (hash_kind == ZK_HASH_BLAKE2S && c->tail) return fail(ZK_ERR_INVALID, "zk_ctx_set_hash: %s", kNoBlake2s);
+    if (hash_kind == ZK_HASH_BLAKE2S && c->fmt.ext) return fail(ZK_ERR_INVALID, "zk_ctx_set_hash: BLAKE2s (hash 2) and ext_log = 1 do not combine: BLAKE2s has no row leaf");
     c->hash = hash_kind;
     return ZK_OK;
 }
@@ -1555,6 +1741,21 @@ int zk_verify_cap(const uint8_t* proof, size_t len, const uint8_t* state, uint32
                                     .cap = cap_log},
                         &public_last, hash_kind, check_out, nullptr, "");
 }
+// zk_verify_cap with ProofFormat::ext (transcript.hpp "ext"); ext_log = 0 is zk_verify_cap, line for line
+int zk_verify_ext(const uint8_t* proof, size_t len, const uint8_t* state, uint32_t log_n, uint32_t log_b, uint32_t public_last,
+                  int hash_kind, uint32_t n_queries, uint32_t grind_bits, uint32_t fold_log, int coset_leaves, uint32_t stop_log, uint32_t cap_log,
+                  uint32_t ext_log, int32_t* check_out) {
+    if (!ext_log)
+        return zk_verify_cap(proof, len, state, log_n, log_b, public_last, hash_kind, n_queries, grind_bits, fold_log, coset_leaves, stop_log, cap_log, check_out);
+    if (!proof || !check_out) return fail(ZK_ERR_INVALID, "zk_verify_ext: null argument");
+    *check_out = -1;
+    if (ext_log != 1) return fail(ZK_ERR_INVALID, "zk_verify_ext: ext_log must be 0 or 1 (got %u; 2, the quartic extension, is reserved)", ext_log);
+    if (hash_kind == ZK_HASH_BLAKE2S) return fail(ZK_ERR_INVALID, "zk_verify_ext: ext_log = 1 and BLAKE2s (hash 2) do not combine: BLAKE2s has no row leaf");
+    return verify_entry("zk_verify_ext", proof, len, state,
+                        ProofFormat{.log_n = log_n, .log_b = log_b, .q = n_queries, .grind = grind_bits, .fold = fold_log, .coset = coset_leaves != 0, .stop = stop_log,
+                                    .cap = cap_log, .ext = ext_log},
+                        &public_last, hash_kind, check_out, nullptr, "");
+}
 // zk_verify_cap for ONE proof of 2^log_batch statements (transcript.hpp "lb"); public_last: one value per statement.
 // log_batch outside 1..8 is refused with check -1: a batch of one is a plain proof and goes to zk_verify_cap.
 int zk_verify_shared(const uint8_t* proof, size_t len, const uint8_t* state, uint32_t log_n, uint32_t log_b, const uint32_t* public_last,
@@ -1609,6 +1810,14 @@ size_t zk_proof_data_len_cap(uint32_t log_n, uint32_t log_b, uint32_t n_queries,
                              uint32_t cap_log) {
     if (fold_log < 1 || fold_log > kMaxFoldLog || !stop_ok(log_n, log_b, stop_log) || cap_log > kMaxCapLog) return 0;
     return ProofFormat{.log_n = log_n, .log_b = log_b, .q = n_queries, .grind = grind_bits, .fold = fold_log, .coset = coset_leaves != 0, .stop = stop_log, .cap = cap_log}
+        .data_len();
+}
+// ext_log = 0: zk_proof_data_len_cap; 0 for an ext_log other than 0 or 1
+size_t zk_proof_data_len_ext(uint32_t log_n, uint32_t log_b, uint32_t n_queries, uint32_t grind_bits, uint32_t fold_log, int coset_leaves, uint32_t stop_log,
+                             uint32_t cap_log, uint32_t ext_log) {
+    if (fold_log < 1 || fold_log > kMaxFoldLog || !stop_ok(log_n, log_b, stop_log) || cap_log > kMaxCapLog || ext_log > 1) return 0;
+    return ProofFormat{.log_n = log_n, .log_b = log_b, .q = n_queries, .grind = grind_bits, .fold = fold_log, .coset = coset_leaves != 0, .stop = stop_log, .cap = cap_log,
+                       .ext = ext_log}
         .data_len();
 }
 // log_batch = 0: zk_proof_data_len_cap
@@ -1799,6 +2008,22 @@ int zk_dev_fri_fold_multi(const zk_dom* d, const uint32_t* d_in, uint32_t* d_out
         return fail(ZK_ERR_INVALID, "zk_dev_fri_fold_multi: layer 2^%u, rounds %u..%u do not fit a domain of %u rounds", log_m, round, round + steps, d->log_n);
     HIPCHK(hipSetDevice(d->device));
     return dom_fold_multi(d, d_in, d_out, log_m, round, steps, beta_raw, (hipStream_t)stream, dev_prof());
+}
+int zk_dev_compose_ext(const zk_dom* d, const uint32_t* d_f, uint32_t* d_cp, uint32_t first, uint32_t last,
+                       const uint32_t alpha_raw[6], void* stream) {
+    if (!d || !d_f || !d_cp || !alpha_raw) return fail(ZK_ERR_INVALID, "zk_dev_compose_ext: null argument");
+    if (!d->d_inv_xm1) return fail(ZK_ERR_STATE, "zk_dev_compose_ext: fold-only domain");
+    HIPCHK(hipSetDevice(d->device));
+    return dom_compose_ext(d, d_f, d_cp, first, last, alpha_raw, (hipStream_t)stream, dev_prof());
+}
+int zk_dev_fri_fold_multi_ext(const zk_dom* d, const uint32_t* d_in, uint32_t* d_out, uint32_t log_m, uint32_t round, uint32_t steps,
+                              const uint32_t beta_raw[2], void* stream) {
+    if (!d || !d_in || !d_out || !beta_raw) return fail(ZK_ERR_INVALID, "zk_dev_fri_fold_multi_ext: null argument");
+    if (steps < 1 || steps > kMaxFoldLog) return fail(ZK_ERR_INVALID, "zk_dev_fri_fold_multi_ext: steps must be 1..%u (got %u)", kMaxFoldLog, steps);
+    if (round + steps > d->log_n || log_m + round != d->L)
+        return fail(ZK_ERR_INVALID, "zk_dev_fri_fold_multi_ext: layer 2^%u, rounds %u..%u do not fit a domain of %u rounds", log_m, round, round + steps, d->log_n);
+    HIPCHK(hipSetDevice(d->device));
+    return dom_fold_multi_ext(d, d_in, d_out, log_m, round, steps, beta_raw, (hipStream_t)stream, dev_prof());
 }
 int zk_dev_fri_fold_multi_batch(const zk_dom* d, const uint32_t* d_in, uint32_t* d_out, uint32_t log_m, uint32_t round, uint32_t steps,
                                 const uint32_t* d_beta_raw, uint32_t* d_work, uint32_t batch, void* stream) {

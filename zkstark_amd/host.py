@@ -27,6 +27,8 @@ def _proof_data_len(o, log_batch=0, rows=False):
     """Bytes of a proof in the format of `o` (a Proof, Context, BatchContext or Verifier).  zk_proof_data_len_shared is the general
     entry point: log_batch 0 (one statement per proof), cap 0, stop 0 and one-value leaves are the older formats byte for byte.
     log_batch > 0: ONE shared proof of 2^log_batch statements (BatchContext.prove_shared); rows: with row leaves."""
+    if getattr(o, "ext_log", 0):                    # challenges in E (Context(ext_log=1), Proof(ext_log=1)): one statement
+        return _lib.load().zk_proof_data_len_ext(o.log_n, o.log_blowup, o.queries, o.grind_bits, o.fold_log, int(o.coset_leaves), o.stop_log, o.cap_log, o.ext_log)
     if rows:
         return _lib.load().zk_proof_data_len_shared_rows(o.log_n, o.log_blowup, o.queries, o.grind_bits, o.fold_log, int(o.coset_leaves), o.stop_log,
                                                          o.cap_log, log_batch, 1)
@@ -78,6 +80,29 @@ class field:
     def root_of_unity(log_order): return _lib.load().zk_field_root_of_unity(log_order)
     @staticmethod
     def order(a): return _lib.load().zk_field_order(a)     # field.rs:45-49
+
+
+def _ext_call(fn, *args):
+    out = (C.c_uint32 * 2)()
+    check(fn(*[(C.c_uint32 * 2)(a[0] & 0xFFFFFFFF, a[1] & 0xFFFFFFFF) if isinstance(a, (tuple, list)) else a for a in args], out))
+    return (int(out[0]), int(out[1]))
+
+
+def ext_mul(a, b):
+    """Product in E = F_P[u] / (u^2 - 5) of the pairs (c0, c1) = c0 + c1 u (zk_ext_mul)."""
+    return _ext_call(_lib.load().zk_ext_mul, tuple(a), tuple(b))
+
+
+def ext_inv(a):
+    """Inverse in E (zk_ext_inv); zero has none."""
+    if a[0] % P == 0 and a[1] % P == 0:
+        raise ZeroDivisionError("the inverse of zero in E")
+    return _ext_call(_lib.load().zk_ext_inv, tuple(a))
+
+
+def ext_pow(a, e):
+    """a^e in E for an exponent 0 <= e < 2^64 (zk_ext_pow)."""
+    return _ext_call(_lib.load().zk_ext_pow, tuple(a), C.c_uint64(e))
 
 
 def host_hash_mode():
@@ -164,8 +189,9 @@ class Proof:
     """proof.rs:5-154.  verify() raises ZkError where the reference panics."""
 
     def __init__(self, state, data, log_n=10, log_blowup=3, public_last=2338775057, hash="sha256", queries=1, grind_bits=0,
-                 fold_log=1, coset_leaves=False, stop_log=0, cap_log=0):   # proof.rs:11
+                 fold_log=1, coset_leaves=False, stop_log=0, cap_log=0, ext_log=0):   # proof.rs:11
         self.state, self.data = bytes(state), bytes(data)
+        self.ext_log = ext_log                       # challenges, cp and the FRI layers in E (DESIGN.md 7j): zk_verify_ext, zk_proof_data_len_ext
         self.cap_log = cap_log                       # made with zk_ctx_set_merkle_cap: zk_verify_cap, zk_proof_data_len_cap
         self.stop_log = stop_log                     # made with zk_ctx_set_fri_stop: zk_verify_stop, zk_proof_data_len_stop
         self.log_n, self.log_blowup, self.public_last = log_n, log_blowup, public_last
@@ -181,9 +207,13 @@ class Proof:
     def _general(self):
         """Folded, coset-leaf, stopped and BLAKE2s proofs go through the general entry points (zk_verify_check and zk_verify_fold keep
         the two hashes they were defined with: a BLAKE2s proof of any setting is verified by zk_verify_stop)."""
-        return self.fold_log != 1 or self.coset_leaves or self.stop_log or self.cap_log or self.hash == "blake2s"
+        return self.fold_log != 1 or self.coset_leaves or self.stop_log or self.cap_log or self.hash == "blake2s" or self.ext_log
 
     def _verify_general(self, strict, out):
+        if self.ext_log:                             # the one entry point that takes ext_log
+            return _lib.load().zk_verify_ext(self.data, len(self.data), self.state if strict else None, self.log_n, self.log_blowup,
+                                             self.public_last, HASHES[self.hash], self.queries, self.grind_bits, self.fold_log,
+                                             int(self.coset_leaves), self.stop_log, self.cap_log, self.ext_log, C.byref(out))
         if self.cap_log:                             # Merkle caps: the one entry point that takes cap_log
             return _lib.load().zk_verify_cap(self.data, len(self.data), self.state if strict else None, self.log_n, self.log_blowup,
                                              self.public_last, HASHES[self.hash], self.queries, self.grind_bits, self.fold_log,
@@ -306,8 +336,9 @@ class Context:
     """Device-resident prover state for one (log_n, log_blowup): zk_ctx."""
 
     def __init__(self, log_n=10, log_blowup=3, device=0, hash="sha256", queries=1, host_levels=None, grind_bits=0, fold_log=1,
-                 coset_leaves=False, stop_log=0, cap_log=0):
-        """cap_log: commit every tree by its 2^cap_log digests of depth cap_log and open paths that much shorter (zk_ctx_set_merkle_cap;
+                 coset_leaves=False, stop_log=0, cap_log=0, ext_log=0):
+        """ext_log: 1 draws the challenges, and holds cp and the FRI layers, in the quadratic extension E (zk_ctx_set_ext; 0 = the base field).
+        cap_log: commit every tree by its 2^cap_log digests of depth cap_log and open paths that much shorter (zk_ctx_set_merkle_cap;
         0 = roots).  host_levels: (top_log, tail_log) of zk_ctx_set_host_levels; None = the library default.  grind_bits: proof-of-work
         bits before the query draw (zk_ctx_set_grinding; 0 = none).  fold_log: FRI folding factor 2^fold_log between commitments
         (zk_ctx_set_fold; 1 = the reference).  coset_leaves: one coset per Merkle leaf of the FRI trees (zk_ctx_set_coset_leaves).
@@ -316,6 +347,7 @@ class Context:
         self.coset_leaves = False
         self.stop_log = 0
         self.cap_log = 0
+        self.ext_log = 0
         self.log_n, self.log_blowup, self.device, self.hash, self.queries = log_n, log_blowup, device, hash, queries
         self.grind_bits = grind_bits
         self.n, self.B = 1 << log_n, 1 << log_blowup
@@ -338,6 +370,20 @@ class Context:
             self.set_fri_stop(stop_log)
         if cap_log:
             self.set_merkle_cap(cap_log)
+        if ext_log:
+            self.set_ext(ext_log)
+
+    def set_ext(self, ext_log):
+        """zk_ctx_set_ext: from the next proof on, challenges in E = F_P[u] / (u^2 - 5) (1) or in the base field (0).  Sizes the second planes of
+        the layers and the decommitment buffers when called; refused (ZK_ERR_STATE) while a proof runs on the context."""
+        check(_lib.load().zk_ctx_set_ext(self._h, ext_log))
+        self.ext_log = ext_log
+
+    def ext_challenges(self):
+        """The component-1 raws of the last proof's challenges: three alphas, then one per group (zk_ctx_ext_challenges)."""
+        out, n = (C.c_uint32 * 64)(), C.c_size_t()
+        check(_lib.load().zk_ctx_ext_challenges(self._h, out, 64, C.byref(n)))
+        return [int(out[i]) for i in range(n.value)]
 
     def set_merkle_cap(self, cap_log):
         """zk_ctx_set_merkle_cap: from the next one-call proof on, a tree of 2^lg leaves is committed by the 2^ce digests of depth
@@ -488,7 +534,7 @@ class Context:
             check(_lib.load().zk_prove(self._h, _ptr(t), len(t), buf, cap, C.byref(n), st))
         info = self.last_transcript()
         return Proof(st.raw, buf.raw[:n.value], self.log_n, self.log_blowup, info.public_last, self.hash, self.queries, self.grind_bits,
-                     self.fold_log, self.coset_leaves, self.stop_log, self.cap_log)
+                     self.fold_log, self.coset_leaves, self.stop_log, self.cap_log, self.ext_log)
 
     def prove_channel(self, channel):
         """generate_proof(channel) (prover.rs:9) in one C call on the caller's Channel (zk_prove_channel): the
@@ -496,7 +542,7 @@ class Context:
         check(_lib.load().zk_prove_channel(self._h, channel._h))
         proof = channel.finalize(self.log_n, self.log_blowup, self.last_transcript().public_last)
         proof.grind_bits, proof.fold_log, proof.coset_leaves = self.grind_bits, self.fold_log, self.coset_leaves
-        proof.stop_log, proof.cap_log = self.stop_log, self.cap_log
+        proof.stop_log, proof.cap_log, proof.ext_log = self.stop_log, self.cap_log, self.ext_log
         return proof
 
     def set_host_levels(self, top_log, tail_log):
@@ -546,7 +592,7 @@ def prove_many(ctxs):
     out = []
     for i, c in enumerate(ctxs):
         out.append(Proof(states[i].tobytes(), data[i, :lens[i]].tobytes(), c.log_n, c.log_blowup, c.last_transcript().public_last,
-                         c.hash, c.queries, c.grind_bits, c.fold_log, c.coset_leaves, c.stop_log, c.cap_log))
+                         c.hash, c.queries, c.grind_bits, c.fold_log, c.coset_leaves, c.stop_log, c.cap_log, c.ext_log))
     return out
 
 
