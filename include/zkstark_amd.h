@@ -279,7 +279,7 @@ int zk_ctx_set_merkle_cap(zk_ctx *ctx, uint32_t cap_log);
  * next one-call proof on (zk_prove, zk_prove_resident, zk_prove_channel, zk_prove_many), with every fold_log, leaf format, fri_stop,
  * merkle_cap, query count, grinding, hashes 0 and 1 and host levels.  The trace and f stay in the base field; the alphas, cp, every beta
  * and every FRI layer are in E.  With ext on every folding factor and leaf format takes the grouped round loop (no fused leaf launches,
- * early launch or host FRI tail), the trees over cp and the FRI layers are row trees over the layer's two planes, and the reference
+ * early launch or host FRI tail: zk_ctx_get_early_launch answers 0), the trees over cp and the FRI layers are row trees over the layer's two planes, and the reference
  * self-checks (zk_ctx_set_checks) hold both planes to the degree bound.  The setter sizes the second planes and the decommitment buffers
  * when called, both ways: with ext_log = 0 zk_ctx_device_bytes, every launch and every byte are what they were.  It drops the layers of
  * the last proof.  ZK_ERR_INVALID for ext_log > 1 (2, the quartic extension, is reserved) and for ext_log = 1 with BLAKE2s, which has no

@@ -159,7 +159,8 @@ class Committed:
 
 
 @functools.lru_cache(maxsize=64)
-def committed(orc, log_n, log_b, hash_kind, K, coset, D, c, a1=3141592):
+def committed(orc, log_n, log_b, hash_kind, K, coset, D, c, a1=3141592, prefix=b""):
+    """prefix: what the channel holds before the proof starts (zk_prove_channel), as cap_ref.committed."""
     assert stop_ref.admissible(log_n, log_b, D) and 0 <= c <= cap_ref.MAX_CAP and hash_kind in (0, 1)
     r = orc.prove(log_n, log_b, 1, a1, want_vectors=True)
     assert r.rc == 0
@@ -167,7 +168,7 @@ def committed(orc, log_n, log_b, hash_kind, K, coset, D, c, a1=3141592):
     grp = groups(Rp, K)
     out = Committed()
     out.public_last, out.layers, out.trees, out.lg, out.ce, out.caps, out.betas = r.public_last, {}, {}, {}, {}, {}, {}
-    ch = _Channel()
+    ch = _Channel(prefix)
     orc.set_hash(hash_kind)
     try:
         def commit_tree(i, heap):
@@ -207,9 +208,9 @@ def committed(orc, log_n, log_b, hash_kind, K, coset, D, c, a1=3141592):
     return out
 
 
-def proof(orc, log_n, log_b, q, hash_kind, K, coset, D, c, bits=0, a1=3141592):
-    """.data, .state, .public_last, .nonce, .raws, .c (Committed)."""
-    cm = committed(orc, log_n, log_b, hash_kind, K, bool(coset), D, c, a1)
+def proof(orc, log_n, log_b, q, hash_kind, K, coset, D, c, bits=0, a1=3141592, prefix=b""):
+    """.data (the prefix included), .state, .public_last, .nonce, .raws, .c (Committed)."""
+    cm = committed(orc, log_n, log_b, hash_kind, K, bool(coset), D, c, a1, prefix)
     N, B = 1 << (log_n + log_b), 1 << log_b
     ch = _Channel()
     ch.state, ch.data = cm.prefix_state, bytearray(cm.prefix_data)
@@ -241,7 +242,7 @@ def proof(orc, log_n, log_b, q, hash_kind, K, coset, D, c, bits=0, a1=3141592):
                 idx = [(x % size + t * (size >> steps)) % size for t in range(1 << steps)]
                 ch.commit(words([int(planes[j * size + i]) for j in (0, 1) for i in idx]) + b"".join(counted_path(1 + r0, i) for i in idx))
     out.data, out.state, out.raws = bytes(ch.data), ch.state, raws
-    assert len(out.data) == proof_len(log_n, log_b, q, bits, K, coset, D, c)
+    assert len(out.data) - len(prefix) == proof_len(log_n, log_b, q, bits, K, coset, D, c)
     return out
 
 

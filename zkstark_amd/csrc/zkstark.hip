@@ -1193,7 +1193,7 @@ int zk_ctx_set_early_launch(zk_ctx* c, int on) {
     c->early = on != 0;
     return ZK_OK;
 }
-int zk_ctx_get_early_launch(const zk_ctx* c) { return c && c->early && c->early_ok && c->fmt.fold == 1 && !c->fmt.coset && !c->fmt.stop ? 1 : 0; }
+int zk_ctx_get_early_launch(const zk_ctx* c) { return c && c->early && c->early_ok && c->fmt.fold == 1 && !c->fmt.coset && !c->fmt.stop && !c->fmt.ext ? 1 : 0; }
 // FRI folding factor 2^fold_log between commitments (include/zkstark_amd.h).  A query of a folded proof opens 2^fold_log values and
 // paths per group: the decommitment buffers grow here, not inside the first proof.
 // The decommitment buffers hold `cap` items (8 bytes of work list and 32 of result each, on the device and pinned); with ext off they only

@@ -409,8 +409,9 @@ class Context:
         self.stop_log = stop_log
 
     def final_poly(self):
-        """zk_ctx_final_poly: the coefficients the last proof ended with (stop_log 0: one value, the free term)."""
-        out, n = np.zeros(1 << 8, dtype=np.uint32), C.c_size_t()
+        """zk_ctx_final_poly: the coefficients the last proof ended with (stop_log 0: one value, the free term); with ext_log = 1 the words
+        of both planes in wire order, 2 * 2^stop_log of them."""
+        out, n = np.zeros(2 << 8, dtype=np.uint32), C.c_size_t()
         check(_lib.load().zk_ctx_final_poly(self._h, _ptr(out), len(out), C.byref(n)))
         return out[:n.value].copy()
 
