@@ -1,73 +1,62 @@
 // verify.hip -- batched proof verification on the device (zk_verifier_*).  The single-proof entry points (zk_verify*) are in
 // zkstark.hip; the CPU verifier itself, one for every folding factor, is transcript.hpp.
 //
-// The result of every proof is the number the CPU verifier stops at (transcript.hpp: verify_transcript, then verify_proof),
-// for every input.  The device gets there without a per-proof parser:
-//   * once the length is fixed, every field of a proof sits at a fixed offset if every u64 path count has its expected
-//     value (L for the four f / cp paths, L - k for the two paths of layer k).  verify_algebra_kernel checks the counts;
-//     a proof whose counts differ is "malformed" and the host runs verify_proof on it (only garbage takes that path).  On
-//     the fixed layout the checks -1, -3, -(200 + k) and -8 cannot fail;
-//   * every other check runs in parallel and posts an order key (query * (5 + 3R) + position, the order verify_proof
-//     visits them in); the smallest key per proof is the first failure (atomicMin);
+// The result of every proof is the number the CPU verifier stops at (transcript.hpp: verify_transcript, then verify_proof, with the
+// ProofFormat of the handle), for every input.  The device gets there without a per-proof parser:
+//   * once the length is fixed, every field of a proof sits at a fixed offset if every u64 path count has its expected value.  The host
+//     lays the format out once per run, from ProofFormat::for_each_head / for_each_tuple, into a table of at most 32 trees that travels
+//     with the launch arguments (ProofLayout): the header words of the alphas, of every beta and tree commitment and of the free term, the
+//     words of the f and cp tuples, and per group the first word of its opening and the digests of its paths.  The kernels read every
+//     offset from it; none is restated in closed form.  The algebra kernel checks the counts; a proof whose counts differ is "malformed"
+//     and the host runs verify_proof on it (only garbage takes that path).  On the fixed layout the checks -1, -3, -(200 + j) and -8
+//     cannot fail;
+//   * every other check runs in parallel and posts an order key (query * keys + position, the order verify_proof visits them in); the
+//     smallest key per proof is the first failure (atomicMin), whichever lane finishes first;
 //   * strict mode: a transcript failure wins (verify_transcript runs first on the CPU), so it has its own result.
-// The raw-value rules of verify_proof are kept: values are reduced % P before arithmetic, but fv[3] is compared unreduced
-// with cp0, and the FRI expectation (value 0 of the next round's pair, or the free term) unreduced with a reduced calc.  Leaf hashes take the raw word.
+// The raw-value rules of verify_proof are kept: values are reduced % P before arithmetic, but cp(x) is compared unreduced with cp0, and
+// the FRI expectation (value 0 of the next group, or the free term) unreduced with a reduced calc.  Leaf hashes take the raw word.
 //
-// Folding factor 2^K (zk_verifier_set_fold, K = 2 or 3; transcript.hpp: verify_transcript, then verify_proof, with fold = K): the R
-// rounds come in G = ceil(R / K) groups, group j opens the s_j = 2^steps_j values of its input layer (round r0 = j K) and then
-// their s_j paths of L - r0 digests, so the layout is fixed in the same way and only the last group can be short.  The order
-// keys are query * (5 + 9G) + position: 0 (-2), 1..4 (-4..-7), 5 + j (the fold comparison of group j), 5 + G + 8j + t (path t
-// of group j: -(300 + j) for t = 0, -(400 + j) for t >= 1).  The fold comparison inverts x once per (proof, query) and squares
-// the inverse from round to round; the inverse powers of the 8th root of unity that tell the s points of a group apart come
-// with the launch arguments (residues are canonical, so an algebraically equal evaluation is bit-exact).  K = 1 runs the
-// kernels it always ran: the paths and transcript kernels are templates whose unfolded instance is the code as it was.
+// One format, of which every setter's default is the degenerate case:
+//   * folding factor 2^K (zk_verifier_set_fold, K = 1..3): the R rounds come in G = ceil(R / K) groups, group j opens the s_j = 2^steps_j
+//     values of its input layer (round r0 = jK) and only the last group can be short.  K = 1 is G = R groups of two values.  The fold
+//     comparison inverts x once per (proof, query) and squares the inverse from round to round; the inverse powers of the 8th root of
+//     unity that tell the s points of a group apart come with the launch arguments (residues are canonical, so an algebraically equal
+//     evaluation is bit-exact);
+//   * leaf format (zk_verifier_set_coset_leaves).  One-value leaves: a query is four tuples (f(x), f(gx), f(g^2 x), cp(x)) of a value, a
+//     count and a path, then per group its s_j values and s_j paths.  Order keys, 5 + 9G per query: 0 (-2), 1..4 (-4..-7), 5 + j (the
+//     fold comparison of group j, -(100 + j)), 5 + G + 8j + u (path u of group j: -(300 + j) for u = 0, -(400 + j) for u >= 1).  Coset
+//     leaves: three f tuples, then per group its s_j slot words in slot order, ONE count and ONE path.  Value u of group j is slot
+//     (rot + u) & (s - 1) with rot = (tp % len) >> (log len - steps): the kernels read it at that address, and cp(x) is value 0 of group
+//     0.  Order keys, 4 + 2G per query: 0 (-2), 1..3 (-4..-6), 4 + j (-(100 + j)), 4 + G + j (the path of group j, -(300 + j)); -7 and
+//     -(400 + j) cannot occur;
+//   * early stop (zk_verifier_set_fri_stop, D = 0..8): the groups are those of the R' = log_n - D folded rounds, and the launch arguments
+//     carry R', G' and the last group's steps as R, G and ls (the cp0 relation alone keeps log_n).  With D != 0 the header has no last
+//     tree, and the 2^D coefficients stand where the free term was: the last group's fold is compared with p(x^(2^R')) by Horner over
+//     the coefficients, each reduced % P on reading, canonical against canonical.  A uniform branch on D;
+//   * Merkle caps (zk_verifier_set_merkle_cap, c = 0..8): every tree commitment is the tree's 2^ce digests and every path is ce digests
+//     shorter, with ce = min(c, lg - 1) per tree.  A path walks lg - ce levels and is compared with cap entry leaf >> (lg - ce); the
+//     transcript commits the 8 * 2^ce words of a cap in one piece.  c = 0 is one digest per cap, the root;
+//   * shared proofs (zk_verifier_set_shared, lb = 0..8, with or without row leaves): ONE proof of M = 2^lb statements, M public values
+//     per proof; the layout also says how many f tuples a query has (nft = 3M, or 3 rows; lb = 0: 3), how long one is, and where
+//     statement p's share of the f commitment starts.
+// Three kernels check a plain proof (lb = 0), one instance each per leaf format (and hash): verify_algebra_kernel, verify_paths_kernel
+// and, strict, verify_transcript_kernel.  Slot and tree are uniform per blockIdx.y, so all lanes of a wave walk paths of one length.
 //
-// Coset leaves (zk_verifier_set_coset_leaves; verify_transcript, then verify_proof, with coset = true; any K in 1..3, K = 1 being
-// G = R groups of s = 2): a query is three f tuples, then per group its s_j slot words in slot order, ONE u64 count and ONE path of
-// L - jK - steps_j digests, so the layout is fixed once the 3 + G counts have their values.  Value t of group j is slot
-// (rot + t) & (s - 1) with rot = (tp % len) >> (log len - steps): the kernels read it at that address.  The order keys are
-// query * (4 + 2G) + position: 0 (-2), 1..3 (-4..-6), 4 + j (the fold comparison of group j), 4 + G + j (the path of group j,
-// -(300 + j)); -3, -7, -(200 + j), -(400 + j) and -8 cannot occur on the fixed layout.  The coset kernels are instances of their
-// own (verify_coset_*_kernel, and the COSET instance of the transcript kernel); the other instances are the code they were.
-//
-// Early stop (zk_verifier_set_fri_stop, D = 1..8; verify_transcript, then verify_proof, with stop = D; any K and leaf format): the
-// groups are the G' of the R' = log_n - D folded rounds, and the launch arguments carry R', G' and the last group's steps in the
-// places of R, G and ls, so every offset, path slot and order key above holds with them (the cp0 relation alone keeps log_n).  In the
-// header the last root and the free term give way to the 2^D coefficients at word 11 + 9G'.  Two things differ, each in a STOP
-// instance of its own (the instances without it are the code they were): the last group's fold is compared with p(x^(2^R')) by
-// Horner over the coefficients, each reduced % P on reading, canonical against canonical; and the transcript schedule has no last
-// root and commits the 2^D words in one piece where the free term was.
-//
-// Merkle caps (zk_verifier_set_merkle_cap, c = 1..8; verify_transcript, then verify_proof, with cap = c; any K, leaf format and D): every
-// root of the header is the tree's 2^ce digests and every path is ce digests shorter, with ce = min(c, lg - 1) per tree, so the small trees of
-// a proof have caps of their own and no offset keeps its closed form.  The layout is still fixed once the path counts have their values; the
-// host lays it out once per run into a table of at most 32 trees that travels with the launch arguments (CapLayout): per group the first word
-// of its opening, the digests of its paths, the header word of its beta and of the cap of its input tree.  Three kernels of their own read
-// it (verify_cap_algebra_kernel, verify_cap_paths_kernel, verify_cap_transcript_kernel: the kernels above are the code they were): one
-// instance per leaf format covers K = 1..3 and D (K = 1 is G = R groups of two values), a path walks lg - ce levels and is compared with
-// cap entry leaf >> (lg - ce), the transcript commits the 8 * 2^ce words of a cap in one piece.  Slot and tree are uniform per blockIdx.y, so
-// all lanes of a wave still walk paths of one length.  The order keys are those of a folded proof (5 + 9G per query) or of a coset proof
-// (4 + 2G).  No scratch and no LDS.
-//
-// Shared proofs (zk_verifier_set_shared, lb = 1..8, with or without row leaves; verify_transcript, then verify_proof, with lb / rows; any K,
-// leaf format, D and cap): ONE proof of M = 2^lb statements, M public values per proof.  A shared proof always takes the table (cap 0: ce = 0,
-// one digest per cap); the table also says how many f tuples a query has (nft = 3M, or 3 rows), how long one is, and where statement p's share
-// of the f commitment starts.  Five kernels of their own (the kernels above are the code they were; two of the five are further instances of
-// the cap kernels' bodies):
+// A shared proof has five kernels, two of them further instances of the bodies above:
 //   * verify_shared_algebra_kernel, one lane per (proof, query): the counts of the cp tuple, the groups and the three rows, the -2 relation
 //     summed over the M statements as verify_proof sums it (three inversions per lane, three multiplications by alpha per statement), the G
-//     fold comparisons of the cap kernel;
+//     fold comparisons of verify_algebra_kernel;
 //   * verify_shared_f_paths_kernel (one-value leaves), one lane per (proof, statement) and blockIdx.y = (query, k): shared batches are few
 //     proofs of many statements, so the statement is on the lane.  Each lane checks the count of its own tuple before it walks L - ce_f levels;
 //   * verify_shared_row_paths_kernel (row leaves), one lane per proof and blockIdx.y = (query, row): the row's leaf is host_coset_leaf_hash
 //     with s = M bit for bit -- the coset leaf up to M = 8, streamed SHA-256 blocks or the field hash's chain from M = 16 on;
-//   * verify_shared_paths_kernel: the cp tuple and the group paths, the slots >= 3 of verify_cap_paths_kernel behind the nft f tuples;
+//   * verify_shared_paths_kernel: the cp tuple and the group paths, the slots >= 3 of verify_paths_kernel behind the nft f tuples;
 //   * verify_shared_transcript_kernel (strict), one lane per proof: the f commitment in one commit, 3M alphas, nft f tuples per query.  This
 //     chain is serial in the proof's length, which with one-value leaves grows with M q.
-// The order keys are query * keys + position in verify_proof's visiting order: 0 (-2), 1 + 3p + k (-(4 + k) for statement p; rows: 1 + k),
-// with one-value leaves nft + 1 (-7), then the G fold comparisons, then the group paths as for a folded (8 per group) or a coset proof (1 per
-// group); keys = nft + 2 + 9G, or nft + 1 + 2G with coset leaves (shared_key_to_check).  atomicMin makes the first failing tuple in wire order
-// the result whichever lane finishes first.  No scratch, no LDS, at most 116 VGPRs.
+// Its order keys are query * keys + position in verify_proof's visiting order: 0 (-2), 1 + 3p + k (-(4 + k) for statement p; rows: 1 + k),
+// with one-value leaves nft + 1 (-7), then the G fold comparisons, then the group paths (8 per group, or 1 with coset leaves);
+// keys = nft + 2 + 9G, or nft + 1 + 2G with coset leaves: at nft = 3 the keys of a plain proof (order_key_to_check).
+// No kernel uses scratch or LDS; at most 116 VGPRs.
 #include <cstdio>
 #include <cstring>
 #include <mutex>
@@ -92,8 +81,28 @@ __constant__ FieldHashConsts64 g_vfh_consts64;
 constexpr int32_t kNoFailure = 0x7f7f7f7f;   // the memset pattern of the per-proof key: above every order key
 constexpr uint32_t kVerifyThreads = 64;      // one wave per workgroup: the proofs of a batch spread over as many SIMDs as possible
 
-// Where the fields of a proof sit (in 32-bit words; every field of the wire format is 4-byte aligned and ProofFormat::data_len is a
-// multiple of 4), for the fixed layout.
+// Where the fields of a proof sit, in 32-bit words (every field of the wire format is 4-byte aligned and ProofFormat::data_len is a
+// multiple of 4), for the fixed layout: filled by verifier_chunk from ProofFormat.  Group j < G opens the tree over its input layer;
+// entry G of capw / capn is the tree over the last layer (D = 0), which nothing opens.
+constexpr uint32_t kLayoutTrees = 32;
+struct ProofLayout {
+    uint32_t fplen, fwords;     // an f path has L - ce_f digests; an f tuple 3 + 8 fplen words
+    uint32_t cpplen, cpwords;   // one-value leaves: the cp(x) tuple, a path into the tree of group 0
+    uint32_t fcapn, aw, ftw;    // words of f's cap (it starts the proof); header word of alpha0; of the free term / the coefficients
+    uint32_t bw[kLayoutTrees];     // header word of group j's beta
+    uint32_t capw[kLayoutTrees];   // header word of the cap of the tree over group j's input layer
+    uint32_t capn[kLayoutTrees];   // its words: 8 * 2^ce
+    uint32_t plen[kLayoutTrees];   // digests of a path into that tree: lg - ce
+    uint32_t gw[kLayoutTrees];     // first word of group j's opening, counted from the first word of the query
+    // shared proofs (ProofFormat::lb / rows; the kernels of a plain proof read none of these).  fwords is then the words of ONE f tuple,
+    // 3 + 8 fplen for a statement's value or 2^lb + 2 + 8 fplen for a row, and the cp tuple (coset: group 0) follows the nft f tuples
+    uint32_t nft;               // f tuples per query: 3 * 2^lb, or 3 rows (a plain proof: 3)
+    uint32_t fshare;            // words of one statement's share of the f commitment: 8 * 2^ce_f (rows: unused, one cap for all)
+    uint32_t lb;                // log2 of the statements of a proof
+    uint32_t keys;              // order keys per query (order_key_to_check): nft + 2 + 9G, or nft + 1 + 2G with coset leaves
+};
+
+// The launch arguments of every kernel: the buffers, the sizes and constants of the format, and the layout.
 struct VerifyArgs {
     const uint32_t* proofs;     // [count][words]
     const uint32_t* pub;        // [count] public_last (raw)
@@ -102,15 +111,16 @@ struct VerifyArgs {
     uint32_t* malformed;        // [count] 1: a path count differs from the fixed layout
     int32_t* tcode;             // [count] transcript result: 0, -(1000 + k), -1999
     uint32_t count, words, q, R, L, B, N;
-    uint32_t log_n, h, gm1, gm2, gm3, inv2;
+    uint32_t log_n, h, gm1, gm2, gm3;
     uint32_t gw;                // words of the grinding nonce after the free term: 0 or 2 (the query raws follow it)
     uint32_t gmask;             // grinding: the state after the nonce commit must have (word 0 & gmask) == 0
     uint32_t qbase;             // first word of query 0's openings
     uint32_t per_q;             // words of one query's openings
-    // folding factor 2^K (K > 1 only): G groups of K rounds, the last one of ls <= K; constants in Montgomery form
+    // folding factor 2^K: G groups of K rounds, the last one of ls <= K (K = 1: G = R groups of two values); constants in Montgomery form
     uint32_t K, G, ls;
     uint32_t inv2m, wm1, wm2, wm3;   // 1/2 and w, w^2, w^3 for w = the inverse of the primitive 8th root of unity h^(N/8)
-    uint32_t D;                 // early stop: 2^D coefficients at word 11 + 9G (R, G, ls are then those of the log_n - D folded rounds)
+    uint32_t D;                 // early stop: 2^D coefficients at a.t.ftw (R, G, ls are then those of the log_n - D folded rounds)
+    ProofLayout t;
 };
 
 __device__ __forceinline__ uint32_t be_word(const uint32_t* p) { return __builtin_bswap32(*p); }
@@ -130,34 +140,20 @@ __device__ __forceinline__ uint32_t dpow(uint32_t a, uint32_t e) {
 }
 __device__ __forceinline__ uint32_t dinv(uint32_t a) { return dpow(a, P - 2); }   // invmod: 0 -> 0, as on the host
 
-__device__ __forceinline__ uint32_t root_word(const VerifyArgs& a, uint32_t k) { return k == 0 ? 11u : 20u + 9u * (k - 1u); }
-__device__ __forceinline__ uint32_t layer_word(const VerifyArgs& a, uint32_t qk, uint32_t k) {
-    return a.qbase + qk * a.per_q + 4u * (3u + 8u * a.L) + 6u * k + 16u * (k * a.L - k * (k - 1u) / 2u);
-}
 __device__ __forceinline__ uint32_t query_tp(const VerifyArgs& a, const uint32_t* pr, uint32_t qk) {
     return pr[a.qbase - a.q + qk] % (a.N - 2u * a.B);                        // tp = test_raw % (N - 2B); the raws end at qbase
 }
 
-// Folded layout: the first word of group j's openings (s values, then s paths of a u64 count and L - jK digests).  Every group
-// before j is full, so the offset has a closed form.
-__device__ __forceinline__ uint32_t group_word(const VerifyArgs& a, uint32_t qk, uint32_t j) {
-    return a.qbase + qk * a.per_q + 4u * (3u + 8u * a.L) + ((3u * j + 8u * (a.L * j - a.K * (j * (j - 1u) / 2u))) << a.K);
-}
-__device__ __forceinline__ uint32_t group_size(const VerifyArgs& a, uint32_t j) { return 1u << (j + 1u < a.G ? a.K : a.ls); }
-// Coset leaves: the first word of group j's opening (s slots, a u64 count, L - jK - steps digests) after the three f tuples.  Every
-// group before j is full: 2^K + 2 + 8 (L - iK - K) words for i < j.
-__device__ __forceinline__ uint32_t coset_group_word(const VerifyArgs& a, uint32_t qk, uint32_t j) {
-    return a.qbase + qk * a.per_q + 3u * (3u + 8u * a.L) + j * ((1u << a.K) + 2u) + 8u * (j * (a.L - a.K) - a.K * (j * (j - 1u) / 2u));
-}
-// ... and the slot that holds value 0 of group j (the one at tp % len): rot = (tp % len) >> (log len - steps)
+__device__ __forceinline__ uint32_t group_steps(const VerifyArgs& a, uint32_t j) { return j + 1u < a.G ? a.K : a.ls; }
+// Coset leaves: the slot that holds value 0 of group j (the one at tp % len): rot = (tp % len) >> (log len - steps)
 __device__ __forceinline__ uint32_t coset_rot(const VerifyArgs& a, uint32_t tp, uint32_t j) {
-    const uint32_t lg = a.L - j * a.K, steps = j + 1u < a.G ? a.K : a.ls;
+    const uint32_t lg = a.L - j * a.K, steps = group_steps(a, j);
     return (tp & ((1u << lg) - 1u)) >> (lg - steps);
 }
 
 // proof.rs:63-77: the composition polynomial at x from f(x), f(gx), f(g^2 x), against the raw cp(x) of the proof: the value of
 // the fourth tuple, or, with coset leaves, slot rot0 of group 0's leaf, which starts where that tuple would
-// fb: words of an f tuple, aw: the header word of alpha0 (a root in front of it: 3 + 8 L and 8; a cap: CapLayout)
+// fb: words of an f tuple, aw: the header word of alpha0 (ProofLayout: fwords, aw)
 __device__ __forceinline__ bool cp0_matches_at(const VerifyArgs& a, const uint32_t* pr, uint32_t p, uint32_t fq, uint32_t x, uint32_t rot0, uint32_t fb, uint32_t aw) {
     const uint32_t f_x = pr[fq] % P, f_gx = pr[fq + fb] % P, f_ggx = pr[fq + 2u * fb] % P, cp_raw = pr[fq + 3u * fb + rot0];
     const uint32_t p0 = dmul(sub(f_x, 1u), dinv(sub(x, 1u)));
@@ -170,9 +166,6 @@ __device__ __forceinline__ bool cp0_matches_at(const VerifyArgs& a, const uint32
     const uint32_t cp0 = add(add(dmul(pr[aw] % P, p0), dmul(pr[aw + 1u] % P, p1)), dmul(pr[aw + 2u] % P, p2));
     return cp0 == cp_raw;
 }
-__device__ __forceinline__ bool cp0_matches(const VerifyArgs& a, const uint32_t* pr, uint32_t p, uint32_t fq, uint32_t x, uint32_t rot0 = 0u) {
-    return cp0_matches_at(a, pr, p, fq, x, rot0, 3u + 8u * a.L, 8u);
-}
 
 // Early stop: p(xs) for xs = x^(2^R'), the point of the stopped layer, by Horner from the highest of the 2^D coefficients; each is
 // reduced % P on reading (verify_proof does the same), the result is canonical.  xs goes to Montgomery form once, so a step is one
@@ -184,61 +177,6 @@ __device__ __forceinline__ uint32_t final_poly_from(const VerifyArgs& a, const u
     for (uint32_t k = 1u << a.D; k-- > 0u;) acc = add(mont_mul(acc, xm), c[k] % P);
     return acc;
 }
-__device__ __forceinline__ uint32_t final_poly_at(const VerifyArgs& a, const uint32_t* pr, uint32_t xs) {
-    return final_poly_from(a, pr + 11u + 9u * a.G, xs);
-}
-// ... for the grouped kernels, which carry only the inverse power of x: R' <= 29 squarings of x give the forward one
-__device__ __forceinline__ uint32_t final_poly_at_power(const VerifyArgs& a, const uint32_t* pr, uint32_t x) {
-    uint32_t xs = x;
-#pragma unroll 1
-    for (uint32_t i = 0; i < a.R; ++i) xs = dmul(xs, xs);
-    return final_poly_at(a, pr, xs);
-}
-
-// (1) layout + algebra: one lane per (proof, query).  Path counts, the cp0 relation (-2) and the R FRI relations (-(100 + k)).
-// STOP: the last relation is against p(x^(2^R)) (xk squared once more is that power), a canonical value.
-template <bool STOP>
-__device__ __forceinline__ void verify_algebra(const VerifyArgs& a) {
-    const uint64_t lane = (uint64_t)blockIdx.x * kVerifyThreads + threadIdx.x;
-    if (lane >= (uint64_t)a.count * a.q) return;
-    const uint32_t p = (uint32_t)(lane / a.q), qk = (uint32_t)(lane % a.q);
-    const uint32_t* pr = a.proofs + (size_t)p * a.words;
-    const uint32_t keys = 5u + 3u * a.R;
-    const uint32_t fq = a.qbase + qk * a.per_q;
-    bool ok = true;
-    for (uint32_t j = 0; j < 4; ++j) {
-        const uint32_t* c = pr + fq + j * (3u + 8u * a.L) + 1u;
-        ok = ok && c[0] == a.L && c[1] == 0u;
-    }
-    for (uint32_t k = 0; k < a.R; ++k) {
-        const uint32_t* c = pr + layer_word(a, qk, k) + 2u;
-        const uint32_t len = a.L - k;
-        ok = ok && c[0] == len && c[1] == 0u && c[2u + 8u * len] == len && c[3u + 8u * len] == 0u;
-    }
-    if (!ok) { a.malformed[p] = 1u; return; }
-
-    const uint32_t tp = query_tp(a, pr, qk);
-    const uint32_t x = dmul(GEN_W, dpow(a.h, tp));
-    int32_t key = kNoFailure;
-    if (!cp0_matches(a, pr, p, fq, x)) key = (int32_t)(qk * keys);
-    // proof.rs:101-126, the relations in k order: the first failing one is the smallest key of this lane
-    uint32_t xk = x;
-    for (uint32_t k = 0; k < a.R && key == kNoFailure; ++k) {
-        const uint32_t lw = layer_word(a, qk, k);
-        const uint32_t lx = pr[lw] % P, lnx = pr[lw + 1u] % P;
-        const uint32_t gx = dmul(add(lx, lnx), a.inv2);
-        const uint32_t hx = dmul(sub(lx, lnx), dinv(dmul(xk, 2u)));
-        const uint32_t calc = add(gx, dmul(pr[19u + 9u * k] % P, hx));   // betas[k + 1]
-        uint32_t expect;
-        if constexpr (STOP) expect = k + 1u < a.R ? pr[layer_word(a, qk, k + 1u)] : final_poly_at(a, pr, dmul(xk, xk));
-        else expect = k + 1u < a.R ? pr[layer_word(a, qk, k + 1u)] : pr[19u + 9u * a.R];
-        if (calc != expect) key = (int32_t)(qk * keys + 5u + k);
-        xk = dmul(xk, xk);
-    }
-    if (key != kNoFailure) atomicMin(&a.best[p], key);
-}
-__global__ void __launch_bounds__(kVerifyThreads) verify_algebra_kernel(VerifyArgs a) { verify_algebra<false>(a); }
-__global__ void __launch_bounds__(kVerifyThreads) verify_stop_algebra_kernel(VerifyArgs a) { verify_algebra<true>(a); }
 
 // STEPS successive reference folds (proof.rs:110-113) of the 2^STEPS values of one group, in registers: round k pairs t with
 // t + cnt and divides by twice the point of t, x^(2^(r0 + k)) om^(2^k t) for the 2^STEPS-th root of unity om.  ixk comes in as
@@ -268,95 +206,6 @@ __device__ __forceinline__ uint32_t fold_group(const VerifyArgs& a, const uint32
     return v[0];
 }
 
-// (1) for a folded proof: one lane per (proof, query).  Path counts, the cp0 relation (-2) and the G fold comparisons
-// (-(100 + j)); K is the folding factor of the full groups, the short last group (a.ls < K) has its own instance.
-// STOP: the last group's comparison is against p(x^(2^R)), a canonical value.
-template <int K, bool STOP = false>
-__global__ void __launch_bounds__(kVerifyThreads) verify_fold_algebra_kernel(VerifyArgs a) {
-    const uint64_t lane = (uint64_t)blockIdx.x * kVerifyThreads + threadIdx.x;
-    if (lane >= (uint64_t)a.count * a.q) return;
-    const uint32_t p = (uint32_t)(lane / a.q), qk = (uint32_t)(lane % a.q);
-    const uint32_t* pr = a.proofs + (size_t)p * a.words;
-    const uint32_t keys = 5u + 9u * a.G;
-    const uint32_t fq = a.qbase + qk * a.per_q;
-    bool ok = true;
-    for (uint32_t j = 0; j < 4; ++j) {
-        const uint32_t* c = pr + fq + j * (3u + 8u * a.L) + 1u;
-        ok = ok && c[0] == a.L && c[1] == 0u;
-    }
-    for (uint32_t j = 0; j < a.G; ++j) {
-        const uint32_t s = group_size(a, j), len = a.L - j * (uint32_t)K;
-        const uint32_t* c = pr + group_word(a, qk, j) + s;
-        for (uint32_t t = 0; t < s; ++t) ok = ok && c[t * (2u + 8u * len)] == len && c[t * (2u + 8u * len) + 1u] == 0u;
-    }
-    if (!ok) { a.malformed[p] = 1u; return; }
-
-    const uint32_t tp = query_tp(a, pr, qk);
-    const uint32_t x = dmul(GEN_W, dpow(a.h, tp));
-    int32_t key = kNoFailure;
-    if (!cp0_matches(a, pr, p, fq, x)) key = (int32_t)(qk * keys);
-    // proof.rs:101-126 widened, the groups in j order: the first failing one is the smallest key of this lane
-    uint32_t ixk = dinv(x);                               // x = 5 h^tp is never zero: the one inversion of this lane's folds
-#pragma unroll 1
-    for (uint32_t j = 0; j < a.G && key == kNoFailure; ++j) {
-        const uint32_t* vals = pr + group_word(a, qk, j);
-        const uint32_t beta = pr[19u + 9u * j] % P;
-        uint32_t calc;
-        if (j + 1u < a.G || a.ls == (uint32_t)K) calc = fold_group<K>(a, vals, beta, ixk);
-        else if (K == 3 && a.ls == 2u) calc = fold_group<2>(a, vals, beta, ixk);
-        else calc = fold_group<1>(a, vals, beta, ixk);
-        uint32_t expect;
-        if constexpr (STOP) expect = j + 1u < a.G ? pr[group_word(a, qk, j + 1u)] : final_poly_at_power(a, pr, x);
-        else expect = j + 1u < a.G ? pr[group_word(a, qk, j + 1u)] : pr[19u + 9u * a.G];
-        if (calc != expect) key = (int32_t)(qk * keys + 5u + j);
-    }
-    if (key != kNoFailure) atomicMin(&a.best[p], key);
-}
-
-// (1) with coset leaves: one lane per (proof, query).  The 3 + G path counts, the cp0 relation (-2) against value 0 of group 0 and
-// the G fold comparisons (-(100 + j)) against value 0 of the next group, both raw; the values come from the rotated slots.
-// STOP: the last group's comparison is against p(x^(2^R)), a canonical value.
-template <int K, bool STOP = false>
-__global__ void __launch_bounds__(kVerifyThreads) verify_coset_algebra_kernel(VerifyArgs a) {
-    const uint64_t lane = (uint64_t)blockIdx.x * kVerifyThreads + threadIdx.x;
-    if (lane >= (uint64_t)a.count * a.q) return;
-    const uint32_t p = (uint32_t)(lane / a.q), qk = (uint32_t)(lane % a.q);
-    const uint32_t* pr = a.proofs + (size_t)p * a.words;
-    const uint32_t keys = 4u + 2u * a.G;
-    const uint32_t fq = a.qbase + qk * a.per_q;
-    bool ok = true;
-    for (uint32_t j = 0; j < 3; ++j) {
-        const uint32_t* c = pr + fq + j * (3u + 8u * a.L) + 1u;
-        ok = ok && c[0] == a.L && c[1] == 0u;
-    }
-    for (uint32_t j = 0; j < a.G; ++j) {
-        const uint32_t steps = j + 1u < a.G ? (uint32_t)K : a.ls;
-        const uint32_t* c = pr + coset_group_word(a, qk, j) + (1u << steps);
-        ok = ok && c[0] == a.L - j * (uint32_t)K - steps && c[1] == 0u;
-    }
-    if (!ok) { a.malformed[p] = 1u; return; }
-
-    const uint32_t tp = query_tp(a, pr, qk);
-    const uint32_t x = dmul(GEN_W, dpow(a.h, tp));
-    int32_t key = kNoFailure;
-    if (!cp0_matches(a, pr, p, fq, x, coset_rot(a, tp, 0u))) key = (int32_t)(qk * keys);
-    uint32_t ixk = dinv(x);                               // x = 5 h^tp is never zero: the one inversion of this lane's folds
-#pragma unroll 1
-    for (uint32_t j = 0; j < a.G && key == kNoFailure; ++j) {
-        const uint32_t* vals = pr + coset_group_word(a, qk, j);
-        const uint32_t beta = pr[19u + 9u * j] % P, rot = coset_rot(a, tp, j);
-        uint32_t calc;
-        if (j + 1u < a.G || a.ls == (uint32_t)K) calc = fold_group<K>(a, vals, beta, ixk, rot);
-        else if (K == 3 && a.ls == 2u) calc = fold_group<2>(a, vals, beta, ixk, rot);
-        else calc = fold_group<1>(a, vals, beta, ixk, rot);
-        uint32_t expect;
-        if constexpr (STOP) expect = j + 1u < a.G ? pr[coset_group_word(a, qk, j + 1u) + coset_rot(a, tp, j + 1u)] : final_poly_at_power(a, pr, x);
-        else expect = j + 1u < a.G ? pr[coset_group_word(a, qk, j + 1u) + coset_rot(a, tp, j + 1u)] : pr[19u + 9u * a.G];
-        if (calc != expect) key = (int32_t)(qk * keys + 4u + j);
-    }
-    if (key != kNoFailure) atomicMin(&a.best[p], key);
-}
-
 template <int HASH>
 __device__ __forceinline__ Digest vleaf(uint32_t v) {
     if constexpr (HASH == 0) return sha256_leaf(v);
@@ -366,64 +215,6 @@ template <int HASH>
 __device__ __forceinline__ Digest vinner(const Digest& l, const Digest& r) {
     if constexpr (HASH == 0) return sha256_inner(l, r);
     else return fieldhash_inner64(l, r, g_vfh_consts64);
-}
-
-// (2) paths: one lane per (proof, query, path slot).  blockIdx.y = query * (4 + 2R) + slot and the proof on the lane, so every
-// lane of a wave walks a path of the same length; left / right is a select per level (merkle.rs:82-110).
-// FOLD: 4 + sum s_j slots; slot 4 + (j << K) + t is path t of group j, against the root of that group's input layer.
-template <int HASH, bool FOLD>
-__global__ void __launch_bounds__(kVerifyThreads) verify_paths_kernel(VerifyArgs a) {
-    const uint32_t p = blockIdx.x * kVerifyThreads + threadIdx.x;
-    if (p >= a.count) return;
-    const uint32_t slots = FOLD ? 4u + ((a.G - 1u) << a.K) + (1u << a.ls) : 4u + 2u * a.R;
-    const uint32_t qk = blockIdx.y / slots, slot = blockIdx.y % slots;
-    const uint32_t* pr = a.proofs + (size_t)p * a.words;
-    const uint32_t tp = query_tp(a, pr, qk);
-    uint32_t val_w, path_w, plen, idx, rootw, pos;
-    if (slot < 4u) {                                      // f(x), f(gx), f(g^2 x) against the f root, cp(x) against the cp root
-        val_w = a.qbase + qk * a.per_q + slot * (3u + 8u * a.L);
-        path_w = val_w + 3u;
-        plen = a.L;
-        idx = tp + (slot < 3u ? slot * a.B : 0u);
-        rootw = slot < 3u ? 0u : 11u;
-        pos = 1u + slot;
-    } else if constexpr (FOLD) {                          // group j at (tp % size + t size / s) % size
-        const uint32_t j = (slot - 4u) >> a.K, t = (slot - 4u) & ((1u << a.K) - 1u);
-        const uint32_t s = group_size(a, j), gw = group_word(a, qk, j), size = a.N >> (j * a.K);
-        plen = a.L - j * a.K;
-        val_w = gw + t;
-        path_w = gw + s + t * (2u + 8u * plen) + 2u;
-        idx = (tp % size + t * (size / s)) % size;
-        rootw = root_word(a, j);
-        pos = 5u + a.G + 8u * j + t;
-    } else {                                              // layer k at x and at -x
-        const uint32_t k = (slot - 4u) / 2u, which = (slot - 4u) & 1u;
-        const uint32_t lw = layer_word(a, qk, k), size = a.N >> k;
-        plen = a.L - k;
-        val_w = lw + which;
-        path_w = lw + 4u + which * (2u + 8u * plen);
-        idx = which ? (tp + size / 2u) % size : tp % size;
-        rootw = root_word(a, k);
-        pos = 5u + a.R + 2u * k + which;
-    }
-    Digest cur = vleaf<HASH>(pr[val_w]);
-    uint32_t node = idx + (1u << plen) - 1u;              // heap index, < 2^31
-    for (uint32_t lvl = 0; lvl < plen; ++lvl) {
-        Digest sib;
-        const uint32_t* s = pr + path_w + 8u * lvl;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) sib.w[i] = be_word(s + i);
-        const bool right = (node & 1u) == 0u;             // an even heap index is a right child
-        Digest l, r;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) { l.w[i] = right ? sib.w[i] : cur.w[i]; r.w[i] = right ? cur.w[i] : sib.w[i]; }
-        cur = vinner<HASH>(l, r);
-        node = (node - (right ? 2u : 1u)) >> 1;
-    }
-    bool same = true;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) same = same && cur.w[i] == be_word(pr + rootw + i);
-    if (!same) atomicMin(&a.best[p], (int32_t)(qk * (FOLD ? 5u + 9u * a.G : 5u + 3u * a.R) + pos));
 }
 
 // The digest of a leaf of s = 1, 2, 4 or 8 slot words, bit for bit host_coset_leaf_hash (transcript.hpp) and coset_leaf_digest
@@ -462,57 +253,6 @@ __device__ __forceinline__ Digest coset_vleaf(const uint32_t* slots, uint32_t s)
     return d;
 }
 
-// (2) with coset leaves: one lane per (proof, query, path slot).  blockIdx.y = query * (3 + G) + slot and the proof on the lane, so
-// every lane of a wave walks a path of the same length from a leaf of the same width.  Slots 0..2: f(x), f(gx), f(g^2 x), one-value
-// leaves against the f root; slot 3 + j: the leaf of group j from its s_j slot words in slot order (not rotated), leaf index
-// tp % (len / s), L - jK - steps digests, against the root of that group's input layer.
-template <int HASH>
-__global__ void __launch_bounds__(kVerifyThreads) verify_coset_paths_kernel(VerifyArgs a) {
-    const uint32_t p = blockIdx.x * kVerifyThreads + threadIdx.x;
-    if (p >= a.count) return;
-    const uint32_t slots = 3u + a.G;
-    const uint32_t qk = blockIdx.y / slots, slot = blockIdx.y % slots;
-    const uint32_t* pr = a.proofs + (size_t)p * a.words;
-    const uint32_t tp = query_tp(a, pr, qk);
-    uint32_t val_w, path_w, plen, idx, rootw, pos, s;
-    if (slot < 3u) {
-        val_w = a.qbase + qk * a.per_q + slot * (3u + 8u * a.L);
-        path_w = val_w + 3u;
-        plen = a.L;
-        idx = tp + slot * a.B;
-        rootw = 0u;
-        pos = 1u + slot;
-        s = 1u;
-    } else {
-        const uint32_t j = slot - 3u, steps = j + 1u < a.G ? a.K : a.ls;
-        s = 1u << steps;
-        val_w = coset_group_word(a, qk, j);
-        path_w = val_w + s + 2u;
-        plen = a.L - j * a.K - steps;                     // >= log_b >= 1
-        idx = tp & ((1u << plen) - 1u);
-        rootw = root_word(a, j);
-        pos = 4u + a.G + j;
-    }
-    Digest cur = coset_vleaf<HASH>(pr + val_w, s);
-    uint32_t node = idx + (1u << plen) - 1u;              // heap index, < 2^31
-    for (uint32_t lvl = 0; lvl < plen; ++lvl) {
-        Digest sib;
-        const uint32_t* sp = pr + path_w + 8u * lvl;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) sib.w[i] = be_word(sp + i);
-        const bool right = (node & 1u) == 0u;             // an even heap index is a right child
-        Digest l, r;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) { l.w[i] = right ? sib.w[i] : cur.w[i]; r.w[i] = right ? cur.w[i] : sib.w[i]; }
-        cur = vinner<HASH>(l, r);
-        node = (node - (right ? 2u : 1u)) >> 1;
-    }
-    bool same = true;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) same = same && cur.w[i] == be_word(pr + rootw + i);
-    if (!same) atomicMin(&a.best[p], (int32_t)(qk * (4u + 2u * a.G) + pos));
-}
-
 // SHA-256(state || data[0 .. nw)) into state (channel.rs:19-26), streamed over sha256_compress.  nw is the same for every lane,
 // so the lanes of a wave stay in lockstep; data words are read little-endian and swapped to message order.
 __device__ __forceinline__ void commit_words(uint32_t (&st)[8], const uint32_t* data, uint32_t nw) {
@@ -539,96 +279,12 @@ __device__ __forceinline__ void commit_words(uint32_t (&st)[8], const uint32_t* 
     for (int i = 0; i < 8; ++i) st[i] = hs[i];
 }
 
-// (3) transcript (strict only): one lane per proof, the commits of verify_transcript in its order.  The order is a schedule of
-// steps the same for every lane (a challenge, or a commit of nw words), walked by one loop with one commit site: the
-// compression is inlined once and the state stays in registers.  FOLD (verify_transcript with fold > 1): G (beta, root) pairs, and per
-// query one commit per group of its s_j values and paths.  COSET (with FOLD, any K): three f tuples per query, and a group's commit is
-// its s_j slots, one count and one path of L - jK - steps_j digests.  STOP: the last of the R betas has no root after it, and the step
-// of the free term commits the 2^D coefficients, so that step (ft) and everything after it come one step earlier.
-template <bool FOLD, bool COSET = false, bool STOP = false>
-__global__ void __launch_bounds__(kVerifyThreads) verify_transcript_kernel(VerifyArgs a) {
-    static_assert(FOLD || !COSET, "the coset instance reads the group fields");
-    constexpr uint32_t NF = COSET ? 3u : 4u;              // f tuples per query
-    const uint32_t p = blockIdx.x * kVerifyThreads + threadIdx.x;
-    if (p >= a.count) return;
-    const uint32_t* pr = a.proofs + (size_t)p * a.words;
-    uint32_t st[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) st[i] = 0u;
-    const uint32_t R = FOLD ? a.G : a.R, L = a.L, q = a.q;   // R: the (beta, root) pairs = the layer commits of a query
-    // steps: f root | 3 alphas | cp root | R x (beta, layer root) | free term | [nonce] | q query raws | q x (NF f paths, R layer pairs)
-    // STOP:  f root | 3 alphas | cp root | (R - 1) x (beta, layer root) | beta | 2^D coefficients | [nonce] | q query raws | the same
-    const uint32_t gs = a.gw ? 1u : 0u;                   // the nonce step: a commit of 2 words, then the zero-bit test (-1998)
-    const uint32_t ft = (STOP ? 4u : 5u) + 2u * R;        // the step of the free term, or of the coefficients
-    const uint32_t head = ft + 1u + gs + q;
-    const uint32_t steps = head + q * (NF + R);
-    uint32_t cur = 0, k = 0;
-    int32_t code = 0;
-    for (uint32_t s = 0; s < steps; ++s) {
-        bool chal;
-        uint32_t nw;
-        if (s < head) {
-            chal = (s >= 1u && s <= 3u) || (s >= 5u && s < ft && ((s - 5u) & 1u) == 0u) || s >= ft + 1u + gs;
-            nw = chal ? 1u : (s == ft ? (STOP ? 1u << a.D : 1u) : (gs && s == ft + 1u) ? 2u : 8u);
-        } else {
-            const uint32_t t = (s - head) % (NF + R);
-            chal = false;
-            if constexpr (COSET) {
-                const uint32_t j = t - 3u, gsteps = t - 2u < R ? a.K : a.ls;   // t >= 3: group j, the last one short
-                nw = t < 3u ? 3u + 8u * L : (1u << gsteps) + 2u + 8u * (L - j * a.K - gsteps);
-            } else if constexpr (FOLD) nw = t < 4u ? 3u + 8u * L : (3u + 8u * (L - (t - 4u) * a.K)) << (t - 3u < R ? a.K : a.ls);
-            else nw = t < 4u ? 3u + 8u * L : 6u + 16u * (L - (t - 4u));
-        }
-        if (chal) {                                       // state word 0 (big-endian bytes 0..3) against the little-endian u32 here
-            ++k;
-            if (st[0] != pr[cur]) { code = -(int32_t)(1000u + k); break; }
-        }
-        commit_words(st, pr + cur, nw);
-        cur += nw;
-        if (gs && s == ft + 1u && (st[0] & a.gmask) != 0u) { code = -1998; break; }   // SHA-256(S || le64(w)) is the new state
-    }
-    if (code == 0) {
-        bool same = true;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) same = same && st[i] == be_word(a.states + (size_t)p * 8u + i);
-        if (!same) code = -1999;
-    }
-    a.tcode[p] = code;
-}
-
-// ---- Merkle caps (the file header) ---------------------------------------------------------------------------------------------
-// The layout of a capped proof, in 32-bit words.  Group j < G opens the tree over its input layer; entry G of capw / capn is the tree over
-// the last layer (D = 0), which nothing opens.  a.K, a.G, a.ls describe the groups as for a folded proof, K = 1 included.
-constexpr uint32_t kCapTrees = 32;
-struct CapLayout {
-    uint32_t fplen, fwords;     // an f path has L - ce_f digests; an f tuple 3 + 8 fplen words
-    uint32_t cpplen, cpwords;   // one-value leaves: the cp(x) tuple, a path into the tree of group 0
-    uint32_t fcapn, aw, ftw;    // words of f's cap (it starts the proof); header word of alpha0; of the free term / the coefficients
-    uint32_t bw[kCapTrees];     // header word of group j's beta
-    uint32_t capw[kCapTrees];   // header word of the cap of the tree over group j's input layer
-    uint32_t capn[kCapTrees];   // its words: 8 * 2^ce
-    uint32_t plen[kCapTrees];   // digests of a path into that tree: lg - ce
-    uint32_t gw[kCapTrees];     // first word of group j's opening, counted from the first word of the query
-    // shared proofs (ProofFormat::lb / rows; the kernels of a plain proof read none of these).  fwords is then the words of ONE f tuple,
-    // 3 + 8 fplen for a statement's value or 2^lb + 2 + 8 fplen for a row, and the cp tuple (coset: group 0) follows the nft f tuples
-    uint32_t nft;               // f tuples per query: 3 * 2^lb, or 3 rows
-    uint32_t fshare;            // words of one statement's share of the f commitment: 8 * 2^ce_f (rows: unused, one cap for all)
-    uint32_t lb;                // log2 of the statements of a proof
-    uint32_t keys;              // order keys per query (shared_key_to_check): nft + 2 + 9G, or nft + 1 + 2G with coset leaves
-};
-struct VerifyCapArgs {
-    VerifyArgs a;
-    CapLayout t;
-};
-
-__device__ __forceinline__ uint32_t cap_group_steps(const VerifyArgs& a, uint32_t j) { return j + 1u < a.G ? a.K : a.ls; }
-
-// (1) with caps: one lane per (proof, query).  Path counts, the cp0 relation (-2) and the G fold comparisons (-(100 + j)), for every K
-// (the steps of a group select the unrolled fold) and D (a.D != 0: the last comparison is against p(x^(2^R))).
+// ---- plain proofs (the file header) --------------------------------------------------------------------------------------------
+// (1) layout + algebra: one lane per (proof, query).  Path counts, the cp0 relation (-2) and the G fold comparisons (-(100 + j)), for every K
+// (the steps of a group select the unrolled fold) and D (a.D != 0: the last comparison is against p(x^(2^R)), a canonical value).  With
+// coset leaves the values come from the rotated slots, and cp(x) is value 0 of group 0.
 template <bool COSET>
-__global__ void __launch_bounds__(kVerifyThreads) verify_cap_algebra_kernel(VerifyCapArgs ca) {
-    const VerifyArgs& a = ca.a;
-    const CapLayout& t = ca.t;
+__global__ void __launch_bounds__(kVerifyThreads) verify_algebra_kernel(VerifyArgs a) {
     const uint64_t lane = (uint64_t)blockIdx.x * kVerifyThreads + threadIdx.x;
     if (lane >= (uint64_t)a.count * a.q) return;
     const uint32_t p = (uint32_t)(lane / a.q), qk = (uint32_t)(lane % a.q);
@@ -637,17 +293,17 @@ __global__ void __launch_bounds__(kVerifyThreads) verify_cap_algebra_kernel(Veri
     const uint32_t fq = a.qbase + qk * a.per_q;
     bool ok = true;
     for (uint32_t j = 0; j < 3; ++j) {
-        const uint32_t* c = pr + fq + j * t.fwords + 1u;
-        ok = ok && c[0] == t.fplen && c[1] == 0u;
+        const uint32_t* c = pr + fq + j * a.t.fwords + 1u;
+        ok = ok && c[0] == a.t.fplen && c[1] == 0u;
     }
     if constexpr (!COSET) {
-        const uint32_t* c = pr + fq + 3u * t.fwords + 1u;
-        ok = ok && c[0] == t.cpplen && c[1] == 0u;
+        const uint32_t* c = pr + fq + 3u * a.t.fwords + 1u;
+        ok = ok && c[0] == a.t.cpplen && c[1] == 0u;
     }
 #pragma unroll 1
     for (uint32_t j = 0; j < a.G; ++j) {
-        const uint32_t s = 1u << cap_group_steps(a, j), len = t.plen[j];
-        const uint32_t* c = pr + fq + t.gw[j] + s;
+        const uint32_t s = 1u << group_steps(a, j), len = a.t.plen[j];
+        const uint32_t* c = pr + fq + a.t.gw[j] + s;
         if constexpr (COSET) ok = ok && c[0] == len && c[1] == 0u;
         else for (uint32_t u = 0; u < s; ++u) ok = ok && c[u * (2u + 8u * len)] == len && c[u * (2u + 8u * len) + 1u] == 0u;
     }
@@ -656,43 +312,43 @@ __global__ void __launch_bounds__(kVerifyThreads) verify_cap_algebra_kernel(Veri
     const uint32_t tp = query_tp(a, pr, qk);
     const uint32_t x = dmul(GEN_W, dpow(a.h, tp));
     int32_t key = kNoFailure;
-    if (!cp0_matches_at(a, pr, p, fq, x, COSET ? coset_rot(a, tp, 0u) : 0u, t.fwords, t.aw)) key = (int32_t)(qk * keys);
+    if (!cp0_matches_at(a, pr, p, fq, x, COSET ? coset_rot(a, tp, 0u) : 0u, a.t.fwords, a.t.aw)) key = (int32_t)(qk * keys);
     uint32_t ixk = dinv(x);                               // x = 5 h^tp is never zero: the one inversion of this lane's folds
 #pragma unroll 1
     for (uint32_t j = 0; j < a.G && key == kNoFailure; ++j) {
-        const uint32_t* vals = pr + fq + t.gw[j];
-        const uint32_t beta = pr[t.bw[j]] % P, rot = COSET ? coset_rot(a, tp, j) : 0u, steps = cap_group_steps(a, j);
+        const uint32_t* vals = pr + fq + a.t.gw[j];
+        const uint32_t beta = pr[a.t.bw[j]] % P, rot = COSET ? coset_rot(a, tp, j) : 0u, steps = group_steps(a, j);
         uint32_t calc;
         if (steps == 3u) calc = fold_group<3>(a, vals, beta, ixk, rot);
         else if (steps == 2u) calc = fold_group<2>(a, vals, beta, ixk, rot);
         else calc = fold_group<1>(a, vals, beta, ixk, rot);
         uint32_t expect;
-        if (j + 1u < a.G) expect = pr[fq + t.gw[j + 1u] + (COSET ? coset_rot(a, tp, j + 1u) : 0u)];
+        if (j + 1u < a.G) expect = pr[fq + a.t.gw[j + 1u] + (COSET ? coset_rot(a, tp, j + 1u) : 0u)];
         else if (a.D) {
             uint32_t xs = x;
 #pragma unroll 1
             for (uint32_t i = 0; i < a.R; ++i) xs = dmul(xs, xs);
-            expect = final_poly_from(a, pr + t.ftw, xs);
-        } else expect = pr[t.ftw];
+            expect = final_poly_from(a, pr + a.t.ftw, xs);
+        } else expect = pr[a.t.ftw];
         if (calc != expect) key = (int32_t)(qk * keys + first + j);
     }
     if (key != kNoFailure) atomicMin(&a.best[p], key);
 }
 
-// (2) with caps: one lane per (proof, query, path slot), the slots of verify_paths_kernel<.., FOLD> (4 + sum s_j) or of
-// verify_coset_paths_kernel (3 + G).  A path climbs plen = lg - ce levels from the leaf's position inside the sub-tree of its cap entry
-// and is compared with entry idx >> plen of the tree's cap.  plen depends on the slot alone: uniform over the wave.
+// (2) paths: one lane per (proof, query, path slot).  blockIdx.y = query * slots + slot and the proof on the lane, so every lane of a wave
+// walks a path of the same length from a leaf of the same width; left / right is a select per level (merkle.rs:82-110).  One-value leaves:
+// 4 + sum s_j slots, f(x), f(gx), f(g^2 x), cp(x), then slot 4 + (j << K) + u = path u of group j.  Coset leaves: 3 + G slots, the three
+// f values, then slot 3 + j = the leaf of group j from its s_j slot words in slot order (not rotated).  A path climbs plen = lg - ce levels
+// from the leaf's position inside the sub-tree of its cap entry and is compared with entry idx >> plen of the tree's cap (ce = 0: the root).
 // SHARED (a shared proof, below): the f tuples have kernels of their own, so the slots start at 3 (blockIdx.y counts from there), the
-// cp tuple and the groups follow the nft f tuples, and the order keys are the shared ones (shared_key_to_check).
+// cp tuple and the groups follow the nft f tuples, and the order keys are the shared ones (order_key_to_check).
 template <int HASH, bool COSET, bool SHARED>
-__device__ __forceinline__ void verify_cap_paths(const VerifyCapArgs& ca) {
-    const VerifyArgs& a = ca.a;
-    const CapLayout& t = ca.t;
+__device__ __forceinline__ void verify_paths(const VerifyArgs& a) {
     const uint32_t p = blockIdx.x * kVerifyThreads + threadIdx.x;
     if (p >= a.count) return;
     const uint32_t slots = (COSET ? 3u + a.G : 4u + ((a.G - 1u) << a.K) + (1u << a.ls)) - (SHARED ? 3u : 0u);
     const uint32_t qk = blockIdx.y / slots, slot = blockIdx.y % slots + (SHARED ? 3u : 0u);
-    const uint32_t nft = SHARED ? t.nft : 3u;
+    const uint32_t nft = SHARED ? a.t.nft : 3u;
     // where the keys of the fold comparisons start: after -2, the f tuples and (one-value leaves) cp(x)
     const uint32_t first = SHARED ? nft + (COSET ? 1u : 2u) : COSET ? 4u : 5u;
     const uint32_t* pr = a.proofs + (size_t)p * a.words;
@@ -700,36 +356,36 @@ __device__ __forceinline__ void verify_cap_paths(const VerifyCapArgs& ca) {
     const uint32_t fq = a.qbase + qk * a.per_q;
     uint32_t val_w, path_w, plen, idx, capw, pos, s = 1u;
     if (slot < 3u) {                                      // f(x), f(gx), f(g^2 x) against f's cap
-        val_w = fq + slot * t.fwords;
+        val_w = fq + slot * a.t.fwords;
         path_w = val_w + 3u;
-        plen = t.fplen;
+        plen = a.t.fplen;
         idx = tp + slot * a.B;
         capw = 0u;
         pos = 1u + slot;
     } else if (!COSET && slot == 3u) {                    // cp(x) against the cap of group 0's tree
-        val_w = fq + nft * t.fwords;
+        val_w = fq + nft * a.t.fwords;
         path_w = val_w + 3u;
-        plen = t.cpplen;
+        plen = a.t.cpplen;
         idx = tp;
-        capw = t.capw[0];
+        capw = a.t.capw[0];
         pos = first - 1u;
     } else if constexpr (COSET) {                         // the leaf of group j from its s_j slot words
-        const uint32_t j = slot - 3u, steps = cap_group_steps(a, j);
+        const uint32_t j = slot - 3u, steps = group_steps(a, j);
         s = 1u << steps;
-        val_w = fq + t.gw[j];
+        val_w = fq + a.t.gw[j];
         path_w = val_w + s + 2u;
-        plen = t.plen[j];
+        plen = a.t.plen[j];
         idx = tp & ((1u << (a.L - j * a.K - steps)) - 1u);
-        capw = t.capw[j];
+        capw = a.t.capw[j];
         pos = first + a.G + j;
     } else {                                              // value u of group j at (tp % size + u size / s) % size
         const uint32_t j = (slot - 4u) >> a.K, u = (slot - 4u) & ((1u << a.K) - 1u);
-        const uint32_t gs = 1u << cap_group_steps(a, j), gw = fq + t.gw[j], size = a.N >> (j * a.K);
-        plen = t.plen[j];
+        const uint32_t gs = 1u << group_steps(a, j), gw = fq + a.t.gw[j], size = a.N >> (j * a.K);
+        plen = a.t.plen[j];
         val_w = gw + u;
         path_w = gw + gs + u * (2u + 8u * plen) + 2u;
         idx = (tp % size + u * (size / gs)) % size;
-        capw = t.capw[j];
+        capw = a.t.capw[j];
         pos = first + a.G + 8u * j + u;
     }
     Digest cur;
@@ -755,16 +411,16 @@ __device__ __forceinline__ void verify_cap_paths(const VerifyCapArgs& ca) {
     if (!same) atomicMin(&a.best[p], (int32_t)(qk * (first + (COSET ? 2u : 9u) * a.G) + pos));
 }
 template <int HASH, bool COSET>
-__global__ void __launch_bounds__(kVerifyThreads) verify_cap_paths_kernel(VerifyCapArgs ca) { verify_cap_paths<HASH, COSET, false>(ca); }
+__global__ void __launch_bounds__(kVerifyThreads) verify_paths_kernel(VerifyArgs a) { verify_paths<HASH, COSET, false>(a); }
 
-// (3) with caps (strict only): one lane per proof, the schedule of verify_transcript_kernel with every root commit widened to the cap's
-// words and every tuple shortened to its paths' digests; D != 0 drops the last root and commits the 2^D coefficients where the free term was.
+// (3) transcript (strict only): one lane per proof, the commits of verify_transcript in its order.  The order is a schedule of steps the
+// same for every lane (a challenge, or a commit of nw words), walked by one loop with one commit site: the compression is inlined once and
+// the state stays in registers.  A tree's commit is the 8 * 2^ce words of its cap, a tuple's its values, counts and paths' digests; D != 0
+// drops the last tree and commits the 2^D coefficients where the free term was.
 // SHARED (a shared proof, below): na = 3 * 2^lb alphas after the f commitment, and nft f tuples (rows: 3) in front of a query's cp tuple.
 template <bool COSET, bool SHARED>
-__device__ __forceinline__ void verify_cap_transcript(const VerifyCapArgs& ca) {
-    const VerifyArgs& a = ca.a;
-    const CapLayout& t = ca.t;
-    const uint32_t na = SHARED ? 3u << t.lb : 3u, nft = SHARED ? t.nft : 3u;
+__device__ __forceinline__ void replay_transcript(const VerifyArgs& a) {
+    const uint32_t na = SHARED ? 3u << a.t.lb : 3u, nft = SHARED ? a.t.nft : 3u;
     const uint32_t NF = nft + (COSET ? 0u : 1u);          // f tuples per query, cp(x) included
     const uint32_t p = blockIdx.x * kVerifyThreads + threadIdx.x;
     if (p >= a.count) return;
@@ -787,16 +443,16 @@ __device__ __forceinline__ void verify_cap_transcript(const VerifyCapArgs& ca) {
         if (s < head) {
             chal = (s >= 1u && s <= na) || (s >= na + 2u && s < ft && ((s - na - 2u) & 1u) == 0u) || s >= ft + 1u + gs;
             if (chal) nw = 1u;
-            else if (s == 0u) nw = t.fcapn;
-            else if (s < ft) nw = t.capn[(s - na - 1u) >> 1];   // s = na + 1: the tree of group 0; s = na + 3 + 2j: of group j + 1 (the last layer's: entry G)
+            else if (s == 0u) nw = a.t.fcapn;
+            else if (s < ft) nw = a.t.capn[(s - na - 1u) >> 1];   // s = na + 1: the tree of group 0; s = na + 3 + 2j: of group j + 1 (the last layer's: entry G)
             else nw = s == ft ? 1u << a.D : 2u;           // D = 0: the free term, one word
         } else {
             const uint32_t u = (s - head) % (NF + R);
-            if (u < nft) nw = t.fwords;
-            else if (!COSET && u == nft) nw = t.cpwords;
+            if (u < nft) nw = a.t.fwords;
+            else if (!COSET && u == nft) nw = a.t.cpwords;
             else {
-                const uint32_t j = u - NF, gsteps = cap_group_steps(a, j);
-                nw = COSET ? (1u << gsteps) + 2u + 8u * t.plen[j] : (3u + 8u * t.plen[j]) << gsteps;
+                const uint32_t j = u - NF, gsteps = group_steps(a, j);
+                nw = COSET ? (1u << gsteps) + 2u + 8u * a.t.plen[j] : (3u + 8u * a.t.plen[j]) << gsteps;
             }
         }
         if (chal) {                                       // state word 0 (big-endian bytes 0..3) against the little-endian u32 here
@@ -816,45 +472,41 @@ __device__ __forceinline__ void verify_cap_transcript(const VerifyCapArgs& ca) {
     a.tcode[p] = code;
 }
 template <bool COSET>
-__global__ void __launch_bounds__(kVerifyThreads) verify_cap_transcript_kernel(VerifyCapArgs ca) { verify_cap_transcript<COSET, false>(ca); }
+__global__ void __launch_bounds__(kVerifyThreads) verify_transcript_kernel(VerifyArgs a) { replay_transcript<COSET, false>(a); }
 
 // ---- shared proofs (the file header) ---------------------------------------------------------------------------------------------
 // The order keys of a shared proof, per query (verify_proof's visiting order): 0 (-2), 1 + 3p + k (the path of statement p's f(g^k x),
-// -(4 + k); rows: 1 + k, the path of row k), then with one-value leaves nft + 1 (-7), then the G fold comparisons and the group paths as
-// for a folded (9G keys) or a coset proof (2G keys).
-__device__ __forceinline__ uint32_t shared_first(const CapLayout& t, bool coset) { return t.nft + (coset ? 1u : 2u); }   // the key of group 0's fold
-__device__ __forceinline__ uint32_t shared_keys(const VerifyArgs& a, const CapLayout& t, bool coset) {
-    return shared_first(t, coset) + (coset ? 2u : 9u) * a.G;
-}
+// -(4 + k); rows: 1 + k, the path of row k), then with one-value leaves nft + 1 (-7), then the G fold comparisons and the group paths
+// (one-value leaves: 9G keys; coset leaves: 2G keys).
+__device__ __forceinline__ uint32_t shared_first(const VerifyArgs& a, bool coset) { return a.t.nft + (coset ? 1u : 2u); }   // the key of group 0's fold
+__device__ __forceinline__ uint32_t shared_keys(const VerifyArgs& a, bool coset) { return shared_first(a, coset) + (coset ? 2u : 9u) * a.G; }
 
 // (1) of a shared proof: one lane per (proof, query).  The path counts of the cp tuple and the groups, and with rows those of the three
 // rows (the plain f tuples check their own: verify_shared_f_paths_kernel); the -2 relation summed over the 2^lb statements; the G fold
-// comparisons of verify_cap_algebra_kernel.  The denominators of -2 depend on x alone: the sums of alpha_i times numerator_i over the
+// comparisons of verify_algebra_kernel.  The denominators of -2 depend on x alone: the sums of alpha_i times numerator_i over the
 // statements are kept Montgomery-scaled (one mont_mul per term) and meet the three inverses, scaled the other way, once at the end.  All
 // residues are canonical, so the sum equals verify_proof's bit for bit.
 template <bool COSET, bool ROWS>
-__global__ void __launch_bounds__(kVerifyThreads) verify_shared_algebra_kernel(VerifyCapArgs ca) {
-    const VerifyArgs& a = ca.a;
-    const CapLayout& t = ca.t;
+__global__ void __launch_bounds__(kVerifyThreads) verify_shared_algebra_kernel(VerifyArgs a) {
     const uint64_t lane = (uint64_t)blockIdx.x * kVerifyThreads + threadIdx.x;
     if (lane >= (uint64_t)a.count * a.q) return;
     const uint32_t p = (uint32_t)(lane / a.q), qk = (uint32_t)(lane % a.q);
     const uint32_t* pr = a.proofs + (size_t)p * a.words;
-    const uint32_t M = 1u << t.lb;
-    const uint32_t keys = shared_keys(a, t, COSET), first = shared_first(t, COSET);
-    const uint32_t fq = a.qbase + qk * a.per_q, cpw = fq + t.nft * t.fwords;   // cpw: the cp tuple, or group 0's leaf
+    const uint32_t M = 1u << a.t.lb;
+    const uint32_t keys = shared_keys(a, COSET), first = shared_first(a, COSET);
+    const uint32_t fq = a.qbase + qk * a.per_q, cpw = fq + a.t.nft * a.t.fwords;   // cpw: the cp tuple, or group 0's leaf
     bool ok = true;
     if constexpr (ROWS) {
         for (uint32_t k = 0; k < 3; ++k) {
-            const uint32_t* c = pr + fq + k * t.fwords + M;
-            ok = ok && c[0] == t.fplen && c[1] == 0u;
+            const uint32_t* c = pr + fq + k * a.t.fwords + M;
+            ok = ok && c[0] == a.t.fplen && c[1] == 0u;
         }
     }
-    if constexpr (!COSET) ok = ok && pr[cpw + 1u] == t.cpplen && pr[cpw + 2u] == 0u;
+    if constexpr (!COSET) ok = ok && pr[cpw + 1u] == a.t.cpplen && pr[cpw + 2u] == 0u;
 #pragma unroll 1
     for (uint32_t j = 0; j < a.G; ++j) {
-        const uint32_t s = 1u << cap_group_steps(a, j), len = t.plen[j];
-        const uint32_t* c = pr + fq + t.gw[j] + s;
+        const uint32_t s = 1u << group_steps(a, j), len = a.t.plen[j];
+        const uint32_t* c = pr + fq + a.t.gw[j] + s;
         if constexpr (COSET) ok = ok && c[0] == len && c[1] == 0u;
         else for (uint32_t u = 0; u < s; ++u) ok = ok && c[u * (2u + 8u * len)] == len && c[u * (2u + 8u * len) + 1u] == 0u;
     }
@@ -871,12 +523,12 @@ __global__ void __launch_bounds__(kVerifyThreads) verify_shared_algebra_kernel(V
         const uint32_t i0 = mont_mul(mont_mul(dinv(sub(x, 1u)), R2), R2), i1 = mont_mul(mont_mul(dinv(sub(x, a.gm2)), R2), R2);
         const uint32_t i2 = mont_mul(mont_mul(dinv(den), R2), R2);
         const uint32_t* pub = a.pub + (size_t)p * M;
-        const uint32_t fstep = ROWS ? 1u : 3u * t.fwords, kstep = t.fwords;   // from statement to statement, from f(g^k x) to f(g^(k+1) x)
+        const uint32_t fstep = ROWS ? 1u : 3u * a.t.fwords, kstep = a.t.fwords;   // from statement to statement, from f(g^k x) to f(g^(k+1) x)
         uint32_t s0 = 0u, s1 = 0u, s2 = 0u;
 #pragma unroll 2
         for (uint32_t s = 0; s < M; ++s) {
             const uint32_t* fv = pr + fq + s * fstep;
-            const uint32_t* al = pr + t.aw + 3u * s;
+            const uint32_t* al = pr + a.t.aw + 3u * s;
             const uint32_t f_x = fv[0] % P, f_gx = fv[kstep] % P, f_ggx = fv[2u * kstep] % P;
             const uint32_t num = sub(sub(f_ggx, dmul(f_gx, f_gx)), dmul(f_x, f_x));
             s0 = add(s0, mont_mul(al[0] % P, sub(f_x, 1u)));
@@ -889,27 +541,27 @@ __global__ void __launch_bounds__(kVerifyThreads) verify_shared_algebra_kernel(V
     uint32_t ixk = dinv(x);                               // x = 5 h^tp is never zero: the one inversion of this lane's folds
 #pragma unroll 1
     for (uint32_t j = 0; j < a.G && key == kNoFailure; ++j) {
-        const uint32_t* vals = pr + fq + t.gw[j];
-        const uint32_t beta = pr[t.bw[j]] % P, rot = COSET ? coset_rot(a, tp, j) : 0u, steps = cap_group_steps(a, j);
+        const uint32_t* vals = pr + fq + a.t.gw[j];
+        const uint32_t beta = pr[a.t.bw[j]] % P, rot = COSET ? coset_rot(a, tp, j) : 0u, steps = group_steps(a, j);
         uint32_t calc;
         if (steps == 3u) calc = fold_group<3>(a, vals, beta, ixk, rot);
         else if (steps == 2u) calc = fold_group<2>(a, vals, beta, ixk, rot);
         else calc = fold_group<1>(a, vals, beta, ixk, rot);
         uint32_t expect;
-        if (j + 1u < a.G) expect = pr[fq + t.gw[j + 1u] + (COSET ? coset_rot(a, tp, j + 1u) : 0u)];
+        if (j + 1u < a.G) expect = pr[fq + a.t.gw[j + 1u] + (COSET ? coset_rot(a, tp, j + 1u) : 0u)];
         else if (a.D) {
             uint32_t xs = x;
 #pragma unroll 1
             for (uint32_t i = 0; i < a.R; ++i) xs = dmul(xs, xs);
-            expect = final_poly_from(a, pr + t.ftw, xs);
-        } else expect = pr[t.ftw];
+            expect = final_poly_from(a, pr + a.t.ftw, xs);
+        } else expect = pr[a.t.ftw];
         if (calc != expect) key = (int32_t)(qk * keys + first + j);
     }
     if (key != kNoFailure) atomicMin(&a.best[p], key);
 }
 
 // One path of one-value or coset / row leaves from digest `cur` of leaf idx: plen levels up inside the sub-tree of its cap entry, then
-// the comparison with entry idx >> plen of the cap at `cap` (the walk of verify_cap_paths).
+// the comparison with entry idx >> plen of the cap at `cap` (the walk of verify_paths).
 template <int HASH>
 __device__ __forceinline__ bool path_misses(Digest cur, const uint32_t* path, uint32_t plen, uint32_t idx, const uint32_t* cap) {
     uint32_t node = (idx & ((1u << plen) - 1u)) + (1u << plen) - 1u;   // heap index inside the sub-tree of the cap entry
@@ -937,19 +589,17 @@ __device__ __forceinline__ bool path_misses(Digest cur, const uint32_t* path, ui
 // L - ce_f levels.  Tuple 3p + k of the query holds f_p(g^k x); its path lands in statement p's share of the f commitment.  Each lane
 // checks the u64 count of its own tuple (the algebra kernel does not) before it walks.
 template <int HASH>
-__global__ void __launch_bounds__(kVerifyThreads) verify_shared_f_paths_kernel(VerifyCapArgs ca) {
-    const VerifyArgs& a = ca.a;
-    const CapLayout& t = ca.t;
+__global__ void __launch_bounds__(kVerifyThreads) verify_shared_f_paths_kernel(VerifyArgs a) {
     const uint64_t lane = (uint64_t)blockIdx.x * kVerifyThreads + threadIdx.x;
-    if (lane >= ((uint64_t)a.count << t.lb)) return;
-    const uint32_t p = (uint32_t)(lane >> t.lb), st = (uint32_t)lane & ((1u << t.lb) - 1u);
+    if (lane >= ((uint64_t)a.count << a.t.lb)) return;
+    const uint32_t p = (uint32_t)(lane >> a.t.lb), st = (uint32_t)lane & ((1u << a.t.lb) - 1u);
     const uint32_t qk = blockIdx.y / 3u, k = blockIdx.y % 3u;
     const uint32_t* pr = a.proofs + (size_t)p * a.words;
-    const uint32_t* tup = pr + a.qbase + qk * a.per_q + (3u * st + k) * t.fwords;
-    if (tup[1] != t.fplen || tup[2] != 0u) { a.malformed[p] = 1u; return; }
+    const uint32_t* tup = pr + a.qbase + qk * a.per_q + (3u * st + k) * a.t.fwords;
+    if (tup[1] != a.t.fplen || tup[2] != 0u) { a.malformed[p] = 1u; return; }
     const uint32_t idx = query_tp(a, pr, qk) + k * a.B;
-    if (path_misses<HASH>(vleaf<HASH>(tup[0]), tup + 3u, t.fplen, idx, pr + st * t.fshare))
-        atomicMin(&a.best[p], (int32_t)(qk * t.keys + 1u + 3u * st + k));
+    if (path_misses<HASH>(vleaf<HASH>(tup[0]), tup + 3u, a.t.fplen, idx, pr + st * a.t.fshare))
+        atomicMin(&a.best[p], (int32_t)(qk * a.t.keys + 1u + 3u * st + k));
 }
 
 // The digest of a row of M = 2^lb values, bit for bit host_coset_leaf_hash (transcript.hpp), raw words >= P included.  M <= 8: the coset
@@ -1022,27 +672,25 @@ __device__ __forceinline__ bool row_path_misses(const uint32_t* pr, uint32_t row
 // The second launch bound asks for five waves per SIMD, the occupancy of the other field-hash paths kernels (88 VGPRs): without it the
 // sixteen S-boxes of the leaf chain's full rounds are interleaved up to 130 VGPRs.
 template <int HASH>
-__global__ void __launch_bounds__(kVerifyThreads, 5) verify_shared_row_paths_kernel(VerifyCapArgs ca) {
-    const VerifyArgs& a = ca.a;
-    const CapLayout& t = ca.t;
+__global__ void __launch_bounds__(kVerifyThreads, 5) verify_shared_row_paths_kernel(VerifyArgs a) {
     const uint32_t p = blockIdx.x * kVerifyThreads + threadIdx.x;
     if (p >= a.count) return;
-    const uint32_t qk = blockIdx.y / 3u, k = blockIdx.y % 3u, M = 1u << t.lb;
+    const uint32_t qk = blockIdx.y / 3u, k = blockIdx.y % 3u, M = 1u << a.t.lb;
     const uint32_t* pr = a.proofs + (size_t)p * a.words;
     const uint32_t idx = query_tp(a, pr, qk) + k * a.B;
-    if (row_path_misses<HASH>(pr, a.qbase + qk * a.per_q + k * t.fwords, M, t.fplen, idx))
-        atomicMin(&a.best[p], (int32_t)(qk * t.keys + 1u + k));
+    if (row_path_misses<HASH>(pr, a.qbase + qk * a.per_q + k * a.t.fwords, M, a.t.fplen, idx))
+        atomicMin(&a.best[p], (int32_t)(qk * a.t.keys + 1u + k));
 }
 
-// (2c) the cp tuple and the group paths of a shared proof: the slots >= 3 of verify_cap_paths_kernel, behind the nft f tuples.
+// (2c) the cp tuple and the group paths of a shared proof: the slots >= 3 of verify_paths_kernel, behind the nft f tuples.
 template <int HASH, bool COSET>
-__global__ void __launch_bounds__(kVerifyThreads) verify_shared_paths_kernel(VerifyCapArgs ca) { verify_cap_paths<HASH, COSET, true>(ca); }
+__global__ void __launch_bounds__(kVerifyThreads) verify_shared_paths_kernel(VerifyArgs a) { verify_paths<HASH, COSET, true>(a); }
 
 // (3) of a shared proof (strict only): one lane per proof; the f commitment is one commit of all its words, 3 * 2^lb alphas follow it,
 // and a query commits its nft f tuples one by one.  The chain is serial in the proof's length: with one-value leaves that is 3 * 2^lb
 // tuples per query.
 template <bool COSET>
-__global__ void __launch_bounds__(kVerifyThreads) verify_shared_transcript_kernel(VerifyCapArgs ca) { verify_cap_transcript<COSET, true>(ca); }
+__global__ void __launch_bounds__(kVerifyThreads) verify_shared_transcript_kernel(VerifyArgs a) { replay_transcript<COSET, true>(a); }
 
 std::mutex g_consts_mu;
 bool g_consts_done[64] = {false};
@@ -1062,34 +710,9 @@ hipError_t ensure_verify_consts() {
     return e;
 }
 
-// An order key -> the check number verify_proof returns for it.
-int32_t key_to_check(int32_t key, uint32_t R) {
-    const uint32_t pos = (uint32_t)key % (5u + 3u * R);
-    if (pos == 0) return -2;
-    if (pos < 5) return -(int32_t)(3u + pos);             // -4 .. -7
-    if (pos < 5 + R) return -(int32_t)(100u + (pos - 5u));
-    const uint32_t j = pos - 5u - R;
-    return -(int32_t)((j & 1u ? 400u : 300u) + j / 2u);
-}
-// The same for the keys of a folded proof (G groups): verify_proof's number with fold > 1.
-int32_t fold_key_to_check(int32_t key, uint32_t G) {
-    const uint32_t pos = (uint32_t)key % (5u + 9u * G);
-    if (pos == 0) return -2;
-    if (pos < 5) return -(int32_t)(3u + pos);             // -4 .. -7
-    if (pos < 5 + G) return -(int32_t)(100u + (pos - 5u));
-    const uint32_t j = (pos - 5u - G) / 8u, t = (pos - 5u - G) % 8u;
-    return -(int32_t)((t ? 400u : 300u) + j);
-}
-// The same for the keys of a proof with coset leaves: one fold comparison and one path per group.
-int32_t coset_key_to_check(int32_t key, uint32_t G) {
-    const uint32_t pos = (uint32_t)key % (4u + 2u * G);
-    if (pos == 0) return -2;
-    if (pos < 4) return -(int32_t)(3u + pos);             // -4 .. -6
-    if (pos < 4 + G) return -(int32_t)(100u + (pos - 4u));
-    return -(int32_t)(300u + (pos - 4u - G));
-}
-// The same for the keys of a shared proof: nft f tuples per query (3 per statement, or 3 rows) in front of the cp tuple and the groups.
-int32_t shared_key_to_check(int32_t key, uint32_t nft, uint32_t G, bool coset) {
+// An order key -> the check number verify_proof returns for it: nft f tuples per query (a plain proof: 3; a shared one: 3 per statement,
+// or 3 rows) in front of the cp tuple and the groups.
+int32_t order_key_to_check(int32_t key, uint32_t nft, uint32_t G, bool coset) {
     const uint32_t first = nft + (coset ? 1u : 2u), pos = (uint32_t)key % (first + (coset ? 2u : 9u) * G);
     if (pos == 0) return -2;
     if (pos <= nft) return -(int32_t)(4u + (pos - 1u) % 3u);   // -4 .. -6 of statement (pos - 1) / 3, or of row pos - 1
@@ -1166,45 +789,43 @@ int verifier_chunk(zk_verifier* v, const uint8_t* proofs, size_t stride, size_t 
     a.B = 1u << log_b; a.N = 1u << L; a.log_n = log_n;
     a.h = root_of_unity(L);
     const uint32_t g = root_of_unity(log_n);
-    a.gm1 = invmod(g); a.gm2 = mulmod(a.gm1, a.gm1); a.gm3 = mulmod(a.gm2, a.gm1); a.inv2 = invmod(2);
+    a.gm1 = invmod(g); a.gm2 = mulmod(a.gm1, a.gm1); a.gm3 = mulmod(a.gm2, a.gm1);
     a.gw = f.grind ? 2u : 0u;
     a.gmask = f.grind ? ~0u << (32u - f.grind) : 0u;
     a.D = D;
     a.K = K; a.G = G; a.ls = f.steps(G - 1u);
-    // Where the fields sit, in words, from one pass over the header and one over a query (transcript.hpp); the kernels without caps
-    // take only qbase and per_q from it and know the rest in closed form, the cap kernels read all of it (CapLayout)
-    if (G + 1u > kCapTrees) return fail(ZK_ERR_STATE, "zk_verifier_run: more than %u trees", kCapTrees);
-    CapLayout t{};
+    // Where the fields sit, in words, from one pass over the header and one over a query (transcript.hpp): ProofLayout
+    if (G + 1u > kLayoutTrees) return fail(ZK_ERR_STATE, "zk_verifier_run: more than %u trees", kLayoutTrees);
     uint32_t w = 0;
     f.for_each_head([&](ProofFormat::Head what, uint32_t j, size_t bytes) {
         switch (what) {
-            case ProofFormat::kFTree: t.fcapn = (uint32_t)(bytes / 4); break;
-            case ProofFormat::kAlphas: t.aw = w; break;
-            case ProofFormat::kTree: t.capw[j] = w; t.capn[j] = (uint32_t)(bytes / 4); break;
-            case ProofFormat::kBeta: t.bw[j] = w; break;
-            case ProofFormat::kFinal: t.ftw = w; break;
+            case ProofFormat::kFTree: a.t.fcapn = (uint32_t)(bytes / 4); break;
+            case ProofFormat::kAlphas: a.t.aw = w; break;
+            case ProofFormat::kTree: a.t.capw[j] = w; a.t.capn[j] = (uint32_t)(bytes / 4); break;
+            case ProofFormat::kBeta: a.t.bw[j] = w; break;
+            case ProofFormat::kFinal: a.t.ftw = w; break;
             case ProofFormat::kNonce: case ProofFormat::kRaws: break;
         }
         w += (uint32_t)(bytes / 4);
         return true;
     });
     a.qbase = w;
-    t.fplen = (uint32_t)f.f_path();
-    t.fwords = (uint32_t)(Channel::group_bytes(f.rows ? (size_t)1 << f.lb : 1, t.fplen, f.rows) / 4);   // 3 + 8 fplen, or a row's 2^lb + 2 + 8 fplen
-    t.cpplen = (uint32_t)f.tree_path(0); t.cpwords = 3u + 8u * t.cpplen;
-    t.lb = f.lb; t.nft = f.rows ? 3u : 3u << f.lb; t.fshare = f.rows ? 0u : 8u << f.f_cap();
-    t.keys = t.nft + (coset ? 1u + 2u * G : 2u + 9u * G);
-    const uint32_t nf = t.nft + (coset ? 0u : 1u);         // the tuples in front of group 0: the f tuples and, with one-value leaves, cp(x)
+    a.t.fplen = (uint32_t)f.f_path();
+    a.t.fwords = (uint32_t)(Channel::group_bytes(f.rows ? (size_t)1 << f.lb : 1, a.t.fplen, f.rows) / 4);   // 3 + 8 fplen, or a row's 2^lb + 2 + 8 fplen
+    a.t.cpplen = (uint32_t)f.tree_path(0); a.t.cpwords = 3u + 8u * a.t.cpplen;
+    a.t.lb = f.lb; a.t.nft = f.rows ? 3u : 3u << f.lb; a.t.fshare = f.rows ? 0u : 8u << f.f_cap();
+    a.t.keys = a.t.nft + (coset ? 1u + 2u * G : 2u + 9u * G);
+    const uint32_t nf = a.t.nft + (coset ? 0u : 1u);         // the tuples in front of group 0: the f tuples and, with one-value leaves, cp(x)
     uint32_t tuple = 0, off = 0;
     f.for_each_tuple([&](size_t s, size_t plen, bool one_leaf) {
-        if (tuple >= nf) { t.plen[tuple - nf] = (uint32_t)plen; t.gw[tuple - nf] = off; }
+        if (tuple >= nf) { a.t.plen[tuple - nf] = (uint32_t)plen; a.t.gw[tuple - nf] = off; }
         off += (uint32_t)(Channel::group_bytes(s, plen, one_leaf) / 4);
         ++tuple;
     });
     a.per_q = off;
     if (a.qbase + (size_t)q * a.per_q != len / 4) return fail(ZK_ERR_STATE, "zk_verifier_run: the layout does not add up to the proof length");
     const uint32_t w8 = invmod(powmod(a.h, (uint64_t)a.N >> 3));
-    a.inv2m = to_mont(a.inv2); a.wm1 = to_mont(w8); a.wm2 = to_mont(mulmod(w8, w8)); a.wm3 = to_mont(mulmod(mulmod(w8, w8), w8));
+    a.inv2m = to_mont(invmod(2)); a.wm1 = to_mont(w8); a.wm2 = to_mont(mulmod(w8, w8)); a.wm3 = to_mont(mulmod(mulmod(w8, w8), w8));
 
     HIPCHK(hipMemcpyAsync(d, hp, count * len, hipMemcpyHostToDevice, v->stream));
     HIPCHK(hipMemcpyAsync(d_pub, hp + count * len, count * pub, hipMemcpyHostToDevice, v->stream));
@@ -1213,23 +834,14 @@ int verifier_chunk(zk_verifier* v, const uint8_t* proofs, size_t stride, size_t 
     HIPCHK(hipMemsetAsync(a.malformed, 0, count * 4, v->stream));
     HIPCHK(hipMemsetAsync(a.tcode, 0, count * 4, v->stream));
     const uint32_t gx = (uint32_t)((count + kVerifyThreads - 1) / kVerifyThreads);
-    const VerifyCapArgs ca{a, t};
     if (states) {                                      // the transcript chains run beside the paths: cost = max of the two
         HIPCHK(hipEventRecord(v->ev_in, v->stream));
         HIPCHK(hipStreamWaitEvent(v->tstream, v->ev_in, 0));
-        if (shared) {                                  // a shared proof takes the table whatever its cap
-            if (coset) hipLaunchKernelGGL(verify_shared_transcript_kernel<true>, dim3(gx), dim3(kVerifyThreads), 0, v->tstream, ca);
-            else hipLaunchKernelGGL(verify_shared_transcript_kernel<false>, dim3(gx), dim3(kVerifyThreads), 0, v->tstream, ca);
-        } else if (v->fmt.cap) {
-            if (coset) hipLaunchKernelGGL(verify_cap_transcript_kernel<true>, dim3(gx), dim3(kVerifyThreads), 0, v->tstream, ca);
-            else hipLaunchKernelGGL(verify_cap_transcript_kernel<false>, dim3(gx), dim3(kVerifyThreads), 0, v->tstream, ca);
-        } else if (D) {
-            if (coset) hipLaunchKernelGGL((verify_transcript_kernel<true, true, true>), dim3(gx), dim3(kVerifyThreads), 0, v->tstream, a);
-            else if (K == 1) hipLaunchKernelGGL((verify_transcript_kernel<false, false, true>), dim3(gx), dim3(kVerifyThreads), 0, v->tstream, a);
-            else hipLaunchKernelGGL((verify_transcript_kernel<true, false, true>), dim3(gx), dim3(kVerifyThreads), 0, v->tstream, a);
-        } else if (coset) hipLaunchKernelGGL((verify_transcript_kernel<true, true>), dim3(gx), dim3(kVerifyThreads), 0, v->tstream, a);
-        else if (K == 1) hipLaunchKernelGGL(verify_transcript_kernel<false>, dim3(gx), dim3(kVerifyThreads), 0, v->tstream, a);
-        else hipLaunchKernelGGL(verify_transcript_kernel<true>, dim3(gx), dim3(kVerifyThreads), 0, v->tstream, a);
+        if (shared) {
+            if (coset) hipLaunchKernelGGL(verify_shared_transcript_kernel<true>, dim3(gx), dim3(kVerifyThreads), 0, v->tstream, a);
+            else hipLaunchKernelGGL(verify_shared_transcript_kernel<false>, dim3(gx), dim3(kVerifyThreads), 0, v->tstream, a);
+        } else if (coset) hipLaunchKernelGGL(verify_transcript_kernel<true>, dim3(gx), dim3(kVerifyThreads), 0, v->tstream, a);
+        else hipLaunchKernelGGL(verify_transcript_kernel<false>, dim3(gx), dim3(kVerifyThreads), 0, v->tstream, a);
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(v->ev_t, v->tstream));
     }
@@ -1237,67 +849,39 @@ int verifier_chunk(zk_verifier* v, const uint8_t* proofs, size_t stride, size_t 
     const dim3 agrid((uint32_t)((lanes + kVerifyThreads - 1) / kVerifyThreads));
     if (shared) {
         if (coset) {
-            if (f.rows) hipLaunchKernelGGL((verify_shared_algebra_kernel<true, true>), agrid, dim3(kVerifyThreads), 0, v->stream, ca);
-            else hipLaunchKernelGGL((verify_shared_algebra_kernel<true, false>), agrid, dim3(kVerifyThreads), 0, v->stream, ca);
-        } else if (f.rows) hipLaunchKernelGGL((verify_shared_algebra_kernel<false, true>), agrid, dim3(kVerifyThreads), 0, v->stream, ca);
-        else hipLaunchKernelGGL((verify_shared_algebra_kernel<false, false>), agrid, dim3(kVerifyThreads), 0, v->stream, ca);
-    } else if (v->fmt.cap) {                               // one instance per leaf format covers every K and D
-        if (coset) hipLaunchKernelGGL(verify_cap_algebra_kernel<true>, agrid, dim3(kVerifyThreads), 0, v->stream, ca);
-        else hipLaunchKernelGGL(verify_cap_algebra_kernel<false>, agrid, dim3(kVerifyThreads), 0, v->stream, ca);
-    } else if (D) {                                           // the STOP instances: the last group against the final polynomial
-        if (coset) {
-            if (K == 1) hipLaunchKernelGGL((verify_coset_algebra_kernel<1, true>), agrid, dim3(kVerifyThreads), 0, v->stream, a);
-            else if (K == 2) hipLaunchKernelGGL((verify_coset_algebra_kernel<2, true>), agrid, dim3(kVerifyThreads), 0, v->stream, a);
-            else hipLaunchKernelGGL((verify_coset_algebra_kernel<3, true>), agrid, dim3(kVerifyThreads), 0, v->stream, a);
-        } else if (K == 1) hipLaunchKernelGGL(verify_stop_algebra_kernel, agrid, dim3(kVerifyThreads), 0, v->stream, a);
-        else if (K == 2) hipLaunchKernelGGL((verify_fold_algebra_kernel<2, true>), agrid, dim3(kVerifyThreads), 0, v->stream, a);
-        else hipLaunchKernelGGL((verify_fold_algebra_kernel<3, true>), agrid, dim3(kVerifyThreads), 0, v->stream, a);
-    } else if (coset) {
-        if (K == 1) hipLaunchKernelGGL(verify_coset_algebra_kernel<1>, agrid, dim3(kVerifyThreads), 0, v->stream, a);
-        else if (K == 2) hipLaunchKernelGGL(verify_coset_algebra_kernel<2>, agrid, dim3(kVerifyThreads), 0, v->stream, a);
-        else hipLaunchKernelGGL(verify_coset_algebra_kernel<3>, agrid, dim3(kVerifyThreads), 0, v->stream, a);
-    } else if (K == 1) hipLaunchKernelGGL(verify_algebra_kernel, agrid, dim3(kVerifyThreads), 0, v->stream, a);
-    else if (K == 2) hipLaunchKernelGGL(verify_fold_algebra_kernel<2>, agrid, dim3(kVerifyThreads), 0, v->stream, a);
-    else hipLaunchKernelGGL(verify_fold_algebra_kernel<3>, agrid, dim3(kVerifyThreads), 0, v->stream, a);
+            if (f.rows) hipLaunchKernelGGL((verify_shared_algebra_kernel<true, true>), agrid, dim3(kVerifyThreads), 0, v->stream, a);
+            else hipLaunchKernelGGL((verify_shared_algebra_kernel<true, false>), agrid, dim3(kVerifyThreads), 0, v->stream, a);
+        } else if (f.rows) hipLaunchKernelGGL((verify_shared_algebra_kernel<false, true>), agrid, dim3(kVerifyThreads), 0, v->stream, a);
+        else hipLaunchKernelGGL((verify_shared_algebra_kernel<false, false>), agrid, dim3(kVerifyThreads), 0, v->stream, a);
+    } else if (coset) hipLaunchKernelGGL(verify_algebra_kernel<true>, agrid, dim3(kVerifyThreads), 0, v->stream, a);   // one instance per leaf format covers every K and D
+    else hipLaunchKernelGGL(verify_algebra_kernel<false>, agrid, dim3(kVerifyThreads), 0, v->stream, a);
     HIPCHK(hipGetLastError());
     const bool sha = v->hash == ZK_HASH_SHA256;
     if (shared) {
         // the f tuples: three rows per query with the proof on the lane, or 3 * 2^lb tuples with the (proof, statement) on the lane
         if (f.rows) {
             const dim3 fgrid(gx, 3u * q);
-            if (sha) hipLaunchKernelGGL(verify_shared_row_paths_kernel<0>, fgrid, dim3(kVerifyThreads), 0, v->stream, ca);
-            else hipLaunchKernelGGL(verify_shared_row_paths_kernel<1>, fgrid, dim3(kVerifyThreads), 0, v->stream, ca);
+            if (sha) hipLaunchKernelGGL(verify_shared_row_paths_kernel<0>, fgrid, dim3(kVerifyThreads), 0, v->stream, a);
+            else hipLaunchKernelGGL(verify_shared_row_paths_kernel<1>, fgrid, dim3(kVerifyThreads), 0, v->stream, a);
         } else {
             const dim3 fgrid((uint32_t)((((uint64_t)count << f.lb) + kVerifyThreads - 1) / kVerifyThreads), 3u * q);
-            if (sha) hipLaunchKernelGGL(verify_shared_f_paths_kernel<0>, fgrid, dim3(kVerifyThreads), 0, v->stream, ca);
-            else hipLaunchKernelGGL(verify_shared_f_paths_kernel<1>, fgrid, dim3(kVerifyThreads), 0, v->stream, ca);
+            if (sha) hipLaunchKernelGGL(verify_shared_f_paths_kernel<0>, fgrid, dim3(kVerifyThreads), 0, v->stream, a);
+            else hipLaunchKernelGGL(verify_shared_f_paths_kernel<1>, fgrid, dim3(kVerifyThreads), 0, v->stream, a);
         }
         HIPCHK(hipGetLastError());
         const dim3 pgrid(gx, q * (coset ? G : 1u + ((G - 1u) << K) + (1u << a.ls)));   // the cp tuple and the groups
         if (coset) {
-            if (sha) hipLaunchKernelGGL((verify_shared_paths_kernel<0, true>), pgrid, dim3(kVerifyThreads), 0, v->stream, ca);
-            else hipLaunchKernelGGL((verify_shared_paths_kernel<1, true>), pgrid, dim3(kVerifyThreads), 0, v->stream, ca);
-        } else if (sha) hipLaunchKernelGGL((verify_shared_paths_kernel<0, false>), pgrid, dim3(kVerifyThreads), 0, v->stream, ca);
-        else hipLaunchKernelGGL((verify_shared_paths_kernel<1, false>), pgrid, dim3(kVerifyThreads), 0, v->stream, ca);
-    } else if (v->fmt.cap) {
+            if (sha) hipLaunchKernelGGL((verify_shared_paths_kernel<0, true>), pgrid, dim3(kVerifyThreads), 0, v->stream, a);
+            else hipLaunchKernelGGL((verify_shared_paths_kernel<1, true>), pgrid, dim3(kVerifyThreads), 0, v->stream, a);
+        } else if (sha) hipLaunchKernelGGL((verify_shared_paths_kernel<0, false>), pgrid, dim3(kVerifyThreads), 0, v->stream, a);
+        else hipLaunchKernelGGL((verify_shared_paths_kernel<1, false>), pgrid, dim3(kVerifyThreads), 0, v->stream, a);
+    } else {
         const dim3 pgrid(gx, q * (coset ? 3u + G : 4u + ((G - 1u) << K) + (1u << a.ls)));
         if (coset) {
-            if (sha) hipLaunchKernelGGL((verify_cap_paths_kernel<0, true>), pgrid, dim3(kVerifyThreads), 0, v->stream, ca);
-            else hipLaunchKernelGGL((verify_cap_paths_kernel<1, true>), pgrid, dim3(kVerifyThreads), 0, v->stream, ca);
-        } else if (sha) hipLaunchKernelGGL((verify_cap_paths_kernel<0, false>), pgrid, dim3(kVerifyThreads), 0, v->stream, ca);
-        else hipLaunchKernelGGL((verify_cap_paths_kernel<1, false>), pgrid, dim3(kVerifyThreads), 0, v->stream, ca);
-    } else if (coset) {
-        const dim3 pgrid(gx, q * (3u + G));
-        if (sha) hipLaunchKernelGGL(verify_coset_paths_kernel<0>, pgrid, dim3(kVerifyThreads), 0, v->stream, a);
-        else hipLaunchKernelGGL(verify_coset_paths_kernel<1>, pgrid, dim3(kVerifyThreads), 0, v->stream, a);
-    } else if (K == 1) {
-        const dim3 pgrid(gx, q * (4u + 2u * R));
-        if (sha) hipLaunchKernelGGL((verify_paths_kernel<0, false>), pgrid, dim3(kVerifyThreads), 0, v->stream, a);
+            if (sha) hipLaunchKernelGGL((verify_paths_kernel<0, true>), pgrid, dim3(kVerifyThreads), 0, v->stream, a);
+            else hipLaunchKernelGGL((verify_paths_kernel<1, true>), pgrid, dim3(kVerifyThreads), 0, v->stream, a);
+        } else if (sha) hipLaunchKernelGGL((verify_paths_kernel<0, false>), pgrid, dim3(kVerifyThreads), 0, v->stream, a);
         else hipLaunchKernelGGL((verify_paths_kernel<1, false>), pgrid, dim3(kVerifyThreads), 0, v->stream, a);
-    } else {
-        const dim3 pgrid(gx, q * (4u + ((G - 1u) << K) + (1u << a.ls)));
-        if (sha) hipLaunchKernelGGL((verify_paths_kernel<0, true>), pgrid, dim3(kVerifyThreads), 0, v->stream, a);
-        else hipLaunchKernelGGL((verify_paths_kernel<1, true>), pgrid, dim3(kVerifyThreads), 0, v->stream, a);
     }
     HIPCHK(hipGetLastError());
     if (states) HIPCHK(hipStreamWaitEvent(v->stream, v->ev_t, 0));
@@ -1314,8 +898,7 @@ int verifier_chunk(zk_verifier* v, const uint8_t* proofs, size_t stride, size_t 
         else if (malformed[i])                             // garbage only
             c = verify_proof(proofs + i * stride, len, f, public_last + (i << f.lb), v->hash);
         else if (best[i] == kNoFailure) c = 0;
-        else if (shared) c = shared_key_to_check(best[i], t.nft, G, coset);
-        else c = coset ? coset_key_to_check(best[i], G) : (K == 1 && !v->fmt.cap) ? key_to_check(best[i], R) : fold_key_to_check(best[i], G);
+        else c = order_key_to_check(best[i], a.t.nft, G, coset);
         checks_out[i] = c;
     }
     return ZK_OK;
