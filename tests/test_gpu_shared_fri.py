@@ -35,6 +35,7 @@ def _same(got, ref, lib, s):
 #   (2,1,1)      N = 8: one value per thread, B = 2
 #   (4,1,*)      B = 2: the windows of two vectors, four values per thread
 #   (5,2,3)      B = 4: whole vectors; a wave of the f build spans statements
+#   (5,2,2) g 12 the nonce is searched on the device (above kGrindHostMaxBits = 10) with one job
 #   (7,2,2) c 8  the caps clamp on the small FRI trees, the f level is 2^10 digests through the mailbox
 #   (7,2,4) c 8  the f level is 2^12 digests through the post kernel
 #   (6,2,8)      256 statements
@@ -47,6 +48,7 @@ CASES = [
     ((4, 1, 3, 3, False, 0, 3, 1, 0, 1), (None,)),
     ((4, 1, 3, 1, True, 0, 0, 16, 0, 0), (None,)),
     ((5, 2, 3, 1, False, 0, 0, 1, 8, 0), (None,)),
+    ((5, 2, 2, 1, False, 0, 0, 1, 12, 0), (None,)),
     ((5, 2, 3, 3, True, 2, 3, 3, 0, 1), (None,)),
     ((5, 2, 3, 2, False, 2, 8, 2, 0, 0), (1, 0)),
     ((7, 2, 2, 1, False, 0, 8, 2, 0, 0), (1, 0)),
@@ -69,7 +71,7 @@ CASES = [
 def test_every_setting_appears():
     col = list(zip(*[s for s, _ in CASES]))
     assert set(col[3]) == {1, 2, 3} and set(col[4]) == {False, True} and set(col[5]) == {0, 2} and set(col[6]) == {0, 3, 8}
-    assert {1, 16} <= set(col[7]) and set(col[8]) == {0, 8} and set(col[9]) == {0, 1}
+    assert {1, 16} <= set(col[7]) and set(col[8]) == {0, 8, 12} and set(col[9]) == {0, 1}
     assert {lv for _, levels in CASES for lv in levels} == {None, 0, 1}
 
 

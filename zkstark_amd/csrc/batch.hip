@@ -7,6 +7,11 @@
 // draws its own challenges (host threads), and the next launch reads them from a per-proof table.
 // One loop over the groups of `fold` rounds serves every folding factor (K = 1: one round per group, fold fused into the leaf
 // hashing); the openings and their encoding are transcript.hpp's for_each_opening and Channel::commit_group.
+// ONE pipeline makes every proof (struct Run and run_commit_f, run_groups, run_queries, run_decommit below): a run has a number of
+// channels and the widths of its two stages, log2 of the trees a launch builds side by side.  zk_batch_prove is the run with 2^lb channels
+// at width lb; a shared proof (zk_batch_prove_shared: one proof over the sum of the batch's compositions) is the run with ONE channel whose
+// FRI stage has width 0 and whose f stage has width lb, or 0 with row leaves.  The entry points differ in how tree 0 is committed, how the
+// alphas are drawn and how cp is made, and in nothing after that: a new format setting is written into the pipeline once.
 // Coset leaves (zk_batch_set_coset_leaves): the tree over a group's input layer has one leaf per opened coset, so proof p's tree over
 // len values has m = len / s leaves and the batch heap batch * m; cp is composed by its own launch, every K folds with the batched
 // multi-fold, and the trees come from launch_merkle_build_coset_batch -- prove_resident / prove_fold_rounds (zkstark.hip) per proof.
@@ -281,9 +286,257 @@ int bset_format(zk_batch* b, const ProofFormat& next, const char* who) {
     return ZK_OK;
 }
 
-int bchal_upload(zk_batch* b) {
-    HIPCHK(hipMemcpyAsync(b->d_chal, b->h_chal, b->batch * sizeof(BatchChal), hipMemcpyHostToDevice, b->stream));
+// the first `count` entries of the challenge table: the batch's for the alphas, afterwards one per channel
+int bchal_upload(zk_batch* b, size_t count) {
+    HIPCHK(hipMemcpyAsync(b->d_chal, b->h_chal, count * sizeof(BatchChal), hipMemcpyHostToDevice, b->stream));
     return ZK_OK;
+}
+
+// ---- the pipeline.  One run of it makes the proofs of one call: as many as it has channels.
+struct Run {
+    zk_batch* b;
+    ProofFormat f;                    // of the proofs made (zk_batch_prove: the batch's; shared: with lb and rows)
+    std::vector<Channel> ch;          // 2^lb (zk_batch_prove), or one (zk_batch_prove_shared)
+    uint32_t w;                       // width of the FRI stage, log2 of the trees built side by side from cp on: lb, or 0
+    uint32_t fw;                      // ... and of the f stage: lb, or 0 with row leaves
+    const char* who;                  // the entry point, for its errors
+    double T0, t_wait = 0, t_caps = 0;   // ZK_HOST_TIMING: the last lap, waiting for the device, the pool hashing cap commits
+    size_t nv = 0, ndg = 0;           // values and digests the queries of one channel open (run_queries)
+};
+bool btiming() { static const bool on = getenv("ZK_HOST_TIMING") != nullptr; return on; }
+void lap(Run& r, const char* what) {
+    if (!btiming()) return;
+    double t = now_us();
+    fprintf(stderr, "[zk batch timing] %-28s %8.1f us\n", what, t - r.T0);
+    r.T0 = t;
+}
+int wait_roots(Run& r) { double t = now_us(); int rc = bwait_roots(r.b); r.t_wait += now_us() - t; return rc; }
+// the pool's share of a commit round that hashes caps (ZK_HOST_TIMING)
+void cap_lap(Run& r, uint32_t ce, double t) { if (btiming() && ce) r.t_caps += now_us() - t; }
+// What a channel commits for a tree (prover.rs:85, :180, :224): the 2^ce digests of depth ce in ONE commit (ce = 0: the root).
+// from: its [2^ce][8] state words (bfinish_roots).  A buffer on the stack: this runs once per proof and round on the pool.
+void commit_cap(Channel& ch, const uint32_t* from, uint32_t ce) {
+    uint8_t cb[32 << kMaxCapLog];
+    for (size_t i = 0; i < ((size_t)1 << ce); ++i) digest_words_to_bytes(from + 8 * i, cb + 32 * i);
+    ch.commit_bytes(cb, (size_t)32 << ce);
+}
+// The three alphas of statement p from `ch` (prover.rs:163-165) and its row of the challenge table.  g2 = g^2.
+void balphas(zk_batch* b, size_t p, Channel& ch, uint32_t g2) {
+    const uint32_t a0 = ch.get_u32() % P, a1 = ch.get_u32() % P, a2 = ch.get_u32() % P;
+    BatchChal& c = b->h_chal[p];
+    c.first = b->first[p]; c.last = b->last[p];
+    c.alpha0_mont = to_mont(a0); c.alpha1g2_mont = to_mont(mulmod(a1, g2)); c.alpha2_mont = to_mont(a2);
+}
+// The tree over layer `id` of a stage of width w: 2^log_len values per proof, 2^leaf_steps to a leaf (0: one-value leaves, prover.rs:214).
+int btree(zk_batch* b, uint32_t id, uint32_t log_len, uint32_t leaf_steps, uint32_t w) {
+    b->tree_steps[id] = (uint8_t)leaf_steps;
+    if (leaf_steps) HIPCHK(launch_merkle_build_coset_batch(b->d_layers + b->layer_off[id], log_len, leaf_steps, w, b->d_trees + b->tree_off[id], b->stream, nullptr,
+                                                           bmail(b, id, log_len - leaf_steps, w), b->hash));
+    else HIPCHK(launch_merkle_build(b->d_layers + b->layer_off[id], log_len + w, b->d_trees + b->tree_off[id], b->stream, nullptr, bmail(b, id, log_len, w), b->hash));
+    return bpost(b, id, log_len - leaf_steps, w);
+}
+
+// f = the LDE of every trace (prover.rs:60-85) and its tree at width fw -- the batch heap, or the one tree over the rows -- with the
+// bookkeeping of a new proof (skipped: the trees it will not have built for the batch, to which run_groups adds).  Returns with tree 0
+// handed over and finished (*roots: 2^(fw + ce) digests) and the proof-independent part of cp's constants (compose_args with alpha = 1).
+int run_commit_f(Run& r, uint64_t skipped, ComposeBatchArgs& ca, const uint32_t** roots) {
+    zk_batch* b = r.b;
+    const uint32_t L = b->L, lb = b->lb;
+    uint32_t* f0 = b->d_layers + b->layer_off[0];
+    int rc;
+    if ((rc = dom_lde(b->dom, b->d_trace, b->d_coef, f0, b->stream, nullptr, (uint32_t)b->batch))) return rc;
+    b->stage_used = 0; b->n_segs = 0; b->seg_words = 0;
+    b->skipped_trees = skipped; b->proved_fold = r.f.fold; b->proved_stop = r.f.stop; b->proved_hash = b->hash;
+    memset(b->tree_steps, 0, sizeof b->tree_steps);
+    memset(b->tree_cap, 0, sizeof b->tree_cap);
+    b->proved = true; b->rows_tree0 = r.f.rows;
+    if (r.f.rows) HIPCHK(launch_merkle_build_rows(f0, L, lb, b->d_trees + b->tree_off[0], b->stream, nullptr, bmail(b, 0, L, 0), b->hash));
+    else HIPCHK(launch_merkle_build(f0, L + lb, b->d_trees + b->tree_off[0], b->stream, nullptr, bmail(b, 0, L, lb), b->hash));
+    if ((rc = bpost(b, 0, L, r.fw))) return rc;
+    const uint32_t one[3] = {1, 1, 1};
+    if ((rc = compose_args(b->dom, f0, b->d_layers + b->layer_off[1], 0, 0, one, ca.a))) return rc;
+    ca.chal = b->d_chal;
+    if ((rc = wait_roots(r))) return rc;
+    *roots = bfinish_roots(b, 0, L, r.fw);
+    return ZK_OK;
+}
+
+// The groups of `fold` rounds, from "tree 1 is built and posted" to "the last tree is committed" or, with an early stop, "the layer
+// the proofs stop at is folded" (it gets no tree, no wait and no root).  Per group: the roots arrive, every channel commits its tree and
+// draws its beta (prover.rs:180 / :224, :200) into its row of the table, the rows go up, and the fold and the next tree are launched --
+// one fused launch when K = 1 without coset leaves or stop (prover.rs:201-214), else the multi-fold (prover.rs:201-211, steps times)
+// and a tree over the next group's input, whose leaves are that group's cosets (the last layer: one value).
+int run_groups(Run& r) {
+    zk_batch* b = r.b;
+    const ProofFormat& f = r.f;
+    const zk_dom* d = b->dom;
+    const size_t np = r.ch.size();
+    const uint32_t w = r.w, L = b->L, G = f.groups();
+    const bool fused = f.fold == 1 && !f.coset && !f.stop;                // the fold inside the leaf hashing of its tree
+    int rc;
+    for (uint32_t j = 0;; ++j) {                                          // tree 1 + r0 is the last one launched
+        const uint32_t r0 = f.round0(j);
+        if ((rc = wait_roots(r))) return rc;
+        const uint32_t* roots = bfinish_roots(b, 1 + r0, L - r0 - b->tree_steps[1 + r0], w);   // 2^(L - r0) values per proof, 2^tree_steps per leaf
+        const uint32_t ce = b->tree_cap[1 + r0];                          // ... committed by its 2^ce digests of depth ce
+        const double tc = btiming() ? now_us() : 0;
+        if (j == G) {
+            b->pool->run(np, 32, [&](size_t p) { commit_cap(r.ch[p], roots + ((p << ce) * 8), ce); });
+            cap_lap(r, ce, tc);
+            break;
+        }
+        const uint32_t steps = f.steps(j), id = f.tree_id(j + 1);
+        // K = 1: the fold constant is reduced on the host; otherwise the challenge goes up RAW and is reduced on the device
+        const uint32_t winv_half = fused ? mulmod(invmod(powmod(d->shift, (uint64_t)1 << r0)), invmod(2)) : 0;
+        b->pool->run(np, 32, [&](size_t p) {
+            commit_cap(r.ch[p], roots + ((p << ce) * 8), ce);
+            const uint32_t beta = r.ch[p].get_u32();
+            b->h_chal[p].c_mont = fused ? to_mont(mulmod(beta % P, winv_half)) : beta;
+        });
+        cap_lap(r, ce, tc);
+        if ((rc = bchal_upload(b, np))) return rc;
+        if (fused) {
+            FoldBatchArgs fa;
+            if ((rc = fold_args(d, b->d_layers + b->layer_off[1 + r0], b->d_layers + b->layer_off[id], L - r0, r0, 0, fa.a))) return rc;
+            fa.chal = b->d_chal;
+            HIPCHK(launch_fold_merkle_batch(fa, w, b->d_trees + b->tree_off[id], b->stream, nullptr, bmail(b, id, L - r0 - 1, w), b->hash));
+            if ((rc = bpost(b, id, L - r0 - 1, w))) return rc;
+            continue;
+        }
+        if ((rc = dom_fold_multi_batch(d, b->d_layers + b->layer_off[1 + r0], b->d_layers + b->layer_off[id], L - r0, r0, steps, &b->d_chal->c_mont,
+                                       (uint32_t)(sizeof(BatchChal) / 4), b->d_work, (uint32_t)np, b->stream, nullptr))) return rc;
+        for (uint32_t l = 2 + r0; l < id; ++l) b->skipped_trees |= (uint64_t)1 << l;
+        if (f.stop && j + 1 == G) {
+            for (uint32_t l = id; l <= b->R + 1; ++l) b->skipped_trees |= (uint64_t)1 << l;
+            break;
+        }
+        if ((rc = btree(b, id, L - r0 - steps, f.slots_log(j + 1), w))) return rc;
+    }
+    lap(r, "lde .. last roots");
+    if (btiming()) fprintf(stderr, "[zk batch timing]   of which waiting for the device %.1f us\n", r.t_wait);
+    if (btiming() && f.cap) fprintf(stderr, "[zk batch timing]   of which host threads hashing cap commits %.1f us\n", r.t_caps);
+    return ZK_OK;
+}
+
+// The end of FRI.  Early stop: one launch turns layer 1 + R' (2^(stop + log_b) values per proof) into the rows (count, c_0 .. c_(2^stop - 1))
+// of h_final, and every coefficient of degree >= 2^stop must be zero; else the last layer is B equal values per proof (prover.rs:238, :251).
+// Each channel then commits its free term (prover.rs:254) or its 4 * 2^stop coefficient bytes in one commit (transcript.hpp "stop"),
+// grinds, and draws its Q query raws (prover.rs:263); the offsets of what they open go to h_goff: channel c's value words at c * nv,
+// its digests at np * nv + c * ndg.
+int run_queries(Run& r) {
+    zk_batch* b = r.b;
+    const ProofFormat& f = r.f;
+    const size_t np = r.ch.size(), N = b->N, B = b->B;
+    const uint32_t stop = f.stop, Rp = f.rounds(), L = b->L, Q = f.q;
+    const size_t ncoef = (size_t)1 << stop, frow = ncoef + 1;
+    static const char kWhich[] = "some trace of the batch does not satisfy the constraints (the sum does not tell which)";
+    const bool shared = f.lb != 0;                                        // whose failure no single trace answers for
+    int rc;
+    if (stop) {
+        if ((rc = dom_final_poly_batch(b->dom, b->d_layers + b->layer_off[1 + Rp], b->d_final, L - Rp, Rp, (uint32_t)ncoef, (uint32_t)np, b->stream, nullptr))) return rc;
+        HIPCHK(hipMemcpyAsync(b->h_final, b->d_final, np * frow * 4, hipMemcpyDeviceToHost, b->stream));
+        HIPCHK(hipStreamSynchronize(b->stream));
+        for (size_t p = 0; p < np; ++p) {
+            const uint32_t above = b->h_final[p * frow];
+            if (above && shared) return fail(ZK_ERR_CHECK, "%s: final FRI layer has degree >= 2^%u (%u non-zero coefficients above): %s", r.who, stop, above, kWhich);
+            if (above)
+                return fail(ZK_ERR_CHECK, "proof %zu of the batch: final FRI layer has degree >= 2^%u: its trace does not satisfy the constraints (%u non-zero coefficients above; cf. prover.rs:238)",
+                            p, stop, above);
+        }
+    } else {
+        HIPCHK(hipMemcpyAsync(b->h_last, b->d_layers + b->layer_off[1 + b->R], np * B * 4, hipMemcpyDeviceToHost, b->stream));
+        HIPCHK(hipStreamSynchronize(b->stream));
+        for (size_t p = 0; p < np; ++p)
+            for (size_t i = 1; i < B; ++i) {
+                if (b->h_last[p * B + i] == b->h_last[p * B]) continue;
+                if (shared) return fail(ZK_ERR_CHECK, "%s: last FRI layer is not constant (prover.rs:238): %s", r.who, kWhich);
+                return fail(ZK_ERR_CHECK, "proof %zu of the batch: last FRI layer is not constant (prover.rs:238): its trace does not satisfy the constraints", p);
+            }
+    }
+    auto commit_final = [&](size_t p) {
+        if (!stop) { r.ch[p].commit_u32(b->h_last[p * B]); return; }
+        uint8_t cb[4 << kMaxStopLog];
+        const uint32_t* c = b->h_final + p * frow + 1;
+        for (size_t k = 0; k < ncoef; ++k)
+            for (int i = 0; i < 4; ++i) cb[4 * k + i] = (uint8_t)(c[k] >> (8 * i));
+        r.ch[p].commit_bytes(cb, 4 * ncoef);
+    };
+    bopenings(f, &r.nv, &r.ndg);
+    r.nv *= Q; r.ndg *= Q;
+    const size_t nv = r.nv, ndg = r.ndg;
+    if (f.grind) {                                                        // free terms, then the nonces of all channels at once
+        b->pool->run(np, 16, [&](size_t p) { commit_final(p); });
+        if ((rc = bgrind(b, r.ch))) return rc;
+        lap(r, "grind");
+    }
+    std::atomic<int> bad{0};
+    b->pool->run(np, 16, [&](size_t c) {
+        if (!f.grind) commit_final(c);
+        uint32_t qraw[kMaxQueries];
+        for (uint32_t k = 0; k < Q; ++k) qraw[k] = r.ch[c].get_u32();     // prover.rs:263 (x Q)
+        uint64_t *const vo0 = b->h_goff + c * nv, *const do0 = b->h_goff + np * nv + c * ndg;
+        uint64_t *vo = vo0, *dofs = do0;
+        std::vector<size_t> nodes;
+        // An opening (prover.rs:263-289) is a leaf of `layer` in a stage of width wl = fw (layer 0) or w, of the proof p of that stage:
+        // this channel's (the walk has lb = 0: the leaf is its index in the proof's layer), or, for the f leaves of a shared proof without
+        // rows, the statement the leaf index leads with (at every other layer it leads with 0).  One of the two terms of p is zero.
+        // Layer l is stored proof-major, so the 2^slots_log values of the leaf (one unless coset or row leaves) are words
+        // (p << (log_m + slots_log)) + at + (u << log_m) of it; node (depth dd, index i) of the proof's tree over 2^log_m leaves is node
+        // 2^(wl + dd) - 1 + p 2^dd + i of the heap; path_nodes walks from the leaf level up, and the path ends below the tree's cap.
+        for (uint32_t k = 0; k < Q; ++k)
+            f.for_each_opening((size_t)qraw[k] % (N - 2 * B), [&](uint32_t layer, uint32_t log_m, size_t leaf, uint32_t slots_log) {
+                const uint32_t wl = layer == 0 ? r.fw : r.w;
+                const size_t p = c + (leaf >> log_m), at = leaf & (((size_t)1 << log_m) - 1);
+                for (size_t u = 0; u < ((size_t)1 << slots_log); ++u) *vo++ = b->layer_off[layer] + (p << (log_m + slots_log)) + at + (u << log_m);
+                nodes.clear();
+                path_nodes((size_t)1 << log_m, at, nodes);
+                nodes.resize(log_m - b->tree_cap[layer]);
+                uint32_t dd = log_m;
+                for (size_t nd : nodes) {
+                    const size_t i = nd - (((size_t)1 << dd) - 1);
+                    *dofs++ = (uint64_t)b->tree_off[layer] + (uint64_t)((((size_t)1 << (wl + dd)) - 1) + (p << dd) + i) * 8;
+                    --dd;
+                }
+            });
+        if ((size_t)(vo - vo0) != nv || (size_t)(dofs - do0) != ndg) bad.store(1);
+    });
+    lap(r, "queries + opening offsets");
+    return bad.load() ? fail(ZK_ERR_STATE, "%s: unexpected number of openings", r.who) : (int)ZK_OK;
+}
+
+// The openings themselves: the host-built levels go into the trees, two gathers fetch every channel's values and digests, and each channel
+// commits its tuples (prover.rs:274-277, then per group prover.rs:280-289).  Channel c's proof goes to proofs_out + c * stride, its
+// Channel.state to states_out + 32 c (channel.rs:34-36).
+int run_decommit(Run& r, uint8_t* proofs_out, size_t stride, uint8_t* states_out) {
+    zk_batch* b = r.b;
+    const ProofFormat& f = r.f;
+    const size_t np = r.ch.size(), nv = r.nv, ndg = r.ndg, tv = np * nv, td = np * ndg, plen = f.data_len();
+    HIPCHK(hipMemcpyAsync(b->d_goff, b->h_goff, (tv + td) * 8, hipMemcpyHostToDevice, b->stream));
+    HIPCHK(launch_scatter(b->d_stage, b->d_segs, b->n_segs, b->seg_words, b->d_trees, nullptr, b->stream, nullptr));   // host-built levels
+    HIPCHK(launch_gather(b->d_layers, b->d_goff, (uint32_t)tv, 1, b->d_gout, b->stream, nullptr));
+    HIPCHK(launch_gather(b->d_trees, b->d_goff + tv, (uint32_t)td, 8, b->d_gout + tv, b->stream, nullptr));
+    HIPCHK(hipMemcpyAsync(b->h_gout, b->d_gout, (tv + td * 8) * 4, hipMemcpyDeviceToHost, b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    lap(r, "gather");
+    size_t widest = Channel::group_bytes((size_t)1 << f.steps(0), b->L, false);   // the first group's tuple, or a row of 2^lb values
+    if (f.rows && Channel::group_bytes(b->batch, b->L, true) > widest) widest = Channel::group_bytes(b->batch, b->L, true);
+    std::atomic<int> bad{0};
+    b->pool->run(np, 4, [&](size_t c) {
+        Channel& ch = r.ch[c];
+        const uint32_t* vals = b->h_gout + c * nv;
+        const uint32_t* dw = b->h_gout + tv + c * ndg * 8;
+        std::vector<uint8_t> buf(widest);                                 // one buffer per channel
+        auto tuple = [&](size_t s, size_t pl, bool one_leaf) {
+            ch.commit_group(buf.data(), s, pl, [&](size_t t) { return vals[t]; }, [&](size_t i, uint8_t* out) { digest_words_to_bytes(dw + 8 * i, out); }, one_leaf);
+            vals += s; dw += 8 * (one_leaf ? 1 : s) * pl;
+        };
+        for (uint32_t q = 0; q < f.q; ++q) f.for_each_tuple(tuple);
+        if (ch.data.size() != plen) { bad.store(1); return; }
+        memcpy(proofs_out + c * stride, ch.data.data(), plen);
+        memcpy(states_out + 32 * c, ch.state, 32);
+    });
+    lap(r, "decommit hashing + copy out");
+    return bad.load() ? fail(ZK_ERR_STATE, "%s: unexpected proof length", r.who) : (int)ZK_OK;
 }
 
 }  // namespace
@@ -637,22 +890,17 @@ int zk_batch_merkle_cap(zk_batch* b, uint32_t tree, size_t proof, uint8_t* out, 
     return merkle_nodes_to_host(b->device, b->stream, b->d_trees + b->tree_off[tree], (((size_t)1 << (b->lb + ce)) - 1) + (proof << ce), (size_t)1 << ce, out);
 }
 
-// generate_proof (prover.rs:9-293) for every resident trace.  proofs_out: [batch][stride] bytes, stride >=
-// zk_proof_data_len_fold(log_n, log_b, queries, grind, fold) (coset leaves: zk_proof_data_len_coset; early stop: zk_proof_data_len_stop); states_out: [batch][32] (Channel.state of each proof, proof.rs:6).
-// fold > 1 (DESIGN.md "Folding factor"): the rounds in groups of `fold`; per group one challenge per proof, one pass of the batched
-// multi-fold kernel and one tree over its output, as prove_fold_rounds (zkstark.hip) does for one proof.  The wire format (openings,
-// tuples, length) is transcript.hpp's for every fold.
-// stop > 0: the loop ends after the fold of the last group of R - stop rounds, whose output gets no tree, no mailbox wait and no root; the
-// final polynomials of the whole batch come from one launch and one copy, and the ids from 1 + R - stop on are not materialised.
+// generate_proof (prover.rs:9-293) for every resident trace: the run of the pipeline with 2^lb channels, every stage at width lb.
+// proofs_out: [batch][stride] bytes, stride >= the length of the batch's format (zk_proof_data_len_* of its settings); states_out:
+// [batch][32] (Channel.state of each proof, proof.rs:6).  Its own: every channel commits its own 2^ce digests of the f heap and draws
+// its own alphas, on the pool; cp comes fused with its tree (prover.rs:166-176), or with coset leaves from its own launch under the tree
+// with group 0's cosets as leaves.  A batch of one goes to the one-call prover.
 int zk_batch_prove(zk_batch* b, uint8_t* proofs_out, size_t stride, uint8_t* states_out) {
     if (!b || !proofs_out || !states_out) return fail(ZK_ERR_INVALID, "zk_batch_prove: null argument");
     if (!b->have_traces) return fail(ZK_ERR_STATE, "zk_batch_prove: no traces");
     BusyScope busy(b);
     if (!busy.mine) return fail(ZK_ERR_STATE, "zk_batch_prove: another zk_batch_prove is running on this batch");
     const ProofFormat f = b->fmt;
-    const uint32_t Q = f.q, K = f.fold, stop = f.stop, G = f.groups();
-    const int hash = b->hash;
-    const bool coset = f.coset;
     const size_t plen = f.data_len();
     if (stride < plen) return fail(ZK_ERR_BUFFER, "zk_batch_prove: stride %zu < proof length %zu", stride, plen);
     if (b->single) {
@@ -662,227 +910,43 @@ int zk_batch_prove(zk_batch* b, uint8_t* proofs_out, size_t stride, uint8_t* sta
         return rc1;
     }
     HIPCHK(hipSetDevice(b->device));
-    const size_t nb = b->batch, N = b->N, B = b->B;
-    const uint32_t R = b->R, L = b->L, lb = b->lb;
-    const uint32_t Rp = f.rounds();                                       // folded rounds (early stop: the groups are those of Rp)
-    const zk_dom* d = b->dom;
-    std::vector<Channel> ch(nb);
-    for (auto& c : ch) c.data.reserve(plen);
+    const size_t nb = b->batch;
+    const uint32_t L = b->L, lb = b->lb;
+    Run r{b, f, std::vector<Channel>(nb), lb, lb, "zk_batch_prove", 0};
+    for (auto& c : r.ch) c.data.reserve(plen);
+    r.T0 = now_us();
     int rc;
-    static const bool timing = getenv("ZK_HOST_TIMING") != nullptr;
-    double T0 = now_us(), t_wait = 0;
-    auto lap = [&](const char* what) {
-        if (!timing) return;
-        double t = now_us();
-        fprintf(stderr, "[zk batch timing] %-28s %8.1f us\n", what, t - T0);
-        T0 = t;
-    };
-    auto wait_roots = [&]() { double t = now_us(); int r = bwait_roots(b); t_wait += now_us() - t; return r; };
-    // What proof p commits for a tree (prover.rs:85, :180, :224): the 2^ce digests of depth ce in ONE commit (ce = 0: the root).
-    // from: [batch][2^ce][8] state words (bfinish_roots).
-    double t_caps = 0;
-    auto commit_tree = [&](size_t p, const uint32_t* from, uint32_t ce) {
-        uint8_t cb[32 << kMaxCapLog];
-        const uint32_t* w = from + ((p << ce) * 8);
-        for (size_t i = 0; i < ((size_t)1 << ce); ++i) digest_words_to_bytes(w + 8 * i, cb + 32 * i);
-        ch[p].commit_bytes(cb, (size_t)32 << ce);
-    };
-    // the pool's share of a commit round that hashes caps (ZK_HOST_TIMING)
-    auto cap_lap = [&](uint32_t ce, double t) { if (timing && ce) t_caps += now_us() - t; };
-    // f = LDE of every trace, committed (prover.rs:60-85)
-    if ((rc = dom_lde(d, b->d_trace, b->d_coef, b->d_layers + b->layer_off[0], b->stream, nullptr, (uint32_t)nb))) return rc;
-    b->stage_used = 0; b->n_segs = 0; b->seg_words = 0;
-    b->skipped_trees = 0; b->proved_fold = K; b->proved_stop = stop; b->proved_hash = hash;
-    memset(b->tree_steps, 0, sizeof b->tree_steps);
-    memset(b->tree_cap, 0, sizeof b->tree_cap);
-    b->proved = true; b->rows_tree0 = false;
-    HIPCHK(launch_merkle_build(b->d_layers + b->layer_off[0], L + lb, b->d_trees + b->tree_off[0], b->stream, nullptr, bmail(b, 0, L, lb), hash));
-    if ((rc = bpost(b, 0, L, lb))) return rc;
-    // proof-independent part of the composition constants (compose_args with alpha = 1)
     ComposeBatchArgs ca;
-    {
-        const uint32_t one[3] = {1, 1, 1};
-        if ((rc = compose_args(d, b->d_layers + b->layer_off[0], b->d_layers + b->layer_off[1], 0, 0, one, ca.a))) return rc;
-        ca.chal = b->d_chal;
-    }
-    const uint32_t g2 = mulmod(d->g, d->g);
-    if ((rc = wait_roots())) return rc;
-    const uint32_t* roots = bfinish_roots(b, 0, L, lb);
-    double tc = timing ? now_us() : 0;
+    const uint32_t* roots;
+    if ((rc = run_commit_f(r, 0, ca, &roots))) return rc;
+    const uint32_t g2 = mulmod(b->dom->g, b->dom->g), ce = b->tree_cap[0];
+    const double tc = btiming() ? now_us() : 0;
     b->pool->run(nb, 16, [&](size_t p) {
-        commit_tree(p, roots, b->tree_cap[0]);                            // prover.rs:85
-        uint32_t a0 = ch[p].get_u32() % P, a1 = ch[p].get_u32() % P, a2 = ch[p].get_u32() % P;   // prover.rs:163-165
-        BatchChal& c = b->h_chal[p];
-        c.first = b->first[p]; c.last = b->last[p];
-        c.alpha0_mont = to_mont(a0); c.alpha1g2_mont = to_mont(mulmod(a1, g2)); c.alpha2_mont = to_mont(a2);
+        commit_cap(r.ch[p], roots + ((p << ce) * 8), ce);
+        balphas(b, p, r.ch[p], g2);
     });
-    cap_lap(b->tree_cap[0], tc);
-    if ((rc = bchal_upload(b))) return rc;
-    if (coset) {                                                          // prover.rs:166-176, then the tree with group 0's cosets as leaves
-        const uint32_t s0 = f.steps(0);
+    cap_lap(r, ce, tc);
+    if ((rc = bchal_upload(b, nb))) return rc;
+    if (f.coset) {
         HIPCHK(launch_compose_batch(ca, lb, b->stream, nullptr));
-        b->tree_steps[1] = (uint8_t)s0;
-        HIPCHK(launch_merkle_build_coset_batch(b->d_layers + b->layer_off[1], L, s0, lb, b->d_trees + b->tree_off[1], b->stream, nullptr,
-                                               bmail(b, 1, L - s0, lb), hash));
-        if ((rc = bpost(b, 1, L - s0, lb))) return rc;
+        if ((rc = btree(b, 1, L, f.steps(0), lb))) return rc;
     } else {
-        HIPCHK(launch_compose_merkle_batch(ca, lb, b->d_trees + b->tree_off[1], b->stream, nullptr, bmail(b, 1, L, lb), hash));   // prover.rs:166-176
+        HIPCHK(launch_compose_merkle_batch(ca, lb, b->d_trees + b->tree_off[1], b->stream, nullptr, bmail(b, 1, L, lb), b->hash));
         if ((rc = bpost(b, 1, L, lb))) return rc;
     }
-    const bool fused = K == 1 && !coset && !stop;                         // the fold inside the leaf hashing of its tree
-    for (uint32_t j = 0;; ++j) {                                          // per group; tree 1 + r0 is the last one committed
-        const uint32_t r0 = f.round0(j);
-        if ((rc = wait_roots())) return rc;
-        roots = bfinish_roots(b, 1 + r0, L - r0 - b->tree_steps[1 + r0], lb);   // tree 1 + r0: 2^(L - r0) values per proof, 2^tree_steps per leaf
-        const uint32_t ce = b->tree_cap[1 + r0];                          // ... committed by its 2^ce digests of depth ce
-        tc = timing ? now_us() : 0;
-        if (j == G) {
-            b->pool->run(nb, 32, [&](size_t p) { commit_tree(p, roots, ce); });
-            cap_lap(ce, tc);
-            break;
-        }
-        const uint32_t steps = f.steps(j), id = f.tree_id(j + 1);
-        const bool stopped = stop && j + 1 == G;                          // the layer the proofs stop at: no tree
-        // K = 1: the fold constant is reduced on the host; K > 1: the challenge goes up RAW and is reduced on the device
-        const uint32_t winv_half = fused ? mulmod(invmod(powmod(d->shift, (uint64_t)1 << r0)), invmod(2)) : 0;
-        b->pool->run(nb, 32, [&](size_t p) {
-            commit_tree(p, roots, ce);                                    // prover.rs:180 / :224
-            const uint32_t beta = ch[p].get_u32();                        // prover.rs:200, once per group
-            b->h_chal[p].c_mont = fused ? to_mont(mulmod(beta % P, winv_half)) : beta;
-        });
-        cap_lap(ce, tc);
-        if ((rc = bchal_upload(b))) return rc;
-        if (fused) {
-            FoldBatchArgs fa;
-            if ((rc = fold_args(d, b->d_layers + b->layer_off[1 + r0], b->d_layers + b->layer_off[id], L - r0, r0, 0, fa.a))) return rc;
-            fa.chal = b->d_chal;
-            HIPCHK(launch_fold_merkle_batch(fa, lb, b->d_trees + b->tree_off[id], b->stream, nullptr, bmail(b, id, L - r0 - 1, lb), hash));   // prover.rs:201-214
-            if ((rc = bpost(b, id, L - r0 - 1, lb))) return rc;
-        } else {
-            if ((rc = dom_fold_multi_batch(d, b->d_layers + b->layer_off[1 + r0], b->d_layers + b->layer_off[id], L - r0, r0, steps, &b->d_chal->c_mont,
-                                           (uint32_t)(sizeof(BatchChal) / 4), b->d_work, (uint32_t)nb, b->stream, nullptr))) return rc;   // prover.rs:201-211, steps times
-            // coset leaves: this tree is the one over the NEXT group's input, its leaves are that group's cosets (the last layer: one value)
-            const uint32_t leaf_steps = f.slots_log(j + 1);
-            for (uint32_t l = 2 + r0; l < id; ++l) b->skipped_trees |= (uint64_t)1 << l;
-            if (stopped) {
-                for (uint32_t l = id; l <= R + 1; ++l) b->skipped_trees |= (uint64_t)1 << l;
-                break;
-            }
-            if (leaf_steps) {
-                b->tree_steps[id] = (uint8_t)leaf_steps;
-                HIPCHK(launch_merkle_build_coset_batch(b->d_layers + b->layer_off[id], L - r0 - steps, leaf_steps, lb, b->d_trees + b->tree_off[id],
-                                                       b->stream, nullptr, bmail(b, id, L - r0 - steps - leaf_steps, lb), hash));
-            } else
-            HIPCHK(launch_merkle_build(b->d_layers + b->layer_off[id], L - r0 - steps + lb, b->d_trees + b->tree_off[id], b->stream, nullptr,
-                                       bmail(b, id, L - r0 - steps, lb), hash));      // prover.rs:214
-            if ((rc = bpost(b, id, L - r0 - steps - leaf_steps, lb))) return rc;
-        }
-    }
-    lap("lde .. last roots");
-    if (timing) fprintf(stderr, "[zk batch timing]   of which waiting for the device %.1f us\n", t_wait);
-    if (timing && f.cap) fprintf(stderr, "[zk batch timing]   of which host threads hashing cap commits %.1f us\n", t_caps);
-    const size_t ncoef = (size_t)1 << stop, frow = ncoef + 1;             // early stop: a row of h_final is (count, c_0 .. c_(2^stop - 1))
-    if (stop) {
-        // final polynomials: layer 1 + Rp holds 2^(stop + log_b) values per proof; every coefficient of degree >= 2^stop must be zero
-        if ((rc = dom_final_poly_batch(d, b->d_layers + b->layer_off[1 + Rp], b->d_final, L - Rp, Rp, (uint32_t)ncoef, (uint32_t)nb, b->stream, nullptr))) return rc;
-        HIPCHK(hipMemcpyAsync(b->h_final, b->d_final, nb * frow * 4, hipMemcpyDeviceToHost, b->stream));
-        HIPCHK(hipStreamSynchronize(b->stream));
-        for (size_t p = 0; p < nb; ++p)
-            if (b->h_final[p * frow])
-                return fail(ZK_ERR_CHECK, "proof %zu of the batch: final FRI layer has degree >= 2^%u: its trace does not satisfy the constraints (%u non-zero coefficients above; cf. prover.rs:238)",
-                            p, stop, b->h_final[p * frow]);
-    } else {
-    // last layers: B equal values per proof (prover.rs:238, :251), free term (prover.rs:254)
-    HIPCHK(hipMemcpyAsync(b->h_last, b->d_layers + b->layer_off[1 + R], nb * B * 4, hipMemcpyDeviceToHost, b->stream));
-    HIPCHK(hipStreamSynchronize(b->stream));
-    for (size_t p = 0; p < nb; ++p)
-        for (size_t i = 1; i < B; ++i)
-            if (b->h_last[p * B + i] != b->h_last[p * B])
-                return fail(ZK_ERR_CHECK, "proof %zu of the batch: last FRI layer is not constant (prover.rs:238): its trace does not satisfy the constraints", p);
-    }
-    // the free term (prover.rs:254), or the 4 * 2^stop coefficient bytes in one commit (transcript.hpp "stop")
-    auto commit_final = [&](size_t p) {
-        if (!stop) { ch[p].commit_u32(b->h_last[p * B]); return; }
-        uint8_t cb[4 << kMaxStopLog];
-        const uint32_t* c = b->h_final + p * frow + 1;
-        for (size_t k = 0; k < ncoef; ++k)
-            for (int i = 0; i < 4; ++i) cb[4 * k + i] = (uint8_t)(c[k] >> (8 * i));
-        ch[p].commit_bytes(cb, 4 * ncoef);
-    };
-    // queries and the offsets of every opening (prover.rs:263-289); node j of proof p's tree over m leaves
-    // (depth dd, index i) is node 2^(lb+dd) - 1 + p 2^dd + i of the batch heap
-    const size_t nv = Q * b->per_proof_vals, ndg = Q * b->per_proof_digs;     // per proof, all its queries
-    uint64_t* voff = b->h_goff;
-    uint64_t* doff = b->h_goff + nb * nv;
-    if (b->fmt.grind) {                                                   // free terms, then the nonces of all proofs at once
-        b->pool->run(nb, 16, [&](size_t p) { commit_final(p); });
-        if ((rc = bgrind(b, ch))) return rc;
-        lap("grind");
-    }
-    b->pool->run(nb, 16, [&](size_t p) {
-        if (!b->fmt.grind) commit_final(p);
-        uint32_t qraw[kMaxQueries];
-        for (uint32_t k = 0; k < Q; ++k) qraw[k] = ch[p].get_u32();       // prover.rs:263 (x Q)
-        uint64_t* vo = voff + p * nv;
-        uint64_t* dofs = doff + p * ndg;
-        std::vector<size_t> nodes;
-        auto add_path = [&](uint32_t tree, uint32_t log_m, size_t leaf) {
-            nodes.clear();
-            path_nodes((size_t)1 << log_m, leaf, nodes);
-            uint32_t dd = log_m;                                          // path_nodes walks from the leaf level up
-            nodes.resize(log_m - b->tree_cap[tree]);                      // ... and the path ends below the tree's cap
-            for (size_t nd : nodes) {
-                size_t i = nd - (((size_t)1 << dd) - 1);
-                *dofs++ = (uint64_t)b->tree_off[tree] + (uint64_t)((((size_t)1 << (lb + dd)) - 1) + (p << dd) + i) * 8;
-                --dd;
-            }
-        };
-        for (uint32_t k = 0; k < Q; ++k)                                  // layer l is stored proof-major: proof p's values at p * len
-            f.for_each_opening((size_t)qraw[k] % (N - 2 * B), [&](uint32_t layer, uint32_t log_leaves, size_t leaf, uint32_t slots_log) {
-                for (size_t u = 0; u < ((size_t)1 << slots_log); ++u)     // the slots of one leaf (one value unless coset leaves)
-                    *vo++ = b->layer_off[layer] + (p << (log_leaves + slots_log)) + leaf + (u << log_leaves);
-                add_path(layer, log_leaves, leaf);
-            });
-    });
-    lap("queries + opening offsets");
-    const size_t tv = nb * nv, td = nb * ndg;
-    HIPCHK(hipMemcpyAsync(b->d_goff, b->h_goff, (tv + td) * 8, hipMemcpyHostToDevice, b->stream));
-    HIPCHK(launch_scatter(b->d_stage, b->d_segs, b->n_segs, b->seg_words, b->d_trees, nullptr, b->stream, nullptr));   // host-built levels
-    HIPCHK(launch_gather(b->d_layers, b->d_goff, (uint32_t)tv, 1, b->d_gout, b->stream, nullptr));
-    HIPCHK(launch_gather(b->d_trees, b->d_goff + tv, (uint32_t)td, 8, b->d_gout + tv, b->stream, nullptr));
-    HIPCHK(hipMemcpyAsync(b->h_gout, b->d_gout, (tv + td * 8) * 4, hipMemcpyDeviceToHost, b->stream));
-    HIPCHK(hipStreamSynchronize(b->stream));
-    lap("gather");
-    std::atomic<int> bad{0};
-    b->pool->run(nb, 4, [&](size_t p) {
-        const uint32_t* vals = b->h_gout + p * nv;
-        const uint32_t* dw = b->h_gout + tv + p * ndg * 8;
-        std::vector<uint8_t> buf(Channel::group_bytes((size_t)1 << f.steps(0), L, false));   // one buffer per proof: the first group's tuple is the largest
-        auto tuple = [&](size_t s, size_t pl, bool one_leaf) {
-            ch[p].commit_group(buf.data(), s, pl, [&](size_t t) { return vals[t]; }, [&](size_t i, uint8_t* out) { digest_words_to_bytes(dw + 8 * i, out); },
-                               one_leaf);
-            vals += s; dw += 8 * (one_leaf ? 1 : s) * pl;
-        };
-        for (uint32_t q = 0; q < Q; ++q) f.for_each_tuple(tuple);         // prover.rs:274-277, then per group prover.rs:280-289
-        if (ch[p].data.size() != plen) { bad.store(1); return; }
-        memcpy(proofs_out + p * stride, ch[p].data.data(), plen);          // channel.rs:34-36
-        memcpy(states_out + 32 * p, ch[p].state, 32);
-    });
-    lap("decommit hashing + copy out");
-    if (bad.load()) return fail(ZK_ERR_STATE, "zk_batch_prove: unexpected proof length");
-    return ZK_OK;
+    if ((rc = run_groups(r)) || (rc = run_queries(r))) return rc;
+    return run_decommit(r, proofs_out, stride, states_out);
 }
 
-// ONE proof of the batch's 2^log_batch resident traces (transcript.hpp "lb"): the f trees of zk_batch_prove, then one FRI over
-// CP = sum_p cp_p.  f: the LDE and the heap over all f layers are zk_batch_prove's launches, and the level they hand over is committed
-// once.  3 alphas per statement go into the BatchChal table; launch_compose_sum_batch writes CP into the first N words of layer 1.
-// From there on the stages of zk_batch_prove run at width one (lb = 0 in every launch and helper): proof 0's share of each layer slot
-// and heap, h_chal[0].c_mont for the challenge, row 0 of the final-polynomial table.  The gather buffers of the batch always hold a
-// shared proof's openings (3M f tuples and one set of group tuples per query against M sets of both).
+// ONE proof of the batch's 2^log_batch resident traces (transcript.hpp "lb"): the run of the pipeline with one channel, whose
+// FRI stage has width 0 -- proof 0's share of each layer slot and heap, row 0 of the challenge and final-polynomial tables -- over
+// CP = sum_p cp_p.  Its own: the level the f heap hands over is committed once, 2^(lb + ce) digests; the one channel draws the 3 alphas of
+// every statement; launch_compose_sum_batch writes CP into the first N words of layer 1 and its tree is built at width 0.  The gather
+// buffers of the batch always hold a shared proof's openings (3M f tuples and one set of group tuples per query against M sets of both).
 // Afterwards tree 0 is the batch's f heap as ever; the ids >= 1 hold one statement's worth and are reported as not built.
-// Row leaves (zk_batch_set_shared_rows; transcript.hpp "rows"): the f stage runs at width one too -- ONE tree over the N rows
-// of layer 0 from launch_merkle_build_rows, handed over, posted and finished like cp's tree -- and a query opens three leaves of M slots
-// in it.  Tree 0 is then that tree (2N - 1 nodes at tree_off[0]), not the batch's heap, and is reported as not built.
+// Row leaves (zk_batch_set_shared_rows; transcript.hpp "rows"): the f stage has width 0 too -- ONE tree over the N rows of
+// layer 0, handed over, posted and finished like cp's tree -- and a query opens three leaves of M slots in it.  Tree 0 is then that tree
+// (2N - 1 nodes at tree_off[0]), not the batch's heap, and is reported as not built.
 int zk_batch_prove_shared(zk_batch* b, uint8_t* proof_out, size_t cap, size_t* proof_len, uint8_t state_out[32]) {
     if (!b || !proof_out || !proof_len || !state_out) return fail(ZK_ERR_INVALID, "zk_batch_prove_shared: null argument");
     if (b->single || b->lb > kMaxSharedLog)
@@ -893,159 +957,36 @@ int zk_batch_prove_shared(zk_batch* b, uint8_t* proof_out, size_t cap, size_t* p
     ProofFormat f = b->fmt;
     f.lb = b->lb;
     f.rows = b->shared_rows;
-    const uint32_t Q = f.q, K = f.fold, stop = f.stop, G = f.groups(), lb = b->lb;
-    const int hash = b->hash;
-    const bool coset = f.coset;
     const size_t plen = f.data_len();
     *proof_len = plen;
     if (cap < plen) return fail(ZK_ERR_BUFFER, "zk_batch_prove_shared: buffer of %zu bytes < proof length %zu", cap, plen);
-    size_t nv = 0, ndg = 0;                                               // values and digests the Q queries open
+    size_t nv = 0, ndg = 0;                                               // values and digests a query opens
     bopenings(f, &nv, &ndg);
-    nv *= Q; ndg *= Q;
-    if (nv + ndg > b->batch * Q * (b->per_proof_vals + b->per_proof_digs) || nv + 8 * ndg > b->batch * Q * (b->per_proof_vals + 8 * b->per_proof_digs)) return fail(ZK_ERR_STATE, "zk_batch_prove_shared: gather buffers too small");
+    if (nv + ndg > b->batch * (b->per_proof_vals + b->per_proof_digs) || nv + 8 * ndg > b->batch * (b->per_proof_vals + 8 * b->per_proof_digs))
+        return fail(ZK_ERR_STATE, "zk_batch_prove_shared: gather buffers too small");
     HIPCHK(hipSetDevice(b->device));
-    const size_t nb = b->batch, N = b->N, B = b->B;
-    const uint32_t R = b->R, L = b->L, Rp = f.rounds();
-    const zk_dom* d = b->dom;
-    Channel ch;
+    const uint32_t L = b->L, lb = b->lb;
+    Run r{b, f, std::vector<Channel>(1), 0, f.rows ? 0 : lb, "zk_batch_prove_shared", 0};
+    Channel& ch = r.ch[0];
     ch.data.reserve(plen);
+    r.T0 = now_us();
     int rc;
-    auto commit_level = [&](const uint32_t* from, size_t count) {       // `count` digests (state words) in ONE commit
-        std::vector<uint8_t> cb(32 * count);
-        for (size_t i = 0; i < count; ++i) digest_words_to_bytes(from + 8 * i, cb.data() + 32 * i);
-        ch.commit_bytes(cb.data(), cb.size());
-    };
-    // f of every statement, committed together (prover.rs:60-85): zk_batch_prove's launches
-    if ((rc = dom_lde(d, b->d_trace, b->d_coef, b->d_layers + b->layer_off[0], b->stream, nullptr, (uint32_t)nb))) return rc;
-    b->stage_used = 0; b->n_segs = 0; b->seg_words = 0;
-    b->skipped_trees = ~(uint64_t)1;                                      // only tree 0 is the batch's
-    b->proved_fold = K; b->proved_stop = stop; b->proved_hash = hash;
-    memset(b->tree_steps, 0, sizeof b->tree_steps);
-    memset(b->tree_cap, 0, sizeof b->tree_cap);
-    b->proved = true; b->rows_tree0 = f.rows;
-    const uint32_t fw = f.rows ? 0 : lb;                                  // width of the f stage: row leaves make ONE tree of N leaves
-    if (f.rows) HIPCHK(launch_merkle_build_rows(b->d_layers + b->layer_off[0], L, lb, b->d_trees + b->tree_off[0], b->stream, nullptr, bmail(b, 0, L, 0), hash));
-    else HIPCHK(launch_merkle_build(b->d_layers + b->layer_off[0], L + lb, b->d_trees + b->tree_off[0], b->stream, nullptr, bmail(b, 0, L, lb), hash));
-    if ((rc = bpost(b, 0, L, fw))) return rc;
     ComposeBatchArgs ca;
+    const uint32_t* roots;
+    if ((rc = run_commit_f(r, ~(uint64_t)1, ca, &roots))) return rc;      // only tree 0 is the batch's
     {
-        const uint32_t one[3] = {1, 1, 1};
-        if ((rc = compose_args(d, b->d_layers + b->layer_off[0], b->d_layers + b->layer_off[1], 0, 0, one, ca.a))) return rc;
-        ca.chal = b->d_chal;
+        const size_t count = ((size_t)1 << r.fw) << b->tree_cap[0];       // up to 2 MB in ONE commit: not on the stack
+        std::vector<uint8_t> cb(32 * count);
+        for (size_t i = 0; i < count; ++i) digest_words_to_bytes(roots + 8 * i, cb.data() + 32 * i);
+        ch.commit_bytes(cb.data(), cb.size());
     }
-    const uint32_t g2 = mulmod(d->g, d->g);
-    if ((rc = bwait_roots(b))) return rc;
-    const uint32_t* roots = bfinish_roots(b, 0, L, fw);
-    commit_level(roots, ((size_t)1 << fw) << b->tree_cap[0]);
-    for (size_t p = 0; p < nb; ++p) {                                     // prover.rs:163-165 per statement, statement-major
-        const uint32_t a0 = ch.get_u32() % P, a1 = ch.get_u32() % P, a2 = ch.get_u32() % P;
-        BatchChal& c = b->h_chal[p];
-        c.first = b->first[p]; c.last = b->last[p];
-        c.alpha0_mont = to_mont(a0); c.alpha1g2_mont = to_mont(mulmod(a1, g2)); c.alpha2_mont = to_mont(a2);
-    }
-    if ((rc = bchal_upload(b))) return rc;
-    HIPCHK(launch_compose_sum_batch(ca, lb, b->stream, nullptr));         // CP: the first N words of layer 1
-    const uint32_t s0 = f.slots_log(0);
-    b->tree_steps[1] = (uint8_t)s0;
-    if (s0) HIPCHK(launch_merkle_build_coset_batch(b->d_layers + b->layer_off[1], L, s0, 0, b->d_trees + b->tree_off[1], b->stream, nullptr, bmail(b, 1, L - s0, 0), hash));
-    else HIPCHK(launch_merkle_build(b->d_layers + b->layer_off[1], L, b->d_trees + b->tree_off[1], b->stream, nullptr, bmail(b, 1, L, 0), hash));
-    if ((rc = bpost(b, 1, L - s0, 0))) return rc;
-    const bool fused = K == 1 && !coset && !stop;
-    for (uint32_t j = 0;; ++j) {                                          // zk_batch_prove's loop over the groups, one proof wide
-        const uint32_t r0 = f.round0(j);
-        if ((rc = bwait_roots(b))) return rc;
-        roots = bfinish_roots(b, 1 + r0, L - r0 - b->tree_steps[1 + r0], 0);
-        commit_level(roots, (size_t)1 << b->tree_cap[1 + r0]);            // prover.rs:180 / :224
-        if (j == G) break;
-        const uint32_t steps = f.steps(j), id = f.tree_id(j + 1);
-        const uint32_t beta = ch.get_u32();                               // prover.rs:200, once per group
-        b->h_chal[0].c_mont = fused ? to_mont(mulmod(beta % P, mulmod(invmod(powmod(d->shift, (uint64_t)1 << r0)), invmod(2)))) : beta;
-        HIPCHK(hipMemcpyAsync(b->d_chal, b->h_chal, sizeof(BatchChal), hipMemcpyHostToDevice, b->stream));
-        if (fused) {
-            FoldBatchArgs fa;
-            if ((rc = fold_args(d, b->d_layers + b->layer_off[1 + r0], b->d_layers + b->layer_off[id], L - r0, r0, 0, fa.a))) return rc;
-            fa.chal = b->d_chal;
-            HIPCHK(launch_fold_merkle_batch(fa, 0, b->d_trees + b->tree_off[id], b->stream, nullptr, bmail(b, id, L - r0 - 1, 0), hash));
-            if ((rc = bpost(b, id, L - r0 - 1, 0))) return rc;
-            continue;
-        }
-        if ((rc = dom_fold_multi_batch(d, b->d_layers + b->layer_off[1 + r0], b->d_layers + b->layer_off[id], L - r0, r0, steps, &b->d_chal->c_mont,
-                                       (uint32_t)(sizeof(BatchChal) / 4), b->d_work, 1u, b->stream, nullptr))) return rc;
-        if (stop && j + 1 == G) break;                                    // the layer the proof stops at: no tree
-        const uint32_t leaf_steps = f.slots_log(j + 1);
-        b->tree_steps[id] = (uint8_t)leaf_steps;
-        if (leaf_steps) HIPCHK(launch_merkle_build_coset_batch(b->d_layers + b->layer_off[id], L - r0 - steps, leaf_steps, 0, b->d_trees + b->tree_off[id], b->stream,
-                                                               nullptr, bmail(b, id, L - r0 - steps - leaf_steps, 0), hash));
-        else HIPCHK(launch_merkle_build(b->d_layers + b->layer_off[id], L - r0 - steps, b->d_trees + b->tree_off[id], b->stream, nullptr,
-                                        bmail(b, id, L - r0 - steps, 0), hash));
-        if ((rc = bpost(b, id, L - r0 - steps - leaf_steps, 0))) return rc;
-    }
-    static const char kWhich[] = "some trace of the batch does not satisfy the constraints (the sum does not tell which)";
-    if (stop) {                                                           // the final polynomial of the sum: row 0 of the tables
-        const size_t ncoef = (size_t)1 << stop;
-        if ((rc = dom_final_poly_batch(d, b->d_layers + b->layer_off[1 + Rp], b->d_final, L - Rp, Rp, (uint32_t)ncoef, 1u, b->stream, nullptr))) return rc;
-        HIPCHK(hipMemcpyAsync(b->h_final, b->d_final, (ncoef + 1) * 4, hipMemcpyDeviceToHost, b->stream));
-        HIPCHK(hipStreamSynchronize(b->stream));
-        if (b->h_final[0])
-            return fail(ZK_ERR_CHECK, "zk_batch_prove_shared: final FRI layer has degree >= 2^%u (%u non-zero coefficients above): %s", stop, b->h_final[0], kWhich);
-        uint8_t cb[4 << kMaxStopLog];
-        for (size_t k = 0; k < ncoef; ++k)
-            for (int i = 0; i < 4; ++i) cb[4 * k + i] = (uint8_t)(b->h_final[1 + k] >> (8 * i));
-        ch.commit_bytes(cb, 4 * ncoef);
-    } else {                                                              // prover.rs:238, :251, :254
-        HIPCHK(hipMemcpyAsync(b->h_last, b->d_layers + b->layer_off[1 + R], B * 4, hipMemcpyDeviceToHost, b->stream));
-        HIPCHK(hipStreamSynchronize(b->stream));
-        for (size_t i = 1; i < B; ++i)
-            if (b->h_last[i] != b->h_last[0]) return fail(ZK_ERR_CHECK, "zk_batch_prove_shared: last FRI layer is not constant (prover.rs:238): %s", kWhich);
-        ch.commit_u32(b->h_last[0]);
-    }
-    if (f.grind) {
-        std::vector<Channel> one(1, ch);
-        if ((rc = bgrind(b, one))) return rc;
-        ch = one[0];
-    }
-    uint32_t qraw[kMaxQueries];
-    for (uint32_t k = 0; k < Q; ++k) qraw[k] = ch.get_u32();              // prover.rs:263
-    // the openings: layer 0 and tree 0 at the batch's width (leaf = (p << L) + index; row leaves: at width one, 2^lb slots a leaf),
-    // everything else at width one
-    uint64_t *vo = b->h_goff, *dofs = b->h_goff + nv;
-    std::vector<size_t> nodes;
-    for (uint32_t k = 0; k < Q; ++k)
-        f.for_each_opening((size_t)qraw[k] % (N - 2 * B), [&](uint32_t layer, uint32_t log_leaves, size_t leaf, uint32_t slots_log) {
-            const uint32_t w = layer == 0 ? fw : 0;
-            const size_t p = leaf >> log_leaves, at = leaf & (((size_t)1 << log_leaves) - 1);   // p = 0 unless layer 0
-            for (size_t u = 0; u < ((size_t)1 << slots_log); ++u) *vo++ = b->layer_off[layer] + (p << (log_leaves + slots_log)) + at + (u << log_leaves);
-            nodes.clear();
-            path_nodes((size_t)1 << log_leaves, at, nodes);
-            nodes.resize(log_leaves - b->tree_cap[layer]);
-            uint32_t dd = log_leaves;
-            for (size_t nd : nodes) {
-                const size_t i = nd - (((size_t)1 << dd) - 1);
-                *dofs++ = (uint64_t)b->tree_off[layer] + (uint64_t)((((size_t)1 << (w + dd)) - 1) + (p << dd) + i) * 8;
-                --dd;
-            }
-        });
-    if ((size_t)(vo - b->h_goff) != nv || (size_t)(dofs - b->h_goff) != nv + ndg) return fail(ZK_ERR_STATE, "zk_batch_prove_shared: unexpected number of openings");
-    HIPCHK(hipMemcpyAsync(b->d_goff, b->h_goff, (nv + ndg) * 8, hipMemcpyHostToDevice, b->stream));
-    HIPCHK(launch_scatter(b->d_stage, b->d_segs, b->n_segs, b->seg_words, b->d_trees, nullptr, b->stream, nullptr));   // host-built levels
-    HIPCHK(launch_gather(b->d_layers, b->d_goff, (uint32_t)nv, 1, b->d_gout, b->stream, nullptr));
-    HIPCHK(launch_gather(b->d_trees, b->d_goff + nv, (uint32_t)ndg, 8, b->d_gout + nv, b->stream, nullptr));
-    HIPCHK(hipMemcpyAsync(b->h_gout, b->d_gout, (nv + ndg * 8) * 4, hipMemcpyDeviceToHost, b->stream));
-    HIPCHK(hipStreamSynchronize(b->stream));
-    const uint32_t* vals = b->h_gout;
-    const uint32_t* dw = b->h_gout + nv;
-    size_t widest = Channel::group_bytes((size_t)1 << f.steps(0), L, false);   // the first group's tuple, or a row of 2^lb values
-    if (f.rows && Channel::group_bytes(nb, L, true) > widest) widest = Channel::group_bytes(nb, L, true);
-    std::vector<uint8_t> buf(widest);
-    for (uint32_t q = 0; q < Q; ++q)
-        f.for_each_tuple([&](size_t s, size_t pl, bool one_leaf) {
-            ch.commit_group(buf.data(), s, pl, [&](size_t t) { return vals[t]; }, [&](size_t i, uint8_t* out) { digest_words_to_bytes(dw + 8 * i, out); }, one_leaf);
-            vals += s; dw += 8 * (one_leaf ? 1 : s) * pl;
-        });
-    if (ch.data.size() != plen) return fail(ZK_ERR_STATE, "zk_batch_prove_shared: unexpected proof length");
-    memcpy(proof_out, ch.data.data(), plen);
-    memcpy(state_out, ch.state, 32);
-    return ZK_OK;
+    const uint32_t g2 = mulmod(b->dom->g, b->dom->g);
+    for (size_t p = 0; p < b->batch; ++p) balphas(b, p, ch, g2);          // statement-major
+    if ((rc = bchal_upload(b, b->batch))) return rc;
+    HIPCHK(launch_compose_sum_batch(ca, lb, b->stream, nullptr));
+    if ((rc = btree(b, 1, L, f.slots_log(0), 0))) return rc;
+    if ((rc = run_groups(r)) || (rc = run_queries(r))) return rc;
+    return run_decommit(r, proof_out, 0, state_out);
 }
 
 }  // extern "C"
