@@ -726,6 +726,18 @@ uint32_t zk_verifier_get_merkle_cap(const zk_verifier *v);
 int zk_verifier_set_shared(zk_verifier *v, uint32_t log_batch, int row_leaves);
 uint32_t zk_verifier_get_shared(const zk_verifier *v);
 int zk_verifier_get_shared_rows(const zk_verifier *v);
+/* Proofs made with zk_ctx_set_ext(ext_log = 1), challenges, cp and FRI layers in E = F_P[u] / (u^2 - 5): ext_log 0
+ * (default) or 1, from the next zk_verifier_run on (a verifier may change it between runs); it combines with every fold_log, leaf
+ * format, stop_log, cap_log, query count, grinding and both hashes of this class.  zk_verifier_run then takes
+ * zk_proof_data_len_ext(log_n, log_blowup, q, grind_bits, fold_log, coset_leaves, D, c, 1) bytes and one public value per proof, and
+ * checks_out[i] is what zk_verify_ext gives proof i with the same arguments, for EVERY input, strict or not.  Kernels of their own
+ * (csrc/verify.hip "proofs over E"): both components of every comparison, row leaves of the values' words, two draws per challenge in the
+ * strict replay; proofs whose path counts differ from the fixed layout go to the CPU verifier.  A null verifier or ext_log > 1:
+ * ZK_ERR_INVALID and the setting unchanged.  Ext and shared proofs refuse each other, whichever is set second: zk_verifier_set_ext(v, 1)
+ * on a verifier with log_batch >= 1, and zk_verifier_set_shared(v, lb >= 1, .) on one with ext on, are ZK_ERR_INVALID and change nothing.
+ * With ext_log = 0 lengths, results and launches are what they were.  zk_verifier_get_ext: the current ext_log, 0 for a null verifier. */
+int zk_verifier_set_ext(zk_verifier *v, uint32_t ext_log);
+uint32_t zk_verifier_get_ext(const zk_verifier *v);
 /* count proofs at proofs + i*stride, each exactly zk_proof_data_len_fold(log_n, log_blowup, q, grind_bits, fold_log) bytes (with
  * the defaults zk_proof_data_len_queries(log_n, log_blowup, q); with coset leaves zk_proof_data_len_coset of the same arguments;
  * with an early stop zk_proof_data_len_stop; stride >= that, any alignment); states: count*32 bytes, or NULL = not strict;

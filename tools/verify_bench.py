@@ -31,7 +31,15 @@ yardstick is zk_verify_shared_rows on a 16-thread pool in this process: per sett
 of the pool, in turn, so that drift falls on both alike; both are reported as medians, a result is named NAME_lbLB[_rows]_kK[_coset]_qQ.
 A shape whose batch does not fit the device is reported with its error.
 
+--ext [E0,E1] measures proofs over E (Verifier(ext_log=1)) beside base-field proofs (bare --ext: 0,1) on 1 024 proofs of 2^13, 1 024 at
+domain 2^20 and 16 at 2^24: K = 1 with one-value leaves and K = 3 with coset leaves, q = 1, SHA-256, strict.  The proofs come from the
+one-call prover (Context(ext_log=E), a few distinct ones per setting, tiled), each checked on the CPU before it is timed.  Per setting one
+verifier per ext_log lives in the same process: --blocks rounds of --steps GPU calls per ext_log in turn, then one pass of a 16-thread
+pool per ext_log over the same proofs (zk_verify_ext; with ext_log 0 that is zk_verify_cap).  Medians; a result is named
+NAME_COUNT_kK[_coset]_extE.  --ext 0 measures the base-field side alone, the run to compare two builds by.
+
     python tools/verify_bench.py [--steps 20] [--warmup 3] [--profile] [--only NAME,...] [--fold 1,2,3 --blocks 5] [--coset] [--stop 0,4,8] [--cap 0,4,8]
+    python tools/verify_bench.py --ext [0,1] [--steps 20] [--blocks 3] [--only 2e13_1024,2e20_64,2e24_16]
     python tools/verify_bench.py --shared 3,6 [--rows] [--queries 1,16] [--steps 3 --blocks 3] [--only NAME,...]
 """
 import argparse
@@ -248,6 +256,78 @@ def shared_main(a):
                       "rows": a.rows, "shapes": res}), flush=True)
 
 
+def ext_result(log_n, log_b, count, K, coset, exts, steps, warmup, blocks):
+    """One --ext setting: per ext_log of `exts` a verifier and `count` strict SHA-256 proofs with q = 1 from the one-call prover (a few
+    distinct ones, tiled).  Every block times `steps` GPU calls per ext_log, in turn, then one pass of the 16-thread pool per ext_log over
+    the same proofs (zk_verify_ext; ext_log = 0 is zk_verify_cap, which is what is called, so the mode also runs on a build without ext)."""
+    lib = _lib.load()
+    kw = dict(queries=1, fold_log=K, coset_leaves=coset)
+    check = C.c_int32 * 1
+    runs = {}
+    for e in exts:
+        xkw = dict(kw, ext_log=1) if e else kw
+        with zk.Context(log_n, log_b, **xkw) as ctx:
+            ps = [ctx.prove(zk.trace_fibsq((1 << log_n) - 1, 1, 3141592 + p)) for p in range(16 if log_n <= 10 else (4 if log_n <= 17 else 2))]
+        for p in ps:
+            assert p.check(strict=True) == 0
+        idx = np.arange(count) % len(ps)
+        data = np.ascontiguousarray(np.stack([np.frombuffer(p.data, dtype=np.uint8) for p in ps])[idx])
+        states = np.ascontiguousarray(np.stack([np.frombuffer(p.state, dtype=np.uint8) for p in ps])[idx])
+        last = np.ascontiguousarray(np.array([p.public_last & 0xFFFFFFFF for p in ps], dtype=np.uint32)[idx])
+        runs[e] = {"v": zk.Verifier(log_n, log_b, **xkw), "data": data, "states": states, "last": last, "gpu": [], "cpu": [],
+                   "jobs": [(data[i].ctypes.data, states[i].ctypes.data, int(last[i])) for i in range(count)]}
+
+    def one(e, plen):
+        if e:
+            return lambda r: lib.zk_verify_ext(r[0], plen, r[1], log_n, log_b, r[2], 0, 1, 0, K, int(coset), 0, 0, 1, check())
+        return lambda r: lib.zk_verify_cap(r[0], plen, r[1], log_n, log_b, r[2], 0, 1, 0, K, int(coset), 0, 0, check())
+
+    try:
+        with concurrent.futures.ThreadPoolExecutor(16) as ex:
+            for e, r in runs.items():
+                assert r["v"].proof_len == r["data"].shape[1]
+                for _ in range(warmup):
+                    assert (r["v"].verify_raw(r["data"], r["last"], r["states"]) == 0).all()
+                list(ex.map(one(e, r["data"].shape[1]), r["jobs"][:16]))
+            for _ in range(blocks):
+                for e, r in runs.items():
+                    for _ in range(steps):
+                        t0 = time.perf_counter()
+                        r["v"].verify_raw(r["data"], r["last"], r["states"])
+                        r["gpu"].append((time.perf_counter() - t0) * 1e3)
+                for e, r in runs.items():
+                    t0 = time.perf_counter()
+                    rcs = list(ex.map(one(e, r["data"].shape[1]), r["jobs"], chunksize=max(1, count // 64)))
+                    r["cpu"].append((time.perf_counter() - t0) * 1e3)
+                    assert all(rc == 0 for rc in rcs)
+    finally:
+        for r in runs.values():
+            r["v"].close()
+    out = {}
+    for e, r in runs.items():
+        gpu, cpu = sorted(r["gpu"]), sorted(r["cpu"])
+        out[e] = {"log_n": log_n, "log_blowup": log_b, "count": count, "ext_log": e, "fold_log": K, "coset_leaves": coset, "queries": 1, "strict": True,
+                  "proof_bytes": int(r["data"].shape[1]), "gpu_ms_median": round(gpu[len(gpu) // 2], 4), "gpu_ms_min": round(gpu[0], 4),
+                  "gpu_ms_max": round(gpu[-1], 4), "cpu_16t_ms_median": round(cpu[len(cpu) // 2], 3), "cpu_16t_ms_min": round(cpu[0], 3),
+                  "speedup_vs_16t": round(cpu[len(cpu) // 2] / gpu[len(gpu) // 2], 2)}
+    return out
+
+
+def ext_main(a):
+    exts = tuple(int(x) for x in a.ext.split(","))
+    res = {}
+    for name, (log_n, log_b, count) in SHARED_SHAPES.items():      # 1 024 x 2^13, the batch at domain 2^20, 16 x 2^24
+        if a.only and name not in a.only.split(","):
+            continue
+        for K, coset in ((1, False), (3, True)):
+            for e, r in ext_result(log_n, log_b, 1024 if name == "2e20_64" else count, K, coset, exts, a.steps, a.warmup, a.blocks).items():
+                key = f"{name.rsplit('_', 1)[0]}_{r['count']}_k{K}" + ("_coset" if coset else "") + f"_ext{e}"
+                res[key] = r
+                print(f"# {key}: {r}", file=sys.stderr, flush=True)
+    print(json.dumps({"tool": "verify_bench", "build_hash": _lib.build_hash(), "steps": a.steps, "warmup": a.warmup, "blocks": a.blocks, "ext": list(exts),
+                      "shapes": res}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=20)
@@ -263,7 +343,11 @@ def main():
     ap.add_argument("--shared", default="", help="log_batch of shared proofs to measure, e.g. 3,6 (the shapes of SHARED_SHAPES)")
     ap.add_argument("--rows", action="store_true", help="with --shared: proofs with row leaves")
     ap.add_argument("--queries", default="1,16", help="with --shared: the query counts to measure (the batched prover makes at most 16)")
+    ap.add_argument("--ext", nargs="?", const="0,1", default="", help="ext_log values to measure, interleaved in one process (bare --ext: 0,1)")
     a = ap.parse_args()
+    if a.ext:
+        ext_main(a)
+        return
     if a.shared:
         shared_main(a)
         return

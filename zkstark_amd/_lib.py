@@ -222,6 +222,8 @@ SYMBOLS = {
     "zk_verifier_set_shared": (_int, [_vp, _u32, _int]),
     "zk_verifier_get_shared": (_u32, [_vp]),
     "zk_verifier_get_shared_rows": (_int, [_vp]),
+    "zk_verifier_set_ext": (_int, [_vp, _u32]),
+    "zk_verifier_get_ext": (_u32, [_vp]),
     "zk_verifier_run": (_int, [_vp, _vp, _sz, _sz, _vp, _vp, _vp]),
     "zk_merkle_build_host_ex": (_int, [_int, _vp, _sz, _vp, _int]),
     "zk_dev_merkle_build_ex": (_int, [_vp, _u32, _vp, _vp, _int]),

@@ -56,6 +56,21 @@
 // Its order keys are query * keys + position in verify_proof's visiting order: 0 (-2), 1 + 3p + k (-(4 + k) for statement p; rows: 1 + k),
 // with one-value leaves nft + 1 (-7), then the G fold comparisons, then the group paths (8 per group, or 1 with coset leaves);
 // keys = nft + 2 + 9G, or nft + 1 + 2G with coset leaves: at nft = 3 the keys of a plain proof (order_key_to_check).
+//
+// A proof over E = F_P[u] / (u^2 - 5) (zk_verifier_set_ext, ext_log = 1; transcript.hpp "ext"; never shared) has three kernels
+// of its own, so that the kernels above are what they were.  On the wire the alphas are six words, a beta two, the free term two (D != 0: two
+// planes of 2^D coefficients), and every cp or group tuple sends 2 s value words where it sent s: the component-0 words, then the
+// component-1 words.  The layout table gets these sizes from the same two walks (the tuple walk with the words per value); the order keys
+// are a plain proof's.
+//   * verify_ext_algebra_kernel, one lane per (proof, query): the counts behind the doubled value words; the -2 relation per component
+//     with the base-field quotients computed once; fold_group_ext, the fold in E against base-field points; the expectation in both words
+//     (D != 0: one Horner loop over both planes).  A comparison fails when either component differs;
+//   * verify_ext_paths_kernel, one lane per proof, blockIdx.y = (query, slot): the f slots are one-word leaves; every other leaf is the row
+//     leaf of the value's words (host_coset_leaf_hash): the 2 words of one value of E, not adjacent in a group tuple, or with coset leaves
+//     the 2 s contiguous words of the group, 16 of them for a full group at K = 3 (the row leaf of M = 16: two SHA-256 blocks, or two
+//     links of the field hash's chain);
+//   * verify_ext_transcript_kernel (strict): replay_transcript with two draws per challenge of E and two words per value, 6 + 2G + q
+//     challenges.
 // No kernel uses scratch or LDS; at most 116 VGPRs.
 #include <cstdio>
 #include <cstring>
@@ -100,6 +115,7 @@ struct ProofLayout {
     uint32_t fshare;            // words of one statement's share of the f commitment: 8 * 2^ce_f (rows: unused, one cap for all)
     uint32_t lb;                // log2 of the statements of a proof
     uint32_t keys;              // order keys per query (order_key_to_check): nft + 2 + 9G, or nft + 1 + 2G with coset leaves
+    uint32_t ext;               // ProofFormat::ext: 1 = cp, the groups and the free term hold values of E, two words each (the ext kernels)
 };
 
 // The launch arguments of every kernel: the buffers, the sizes and constants of the format, and the layout.
@@ -221,18 +237,9 @@ __device__ __forceinline__ Digest vinner(const Digest& l, const Digest& r) {
 // (kernels.hip), raw words >= P included: SHA-256 is one block over the s big-endian words with the padding in place, the field
 // hash the compression of (slot_0 .. slot_{s-1}, 0, ..., 0, s).  s = 1 is vleaf.  s is the same for every lane of a launch row
 // (a uniform branch skips the loads past s); the words are placed with selects on static register indices.
+// words_vleaf: from the s words already placed in v (v[i] = 0 for i >= s), for words that do not lie side by side in the proof (ext_vleaf).
 template <int HASH>
-__device__ __forceinline__ Digest coset_vleaf(const uint32_t* slots, uint32_t s) {
-    uint32_t v[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) v[i] = 0u;
-    v[0] = slots[0];
-    if (s >= 2u) v[1] = slots[1];
-    if (s >= 4u) { v[2] = slots[2]; v[3] = slots[3]; }
-    if (s >= 8u) {
-#pragma unroll
-        for (int i = 4; i < 8; ++i) v[i] = slots[i];
-    }
+__device__ __forceinline__ Digest words_vleaf(const uint32_t (&v)[8], uint32_t s) {
     Digest d;
     if constexpr (HASH == 0) {
         uint32_t w[16];
@@ -251,6 +258,20 @@ __device__ __forceinline__ Digest coset_vleaf(const uint32_t* slots, uint32_t s)
         fh64_compress(in, d.w, g_vfh_consts64);
     }
     return d;
+}
+template <int HASH>
+__device__ __forceinline__ Digest coset_vleaf(const uint32_t* slots, uint32_t s) {
+    uint32_t v[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) v[i] = 0u;
+    v[0] = slots[0];
+    if (s >= 2u) v[1] = slots[1];
+    if (s >= 4u) { v[2] = slots[2]; v[3] = slots[3]; }
+    if (s >= 8u) {
+#pragma unroll
+        for (int i = 4; i < 8; ++i) v[i] = slots[i];
+    }
+    return words_vleaf<HASH>(v, s);
 }
 
 // SHA-256(state || data[0 .. nw)) into state (channel.rs:19-26), streamed over sha256_compress.  nw is the same for every lane,
@@ -418,9 +439,12 @@ __global__ void __launch_bounds__(kVerifyThreads) verify_paths_kernel(VerifyArgs
 // the state stays in registers.  A tree's commit is the 8 * 2^ce words of its cap, a tuple's its values, counts and paths' digests; D != 0
 // drops the last tree and commits the 2^D coefficients where the free term was.
 // SHARED (a shared proof, below): na = 3 * 2^lb alphas after the f commitment, and nft f tuples (rows: 3) in front of a query's cp tuple.
-template <bool COSET, bool SHARED>
+// EXT (a plain proof over E, below): a challenge of E is vw = 2 draws in a row, so 6 alphas and cb = 2 challenge steps per beta, and every
+// value of cp, of a group and of the free term or the coefficients is vw words.  EXT = 0: vw = cb = 1, the schedule as it was.
+template <bool COSET, bool SHARED, int EXT = 0>
 __device__ __forceinline__ void replay_transcript(const VerifyArgs& a) {
-    const uint32_t na = SHARED ? 3u << a.t.lb : 3u, nft = SHARED ? a.t.nft : 3u;
+    constexpr uint32_t vw = 1u << EXT, cb = vw;
+    const uint32_t na = SHARED ? 3u << a.t.lb : 3u * vw, nft = SHARED ? a.t.nft : 3u;
     const uint32_t NF = nft + (COSET ? 0u : 1u);          // f tuples per query, cp(x) included
     const uint32_t p = blockIdx.x * kVerifyThreads + threadIdx.x;
     if (p >= a.count) return;
@@ -429,10 +453,10 @@ __device__ __forceinline__ void replay_transcript(const VerifyArgs& a) {
 #pragma unroll
     for (int i = 0; i < 8; ++i) st[i] = 0u;
     const uint32_t R = a.G, q = a.q;
-    // steps: f cap | 3 alphas | cap 0 | R x (beta, cap j + 1) | free term | [nonce] | q query raws | q x (NF f tuples, R groups)
+    // steps: f cap | na alphas | cap 0 | R x (cb betas, cap j + 1) | free term | [nonce] | q query raws | q x (NF f tuples, R groups)
     // D != 0: the last beta has no cap after it, and the step of the free term commits the 2^D coefficients
     const uint32_t gs = a.gw ? 1u : 0u;
-    const uint32_t ft = na + (a.D ? 1u : 2u) + 2u * R;
+    const uint32_t ft = na + (a.D ? 1u : 2u) + (cb + 1u) * R;
     const uint32_t head = ft + 1u + gs + q;
     const uint32_t steps = head + q * (NF + R);
     uint32_t cur = 0, k = 0;
@@ -441,18 +465,18 @@ __device__ __forceinline__ void replay_transcript(const VerifyArgs& a) {
         bool chal = false;
         uint32_t nw;
         if (s < head) {
-            chal = (s >= 1u && s <= na) || (s >= na + 2u && s < ft && ((s - na - 2u) & 1u) == 0u) || s >= ft + 1u + gs;
+            chal = (s >= 1u && s <= na) || (s >= na + 2u && s < ft && (s - na - 2u) % (cb + 1u) < cb) || s >= ft + 1u + gs;
             if (chal) nw = 1u;
             else if (s == 0u) nw = a.t.fcapn;
-            else if (s < ft) nw = a.t.capn[(s - na - 1u) >> 1];   // s = na + 1: the tree of group 0; s = na + 3 + 2j: of group j + 1 (the last layer's: entry G)
-            else nw = s == ft ? 1u << a.D : 2u;           // D = 0: the free term, one word
+            else if (s < ft) nw = a.t.capn[(s - na - 1u) / (cb + 1u)];   // s = na + 1: the tree of group 0; s = na + (cb + 1)(j + 1) + 1: of group j + 1 (the last layer's: entry G)
+            else nw = s == ft ? vw << a.D : 2u;           // D = 0: the free term, one value
         } else {
             const uint32_t u = (s - head) % (NF + R);
             if (u < nft) nw = a.t.fwords;
             else if (!COSET && u == nft) nw = a.t.cpwords;
             else {
                 const uint32_t j = u - NF, gsteps = group_steps(a, j);
-                nw = COSET ? (1u << gsteps) + 2u + 8u * a.t.plen[j] : (3u + 8u * a.t.plen[j]) << gsteps;
+                nw = COSET ? (vw << gsteps) + 2u + 8u * a.t.plen[j] : (vw + 2u + 8u * a.t.plen[j]) << gsteps;
             }
         }
         if (chal) {                                       // state word 0 (big-endian bytes 0..3) against the little-endian u32 here
@@ -640,12 +664,26 @@ __device__ __forceinline__ Digest row_vleaf(const uint32_t* vals, uint32_t M) {
 // max(M / 8, 1) compressions whose first trip is the first chunk (v_0 .. v_7, or with M < 8 the M values and zeros; then 0, .., 0, M), so
 // the kernel holds two inlined compressions, the leaf's and the inner node's, as the paths kernels of one-value leaves do.
 // pr: the proof; roww: the first word of the row tuple (M values, the count, plen digests), the same for every lane; the cap is at word 0.
+// fh_row_chain: the chain from its first chunk `in` (v_0 .. v_7, 0, .., 0, M) on; vals: the row's first word, read from word 8 on.
+__device__ __forceinline__ Digest fh_row_chain(uint32_t (&in)[kFhT], const uint32_t* vals, uint32_t M) {
+    const uint32_t nb = M > 8u ? M / 8u : 1u;
+    Digest cur;
+    uint32_t k = 1u;
+#pragma unroll 1
+    for (;;) {
+        fh64_compress(in, cur.w, g_vfh_consts64);
+        if (k >= nb) break;
+        const uint32_t* src = vals + 8u * k;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) { in[i] = cur.w[i]; in[8 + i] = src[i]; }
+        ++k;
+    }
+    return cur;
+}
 template <int HASH>
 __device__ __forceinline__ bool row_path_misses(const uint32_t* pr, uint32_t roww, uint32_t M, uint32_t plen, uint32_t idx) {
     if constexpr (HASH == 0) return path_misses<0>(row_vleaf<0>(pr + roww, M), pr + roww + M + 2u, plen, idx, pr);
     else {
-        const uint32_t nb = M > 8u ? M / 8u : 1u;
-        Digest cur;
         uint32_t in[kFhT];
 #pragma unroll
         for (int i = 0; i < 8; ++i) {                     // M < 8: the words past the values are the count and the path, loaded but not used
@@ -653,17 +691,7 @@ __device__ __forceinline__ bool row_path_misses(const uint32_t* pr, uint32_t row
             in[i] = (uint32_t)i < M ? w : 0u;
             in[8 + i] = i == 7 ? M : 0u;
         }
-        uint32_t k = 1u;
-#pragma unroll 1
-        for (;;) {
-            fh64_compress(in, cur.w, g_vfh_consts64);
-            if (k >= nb) break;
-            const uint32_t* src = pr + roww + 8u * k;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) { in[i] = cur.w[i]; in[8 + i] = src[i]; }
-            ++k;
-        }
-        return path_misses<1>(cur, pr + roww + M + 2u, plen, idx, pr);
+        return path_misses<1>(fh_row_chain(in, pr + roww, M), pr + roww + M + 2u, plen, idx, pr);
     }
 }
 
@@ -691,6 +719,217 @@ __global__ void __launch_bounds__(kVerifyThreads) verify_shared_paths_kernel(Ver
 // tuples per query.
 template <bool COSET>
 __global__ void __launch_bounds__(kVerifyThreads) verify_shared_transcript_kernel(VerifyArgs a) { replay_transcript<COSET, true>(a); }
+
+// ---- proofs over E = F_P[u] / (u^2 - 5) (zk_verifier_set_ext; the file header) -------------------------------------------------------
+// 5 a by additions (u^2 = 5): linear, so it holds for canonical and for Montgomery residues alike
+__device__ __forceinline__ uint32_t times5(uint32_t a) {
+    const uint32_t a2 = add(a, a);
+    return add(add(a2, a2), a);
+}
+
+// fold_group for a group of values of E: component 0 of value t is word (rot + t) & (S - 1) of the group, component 1 word S + that.  The
+// points are base-field, so the multiplier of round k, beta^(2^k) / x^(2^(r0 + k)), is a base scalar times a value of E; it becomes an
+// ExtConst once per round (two multiplications and 5 c1) and meets every (lo - hi) in ext.hpp's schoolbook product.  The powers of the 8th
+// root and 1/2 scale both components; beta is squared in E.  Canonical residues throughout: bit-exact against verify_proof_ext.
+template <int STEPS>
+__device__ __forceinline__ Ext fold_group_ext(const VerifyArgs& a, const uint32_t* vals, Ext beta, uint32_t& ixk, uint32_t rot = 0u) {
+    constexpr int S = 1 << STEPS;
+    Ext v[S];
+#pragma unroll
+    for (int t = 0; t < S; ++t) {
+        const uint32_t u = (rot + (uint32_t)t) & (uint32_t)(S - 1);
+        v[t] = Ext{vals[u] % P, vals[(uint32_t)S + u] % P};
+    }
+    Ext bk = beta;
+#pragma unroll
+    for (int k = 0; k < STEPS; ++k) {
+        const uint32_t ixm = mont_mul(ixk, R2);
+        ExtConst m;
+        m.c0 = dmul(bk.c0, ixm);
+        m.c1 = dmul(bk.c1, ixm);
+        m.c1w = times5(m.c1);
+#pragma unroll
+        for (int t = 0; t < (S >> (k + 1)); ++t) {
+            const int e = (8 >> STEPS) * (t << k);
+            const Ext lo = v[t], hi = v[t + (S >> (k + 1))];
+            Ext h = ext_mul_const(ext_sub(lo, hi), m);
+            if (e != 0) h = ext_scale(h, e == 1 ? a.wm1 : e == 2 ? a.wm2 : a.wm3);
+            v[t] = ext_scale(ext_add(ext_add(lo, hi), h), a.inv2m);
+        }
+        ixk = dmul(ixk, ixk);
+        bk = Ext{add(dmul(bk.c0, bk.c0), times5(dmul(bk.c1, bk.c1))), dmul(add(bk.c0, bk.c0), bk.c1)};
+    }
+    return v[0];
+}
+
+// (1) of a proof over E: one lane per (proof, query).  The three f tuples are a plain proof's; the cp tuple has two value words in front of
+// its count and a group 2 s_j.  p0, p1, p2 of the -2 relation are base-field and computed once; component c of cp takes alpha_i.c at word
+// aw + 2 i + c and is compared raw with word c of the cp value (coset leaves: slots rot0 and s_0 + rot0 of group 0's leaf).  The fold is
+// compared with both words of value 0 of the next group, with both words of the free term (raw), or with the two planes of coefficients
+// (component 0 at ftw + k, component 1 at ftw + 2^D + k) by one Horner loop at the base-field point x^(2^R').  Either component posts the key.
+template <bool COSET>
+__global__ void __launch_bounds__(kVerifyThreads) verify_ext_algebra_kernel(VerifyArgs a) {
+    const uint64_t lane = (uint64_t)blockIdx.x * kVerifyThreads + threadIdx.x;
+    if (lane >= (uint64_t)a.count * a.q) return;
+    const uint32_t p = (uint32_t)(lane / a.q), qk = (uint32_t)(lane % a.q);
+    const uint32_t* pr = a.proofs + (size_t)p * a.words;
+    const uint32_t keys = COSET ? 4u + 2u * a.G : 5u + 9u * a.G, first = COSET ? 4u : 5u;
+    const uint32_t fq = a.qbase + qk * a.per_q, cpw = fq + 3u * a.t.fwords;   // cpw: the cp tuple, or group 0's leaf
+    bool ok = true;
+    for (uint32_t j = 0; j < 3; ++j) {
+        const uint32_t* c = pr + fq + j * a.t.fwords + 1u;
+        ok = ok && c[0] == a.t.fplen && c[1] == 0u;
+    }
+    if constexpr (!COSET) ok = ok && pr[cpw + 2u] == a.t.cpplen && pr[cpw + 3u] == 0u;
+#pragma unroll 1
+    for (uint32_t j = 0; j < a.G; ++j) {
+        const uint32_t s = 1u << group_steps(a, j), len = a.t.plen[j];
+        const uint32_t* c = pr + fq + a.t.gw[j] + 2u * s;
+        if constexpr (COSET) ok = ok && c[0] == len && c[1] == 0u;
+        else for (uint32_t u = 0; u < s; ++u) ok = ok && c[u * (2u + 8u * len)] == len && c[u * (2u + 8u * len) + 1u] == 0u;
+    }
+    if (!ok) { a.malformed[p] = 1u; return; }
+
+    const uint32_t tp = query_tp(a, pr, qk);
+    const uint32_t x = dmul(GEN_W, dpow(a.h, tp));
+    int32_t key = kNoFailure;
+    {   // proof.rs:63-77 with the alphas in E
+        const uint32_t f_x = pr[fq] % P, f_gx = pr[fq + a.t.fwords] % P, f_ggx = pr[fq + 2u * a.t.fwords] % P;
+        const uint32_t p0 = dmul(sub(f_x, 1u), dinv(sub(x, 1u)));
+        const uint32_t p1 = dmul(sub(f_x, a.pub[p] % P), dinv(sub(x, a.gm2)));
+        const uint32_t num = sub(sub(f_ggx, dmul(f_gx, f_gx)), dmul(f_x, f_x));
+        uint32_t xn = x;
+        for (uint32_t i = 0; i < a.log_n; ++i) xn = dmul(xn, xn);
+        const uint32_t den = dmul(sub(xn, 1u), dinv(dmul(dmul(sub(x, a.gm3), sub(x, a.gm2)), sub(x, a.gm1))));
+        const uint32_t p2 = dmul(num, dinv(den));
+        const uint32_t* al = pr + a.t.aw;
+        const uint32_t c0w = cpw + (COSET ? coset_rot(a, tp, 0u) : 0u), c1w = c0w + (COSET ? 1u << group_steps(a, 0u) : 1u);
+        const uint32_t cp_c0 = add(add(dmul(al[0] % P, p0), dmul(al[2] % P, p1)), dmul(al[4] % P, p2));
+        const uint32_t cp_c1 = add(add(dmul(al[1] % P, p0), dmul(al[3] % P, p1)), dmul(al[5] % P, p2));
+        if (cp_c0 != pr[c0w] || cp_c1 != pr[c1w]) key = (int32_t)(qk * keys);
+    }
+    uint32_t ixk = dinv(x);                               // x = 5 h^tp is never zero: the one inversion of this lane's folds
+#pragma unroll 1
+    for (uint32_t j = 0; j < a.G && key == kNoFailure; ++j) {
+        const uint32_t* vals = pr + fq + a.t.gw[j];
+        const Ext beta{pr[a.t.bw[j]] % P, pr[a.t.bw[j] + 1u] % P};
+        const uint32_t rot = COSET ? coset_rot(a, tp, j) : 0u, steps = group_steps(a, j);
+        Ext calc;
+        if (steps == 3u) calc = fold_group_ext<3>(a, vals, beta, ixk, rot);
+        else if (steps == 2u) calc = fold_group_ext<2>(a, vals, beta, ixk, rot);
+        else calc = fold_group_ext<1>(a, vals, beta, ixk, rot);
+        Ext expect;
+        if (j + 1u < a.G) {
+            const uint32_t nw = fq + a.t.gw[j + 1u] + (COSET ? coset_rot(a, tp, j + 1u) : 0u);
+            expect = Ext{pr[nw], pr[nw + (1u << group_steps(a, j + 1u))]};
+        } else if (a.D) {
+            uint32_t xs = x;
+#pragma unroll 1
+            for (uint32_t i = 0; i < a.R; ++i) xs = dmul(xs, xs);
+            const uint32_t xm = mont_mul(xs, R2), nc = 1u << a.D;
+            const uint32_t* c = pr + a.t.ftw;
+            expect = Ext{0u, 0u};
+#pragma unroll 1
+            for (uint32_t k = nc; k-- > 0u;) expect = Ext{add(mont_mul(expect.c0, xm), c[k] % P), add(mont_mul(expect.c1, xm), c[nc + k] % P)};
+        } else expect = Ext{pr[a.t.ftw], pr[a.t.ftw + 1u]};
+        if (calc.c0 != expect.c0 || calc.c1 != expect.c1) key = (int32_t)(qk * keys + first + j);
+    }
+    if (key != kNoFailure) atomicMin(&a.best[p], key);
+}
+
+// The leaf of `width` words of a proof over E, bit for bit host_coset_leaf_hash: word 0 at w0, words 1 .. width - 1 from w1 on.  width 1 is an
+// f value (vleaf), 2 one value of E, whose components need not be adjacent, 4 and 8 a coset leaf of two or four values, 16 (WIDE only) the
+// leaf of a full group at K = 3: its 16 contiguous words as the row leaf of M = 16 (row_vleaf<0>; the field hash takes every width
+// through the one chain of row_path_misses, a single trip up to 8 words).  width is the same for every lane of a launch row.
+template <int HASH, bool WIDE>
+__device__ __forceinline__ Digest ext_vleaf(const uint32_t* pr, uint32_t w0, uint32_t w1, uint32_t width) {
+    if constexpr (HASH == 0 && WIDE) {
+        if (width == 16u) return row_vleaf<0>(pr + w0, 16u);
+    }
+    uint32_t v[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) v[i] = 0u;
+    v[0] = pr[w0];
+    if (width >= 2u) v[1] = pr[w1];
+    if constexpr (WIDE) {
+        if (width >= 4u) { v[2] = pr[w1 + 1u]; v[3] = pr[w1 + 2u]; }
+        if (width >= 8u) {
+#pragma unroll
+            for (int i = 4; i < 8; ++i) v[i] = pr[w1 + (uint32_t)(i - 1)];
+        }
+    }
+    if constexpr (HASH == 1 && WIDE) {
+        uint32_t in[kFhT];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) { in[i] = v[i]; in[8 + i] = i == 7 ? width : 0u; }
+        return fh_row_chain(in, pr + w0, width);
+    } else return words_vleaf<HASH>(v, width);
+}
+
+// (2) of a proof over E: one lane per proof, blockIdx.y = (query, slot) as in verify_paths_kernel.  Slots 0..2 are the f values, one-word
+// leaves.  Every other leaf is the row leaf of the value's words.  One-value leaves: the two words (c0, c1) of the cp tuple, and of opening
+// u of group j, which lie at gw + u and gw + s + u; the paths start behind the 2 s value words.  Coset leaves: the 2 s contiguous words of
+// the group.  The width is uniform per blockIdx.y, so a wave stays in lockstep.
+// The field-hash instance with coset leaves holds the leaf chain of verify_shared_row_paths_kernel<1> and shows the same interleaving: built
+// without a second launch bound it takes 132 VGPRs, so it asks for five waves per SIMD as that kernel does.  The other three build at or
+// under the counts of verify_paths_kernel without one (a bound of one wave asks for nothing).
+template <int HASH, bool COSET>
+__global__ void __launch_bounds__(kVerifyThreads, (HASH == 1 && COSET) ? 5 : 1) verify_ext_paths_kernel(VerifyArgs a) {
+    const uint32_t p = blockIdx.x * kVerifyThreads + threadIdx.x;
+    if (p >= a.count) return;
+    const uint32_t slots = COSET ? 3u + a.G : 4u + ((a.G - 1u) << a.K) + (1u << a.ls);
+    const uint32_t qk = blockIdx.y / slots, slot = blockIdx.y % slots;
+    const uint32_t first = COSET ? 4u : 5u;
+    const uint32_t* pr = a.proofs + (size_t)p * a.words;
+    const uint32_t tp = query_tp(a, pr, qk);
+    const uint32_t fq = a.qbase + qk * a.per_q;
+    uint32_t w0, w1, width, path_w, plen, idx, capw, pos;
+    if (slot < 3u) {                                      // f(x), f(gx), f(g^2 x) against f's cap
+        w0 = w1 = fq + slot * a.t.fwords;
+        width = 1u;
+        path_w = w0 + 3u;
+        plen = a.t.fplen;
+        idx = tp + slot * a.B;
+        capw = 0u;
+        pos = 1u + slot;
+    } else if (!COSET && slot == 3u) {                    // cp(x), one value of E, against the cap of group 0's tree
+        w0 = fq + 3u * a.t.fwords;
+        w1 = w0 + 1u;
+        width = 2u;
+        path_w = w0 + 4u;
+        plen = a.t.cpplen;
+        idx = tp;
+        capw = a.t.capw[0];
+        pos = 4u;
+    } else if constexpr (COSET) {                         // the leaf of group j: its s_j component-0 words, then its s_j component-1 words
+        const uint32_t j = slot - 3u, steps = group_steps(a, j);
+        w0 = fq + a.t.gw[j];
+        w1 = w0 + 1u;
+        width = 2u << steps;
+        path_w = w0 + width + 2u;
+        plen = a.t.plen[j];
+        idx = tp & ((1u << (a.L - j * a.K - steps)) - 1u);
+        capw = a.t.capw[j];
+        pos = first + a.G + j;
+    } else {                                              // value u of group j at (tp % size + u size / s) % size
+        const uint32_t j = (slot - 4u) >> a.K, u = (slot - 4u) & ((1u << a.K) - 1u);
+        const uint32_t gs = 1u << group_steps(a, j), gw = fq + a.t.gw[j], size = a.N >> (j * a.K);
+        plen = a.t.plen[j];
+        w0 = gw + u;
+        w1 = gw + gs + u;
+        width = 2u;
+        path_w = gw + 2u * gs + u * (2u + 8u * plen) + 2u;
+        idx = (tp % size + u * (size / gs)) % size;
+        capw = a.t.capw[j];
+        pos = first + a.G + 8u * j + u;
+    }
+    if (path_misses<HASH>(ext_vleaf<HASH, COSET>(pr, w0, w1, width), pr + path_w, plen, idx, pr + capw))
+        atomicMin(&a.best[p], (int32_t)(qk * (first + (COSET ? 2u : 9u) * a.G) + pos));
+}
+
+// (3) of a proof over E (strict only): replay_transcript with two draws per challenge of E and two words per value.
+template <bool COSET>
+__global__ void __launch_bounds__(kVerifyThreads) verify_ext_transcript_kernel(VerifyArgs a) { replay_transcript<COSET, false, 1>(a); }
 
 std::mutex g_consts_mu;
 bool g_consts_done[64] = {false};
@@ -766,7 +1005,7 @@ int verifier_chunk(zk_verifier* v, const uint8_t* proofs, size_t stride, size_t 
     const ProofFormat& f = v->fmt;
     const uint32_t log_n = f.log_n, log_b = f.log_b, q = f.q, D = f.stop, L = f.L();
     const uint32_t R = f.rounds(), K = f.fold, G = f.groups();   // the folded rounds (early stop: R', and G' groups)
-    const bool coset = f.coset, shared = f.lb != 0;
+    const bool coset = f.coset, shared = f.lb != 0, ext = f.ext != 0;   // ProofFormat::ok(): never shared and ext
     const size_t pub = (size_t)4 << f.lb;                  // bytes of a proof's public values
     // inputs: [count][len] proofs, [count][2^lb] public_last, [count][32] states, packed into the pinned staging buffer
     uint8_t* hp = v->h_in;
@@ -812,14 +1051,16 @@ int verifier_chunk(zk_verifier* v, const uint8_t* proofs, size_t stride, size_t 
     a.qbase = w;
     a.t.fplen = (uint32_t)f.f_path();
     a.t.fwords = (uint32_t)(Channel::group_bytes(f.rows ? (size_t)1 << f.lb : 1, a.t.fplen, f.rows) / 4);   // 3 + 8 fplen, or a row's 2^lb + 2 + 8 fplen
-    a.t.cpplen = (uint32_t)f.tree_path(0); a.t.cpwords = 3u + 8u * a.t.cpplen;
-    a.t.lb = f.lb; a.t.nft = f.rows ? 3u : 3u << f.lb; a.t.fshare = f.rows ? 0u : 8u << f.f_cap();
+    a.t.cpplen = (uint32_t)f.tree_path(0);
+    a.t.lb = f.lb; a.t.ext = f.ext; a.t.nft = f.rows ? 3u : 3u << f.lb; a.t.fshare = f.rows ? 0u : 8u << f.f_cap();
     a.t.keys = a.t.nft + (coset ? 1u + 2u * G : 2u + 9u * G);
     const uint32_t nf = a.t.nft + (coset ? 0u : 1u);         // the tuples in front of group 0: the f tuples and, with one-value leaves, cp(x)
     uint32_t tuple = 0, off = 0;
-    f.for_each_tuple([&](size_t s, size_t plen, bool one_leaf) {
+    f.for_each_tuple([&](size_t s, size_t plen, bool one_leaf, uint32_t words) {   // words per value: 2 for cp and the groups of an ext proof
+        const uint32_t tw = (uint32_t)(ProofFormat::tuple_bytes(s, plen, one_leaf, words) / 4);
         if (tuple >= nf) { a.t.plen[tuple - nf] = (uint32_t)plen; a.t.gw[tuple - nf] = off; }
-        off += (uint32_t)(Channel::group_bytes(s, plen, one_leaf) / 4);
+        else if (tuple == a.t.nft) a.t.cpwords = tw;       // one-value leaves: 2 + words + 8 cpplen
+        off += tw;
         ++tuple;
     });
     a.per_q = off;
@@ -840,6 +1081,9 @@ int verifier_chunk(zk_verifier* v, const uint8_t* proofs, size_t stride, size_t 
         if (shared) {
             if (coset) hipLaunchKernelGGL(verify_shared_transcript_kernel<true>, dim3(gx), dim3(kVerifyThreads), 0, v->tstream, a);
             else hipLaunchKernelGGL(verify_shared_transcript_kernel<false>, dim3(gx), dim3(kVerifyThreads), 0, v->tstream, a);
+        } else if (ext) {
+            if (coset) hipLaunchKernelGGL(verify_ext_transcript_kernel<true>, dim3(gx), dim3(kVerifyThreads), 0, v->tstream, a);
+            else hipLaunchKernelGGL(verify_ext_transcript_kernel<false>, dim3(gx), dim3(kVerifyThreads), 0, v->tstream, a);
         } else if (coset) hipLaunchKernelGGL(verify_transcript_kernel<true>, dim3(gx), dim3(kVerifyThreads), 0, v->tstream, a);
         else hipLaunchKernelGGL(verify_transcript_kernel<false>, dim3(gx), dim3(kVerifyThreads), 0, v->tstream, a);
         HIPCHK(hipGetLastError());
@@ -853,6 +1097,9 @@ int verifier_chunk(zk_verifier* v, const uint8_t* proofs, size_t stride, size_t 
             else hipLaunchKernelGGL((verify_shared_algebra_kernel<true, false>), agrid, dim3(kVerifyThreads), 0, v->stream, a);
         } else if (f.rows) hipLaunchKernelGGL((verify_shared_algebra_kernel<false, true>), agrid, dim3(kVerifyThreads), 0, v->stream, a);
         else hipLaunchKernelGGL((verify_shared_algebra_kernel<false, false>), agrid, dim3(kVerifyThreads), 0, v->stream, a);
+    } else if (ext) {
+        if (coset) hipLaunchKernelGGL(verify_ext_algebra_kernel<true>, agrid, dim3(kVerifyThreads), 0, v->stream, a);
+        else hipLaunchKernelGGL(verify_ext_algebra_kernel<false>, agrid, dim3(kVerifyThreads), 0, v->stream, a);
     } else if (coset) hipLaunchKernelGGL(verify_algebra_kernel<true>, agrid, dim3(kVerifyThreads), 0, v->stream, a);   // one instance per leaf format covers every K and D
     else hipLaunchKernelGGL(verify_algebra_kernel<false>, agrid, dim3(kVerifyThreads), 0, v->stream, a);
     HIPCHK(hipGetLastError());
@@ -877,7 +1124,13 @@ int verifier_chunk(zk_verifier* v, const uint8_t* proofs, size_t stride, size_t 
         else hipLaunchKernelGGL((verify_shared_paths_kernel<1, false>), pgrid, dim3(kVerifyThreads), 0, v->stream, a);
     } else {
         const dim3 pgrid(gx, q * (coset ? 3u + G : 4u + ((G - 1u) << K) + (1u << a.ls)));
-        if (coset) {
+        if (ext) {                                         // the same slots, leaves of the values' words
+            if (coset) {
+                if (sha) hipLaunchKernelGGL((verify_ext_paths_kernel<0, true>), pgrid, dim3(kVerifyThreads), 0, v->stream, a);
+                else hipLaunchKernelGGL((verify_ext_paths_kernel<1, true>), pgrid, dim3(kVerifyThreads), 0, v->stream, a);
+            } else if (sha) hipLaunchKernelGGL((verify_ext_paths_kernel<0, false>), pgrid, dim3(kVerifyThreads), 0, v->stream, a);
+            else hipLaunchKernelGGL((verify_ext_paths_kernel<1, false>), pgrid, dim3(kVerifyThreads), 0, v->stream, a);
+        } else if (coset) {
             if (sha) hipLaunchKernelGGL((verify_paths_kernel<0, true>), pgrid, dim3(kVerifyThreads), 0, v->stream, a);
             else hipLaunchKernelGGL((verify_paths_kernel<1, true>), pgrid, dim3(kVerifyThreads), 0, v->stream, a);
         } else if (sha) hipLaunchKernelGGL((verify_paths_kernel<0, false>), pgrid, dim3(kVerifyThreads), 0, v->stream, a);
@@ -1005,12 +1258,23 @@ int zk_verifier_set_coset_leaves(zk_verifier* v, int on) {
     return ZK_OK;
 }
 
+int zk_verifier_set_ext(zk_verifier* v, uint32_t ext_log) {
+    if (!v) return fail(ZK_ERR_INVALID, "null verifier");
+    if (ext_log > 1) return fail(ZK_ERR_INVALID, "zk_verifier_set_ext: need ext_log 0 or 1 (got %u; 2, the quartic extension, is reserved)", ext_log);
+    if (ext_log && v->fmt.lb) return fail(ZK_ERR_INVALID, "zk_verifier_set_ext: shared proofs (zk_verifier_set_shared, log_batch %u) have no ext format", v->fmt.lb);
+    v->fmt.ext = ext_log;
+    return ZK_OK;
+}
+
+uint32_t zk_verifier_get_ext(const zk_verifier* v) { return v ? v->fmt.ext : 0u; }
+
 int zk_verifier_get_coset_leaves(const zk_verifier* v) { return v && v->fmt.coset ? 1 : 0; }
 
 int zk_verifier_set_shared(zk_verifier* v, uint32_t log_batch, int row_leaves) {
     if (!v) return fail(ZK_ERR_INVALID, "null verifier");
     if (log_batch > kMaxSharedLog) return fail(ZK_ERR_INVALID, "zk_verifier_set_shared: need log_batch <= %u (got %u)", kMaxSharedLog, log_batch);
     if (row_leaves && log_batch < 1) return fail(ZK_ERR_INVALID, "zk_verifier_set_shared: row leaves need log_batch >= 1");
+    if (log_batch && v->fmt.ext) return fail(ZK_ERR_INVALID, "zk_verifier_set_shared: proofs over E (zk_verifier_set_ext, ext_log %u) are not shared", v->fmt.ext);
     v->fmt.lb = log_batch;
     v->fmt.rows = row_leaves != 0;
     return ZK_OK;

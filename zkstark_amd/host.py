@@ -788,8 +788,10 @@ class Verifier:
     that proof: 0 = accepted, otherwise the CPU verifier's check number."""
 
     def __init__(self, log_n, log_blowup, device=0, hash="sha256", queries=1, grind_bits=0, fold_log=1, coset_leaves=False, stop_log=0,
-                 cap_log=0, log_batch=0, shared_rows=False):
-        """log_batch, shared_rows: the proofs are shared proofs of 2^log_batch statements each (BatchContext.prove_shared), with row leaves
+                 cap_log=0, log_batch=0, shared_rows=False, ext_log=0):
+        """ext_log: 1 = the proofs have their challenges, cp and FRI layers in the quadratic extension E (zk_verifier_set_ext;
+        Context(ext_log=1)); not with log_batch.
+        log_batch, shared_rows: the proofs are shared proofs of 2^log_batch statements each (BatchContext.prove_shared), with row leaves
         when shared_rows (zk_verifier_set_shared; 0: plain proofs).
         cap_log: the proofs commit every tree by 2^cap_log digests (zk_verifier_set_merkle_cap; Context(cap_log=)).
         fold_log: the FRI folding factor 2^fold_log of the proofs to check (zk_verifier_set_fold; 1 = the reference).
@@ -802,6 +804,7 @@ class Verifier:
         self.stop_log = 0
         self.cap_log = 0
         self.log_batch, self.shared_rows = 0, False
+        self.ext_log = 0
         self._h = C.c_void_p()
         check(_lib.load().zk_verifier_create(device, log_n, log_blowup, C.byref(self._h)))
         if hash != "sha256":
@@ -820,10 +823,19 @@ class Verifier:
             self.set_merkle_cap(cap_log)
         if log_batch or shared_rows:
             self.set_shared(log_batch, shared_rows)
+        if ext_log:
+            self.set_ext(ext_log)
+
+    def set_ext(self, ext_log):
+        """zk_verifier_set_ext: from the next run on, check proofs over E = F_P[u] / (u^2 - 5) (1) or base-field proofs (0).  ZkError, and
+        the setting unchanged, for ext_log > 1 and for ext_log = 1 on a verifier of shared proofs."""
+        check(_lib.load().zk_verifier_set_ext(self._h, ext_log))
+        self.ext_log = ext_log
 
     def set_shared(self, log_batch, rows=False):
         """zk_verifier_set_shared: from the next run on, check shared proofs of 2^log_batch statements each (0: plain proofs), committed
-        as row leaves when rows.  public_last is then 2^log_batch values per proof."""
+        as row leaves when rows.  public_last is then 2^log_batch values per proof.  ZkError, and the setting unchanged, for
+        log_batch >= 1 on a verifier with ext on."""
         check(_lib.load().zk_verifier_set_shared(self._h, log_batch, int(bool(rows))))
         self.log_batch, self.shared_rows = log_batch, bool(rows)
 
@@ -906,6 +918,8 @@ class Verifier:
             if bool(getattr(p, "shared_rows", False)) != self.shared_rows:
                 raise ZkError(-1, f"verify: proof {i} was made with shared_rows {bool(getattr(p, 'shared_rows', False))}, "
                                   f"this verifier is set to shared_rows {self.shared_rows}")
+            if getattr(p, "ext_log", 0) != self.ext_log:
+                raise ZkError(-1, f"verify: proof {i} was made with ext_log {getattr(p, 'ext_log', 0)}, this verifier is set to ext_log {self.ext_log}")
             if len(p.data) != plen:
                 raise ZkError(-1, f"verify: proof {i} has {len(p.data)} bytes, this verifier takes {plen}")
             data[i] = np.frombuffer(p.data, dtype=np.uint8)
