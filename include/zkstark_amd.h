@@ -488,6 +488,21 @@ int zk_batch_set_merkle_cap(zk_batch *b, uint32_t cap_log);
 uint32_t zk_batch_get_merkle_cap(const zk_batch *b);
 uint32_t zk_batch_merkle_cap_log(const zk_batch *b, uint32_t tree);
 int zk_batch_merkle_cap(zk_batch *b, uint32_t tree, size_t proof, uint8_t *out, size_t out_len);
+/* Challenges in E = F_P[u] / (u^2 - 5) in the batched prover (zk_ctx_set_ext has the format): ext_log = 1, default 0, from
+ * the next zk_batch_prove on.  It combines with every fold_log, leaf format, stop_log, cap_log, query count, grinding, host-levels setting
+ * and both hashes of this class, and every proof of the batch is byte for byte the one zk_ctx_set_ext(1) + zk_prove makes of the same
+ * trace: zk_proof_data_len_ext bytes (the stride of zk_batch_prove), checked with zk_verify_ext or zk_verifier_set_ext.  With ext on
+ * the layers with id >= 1 are two planes each (component 0 first, each plane the proof-major layer of the base batch), every fold_log
+ * and leaf format takes the grouped round loop (no fused leaf launches), and a tree has as many leaves and nodes as without: the leaf
+ * of a value of E hashes its two words.  The setter sizes the planes, the gather buffers, the per-proof constants of E and the tables of
+ * the final polynomials when called, both ways (counted in zk_batch_device_bytes): with ext_log = 0, also after it was 1, every byte,
+ * launch and allocation is what it was.  ZK_ERR_INVALID for ext_log > 1 (2, the quartic extension, is reserved) or a null batch;
+ * ZK_ERR_STATE while a zk_batch_prove or another setter runs; the value it already has: ZK_OK, nothing reallocated; on ZK_ERR_NOMEM the
+ * batch keeps its setting and buffers.  log_batch = 0 forwards to zk_ctx_set_ext.  Ext and shared proofs stay apart:
+ * zk_batch_prove_shared on a batch with ext on answers ZK_ERR_STATE before any launch and leaves the batch usable.
+ * zk_batch_get_ext: the current ext_log, 0 for a null batch. */
+int zk_batch_set_ext(zk_batch *b, uint32_t ext_log);
+uint32_t zk_batch_get_ext(const zk_batch *b);
 /* on = 0: every tree level of the batch on the device (default: the host threads hash the top levels of each proof's
  * trees when the CPU has SHA extensions, as zk_ctx_set_host_levels).  Results are identical. */
 int zk_batch_set_host_levels(zk_batch *b, int on);
@@ -994,8 +1009,8 @@ int zk_dev_fri_fold_multi(const zk_dom *dom, const uint32_t *d_in, uint32_t *d_o
  * 2 N words, and plane j is what zk_dev_compose gives with (alpha0.cj, alpha1.cj, alpha2.cj) -- in one pass over f.
  * zk_dev_fri_fold_multi_ext: d_in = 2 * 2^log_m words, d_out = 2 * 2^(log_m-steps); beta_raw = (c0, c1), the challenges beta,
  * beta^2, beta^4 squared in E; steps = 1..3.  With beta_raw[1] = 0 each plane is zk_dev_fri_fold_multi of that plane.
- * The one-call prover runs them with zk_ctx_set_ext(ctx, 1); the stage-by-stage context API, the batched and sharded provers and the GPU
- * verifier are base-field; zk_verify_ext is the CPU verifier of the format. */
+ * The one-call prover runs them with zk_ctx_set_ext(ctx, 1) (the batched prover has forms of its own, zk_dev_*_ext_batch below); the
+ * stage-by-stage context API and the sharded prover are base-field; zk_verify_ext is the CPU verifier of the format. */
 int zk_dev_compose_ext(const zk_dom *dom, const uint32_t *d_f, uint32_t *d_cp, uint32_t first, uint32_t last,
                        const uint32_t alpha_raw[6], void *stream);
 int zk_dev_fri_fold_multi_ext(const zk_dom *dom, const uint32_t *d_in, uint32_t *d_out, uint32_t log_m, uint32_t round,
@@ -1006,6 +1021,24 @@ int zk_dev_fri_fold_multi_ext(const zk_dom *dom, const uint32_t *d_in, uint32_t 
  * batch >= 1 with batch * 2^log_m <= 2^32; batch = 1 gives what zk_dev_fri_fold_multi gives. */
 int zk_dev_fri_fold_multi_batch(const zk_dom *dom, const uint32_t *d_in, uint32_t *d_out, uint32_t log_m, uint32_t round,
                                 uint32_t steps, const uint32_t *d_beta_raw, uint32_t *d_work, uint32_t batch, void *stream);
+/* The kernels of the batched prover over E (zk_batch_set_ext).  A layer of E of a batch is two planes, component 0 first,
+ * each proof-major: value i of proof b at words b * len + i and batch * len + b * len + i.  Stream-ordered, no allocation.
+ * zk_dev_compose_ext_batch: d_f = [batch][N], d_cp = two planes [batch][N]; first, last ([batch]) and alpha_raw ([batch][6], in
+ * zk_dev_compose_ext's order) are HOST arrays, turned into the per-proof tables in d_work (12 * batch words, 16-byte aligned; the
+ * call waits for that copy, then launches).  Plane j of proof b is zk_dev_compose of proof b's f with component j of its alphas.
+ * zk_dev_fri_fold_multi_ext_batch: d_in = two planes [batch][2^log_m], d_out = two planes [batch][2^(log_m-steps)], proof b folded with
+ * the challenge (d_beta_raw[2 b], d_beta_raw[2 b + 1]) (raw u32 values on the device; values >= P are accepted and reduced).  d_work:
+ * 24 * batch words of scratch, 16-byte aligned.  Two launches.  Proof b's planes are zk_dev_fri_fold_multi_ext of its input planes.
+ * zk_dev_merkle_build_coset_ext_batch: d_vals = two planes [2^log_batch][2^log_len], steps 1..3 < log_len, hash 0 or 1; d_nodes: the
+ * heap over 2^(log_batch + log_len - steps) leaves, all (2 leaves - 1) * 8 words, leaf (p, c) the row leaf (zk_row_leaf_hash) of the
+ * 2 * 2^steps words d_vals[plane * batch * len + p * len + c + u * (len >> steps)], component 0's slots first.
+ * Any batch >= 1 with batch * 2^log_m <= 2^32 for the first two. */
+int zk_dev_compose_ext_batch(const zk_dom *dom, const uint32_t *d_f, uint32_t *d_cp, const uint32_t *first, const uint32_t *last,
+                             const uint32_t *alpha_raw, uint32_t *d_work, uint32_t batch, void *stream);
+int zk_dev_fri_fold_multi_ext_batch(const zk_dom *dom, const uint32_t *d_in, uint32_t *d_out, uint32_t log_m, uint32_t round,
+                                    uint32_t steps, const uint32_t *d_beta_raw, uint32_t *d_work, uint32_t batch, void *stream);
+int zk_dev_merkle_build_coset_ext_batch(const uint32_t *d_vals, uint32_t log_len, uint32_t steps, uint32_t log_batch, uint32_t *d_nodes,
+                                        void *stream, int hash_kind);
 /* Batch trace generation: prover.rs:32-39 is serial per trace, so one
  * lane generates one trace; out[t*count + i] = a_i of trace t seeded by (a0[t], a1[t]). */
 int zk_dev_trace_fibsq_batch(const uint32_t *d_a0, const uint32_t *d_a1, uint32_t batch, uint32_t count,

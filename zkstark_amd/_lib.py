@@ -168,6 +168,9 @@ SYMBOLS = {
     "zk_verify_stop": (_int, [_vp, _sz, _vp, _u32, _u32, _u32, _int, _u32, _u32, _u32, _int, _u32, C.POINTER(C.c_int32)]),
     "zk_dev_fri_fold_multi": (_int, [_vp, _vp, _vp, _u32, _u32, _u32, _u32, _vp]),
     "zk_dev_fri_fold_multi_batch": (_int, [_vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _u32, _vp]),
+    "zk_dev_compose_ext_batch": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp]),
+    "zk_dev_fri_fold_multi_ext_batch": (_int, [_vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _u32, _vp]),
+    "zk_dev_merkle_build_coset_ext_batch": (_int, [_vp, _u32, _u32, _u32, _vp, _vp, _int]),
     "zk_batch_set_fold": (_int, [_vp, _u32]),
     "zk_batch_get_fold": (_u32, [_vp]),
     "zk_proof_data_len_fold": (_sz, [_u32, _u32, _u32, _u32, _u32]),
@@ -209,6 +212,8 @@ SYMBOLS = {
     "zk_batch_get_coset_leaves": (_int, [_vp]),
     "zk_batch_set_fri_stop": (_int, [_vp, _u32]),
     "zk_batch_get_fri_stop": (_u32, [_vp]),
+    "zk_batch_set_ext": (_int, [_vp, _u32]),
+    "zk_batch_get_ext": (_u32, [_vp]),
     "zk_batch_set_merkle_cap": (_int, [_vp, _u32]),
     "zk_batch_get_merkle_cap": (_u32, [_vp]),
     "zk_batch_merkle_cap_log": (_u32, [_vp, _u32]),

@@ -18,6 +18,11 @@
 // Early stop (zk_batch_set_fri_stop, D > 0): the groups are those of the first R' = log_n - D rounds, every K folds with the batched
 // multi-fold, the last group's output (layer 1 + R' of the batch) gets no tree; one launch of fri_final_poly_batch_kernel turns it into
 // the compact [batch][1 + 2^D] table (count, coefficients) and each proof's channel commits its own 4 * 2^D bytes -- prove_finish per proof.
+// Challenges in E (zk_batch_set_ext): the layers >= 1 are two planes [batch][m_l] each, the component-1 halves of every
+// proof's challenges sit in a table beside BatchChal, cp comes from one launch of compose_ext_batch_kernel, every K and leaf format takes
+// the grouped loop with the batched butterfly over E, the trees are the row tree over the two planes (one-value leaves) or come from
+// launch_merkle_build_coset_ext_batch, and a query gathers the component-0 slots of a leaf, then its component-1 slots --
+// prove_ext_rounds / prove_finish (zkstark.hip) per proof.  zk_batch_prove only: a shared proof has no ext format.
 #include <atomic>
 #include <condition_variable>
 #include <cstdio>
@@ -101,12 +106,23 @@ struct zk_batch {
     // no per-round challenge table), so the smallest batch is never slower than zk_prove.
     zk_ctx* single = nullptr;
     std::vector<uint32_t> single_trace;
+    // Challenges in E (zk_batch_set_ext; transcript.hpp "ext").  With fmt.ext = 1 layer id >= 1 is two planes, component 0
+    // first, each the proof-major [batch][m_l] layer above; they lie behind the base layers in d_layers, from word ext_base on (the setter
+    // sizes d_layers both ways, as zk_ctx_set_ext does).  layer_words: the base layers.  xchal: the component-1 halves of every proof's
+    // challenges beside its BatchChal row; d_xwork: [batch][kFoldExtRow] constants of E of the group fold; h_xlast: plane 1 of the last
+    // layer, [batch][B], behind h_xchal in one pinned block.  All four exist only while ext is on.
+    size_t layer_words = 0, ext_base = 0;
+    BatchChalExt *h_xchal = nullptr, *d_xchal = nullptr;
+    uint32_t *d_xwork = nullptr, *h_xlast = nullptr;
 };
 
 namespace {
 
 size_t blayer_size(const zk_batch* b, uint32_t layer) { return layer == 0 ? b->N : (b->N >> (layer - 1)); }
 uint32_t blayer_log(const zk_batch* b, uint32_t layer) { return layer == 0 ? b->L : b->L - (layer - 1); }
+// Layer id >= 1 of an ext batch: two planes of batch * m_l words, component 0 first
+size_t bext_off(const zk_batch* b, uint32_t id) { return b->ext_base + 2 * (b->layer_off[id] - b->layer_off[1]); }
+uint32_t* bext_layer(zk_batch* b, uint32_t id) { return b->d_layers + bext_off(b, id); }
 
 // Levels of each proof's tree (over 2^log_m leaves) that the host hashes: as many as the mailbox holds
 // (2^kMaxHostLog digests for the whole batch), none for the field hash or without SHA extensions.
@@ -211,7 +227,7 @@ const uint32_t* bfinish_roots(zk_batch* b, uint32_t tree, uint32_t log_m, uint32
 // values and path digests one query opens
 void bopenings(const ProofFormat& f, size_t* vals, size_t* digs) {
     *vals = *digs = 0;
-    f.for_each_tuple([&](size_t s, size_t plen, bool one_leaf) { *vals += s; *digs += (one_leaf ? 1 : s) * plen; });
+    f.for_each_tuple([&](size_t s, size_t plen, bool one_leaf, uint32_t words) { *vals += s * words; *digs += (one_leaf ? 1 : s) * plen; });
 }
 // gather buffers for q queries per proof (offsets in, values + digests out; device and pinned host copies), for the current fold
 int balloc_gather(zk_batch* b, uint32_t q) {
@@ -228,10 +244,11 @@ int balloc_gather(zk_batch* b, uint32_t q) {
     return ZK_OK;
 }
 
-// The batch goes to the format `next` (fold, coset, stop, cap; q and grind have setters of their own): d_work for the multi-fold (every
-// fold > 1, and every fold with coset leaves or an early stop), the [batch][1 + 2^stop] tables of the final polynomials, the gather buffers
-// for what a query of that format opens, the pinned buffer for caps the mailbox cannot hold.  On failure the batch keeps its settings
-// and the buffers they need.
+// The batch goes to the format `next` (fold, coset, stop, cap, ext; q and grind have setters of their own): d_work for the multi-fold (every
+// fold > 1, and every fold with coset leaves or an early stop), the [batch][1 + 2^stop] tables of the final polynomials (two rows per proof
+// with ext), the gather buffers for what a query of that format opens, the pinned buffer for caps the mailbox cannot hold and, when ext
+// changes, d_layers with or without the planes, the component-1 challenge table and the constants of E.  Every new buffer is allocated
+// before an old one goes: on failure the batch keeps its settings and the buffers they need.
 int bset_format(zk_batch* b, const ProofFormat& next, const char* who) {
     const uint32_t stop = next.stop;
     HIPCHK(hipSetDevice(b->device));
@@ -241,32 +258,42 @@ int bset_format(zk_batch* b, const ProofFormat& next, const char* who) {
         if (e != hipSuccess) return fail(ZK_ERR_NOMEM, "%s: hipMalloc(%zu) failed: %s", who, b->batch * 32, hipGetErrorString(e));
         b->device_bytes += b->batch * 32;
     }
-    auto final_bytes = [&](uint32_t D) { return D ? b->batch * (((size_t)1 << D) + 1) * 4 : (size_t)0; };
+    auto final_bytes = [&](const ProofFormat& f) { return f.stop ? (b->batch << f.ext) * (((size_t)1 << f.stop) + 1) * 4 : (size_t)0; };
+    const bool ext_change = next.ext != b->fmt.ext, final_change = final_bytes(next) != final_bytes(b->fmt);
     uint32_t *nd_final = nullptr, *nh_final = nullptr;    // the new tables first: the old ones stay until nothing can fail any more
-    if (stop && stop != b->fmt.stop) {
-        hipError_t e = hipMalloc((void**)&nd_final, final_bytes(stop));
-        if (e == hipSuccess && (e = hipHostMalloc((void**)&nh_final, final_bytes(stop))) != hipSuccess) { (void)hipFree(nd_final); nd_final = nullptr; }
-        if (e != hipSuccess) return fail(ZK_ERR_NOMEM, "%s: allocating %zu bytes for the final polynomials failed: %s", who, final_bytes(stop), hipGetErrorString(e));
+    uint32_t *nh_cap = nullptr, *nd_cap = nullptr, *nd_layers = nullptr, *nd_xwork = nullptr;
+    BatchChalExt *nd_xchal = nullptr, *nh_xchal = nullptr;
+    auto undo = [&] {
+        for (void* p : {(void*)nd_final, (void*)nd_layers, (void*)nd_xwork, (void*)nd_xchal}) if (p) (void)hipFree(p);
+        for (void* p : {(void*)nh_final, (void*)nh_cap, (void*)nh_xchal}) if (p) (void)hipHostFree(p);
+    };
+    if (final_change && stop) {
+        hipError_t e = hipMalloc((void**)&nd_final, final_bytes(next));
+        if (e == hipSuccess) e = hipHostMalloc((void**)&nh_final, final_bytes(next));
+        if (e != hipSuccess) { undo(); return fail(ZK_ERR_NOMEM, "%s: allocating %zu bytes for the final polynomials failed: %s", who, final_bytes(next), hipGetErrorString(e)); }
     }
     const size_t cap_words = bcap_words(b, next);
-    uint32_t *nh_cap = nullptr, *nd_cap = nullptr;
     if (cap_words && cap_words != b->cap_words) {
         hipError_t e = hipHostMalloc((void**)&nh_cap, cap_words * 4, hipHostMallocMapped | hipHostMallocCoherent);
-        if (e == hipSuccess && (e = hipHostGetDevicePointer((void**)&nd_cap, nh_cap, 0)) != hipSuccess) (void)hipHostFree(nh_cap);
-        if (e != hipSuccess) {
-            if (nd_final) (void)hipFree(nd_final);
-            if (nh_final) (void)hipHostFree(nh_final);
-            return fail(ZK_ERR_NOMEM, "%s: allocating %zu pinned bytes for the Merkle caps failed: %s", who, cap_words * 4, hipGetErrorString(e));
-        }
+        if (e == hipSuccess) e = hipHostGetDevicePointer((void**)&nd_cap, nh_cap, 0);
+        if (e != hipSuccess) { undo(); return fail(ZK_ERR_NOMEM, "%s: allocating %zu pinned bytes for the Merkle caps failed: %s", who, cap_words * 4, hipGetErrorString(e)); }
+    }
+    // ext: the planes of the layers >= 1 behind the base layers; the component-1 challenges, plane 1 of the last layer, the constants of E
+    const size_t plane_words = 2 * (b->layer_words - b->N * b->batch), xwork_bytes = b->batch * kFoldExtRow * 4, xchal_bytes = b->batch * sizeof(BatchChalExt);
+    if (ext_change) {
+        const size_t words = b->layer_words + (next.ext ? plane_words : 0);
+        hipError_t e = hipMalloc((void**)&nd_layers, words * 4);
+        if (e == hipSuccess && next.ext) e = hipMalloc((void**)&nd_xwork, xwork_bytes);
+        if (e == hipSuccess && next.ext) e = hipMalloc((void**)&nd_xchal, xchal_bytes);
+        if (e == hipSuccess && next.ext) e = hipHostMalloc((void**)&nh_xchal, xchal_bytes + b->batch * b->B * 4);
+        if (e != hipSuccess) { undo(); return fail(ZK_ERR_NOMEM, "%s: allocating the layers of %zu words failed: %s", who, words, hipGetErrorString(e)); }
     }
     const size_t old_vals = b->per_proof_vals, old_digs = b->per_proof_digs;
     bopenings(next, &b->per_proof_vals, &b->per_proof_digs);
     if (int rc = balloc_gather(b, b->fmt.q)) {            // the old buffers are gone: put back what the old format needs, or fail again later
         b->per_proof_vals = old_vals; b->per_proof_digs = old_digs;
         (void)balloc_gather(b, b->fmt.q);
-        if (nd_final) (void)hipFree(nd_final);
-        if (nh_final) (void)hipHostFree(nh_final);
-        if (nh_cap) (void)hipHostFree(nh_cap);
+        undo();
         return rc;
     }
     if (cap_words != b->cap_words) {                      // cap 0, or a cap the mailbox holds, gives the buffer back
@@ -275,12 +302,21 @@ int bset_format(zk_batch* b, const ProofFormat& next, const char* who) {
         b->device_bytes -= b->cap_words * 4;
         b->h_cap = nh_cap; b->d_cap = nd_cap; b->cap_words = cap_words;
     }
-    if (stop != b->fmt.stop) {                            // stop = 0 gives the tables back
+    if (final_change) {                                   // stop = 0 gives the tables back
         if (b->d_final) (void)hipFree(b->d_final);
         if (b->h_final) (void)hipHostFree(b->h_final);
-        b->device_bytes += final_bytes(stop);
-        b->device_bytes -= final_bytes(b->fmt.stop);
+        b->device_bytes += final_bytes(next);
+        b->device_bytes -= final_bytes(b->fmt);
         b->d_final = nd_final; b->h_final = nh_final;
+    }
+    if (ext_change) {                                     // ext = 0 gives the planes and the tables of E back; the last proof's layers go
+        for (void* p : {(void*)b->d_layers, (void*)b->d_xwork, (void*)b->d_xchal}) if (p) (void)hipFree(p);
+        if (b->h_xchal) (void)hipHostFree(b->h_xchal);
+        const size_t bytes = plane_words * 4 + xwork_bytes + xchal_bytes;
+        if (next.ext) b->device_bytes += bytes; else b->device_bytes -= bytes;
+        b->d_layers = nd_layers; b->d_xwork = nd_xwork; b->d_xchal = nd_xchal; b->h_xchal = nh_xchal;
+        b->h_xlast = nh_xchal ? reinterpret_cast<uint32_t*>(nh_xchal + b->batch) : nullptr;
+        b->ext_base = next.ext ? b->layer_words : 0;
     }
     b->fmt = next;
     return ZK_OK;
@@ -289,6 +325,7 @@ int bset_format(zk_batch* b, const ProofFormat& next, const char* who) {
 // the first `count` entries of the challenge table: the batch's for the alphas, afterwards one per channel
 int bchal_upload(zk_batch* b, size_t count) {
     HIPCHK(hipMemcpyAsync(b->d_chal, b->h_chal, count * sizeof(BatchChal), hipMemcpyHostToDevice, b->stream));
+    if (b->fmt.ext) HIPCHK(hipMemcpyAsync(b->d_xchal, b->h_xchal, count * sizeof(BatchChalExt), hipMemcpyHostToDevice, b->stream));   // component 1 beside
     return ZK_OK;
 }
 
@@ -327,10 +364,25 @@ void balphas(zk_batch* b, size_t p, Channel& ch, uint32_t g2) {
     c.first = b->first[p]; c.last = b->last[p];
     c.alpha0_mont = to_mont(a0); c.alpha1g2_mont = to_mont(mulmod(a1, g2)); c.alpha2_mont = to_mont(a2);
 }
+// ... over E: six draws, alpha0.c0, alpha0.c1, alpha1.c0, .. (prove_ext_rounds' order); component 1 goes to the row of the table beside
+void balphas_ext(zk_batch* b, size_t p, Channel& ch, uint32_t g2) {
+    uint32_t a[6];
+    for (uint32_t& v : a) v = ch.get_u32() % P;
+    BatchChal& c = b->h_chal[p];
+    c.first = b->first[p]; c.last = b->last[p];
+    c.alpha0_mont = to_mont(a[0]); c.alpha1g2_mont = to_mont(mulmod(a[2], g2)); c.alpha2_mont = to_mont(a[4]);
+    b->h_xchal[p] = BatchChalExt{to_mont(a[1]), to_mont(mulmod(a[3], g2)), to_mont(a[5]), 0u};
+}
 // The tree over layer `id` of a stage of width w: 2^log_len values per proof, 2^leaf_steps to a leaf (0: one-value leaves, prover.rs:214).
-int btree(zk_batch* b, uint32_t id, uint32_t log_len, uint32_t leaf_steps, uint32_t w) {
+// ext: the layer is two planes and a leaf hashes its component-0 words, then its component-1 words (transcript.hpp "ext").  With one-value
+// leaves the batch heap over 2^(w + log_len) leaves IS the row tree of the [2][2^(w + log_len)] array the planes are; with coset leaves the
+// slots of a leaf are strided inside one proof and the leaves come from a launch of their own.  Same heap, same hand-over either way.
+int btree(zk_batch* b, uint32_t id, uint32_t log_len, uint32_t leaf_steps, uint32_t w, bool ext = false) {
     b->tree_steps[id] = (uint8_t)leaf_steps;
-    if (leaf_steps) HIPCHK(launch_merkle_build_coset_batch(b->d_layers + b->layer_off[id], log_len, leaf_steps, w, b->d_trees + b->tree_off[id], b->stream, nullptr,
+    if (ext && leaf_steps) HIPCHK(launch_merkle_build_coset_ext_batch(bext_layer(b, id), log_len, leaf_steps, w, b->d_trees + b->tree_off[id], b->stream, nullptr,
+                                                                      bmail(b, id, log_len - leaf_steps, w), b->hash));
+    else if (ext) HIPCHK(launch_merkle_build_rows(bext_layer(b, id), log_len + w, 1, b->d_trees + b->tree_off[id], b->stream, nullptr, bmail(b, id, log_len, w), b->hash));
+    else if (leaf_steps) HIPCHK(launch_merkle_build_coset_batch(b->d_layers + b->layer_off[id], log_len, leaf_steps, w, b->d_trees + b->tree_off[id], b->stream, nullptr,
                                                            bmail(b, id, log_len - leaf_steps, w), b->hash));
     else HIPCHK(launch_merkle_build(b->d_layers + b->layer_off[id], log_len + w, b->d_trees + b->tree_off[id], b->stream, nullptr, bmail(b, id, log_len, w), b->hash));
     return bpost(b, id, log_len - leaf_steps, w);
@@ -372,7 +424,7 @@ int run_groups(Run& r) {
     const zk_dom* d = b->dom;
     const size_t np = r.ch.size();
     const uint32_t w = r.w, L = b->L, G = f.groups();
-    const bool fused = f.fold == 1 && !f.coset && !f.stop;                // the fold inside the leaf hashing of its tree
+    const bool fused = f.fold == 1 && !f.coset && !f.stop && !f.ext;      // the fold inside the leaf hashing of its tree
     int rc;
     for (uint32_t j = 0;; ++j) {                                          // tree 1 + r0 is the last one launched
         const uint32_t r0 = f.round0(j);
@@ -392,6 +444,7 @@ int run_groups(Run& r) {
             commit_cap(r.ch[p], roots + ((p << ce) * 8), ce);
             const uint32_t beta = r.ch[p].get_u32();
             b->h_chal[p].c_mont = fused ? to_mont(mulmod(beta % P, winv_half)) : beta;
+            if (f.ext) b->h_xchal[p].beta1 = r.ch[p].get_u32();           // beta.c1, raw as well (prove_ext_rounds)
         });
         cap_lap(r, ce, tc);
         if ((rc = bchal_upload(b, np))) return rc;
@@ -403,14 +456,17 @@ int run_groups(Run& r) {
             if ((rc = bpost(b, id, L - r0 - 1, w))) return rc;
             continue;
         }
-        if ((rc = dom_fold_multi_batch(d, b->d_layers + b->layer_off[1 + r0], b->d_layers + b->layer_off[id], L - r0, r0, steps, &b->d_chal->c_mont,
-                                       (uint32_t)(sizeof(BatchChal) / 4), b->d_work, (uint32_t)np, b->stream, nullptr))) return rc;
+        if (f.ext) {                                                      // the same butterfly over E, both planes in one launch
+            if ((rc = dom_fold_multi_ext_batch(d, bext_layer(b, 1 + r0), bext_layer(b, id), L - r0, r0, steps, &b->d_chal->c_mont, (uint32_t)(sizeof(BatchChal) / 4),
+                                               &b->d_xchal->beta1, (uint32_t)(sizeof(BatchChalExt) / 4), b->d_xwork, (uint32_t)np, b->stream, nullptr))) return rc;
+        } else if ((rc = dom_fold_multi_batch(d, b->d_layers + b->layer_off[1 + r0], b->d_layers + b->layer_off[id], L - r0, r0, steps, &b->d_chal->c_mont,
+                                              (uint32_t)(sizeof(BatchChal) / 4), b->d_work, (uint32_t)np, b->stream, nullptr))) return rc;
         for (uint32_t l = 2 + r0; l < id; ++l) b->skipped_trees |= (uint64_t)1 << l;
         if (f.stop && j + 1 == G) {
             for (uint32_t l = id; l <= b->R + 1; ++l) b->skipped_trees |= (uint64_t)1 << l;
             break;
         }
-        if ((rc = btree(b, id, L - r0 - steps, f.slots_log(j + 1), w))) return rc;
+        if ((rc = btree(b, id, L - r0 - steps, f.slots_log(j + 1), w, f.ext != 0))) return rc;
     }
     lap(r, "lde .. last roots");
     if (btiming()) fprintf(stderr, "[zk batch timing]   of which waiting for the device %.1f us\n", r.t_wait);
@@ -431,35 +487,44 @@ int run_queries(Run& r) {
     const size_t ncoef = (size_t)1 << stop, frow = ncoef + 1;
     static const char kWhich[] = "some trace of the batch does not satisfy the constraints (the sum does not tell which)";
     const bool shared = f.lb != 0;                                        // whose failure no single trace answers for
+    const size_t planes = (size_t)1 << f.ext;                             // ext: plane 1's layers, rows and values follow plane 0's np
     int rc;
     if (stop) {
-        if ((rc = dom_final_poly_batch(b->dom, b->d_layers + b->layer_off[1 + Rp], b->d_final, L - Rp, Rp, (uint32_t)ncoef, (uint32_t)np, b->stream, nullptr))) return rc;
-        HIPCHK(hipMemcpyAsync(b->h_final, b->d_final, np * frow * 4, hipMemcpyDeviceToHost, b->stream));
+        const uint32_t* last = f.ext ? bext_layer(b, 1 + Rp) : b->d_layers + b->layer_off[1 + Rp];
+        if ((rc = dom_final_poly_batch(b->dom, last, b->d_final, L - Rp, Rp, (uint32_t)ncoef, (uint32_t)(planes * np), b->stream, nullptr))) return rc;
+        HIPCHK(hipMemcpyAsync(b->h_final, b->d_final, planes * np * frow * 4, hipMemcpyDeviceToHost, b->stream));
         HIPCHK(hipStreamSynchronize(b->stream));
         for (size_t p = 0; p < np; ++p) {
-            const uint32_t above = b->h_final[p * frow];
+            const uint32_t above = b->h_final[p * frow] + (f.ext ? b->h_final[(np + p) * frow] : 0u);   // either plane's high coefficients
             if (above && shared) return fail(ZK_ERR_CHECK, "%s: final FRI layer has degree >= 2^%u (%u non-zero coefficients above): %s", r.who, stop, above, kWhich);
             if (above)
                 return fail(ZK_ERR_CHECK, "proof %zu of the batch: final FRI layer has degree >= 2^%u: its trace does not satisfy the constraints (%u non-zero coefficients above; cf. prover.rs:238)",
                             p, stop, above);
         }
     } else {
-        HIPCHK(hipMemcpyAsync(b->h_last, b->d_layers + b->layer_off[1 + b->R], np * B * 4, hipMemcpyDeviceToHost, b->stream));
+        const uint32_t* last = f.ext ? bext_layer(b, 1 + b->R) : b->d_layers + b->layer_off[1 + b->R];
+        HIPCHK(hipMemcpyAsync(b->h_last, last, np * B * 4, hipMemcpyDeviceToHost, b->stream));
+        if (f.ext) HIPCHK(hipMemcpyAsync(b->h_xlast, last + np * B, np * B * 4, hipMemcpyDeviceToHost, b->stream));
         HIPCHK(hipStreamSynchronize(b->stream));
         for (size_t p = 0; p < np; ++p)
             for (size_t i = 1; i < B; ++i) {
-                if (b->h_last[p * B + i] == b->h_last[p * B]) continue;
+                if (b->h_last[p * B + i] == b->h_last[p * B] && (!f.ext || b->h_xlast[p * B + i] == b->h_xlast[p * B])) continue;
                 if (shared) return fail(ZK_ERR_CHECK, "%s: last FRI layer is not constant (prover.rs:238): %s", r.who, kWhich);
                 return fail(ZK_ERR_CHECK, "proof %zu of the batch: last FRI layer is not constant (prover.rs:238): its trace does not satisfy the constraints", p);
             }
     }
+    // ext: (c0, c1) of the free term, or the 2^stop component-0 coefficients, then the component-1 ones, in ONE commit (prove_finish)
     auto commit_final = [&](size_t p) {
-        if (!stop) { r.ch[p].commit_u32(b->h_last[p * B]); return; }
-        uint8_t cb[4 << kMaxStopLog];
-        const uint32_t* c = b->h_final + p * frow + 1;
-        for (size_t k = 0; k < ncoef; ++k)
-            for (int i = 0; i < 4; ++i) cb[4 * k + i] = (uint8_t)(c[k] >> (8 * i));
-        r.ch[p].commit_bytes(cb, 4 * ncoef);
+        if (!stop && !f.ext) { r.ch[p].commit_u32(b->h_last[p * B]); return; }
+        uint8_t cb[8 << kMaxStopLog];
+        size_t n = 0;
+        auto put = [&](uint32_t v) { for (int i = 0; i < 4; ++i) cb[n++] = (uint8_t)(v >> (8 * i)); };
+        for (size_t plane = 0; plane < planes; ++plane) {
+            if (!stop) { put(plane ? b->h_xlast[p * B] : b->h_last[p * B]); continue; }
+            const uint32_t* c = b->h_final + (plane * np + p) * frow + 1;
+            for (size_t k = 0; k < ncoef; ++k) put(c[k]);
+        }
+        r.ch[p].commit_bytes(cb, n);
     };
     bopenings(f, &r.nv, &r.ndg);
     r.nv *= Q; r.ndg *= Q;
@@ -487,7 +552,11 @@ int run_queries(Run& r) {
             f.for_each_opening((size_t)qraw[k] % (N - 2 * B), [&](uint32_t layer, uint32_t log_m, size_t leaf, uint32_t slots_log) {
                 const uint32_t wl = layer == 0 ? r.fw : r.w;
                 const size_t p = c + (leaf >> log_m), at = leaf & (((size_t)1 << log_m) - 1);
-                for (size_t u = 0; u < ((size_t)1 << slots_log); ++u) *vo++ = b->layer_off[layer] + (p << (log_m + slots_log)) + at + (u << log_m);
+                if (f.ext && layer >= 1) {                                // a leaf of E: its component-0 slots, then its component-1 slots
+                    for (size_t plane = 0; plane < 2; ++plane)
+                        for (size_t u = 0; u < ((size_t)1 << slots_log); ++u)
+                            *vo++ = bext_off(b, layer) + ((plane * np + p) << (log_m + slots_log)) + at + (u << log_m);
+                } else for (size_t u = 0; u < ((size_t)1 << slots_log); ++u) *vo++ = b->layer_off[layer] + (p << (log_m + slots_log)) + at + (u << log_m);
                 nodes.clear();
                 path_nodes((size_t)1 << log_m, at, nodes);
                 nodes.resize(log_m - b->tree_cap[layer]);
@@ -518,7 +587,7 @@ int run_decommit(Run& r, uint8_t* proofs_out, size_t stride, uint8_t* states_out
     HIPCHK(hipMemcpyAsync(b->h_gout, b->d_gout, (tv + td * 8) * 4, hipMemcpyDeviceToHost, b->stream));
     HIPCHK(hipStreamSynchronize(b->stream));
     lap(r, "gather");
-    size_t widest = Channel::group_bytes((size_t)1 << f.steps(0), b->L, false);   // the first group's tuple, or a row of 2^lb values
+    size_t widest = ProofFormat::tuple_bytes((size_t)1 << f.steps(0), b->L, false, 1u << f.ext);   // the first group's tuple, or a row of 2^lb values
     if (f.rows && Channel::group_bytes(b->batch, b->L, true) > widest) widest = Channel::group_bytes(b->batch, b->L, true);
     std::atomic<int> bad{0};
     b->pool->run(np, 4, [&](size_t c) {
@@ -526,9 +595,11 @@ int run_decommit(Run& r, uint8_t* proofs_out, size_t stride, uint8_t* states_out
         const uint32_t* vals = b->h_gout + c * nv;
         const uint32_t* dw = b->h_gout + tv + c * ndg * 8;
         std::vector<uint8_t> buf(widest);                                 // one buffer per channel
-        auto tuple = [&](size_t s, size_t pl, bool one_leaf) {
-            ch.commit_group(buf.data(), s, pl, [&](size_t t) { return vals[t]; }, [&](size_t i, uint8_t* out) { digest_words_to_bytes(dw + 8 * i, out); }, one_leaf);
-            vals += s; dw += 8 * (one_leaf ? 1 : s) * pl;
+        // the values were gathered opening by opening (for a value of E: c0, c1); a tuple of s openings sends the s c0 words, then the s c1 words
+        auto tuple = [&](size_t s, size_t pl, bool one_leaf, uint32_t words) {
+            ch.commit_group(buf.data(), s, pl, [&](size_t t) { return vals[words == 2 && !one_leaf ? (t % s) * 2 + t / s : t]; },
+                            [&](size_t i, uint8_t* out) { digest_words_to_bytes(dw + 8 * i, out); }, one_leaf, words);
+            vals += s * words; dw += 8 * (one_leaf ? 1 : s) * pl;
         };
         for (uint32_t q = 0; q < f.q; ++q) f.for_each_tuple(tuple);
         if (ch.data.size() != plen) { bad.store(1); return; }
@@ -550,9 +621,9 @@ int zk_batch_destroy(zk_batch* b) {
     if (b->stream) (void)hipStreamSynchronize(b->stream);
     dom_free(b->dom);
     for (void* p : {(void*)b->d_trace, (void*)b->d_coef, (void*)b->d_layers, (void*)b->d_trees, (void*)b->d_seed, (void*)b->d_chal,
-                    (void*)b->d_counter, (void*)b->d_goff, (void*)b->d_gout, (void*)b->d_work, (void*)b->d_final})
+                    (void*)b->d_counter, (void*)b->d_goff, (void*)b->d_gout, (void*)b->d_work, (void*)b->d_final, (void*)b->d_xwork, (void*)b->d_xchal})
         if (p) (void)hipFree(p);
-    for (void* p : {(void*)b->h_chal, (void*)b->h_mail, (void*)b->h_goff, (void*)b->h_gout, (void*)b->h_last, (void*)b->h_stage, (void*)b->h_final, (void*)b->h_cap})
+    for (void* p : {(void*)b->h_chal, (void*)b->h_mail, (void*)b->h_goff, (void*)b->h_gout, (void*)b->h_last, (void*)b->h_stage, (void*)b->h_final, (void*)b->h_cap, (void*)b->h_xchal})
         if (p) (void)hipHostFree(p);
     grinder_destroy(b->grinder);                         // on b->stream: before the stream goes
     if (b->stream) (void)hipStreamDestroy(b->stream);
@@ -597,6 +668,7 @@ int zk_batch_create(int device, uint32_t log_n, uint32_t log_b, uint32_t log_bat
     size_t off = 0;
     for (uint32_t l = 0; l <= b->R + 1; ++l) { b->layer_off.push_back(off); off += blayer_size(b, l) * b->batch; }
     const size_t layer_words = off;
+    b->layer_words = layer_words;
     off = 0;
     for (uint32_t l = 0; l <= b->R + 1; ++l) { b->tree_off.push_back(off); off += (2 * blayer_size(b, l) * b->batch - 1) * 8; }
     const size_t tree_words = off;
@@ -771,6 +843,25 @@ int zk_batch_set_merkle_cap(zk_batch* b, uint32_t cap_log) {
     return bset_format(b, next, "zk_batch_set_merkle_cap");
 }
 uint32_t zk_batch_get_merkle_cap(const zk_batch* b) { return b ? b->fmt.cap : 0; }
+// Challenges in E (include/zkstark_amd.h): from the next zk_batch_prove on.  An ext proof opens two words per value of cp and
+// of the FRI layers, its layers >= 1 are two planes each and its final polynomial has two rows, so everything is sized here, both ways:
+// with ext off every allocation is what it was.
+int zk_batch_set_ext(zk_batch* b, uint32_t ext_log) {
+    if (!b) return fail(ZK_ERR_INVALID, "null batch");
+    if (ext_log > 1) return fail(ZK_ERR_INVALID, "zk_batch_set_ext: ext_log must be 0 or 1 (got %u; 2, the quartic extension, is reserved)", ext_log);
+    ZK_BATCH_EXCLUSIVE(b, "zk_batch_set_ext");
+    if (b->single) {
+        if (int rc = zk_ctx_set_ext(b->single, ext_log)) return rc;
+        b->fmt.ext = ext_log;
+        b->device_bytes = zk_ctx_device_bytes(b->single);
+        return ZK_OK;
+    }
+    if (ext_log == b->fmt.ext) return ZK_OK;
+    ProofFormat next = b->fmt;
+    next.ext = ext_log;
+    return bset_format(b, next, "zk_batch_set_ext");
+}
+uint32_t zk_batch_get_ext(const zk_batch* b) { return b ? b->fmt.ext : 0; }
 // Row leaves (include/zkstark_amd.h): from the next zk_batch_prove_shared on; zk_batch_prove does not look at it.  A query of such a proof
 // opens as many values and fewer digests than one of a shared proof without, so the gather buffers stay as they are.
 int zk_batch_set_shared_rows(zk_batch* b, int on) {
@@ -923,11 +1014,15 @@ int zk_batch_prove(zk_batch* b, uint8_t* proofs_out, size_t stride, uint8_t* sta
     const double tc = btiming() ? now_us() : 0;
     b->pool->run(nb, 16, [&](size_t p) {
         commit_cap(r.ch[p], roots + ((p << ce) * 8), ce);
-        balphas(b, p, r.ch[p], g2);
+        if (f.ext) balphas_ext(b, p, r.ch[p], g2); else balphas(b, p, r.ch[p], g2);
     });
     cap_lap(r, ce, tc);
     if ((rc = bchal_upload(b, nb))) return rc;
-    if (f.coset) {
+    if (f.ext) {                                                          // both planes of cp from one pass over f, then the tree over them
+        ca.a.cp = bext_layer(b, 1);
+        HIPCHK(launch_compose_ext_batch(ca, b->d_xchal, (uint32_t)nb, b->stream, nullptr));
+        if ((rc = btree(b, 1, L, f.slots_log(0), lb, true))) return rc;
+    } else if (f.coset) {
         HIPCHK(launch_compose_batch(ca, lb, b->stream, nullptr));
         if ((rc = btree(b, 1, L, f.steps(0), lb))) return rc;
     } else {
@@ -954,6 +1049,7 @@ int zk_batch_prove_shared(zk_batch* b, uint8_t* proof_out, size_t cap, size_t* p
     if (!b->have_traces) return fail(ZK_ERR_STATE, "zk_batch_prove_shared: no traces");
     BusyScope busy(b);
     if (!busy.mine) return fail(ZK_ERR_STATE, "zk_batch_prove_shared: another call (zk_batch_prove or a setter) is running on this batch");
+    if (b->fmt.ext) return fail(ZK_ERR_STATE, "zk_batch_prove_shared: the batch has ext_log = 1 and a shared proof has no extension format (zk_batch_set_ext(b, 0) first)");
     ProofFormat f = b->fmt;
     f.lb = b->lb;
     f.rows = b->shared_rows;

@@ -341,6 +341,20 @@ int dom_fold_multi_ext(const zk_dom* d, const uint32_t* d_in, uint32_t* d_out, u
     return ZK_OK;
 }
 
+// The same for a proof-major batch of layers of E (FoldMultiExtBatchArgs): the root-of-unity part of every constant here, the
+// challenges and their powers in E on the device.
+int dom_fold_multi_ext_batch(const zk_dom* d, const uint32_t* d_in, uint32_t* d_out, uint32_t log_m, uint32_t round, uint32_t steps,
+                             const uint32_t* d_beta0_raw, uint32_t stride0, const uint32_t* d_beta1_raw, uint32_t stride1, uint32_t* d_work,
+                             uint32_t batch, hipStream_t s, Profiler* prof) {
+    FoldMultiExtBatchArgs a{};
+    if (int rc = fold_multi_args(d, d_in, d_out, log_m, round, steps, 1u, a.a)) return rc;
+    if (batch < 1 || ((uint64_t)batch << log_m) > ((uint64_t)1 << 32))
+        return fail(ZK_ERR_INVALID, "fold: a batch of %u layers of 2^%u values does not fit 2^32 values", batch, log_m);
+    a.beta0_raw = d_beta0_raw; a.stride0 = stride0; a.beta1_raw = d_beta1_raw; a.stride1 = stride1; a.cb = d_work; a.batch = batch;
+    HIPCHK(launch_fri_fold_multi_ext_batch(a, s, prof));
+    return ZK_OK;
+}
+
 // FRI layer `round` (2^log_m <= 4096 values at (shift h^i)^(2^round)) -> d_out[0] = non-zero coefficients of degree >= bound,
 // d_out[1 + k] = coefficient k of its interpolant in X, k < 2^log_m (FinalPolyArgs); `polys` layers / outputs in_stride / out_stride apart
 int dom_final_poly(const zk_dom* d, const uint32_t* d_in, uint32_t* d_out, uint32_t log_m, uint32_t round, uint32_t bound, hipStream_t s,

@@ -204,6 +204,12 @@ int fold_multi_batch_args(const zk_dom* d, const uint32_t* d_in, uint32_t* d_out
 int dom_fold_multi_batch(const zk_dom* d, const uint32_t* d_in, uint32_t* d_out, uint32_t log_m, uint32_t round, uint32_t steps,
                          const uint32_t* d_beta_raw, uint32_t beta_stride, uint32_t* d_work, uint32_t batch, hipStream_t s,
                          Profiler* prof = nullptr);
+// dom_fold_multi_ext over a proof-major batch of layers of E (two planes [batch][2^log_m] -> two planes [batch][2^(log_m - steps)]),
+// proof b with the raw challenge (d_beta0_raw[b * stride0], d_beta1_raw[b * stride1]); d_work: kFoldExtRow * batch words of device
+// scratch, 16-byte aligned.  Two launches, nothing else.
+int dom_fold_multi_ext_batch(const zk_dom* d, const uint32_t* d_in, uint32_t* d_out, uint32_t log_m, uint32_t round, uint32_t steps,
+                             const uint32_t* d_beta0_raw, uint32_t stride0, const uint32_t* d_beta1_raw, uint32_t stride1, uint32_t* d_work,
+                             uint32_t batch, hipStream_t s, Profiler* prof = nullptr);
 
 // Waits until *flag (host-mapped memory written by a commit launch on `stream`) equals `want`.  poll (optional) is
 // called every few thousand spins; a non-zero return ends the wait with that code (the sharded prover looks for a

@@ -538,6 +538,99 @@ hipError_t launch_compose_batch(const ComposeBatchArgs& a, uint32_t log_batch, h
     return hipGetLastError();
 }
 
+// ---- cp over E of a proof-major batch (launch_compose_ext_batch) ---------------------------------------------------
+// compose_ext_eval with proof b's constants from the two per-proof tables.  a.zz carries no alpha (R^2 / (x^n - 1), as for every batch
+// composition), so the component-free product goes one step further, y = (num * v3) * zz, and each plane takes its three products by
+// its own alphas: 15 Montgomery multiplications per value, one more than compose_ext_eval, which has alpha2 folded into its two zz
+// tables on the host.  Plane j is compose_eval<true> with component j of the alphas, residue for residue.
+struct ComposeExtConsts { uint32_t first, last, a0[2], a1g2[2], a2[2]; };
+__device__ __forceinline__ ComposeExtConsts compose_ext_batch_consts(const BatchChal* __restrict__ chal, const BatchChalExt* __restrict__ xchal, size_t b) {
+    const BatchChal c = chal[b];
+    const BatchChalExt x = xchal[b];
+    return ComposeExtConsts{c.first, c.last, {c.alpha0_mont, x.alpha0_mont1}, {c.alpha1g2_mont, x.alpha1g2_mont1}, {c.alpha2_mont, x.alpha2_mont1}};
+}
+__device__ __forceinline__ Ext compose_ext_batch_eval(const ComposeArgs& a, const ComposeExtConsts& k, uint32_t f0, uint32_t f1, uint32_t f2, uint32_t inv0,
+                                                      uint32_t inv2, uint32_t x, uint32_t zz) {
+    const uint32_t q0 = mont_mul(sub(f0, k.first), inv0);
+    const uint32_t q1 = mont_mul(sub(f0, k.last), inv2);
+    const uint32_t v3 = mont_mul(mont_mul(sub(x, a.gm3_mont), sub(x, a.gm2_mont)), sub(x, a.gm1_mont));   // V*R
+    const uint32_t num = sub(sub(mont_mul(f2, 1u), mont_mul(f1, f1)), mont_mul(f0, f0));
+    const uint32_t y = mont_mul(mont_mul(num, v3), zz);
+    Ext r;
+    r.c0 = add(add(mont_mul(q0, k.a0[0]), mont_mul(q1, k.a1g2[0])), mont_mul(y, k.a2[0]));
+    r.c1 = add(add(mont_mul(q0, k.a0[1]), mont_mul(q1, k.a1g2[1])), mont_mul(y, k.a2[1]));
+    return r;
+}
+// one value per lane: N < 16, or buffers that are not 16-byte aligned.  A workgroup spans several proofs when N < 256: b is per lane.
+__global__ __launch_bounds__(256) void compose_ext_batch_kernel(ComposeArgs a, const BatchChal* __restrict__ chal, const BatchChalExt* __restrict__ xchal,
+                                                                size_t total) {
+    const size_t pos = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (pos >= total) return;
+    const size_t b = pos >> a.logN, i = pos & (((size_t)1 << a.logN) - 1);
+    const ComposeExtConsts k = compose_ext_batch_consts(chal, xchal, b);
+    const ComposeRaw r = compose_fetch(a, a.f + (b << a.logN), i);
+    const uint32_t x = mont_mul(mont_mul(r.x_hi, r.x_lo), a.w_mont);
+    const Ext v = compose_ext_batch_eval(a, k, r.f0, r.f1, r.f2, r.inv0, r.inv2, x, r.zz);
+    a.cp[pos] = v.c0;
+    a.cp[total + pos] = v.c1;
+}
+// compose_ext_kernel4 over the batch: four consecutive values of ONE proof per lane (N >= 16, so a group of four never straddles two
+// proofs and the taps wrap inside the proof's own f), 16-byte loads, one 16-byte store per plane.
+__global__ __launch_bounds__(256) void compose_ext_batch_kernel4(ComposeArgs a, const BatchChal* __restrict__ chal, const BatchChalExt* __restrict__ xchal,
+                                                                 size_t total) {
+    const size_t N = (size_t)1 << a.logN;
+    const uint32_t B = 1u << a.log_b;
+    const size_t pos = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+    if (pos >= total) return;
+    const size_t b = pos >> a.logN, i = pos & (N - 1);
+    const ComposeExtConsts kc = compose_ext_batch_consts(chal, xchal, b);
+    const uint4* fv = reinterpret_cast<const uint4*>(a.f + (b << a.logN));
+    const uint4* iv = reinterpret_cast<const uint4*>(a.inv_xm1);
+    uint32_t f0[4], f1[4], f2[4], inv0[4], inv2[4], zz[4];
+    const uint4 v0 = fv[i >> 2], w0 = iv[i >> 2];
+    f0[0] = v0.x; f0[1] = v0.y; f0[2] = v0.z; f0[3] = v0.w;
+    inv0[0] = w0.x; inv0[1] = w0.y; inv0[2] = w0.z; inv0[3] = w0.w;
+    if (B >= 4) {
+        const uint4 v1 = fv[((i + B) & (N - 1)) >> 2], v2 = fv[((i + 2 * (size_t)B) & (N - 1)) >> 2], w2 = iv[((i + 2 * (size_t)B) & (N - 1)) >> 2];
+        f1[0] = v1.x; f1[1] = v1.y; f1[2] = v1.z; f1[3] = v1.w;
+        f2[0] = v2.x; f2[1] = v2.y; f2[2] = v2.z; f2[3] = v2.w;
+        inv2[0] = w2.x; inv2[1] = w2.y; inv2[2] = w2.z; inv2[3] = w2.w;
+        const uint32_t z0 = (uint32_t)i & (B - 1);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) zz[k] = a.zz[z0 + k];
+    } else {
+        const uint4 v1 = fv[((i + 4) & (N - 1)) >> 2], w1 = iv[((i + 4) & (N - 1)) >> 2];
+        const uint32_t fw[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
+        const uint32_t iw[8] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            f1[k] = B == 1 ? fw[k + 1] : fw[k + 2];
+            f2[k] = B == 1 ? fw[k + 2] : fw[k + 4];
+            inv2[k] = B == 1 ? iw[k + 2] : iw[k + 4];
+            zz[k] = B == 1 ? a.zz[0] : a.zz[k & 1];
+        }
+    }
+    uint32_t x = mont_mul(pow_lookup(a.htab, (uint32_t)i), a.w_mont);
+    const uint32_t h = pow_lookup(a.htab, 1u);
+    Ext r[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        r[k] = compose_ext_batch_eval(a, kc, f0[k], f1[k], f2[k], inv0[k], inv2[k], x, zz[k]);
+        if (k < 3) x = mont_mul(x, h);
+    }
+    reinterpret_cast<uint4*>(a.cp)[pos >> 2] = make_uint4(r[0].c0, r[1].c0, r[2].c0, r[3].c0);
+    reinterpret_cast<uint4*>(a.cp)[(total + pos) >> 2] = make_uint4(r[0].c1, r[1].c1, r[2].c1, r[3].c1);
+}
+hipError_t launch_compose_ext_batch(const ComposeBatchArgs& a, const BatchChalExt* xchal, uint32_t batch, hipStream_t s, Profiler* prof) {
+    if (!a.chal || !xchal || batch < 1 || ((uint64_t)batch << a.a.logN) > ((uint64_t)1 << 32)) return hipErrorInvalidValue;
+    const size_t total = (size_t)batch << a.a.logN;
+    ScopedKernelTimer tm(prof, K_COMPOSE, 12.0 * (double)total, s);   // read f once, write two planes
+    const bool aligned = ((reinterpret_cast<uintptr_t>(a.a.f) | reinterpret_cast<uintptr_t>(a.a.inv_xm1) | reinterpret_cast<uintptr_t>(a.a.cp)) & 15u) == 0;
+    if (a.a.logN >= 4 && aligned) hipLaunchKernelGGL(compose_ext_batch_kernel4, dim3((uint32_t)((total / 4 + 255) / 256)), dim3(256), 0, s, a.a, a.chal, xchal, total);
+    else hipLaunchKernelGGL(compose_ext_batch_kernel, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, s, a.a, a.chal, xchal, total);
+    return hipGetLastError();
+}
+
 // CP = sum_b cp_b (mod P) of a proof-major batch, for the shared proof (transcript.hpp "lb"): a.cp[i], i < N, from a.f = [batch][N].
 // The denominators of the three constraints, x and the vanishing product depend on i alone, so they are taken once per i and the sum
 // runs over the numerators:
@@ -952,6 +1045,143 @@ hipError_t launch_fri_fold_multi_batch(const FoldMultiBatchArgs& p, hipStream_t 
     if (a.steps == 1) fold_multi_batch_launch<1>(p, total, wide, s);
     else if (a.steps == 2) fold_multi_batch_launch<2>(p, total, wide, s);
     else fold_multi_batch_launch<3>(p, total, wide, s);
+    return hipGetLastError();
+}
+
+// ---- the butterfly over E for a proof-major batch (FoldMultiExtBatchArgs) ---------------------------------------------
+// One lane per proof reduces the raw (c0, c1) of its challenge, squares it in E between the steps and writes its row of cb: ExtConst j
+// at words 3 j .. 3 j + 2 = beta^(2^k) * a.c_mont[j] (c0, c1, 5 c1; Montgomery), j = S - (S >> k) + t the slots the butterfly reads,
+// the rest of the kFoldExtRow words 0.  The arithmetic stays in Montgomery form; the residues are fold_multi_ext_args' (domain.hip).
+constexpr uint32_t FIVE_MONT = (uint32_t)(((uint64_t)EXT_NONRESIDUE * R1) % P);
+template <int STEPS>
+__global__ __launch_bounds__(256) void fri_fold_multi_ext_batch_prep_kernel(FoldMultiExtBatchArgs p) {
+    constexpr int S = 1 << STEPS;
+    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= p.batch) return;
+    uint32_t b0 = mont_mul(p.beta0_raw[(size_t)b * p.stride0], R2_MONT);   // any u32 -> the residue mod P, Montgomery form (field.rs:20-24)
+    uint32_t b1 = mont_mul(p.beta1_raw[(size_t)b * p.stride1], R2_MONT);
+    uint32_t row[kFoldExtRow];
+#pragma unroll
+    for (uint32_t j = 0; j < kFoldExtRow; ++j) row[j] = 0u;
+#pragma unroll
+    for (int k = 0; k < STEPS; ++k) {
+#pragma unroll
+        for (int t = 0; t < (S >> (k + 1)); ++t) {
+            const int j = S - (S >> k) + t;
+            const uint32_t c1 = mont_mul(b1, p.a.c_mont[j]);
+            row[3 * j] = mont_mul(b0, p.a.c_mont[j]); row[3 * j + 1] = c1; row[3 * j + 2] = mont_mul(c1, FIVE_MONT);
+        }
+        if (k + 1 < STEPS) {                                               // (b0 + b1 u)^2 = b0^2 + 5 b1^2 + 2 b0 b1 u
+            const uint32_t cross = mont_mul(b0, b1);
+            b0 = add(mont_mul(b0, b0), mont_mul(mont_mul(b1, b1), FIVE_MONT));
+            b1 = add(cross, cross);
+        }
+    }
+    uint4* out = reinterpret_cast<uint4*>(p.cb + (size_t)b * kFoldExtRow);
+#pragma unroll
+    for (uint32_t j = 0; j < kFoldExtRow / 4; ++j) out[j] = make_uint4(row[4 * j], row[4 * j + 1], row[4 * j + 2], row[4 * j + 3]);
+}
+// Proof b's constants.  UNIFORM: every lane of the wave works on proof b (the caller made b wave-uniform), and the row was written by
+// the launch before this one, so it is read through the constant address space -- scalar loads into SGPRs, no vector registers.
+template <int STEPS, bool UNIFORM>
+__device__ __forceinline__ void fold_multi_ext_batch_consts(const uint32_t* cb, size_t b, ExtConst (&c)[7]) {
+    constexpr int S = 1 << STEPS;
+    if constexpr (UNIFORM) {
+        const __attribute__((address_space(4))) uint32_t* row = (const __attribute__((address_space(4))) uint32_t*)(cb + b * kFoldExtRow);
+#pragma unroll
+        for (int j = 0; j < 7; ++j) c[j] = j < S - 1 ? ExtConst{row[3 * j], row[3 * j + 1], row[3 * j + 2]} : ExtConst{0u, 0u, 0u};
+    } else {
+        const uint32_t* row = cb + b * kFoldExtRow;
+#pragma unroll
+        for (int j = 0; j < 7; ++j) c[j] = j < S - 1 ? ExtConst{row[3 * j], row[3 * j + 1], row[3 * j + 2]} : ExtConst{0u, 0u, 0u};
+    }
+}
+template <int STEPS, bool UNIFORM>
+__device__ __forceinline__ void fold_multi_ext_batch_one(const FoldMultiExtBatchArgs& p, size_t pos, size_t b, size_t total_in, size_t total_out) {
+    constexpr int S = 1 << STEPS;
+    const uint32_t log_q = p.a.log_m - STEPS;
+    const size_t q = (size_t)1 << log_q, i = pos & (q - 1);
+    const uint32_t* in = p.a.in + (b << p.a.log_m);
+    Ext v[S];
+#pragma unroll
+    for (int t = 0; t < S; ++t) v[t] = Ext{in[i + t * q], in[total_in + i + t * q]};
+    ExtConst c[7];
+    fold_multi_ext_batch_consts<STEPS, UNIFORM>(p.cb, b, c);
+    const Ext r = fold_multi_ext_core<STEPS>(c, p.a.scale_mont, v, pow_lookup(p.a.hinv, (uint32_t)(i << p.a.round)));
+    p.a.out[pos] = r.c0;
+    p.a.out[total_out + pos] = r.c1;
+}
+// one output per lane: per-proof outputs of fewer than 4 values, or planes that are not 16-byte aligned.  A wave's 64 positions lie in
+// one proof when q >= 64 (a uniform test on a kernel argument).
+template <int STEPS>
+__global__ __launch_bounds__(256) void fri_fold_multi_ext_batch_kernel1(FoldMultiExtBatchArgs p) {
+    const uint32_t log_q = p.a.log_m - STEPS;
+    const size_t total_out = (size_t)p.batch << log_q, total_in = (size_t)p.batch << p.a.log_m;
+    const size_t pos = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (pos >= total_out) return;
+    const uint32_t b = (uint32_t)(pos >> log_q);
+    if (log_q >= 6) fold_multi_ext_batch_one<STEPS, true>(p, pos, __builtin_amdgcn_readfirstlane(b), total_in, total_out);
+    else fold_multi_ext_batch_one<STEPS, false>(p, pos, b, total_in, total_out);
+}
+template <int STEPS, bool UNIFORM>
+__device__ __forceinline__ void fold_multi_ext_batch_four(const FoldMultiExtBatchArgs& p, size_t pos, size_t b, size_t total_in, size_t total_out) {
+    constexpr int S = 1 << STEPS;
+    const uint32_t log_q = p.a.log_m - STEPS;
+    const size_t q = (size_t)1 << log_q, i = pos & (q - 1);
+    const uint4* in = reinterpret_cast<const uint4*>(p.a.in + (b << p.a.log_m));
+    uint4 l0[S], l1[S];
+#pragma unroll
+    for (int t = 0; t < S; ++t) {
+        l0[t] = in[(i + t * q) >> 2];
+        l1[t] = in[(total_in + i + t * q) >> 2];
+    }
+    ExtConst c[7];
+    fold_multi_ext_batch_consts<STEPS, UNIFORM>(p.cb, b, c);
+    uint32_t xinv = pow_lookup(p.a.hinv, (uint32_t)(i << p.a.round));
+    const uint32_t step = pow_lookup(p.a.hinv, 1u << p.a.round);
+    Ext r[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        Ext v[S];
+#pragma unroll
+        for (int t = 0; t < S; ++t)
+            v[t] = e == 0 ? Ext{l0[t].x, l1[t].x} : e == 1 ? Ext{l0[t].y, l1[t].y} : e == 2 ? Ext{l0[t].z, l1[t].z} : Ext{l0[t].w, l1[t].w};
+        r[e] = fold_multi_ext_core<STEPS>(c, p.a.scale_mont, v, xinv);
+        if (e < 3) xinv = mont_mul(xinv, step);
+    }
+    reinterpret_cast<uint4*>(p.a.out)[pos >> 2] = make_uint4(r[0].c0, r[1].c0, r[2].c0, r[3].c0);
+    reinterpret_cast<uint4*>(p.a.out)[(total_out + pos) >> 2] = make_uint4(r[0].c1, r[1].c1, r[2].c1, r[3].c1);
+}
+// four consecutive outputs of one proof per lane (q >= 4, so a group of four never straddles two proofs): S coalesced 16-byte loads
+// and one 16-byte store per plane.  A wave's 256 positions lie in one proof when q >= 256.
+template <int STEPS>
+__global__ __launch_bounds__(256) void fri_fold_multi_ext_batch_kernel(FoldMultiExtBatchArgs p) {
+    const uint32_t log_q = p.a.log_m - STEPS;
+    const size_t total_out = (size_t)p.batch << log_q, total_in = (size_t)p.batch << p.a.log_m;
+    const size_t pos = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+    if (pos >= total_out) return;
+    const uint32_t b = (uint32_t)(pos >> log_q);
+    if (log_q >= 8) fold_multi_ext_batch_four<STEPS, true>(p, pos, __builtin_amdgcn_readfirstlane(b), total_in, total_out);
+    else fold_multi_ext_batch_four<STEPS, false>(p, pos, b, total_in, total_out);
+}
+template <int STEPS>
+static void fold_multi_ext_batch_launch(const FoldMultiExtBatchArgs& p, size_t total, bool wide, hipStream_t s) {
+    hipLaunchKernelGGL(fri_fold_multi_ext_batch_prep_kernel<STEPS>, dim3((p.batch + 255) / 256), dim3(256), 0, s, p);
+    if (wide) hipLaunchKernelGGL(fri_fold_multi_ext_batch_kernel<STEPS>, dim3((uint32_t)((total / 4 + 255) / 256)), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL(fri_fold_multi_ext_batch_kernel1<STEPS>, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, s, p);
+}
+hipError_t launch_fri_fold_multi_ext_batch(const FoldMultiExtBatchArgs& p, hipStream_t s, Profiler* prof) {
+    const FoldMultiArgs& a = p.a;
+    if (a.steps < 1 || a.steps > 3 || a.log_m < a.steps || a.log_m > 32 || p.batch < 1 || !p.beta0_raw || !p.beta1_raw || !p.cb) return hipErrorInvalidValue;
+    if ((reinterpret_cast<uintptr_t>(p.cb) & 15u) != 0) return hipErrorInvalidValue;   // the rows are written 16 bytes at a time
+    const size_t m = (size_t)1 << a.log_m, q = m >> a.steps, total = (size_t)p.batch * q;
+    if ((size_t)p.batch * m > ((size_t)1 << 32)) return hipErrorInvalidValue;
+    ScopedKernelTimer tm(prof, K_FOLD, 8.0 * (double)p.batch * (double)(m + q), s);   // read two planes of batch * m words, write two of batch * m / S
+    // both planes of the input and of the output are 16-byte aligned when the first is and a plane is a multiple of four words
+    const bool wide = q >= 4 && (total & 3) == 0 && ((reinterpret_cast<uintptr_t>(a.in) | reinterpret_cast<uintptr_t>(a.out)) & 15u) == 0;
+    if (a.steps == 1) fold_multi_ext_batch_launch<1>(p, total, wide, s);
+    else if (a.steps == 2) fold_multi_ext_batch_launch<2>(p, total, wide, s);
+    else fold_multi_ext_batch_launch<3>(p, total, wide, s);
     return hipGetLastError();
 }
 
@@ -2277,6 +2507,109 @@ hipError_t launch_merkle_build_rows(const uint32_t* vals, uint32_t log_len, uint
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     return merkle_build_t(PlainSrc{nullptr}, 0.0, log_len, nodes, s, prof, mail, hash, log_len, 0, false);
+}
+// ---- coset leaves over a batch of layers of E (launch_merkle_build_coset_ext_batch) --------------------------------
+// vals: two planes [batch][2^log_len].  Global leaf g = (p, c) as in coset_leaf_hash_batch_kernel; it holds the M = 2 S words
+// vals[plane * batch * len + (p << log_len) + c + u m], u < S, plane 0's first: the row leaf of M values that row_leaf_hash_kernel<HASH, STEPS + 1>
+// hashes over the [M][m] array one proof's two planes are, so the digest is the one-call prover's.  M <= 8: one compression
+// (coset_leaf_digest).  M = 16 (STEPS = 3): SHA-256 takes the 16 words as one message block and then the constant padding block, whose
+// schedule folds at compile time; the field hash its chain of two compressions of 8 values, in a loop that is not unrolled so that the
+// kernel holds one inlined permutation.  The walk, the prefetch of the lane's next leaf and the equal trip counts are the base kernel's.
+template <int HASH, int M>
+__device__ __forceinline__ Digest ext_leaf_digest(const uint32_t (&v)[M]) {
+    if constexpr (M <= 8) {
+        return coset_leaf_digest<HASH, M>(v);
+    } else {
+        static_assert(M == 16, "a leaf of E holds at most 2 * 8 words");
+        Digest d;
+        if constexpr (HASH == ZK_HASH_FIELD) {
+#pragma unroll
+            for (int i = 0; i < 8; ++i) d.w[i] = 0u;
+#pragma unroll 1
+            for (int k = 0; k < 2; ++k) {
+                uint32_t in[kFhT];
+#pragma unroll
+                for (int i = 0; i < 8; ++i) {
+                    in[i] = k == 0 ? v[i] : d.w[i];
+                    in[8 + i] = k == 0 ? (i == 7 ? (uint32_t)M : 0u) : v[8 + i];
+                }
+                fh64_compress(in, d.w, g_fh_consts64);
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < 8; ++i) d.w[i] = SHA_IV[i];
+            uint32_t w[16];
+#pragma unroll
+            for (int i = 0; i < 16; ++i) w[i] = v[i];
+            sha256_compress(d.w, w);
+            uint32_t pad[16] = {0x80000000u, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 32u * M};
+            sha256_compress(d.w, pad);
+        }
+        return d;
+    }
+}
+template <int HASH, int STEPS>
+__global__ __launch_bounds__(kCosetThreads) void coset_ext_leaf_hash_batch_kernel(const uint32_t* __restrict__ vals, uint32_t log_len, uint32_t log_batch,
+                                                                                  uint32_t* __restrict__ nodes) {
+    constexpr int S = 1 << STEPS, M = 2 * S;
+    const uint32_t log_m = log_len - STEPS;
+    const size_t m = (size_t)1 << log_m;                         // leaves per proof, also the distance between two slots of a leaf
+    const size_t total = m << log_batch;
+    const size_t plane = (size_t)1 << (log_len + log_batch);     // words of one plane
+    const size_t stride = (size_t)gridDim.x * kCosetThreads;     // a power of two <= total, or every leaf has a lane of its own
+    size_t g = (size_t)blockIdx.x * kCosetThreads + threadIdx.x;
+    if (g >= total) return;
+    uint32_t v[M], nx[M] = {};
+    {
+        const uint32_t* src = vals + ((g >> log_m) << log_len) + (g & (m - 1));
+#pragma unroll
+        for (int u = 0; u < S; ++u) { v[u] = src[(size_t)u * m]; v[S + u] = src[plane + (size_t)u * m]; }
+    }
+    bool more;
+#pragma unroll 1
+    do {
+        const size_t gn = g + stride;
+        more = gn < total;
+        if (more) {
+            const uint32_t* src = vals + ((gn >> log_m) << log_len) + (gn & (m - 1));
+#pragma unroll
+            for (int u = 0; u < S; ++u) { nx[u] = src[(size_t)u * m]; nx[S + u] = src[plane + (size_t)u * m]; }
+        }
+        store_digest(nodes, total - 1 + g, ext_leaf_digest<HASH, M>(v));
+#pragma unroll
+        for (int u = 0; u < M; ++u) v[u] = nx[u];
+        g = gn;
+    } while (more);
+}
+template <int HASH>
+static void coset_ext_leaf_batch_launch(const uint32_t* vals, uint32_t log_len, uint32_t steps, uint32_t log_batch, uint32_t* nodes, uint32_t blocks,
+                                        hipStream_t s) {
+    const dim3 g(blocks), b(kCosetThreads);
+    if (steps == 1) hipLaunchKernelGGL((coset_ext_leaf_hash_batch_kernel<HASH, 1>), g, b, 0, s, vals, log_len, log_batch, nodes);
+    else if (steps == 2) hipLaunchKernelGGL((coset_ext_leaf_hash_batch_kernel<HASH, 2>), g, b, 0, s, vals, log_len, log_batch, nodes);
+    else hipLaunchKernelGGL((coset_ext_leaf_hash_batch_kernel<HASH, 3>), g, b, 0, s, vals, log_len, log_batch, nodes);
+}
+hipError_t launch_merkle_build_coset_ext_batch(const uint32_t* vals, uint32_t log_len, uint32_t steps, uint32_t log_batch, uint32_t* nodes, hipStream_t s,
+                                               Profiler* prof, const MailArgs& mail, int hash) {
+    if (steps < 1 || steps > 3 || log_len <= steps || log_len + log_batch > 31) return hipErrorInvalidValue;
+    if (hash != ZK_HASH_SHA256 && hash != ZK_HASH_FIELD) return hipErrorInvalidValue;   // a leaf of E is a row leaf: no BLAKE2s (transcript.hpp "ext")
+    if (hash == ZK_HASH_FIELD) {
+        hipError_t e = ensure_fieldhash_consts();
+        if (e != hipSuccess) return e;
+    }
+    const uint32_t log_m = log_len - steps + log_batch;          // leaves of the batch heap
+    const size_t leaves = (size_t)1 << log_m;
+    const size_t lanes = leaves > 4 * (size_t)kCosetThreads ? leaves / 4 : leaves;   // up to four leaves per lane, as the base launch
+    const uint32_t blocks = (uint32_t)((lanes + kCosetThreads - 1) / kCosetThreads);
+    {
+        ScopedKernelTimer tm(prof, K_MERKLE_LEAF, 8.0 * (double)((size_t)1 << (log_len + log_batch)) + 32.0 * (double)leaves, s,
+                             (double)leaves * row_leaf_compressions(steps + 1, hash) * hash_leaf_ops(hash));
+        if (hash == ZK_HASH_FIELD) coset_ext_leaf_batch_launch<1>(vals, log_len, steps, log_batch, nodes, blocks, s);
+        else coset_ext_leaf_batch_launch<0>(vals, log_len, steps, log_batch, nodes, blocks, s);
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    return merkle_build_t(PlainSrc{nullptr}, 0.0, log_m, nodes, s, prof, mail, hash, log_m, 0, false);   // mail.top: the per-proof roots or below
 }
 // commitment of a block whose leaves are still in all-to-all order (no interleave pass, no block buffer)
 hipError_t launch_merkle_build_interleaved(const uint32_t* recv, uint32_t log_parts, uint32_t log_cnt, uint32_t* nodes, hipStream_t s,

@@ -379,6 +379,38 @@ hipError_t launch_merkle_build_coset_batch(const uint32_t* vals, uint32_t log_le
 hipError_t launch_merkle_build_rows(const uint32_t* vals, uint32_t log_len, uint32_t log_batch, uint32_t* nodes, hipStream_t s, Profiler* prof,
                                     const MailArgs& mail, int hash);
 
+// ---- the batch with challenges in E (zk_batch_set_ext) ----------------------------------------------------------
+// Layer id >= 1 of an ext batch is two planes, component 0 first, each the proof-major [batch][m] layer of the base batch: the second
+// plane lies batch * m words behind the first.  f (layer 0) stays [batch][N] in the base field.
+struct BatchChalExt {           // per proof, beside its BatchChal row: the component-1 halves of its challenges
+    uint32_t alpha0_mont1, alpha1g2_mont1, alpha2_mont1;   // alpha0.c1, alpha1.c1 * g^2, alpha2.c1 (Montgomery)
+    uint32_t beta1;             // this group's beta.c1, raw (beta.c0 raw is BatchChal::c_mont)
+};
+// cp over E of the whole batch in one pass over f: a.a.cp = two planes of batch * N words, value (b, i) of plane j = cp_b[i] with
+// component j of proof b's alphas (a.chal: component 0, first, last; xchal: component 1), launch_compose_ext's arithmetic with
+// a.a.zz free of alpha2 as in every batch composition.  Any batch >= 1 with batch * N <= 2^32.
+hipError_t launch_compose_ext_batch(const ComposeBatchArgs& a, const BatchChalExt* xchal, uint32_t batch, hipStream_t s, Profiler* prof = nullptr);
+// launch_fri_fold_multi_ext over a batch: a.in = two planes [batch][m], a.out = two planes [batch][m / S]; proof b folds with
+// beta_b = (beta0_raw[b * stride0], beta1_raw[b * stride1]) (raw u32, reduced mod P on the device).  a.c_mont holds the root-of-unity
+// part of each constant; a one-lane-per-proof launch ahead of the fold writes proof b's seven ExtConst (beta_b^(2^k) in E times
+// a.c_mont[j]: 21 words, the row padded to kFoldExtRow) to cb, which the fold reads in place of kernel arguments.  cb: kFoldExtRow * batch
+// words of scratch.  batch * m <= 2^32; any batch >= 1.
+constexpr uint32_t kFoldExtRow = 24;
+struct FoldMultiExtBatchArgs {
+    FoldMultiArgs a;
+    const uint32_t *beta0_raw, *beta1_raw;
+    uint32_t stride0, stride1;   // in words
+    uint32_t* cb;
+    uint32_t batch;
+};
+hipError_t launch_fri_fold_multi_ext_batch(const FoldMultiExtBatchArgs& a, hipStream_t s, Profiler* prof = nullptr);
+// launch_merkle_build_coset_batch over such a layer (vals: two planes [batch][2^log_len], steps 1..3 < log_len): leaf c of proof p
+// hashes the 2 * 2^steps words vals[plane * batch * len + (p << log_len) + c + u m], component 0's slots u < 2^steps first, then
+// component 1's -- the row leaf of 2^(steps + 1) values the one-call prover's tree over a layer of E has.  Heap, mail and hashes as
+// launch_merkle_build_coset_batch.
+hipError_t launch_merkle_build_coset_ext_batch(const uint32_t* vals, uint32_t log_len, uint32_t steps, uint32_t log_batch, uint32_t* nodes,
+                                               hipStream_t s, Profiler* prof, const MailArgs& mail, int hash);
+
 // batch traces of prover.rs:32-39, one lane per trace: out[t*stride + i], i < count (stride 0 = count)
 hipError_t launch_trace_fibsq_batch(const uint32_t* a0, const uint32_t* a1, uint32_t batch, uint32_t count, uint32_t* out, hipStream_t s,
                                     uint32_t stride = 0);

@@ -2036,6 +2036,57 @@ int zk_dev_fri_fold_multi_batch(const zk_dom* d, const uint32_t* d_in, uint32_t*
     HIPCHK(hipSetDevice(d->device));
     return dom_fold_multi_batch(d, d_in, d_out, log_m, round, steps, d_beta_raw, 1, d_work, batch, (hipStream_t)stream, dev_prof());
 }
+// The kernels of the batch over E (zk_batch_set_ext), one at a time.
+int zk_dev_compose_ext_batch(const zk_dom* d, const uint32_t* d_f, uint32_t* d_cp, const uint32_t* first, const uint32_t* last, const uint32_t* alpha_raw,
+                             uint32_t* d_work, uint32_t batch, void* stream) {
+    if (!d || !d_f || !d_cp || !first || !last || !alpha_raw || !d_work) return fail(ZK_ERR_INVALID, "zk_dev_compose_ext_batch: null argument");
+    if (!d->d_inv_xm1) return fail(ZK_ERR_STATE, "zk_dev_compose_ext_batch: fold-only domain");
+    if (batch < 1 || ((uint64_t)batch << d->L) > ((uint64_t)1 << 32))
+        return fail(ZK_ERR_INVALID, "zk_dev_compose_ext_batch: need batch >= 1 and batch * N <= 2^32 (got %u, N = 2^%u)", batch, d->L);
+    if (reinterpret_cast<uintptr_t>(d_work) & 15u) return fail(ZK_ERR_INVALID, "zk_dev_compose_ext_batch: d_work must be 16-byte aligned");
+    HIPCHK(hipSetDevice(d->device));
+    ComposeBatchArgs ca;
+    const uint32_t one[3] = {1, 1, 1};
+    if (int rc = compose_args(d, d_f, d_cp, 0, 0, one, ca.a)) return rc;
+    const uint32_t g2 = mulmod(d->g, d->g);
+    std::vector<BatchChal> chal(batch);                       // proof b's rows of the two tables, as the batched prover fills them
+    std::vector<BatchChalExt> xchal(batch);
+    for (uint32_t b = 0; b < batch; ++b) {
+        const uint32_t* a = alpha_raw + 6 * (size_t)b;
+        chal[b] = BatchChal{first[b] % P, last[b] % P, to_mont(a[0] % P), to_mont(mulmod(a[2] % P, g2)), to_mont(a[4] % P), 0u, {0u, 0u}};
+        xchal[b] = BatchChalExt{to_mont(a[1] % P), to_mont(mulmod(a[3] % P, g2)), to_mont(a[5] % P), 0u};
+    }
+    BatchChal* d_chal = reinterpret_cast<BatchChal*>(d_work);
+    BatchChalExt* d_xchal = reinterpret_cast<BatchChalExt*>(d_work + (size_t)batch * (sizeof(BatchChal) / 4));
+    HIPCHK(hipMemcpyAsync(d_chal, chal.data(), batch * sizeof(BatchChal), hipMemcpyHostToDevice, (hipStream_t)stream));
+    HIPCHK(hipMemcpyAsync(d_xchal, xchal.data(), batch * sizeof(BatchChalExt), hipMemcpyHostToDevice, (hipStream_t)stream));
+    HIPCHK(hipStreamSynchronize((hipStream_t)stream));        // the host tables go out of scope
+    ca.chal = d_chal;
+    HIPCHK(launch_compose_ext_batch(ca, d_xchal, batch, (hipStream_t)stream, dev_prof()));
+    return ZK_OK;
+}
+int zk_dev_fri_fold_multi_ext_batch(const zk_dom* d, const uint32_t* d_in, uint32_t* d_out, uint32_t log_m, uint32_t round, uint32_t steps,
+                                    const uint32_t* d_beta_raw, uint32_t* d_work, uint32_t batch, void* stream) {
+    if (!d || !d_in || !d_out || !d_beta_raw || !d_work) return fail(ZK_ERR_INVALID, "zk_dev_fri_fold_multi_ext_batch: null argument");
+    if (steps < 1 || steps > kMaxFoldLog) return fail(ZK_ERR_INVALID, "zk_dev_fri_fold_multi_ext_batch: steps must be 1..%u (got %u)", kMaxFoldLog, steps);
+    if (round + steps > d->log_n || log_m + round != d->L)
+        return fail(ZK_ERR_INVALID, "zk_dev_fri_fold_multi_ext_batch: layer 2^%u, rounds %u..%u do not fit a domain of %u rounds", log_m, round, round + steps, d->log_n);
+    if (batch < 1 || ((uint64_t)batch << log_m) > ((uint64_t)1 << 32))
+        return fail(ZK_ERR_INVALID, "zk_dev_fri_fold_multi_ext_batch: need batch >= 1 and batch * 2^log_m <= 2^32 (got %u, log_m %u)", batch, log_m);
+    if (reinterpret_cast<uintptr_t>(d_work) & 15u) return fail(ZK_ERR_INVALID, "zk_dev_fri_fold_multi_ext_batch: d_work must be 16-byte aligned");
+    HIPCHK(hipSetDevice(d->device));
+    return dom_fold_multi_ext_batch(d, d_in, d_out, log_m, round, steps, d_beta_raw, 2, d_beta_raw + 1, 2, d_work, batch, (hipStream_t)stream, dev_prof());
+}
+int zk_dev_merkle_build_coset_ext_batch(const uint32_t* d_vals, uint32_t log_len, uint32_t steps, uint32_t log_batch, uint32_t* d_nodes, void* stream,
+                                        int hash_kind) {
+    if (!d_vals || !d_nodes) return fail(ZK_ERR_INVALID, "zk_dev_merkle_build_coset_ext_batch: null argument");
+    if (steps < 1 || steps > kMaxFoldLog || log_len <= steps || log_len + log_batch > 30)
+        return fail(ZK_ERR_INVALID, "zk_dev_merkle_build_coset_ext_batch: need 1 <= steps <= %u, steps < log_len and log_len + log_batch <= 30", kMaxFoldLog);
+    if (hash_kind != ZK_HASH_SHA256 && hash_kind != ZK_HASH_FIELD)
+        return fail(ZK_ERR_INVALID, "zk_dev_merkle_build_coset_ext_batch: leaves of E take hash 0 or 1 (got %d)", hash_kind);
+    HIPCHK(launch_merkle_build_coset_ext_batch(d_vals, log_len, steps, log_batch, d_nodes, (hipStream_t)stream, dev_prof(), MailArgs{}, hash_kind));
+    return ZK_OK;
+}
 int zk_dev_trace_fibsq_batch(const uint32_t* d_a0, const uint32_t* d_a1, uint32_t batch, uint32_t count, uint32_t* d_out, void* stream) {
     if ((batch && (!d_a0 || !d_a1 || !d_out))) return fail(ZK_ERR_INVALID, "zk_dev_trace_fibsq_batch: null argument");
     HIPCHK(launch_trace_fibsq_batch(d_a0, d_a1, batch, count, d_out, (hipStream_t)stream));

@@ -602,8 +602,10 @@ class BatchContext:
     launch over the whole batch; each proof has its own channel and is byte-identical to Context.prove()."""
 
     def __init__(self, log_n=10, log_blowup=3, log_batch=4, device=0, hash="sha256", queries=1, grind_bits=0, fold_log=1, coset_leaves=False,
-                 stop_log=0, cap_log=0, shared_rows=False):
-        """shared_rows: prove_shared() commits the traces as row leaves, one f tree and three f paths per query (zk_batch_set_shared_rows).
+                 stop_log=0, cap_log=0, shared_rows=False, ext_log=0):
+        """ext_log: 1 draws every proof's challenges, and holds cp and the FRI layers, in the quadratic extension E (zk_batch_set_ext;
+        0 = the base field); prove() then returns Proofs with ext_log = 1, prove_shared() is refused.
+        shared_rows: prove_shared() commits the traces as row leaves, one f tree and three f paths per query (zk_batch_set_shared_rows).
         fold_log: FRI folding factor 2^fold_log between commitments for every proof of the batch (zk_batch_set_fold; 1 = the
         reference).  coset_leaves: one coset per Merkle leaf of the FRI trees (zk_batch_set_coset_leaves).  stop_log: every proof stops
         FRI at a polynomial of degree < 2^stop_log and sends its coefficients (zk_batch_set_fri_stop; 0 = fold to a constant).
@@ -615,6 +617,7 @@ class BatchContext:
         self.coset_leaves = False
         self.stop_log = 0
         self.cap_log = 0
+        self.ext_log = 0
         self.shared_rows = False
         self.n, self.batch = 1 << log_n, 1 << log_batch
         self._h = C.c_void_p()
@@ -635,6 +638,14 @@ class BatchContext:
             self.set_merkle_cap(cap_log)
         if shared_rows:
             self.set_shared_rows(True)
+        if ext_log:
+            self.set_ext(ext_log)
+
+    def set_ext(self, ext_log):
+        """zk_batch_set_ext: from the next zk_batch_prove on, challenges in E = F_P[u] / (u^2 - 5) (1) or in the base field (0).  Sizes the
+        planes of the layers, the gather buffers and the tables of E when called, both ways; ZkError for ext_log > 1 or while a prove runs."""
+        check(_lib.load().zk_batch_set_ext(self._h, ext_log))
+        self.ext_log = ext_log
 
     def set_shared_rows(self, on=True):
         """zk_batch_set_shared_rows: from the next prove_shared() on, the 2^log_batch trace polynomials are committed as ONE tree whose leaf i
@@ -725,7 +736,7 @@ class BatchContext:
         data, states = self.prove_raw()
         last = self.public_last()
         return [Proof(states[p].tobytes(), data[p].tobytes(), self.log_n, self.log_blowup, int(last[p]), self.hash, self.queries,
-                      self.grind_bits, self.fold_log, self.coset_leaves, self.stop_log, self.cap_log) for p in range(self.batch)]
+                      self.grind_bits, self.fold_log, self.coset_leaves, self.stop_log, self.cap_log, self.ext_log) for p in range(self.batch)]
 
     def prove_shared(self):
         """zk_batch_prove_shared: ONE SharedProof of the batch's resident traces with the current settings."""
